@@ -163,7 +163,9 @@ def action_batches(worlds, agents, device, seed, n=8):
 def run_steps(sim, batches, all_worlds, n, start=0, tracker=None):
     act = sim.action_tensor().to_torch()
     for k in range(start, start + n):
-        act.copy_(batches[k % len(batches)])
+        # the batch is picked by the step's place in its episode: a timed stretch starts at an episode's first step, so what
+        # it computes does not depend on how many spin-up steps ran before it (--dump-outputs compares runs)
+        act.copy_(batches[k % EPISODE % len(batches)])
         if tracker is not None:
             # "rl_loop": the step as a learner sees it: simulator step, episode
             # bookkeeping + device-driven reset of finished worlds, fused observation pack; no host sync
@@ -174,6 +176,40 @@ def run_steps(sim, batches, all_worlds, n, start=0, tracker=None):
         if (k + 1) % EPISODE == 0:
             sim.reset(all_worlds)
     return start + n
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(sim, out_dir, workload, kw, packed=None, raw_rows=True):
+    """--dump-outputs: the arrays the timed step hands its caller, as they stand after the last timed step, one
+    DIR/<name>.npy each (float tensors as float32, integer ones as float64, which holds them exactly).  When all worlds
+    together exceed DUMP_BYTES, a fixed, seeded sample of worlds is written (the same one in every run)."""
+    getters = ["reward_tensor", "done_tensor", "info_tensor", "self_observation_tensor", "absolute_self_observation_tensor",
+               "steps_remaining_tensor"]
+    if raw_rows:  # (not written by the step under gd_attach_packed(only=1): the packed observation is what the caller gets)
+        getters += ["partner_observations_tensor", "agent_roadmap_tensor"]
+    if kw.get("enableLidar"):
+        getters.append("lidar_tensor")
+    if workload == "bev":
+        getters.append("bev_observation_tensor")
+    arrays = {g[:-len("_tensor")]: getattr(sim, g)().to_torch() for g in getters}
+    if packed is not None:
+        arrays["packed_observations"] = packed
+    wide = lambda t: t.dtype == torch.float64 or not t.is_floating_point()
+    worlds = next(iter(arrays.values())).shape[0]
+    per_world = sum((8 if wide(t) else 4) * t[0].numel() for t in arrays.values())
+    n = max(1, min(worlds, DUMP_BYTES // per_world))
+    sample = np.sort(np.random.default_rng(0).choice(worlds, n, replace=False)) if n < worlds else np.arange(worlds)
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, t in arrays.items():
+        a = t.index_select(0, torch.as_tensor(sample, device=t.device)).cpu().numpy()
+        a = a.astype(np.float64 if wide(t) else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return dict(dir=out_dir, files=sorted(name + ".npy" for name in arrays), bytes=written,
+                worlds=sample.tolist() if n < worlds else "all")
 
 
 def linear_roads_scanned(sim, radius, k=200, chunk=16):
@@ -285,6 +321,10 @@ def _bench_workload(name, args, rank, local_rank, world, device):
     base = {}
     k, local_elapsed = timed_stretch(k, pre_t0=lambda: base.update(graph=sim.stat(0), plain=sim.stat(1)))
     graph_steps, plain_steps = sim.stat(0) - base["graph"], sim.stat(1) - base["plain"]
+    dumped = None
+    if args.dump_outputs and rank == 0 and name == args.workloads.split(",")[0]:
+        dumped = dump_outputs(sim, args.dump_outputs, workload, kw, packed=sim.packed_observations() if tracker is not None else None,
+                              raw_rows=not direct)
     elapsed = sharding.reduce_max(local_elapsed, device)
     elapsed_min = -sharding.reduce_max(-local_elapsed, device)
     # ---- 2. the same K steps again with HIP events around every kernel launch (kernel by kernel); a few untimed steps
@@ -306,7 +346,7 @@ def _bench_workload(name, args, rank, local_rank, world, device):
         agent_steps_per_s=total_live * args.steps / elapsed,
         padded_agent_steps_per_s=world * args.worlds * args.agents * args.steps / elapsed,
         timed_region=dict(graph_steps=graph_steps, plain_steps=plain_steps, episode_resets=args.steps // EPISODE),
-        gc_ms_in_timed_stretches=gc_ms[0], spin_up_steps=spin_steps[0],
+        gc_ms_in_timed_stretches=gc_ms[0], spin_up_steps=spin_steps[0], dump_outputs=dumped,
         worlds=args.worlds, packed_observation="written by the step (gd_attach_packed, raw partner / road rows not written)" if direct
         else ("second pass over the raw tensors (k_pack_obs)" if tracker is not None else None),
     )
@@ -625,6 +665,10 @@ def main():
     ap.add_argument("--dist-backend", default=None, choices=(None, "nccl", "gloo"),
                     help="default: nccl (RCCL); gloo + --single-device rehearses the N>1 path on one GPU")
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the primary workload, write what its last step handed the caller as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed, seeded sample of worlds when larger); "
+                         "the same arguments give the same inputs in every run, so two builds can be compared output for output")
     ap.add_argument("--knn-order", type=int, default=0, choices=(0, 1),
                     help="0 = reference heap order (default, elementwise parity); 1 = same row set, in the engine's own (grid-cell) order")
     args = ap.parse_args()
@@ -770,6 +814,7 @@ def main():
                                    "ms_per_step_events", "gc_ms_in_timed_stretches", "spin_up_steps", "overlapped_kernels", "kernels_sum_us", "live_agents_per_rank", "live_agents_with_roads_in_reach", "road_entities_per_rank",
                                    "roofline", "kernels", "other_rooflines")}
                 for r in results[1:]],
+            "dump_outputs": primary["dump_outputs"],
             "init_seconds": primary["init_seconds"],
             "live_agents_per_rank": primary["live_agents_per_rank"],
             "live_agents_with_roads_in_reach": primary["live_agents_with_roads_in_reach"],

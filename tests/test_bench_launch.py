@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,3 +100,79 @@ def test_a_signal_to_the_launcher_ends_every_rank():
             break
         time.sleep(1.0)
     assert not left, "ranks survived the launcher"
+
+
+class _FakeTensor:
+    def __init__(self, t):
+        self._t = t
+
+    def to_torch(self):
+        return self._t
+
+
+class _FakeSim:
+    """The slot getters dump_outputs reads, on host tensors of the exported shapes (W worlds x 64 agent slots)."""
+
+    def __init__(self, worlds):
+        g = torch.Generator().manual_seed(3)
+        W, A = worlds, 64
+        self.t = dict(reward=torch.rand(W, A, 1, generator=g), done=torch.randint(0, 2, (W, A, 1), generator=g, dtype=torch.int32),
+                      info=torch.randint(-3, 3, (W, A, 5), generator=g, dtype=torch.int32),
+                      self_observation=torch.rand(W, A, 8, generator=g), absolute_self_observation=torch.rand(W, A, 14, generator=g),
+                      steps_remaining=torch.randint(0, 91, (W, A, 1), generator=g, dtype=torch.int32),
+                      partner_observations=torch.rand(W, A, A - 1, 9, generator=g), agent_roadmap=torch.rand(W, A, 200, 9, generator=g))
+
+    def __getattr__(self, name):
+        if name.endswith("_tensor") and name[:-len("_tensor")] in self.__dict__.get("t", {}):
+            return lambda: _FakeTensor(self.t[name[:-len("_tensor")]])
+        raise AttributeError(name)
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_byte_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per array the step hands its caller, floats as float32 and ints as float64 (exact), the
+    same seeded sample of worlds in every run when everything would exceed the budget, and never more bytes than it."""
+    import numpy as np
+    before = set(os.environ)
+    import bench
+    for k in set(os.environ) - before:  # (bench.py's environment defaults are for its own process)
+        del os.environ[k]
+    sim = _FakeSim(40)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 << 20)
+    kw = bench.params_for("synthetic")
+    a = bench.dump_outputs(sim, str(tmp_path / "a"), "synthetic", kw)
+    b = bench.dump_outputs(sim, str(tmp_path / "b"), "synthetic", kw)
+    assert a["worlds"] == b["worlds"] and a["worlds"] != "all" and 0 < len(a["worlds"]) < 40
+    assert a["bytes"] <= 4 << 20
+    assert sorted(os.listdir(tmp_path / "a")) == a["files"] == sorted(k + ".npy" for k in sim.t)
+    idx = a["worlds"]
+    for k, t in sim.t.items():
+        arr = np.load(tmp_path / "a" / (k + ".npy"))
+        assert arr.dtype == (np.float32 if t.is_floating_point() else np.float64), k
+        assert np.array_equal(arr, t[idx].numpy().astype(arr.dtype)), k
+        assert np.array_equal(arr, np.load(tmp_path / "b" / (k + ".npy"))), k
+    # (the raw partner / road rows are left out where the step does not write them)
+    c = bench.dump_outputs(sim, str(tmp_path / "c"), "synthetic", kw, raw_rows=False)
+    assert "agent_roadmap.npy" not in c["files"] and c["worlds"] == "all"
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_do_not_depend_on_the_spin_up(tmp_path):
+    """Two runs of the same timed steps, one with no spin-up and one with 200 ms of it (a different number of untimed steps
+    before the stretch), must dump the same arrays bit for bit; `--steps` sets the number of timed steps."""
+    import numpy as np
+    lines = []
+    for spin, d in (("0", "a"), ("200", "b")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--workloads", "synthetic", "--worlds", "64", "--no-cpu-baseline", "--spin-ms", spin,
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    for line in lines:
+        assert line["steps"] == 7 and line["ms_per_step"] > 0
+        assert line["kernels"]["k_world_step"]["launches"] == 7
+    a, b = (line["dump_outputs"] for line in lines)
+    assert a["files"] == b["files"] and "agent_roadmap.npy" in a["files"] and a["bytes"] <= 64 << 20
+    for f in a["files"]:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 64
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f
