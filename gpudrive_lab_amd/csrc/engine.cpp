@@ -764,8 +764,11 @@ struct gd_sim {
             // interleaved workgroup by workgroup (4 * lin_apw entries each): workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md,
             // dispatch), so every workgroup that holds agents of a world -- and the world's road arrays -- stays on one XCD's L2.
             // Classes are filled greedily (fewest entries so far) so that ragged batches leave few filler entries.  Two lists:
-            // every live agent (reset passes), and the agents that can move (step passes: a `Static` agent's rows were written
-            // by the reset pass that follows every rebuild, and nothing moves it afterwards).
+            // every live agent (reset passes), and the agents that can move (step passes).  A `Static` agent's rows were written
+            // by the reset pass that follows every rebuild, and its own movement never moves it -- but under AgentRemoved a
+            // Static agent that is hit is moved to the padding position by the next step (reference src/sim.cpp:302-313, the
+            // collision switch comes before the Static early return), so there the step passes take every live agent too
+            // (the pose stamps still skip the ones that did not move).
             const int per = 4 * d.lin_apw;
             auto build = [&](bool dyn_only, std::vector<int32_t> &list) -> int {
                 std::vector<int32_t> seq[8];
@@ -788,7 +791,7 @@ struct gd_sim {
             };
             std::vector<int32_t> full, dyn;
             d.lin_blocks = build(false, full);
-            d.lin_blocks_dyn = build(true, dyn);
+            d.lin_blocks_dyn = build(params.collisionBehaviour != GD_COLLISION_AGENT_REMOVED, dyn);
             lin_static_agents = 0;
             for (int32_t e : full) lin_static_agents += e >= 0;
             for (int32_t e : dyn) lin_static_agents -= e >= 0;

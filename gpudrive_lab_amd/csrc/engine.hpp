@@ -115,8 +115,9 @@ struct DevSim {
     float4 *knn_prev;              // [W][A] {x, y, K-th key of the previous selection or +inf, 0}
     // linear road selection (map_obs_linear.hip): the live agents as (world << 8 | agent) or -1 (filler), 4 * lin_apw entries per
     // workgroup, ordered so that every workgroup that holds agents of a world has the same index modulo 8 (= runs on the same
-    // XCD); lin_list_dyn: the same without the agents whose response type is Static (they never move: reference
-    // src/sim.cpp:327-331), what a step pass takes; lin_dyn_off: this pass takes the full list all the same
+    // XCD); lin_list_dyn: the same without the agents whose response type is Static (their own movement never moves them:
+    // reference src/sim.cpp:327-331), what a step pass takes -- every live agent under AgentRemoved, which moves a Static agent
+    // that was hit (src/sim.cpp:302-313); lin_dyn_off: this pass takes the full list all the same
     const int32_t *lin_list, *lin_list_dyn;
     int lin_blocks, lin_blocks_dyn;
     int lin_dyn_off;

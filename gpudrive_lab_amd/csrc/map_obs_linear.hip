@@ -27,7 +27,8 @@
 //     src/level_gen.cpp:102-113, src/sim.cpp:327-331) and finished agents are most of a Waymo scene.
 //   * agents are dealt to the XCDs by world (engine.cpp lin_list: workgroup b runs on XCD b % 8, and the list puts every agent
 //     of a world at the same b % 8, in consecutive workgroups), so that a world's road arrays are fetched into one L2, not
-//     eight.  Step passes take a second list that leaves out the agents that never move (`Static`).
+//     eight.  Step passes take a second list that leaves out the `Static` agents -- unless collisions remove agents
+//     (AgentRemoved moves a Static agent that was hit to the padding position; engine.cpp, the work lists).
 //
 // With DevSim::pack set (gd_attach_packed) the wave also -- or only: pack_only -- writes the agent's 200 x 13 normalised road
 // columns of the packed observation (pack_cols.hpp), so that a learner that reads packed_observations() pays no second pass.
@@ -250,8 +251,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE)
 }  // namespace
 
 void launch_map_obs_linear(const DevSim &d0, hipStream_t st, bool move) {
-    // A step pass takes the list without the agents that never move (`Static`: their rows were written by the last reset pass,
-    // which follows every rebuild, and their stamps would only confirm it); every other pass takes every live agent.
+    // A step pass takes the list without the `Static` agents (their rows were written by the last reset pass, which follows every
+    // rebuild, and their stamps would only confirm it; under AgentRemoved, where a Static agent that is hit does move, that list
+    // holds every live agent); every other pass takes every live agent.
     DevSim d = d0;
     if (move && d.pose_skip != 0 && d.lin_dyn_off == 0) {
         d.lin_list = d.lin_list_dyn;

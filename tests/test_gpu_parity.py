@@ -229,19 +229,10 @@ def test_packed_observations_match_reference_python_golden():
     got = out[0, :n].cpu().numpy()
     # torch CPU divides, the kernel divides: bit-exact expected; allow one ulp of a [-1,1] value
     assert np.allclose(got, g["expected"], atol=1.2e-7, rtol=0), np.abs(got - g["expected"]).max()
-    # and against a torch restatement on the device for every agent slot (incl. padding rows)
-    so = gpu.self_observation_tensor().to_torch()
-    po = gpu.partner_observations_tensor().to_torch()
-    ro = gpu.agent_roadmap_tensor().to_torch()
-    nm = lambda x: 2 * ((x + 1000) / 2000) - 1
-    ego = torch.stack([so[..., 0] / 100, so[..., 1] * 0.7 / 30, so[..., 2] * 0.7 / 15, nm(so[..., 4]), nm(so[..., 5]),
-                       so[..., 6]], -1)
-    part = torch.stack([po[..., 0] / 100, nm(po[..., 1]), nm(po[..., 2]), po[..., 3] / (2 * np.pi),
-                        po[..., 4] * 0.7 / 30, po[..., 5] * 0.7 / 15], -1).flatten(2)
-    road = torch.cat([nm(ro[..., 0:1]), nm(ro[..., 1:2]), ro[..., 2:5] / 100, ro[..., 5:6] / (2 * np.pi),
-                      torch.nn.functional.one_hot(ro[..., 6].long(), 7).float()], -1).flatten(2)
-    ref = torch.cat([ego, part, road], -1)
-    assert torch.allclose(out, ref, atol=3e-7, rtol=1e-6)  # GPU torch multiplies by 1/scalar: last-bit differences
+    # and against the float64 restatement (tests/parity.py, pinned to the golden on the CPU) for every agent slot (incl.
+    # padding rows): within P.PACK_ATOL = 3e-7, P.PACK_RTOL = 1e-6
+    P.compare_packed(out.cpu().numpy(), RC.as_np(gpu.self_observation_tensor()), RC.as_np(gpu.partner_observations_tensor()),
+                     RC.as_np(gpu.agent_roadmap_tensor()))
     gpu.close()
 
 
