@@ -72,15 +72,22 @@ EPISODE_STAT_NAMES = ("episodes", "finished_agents", "return_sum", "off_road_age
                       "truncated_agents", "length_sum", "total_collisions", "total_off_road")
 
 
+EPISODE_REWARD_WEIGHTED, EPISODE_REWARD_SPARSE, EPISODE_REWARD_CONDITIONED, EPISODE_REWARD_LOG_DISTANCE = range(4)
+CONDITION_RANDOM, CONDITION_PRESET, CONDITION_FIXED = range(3)
+
+
 class GdEpisodeConfig(C.Structure):
     _fields_ = [("collision_weight", C.c_float), ("goal_achieved_weight", C.c_float), ("off_road_weight", C.c_float),
-                ("reward_type", C.c_int32), ("auto_reset", C.c_int32)]
+                ("reward_type", C.c_int32), ("auto_reset", C.c_int32),
+                ("log_distance_weight", C.c_float), ("condition_mode", C.c_int32), ("weights", C.c_float * 3),
+                ("lb", C.c_float * 3), ("ub", C.c_float * 3), ("seed", C.c_uint64)]
 
 
 class GdEpisodeBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "controlled_mask", "agent_episode_returns", "episode_lengths", "collided_in_episode", "offroad_in_episode",
-        "live_agent_mask", "reward_out", "terminal_out", "truncated_out", "mask_out", "done_worlds", "stats", "world_stats")]
+        "live_agent_mask", "reward_out", "terminal_out", "truncated_out", "mask_out", "done_worlds", "stats", "world_stats",
+        "reward_weights", "weight_draws")]
 
 
 # every symbol include/gpudrive_amd.h declares
@@ -88,6 +95,7 @@ SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_episode_step", "gd_sync",
+    "gd_pack_observations_conditioned", "gd_episode_draw_weights",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
     "gd_kernel_timing_enable", "gd_kernel_timing_read", "gd_debug_get_state", "gd_debug_set_state", "gd_debug_road_path",
     "gd_host_world_build", "gd_host_world_free", "gd_scene_cache_write",
@@ -139,6 +147,9 @@ def lib():
     L.gd_attach_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
     L.gd_attach_packed.restype = C.c_int
     L.gd_episode_step.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffers)]
+    L.gd_episode_draw_weights.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffers),
+                                          C.POINTER(C.c_int32), C.c_int32]
+    L.gd_pack_observations_conditioned.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.gd_scene_cache_write.argtypes = [C.c_char_p, C.c_float, C.c_char_p]
     L.gd_expert_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gd_advance_log_playback.argtypes = [C.c_void_p, C.c_int32]

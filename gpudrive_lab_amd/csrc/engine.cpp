@@ -1271,6 +1271,17 @@ int gd_attach_packed(gd_sim *s, float *out, int64_t out_bytes, int32_t only) {
     });
 }
 
+int gd_pack_observations_conditioned(gd_sim *s, const float *weights, float *out, int64_t out_bytes) {
+    if (!s || !weights || !out) return fail(GD_ERR_INVALID, "gd_pack_observations_conditioned: null argument");
+    const int64_t R = 6 + static_cast<int64_t>(s->A - 1) * 6 + GD_MAP_OBS_K * 13 + 3;
+    if (out_bytes < static_cast<int64_t>(s->W) * s->A * R * 4)
+        return fail(GD_ERR_INVALID, "gd_pack_observations_conditioned: output buffer too small");
+    return guarded([&]() {
+        gd::launch_pack_obs_conditioned(s->d, s->stream, weights, out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_expert_actions(gd_sim *s, float *actions, int32_t action_cols, float *pos_xy, float *vel_xy, float *yaw,
                       int32_t *valids) {
     if (!s) return fail(GD_ERR_INVALID, "gd_expert_actions: null sim");
@@ -1302,13 +1313,54 @@ int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_bu
         !b->offroad_in_episode || !b->live_agent_mask || !b->reward_out || !b->terminal_out || !b->truncated_out ||
         !b->mask_out || !b->done_worlds || !b->stats || !b->world_stats)
         return fail(GD_ERR_INVALID, "gd_episode_step: every buffer is required");
-    if (cfg->reward_type != GD_EPISODE_REWARD_WEIGHTED && cfg->reward_type != GD_EPISODE_REWARD_SPARSE)
+    if (cfg->reward_type < GD_EPISODE_REWARD_WEIGHTED || cfg->reward_type > GD_EPISODE_REWARD_LOG_DISTANCE)
         return fail(GD_ERR_INVALID, "gd_episode_step: unknown reward_type");
+    if (cfg->reward_type == GD_EPISODE_REWARD_CONDITIONED && (!b->reward_weights || !b->weight_draws))
+        return fail(GD_ERR_INVALID, "gd_episode_step: reward_conditioned needs reward_weights and weight_draws");
+    if (cfg->reward_type == GD_EPISODE_REWARD_CONDITIONED &&
+        (cfg->condition_mode < GD_CONDITION_RANDOM || cfg->condition_mode > GD_CONDITION_FIXED))
+        return fail(GD_ERR_INVALID, "gd_episode_step: unknown condition_mode");
     return guarded([&]() {
         HIP_CHECK(hipMemsetAsync(s->d.any_reset, 0, sizeof(int32_t), s->stream));
         gd::launch_episode_step(s->d, s->stream, *cfg, *b);
         HIP_CHECK(hipGetLastError());
         if (cfg->auto_reset) s->reset_flagged(true);
+    });
+}
+
+int gd_episode_draw_weights(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b, const int32_t *worlds,
+                            int32_t n) {
+    if (!s || !cfg || !b || !b->reward_weights || !b->weight_draws || (worlds && n < 0))
+        return fail(GD_ERR_INVALID, "gd_episode_draw_weights: bad argument");
+    if (cfg->condition_mode < GD_CONDITION_RANDOM || cfg->condition_mode > GD_CONDITION_FIXED)
+        return fail(GD_ERR_INVALID, "gd_episode_draw_weights: unknown condition_mode");
+    std::vector<int32_t> list;
+    if (worlds) {
+        list.assign(worlds, worlds + n);
+        for (const int32_t w : list)
+            if (w < 0 || w >= s->W) return fail(GD_ERR_INVALID, "gd_episode_draw_weights: world index out of range");
+        std::sort(list.begin(), list.end());  // a world listed twice is drawn once (one workgroup per world)
+        list.erase(std::unique(list.begin(), list.end()), list.end());
+        if (list.empty()) return GD_OK;
+    }
+    return guarded([&]() {
+        if (!worlds) {
+            gd::launch_draw_weights(s->d, s->stream, *cfg, *b, nullptr, s->W);
+            HIP_CHECK(hipGetLastError());
+            return;
+        }
+        // an explicit call outside the step path: a temporary device copy of the list, waited for before it is freed
+        int32_t *dl = nullptr;
+        HIP_CHECK(hipMalloc(&dl, list.size() * sizeof(int32_t)));
+        hipError_t e = hipMemcpyAsync(dl, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s->stream);
+        if (e == hipSuccess) {
+            gd::launch_draw_weights(s->d, s->stream, *cfg, *b, dl, static_cast<int>(list.size()));
+            e = hipGetLastError();
+        }
+        const hipError_t es = hipStreamSynchronize(s->stream);
+        HIP_CHECK(hipFree(dl));
+        HIP_CHECK(e);
+        HIP_CHECK(es);
     });
 }
 

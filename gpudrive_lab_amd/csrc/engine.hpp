@@ -202,5 +202,8 @@ void launch_pack_obs(const DevSim &d, hipStream_t st, float *out);  // pack_obs.
 void launch_expert_actions(const DevSim &d, hipStream_t st, float *actions, float *pos, float *vel, float *yaw, int *valid);
 void launch_set_log_actions(const DevSim &d, hipStream_t st, int t);
 void launch_episode_step(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b);  // episode.hip
+void launch_draw_weights(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b,
+                         const int32_t *worlds, int n);  // episode.hip
+void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out);  // pack_obs.hip
 
 }  // namespace gd

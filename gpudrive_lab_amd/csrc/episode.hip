@@ -4,7 +4,9 @@
 // Info columns gpudrive/datatypes/info.py:11-15), as one kernel per step:
 //
 //   reward   = collision_w * (info[1] + info[2]) + goal_w * info[3] + off_road_w * info[0]
-//              (weighted_combination) or the simulator's reward (sparse_on_goal_achieved)
+//              (weighted_combination) or the simulator's reward (sparse_on_goal_achieved);
+//              reward_conditioned: the same sum with the agent slot's own weights (reward_weights[w][a][0..3));
+//              distance_to_logs: the weighted sum + log_distance_weight * exp(-|log_pos[t] - pos|) (gpudrive_amd.h)
 //   terminal = done != 0
 //   returns[live] += reward;  lengths += 1;  offroad += info[0];  collided += info[1] + info[2]
 //   mask     = live (before the update);  live[terminal] = 0
@@ -12,7 +14,16 @@
 //   world done <=> every controlled agent is terminal: its episode sums go to `stats`, its trackers are
 //   zeroed, live <- controlled, and its reset flag is raised ON THE DEVICE; the reset pass that follows
 //   (gd_sim::reset_flagged) is launched unconditionally and returns at once when nothing was flagged.
+//   reward_conditioned: a finished world's weights are redrawn here, before the reset pass (env_puffer.py:375-390), so the
+//   observation of the reset world already carries them.
 // One workgroup per world, one thread per agent slot.
+//
+// Weight draws (reference env_torch.py:247-401).  random: torch.rand cannot be matched value for value, so the draw is a
+// counter-based hash instead -- key (seed, world, weight_draws[world]), counter (slot, component) -- and matches the reference
+// in distribution only; it is reproducible, independent of launch order and restated bit for bit in numpy
+// (tests/test_reward_modes.py).  x = upper 32 bits of the 64-bit hash, u = (x >> 8) * 2^-24 in [0, 1), and
+// w = lb + u * f32(ub - lb) in f32, as the reference's `lower_bounds + random_values * bounds_range`.  preset / fixed: the
+// three weights of the config, resolved on the host.
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
@@ -20,6 +31,28 @@
 namespace gd {
 
 namespace {
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // the splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// draw `k` of the three weights of slot `a` of world `w` into wt[0..3)
+__device__ __forceinline__ void draw_weights(const gd_episode_config &c, int w, int k, int a, float *wt) {
+    const uint64_t key = mix64(c.seed ^ mix64((uint64_t)(uint32_t)w << 32 | (uint32_t)k));
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        float v = c.weights[j];
+        if (c.condition_mode == GD_CONDITION_RANDOM) {
+            const uint64_t x = mix64(key + (uint64_t)(a * 3 + j + 1) * 0x9E3779B97F4A7C15ull);
+            const float u = (float)(uint32_t)(x >> 40) * 0x1p-24f;
+            const float range = c.ub[j] - c.lb[j];
+            v = c.lb[j] + u * range;
+        }
+        wt[j] = v;
+    }
+}
 
 template <int A_T>
 __device__ __forceinline__ float block_sum(float v, float *scratch, int a) {
@@ -46,9 +79,24 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
     const float off_road = (float)info[0];
     const float collided = (float)(info[1] + info[2]);
     const float goal = (float)info[3];
-    const float reward = c.reward_type == GD_EPISODE_REWARD_SPARSE ? d.reward[i]
-                                                                 : (c.collision_weight * collided + c.goal_achieved_weight * goal) +
-                                                                       c.off_road_weight * off_road;
+    float reward;
+    if (c.reward_type == GD_EPISODE_REWARD_SPARSE) {
+        reward = d.reward[i];
+    } else if (c.reward_type == GD_EPISODE_REWARD_CONDITIONED) {
+        const float *wt = b.reward_weights + i * 3;
+        reward = (wt[0] * collided + wt[1] * goal) + wt[2] * off_road;
+    } else {
+        reward = (c.collision_weight * collided + c.goal_achieved_weight * goal) + c.off_road_weight * off_road;
+        if (c.reward_type == GD_EPISODE_REWARD_LOG_DISTANCE) {
+            // slot 0's length before this step's increment (read before the barriers below, written after them); the clamp
+            // only guards the index
+            const int t = min(max((int)b.episode_lengths[(size_t)w * A_T], 0), GD_EPISODE_LEN - 1);
+            const float *tr = d.traj + i * GD_TRAJECTORY_FLOATS;
+            const float dx = tr[2 * t] - d.abs_obs[i * 14 + 0];
+            const float dy = tr[2 * t + 1] - d.abs_obs[i * 14 + 1];
+            reward = reward + c.log_distance_weight * expf(-sqrtf(dx * dx + dy * dy));
+        }
+    }
     const bool terminal = d.done[i] != 0;
     const bool controlled = b.controlled_mask[i] != 0;
     const bool live = b.live_agent_mask[i] != 0;
@@ -69,6 +117,9 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
     const int n_terminal = __syncthreads_count(controlled && terminal);
     const bool world_done = n_terminal == n_controlled;  // also true for a world without controlled agents
     if (world_done) {
+        const bool redraw = c.reward_type == GD_EPISODE_REWARD_CONDITIONED && c.auto_reset;
+        const int draw = redraw ? b.weight_draws[w] : 0;  // read before the barriers of block_sum, incremented after them
+        if (redraw) draw_weights(c, w, draw, a, b.reward_weights + i * 3);  // this step's reward has read the old ones
         const float fc = controlled ? 1.f : 0.f;
         float sums[8];
         sums[0] = block_sum<A_T>(fc * ret, scratch, a);
@@ -104,6 +155,7 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
             ws[GD_EPISODE_STAT_TOTAL_OFF_ROAD] = sums[7];
             b.done_worlds[w] = 1;
             if (c.auto_reset) { d.reset_flags[w] = 1; *d.any_reset = 1; }
+            if (redraw) b.weight_draws[w] = draw + 1;
         }
         // env_puffer.py:381-391: empty the storage of the finished worlds
         b.agent_episode_returns[i] = 0.f;
@@ -121,7 +173,23 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
     }
 }
 
+// gd_episode_draw_weights: one workgroup per listed world (worlds == null: world blockIdx.x), one thread per agent slot
+template <int A_T>
+__global__ __launch_bounds__(A_T) void k_draw_weights(gd_episode_config c, gd_episode_buffers b, const int32_t *worlds) {
+    const int w = worlds ? worlds[blockIdx.x] : (int)blockIdx.x, a = threadIdx.x;
+    const int draw = b.weight_draws[w];
+    draw_weights(c, w, draw, a, b.reward_weights + ((size_t)w * A_T + a) * 3);
+    __syncthreads();
+    if (a == 0) b.weight_draws[w] = draw + 1;
+}
+
 }  // namespace
+
+void launch_draw_weights(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b,
+                         const int32_t *worlds, int n) {
+    if (d.A == 64) hipLaunchKernelGGL(k_draw_weights<64>, dim3(n), dim3(64), 0, st, c, b, worlds);
+    else hipLaunchKernelGGL(k_draw_weights<128>, dim3(n), dim3(128), 0, st, c, b, worlds);
+}
 
 void launch_episode_step(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b) {
     if (d.A == 64) hipLaunchKernelGGL(k_episode_step<64>, dim3(d.W), dim3(64), 0, st, d, c, b);

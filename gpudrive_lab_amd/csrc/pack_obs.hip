@@ -65,6 +65,95 @@ __global__ __launch_bounds__(256) void k_pack_obs(DevSim d, float *out) {
     }
 }
 
+// ---- the conditioned row (gd_pack_observations_conditioned): ego(6) | weights(3) | partners | roads, R = D + 3 floats ----
+// R is odd, so rows are no longer whole float4 groups; a world's block A * R is (A in {64, 128}) and starts 16-byte aligned.
+// The stores stay 16-byte and coalesced by numbering the float4 groups over the world's block: agent slot a owns the groups
+// whose first element lies in its row, [ceil(a R / 4), ceil((a + 1) R / 4)).  The last of them straddles into the next row
+// by at most 3 floats, which are ego columns 0..2 of slot a + 1: they need that slot's self-observation row only.
+template <int A_T>
+__global__ __launch_bounds__(256) void k_pack_obs_cond(DevSim d, const float *__restrict__ weights, float *out) {
+    constexpr int D = 6 + (A_T - 1) * 6 + K * 13, R = D + 3;
+    static_assert((A_T * R) % 4 == 0 && (K * 9) % 4 == 0, "a world's block is whole float4 groups");
+    constexpr int NP = (A_T - 1) * 9, NR = K * 9;
+    constexpr int GROUP = A_T / GD_PACK_PARTS;
+    __shared__ float s_self[8], s_next[8], s_wt[4];
+    __shared__ float s_partner[NP];
+    __shared__ __attribute__((aligned(16))) float s_road[NR];
+    const int w = blockIdx.x, tid = threadIdx.x;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    f4 *wout = reinterpret_cast<f4 *>(out + (size_t)w * A_T * R);
+    for (int al = 0; al < GROUP; al++) {
+        const int a = blockIdx.y * GROUP + al;
+        const size_t agent = (size_t)w * A_T + a;
+        if (tid < 8) s_self[tid] = d.self_obs[agent * 8 + tid];
+        else if (tid < 16 && a + 1 < A_T) s_next[tid - 8] = d.self_obs[(agent + 1) * 8 + tid - 8];
+        else if (tid >= 16 && tid < 19) s_wt[tid - 16] = weights[agent * 3 + tid - 16];
+        for (int t = tid; t < NP; t += 256) s_partner[t] = d.partner[agent * NP + t];
+        const float4 *rsrc = reinterpret_cast<const float4 *>(d.agent_map + agent * NR);
+        for (int t = tid; t < NR / 4; t += 256) reinterpret_cast<float4 *>(s_road)[t] = rsrc[t];
+        __syncthreads();
+        const int row0 = a * R, row1 = row0 + R;  // this slot's row within the world's block
+        const int q0 = (row0 + 3) / 4, q1 = (row1 + 3) / 4;
+        for (int q = q0 + tid; q < q1; q += 256) {
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int e = 4 * q + k;
+                if (e >= row1) {
+                    v[k] = pack_ego_col(s_next, e - row1);  // e - row1 < 3; never reached for the last slot (q1 * 4 == A R)
+                } else {
+                    const int j = e - row0;
+                    v[k] = j < 6 ? pack_ego_col(s_self, j) : j < 9 ? s_wt[j - 6] : pack_element<A_T>(s_self, s_partner, s_road, j - 3);
+                }
+            }
+            const f4 vv = {v[0], v[1], v[2], v[3]};
+            __builtin_nontemporal_store(vv, wout + q);
+        }
+        __syncthreads();
+    }
+}
+
+// The same rows from the attached direct-pack buffer ([rows][D], the only current copy with gd_attach_packed(only = 1)): one
+// thread per output float4 group over all rows, the three weights inserted after column 5.  Inside a row's body (column >= 9
+// and the group within the row) the four source floats are consecutive, 16-byte aligned up to a shift m = source index mod 4
+// that is the same for the whole row: two aligned 16-byte loads and a select.  The few groups at a row's start and end take
+// element by element.
+template <int A_T>
+__global__ __launch_bounds__(256) void k_pack_relayout(const float *__restrict__ src, const float *__restrict__ weights, float *out,
+                                                       size_t groups) {
+    constexpr int D = 6 + (A_T - 1) * 6 + K * 13, R = D + 3;
+    static_assert(D % 4 == 0 && (A_T * R) % 4 == 0, "source rows and world blocks are whole float4 groups");
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const size_t e = 4 * g, r = e / R;
+    const int j = (int)(e - r * R);
+    float v[4];
+    if (j >= 9 && j + 3 < R) {
+        const size_t sidx = r * D + (j - 3);
+        const float4 *s4 = reinterpret_cast<const float4 *>(src) + (sidx >> 2);
+        const int m = (int)(sidx & 3);
+        const float4 lo = s4[0];
+        if (m == 0) {
+            v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+        } else {
+            const float4 hi = s4[1];  // holds source element sidx + 3 at least: inside the buffer
+            if (m == 1) { v[0] = lo.y; v[1] = lo.z; v[2] = lo.w; v[3] = hi.x; }
+            else if (m == 2) { v[0] = lo.z; v[1] = lo.w; v[2] = hi.x; v[3] = hi.y; }
+            else { v[0] = lo.w; v[1] = hi.x; v[2] = hi.y; v[3] = hi.z; }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const size_t rr = j + k >= R ? r + 1 : r;  // groups is whole, so row r + 1 exists when reached
+            const int jj = j + k >= R ? j + k - R : j + k;
+            v[k] = jj < 6 ? src[rr * D + jj] : jj < 9 ? weights[rr * 3 + jj - 6] : src[rr * D + jj - 3];
+        }
+    }
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const f4 vv = {v[0], v[1], v[2], v[3]};
+    __builtin_nontemporal_store(vv, reinterpret_cast<f4 *>(out) + g);
+}
+
 // ---- expert-action export and log playback ----
 // GPUDriveTorchEnv.get_expert_actions() (reference gpudrive/env/env_torch.py:1445-1509) slices the
 // expert trajectory rows ([pos 182 | vel 182 | yaw 91 | valid 91 | inferred action 910],
@@ -129,6 +218,18 @@ __global__ __launch_bounds__(256) void k_set_log_actions(DevSim d, int t) {
 void launch_pack_obs(const DevSim &d, hipStream_t st, float *out) {
     if (d.A == 64) hipLaunchKernelGGL(k_pack_obs<64>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, out);
     else hipLaunchKernelGGL(k_pack_obs<128>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, out);
+}
+
+void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out) {
+    if (d.pack) {  // the attached buffer is current (its raw rows may not be)
+        const size_t D = 6 + (size_t)(d.A - 1) * 6 + K * 13, groups = (size_t)d.W * d.A * (D + 3) / 4;
+        const dim3 grid((unsigned)((groups + 255) / 256));
+        if (d.A == 64) hipLaunchKernelGGL(k_pack_relayout<64>, grid, dim3(256), 0, st, d.pack, weights, out, groups);
+        else hipLaunchKernelGGL(k_pack_relayout<128>, grid, dim3(256), 0, st, d.pack, weights, out, groups);
+        return;
+    }
+    if (d.A == 64) hipLaunchKernelGGL(k_pack_obs_cond<64>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, weights, out);
+    else hipLaunchKernelGGL(k_pack_obs_cond<128>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, weights, out);
 }
 
 void launch_expert_actions(const DevSim &d, hipStream_t st, float *actions, float *pos, float *vel, float *yaw, int *valid) {

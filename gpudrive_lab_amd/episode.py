@@ -3,19 +3,67 @@
 `EpisodeTracker` keeps what `PufferGPUDrive.step()` keeps (reference gpudrive/env/env_puffer.py:250-403):
 live-agent mask, per-agent episode returns and lengths, collision / off-road counts, detection of
 finished worlds, their statistics and their asynchronous reset -- in ONE kernel per step plus the
-device-side reset pass, with no `.item()` / `.cpu()` synchronisation.  Field names follow the reference."""
+device-side reset pass, with no `.item()` / `.cpu()` synchronisation.  Field names follow the reference.
+
+Reward types (gpudrive/env/env_torch.py:469-603): "weighted_combination", "sparse_on_goal_achieved", "reward_conditioned"
+(every agent slot has its own three weights, `reward_weights_tensor` [W, A, 3], drawn per world at construction and again
+for every world the tracker resets) and "distance_to_logs" (the weighted combination plus
+`log_distance_weight * exp(-distance to the logged position)`, the logged position taken at the episode's step count).
+Condition modes of the weights (env_torch.py:247-401): "random" draws `lb + u * (ub - lb)` per component, u from a
+counter-based generator of (seed, world, draw, slot, component) -- it matches the reference (torch.rand) in distribution,
+not value for value; "preset" and "fixed" match it in value."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _capi
 
-REWARD_TYPES = {"weighted_combination": 0, "sparse_on_goal_achieved": 1}
+REWARD_TYPES = {"weighted_combination": _capi.EPISODE_REWARD_WEIGHTED, "sparse_on_goal_achieved": _capi.EPISODE_REWARD_SPARSE,
+                "reward_conditioned": _capi.EPISODE_REWARD_CONDITIONED, "distance_to_logs": _capi.EPISODE_REWARD_LOG_DISTANCE}
+CONDITION_MODES = {"random": _capi.CONDITION_RANDOM, "preset": _capi.CONDITION_PRESET, "fixed": _capi.CONDITION_FIXED}
+# bounds of (collision, goal_achieved, off_road), gpudrive/env/config.py:103-113
+DEFAULT_LB = (-1.0, 1.0, -1.0)
+DEFAULT_UB = (0.0, 2.0, 0.0)
+# the named weight sets, from the bounds (env_torch.py:290-345), in Python floats
+PRESETS = {
+    "cautious": lambda lb, ub: (lb[0] * 0.9, ub[1] * 0.7, lb[2] * 0.9),
+    "aggressive": lambda lb, ub: (lb[0] * 0.5, ub[1] * 0.9, lb[2] * 0.6),
+    "balanced": lambda lb, ub: ((lb[0] + ub[0]) / 2, (lb[1] + ub[1]) / 2, (lb[2] + ub[2]) / 2),
+    "risk_taker": lambda lb, ub: (lb[0] * 0.3, ub[1], lb[2] * 0.4),
+}
+
+
+def resolve_condition(condition_mode, agent_type=None, lb=DEFAULT_LB, ub=DEFAULT_UB):
+    """(mode code, float32[3] weights) for a condition mode; the weights are zero for "random".  Host only: raises
+    ValueError for an unknown mode or preset name and for a "fixed" `agent_type` whose shape is not (3,)."""
+    if condition_mode not in CONDITION_MODES:
+        raise ValueError("unknown condition_mode %r (one of %s)" % (condition_mode, sorted(CONDITION_MODES)))
+    if condition_mode == "random":
+        return CONDITION_MODES["random"], np.zeros(3, np.float32)
+    if condition_mode == "preset":
+        if not isinstance(agent_type, str) or agent_type not in PRESETS:
+            raise ValueError("unknown agent_type %r for condition_mode='preset' (one of %s)" % (agent_type, sorted(PRESETS)))
+        lb, ub = [float(x) for x in lb], [float(x) for x in ub]
+        return CONDITION_MODES["preset"], np.asarray(PRESETS[agent_type](lb, ub), np.float32)
+    if agent_type is None or isinstance(agent_type, str):
+        raise ValueError("condition_mode='fixed' needs agent_type: a tensor of shape [3]")
+    w = agent_type.detach().cpu().numpy() if isinstance(agent_type, torch.Tensor) else np.asarray(agent_type)
+    if w.shape != (3,):
+        raise ValueError("agent_type must have shape [3], got %s" % (tuple(w.shape),))
+    return CONDITION_MODES["fixed"], w.astype(np.float32)
 
 
 class EpisodeTracker:
     def __init__(self, sim, collision_weight=-0.5, goal_achieved_weight=1.0, off_road_weight=-0.5,
-                 reward_type="weighted_combination", auto_reset=True):
+                 reward_type="weighted_combination", auto_reset=True, *, condition_mode="random", agent_type=None,
+                 reward_weight_lb=DEFAULT_LB, reward_weight_ub=DEFAULT_UB, log_distance_weight=0.01, seed=0):
+        """reward_type: a key of REWARD_TYPES.  reward_conditioned: `condition_mode` / `agent_type` say how the weights of
+        every world are drawn, now and whenever the tracker resets a world (see `set_reward_weights`); `reward_weight_lb`
+        / `_ub` are the (collision, goal_achieved, off_road) bounds of "random" and of the presets; `seed` keys "random".
+        distance_to_logs: `log_distance_weight` scales the distance term."""
+        if reward_type not in REWARD_TYPES:
+            raise ValueError("unknown reward_type %r (one of %s)" % (reward_type, sorted(REWARD_TYPES)))
         self.sim = sim
         self._L = _capi.lib()
         W, A = sim._W, sim._A
@@ -40,6 +88,57 @@ class EpisodeTracker:
             p(self._cmask_u8), p(self.agent_episode_returns), p(self.episode_lengths), p(self.collided_in_episode),
             p(self.offroad_in_episode), p(self.live_agent_mask), p(self.rewards), p(self.terminals), p(self.truncations),
             p(self.masks), p(self.done_worlds), p(self.stats), p(self.world_stats))
+        self._lb = tuple(float(x) for x in reward_weight_lb)
+        self._ub = tuple(float(x) for x in reward_weight_ub)
+        if len(self._lb) != 3 or len(self._ub) != 3:
+            raise ValueError("reward_weight_lb / reward_weight_ub need three components (collision, goal_achieved, off_road)")
+        self.reward_weights_tensor = None  # [W, A, 3] f32: reward_conditioned only (or after set_reward_weights)
+        self.weight_draws = None           # [W] int32: draws of each world's weights so far
+        if reward_type == "distance_to_logs":
+            self.cfg.log_distance_weight = float(log_distance_weight)
+        self.cfg.seed = int(seed) & (2 ** 64 - 1)
+        for j in range(3):
+            self.cfg.lb[j], self.cfg.ub[j] = self._lb[j], self._ub[j]
+        if reward_type == "reward_conditioned":
+            self._set_condition(self.cfg, condition_mode, agent_type)
+            self.set_reward_weights(condition_mode=condition_mode, agent_type=agent_type)  # draw 0 of every world
+
+    def _set_condition(self, cfg, condition_mode, agent_type):
+        mode, w = resolve_condition(condition_mode, agent_type, self._lb, self._ub)
+        cfg.condition_mode = mode
+        for j in range(3):
+            cfg.weights[j] = float(w[j])
+
+    def set_reward_weights(self, worlds=None, condition_mode="random", agent_type=None):
+        """Draw new reward weights for the listed worlds (None: all) into `reward_weights_tensor`, on the device
+        (the reference's _set_reward_weights(env_idx_list, condition_mode, agent_type), env_torch.py:247-401).
+        "random": a new draw of the generator (see the module docstring); "preset": agent_type names one of PRESETS;
+        "fixed": agent_type is a tensor of shape [3].  Arguments are checked before anything reaches the device
+        (ValueError).  The mode the tracker redraws reset worlds in is the one given at construction."""
+        cfg = _capi.GdEpisodeConfig.from_buffer_copy(self.cfg)
+        self._set_condition(cfg, condition_mode, agent_type)
+        idx = None
+        if worlds is not None:
+            if hasattr(worlds, "detach"):
+                worlds = worlds.detach().cpu().numpy()
+            idx = np.ascontiguousarray(np.atleast_1d(np.asarray(worlds)).astype(np.int32).ravel())
+            if ((idx < 0) | (idx >= self.sim._W)).any():
+                raise ValueError("set_reward_weights: world index out of range")
+        if self.reward_weights_tensor is None:
+            W, A = self.sim._W, self.sim._A
+            dev = self.rewards.device
+            self.reward_weights_tensor = torch.zeros((W, A, 3), dtype=torch.float32, device=dev)
+            self.weight_draws = torch.zeros((W,), dtype=torch.int32, device=dev)
+            self._bufs.reward_weights = self.reward_weights_tensor.data_ptr()
+            self._bufs.weight_draws = self.weight_draws.data_ptr()
+        self.sim._bind_stream()
+        if idx is None:
+            rc = self._L.gd_episode_draw_weights(self.sim._h, C.byref(cfg), C.byref(self._bufs), None, 0)
+        else:
+            rc = self._L.gd_episode_draw_weights(self.sim._h, C.byref(cfg), C.byref(self._bufs),
+                                                 idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx))
+        _capi.check(rc, "gd_episode_draw_weights")
+        return self.reward_weights_tensor
 
     def step(self, step_sim=True):
         """sim.step() (actions are already in the action tensor), then the bookkeeping kernel and the

@@ -313,12 +313,27 @@ class SimManager:
     def sync(self):
         _capi.check(self._L.gd_sync(self._h), "gd_sync")
 
-    def packed_observations(self, out=None):
+    def packed_observations(self, out=None, reward_weights=None):
         """Extension (not in the reference module): the flattened, normalised observation that
         `GPUDriveTorchEnv.get_obs()` assembles from the raw tensors (ego 6 | partners (A-1)*6 |
-        road points 200*13), written by one fused kernel.  Returns a [W, A, D] float32 tensor."""
+        road points 200*13), written by one fused kernel.  Returns a [W, A, D] float32 tensor.
+        reward_weights: a [W, A, 3] float32 device tensor (EpisodeTracker.reward_weights_tensor): the observation of the
+        reward-conditioned policy instead, [W, A, D + 3] = ego 6 | the slot's 3 weights | partners | road points
+        (env_torch.py:756-810), from the raw tensors or -- after `direct_pack()` -- from the tensor the step wrote."""
         import torch
         D = 6 + (self._A - 1) * 6 + kMaxAgentMapObservationsCount * 13
+        if reward_weights is not None:
+            wt = reward_weights
+            assert wt.is_cuda and wt.is_contiguous() and wt.dtype == torch.float32 and tuple(wt.shape) == (self._W, self._A, 3)
+            if out is None:
+                out = getattr(self, "_packed_cond", None)
+                if out is None:
+                    out = self._packed_cond = torch.empty((self._W, self._A, D + 3), dtype=torch.float32, device=self._device)
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= self._W * self._A * (D + 3)
+            self._bind_stream()
+            _capi.check(self._L.gd_pack_observations_conditioned(self._h, wt.data_ptr(), out.data_ptr(), out.numel() * 4),
+                        "gd_pack_observations_conditioned")
+            return out.view(-1)[:self._W * self._A * (D + 3)].view(self._W, self._A, D + 3)
         if out is None:
             out = getattr(self, "_packed", None)
             if out is None:

@@ -165,6 +165,12 @@ int gd_pack_observations(gd_sim *sim, float *out, int64_t out_bytes);
  * selections); GD_ERR_UNSUPPORTED only with disableClassicalObs or the developer switch GPUDRIVE_LINEAR_LEGACY=1.  With a
  * buffer attached gd_pack_observations is a no-op for that buffer and a device copy for any other. */
 int gd_attach_packed(gd_sim *sim, float *out, int64_t out_bytes, int32_t only);
+/* The packed observation of the reward-conditioned policy (env_torch.py:756-810; gpudrive/networks/late_fusion.py:104-110):
+ * out[W][A][D + 3] f32 = ego(6) | weights[w][a][0..3) | partners (A-1) x 6 | road points 200 x 13, D as above; every column
+ * but the three inserted ones bit-identical to gd_pack_observations on the same state.  `weights` is a device pointer to
+ * [W][A][3] f32 (EpisodeTracker.reward_weights_tensor).  Written from the raw tensors, or -- while a buffer is attached with
+ * gd_attach_packed -- by a copy of that buffer that inserts the three columns (with only != 0 the raw rows are stale). */
+int gd_pack_observations_conditioned(gd_sim *sim, const float *weights, float *out, int64_t out_bytes);
 /* Expert-action export: GPUDriveTorchEnv.get_expert_actions()
  * (gpudrive/env/env_torch.py:1445-1509 over gpudrive/datatypes/trajectory.py:24-41) in one pass over the
  * expert trajectory rows.  Device pointers, any of them may be NULL:
@@ -182,7 +188,21 @@ int gd_advance_log_playback(gd_sim *sim, int32_t init_steps);
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
  * Call after gd_step.  All pointers are device pointers owned by the caller, [W][A] unless noted. */
 enum { GD_EPISODE_REWARD_WEIGHTED = 0,  /* "weighted_combination": cw*collided + gw*goal_achieved + ow*off_road */
-       GD_EPISODE_REWARD_SPARSE = 1 };  /* "sparse_on_goal_achieved": the simulator's reward tensor */
+       GD_EPISODE_REWARD_SPARSE = 1,    /* "sparse_on_goal_achieved": the simulator's reward tensor */
+       GD_EPISODE_REWARD_CONDITIONED = 2,  /* "reward_conditioned" (env_torch.py:507-522): (w0*collided + w1*goal_achieved)
+                                            * + w2*off_road with w = reward_weights[w][a][0..3) */
+       GD_EPISODE_REWARD_LOG_DISTANCE = 3 };  /* "distance_to_logs" (env_torch.py:566-603): the weighted combination
+                                               * + log_distance_weight * exp(-|log_pos[w][a][t] - pos[w][a]|), pos = columns 0, 1
+                                               * of absolute_self_observation, log_pos = expert_trajectory[w][a][2t .. 2t+2),
+                                               * t = (int)episode_lengths[w][0] BEFORE this step's increment (env_puffer.py:251-256),
+                                               * clamped to [0, 90] (a guard: the reference would index out of range).  t counts
+                                               * from the episode's start, not from the simulator's step: after
+                                               * gd_advance_log_playback it lags the simulator, as it does in the reference loop. */
+/* How the reward weights of the conditioned reward are drawn (env_torch.py:247-401) */
+enum { GD_CONDITION_RANDOM = 0,  /* lb + u * f32(ub - lb) per component, u in [0, 1) from a counter-based generator:
+                                  * key (seed, world, weight_draws[world]), counter (slot, component); see episode.hip */
+       GD_CONDITION_PRESET = 1,  /* the three weights of gd_episode_config, resolved by the caller from a named preset */
+       GD_CONDITION_FIXED = 2 }; /* the three weights of gd_episode_config, given by the caller */
 enum { GD_EPISODE_STAT_EPISODES = 0,    /* finished worlds */
        GD_EPISODE_STAT_FINISHED_AGENTS, /* controlled agents in them */
        GD_EPISODE_STAT_RETURN_SUM,      /* sum of agent_episode_returns over those agents */
@@ -197,6 +217,12 @@ typedef struct gd_episode_config {
     float collision_weight, goal_achieved_weight, off_road_weight;
     int32_t reward_type;  /* GD_EPISODE_REWARD_* */
     int32_t auto_reset;   /* raise the reset flag of finished worlds and reset them (resetSystem + observations) */
+    /* appended; zero-initialised they change nothing for the two reward types above */
+    float log_distance_weight;  /* GD_EPISODE_REWARD_LOG_DISTANCE (reference default 0.01) */
+    int32_t condition_mode;     /* GD_CONDITION_*: how a finished world's weights are redrawn (GD_EPISODE_REWARD_CONDITIONED) */
+    float weights[3];           /* preset / fixed: collision, goal_achieved, off_road */
+    float lb[3], ub[3];         /* random: bounds per component */
+    uint64_t seed;              /* random: the generator's seed */
 } gd_episode_config;
 typedef struct gd_episode_buffers {
     const uint8_t *controlled_mask;  /* cont_agent_mask captured at t = 0 (bool) */
@@ -209,8 +235,18 @@ typedef struct gd_episode_buffers {
     int32_t *done_worlds;  /* [W] 1 for worlds whose episode ended in this step */
     float *stats;          /* [GD_EPISODE_STATS] running sums over finished episodes (the caller zeroes them) */
     float *world_stats;    /* [W][GD_EPISODE_STATS] the same for the last finished episode of each world */
+    /* appended; required by GD_EPISODE_REWARD_CONDITIONED only */
+    float *reward_weights;  /* [W][A][3] collision, goal_achieved, off_road weights of every agent slot */
+    int32_t *weight_draws;  /* [W] draws of each world's weights so far (the generator's draw counter) */
 } gd_episode_buffers;
+/* With GD_EPISODE_REWARD_CONDITIONED a finished world's reward_weights are redrawn in cfg->condition_mode by the same kernel,
+ * before the reset pass, so the observation of the reset world carries its new weights (env_puffer.py:375-390). */
 int gd_episode_step(gd_sim *sim, const gd_episode_config *cfg, const gd_episode_buffers *buffers);
+/* Draw the reward weights of the listed worlds (host array of n world indices; NULL = every world) in cfg->condition_mode
+ * into buffers->reward_weights and count the draw in buffers->weight_draws (EpisodeTracker.set_reward_weights, the
+ * reference's _set_reward_weights(env_idx_list, condition_mode, agent_type), env_torch.py:247-401). */
+int gd_episode_draw_weights(gd_sim *sim, const gd_episode_config *cfg, const gd_episode_buffers *buffers,
+                            const int32_t *worlds, int32_t n);
 
 /* Block until everything launched so far has finished (the reference's step() is synchronous). */
 int gd_sync(gd_sim *sim);
