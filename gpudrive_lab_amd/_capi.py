@@ -90,12 +90,19 @@ class GdEpisodeBuffers(C.Structure):
         "reward_weights", "weight_draws")]
 
 
+class GdEpisodeBuffersRows(GdEpisodeBuffers):
+    """The whole gd_episode_buffers: GdEpisodeBuffers (the layout before the learner rows) + the four flat outputs appended
+    with them.  The entry points take this one only, so that the engine never reads past a caller's struct."""
+    _fields_ = [(n, C.c_void_p) for n in ("reward_rows", "terminal_rows", "truncated_rows", "mask_rows")]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_episode_step", "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights",
+    "gd_set_learner_rows", "gd_attach_packed_rows", "gd_set_discrete_actions",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
     "gd_kernel_timing_enable", "gd_kernel_timing_read", "gd_debug_get_state", "gd_debug_set_state", "gd_debug_road_path",
     "gd_host_world_build", "gd_host_world_free", "gd_scene_cache_write",
@@ -146,9 +153,12 @@ def lib():
     L.gd_pack_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.gd_attach_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
     L.gd_attach_packed.restype = C.c_int
-    L.gd_episode_step.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffers)]
-    L.gd_episode_draw_weights.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffers),
+    L.gd_episode_step.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffersRows)]
+    L.gd_episode_draw_weights.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffersRows),
                                           C.POINTER(C.c_int32), C.c_int32]
+    L.gd_set_learner_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+    L.gd_attach_packed_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    L.gd_set_discrete_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_pack_observations_conditioned.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.gd_scene_cache_write.argtypes = [C.c_char_p, C.c_float, C.c_char_p]
     L.gd_expert_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

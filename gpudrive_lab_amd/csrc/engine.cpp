@@ -134,6 +134,9 @@ struct gd_sim {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     size_t lin_cap = 0;        // entries of d.lin_list / d.lin_list_dyn
+    // learner rows (gd_set_learner_rows): both maps, [W * A] each, and the row count the map kernel returns; d.row_of_slot /
+    // d.slot_of_row point at them while rows are set
+    int32_t *d_row_of_slot = nullptr, *d_slot_of_row = nullptr, *d_row_count = nullptr;
     int32_t *d_lin_list = nullptr, *d_lin_list_dyn = nullptr;
     std::vector<std::vector<int32_t>> w_resp;  // response type of every agent slot (who can move at all)
     bool full_pass_next = false;  // the next step's road pass takes every live agent (state was written from outside)
@@ -804,7 +807,38 @@ struct gd_sim {
         launch(gd::KERNEL_PADDING, false);
         // the packed observation's rows of padding agents come from the raw padding rows just written (the live agents' rows are
         // written by the reset pass that follows every rebuild)
-        if (d.pack) gd::launch_pack_obs(d, stream, d.pack);
+        if (d.pack && d.pack_rows) gd::launch_pack_obs_rows(d, stream, d.pack);
+        else if (d.pack) gd::launch_pack_obs(d, stream, d.pack);
+    }
+
+    // detach the packed buffer (either kind): the raw tensors are written again from the next pass on; bring them up to date now
+    void detach_packed() {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        drop_graph();
+        d.pack = nullptr;
+        d.pack_only = 0;
+        d.pack_rows = 0;
+        HIP_CHECK(hipMemsetAsync(d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(W) * A, stream));
+        reset_flagged(false);
+    }
+
+    // attach `out` as the packed buffer: everything once from the raw tensors (the padding agents' rows never change between
+    // rebuilds); then every pass of the step kernels writes the live agents' rows in place.  Every pose stamp dies: the next
+    // pass writes every live agent's road columns, whatever was skipped before.  rows: out is [n_rows][D] (learner rows).
+    void attach_packed(float *out, bool only, bool rows) {
+        HIP_CHECK(hipStreamSynchronize(stream));
+        drop_graph();
+        d.pack = nullptr;
+        d.pack_only = 0;
+        d.pack_rows = 0;
+        HIP_CHECK(hipMemsetAsync(d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(W) * A, stream));
+        reset_flagged(false);  // raw tensors up to date (a previous pack_only attachment left them stale)
+        if (rows) gd::launch_pack_obs_rows(d, stream, out);
+        else gd::launch_pack_obs(d, stream, out);
+        HIP_CHECK(hipGetLastError());
+        d.pack = out;
+        d.pack_only = only ? 1 : 0;
+        d.pack_rows = rows ? 1 : 0;
     }
 
     // the packed observation can be written where the rows are produced by every road path -- the linear scan, set order
@@ -1131,6 +1165,10 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         d.pose_stamp = s->alloc_internal<uint4>(WA);
         d.pose_skip = std::getenv("GPUDRIVE_NO_POSE_SKIP") == nullptr ? 1 : 0;
         d.stat_skipped = s->alloc_internal<unsigned long long>(GD_SKIP_SLOTS);
+        s->d_row_of_slot = s->alloc_internal<int32_t>(WA);
+        s->d_slot_of_row = s->alloc_internal<int32_t>(WA);
+        s->d_row_count = s->alloc_internal<int32_t>(1);
+        d.bad_actions = s->alloc_internal<unsigned long long>(1);
         d.blk_off = s->alloc_internal<int32_t>(W + 1);
         // rank replay of the reference-order selection (map_obs_rank.hip): a fallback group is one workgroup of k_map_obs.
         // Its buffers (7.4 KB per agent slot) are allocated when a batch first takes the path (rebuild_worlds).
@@ -1230,8 +1268,10 @@ int gd_pack_observations(gd_sim *s, float *out, int64_t out_bytes) {
     const int64_t D = 6 + static_cast<int64_t>(s->A - 1) * 6 + GD_MAP_OBS_K * 13;
     const int64_t need = static_cast<int64_t>(s->W) * s->A * D * 4;
     if (out_bytes < need) return fail(GD_ERR_INVALID, "gd_pack_observations: output buffer too small");
+    if (s->d.pack && s->d.pack_rows && s->d.pack_only)
+        return fail(GD_ERR_UNSUPPORTED, "gd_pack_observations: learner rows are attached with only = 1: the raw rows are stale");
     return guarded([&]() {
-        if (s->d.pack) {  // the step already wrote it (gd_attach_packed): nothing to do, or a copy for another buffer
+        if (s->d.pack && !s->d.pack_rows) {  // the step already wrote it (gd_attach_packed): nothing to do, or a copy for another buffer
             if (out != s->d.pack) HIP_CHECK(hipMemcpyAsync(out, s->d.pack, need, hipMemcpyDeviceToDevice, s->stream));
             return;
         }
@@ -1248,26 +1288,58 @@ int gd_attach_packed(gd_sim *s, float *out, int64_t out_bytes, int32_t only) {
     if (out && !s->direct_pack_supported())
         return fail(GD_ERR_UNSUPPORTED, "gd_attach_packed: not available with disableClassicalObs or GPUDRIVE_LINEAR_LEGACY=1: use gd_pack_observations");
     return guarded([&]() {
+        if (!out) s->detach_packed();  // (either kind)
+        else s->attach_packed(out, only != 0, false);
+    });
+}
+
+int gd_set_learner_rows(gd_sim *s, const uint8_t *mask, int32_t n_rows) {
+    if (!s) return fail(GD_ERR_INVALID, "gd_set_learner_rows: null sim");
+    const size_t WA = static_cast<size_t>(s->W) * s->A;
+    if (mask && (n_rows < 0 || static_cast<size_t>(n_rows) > WA))
+        return fail(GD_ERR_INVALID, "gd_set_learner_rows: n_rows out of range");
+    int32_t count = 0;
+    const int rc = guarded([&]() {
+        if (s->d.pack && s->d.pack_rows) s->detach_packed();  // its rows belong to the previous map
         HIP_CHECK(hipStreamSynchronize(s->stream));
         s->drop_graph();
-        if (!out) {  // detach: the raw tensors are written again from the next pass on; bring them up to date now
-            s->d.pack = nullptr;
-            s->d.pack_only = 0;
-            HIP_CHECK(hipMemsetAsync(s->d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(s->W) * s->A, s->stream));
-            s->reset_flagged(false);
-            return;
-        }
-        // everything once from the raw tensors (the padding agents' rows never change between rebuilds); then every pass of the
-        // step kernels writes the live agents' rows in place.  Every pose stamp dies: the next pass writes every live agent's
-        // road columns, whatever was skipped before.
-        s->d.pack = nullptr;
-        s->d.pack_only = 0;
-        HIP_CHECK(hipMemsetAsync(s->d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(s->W) * s->A, s->stream));
-        s->reset_flagged(false);               // raw tensors up to date (a previous pack_only attachment left them stale)
-        gd::launch_pack_obs(s->d, s->stream, out);
+        s->d.row_of_slot = nullptr;
+        s->d.slot_of_row = nullptr;
+        s->d.n_rows = 0;
+        if (!mask) return;
+        gd::launch_learner_rows(s->stream, mask, WA, s->d_row_of_slot, s->d_slot_of_row, s->d_row_count);
         HIP_CHECK(hipGetLastError());
-        s->d.pack = out;
-        s->d.pack_only = only ? 1 : 0;
+        HIP_CHECK(hipMemcpyAsync(&count, s->d_row_count, sizeof(count), hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+    });
+    if (rc != GD_OK || !mask) return rc;
+    if (count != n_rows) return fail(GD_ERR_INVALID, "gd_set_learner_rows: n_rows differs from the number of true slots of the mask");
+    s->d.row_of_slot = s->d_row_of_slot;
+    s->d.slot_of_row = s->d_slot_of_row;
+    s->d.n_rows = count;
+    return GD_OK;
+}
+
+int gd_attach_packed_rows(gd_sim *s, float *out, int64_t out_bytes, int32_t only) {
+    if (!s || !out) return fail(GD_ERR_INVALID, "gd_attach_packed_rows: null argument (gd_attach_packed(sim, NULL, 0, 0) detaches)");
+    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, "gd_attach_packed_rows: no learner rows set (gd_set_learner_rows)");
+    const int64_t D = 6 + static_cast<int64_t>(s->A - 1) * 6 + GD_MAP_OBS_K * 13;
+    if (out_bytes < static_cast<int64_t>(s->d.n_rows) * D * 4) return fail(GD_ERR_INVALID, "gd_attach_packed_rows: output buffer too small");
+    if (!s->direct_pack_supported())
+        return fail(GD_ERR_UNSUPPORTED, "gd_attach_packed_rows: not available with disableClassicalObs or GPUDRIVE_LINEAR_LEGACY=1");
+    return guarded([&]() { s->attach_packed(out, only != 0, true); });
+}
+
+int gd_set_discrete_actions(gd_sim *s, const int64_t *indices, const float *table, int32_t n_actions) {
+    if (!s) return fail(GD_ERR_INVALID, "gd_set_discrete_actions: null sim");
+    if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
+        return fail(GD_ERR_UNSUPPORTED, "gd_set_discrete_actions: the State dynamics model has no discrete action space");
+    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, "gd_set_discrete_actions: no learner rows set (gd_set_learner_rows)");
+    if (n_actions < 0 || (s->d.n_rows > 0 && (!indices || !table)))
+        return fail(GD_ERR_INVALID, "gd_set_discrete_actions: bad argument");
+    return guarded([&]() {
+        gd::launch_discrete_actions(s->d, s->stream, indices, table, n_actions);
+        HIP_CHECK(hipGetLastError());
     });
 }
 
@@ -1276,6 +1348,8 @@ int gd_pack_observations_conditioned(gd_sim *s, const float *weights, float *out
     const int64_t R = 6 + static_cast<int64_t>(s->A - 1) * 6 + GD_MAP_OBS_K * 13 + 3;
     if (out_bytes < static_cast<int64_t>(s->W) * s->A * R * 4)
         return fail(GD_ERR_INVALID, "gd_pack_observations_conditioned: output buffer too small");
+    if (s->d.pack && s->d.pack_rows && s->d.pack_only)
+        return fail(GD_ERR_UNSUPPORTED, "gd_pack_observations_conditioned: learner rows are attached with only = 1: the raw rows are stale");
     return guarded([&]() {
         gd::launch_pack_obs_conditioned(s->d, s->stream, weights, out);
         HIP_CHECK(hipGetLastError());
@@ -1320,6 +1394,8 @@ int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_bu
     if (cfg->reward_type == GD_EPISODE_REWARD_CONDITIONED &&
         (cfg->condition_mode < GD_CONDITION_RANDOM || cfg->condition_mode > GD_CONDITION_FIXED))
         return fail(GD_ERR_INVALID, "gd_episode_step: unknown condition_mode");
+    if ((b->reward_rows || b->terminal_rows || b->truncated_rows || b->mask_rows) && !s->d.row_of_slot)
+        return fail(GD_ERR_INVALID, "gd_episode_step: flat outputs need learner rows (gd_set_learner_rows)");
     return guarded([&]() {
         HIP_CHECK(hipMemsetAsync(s->d.any_reset, 0, sizeof(int32_t), s->stream));
         gd::launch_episode_step(s->d, s->stream, *cfg, *b);
@@ -1445,6 +1521,14 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
         for (int w = 0; w < s->W; w++)
             for (int a = 0; a < n[static_cast<size_t>(w) * 2] && a < s->A; a++) c += f[static_cast<size_t>(w) * s->A + a] != 0;
         *out = c;
+        return GD_OK;
+    }
+    if (s && out && which == 45) {  // indices outside the table that gd_set_discrete_actions met, since the sim was created
+        unsigned long long v = 0;
+        (void)hipStreamSynchronize(s->stream);
+        if (hipMemcpy(&v, s->d.bad_actions, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(GD_ERR_DEVICE, "gd_stat: reading the action counter failed");
+        *out = static_cast<int64_t>(v);
         return GD_OK;
     }
     if (s && out && which == 21) {  // bounds audit of the rank path (engine.hpp GD_RANK_AUDIT): violations since the buffers exist

@@ -150,6 +150,14 @@ struct DevSim {
     // packed tensor; the padding agents' rows, written when the worlds are built, stay valid)
     float *pack;
     int pack_only;
+    // learner rows (gd_set_learner_rows): the true slots of a [W][A] mask in row-major order.  row_of_slot [W][A] holds a slot's
+    // row (-1: not a learner row), slot_of_row [n_rows] the inverse; both null while no rows are set.  pack_rows: the attached
+    // buffer is [n_rows][D] (gd_attach_packed_rows) and every writer of packed rows stores slot i's row at
+    // pack + row_of_slot[i] * D, nothing for slots without a row.
+    const int32_t *row_of_slot, *slot_of_row;
+    int n_rows;
+    int pack_rows;
+    unsigned long long *bad_actions;  // [1] indices outside the table that gd_set_discrete_actions met (gd_stat 45)
     unsigned long long *stat_skipped;  // [GD_SKIP_SLOTS] agents whose rows were left in place since the counters were last read (gd_stat 30
                                        // sums them): every wave adds to the slot of its own index -- one counter for all of them
                                        // serialises ten thousand atomics at one memory channel (measured: 150 us per launch)
@@ -204,6 +212,10 @@ void launch_set_log_actions(const DevSim &d, hipStream_t st, int t);
 void launch_episode_step(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b);  // episode.hip
 void launch_draw_weights(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b,
                          const int32_t *worlds, int n);  // episode.hip
+void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out);  // pack_obs.hip: learner rows only ([n_rows][D])
+void launch_learner_rows(hipStream_t st, const uint8_t *mask, size_t slots, int32_t *row_of_slot, int32_t *slot_of_row,
+                         int32_t *count);  // learner.hip
+void launch_discrete_actions(const DevSim &d, hipStream_t st, const int64_t *indices, const float *table, int n_actions);  // learner.hip
 void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out);  // pack_obs.hip
 
 }  // namespace gd

@@ -112,6 +112,15 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
     b.terminal_out[i] = terminal ? 1 : 0;
     b.truncated_out[i] = truncated ? 1 : 0;
     b.mask_out[i] = live ? 1 : 0;
+    if (d.row_of_slot) {  // the flat outputs of the learner rows (the engine refuses them without rows)
+        const int r = d.row_of_slot[i];
+        if (r >= 0) {
+            if (b.reward_rows) b.reward_rows[r] = reward;
+            if (b.terminal_rows) b.terminal_rows[r] = terminal ? 1 : 0;
+            if (b.truncated_rows) b.truncated_rows[r] = truncated ? 1 : 0;
+            if (b.mask_rows) b.mask_rows[r] = live ? 1 : 0;
+        }
+    }
 
     const int n_controlled = __syncthreads_count(controlled);
     const int n_terminal = __syncthreads_count(controlled && terminal);

@@ -295,7 +295,8 @@ __device__ __forceinline__ void partner_rows(const DevSim &d, int w, int n, int 
 // slot r - 1) in one contiguous, 16-byte aligned block: a wave takes an agent at a time, 64 rows per pass -- lane r computes row
 // r exactly as partner_rows does and normalises it, the block is laid out in LDS and leaves as whole 16-byte pieces.
 // `s_self`: the agents' raw self-observation columns 0..6 (speed, length, width, -, goal x, goal y, collided), [A][8].
-template <int A_T>
+// ROWS (gd_attach_packed_rows): the head goes to the agent's learner row (DevSim::row_of_slot), none for an agent without one.
+template <int A_T, bool ROWS>
 __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a, const float *s_px, const float *s_py,
                                             const float *s_qw, const float *s_qz, const float *s_speed, const float *s_len,
                                             const float *s_wid, const float *s_self) {
@@ -305,7 +306,13 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
     float *stage = s_head[wave];
     typedef float f4 __attribute__((ext_vector_type(4)));
     for (int ego = wave; ego < n; ego += STEP_THREADS / 64) {
-        float *out = d.pack + ((size_t)w * A_T + ego) * D;
+        size_t prow = (size_t)w * A_T + ego;
+        if (ROWS) {  // (wave-uniform)
+            const int r = d.row_of_slot[prow];
+            if (r < 0) continue;
+            prow = (size_t)r;
+        }
+        float *out = d.pack + prow * D;
 #pragma unroll
         for (int h = 0; h < A_T / 64; h++) {
             const int r = h * 64 + lane;
@@ -340,7 +347,7 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
     }
 }
 
-template <int A_T, bool MOVE>
+template <int A_T, bool MOVE, bool ROWS = false>
 __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     const int w = blockIdx.x, a = threadIdx.x;
     if (!MOVE && d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
@@ -744,7 +751,7 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
         partner_rows<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_hgt, s_etype, s_id, !MOVE || d.pose_skip == 0, s_stage);
     if (d.pack != nullptr && !d.p.disableClassicalObs) {
         __syncthreads();  // the agent threads' self columns
-        packed_head<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
+        packed_head<A_T, ROWS>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
     }
 #ifdef GD_CLOCKS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -797,6 +804,11 @@ static void launch_all(const DevSim &d, hipStream_t st, int which, bool move) {
     case KERNEL_RESET: hipLaunchKernelGGL(k_reset_worlds<A_T>, grid, block, 0, st, d); break;
     case KERNEL_PADDING: hipLaunchKernelGGL(k_init_padding_rows<A_T>, grid, block, 0, st, d); break;
     case KERNEL_STATE:
+        if (d.pack != nullptr && d.pack_rows) {  // gd_attach_packed_rows
+            if (move) hipLaunchKernelGGL((k_world_step<A_T, true, true>), grid, dim3(STEP_THREADS), 0, st, d);
+            else hipLaunchKernelGGL((k_world_step<A_T, false, true>), grid, dim3(STEP_THREADS), 0, st, d);
+            break;
+        }
         if (move) hipLaunchKernelGGL((k_world_step<A_T, true>), grid, dim3(STEP_THREADS), 0, st, d);
         else hipLaunchKernelGGL((k_world_step<A_T, false>), grid, dim3(STEP_THREADS), 0, st, d);
         break;

@@ -477,8 +477,10 @@ __device__ __forceinline__ void order_waves(const DevSim &d, int count, unsigned
 #endif
 // PACK (gd_attach_packed): the same rows also -- or only: DevSim::pack_only -- in the packed observation's 13 normalised columns
 // (pack_cols.hpp), three agents per workgroup instead of five (the 13-column block fills the same LDS).
+// ROWS (gd_attach_packed_rows): the packed rows go to the agent's learner row (DevSim::row_of_slot), none for an agent without one
+// (with pack_only such an agent writes nothing).
 template <bool PACK> struct RowsGeo { static constexpr int AB = PACK ? 3 : 5; };
-template <int A_T, bool PACK = false>
+template <int A_T, bool PACK = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_map_rows(DevSim d) {
     constexpr int ROWS_AB = RowsGeo<PACK>::AB;
     constexpr int U = GD_ROWS_PER_THREAD;  // entries per thread (256 apart): independent load chains in flight
@@ -522,9 +524,13 @@ __global__ __launch_bounds__(256) void k_map_rows(DevSim d) {
     const uint4 st = d.pose_stamp[wa];
     const bool same = d.pose_skip != 0 && st.x != 0xffffffffu && st.x == __float_as_uint(pose.x) && st.y == __float_as_uint(pose.y) &&
                       st.z == __float_as_uint(pose.z) && st.w == __float_as_uint(pose.w);
-    const bool on = act && a0 + al < agents && cnt >= 0 && !same;  // rows of padding agents are written at reset (k_init_padding_rows)
+    const int prow = ROWS ? d.row_of_slot[wa] : 0;
+    const bool on = act && a0 + al < agents && cnt >= 0 && !same &&  // rows of padding agents are written at reset (k_init_padding_rows)
+                    (!ROWS || prow >= 0 || !d.pack_only);
+    __shared__ int s_prow[ROWS ? ROWS_AB : 1];
     if (act && qf == 0) {
         s_on[al] = on ? 1 : 0;
+        if (ROWS) s_prow[al] = prow;
         if (a0 + al < agents && cnt >= 0 && same) atomicAdd(d.stat_skipped + (blockIdx.x & (GD_SKIP_SLOTS - 1)), 1ull);
     }
     // nothing to write for any agent of this workgroup (padding slots, agents that did not move): no gathers, no rows
@@ -591,6 +597,12 @@ __global__ __launch_bounds__(256) void k_map_rows(DevSim d) {
         static_assert(PACK_ROAD0 % 4 == 0 && PACK_D % 4 == 0, "whole 16-byte pieces");
         for (int q = threadIdx.x; q < RB * 13 / 4; q += 256) {
             const int ag = q / PPA13;
+            if (ROWS) {
+                if (s_on[ag] != 0 && s_prow[ag] >= 0)
+                    __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(s_rows + q * 4),
+                                                reinterpret_cast<f4 *>(d.pack + (size_t)s_prow[ag] * PACK_D + PACK_ROAD0 + (size_t)(q - ag * PPA13) * 4));
+                continue;
+            }
             if (s_on[ag] != 0)
                 __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(s_rows + q * 4),
                                             reinterpret_cast<f4 *>(d.pack + (a0 + ag) * (size_t)PACK_D + PACK_ROAD0 + (size_t)(q - ag * PPA13) * 4));
@@ -1061,7 +1073,9 @@ __device__ unsigned long long g_set_clk[8];
 #ifndef GD_SET_WPE
 #define GD_SET_WPE 4
 #endif
-template <int A_T, int NW, bool FUSE, bool PACK = false>
+// ROWS (gd_attach_packed_rows, with PACK): the packed rows go to the agent's learner row (DevSim::row_of_slot), none for an agent
+// without one (with pack_only such an agent selects but writes no rows).
+template <int A_T, int NW, bool FUSE, bool PACK = false, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GD_SET_WPE))) void k_map_obs_set(DevSim d) {
     static_assert(FUSE || !PACK, "the packed rows are written by the fused write-out");
     using S = SetSel<A_T>;
@@ -1465,6 +1479,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GD_SET_
         wave_sync();
         SET_PHASE(5);
         if (!FUSE) continue;  // k_map_rows writes the rows
+        const int prow = ROWS ? d.row_of_slot[i] : 0;  // (wave-uniform)
+        if (ROWS && prow < 0 && d.pack_only) continue;  // no learner row and no raw rows: nothing to write
         // ---- FUSE: the agent's K rows, written by the wave that selected them.  With several generations of workgroups
         // (many worlds) the HBM-bound row stores of one workgroup overlap the issue-bound selection of the others; when every
         // workgroup is resident at once the separate, fully occupied k_map_rows is the faster write-out (launch_map_obs) ----
@@ -1509,9 +1525,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GD_SET_
                     __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(rows_out + p * 576 + q * 4));
                 wave_sync();
             }
+            if (ROWS && prow < 0) continue;
             pack_road_row(raw, stage + lane * 13);
             wave_sync();
-            float *pout = d.pack + i * (size_t)PACK_D + PACK_ROAD0 + p * (64 * 13);
+            float *pout = d.pack + (ROWS ? (size_t)prow : i) * (size_t)PACK_D + PACK_ROAD0 + p * (64 * 13);
             for (int q = lane; q < nrows * 13 / 4; q += 64)
                 __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
             wave_sync();
@@ -1547,6 +1564,11 @@ void launch_map_obs(const DevSim &d, hipStream_t st, bool move) {
         if (d.set_group_count == 0) return;
         const dim3 grid(d.set_group_count);
         if (d.set_fused_rows) {
+            if (d.pack != nullptr && d.pack_rows) {
+                if (d.A == 64) hipLaunchKernelGGL((k_map_obs_set<64, 4, true, true, true>), grid, dim3(256), 0, st, d);
+                else hipLaunchKernelGGL((k_map_obs_set<128, 4, true, true, true>), grid, dim3(256), 0, st, d);
+                return;
+            }
             if (d.pack != nullptr) {
                 if (d.A == 64) hipLaunchKernelGGL((k_map_obs_set<64, 4, true, true>), grid, dim3(256), 0, st, d);
                 else hipLaunchKernelGGL((k_map_obs_set<128, 4, true, true>), grid, dim3(256), 0, st, d);
@@ -1568,6 +1590,11 @@ void launch_map_obs(const DevSim &d, hipStream_t st, bool move) {
     if (d.pack != nullptr) {
         constexpr int AB = RowsGeo<true>::AB;
         const dim3 pgrid((unsigned int)((agents + AB - 1) / AB + 7) / 8 * 8);
+        if (d.pack_rows) {
+            if (d.A == 64) hipLaunchKernelGGL((k_map_rows<64, true, true>), pgrid, dim3(256), 0, st, d);
+            else hipLaunchKernelGGL((k_map_rows<128, true, true>), pgrid, dim3(256), 0, st, d);
+            return;
+        }
         if (d.A == 64) hipLaunchKernelGGL((k_map_rows<64, true>), pgrid, dim3(256), 0, st, d);
         else hipLaunchKernelGGL((k_map_rows<128, true>), pgrid, dim3(256), 0, st, d);
         return;

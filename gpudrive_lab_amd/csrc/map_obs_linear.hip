@@ -69,7 +69,9 @@ constexpr int CU = GD_LIN_CU;  // cull: batches of 64 blocks requested together
 constexpr int PB = GD_LIN_PB;  // scan: passes (of 64 roads) requested together
 static_assert(64 % GD_LIN_BLK == 0, "whole blocks per pass");
 
-template <int A_T, bool PACK>
+// ROWS (gd_attach_packed_rows): the packed rows go to the agent's learner row (DevSim::row_of_slot); an agent without one
+// stores no packed rows, and with pack_only nothing at all, so it is not visited.
+template <int A_T, bool PACK, bool ROWS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE))) void k_map_obs_linear(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     const int tid = threadIdx.x;
@@ -107,6 +109,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE)
         if (p.e < 0) continue;  // filler entry (the XCD classes hold different numbers of agents)
         const int w = p.e >> 8;
         const size_t i = (size_t)w * A_T + (p.e & 255);
+        const int row = ROWS ? d.row_of_slot[i] : 0;        // (wave-uniform)
+        if (ROWS && row < 0 && d.pack_only) continue;       // no learner row and no raw rows: nothing to write
+        const bool pk = PACK && (!ROWS || row >= 0);        // packed rows stored for this agent
+        const size_t prow = ROWS ? (size_t)max(row, 0) : i;  // ... in this row of the packed buffer
         const int r0 = p.r0, R = p.r1 - p.r0;
         const float2 *rxy = d.road_xy + r0;
         const int NB = (R + GD_LIN_BLK - 1) / GD_LIN_BLK;
@@ -232,10 +238,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE)
                     }
                     wave_sync();
                 }
-                if (PACK) {  // (gd_attach_packed) the same rows in the packed observation's 13 normalised columns (pack_cols.hpp)
+                if (pk) {  // (gd_attach_packed) the same rows in the packed observation's 13 normalised columns (pack_cols.hpp)
                     pack_road_row(raw, stage + lane * 13);
                     wave_sync();
-                    float *pout = d.pack + i * (size_t)PACK_D + PACK_ROAD0 + pz * (64 * 13);
+                    float *pout = d.pack + prow * (size_t)PACK_D + PACK_ROAD0 + pz * (64 * 13);
                     for (int q = lane; q < nrows * 13 / 4; q += 64)
                         __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
                     wave_sync();
@@ -261,6 +267,11 @@ void launch_map_obs_linear(const DevSim &d0, hipStream_t st, bool move) {
     }
     if (d.lin_blocks == 0) return;
     const dim3 grid(d.lin_blocks);
+    if (d.pack != nullptr && d.pack_rows) {
+        if (d.A == 64) hipLaunchKernelGGL((k_map_obs_linear<64, true, true>), grid, dim3(256), 0, st, d);
+        else hipLaunchKernelGGL((k_map_obs_linear<128, true, true>), grid, dim3(256), 0, st, d);
+        return;
+    }
     if (d.pack != nullptr) {
         if (d.A == 64) hipLaunchKernelGGL((k_map_obs_linear<64, true>), grid, dim3(256), 0, st, d);
         else hipLaunchKernelGGL((k_map_obs_linear<128, true>), grid, dim3(256), 0, st, d);

@@ -34,18 +34,20 @@ __device__ __forceinline__ float pack_element(const float *self, const float *pa
     return pack_road_col(road[k * 9 + (c < 6 ? c : 6)], c);
 }
 
-template <int A_T>
+// ROWS (gd_attach_packed_rows): one workgroup per learner row, blockIdx.x; out is [n_rows][D] and row r is slot slot_of_row[r].
+template <int A_T, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_pack_obs(DevSim d, float *out) {
     constexpr int D = 6 + (A_T - 1) * 6 + K * 13;
     static_assert(D % 4 == 0 && (K * 9) % 4 == 0, "rows are whole float4 groups");
     constexpr int Q = D / 4, NP = (A_T - 1) * 9, NR = K * 9;
-    constexpr int GROUP = A_T / GD_PACK_PARTS;  // blockIdx.y: a part of the world's agent slots
+    constexpr int GROUP = ROWS ? 1 : A_T / GD_PACK_PARTS;  // blockIdx.y: a part of the world's agent slots
     __shared__ float s_self[8];
     __shared__ float s_partner[NP];
     __shared__ __attribute__((aligned(16))) float s_road[NR];
     const int w = blockIdx.x, tid = threadIdx.x;
     for (int al = 0; al < GROUP; al++) {
-        const size_t agent = (size_t)w * A_T + blockIdx.y * GROUP + al;
+        const size_t agent = ROWS ? (size_t)d.slot_of_row[w] : (size_t)w * A_T + blockIdx.y * GROUP + al;
+        const size_t orow = ROWS ? (size_t)w : agent;
         if (tid < 8) s_self[tid] = d.self_obs[agent * 8 + tid];
         for (int t = tid; t < NP; t += 256) s_partner[t] = d.partner[agent * NP + t];
         const float4 *rsrc = reinterpret_cast<const float4 *>(d.agent_map + agent * NR);
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void k_pack_obs(DevSim d, float *out) {
             v.w = pack_element<A_T>(s_self, s_partner, s_road, 4 * q + 3);
             typedef float f4 __attribute__((ext_vector_type(4)));
             const f4 vv = {v.x, v.y, v.z, v.w};
-            __builtin_nontemporal_store(vv, reinterpret_cast<f4 *>(out + agent * D) + q);  // 782 MB written once: keep it out of the caches
+            __builtin_nontemporal_store(vv, reinterpret_cast<f4 *>(out + orow * D) + q);  // 782 MB written once: keep it out of the caches
         }
         __syncthreads();
     }
@@ -220,8 +222,14 @@ void launch_pack_obs(const DevSim &d, hipStream_t st, float *out) {
     else hipLaunchKernelGGL(k_pack_obs<128>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, out);
 }
 
+void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out) {
+    if (d.n_rows == 0) return;
+    if (d.A == 64) hipLaunchKernelGGL((k_pack_obs<64, true>), dim3(d.n_rows), dim3(256), 0, st, d, out);
+    else hipLaunchKernelGGL((k_pack_obs<128, true>), dim3(d.n_rows), dim3(256), 0, st, d, out);
+}
+
 void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out) {
-    if (d.pack) {  // the attached buffer is current (its raw rows may not be)
+    if (d.pack && !d.pack_rows) {  // the attached buffer is current (its raw rows may not be)
         const size_t D = 6 + (size_t)(d.A - 1) * 6 + K * 13, groups = (size_t)d.W * d.A * (D + 3) / 4;
         const dim3 grid((unsigned)((groups + 255) / 256));
         if (d.A == 64) hipLaunchKernelGGL(k_pack_relayout<64>, grid, dim3(256), 0, st, d.pack, weights, out, groups);

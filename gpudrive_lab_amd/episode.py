@@ -84,7 +84,7 @@ class EpisodeTracker:
         self.world_stats = torch.zeros((W, _capi.EPISODE_STATS), dtype=torch.float32, device=dev)
         self._cmask_u8 = self.controlled_agent_mask.to(torch.uint8).contiguous()
         p = lambda t: C.c_void_p(t.data_ptr())
-        self._bufs = _capi.GdEpisodeBuffers(
+        self._bufs = _capi.GdEpisodeBuffersRows(
             p(self._cmask_u8), p(self.agent_episode_returns), p(self.episode_lengths), p(self.collided_in_episode),
             p(self.offroad_in_episode), p(self.live_agent_mask), p(self.rewards), p(self.terminals), p(self.truncations),
             p(self.masks), p(self.done_worlds), p(self.stats), p(self.world_stats))

@@ -1,0 +1,105 @@
+"""The learner's step on the device: discrete action indices in, flat per-agent tensors out.
+
+`DeviceLearnerEnv` is the shape of the reference's PPO environment (gpudrive/env/env_puffer.py:235-403): `step()` takes one
+discrete action index per controlled agent and returns `obs[controlled_agent_mask]` as [N, D] with the rewards, terminals,
+truncations and masks of the same N rows.  Here nothing is gathered after the fact: the engine's learner rows
+(`SimManager.set_learner_rows`) map every controlled slot to its row once, and then
+
+  - the indices are decoded through the action table into the action tensor by one kernel (`set_discrete_actions`),
+  - the kernels that produce the packed observation write each controlled agent's row straight into the [N, D] buffer
+    (`direct_pack_rows`), and no packed row for any other slot,
+  - the episode kernel writes the four flat outputs through the same map (`EpisodeTracker` with learner rows).
+
+One step is therefore: indices in, flat tensors out, no host synchronisation and nothing sized by padding slots.  The rows are
+fixed until `resample()`; the tensors returned are the same buffers every step (overwritten in place)."""
+from itertools import product
+
+import torch
+
+from .episode import EpisodeTracker
+from .harness import default_action_values
+
+_DYNAMICS_NAMES = {0: "classic", 1: "bicycle", 2: "delta_local", 3: "state"}
+
+
+def action_table(dynamics_model):
+    """The discrete action table of `dynamics_model` ("classic", "bicycle" or "delta_local"): a float32 [n, 3] tensor whose
+    row k is action index k, in `itertools.product(first, second, third)` order (reference _set_discrete_action_space,
+    gpudrive/env/env_torch.py:666-724): 7 x 13 x 1 = 91 rows for classic / bicycle, 20^3 = 8000 for delta_local.
+    ValueError for "state", which has no discrete action space."""
+    if dynamics_model == "state":
+        raise ValueError("action_table: the state dynamics model has no discrete action space")
+    a1, a2, a3 = default_action_values(dynamics_model)
+    return torch.tensor([[v1.item(), v2.item(), v3.item()] for v1, v2, v3 in product(a1, a2, a3)], dtype=torch.float32)
+
+
+_default_table = action_table  # (the constructor's argument of the same name shadows it)
+
+
+class DeviceLearnerEnv:
+    def __init__(self, sim, action_table=None, only=True, **tracker_kwargs):
+        """sim: a SimManager.  action_table: float32 [n, 3] (default: `action_table()` of the simulator's dynamics model).
+        only: the raw partner / road rows are not written any more (nothing but the learner rows).  tracker_kwargs go to
+        `EpisodeTracker` (reward weights, reward_type, auto_reset, ...); "reward_conditioned" is not supported here (its
+        [N, D + 3] layout is a separate feature).  Arguments are checked before anything reaches the device (ValueError)."""
+        if tracker_kwargs.get("reward_type") == "reward_conditioned":
+            raise ValueError("DeviceLearnerEnv: reward_type='reward_conditioned' ([N, D + 3] rows) is not supported; "
+                             "use EpisodeTracker with packed_observations(reward_weights=...)")
+        if action_table is not None:
+            if not isinstance(action_table, torch.Tensor) or action_table.dim() != 2 or action_table.shape[1] != 3 \
+                    or action_table.shape[0] < 1:
+                raise ValueError("DeviceLearnerEnv: action_table must be a [n, 3] tensor, got %s"
+                                 % (tuple(action_table.shape) if isinstance(action_table, torch.Tensor) else type(action_table),))
+        else:
+            action_table = _default_table(_DYNAMICS_NAMES[int(sim._params.dynamicsModel)])
+        self.sim = sim
+        self.only = bool(only)
+        self._tracker_kwargs = dict(tracker_kwargs)
+        self.table = action_table.to(device=sim._device, dtype=torch.float32).contiguous()
+        self._setup()
+
+    def _setup(self):
+        """Tracker (it captures the controlled mask), learner rows from that mask, the row buffer, the flat outputs."""
+        sim = self.sim
+        self.tracker = EpisodeTracker(sim, **self._tracker_kwargs)
+        self.controlled_agent_mask = self.tracker.controlled_agent_mask
+        n = sim.set_learner_rows(self.controlled_agent_mask)  # the one host synchronisation, at setup
+        self.num_agents = n
+        self.obs = sim.direct_pack_rows(only=self.only)
+        dev = self.table.device
+        m = max(n, 1)  # (real allocations for n = 0)
+        self.rewards = torch.zeros((m,), dtype=torch.float32, device=dev)[:n]
+        self.terminals = torch.zeros((m,), dtype=torch.bool, device=dev)[:n]
+        self.truncations = torch.zeros((m,), dtype=torch.bool, device=dev)[:n]
+        self.masks = torch.zeros((m,), dtype=torch.bool, device=dev)[:n]
+        b = self.tracker._bufs
+        b.reward_rows, b.terminal_rows = self.rewards.data_ptr(), self.terminals.data_ptr()
+        b.truncated_rows, b.mask_rows = self.truncations.data_ptr(), self.masks.data_ptr()
+
+    def reset(self):
+        """Empty the episode storage (PufferGPUDrive.reset, env_puffer.py:200-233) and return the [N, D] observations of
+        the current state."""
+        t = self.tracker
+        for x in (t.agent_episode_returns, t.episode_lengths, t.collided_in_episode, t.offroad_in_episode):
+            x.zero_()
+        t.live_agent_mask.fill_(True)
+        return self.obs
+
+    def step(self, actions):
+        """actions: int64 [N] device tensor of action indices.  Decodes them into the action tensor, steps the simulator,
+        runs the episode bookkeeping (finished worlds reset on the device) and returns
+        (obs [N, D], rewards [N], terminals [N], truncations [N], masks [N]).  No host synchronisation."""
+        self.sim.set_discrete_actions(actions, self.table)
+        self.tracker.step()
+        return self.obs, self.rewards, self.terminals, self.truncations, self.masks
+
+    def pop_stats(self):
+        return self.tracker.pop_stats()
+
+    def resample(self, scenes):
+        """A new batch of scenes (the reference's resample_scenario_batch, env_puffer.py:438-453): set_maps, the controlled
+        mask derived again, the learner rows set from it, the row buffer attached again, the storage emptied.  Returns the
+        [N, D] observations of the new worlds."""
+        self.sim.set_maps(scenes)
+        self._setup()
+        return self.reset()

@@ -364,14 +364,82 @@ class SimManager:
             return False
         _capi.check(rc, "gd_attach_packed")
         self._packed = self._direct = out
+        self._direct_rows = None  # (gd_attach_packed replaced a learner-row buffer)
         return True
 
     def direct_pack_off(self):
-        """Back to the raw tensors + the second-pass `packed_observations()`."""
-        if getattr(self, "_direct", None) is not None:
+        """Back to the raw tensors + the second-pass `packed_observations()` (detaches a `direct_pack_rows()` buffer too)."""
+        if getattr(self, "_direct", None) is not None or getattr(self, "_direct_rows", None) is not None:
             self._bind_stream()
             _capi.check(self._L.gd_attach_packed(self._h, None, 0, 0), "gd_attach_packed")
             self._direct = None
+            self._direct_rows = None
+
+    # ---- learner rows: the flat, controlled-agent-only view of the reference's PPO loop (env_puffer.py:235-403) ----
+    def set_learner_rows(self, mask=None):
+        """Extension: the learner rows are the true slots of `mask` ([W, A] bool device tensor; default
+        `controlled_state_tensor() == 1`) in row-major order -- the rows `tensor[mask]` yields.  They index what
+        `direct_pack_rows()`, `set_discrete_actions()` and the tracker's flat outputs work in, and stay fixed until the next
+        call (set_maps / deleteAgents / reset leave them; set them again after set_maps).  Detaches a `direct_pack_rows()`
+        buffer.  Returns the number of rows -- the one host synchronisation of the learner path, at setup."""
+        import torch
+        if mask is None:
+            mask = self.controlled_state_tensor().to_torch().squeeze(-1) == 1
+        assert mask.is_cuda and tuple(mask.shape) == (self._W, self._A), "mask: a [W, A] device tensor"
+        m = mask.to(torch.uint8).contiguous()
+        n = int(m.sum().item())
+        self._bind_stream()
+        _capi.check(self._L.gd_set_learner_rows(self._h, m.data_ptr(), n), "gd_set_learner_rows")
+        self._direct_rows = None
+        self._learner_mask = mask.to(torch.bool).clone()
+        self._n_rows = n
+        return n
+
+    def clear_learner_rows(self):
+        """Extension: no learner rows any more (detaches a `direct_pack_rows()` buffer)."""
+        self._bind_stream()
+        _capi.check(self._L.gd_set_learner_rows(self._h, None, 0), "gd_set_learner_rows")
+        self._direct_rows = None
+        self._learner_mask = None
+        self._n_rows = None
+
+    def direct_pack_rows(self, only=True, out=None):
+        """Extension: `direct_pack()` for the learner rows only.  From now on every step / reset pass writes the packed row
+        of learner row r into row r of the returned [n_rows, D] tensor -- `packed_observations()[mask]`, bit for bit -- and
+        no packed row for any other slot.  `only=True`: the raw partner / road rows are not written either, and
+        `packed_observations()` raises NotImplementedError while the buffer is attached.  Replaces a `direct_pack()`
+        buffer; `direct_pack_off()` detaches it."""
+        import torch
+        n = getattr(self, "_n_rows", None)
+        if n is None:
+            raise ValueError("direct_pack_rows: set the learner rows first (set_learner_rows)")
+        D = 6 + (self._A - 1) * 6 + kMaxAgentMapObservationsCount * 13
+        if out is None:
+            out = torch.empty((max(n, 1), D), dtype=torch.float32, device=self._device)  # (a real allocation for n = 0)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= n * D and out.numel() > 0
+        self._bind_stream()
+        _capi.check(self._L.gd_attach_packed_rows(self._h, out.data_ptr(), out.numel() * 4, 1 if only else 0),
+                    "gd_attach_packed_rows")
+        if getattr(self, "_direct", None) is not None:  # replaced
+            self._packed = self._direct = None
+        self._direct_rows = out
+        return out.view(-1)[:n * D].view(n, D)
+
+    def set_discrete_actions(self, indices, table):
+        """Extension: action[:, :, :3] of every learner row's slot = table[indices] (env_torch.py:615-664), on the device.
+        indices: int64 [n_rows] device tensor; table: float32 [n_actions, 3] device tensor.  Other slots keep their
+        actions; an index outside the table leaves its row's action unchanged and is counted (stat(45)).  No host
+        synchronisation."""
+        import torch
+        n = getattr(self, "_n_rows", None)
+        if n is None:
+            raise ValueError("set_discrete_actions: set the learner rows first (set_learner_rows)")
+        assert indices.is_cuda and indices.dtype == torch.int64 and indices.is_contiguous() and tuple(indices.shape) == (n,)
+        assert (table.is_cuda and table.dtype == torch.float32 and table.is_contiguous() and table.dim() == 2
+                and table.shape[1] == 3)
+        self._bind_stream()
+        _capi.check(self._L.gd_set_discrete_actions(self._h, indices.data_ptr(), table.data_ptr(), int(table.shape[0])),
+                    "gd_set_discrete_actions")
 
     def expert_actions(self):
         """Extension: what `GPUDriveTorchEnv.get_expert_actions()` returns (reference

@@ -171,6 +171,31 @@ int gd_attach_packed(gd_sim *sim, float *out, int64_t out_bytes, int32_t only);
  * [W][A][3] f32 (EpisodeTracker.reward_weights_tensor).  Written from the raw tensors, or -- while a buffer is attached with
  * gd_attach_packed -- by a copy of that buffer that inserts the three columns (with only != 0 the raw rows are stale). */
 int gd_pack_observations_conditioned(gd_sim *sim, const float *weights, float *out, int64_t out_bytes);
+/* Learner rows: the flat, controlled-agent-only view of the reference's PPO loop (gpudrive/env/env_puffer.py:235-403), which
+ * hands the policy obs[controlled_agent_mask] as [N, D] and takes one discrete action index per row.  `mask` is a device
+ * [W][A] bool (uint8); the learner rows are its true slots in row-major (world, agent) order -- the order of torch's boolean
+ * indexing.  The engine builds the maps slot -> row and row -> slot on the device, reads the row count back once (a setup call:
+ * it synchronises) and returns GD_ERR_INVALID, with no rows set, when it differs from n_rows.  mask = NULL clears the rows;
+ * n_rows = 0 is legal.  The map stays as it is until the next call: set_maps, gd_delete_agents and resets do not change it
+ * (the reference captures controlled_agent_mask once and re-derives it in resample_scenario_batch, env_puffer.py:438-453;
+ * after gd_set_maps the caller sets the rows again).  Setting or clearing the rows detaches a gd_attach_packed_rows buffer. */
+int gd_set_learner_rows(gd_sim *sim, const uint8_t *mask, int32_t n_rows);
+/* gd_attach_packed for the learner rows only: out is [n_rows][D], D as above, and from this call on every step / reset pass
+ * writes learner row r at out + r * D -- bit-identical to row slot_of_row[r] of gd_pack_observations on the same state -- and
+ * no packed row for any other slot (with only != 0 the other slots' road rows are not even selected by the linear scan).
+ * One packed buffer exists at a time: this call and gd_attach_packed replace each other, gd_attach_packed(sim, NULL, 0, 0)
+ * detaches either kind, and gd_set_learner_rows detaches this kind.  While attached, gd_pack_observations and
+ * gd_pack_observations_conditioned work from the raw tensors with only = 0 and return GD_ERR_UNSUPPORTED with only != 0 (the
+ * raw rows are stale, and there is no [W][A][D] buffer to copy from).  GD_ERR_INVALID without learner rows;
+ * GD_ERR_UNSUPPORTED where gd_attach_packed is. */
+int gd_attach_packed_rows(gd_sim *sim, float *out, int64_t out_bytes, int32_t only);
+/* Discrete actions decoded on the device: action[slot_of_row[r]][0..3) = table[indices[r]] for every learner row r, what
+ * _apply_actions + _copy_actions_to_simulator do with a [N] index tensor for classic, bicycle and delta_local
+ * (gpudrive/env/env_torch.py:615-664).  indices: device int64 [n_rows]; table: device f32 [n_actions][3].  Other slots are
+ * left untouched (the simulator ignores the actions of uncontrolled agents).  An index outside [0, n_actions) leaves its row's
+ * action as it was and is counted (gd_stat 45).  Launched on the simulator's stream, outside the captured step graph.
+ * GD_ERR_UNSUPPORTED for the State dynamics model (no discrete space in the reference); GD_ERR_INVALID without learner rows. */
+int gd_set_discrete_actions(gd_sim *sim, const int64_t *indices, const float *table, int32_t n_actions);
 /* Expert-action export: GPUDriveTorchEnv.get_expert_actions()
  * (gpudrive/env/env_torch.py:1445-1509 over gpudrive/datatypes/trajectory.py:24-41) in one pass over the
  * expert trajectory rows.  Device pointers, any of them may be NULL:
@@ -238,6 +263,11 @@ typedef struct gd_episode_buffers {
     /* appended; required by GD_EPISODE_REWARD_CONDITIONED only */
     float *reward_weights;  /* [W][A][3] collision, goal_achieved, off_road weights of every agent slot */
     int32_t *weight_draws;  /* [W] draws of each world's weights so far (the generator's draw counter) */
+    /* appended; optional flat outputs through the learner rows (gd_set_learner_rows), [n_rows] each: reward_out[mask],
+     * terminal_out[mask], truncated_out[mask], mask_out[mask] bit for bit.  Any of them non-NULL without learner rows is
+     * GD_ERR_INVALID. */
+    float *reward_rows;
+    uint8_t *terminal_rows, *truncated_rows, *mask_rows;
 } gd_episode_buffers;
 /* With GD_EPISODE_REWARD_CONDITIONED a finished world's reward_weights are redrawn in cfg->condition_mode by the same kernel,
  * before the reset pass, so the observation of the reset world carries its new weights (env_puffer.py:375-390). */
@@ -267,7 +297,8 @@ int gd_attach_bev(gd_sim *sim, float *bev);
  * all since the last read.  Every build: 21 = accesses the rank replay's bounds audit found out of range since its buffers
  * exist (must stay 0), 30 = agents whose road rows were left in place because their pose bits had not changed, since the last
  * read, 31 = BEV rasters painted by the last pass that rasterised (the others could not have changed and were left in
- * place), 44 = agents whose LiDAR returns the last pass marked for tracing (likewise).  Otherwise GD_ERR_INVALID. */
+ * place), 44 = agents whose LiDAR returns the last pass marked for tracing (likewise), 45 = action indices outside the table
+ * that gd_set_discrete_actions met since the simulator was created.  Otherwise GD_ERR_INVALID. */
 int gd_stat(gd_sim *sim, int32_t which, int64_t *out);
 
 /* Timing hooks for the bench: HIP events around the named kernel on the engine's stream (a fixed ring of event pairs,
