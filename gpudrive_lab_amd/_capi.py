@@ -74,6 +74,9 @@ EPISODE_STAT_NAMES = ("episodes", "finished_agents", "return_sum", "off_road_age
 
 EPISODE_REWARD_WEIGHTED, EPISODE_REWARD_SPARSE, EPISODE_REWARD_CONDITIONED, EPISODE_REWARD_LOG_DISTANCE = range(4)
 CONDITION_RANDOM, CONDITION_PRESET, CONDITION_FIXED = range(3)
+WARMUP_RESET_WORLDS, WARMUP_ALL_WORLDS = range(2)
+INIT_STEPS_MAX = 90  # the expert trajectory has 91 steps
+STAT_WARMED_WORLDS = 46  # gd_stat: worlds the warm-up of the device auto-reset advanced
 
 
 class GdEpisodeConfig(C.Structure):
@@ -101,7 +104,7 @@ SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_episode_step", "gd_sync",
-    "gd_pack_observations_conditioned", "gd_episode_draw_weights",
+    "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_set_discrete_actions",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
     "gd_kernel_timing_enable", "gd_kernel_timing_read", "gd_debug_get_state", "gd_debug_set_state", "gd_debug_road_path",
@@ -156,6 +159,7 @@ def lib():
     L.gd_episode_step.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffersRows)]
     L.gd_episode_draw_weights.argtypes = [C.c_void_p, C.POINTER(GdEpisodeConfig), C.POINTER(GdEpisodeBuffersRows),
                                           C.POINTER(C.c_int32), C.c_int32]
+    L.gd_episode_set_warmup.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.gd_set_learner_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_attach_packed_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
     L.gd_set_discrete_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]

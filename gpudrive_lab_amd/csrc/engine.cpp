@@ -1170,6 +1170,10 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         s->d_row_count = s->alloc_internal<int32_t>(1);
         d.bad_actions = s->alloc_internal<unsigned long long>(1);
         d.blk_off = s->alloc_internal<int32_t>(W + 1);
+        d.warm_k = 0;
+        d.warm_all = 0;
+        d.warm_flags = s->alloc_internal<int32_t>(W);
+        d.warm_count = s->alloc_internal<unsigned long long>(1);
         // rank replay of the reference-order selection (map_obs_rank.hip): a fallback group is one workgroup of k_map_obs.
         // Its buffers (7.4 KB per agent slot) are allocated when a batch first takes the path (rebuild_worlds).
         d.rk_on = 0;
@@ -1404,6 +1408,18 @@ int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_bu
     });
 }
 
+int gd_episode_set_warmup(gd_sim *s, int32_t init_steps, int32_t scope) {
+    if (init_steps < 0 || init_steps >= GD_EPISODE_LEN)
+        return fail(GD_ERR_INVALID, "gd_episode_set_warmup: init_steps must be in [0, 90] (the expert trajectory has 91 steps)");
+    if (scope != GD_WARMUP_RESET_WORLDS && scope != GD_WARMUP_ALL_WORLDS)
+        return fail(GD_ERR_INVALID, "gd_episode_set_warmup: unknown scope (GD_WARMUP_RESET_WORLDS or GD_WARMUP_ALL_WORLDS)");
+    if (!s) return fail(GD_ERR_INVALID, "gd_episode_set_warmup: null sim");
+    // Only the gated reset pass reads these fields; the captured step graph holds step passes, which never do, so it stays.
+    s->d.warm_k = init_steps;
+    s->d.warm_all = scope == GD_WARMUP_ALL_WORLDS ? 1 : 0;
+    return GD_OK;
+}
+
 int gd_episode_draw_weights(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b, const int32_t *worlds,
                             int32_t n) {
     if (!s || !cfg || !b || !b->reward_weights || !b->weight_draws || (worlds && n < 0))
@@ -1528,6 +1544,14 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
         (void)hipStreamSynchronize(s->stream);
         if (hipMemcpy(&v, s->d.bad_actions, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
             return fail(GD_ERR_DEVICE, "gd_stat: reading the action counter failed");
+        *out = static_cast<int64_t>(v);
+        return GD_OK;
+    }
+    if (s && out && which == 46) {  // worlds the warm-up of the device auto-reset advanced, since the sim was created
+        unsigned long long v = 0;
+        (void)hipStreamSynchronize(s->stream);
+        if (hipMemcpy(&v, s->d.warm_count, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(GD_ERR_DEVICE, "gd_stat: reading the warm-up counter failed");
         *out = static_cast<int64_t>(v);
         return GD_OK;
     }

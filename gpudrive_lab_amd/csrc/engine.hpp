@@ -198,6 +198,13 @@ struct DevSim {
     uint16_t *cp_road;     // [2][W][A][NCP]
     float *cp_T;           // [2][W][A][NCP]
     float4 *cp_hdr;        // [2][W][A]
+    // warm-up of the device auto-reset (gd_episode_set_warmup): warm_k > 0 makes the gated reset pass launch the warm-up kernel
+    // (k_world_step in WS_WARMUP mode: the reset of the flagged worlds, the reset pass's state phases, then warm_k state steps
+    // with the logged actions) in place of k_reset_worlds, and its state kernel skip the collision re-run of warmed worlds
+    int warm_k;               // init_steps, 0..90 (0: no warm-up, today's reset pass)
+    int warm_all;             // 1: GD_WARMUP_ALL_WORLDS (every world is warmed when any was flagged), 0: the flagged worlds only
+    int32_t *warm_flags;      // [W] 1: the last warm-up launch that ran advanced this world
+    unsigned long long *warm_count;  // [1] worlds warmed since the simulator was created (gd_stat 46)
 };
 
 void launch_kernel(const DevSim &d, hipStream_t st, int which, bool move);

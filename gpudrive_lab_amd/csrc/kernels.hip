@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
+#include "expert.hpp"
 #include "gd_math.hpp"
 #include "map_rows.hpp"
 #include "pack_cols.hpp"
@@ -101,37 +102,40 @@ __device__ __forceinline__ void forward_state(const float *act, Body &b) {  // :
 // ------------------------------------------------------------------------------------------
 // reset of flagged worlds: resetAgent / resetAgentInterface, src/level_gen.cpp:23-54
 // ------------------------------------------------------------------------------------------
+// agent slot i (< the world's agent count) back to its state at t = 0
+__device__ __forceinline__ void reset_agent(const DevSim &d, size_t i) {
+    const float *t = d.traj + i * TRAJ;
+    d.px[i] = t[0];
+    d.py[i] = t[1];
+    d.pz[i] = 1.f;
+    const float heading = t[4 * 91];
+    d.qw[i] = p_cos(heading / 2.f);
+    d.qz[i] = p_sin(heading / 2.f);
+    const bool is_static = d.resp[i] == RESP_Static;
+    d.vx[i] = is_static ? 0.f : t[2 * 91 + 0];
+    d.vy[i] = is_static ? 0.f : t[2 * 91 + 1];
+    d.vz[i] = 0.f;
+    float *act = d.action + i * 10;
+#pragma unroll
+    for (int k = 0; k < 10; k++) act[k] = 0.f;
+    if (d.p.dynamicsModel == GD_DYNAMICS_STATE) act[2] = 1.f;  // getZeroAction, level_gen.hpp:31-34
+    d.steps[i] = EPISODE;
+    d.done[i] = 0;
+    d.reward[i] = 0.f;
+    int32_t *info = d.info + i * 5;
+    info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0;
+    info[4] = d.etype[i];
+    d.resp_export[i] = d.resp[i];
+    d.collided[i] = 0;
+}
+
 template <int A_T>
 __global__ __launch_bounds__(A_T) void k_reset_worlds(DevSim d) {
     const int w = blockIdx.x, a = threadIdx.x;
     if (d.reset_flags[w] == 0) return;
     const int n = d.shape[w * 2 + 0];
     const size_t i = (size_t)w * A_T + a;
-    if (a < n) {
-        const float *t = d.traj + i * TRAJ;
-        d.px[i] = t[0];
-        d.py[i] = t[1];
-        d.pz[i] = 1.f;
-        const float heading = t[4 * 91];
-        d.qw[i] = p_cos(heading / 2.f);
-        d.qz[i] = p_sin(heading / 2.f);
-        const bool is_static = d.resp[i] == RESP_Static;
-        d.vx[i] = is_static ? 0.f : t[2 * 91 + 0];
-        d.vy[i] = is_static ? 0.f : t[2 * 91 + 1];
-        d.vz[i] = 0.f;
-        float *act = d.action + i * 10;
-#pragma unroll
-        for (int k = 0; k < 10; k++) act[k] = 0.f;
-        if (d.p.dynamicsModel == GD_DYNAMICS_STATE) act[2] = 1.f;  // getZeroAction, level_gen.hpp:31-34
-        d.steps[i] = EPISODE;
-        d.done[i] = 0;
-        d.reward[i] = 0.f;
-        int32_t *info = d.info + i * 5;
-        info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0;
-        info[4] = d.etype[i];
-        d.resp_export[i] = d.resp[i];
-        d.collided[i] = 0;
-    }
+    if (a < n) reset_agent(d, i);
     __syncthreads();
     if (a == 0) d.reset_flags[w] = 0;
 }
@@ -347,8 +351,23 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
     }
 }
 
-template <int A_T, bool MOVE, bool ROWS = false>
+// What a launch of k_world_step does (MODE):
+//   WS_STEP          a step (MOVE) or the state kernel of a reset pass (!MOVE): the state phases, then the self / absolute /
+//                    partner observations and the head of the packed observation.
+//   WS_WARMUP        the warm-up of the device auto-reset (gd_episode_set_warmup), launched by the gated reset pass in place of
+//                    k_reset_worlds.  For every world it warms -- the flagged ones, or all of them with GD_WARMUP_ALL_WORLDS --
+//                    the reset of a flagged world, the reset pass's state phases (iteration -1: no movement, the collision with
+//                    the step counter as it is), then warm_k steps of the state phases (iteration t: every agent slot's logged
+//                    action of time t, what k_set_log_actions writes).  No observation phase: the reset pass's kernels that
+//                    follow write every observation of the state it leaves (a !MOVE pass rewrites every agent whose pose moved).
+//   WS_AFTER_WARMUP  the state kernel of that reset pass: a warmed world does not re-run its collision phase (the host
+//                    composition gd_reset + gd_advance_log_playback ends with the last warm-up step's); every other world is
+//                    as in WS_STEP.
+enum { WS_STEP = 0, WS_WARMUP = 1, WS_AFTER_WARMUP = 2 };
+
+template <int A_T, bool MOVE, bool ROWS = false, int MODE = WS_STEP>
 __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
+    constexpr bool OBS = MODE != WS_WARMUP;  // the observation phases
     const int w = blockIdx.x, a = threadIdx.x;
     if (!MOVE && d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     const int n = d.shape[w * 2 + 0];
@@ -382,381 +401,412 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     unsigned long long clk_prev = __builtin_amdgcn_s_memtime();
     if (a == 0) atomicAdd(&g_step_clk[7], 1ull);
 #endif
-    Body b{};
-    int collided = 0, done = 0, resp = RESP_Static, controlled = 0, etype = 0;
-    uint32_t steps = 0;
-    int32_t info0 = 0, info1 = 0, info2 = 0, info3 = 0;
-    float sc0 = 0.f, sc1 = 0.f, length = 0.f, width = 0.f, height = 0.f, gx = 0.f, gy = 0.f;
-
-    // (every agent slot of the world is readable: the loads do not wait for the world's agent count)
-    if (a < A_T) {
-        b.px = d.px[i]; b.py = d.py[i]; b.pz = d.pz[i];
-        b.qw = d.qw[i]; b.qz = d.qz[i];
-        b.vx = d.vx[i]; b.vy = d.vy[i]; b.vz = d.vz[i];
-        collided = d.collided[i];
-        done = d.done[i];
-        resp = d.resp[i];
-        controlled = d.controlled[i];
-        etype = d.etype[i];
-        steps = d.steps[i];
-        const int32_t *info = d.info + i * 5;
-        info0 = info[0]; info1 = info[1]; info2 = info[2]; info3 = info[3];
-        sc0 = d.sc0[i]; sc1 = d.sc1[i];
-        length = d.len[i]; width = d.wid[i]; height = d.hgt[i];
-        gx = d.goal_x[i]; gy = d.goal_y[i];
+    int first = 0, last = 1;  // iterations: one pass; the warm-up's: -1 (the reset pass) and the steps 0 .. warm_k - 1
+    bool skip_collision = false;
+    if (MODE == WS_WARMUP) {
+        const bool flagged = d.reset_flags[w] != 0;
+        const bool warm = flagged || d.warm_all != 0;
+        if (flagged && live) reset_agent(d, i);  // (k_reset_worlds)
+        __syncthreads();  // every thread has read the flag
+        if (a == 0) {
+            d.warm_flags[w] = warm ? 1 : 0;
+            if (flagged) d.reset_flags[w] = 0;
+            if (warm) atomicAdd(d.warm_count, 1ull);
+        }
+        if (!warm) return;
+        first = -1;
+        last = d.warm_k;
     }
+    if (MODE == WS_AFTER_WARMUP) skip_collision = d.warm_flags[w] != 0;
+    int it = first;
+    do {  // (WS_STEP / WS_AFTER_WARMUP: one trip and no back edge -- a loop around the body, even of one trip, costs them 30 VGPRs)
+        const bool moving = MODE == WS_WARMUP ? it >= 0 : MOVE;  // the movement and the step counter run
+        if (MODE == WS_WARMUP && moving && a < A_T) {  // log playback, step `it`: every agent slot's logged action (k_set_log_actions)
+            const int model = d.p.dynamicsModel;
+            float act[10];
+            expert_action(d.traj + i * TRAJ, it, model, act);
+            const int cols = model == GD_DYNAMICS_STATE ? 10 : 3;
+            for (int c = 0; c < cols; c++) d.action[i * 10 + c] = act[c];
+        }
+        Body b{};
+        int collided = 0, done = 0, resp = RESP_Static, controlled = 0, etype = 0;
+        uint32_t steps = 0;
+        int32_t info0 = 0, info1 = 0, info2 = 0, info3 = 0;
+        float sc0 = 0.f, sc1 = 0.f, length = 0.f, width = 0.f, height = 0.f, gx = 0.f, gy = 0.f;
+
+        // (every agent slot of the world is readable: the loads do not wait for the world's agent count)
+        if (a < A_T) {
+            b.px = d.px[i]; b.py = d.py[i]; b.pz = d.pz[i];
+            b.qw = d.qw[i]; b.qz = d.qz[i];
+            b.vx = d.vx[i]; b.vy = d.vy[i]; b.vz = d.vz[i];
+            collided = d.collided[i];
+            done = d.done[i];
+            resp = d.resp[i];
+            controlled = d.controlled[i];
+            etype = d.etype[i];
+            steps = d.steps[i];
+            const int32_t *info = d.info + i * 5;
+            info0 = info[0]; info1 = info[1]; info2 = info[2]; info3 = info[3];
+            sc0 = d.sc0[i]; sc1 = d.sc1[i];
+            length = d.len[i]; width = d.wid[i]; height = d.hgt[i];
+            gx = d.goal_x[i]; gy = d.goal_y[i];
+        }
 
 #ifdef GD_CLOCKS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    STEP_PHASE(0);
-    // ---- movementSystem, src/sim.cpp:294-383 ----
-    if (MOVE && live) {
-        if (collided) {
-            if (d.p.collisionBehaviour == GD_COLLISION_AGENT_STOP) {
-                done = 1;
-                b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
-            } else if (d.p.collisionBehaviour == GD_COLLISION_AGENT_REMOVED) {
-                done = 1;
-                b.px = kPadX; b.py = kPadY; b.pz = kPadZ;
-                b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
-            } else {
-                collided = 0;
-                info0 = 0; info1 = 0; info2 = 0;
+        STEP_PHASE(0);
+        // ---- movementSystem, src/sim.cpp:294-383 ----
+        if (moving && live) {
+            if (collided) {
+                if (d.p.collisionBehaviour == GD_COLLISION_AGENT_STOP) {
+                    done = 1;
+                    b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
+                } else if (d.p.collisionBehaviour == GD_COLLISION_AGENT_REMOVED) {
+                    done = 1;
+                    b.px = kPadX; b.py = kPadY; b.pz = kPadZ;
+                    b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
+                } else {
+                    collided = 0;
+                    info0 = 0; info1 = 0; info2 = 0;
+                }
+            }
+            if (resp != RESP_Static) {
+                if (done) {
+                    b.px = kPadX; b.py = kPadY; b.pz = kPadZ;
+                    b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
+                } else if (controlled) {
+                    float act[10];
+                    float *ap = d.action + i * 10;
+#pragma unroll
+                    for (int k = 0; k < 10; k++) act[k] = ap[k];
+                    switch (d.p.dynamicsModel) {
+                    case GD_DYNAMICS_INVERTIBLE_BICYCLE:
+                        forward_bicycle(act, b);
+                        ap[0] = act[0];
+                        ap[1] = act[1];
+                        break;
+                    case GD_DYNAMICS_DELTA_LOCAL: forward_delta(act, b); break;
+                    case GD_DYNAMICS_STATE: forward_state(act, b); break;
+                    default: forward_classic(act, length, b); break;
+                    }
+                } else {
+                    const float *t = d.traj + i * TRAJ;
+                    const int k = current_step(steps);
+                    b.px = t[2 * k]; b.py = t[2 * k + 1]; b.pz = 1.f;
+                    b.vx = t[2 * 91 + 2 * k]; b.vy = t[2 * 91 + 2 * k + 1]; b.vz = 0.f;
+                    const float heading = t[4 * 91 + k];
+                    p_sincos(heading / 2.f, b.qz, b.qw);
+                }
             }
         }
-        if (resp != RESP_Static) {
-            if (done) {
-                b.px = kPadX; b.py = kPadY; b.pz = kPadZ;
-                b.vx = 0.f; b.vy = 0.f; b.vz = 0.f;
-            } else if (controlled) {
-                float act[10];
-                float *ap = d.action + i * 10;
-#pragma unroll
-                for (int k = 0; k < 10; k++) act[k] = ap[k];
-                switch (d.p.dynamicsModel) {
-                case GD_DYNAMICS_INVERTIBLE_BICYCLE:
-                    forward_bicycle(act, b);
-                    ap[0] = act[0];
-                    ap[1] = act[1];
-                    break;
-                case GD_DYNAMICS_DELTA_LOCAL: forward_delta(act, b); break;
-                case GD_DYNAMICS_STATE: forward_state(act, b); break;
-                default: forward_classic(act, length, b); break;
-                }
-            } else {
+
+        STEP_PHASE(1);
+        // ---- publish per-agent geometry for the pair phases ----
+        bool active = false, moved = false;
+        const bool track_moves = OBS && (d.bev != nullptr || (d.lidar != nullptr && d.p.enableLidar != 0));  // (BEV rasters / LiDAR returns left in place where nothing changed)
+        float theta = 0.f;  // quat_to_yaw of the pose after the movement: the agent's box and its absolute row both need it
+        if (a < A_T) s_hit[a] = 0;
+        if (live) {
+            theta = quat_to_yaw(quat_from_wz(b.qw, b.qz));
+            // isInvalidExpertOrDone, src/sim.cpp:631-662; agents parked at kPaddingPosition overlap nothing
+            bool invalid;
+            if (!controlled) {
                 const float *t = d.traj + i * TRAJ;
-                const int k = current_step(steps);
-                b.px = t[2 * k]; b.py = t[2 * k + 1]; b.pz = 1.f;
-                b.vx = t[2 * 91 + 2 * k]; b.vy = t[2 * 91 + 2 * k + 1]; b.vz = 0.f;
-                const float heading = t[4 * 91 + k];
-                p_sincos(heading / 2.f, b.qz, b.qw);
+                invalid = !(t[5 * 91 + current_step(steps)] != 0.f);
+            } else {
+                invalid = done && !collided;
+            }
+            active = !skip_collision && !(b.pz == kPadZ) && !invalid;
+            s_px[a] = b.px; s_py[a] = b.py; s_qw[a] = b.qw; s_qz[a] = b.qz;
+            s_speed[a] = len_3(b.vx, b.vy, b.vz);
+            s_len[a] = length; s_wid[a] = width; s_hgt[a] = height;
+            s_etype[a] = etype;
+            s_id[a] = d.agent_id[i];
+            s_rad[a] = sqrtf(sc0 * sc0 + sc1 * sc1);
+            s_flags[a] = (active ? 1 : 0) | (resp == RESP_Static ? 2 : 0);
+            if (track_moves) {
+                // (the pose before the movement is still what the state arrays hold: they are written back further down)
+                const float old_px = d.px[i], old_py = d.py[i], old_pz = d.pz[i], old_qw = d.qw[i], old_qz = d.qz[i];
+                s_opx[a] = old_px; s_opy[a] = old_py;
+                moved = __float_as_uint(old_px) != __float_as_uint(b.px) || __float_as_uint(old_py) != __float_as_uint(b.py) ||
+                        __float_as_uint(old_pz) != __float_as_uint(b.pz) ||
+                        __float_as_uint(old_qw) != __float_as_uint(b.qw) || __float_as_uint(old_qz) != __float_as_uint(b.qz);
+            }
+            if (active) {
+                const Obb o = obb_from_yaw(b.px, b.py, theta, sc0, sc1);
+                const float *of = reinterpret_cast<const float *>(&o);
+#pragma unroll
+                for (int k = 0; k < 14; k++) s_obb[k][a] = of[k];
             }
         }
-    }
-
-    STEP_PHASE(1);
-    // ---- publish per-agent geometry for the pair phases ----
-    bool active = false, moved = false;
-    const bool track_moves = d.bev != nullptr || (d.lidar != nullptr && d.p.enableLidar != 0);  // (BEV rasters / LiDAR returns left in place where nothing changed)
-    float theta = 0.f;  // quat_to_yaw of the pose after the movement: the agent's box and its absolute row both need it
-    if (a < A_T) s_hit[a] = 0;
-    if (live) {
-        theta = quat_to_yaw(quat_from_wz(b.qw, b.qz));
-        // isInvalidExpertOrDone, src/sim.cpp:631-662; agents parked at kPaddingPosition overlap nothing
-        bool invalid;
-        if (!controlled) {
-            const float *t = d.traj + i * TRAJ;
-            invalid = !(t[5 * 91 + current_step(steps)] != 0.f);
-        } else {
-            invalid = done && !collided;
-        }
-        active = !(b.pz == kPadZ) && !invalid;
-        s_px[a] = b.px; s_py[a] = b.py; s_qw[a] = b.qw; s_qz[a] = b.qz;
-        s_speed[a] = len_3(b.vx, b.vy, b.vz);
-        s_len[a] = length; s_wid[a] = width; s_hgt[a] = height;
-        s_etype[a] = etype;
-        s_id[a] = d.agent_id[i];
-        s_rad[a] = sqrtf(sc0 * sc0 + sc1 * sc1);
-        s_flags[a] = (active ? 1 : 0) | (resp == RESP_Static ? 2 : 0);
-        if (track_moves) {
-            // (the pose before the movement is still what the state arrays hold: they are written back further down)
-            const float old_px = d.px[i], old_py = d.py[i], old_pz = d.pz[i], old_qw = d.qw[i], old_qz = d.qz[i];
-            s_opx[a] = old_px; s_opy[a] = old_py;
-            moved = __float_as_uint(old_px) != __float_as_uint(b.px) || __float_as_uint(old_py) != __float_as_uint(b.py) ||
-                    __float_as_uint(old_pz) != __float_as_uint(b.pz) ||
-                    __float_as_uint(old_qw) != __float_as_uint(b.qw) || __float_as_uint(old_qz) != __float_as_uint(b.qz);
-        }
-        if (active) {
-            const Obb o = obb_from_yaw(b.px, b.py, theta, sc0, sc1);
-            const float *of = reinterpret_cast<const float *>(&o);
-#pragma unroll
-            for (int k = 0; k < 14; k++) s_obb[k][a] = of[k];
-        }
-    }
-    if (track_moves && a < A_T) {  // (whole waves: the agents that moved, a bit per agent slot)
-        const unsigned long long mv = __ballot(moved);
-        if ((a & 63) == 0) s_moved[a >> 6] = mv;
-    }
-    __syncthreads();
-    STEP_PHASE(2);
-    // ---- which BEV rasters can have changed (collectBevObservationsSystem paints the in-radius roads and partners around the
-    // agent, src/sim.cpp:462-555): the agent's own pose changed, or an agent whose pose changed is within the radius of it now or
-    // was before it moved (a little more than the radius: whoever is marked without need is merely rasterised again) ----
-    if (d.bev != nullptr && live) {
-        int dirty = (!MOVE || d.pose_skip == 0 || d.bev_all_dirty != 0 || moved) ? 1 : 0;
-        if (!dirty) {
-            const float rr = d.p.observationRadius * 1.001f + 0.05f, r2 = rr * rr;
-            const float mx = s_px[a], my = s_py[a];  // (this agent did not move: its old position is its new one)
-#pragma unroll
-            for (int h = 0; h < A_T / 64; h++) {
-                for (unsigned long long m = s_moved[h]; m != 0ull && !dirty; m &= m - 1ull) {
-                    const int j = h * 64 + __ffsll((long long)m) - 1;
-                    const float dx = s_px[j] - mx, dy = s_py[j] - my, ox = s_opx[j] - mx, oy = s_opy[j] - my;
-                    if (!(dx * dx + dy * dy > r2) || !(ox * ox + oy * oy > r2)) dirty = 1;
-                }
-            }
-        }
-        d.bev_dirty[i] = dirty;
-    }
-    // ---- the same for the LiDAR returns (lidarSystem, src/sim.cpp:394-460, 895-913): the agent's own pose or the head angle of its
-    // action row changed, or an agent that moved is or was within the rays' 200 m plus its own bounding radius ----
-    if (d.lidar != nullptr && d.p.enableLidar != 0 && live) {
-        const float head = controlled ? d.action[i * 10 + 2] : 0.f;
-        int dirty = (!MOVE || d.pose_skip == 0 || d.bev_all_dirty != 0 || moved || __float_as_uint(head) != __float_as_uint(d.lidar_head[i])) ? 1 : 0;
-        if (!dirty) {
-            const float mx = s_px[a], my = s_py[a];
-#pragma unroll
-            for (int h = 0; h < A_T / 64; h++) {
-                for (unsigned long long m = s_moved[h]; m != 0ull && !dirty; m &= m - 1ull) {
-                    const int j = h * 64 + __ffsll((long long)m) - 1;
-                    const float rr = (200.f + s_rad[j]) * 1.001f + 0.1f, r2 = rr * rr;
-                    const float dx = s_px[j] - mx, dy = s_py[j] - my, ox = s_opx[j] - mx, oy = s_opy[j] - my;
-                    if (!(dx * dx + dy * dy > r2) || !(ox * ox + oy * oy > r2)) dirty = 1;
-                }
-            }
-        }
-        d.lidar_dirty[i] = dirty;
-    }
-
-    // ---- collisionDetectionSystem over broadphase candidates, src/sim.cpp:628-747, 792-801 ----
-    // All STEP_THREADS threads work here: P = STEP_THREADS / A threads per agent share its candidate
-    // agents and the road boxes of its broadphase cell; the flags they find are OR-ed through LDS.
-    {
-        constexpr int P = STEP_THREADS / A_T;
-        const int ag = a % A_T, part = a / A_T;
-        const int my_fl = ag < n ? s_flags[ag] : 0;
-        if (my_fl & 1) {
-            Obb me;
-            {
-                float *mf = reinterpret_cast<float *>(&me);
-#pragma unroll
-                for (int k = 0; k < 14; k++) mf[k] = s_obb[k][ag];
-            }
-            const float mx = s_px[ag], my = s_py[ag], my_rad = s_rad[ag];
-            const int my_type = s_etype[ag];
-            const bool me_static = (my_fl & 2) != 0;
-            int hit = 0;  // bit 0 collided, bits 1..3 info0..info2
-            for (int j = part; j < n; j += P) {
-                if (GD_DIAG_IS(d.step_dbg, 2)) break;
-                if (j == ag) continue;
-                const int fl = s_flags[j];
-                if (!(fl & 1)) continue;
-                if (me_static && (fl & 2)) continue;  // static-static pairs are never candidates
-                const float dx = mx - s_px[j], dy = my - s_py[j];
-                const float rr = (my_rad + s_rad[j]) * 1.001f + 0.01f;
-                if (dx * dx + dy * dy > rr * rr) continue;
-                Obb ot;
-                float *of = reinterpret_cast<float *>(&ot);
-#pragma unroll
-                for (int k = 0; k < 14; k++) of[k] = s_obb[k][j];
-                if (!obb_collided(me, ot)) continue;
-                const int otype = s_etype[j];
-                if (collision_pair_filtered(my_type, otype)) continue;
-                hit |= 1;
-                if (otype > ET_None && otype <= ET_StopSign) hit |= 2;
-                else if (otype == ET_Vehicle) hit |= 4;
-                else if (otype <= ET_Cyclist) hit |= 8;
-            }
-            if (hit) atomicOr(&s_hit[ag], hit);
-        }
-        STEP_PHASE(3);
-        // Road boxes of the broadphase cell under each agent's centre, as ONE list of (agent, candidate) items dealt evenly to
-        // all STEP_THREADS threads.  (Rounds 1-4 gave every agent's candidates to the P threads that share the agent: the phase
-        // lasted as long as the fullest cell of the world -- 36 % of a workgroup's time on the bench scene, per-phase clocks of a
-        // -DGD_CLOCKS build -- while most threads had finished.)  The agent threads publish their cell's run of the cell-ordered
-        // candidate arrays and its length, a scan over the agents turns the lengths into offsets, and item t belongs to the
-        // agent whose offset range holds t.  Two items per thread and trip, so that their loads are in flight together.
-        {
-            int cnt = 0, c0 = 0;
-            if (a < A_T && (my_fl & 1) && !(my_fl & 2) && !GD_DIAG_IS(d.step_dbg, 1)) {
-                const float fx = (s_px[a] - gh.ox) * gh.inv_cell, fy = (s_py[a] - gh.oy) * gh.inv_cell;
-                if (gh.nx > 0 && fx >= 0.f && fy >= 0.f && fx < (float)gh.nx && fy < (float)gh.ny) {
-                    const int cell = (int)fy * gh.nx + (int)fx;
-                    c0 = d.cell_off[gh.cell_base + cell];
-                    cnt = d.cell_off[gh.cell_base + cell + 1] - c0;
-                    c0 += gh.item_base;
-                }
-            }
-            // inclusive scan over the lanes of a wave (DPP), the waves of agent threads chained through LDS
-            int incl = cnt;
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);  // row_shr:1
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);  // row_shr:2
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);  // row_shr:4
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);  // row_shr:8
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-            incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
-            constexpr int AW = A_T / 64;  // waves of agent threads
-            if (a < A_T && (a & 63) == 63) s_wtot[a >> 6] = incl;
-            if (a == 0) s_nsv[0] = 0;
-            __syncthreads();
-            if (a < A_T) {
-                int base = 0;
-#pragma unroll
-                for (int k = 0; k < AW; k++) base += (k < (a >> 6)) ? s_wtot[k] : 0;
-                s_c0[a] = c0;
-                s_coff[a] = base + incl - cnt;
-            }
-            int total = 0;
-#pragma unroll
-            for (int k = 0; k < AW; k++) total += s_wtot[k];
-            __syncthreads();
-#ifdef GD_CLOCKS
-            if (a == 0) atomicAdd(&g_step_cnt[0], (unsigned long long)total);
-#endif
-            // the exact test of one (agent, box) pair: the box's 14 floats (a gather), the agent's from LDS
-            auto box_test = [&](unsigned int entry) {
-#ifdef GD_CLOCKS
-                atomicAdd(&g_step_cnt[1], 1ull);
-#endif
-                const int g = (int)(entry & 0xffu), rtype = (int)(entry >> 28);
-                const size_t r = (size_t)(bbase + (int)((entry >> 8) & 0xfffffu));
-                const float4 q1 = d.boxes[r * 5 + 1], q2 = d.boxes[r * 5 + 2], q3 = d.boxes[r * 5 + 3], q4 = d.boxes[r * 5 + 4];
-                const float tmp[16] = {q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, q4.z, q4.w};
-                Obb ro, me;
-                float *of = reinterpret_cast<float *>(&ro), *mf = reinterpret_cast<float *>(&me);
-#pragma unroll
-                for (int k = 0; k < 14; k++) { of[k] = tmp[k]; mf[k] = s_obb[k][g]; }
-                if (obb_collided(me, ro)) atomicOr(&s_hit[g], 1 | ((rtype > ET_None && rtype <= ET_StopSign) ? 2 : 0));
-            };
-            // U items per thread and trip, their candidate records requested together: the records of a world's cells are spread
-            // over ~0.7 MB per world (every box is listed in the ~9 cells it can reach), 0.7 GB per batch, so each trip is a miss
-            // all the way to HBM and the phase is as long as the number of dependent trips (1,280 items per world on the bench
-            // scene: one trip).  A candidate that passes the cull goes on the workgroup's list of (agent, box) pairs -- one in
-            // fifteen does, and which threads hold them is a matter of luck -- and the exact tests are dealt out again from the list.
-            constexpr int U = SVCAP / STEP_THREADS;
-            int trip = 0;
-#pragma clang loop unroll(disable)
-            for (int t0 = 0; t0 < total; t0 += SVCAP, trip ^= 1) {  // (uniform: the barriers inside are reached by every thread)
-                int agu[U];
-                float4 hdr[U];
-                bool on[U];
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const int t = t0 + u * STEP_THREADS + a;
-                    on[u] = t < total;
-                    // the LAST agent whose offset is <= t: agents without candidates share the offset of the next agent that has
-                    // some, and "last" picks that one
-                    int lo = 0;
-#pragma unroll
-                    for (int st = A_T / 2; st > 0; st >>= 1)
-                        if (s_coff[lo + st] <= t) lo += st;
-                    agu[u] = lo;
-                    hdr[u] = d.cell_hdr[on[u] ? s_c0[lo] + (t - s_coff[lo]) : 0];
-                }
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const int g = agu[u];
-                    const unsigned int packed = __float_as_uint(hdr[u].w);  // type | local box index << 8 (engine.cpp)
-                    const int rtype = (int)(packed & 0xffu);
-                    const float dx = s_px[g] - hdr[u].x, dy = s_py[g] - hdr[u].y;
-                    const float rr = (s_rad[g] + hdr[u].z) * 1.001f + 0.01f;
-                    if (on[u] && !collision_pair_filtered(s_etype[g], rtype) && !(dx * dx + dy * dy > rr * rr))
-                        s_sv[atomicAdd(&s_nsv[trip], 1)] = (unsigned int)g | (packed >> 8) << 8 | (packed & 0xfu) << 28;  // at most SVCAP items per trip
-                }
-                __syncthreads();
-                const int nsv = s_nsv[trip];
-                if (a == 0) s_nsv[trip ^ 1] = 0;  // (the next trip's counter: nobody touches it before the barrier below)
-                for (int e = a; e < nsv; e += STEP_THREADS) box_test(s_sv[e]);
-                __syncthreads();
-            }
+        if (track_moves && a < A_T) {  // (whole waves: the agents that moved, a bit per agent slot)
+            const unsigned long long mv = __ballot(moved);
+            if ((a & 63) == 0) s_moved[a >> 6] = mv;
         }
         __syncthreads();
-        STEP_PHASE(4);
-        if (live && active) {
-            const int hit = s_hit[a];
-            if (hit & 1) collided = 1;
-            if (hit & 2) info0 = 1;
-            if (hit & 4) info1 = 1;
-            if (hit & 8) info2 = 1;
+        STEP_PHASE(2);
+        // ---- which BEV rasters can have changed (collectBevObservationsSystem paints the in-radius roads and partners around the
+        // agent, src/sim.cpp:462-555): the agent's own pose changed, or an agent whose pose changed is within the radius of it now or
+        // was before it moved (a little more than the radius: whoever is marked without need is merely rasterised again) ----
+        if (OBS && d.bev != nullptr && live) {
+            int dirty = (!moving || d.pose_skip == 0 || d.bev_all_dirty != 0 || moved) ? 1 : 0;
+            if (!dirty) {
+                const float rr = d.p.observationRadius * 1.001f + 0.05f, r2 = rr * rr;
+                const float mx = s_px[a], my = s_py[a];  // (this agent did not move: its old position is its new one)
+#pragma unroll
+                for (int h = 0; h < A_T / 64; h++) {
+                    for (unsigned long long m = s_moved[h]; m != 0ull && !dirty; m &= m - 1ull) {
+                        const int j = h * 64 + __ffsll((long long)m) - 1;
+                        const float dx = s_px[j] - mx, dy = s_py[j] - my, ox = s_opx[j] - mx, oy = s_opy[j] - my;
+                        if (!(dx * dx + dy * dy > r2) || !(ox * ox + oy * oy > r2)) dirty = 1;
+                    }
+                }
+            }
+            d.bev_dirty[i] = dirty;
         }
-    }
+        // ---- the same for the LiDAR returns (lidarSystem, src/sim.cpp:394-460, 895-913): the agent's own pose or the head angle of its
+        // action row changed, or an agent that moved is or was within the rays' 200 m plus its own bounding radius ----
+        if (OBS && d.lidar != nullptr && d.p.enableLidar != 0 && live) {
+            const float head = controlled ? d.action[i * 10 + 2] : 0.f;
+            int dirty = (!moving || d.pose_skip == 0 || d.bev_all_dirty != 0 || moved || __float_as_uint(head) != __float_as_uint(d.lidar_head[i])) ? 1 : 0;
+            if (!dirty) {
+                const float mx = s_px[a], my = s_py[a];
+#pragma unroll
+                for (int h = 0; h < A_T / 64; h++) {
+                    for (unsigned long long m = s_moved[h]; m != 0ull && !dirty; m &= m - 1ull) {
+                        const int j = h * 64 + __ffsll((long long)m) - 1;
+                        const float rr = (200.f + s_rad[j]) * 1.001f + 0.1f, r2 = rr * rr;
+                        const float dx = s_px[j] - mx, dy = s_py[j] - my, ox = s_opx[j] - mx, oy = s_opy[j] - my;
+                        if (!(dx * dx + dy * dy > r2) || !(ox * ox + oy * oy > r2)) dirty = 1;
+                    }
+                }
+            }
+            d.lidar_dirty[i] = dirty;
+        }
 
-    if (live) {
-        // ---- rewardSystem, src/sim.cpp:560-587 ----
-        const float dist = len_2(b.px - gx, b.py - gy);
-        if (d.p.rewardType == GD_REWARD_DISTANCE_BASED) d.reward[i] = -dist;
-        else if (d.p.rewardType == GD_REWARD_ON_GOAL_ACHIEVED) d.reward[i] = dist < d.p.distanceToGoalThreshold ? 1.f : 0.f;
-        // ---- stepTrackerSystem, :589-592 ----
-        if (MOVE) --steps;
-        // ---- doneSystem, :597-626 ----
-        const int32_t num_remaining = (int32_t)steps;
-        if (num_remaining == EPISODE && done != 1) {
-            done = 0;
-        } else {
-            if (num_remaining == 0) done = 1;
-            if (done != 1 || info3 != 1) {
-                if (dist < d.p.distanceToGoalThreshold) { done = 1; info3 = 1; }
+        // ---- collisionDetectionSystem over broadphase candidates, src/sim.cpp:628-747, 792-801 ----
+        // All STEP_THREADS threads work here: P = STEP_THREADS / A threads per agent share its candidate
+        // agents and the road boxes of its broadphase cell; the flags they find are OR-ed through LDS.
+        {
+            constexpr int P = STEP_THREADS / A_T;
+            const int ag = a % A_T, part = a / A_T;
+            const int my_fl = ag < n ? s_flags[ag] : 0;
+            if (my_fl & 1) {
+                Obb me;
+                {
+                    float *mf = reinterpret_cast<float *>(&me);
+#pragma unroll
+                    for (int k = 0; k < 14; k++) mf[k] = s_obb[k][ag];
+                }
+                const float mx = s_px[ag], my = s_py[ag], my_rad = s_rad[ag];
+                const int my_type = s_etype[ag];
+                const bool me_static = (my_fl & 2) != 0;
+                int hit = 0;  // bit 0 collided, bits 1..3 info0..info2
+                for (int j = part; j < n; j += P) {
+                    if (GD_DIAG_IS(d.step_dbg, 2)) break;
+                    if (j == ag) continue;
+                    const int fl = s_flags[j];
+                    if (!(fl & 1)) continue;
+                    if (me_static && (fl & 2)) continue;  // static-static pairs are never candidates
+                    const float dx = mx - s_px[j], dy = my - s_py[j];
+                    const float rr = (my_rad + s_rad[j]) * 1.001f + 0.01f;
+                    if (dx * dx + dy * dy > rr * rr) continue;
+                    Obb ot;
+                    float *of = reinterpret_cast<float *>(&ot);
+#pragma unroll
+                    for (int k = 0; k < 14; k++) of[k] = s_obb[k][j];
+                    if (!obb_collided(me, ot)) continue;
+                    const int otype = s_etype[j];
+                    if (collision_pair_filtered(my_type, otype)) continue;
+                    hit |= 1;
+                    if (otype > ET_None && otype <= ET_StopSign) hit |= 2;
+                    else if (otype == ET_Vehicle) hit |= 4;
+                    else if (otype <= ET_Cyclist) hit |= 8;
+                }
+                if (hit) atomicOr(&s_hit[ag], hit);
+            }
+            STEP_PHASE(3);
+            // Road boxes of the broadphase cell under each agent's centre, as ONE list of (agent, candidate) items dealt evenly to
+            // all STEP_THREADS threads.  (Rounds 1-4 gave every agent's candidates to the P threads that share the agent: the phase
+            // lasted as long as the fullest cell of the world -- 36 % of a workgroup's time on the bench scene, per-phase clocks of a
+            // -DGD_CLOCKS build -- while most threads had finished.)  The agent threads publish their cell's run of the cell-ordered
+            // candidate arrays and its length, a scan over the agents turns the lengths into offsets, and item t belongs to the
+            // agent whose offset range holds t.  Two items per thread and trip, so that their loads are in flight together.
+            {
+                int cnt = 0, c0 = 0;
+                if (a < A_T && (my_fl & 1) && !(my_fl & 2) && !GD_DIAG_IS(d.step_dbg, 1)) {
+                    const float fx = (s_px[a] - gh.ox) * gh.inv_cell, fy = (s_py[a] - gh.oy) * gh.inv_cell;
+                    if (gh.nx > 0 && fx >= 0.f && fy >= 0.f && fx < (float)gh.nx && fy < (float)gh.ny) {
+                        const int cell = (int)fy * gh.nx + (int)fx;
+                        c0 = d.cell_off[gh.cell_base + cell];
+                        cnt = d.cell_off[gh.cell_base + cell + 1] - c0;
+                        c0 += gh.item_base;
+                    }
+                }
+                // inclusive scan over the lanes of a wave (DPP), the waves of agent threads chained through LDS
+                int incl = cnt;
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);  // row_shr:1
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);  // row_shr:2
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);  // row_shr:4
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);  // row_shr:8
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+                incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+                constexpr int AW = A_T / 64;  // waves of agent threads
+                if (a < A_T && (a & 63) == 63) s_wtot[a >> 6] = incl;
+                if (a == 0) s_nsv[0] = 0;
+                __syncthreads();
+                if (a < A_T) {
+                    int base = 0;
+#pragma unroll
+                    for (int k = 0; k < AW; k++) base += (k < (a >> 6)) ? s_wtot[k] : 0;
+                    s_c0[a] = c0;
+                    s_coff[a] = base + incl - cnt;
+                }
+                int total = 0;
+#pragma unroll
+                for (int k = 0; k < AW; k++) total += s_wtot[k];
+                __syncthreads();
+#ifdef GD_CLOCKS
+                if (a == 0) atomicAdd(&g_step_cnt[0], (unsigned long long)total);
+#endif
+                // the exact test of one (agent, box) pair: the box's 14 floats (a gather), the agent's from LDS
+                auto box_test = [&](unsigned int entry) {
+#ifdef GD_CLOCKS
+                    atomicAdd(&g_step_cnt[1], 1ull);
+#endif
+                    const int g = (int)(entry & 0xffu), rtype = (int)(entry >> 28);
+                    const size_t r = (size_t)(bbase + (int)((entry >> 8) & 0xfffffu));
+                    const float4 q1 = d.boxes[r * 5 + 1], q2 = d.boxes[r * 5 + 2], q3 = d.boxes[r * 5 + 3], q4 = d.boxes[r * 5 + 4];
+                    const float tmp[16] = {q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, q4.z, q4.w};
+                    Obb ro, me;
+                    float *of = reinterpret_cast<float *>(&ro), *mf = reinterpret_cast<float *>(&me);
+#pragma unroll
+                    for (int k = 0; k < 14; k++) { of[k] = tmp[k]; mf[k] = s_obb[k][g]; }
+                    if (obb_collided(me, ro)) atomicOr(&s_hit[g], 1 | ((rtype > ET_None && rtype <= ET_StopSign) ? 2 : 0));
+                };
+                // U items per thread and trip, their candidate records requested together: the records of a world's cells are spread
+                // over ~0.7 MB per world (every box is listed in the ~9 cells it can reach), 0.7 GB per batch, so each trip is a miss
+                // all the way to HBM and the phase is as long as the number of dependent trips (1,280 items per world on the bench
+                // scene: one trip).  A candidate that passes the cull goes on the workgroup's list of (agent, box) pairs -- one in
+                // fifteen does, and which threads hold them is a matter of luck -- and the exact tests are dealt out again from the list.
+                constexpr int U = SVCAP / STEP_THREADS;
+                int trip = 0;
+#pragma clang loop unroll(disable)
+                for (int t0 = 0; t0 < total; t0 += SVCAP, trip ^= 1) {  // (uniform: the barriers inside are reached by every thread)
+                    int agu[U];
+                    float4 hdr[U];
+                    bool on[U];
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        const int t = t0 + u * STEP_THREADS + a;
+                        on[u] = t < total;
+                        // the LAST agent whose offset is <= t: agents without candidates share the offset of the next agent that has
+                        // some, and "last" picks that one
+                        int lo = 0;
+#pragma unroll
+                        for (int st = A_T / 2; st > 0; st >>= 1)
+                            if (s_coff[lo + st] <= t) lo += st;
+                        agu[u] = lo;
+                        hdr[u] = d.cell_hdr[on[u] ? s_c0[lo] + (t - s_coff[lo]) : 0];
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        const int g = agu[u];
+                        const unsigned int packed = __float_as_uint(hdr[u].w);  // type | local box index << 8 (engine.cpp)
+                        const int rtype = (int)(packed & 0xffu);
+                        const float dx = s_px[g] - hdr[u].x, dy = s_py[g] - hdr[u].y;
+                        const float rr = (s_rad[g] + hdr[u].z) * 1.001f + 0.01f;
+                        if (on[u] && !collision_pair_filtered(s_etype[g], rtype) && !(dx * dx + dy * dy > rr * rr))
+                            s_sv[atomicAdd(&s_nsv[trip], 1)] = (unsigned int)g | (packed >> 8) << 8 | (packed & 0xfu) << 28;  // at most SVCAP items per trip
+                    }
+                    __syncthreads();
+                    const int nsv = s_nsv[trip];
+                    if (a == 0) s_nsv[trip ^ 1] = 0;  // (the next trip's counter: nobody touches it before the barrier below)
+                    for (int e = a; e < nsv; e += STEP_THREADS) box_test(s_sv[e]);
+                    __syncthreads();
+                }
+            }
+            __syncthreads();
+            STEP_PHASE(4);
+            if (live && active) {
+                const int hit = s_hit[a];
+                if (hit & 1) collided = 1;
+                if (hit & 2) info0 = 1;
+                if (hit & 4) info1 = 1;
+                if (hit & 8) info2 = 1;
             }
         }
-        // ---- write back ----
-        d.px[i] = b.px; d.py[i] = b.py; d.pz[i] = b.pz;
-        d.qw[i] = b.qw; d.qz[i] = b.qz;
-        d.vx[i] = b.vx; d.vy[i] = b.vy; d.vz[i] = b.vz;
-        d.collided[i] = collided;
-        d.done[i] = done;
-        d.steps[i] = steps;
-        int32_t *info = d.info + i * 5;
-        info[0] = info0; info[1] = info1; info[2] = info2; info[3] = info3;
 
-        // ---- collectSelfObsSystem, :168-186 ----
-        const Quat rot = quat_from_wz(b.qw, b.qz);
-        const V3 g = quat_rotate(quat_inv(rot), V3{gx - b.px, gy - b.py, 0.f});
-        float *so = d.self_obs + i * 8;
-        so[0] = s_speed[a];
-        so[1] = length; so[2] = width; so[3] = height;
-        so[4] = g.x; so[5] = g.y;
-        so[6] = collided ? 1.f : 0.f;
-        so[7] = (float)s_id[a];
-        if (d.pack != nullptr) {
-            float *ss = s_self + a * 8;
-            ss[0] = s_speed[a]; ss[1] = length; ss[2] = width; ss[3] = height; ss[4] = g.x; ss[5] = g.y; ss[6] = collided ? 1.f : 0.f;
+        if (live) {
+            // ---- rewardSystem, src/sim.cpp:560-587 ----
+            const float dist = len_2(b.px - gx, b.py - gy);
+            if (d.p.rewardType == GD_REWARD_DISTANCE_BASED) d.reward[i] = -dist;
+            else if (d.p.rewardType == GD_REWARD_ON_GOAL_ACHIEVED) d.reward[i] = dist < d.p.distanceToGoalThreshold ? 1.f : 0.f;
+            // ---- stepTrackerSystem, :589-592 ----
+            if (moving) --steps;
+            // ---- doneSystem, :597-626 ----
+            const int32_t num_remaining = (int32_t)steps;
+            if (num_remaining == EPISODE && done != 1) {
+                done = 0;
+            } else {
+                if (num_remaining == 0) done = 1;
+                if (done != 1 || info3 != 1) {
+                    if (dist < d.p.distanceToGoalThreshold) { done = 1; info3 = 1; }
+                }
+            }
+            // ---- write back ----
+            d.px[i] = b.px; d.py[i] = b.py; d.pz[i] = b.pz;
+            d.qw[i] = b.qw; d.qz[i] = b.qz;
+            d.vx[i] = b.vx; d.vy[i] = b.vy; d.vz[i] = b.vz;
+            d.collided[i] = collided;
+            d.done[i] = done;
+            d.steps[i] = steps;
+            int32_t *info = d.info + i * 5;
+            info[0] = info0; info[1] = info1; info[2] = info2; info[3] = info3;
+
+            if (OBS) {  // (the warm-up leaves them to the reset pass that follows)
+                // ---- collectSelfObsSystem, :168-186 ----
+                const Quat rot = quat_from_wz(b.qw, b.qz);
+                const V3 g = quat_rotate(quat_inv(rot), V3{gx - b.px, gy - b.py, 0.f});
+                float *so = d.self_obs + i * 8;
+                so[0] = s_speed[a];
+                so[1] = length; so[2] = width; so[3] = height;
+                so[4] = g.x; so[5] = g.y;
+                so[6] = collided ? 1.f : 0.f;
+                so[7] = (float)s_id[a];
+                if (d.pack != nullptr) {
+                    float *ss = s_self + a * 8;
+                    ss[0] = s_speed[a]; ss[1] = length; ss[2] = width; ss[3] = height; ss[4] = g.x; ss[5] = g.y; ss[6] = collided ? 1.f : 0.f;
+                }
+                // ---- collectAbsoluteObservationsSystem, :769-783 ----
+                float *ao = d.abs_obs + i * 14;
+                ao[0] = b.px; ao[1] = b.py; ao[2] = b.pz;
+                ao[3] = rot.w; ao[4] = rot.x; ao[5] = rot.y; ao[6] = rot.z;
+                ao[7] = theta;
+                ao[8] = gx; ao[9] = gy;
+                ao[10] = length; ao[11] = width; ao[12] = height;
+                ao[13] = (float)s_id[a];
+            }
         }
-        // ---- collectAbsoluteObservationsSystem, :769-783 ----
-        float *ao = d.abs_obs + i * 14;
-        ao[0] = b.px; ao[1] = b.py; ao[2] = b.pz;
-        ao[3] = rot.w; ao[4] = rot.x; ao[5] = rot.y; ao[6] = rot.z;
-        ao[7] = theta;
-        ao[8] = gx; ao[9] = gy;
-        ao[10] = length; ao[11] = width; ao[12] = height;
-        ao[13] = (float)s_id[a];
-    }
 
 #ifdef GD_CLOCKS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    STEP_PHASE(5);
-    // ---- collectPartnerObsSystem, :188-240: here, or in k_partner_rows on a stream of its own beside the road kernels ----
-    if (!d.p.disableClassicalObs && !d.split_partner && !d.pack_only)
-        partner_rows<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_hgt, s_etype, s_id, !MOVE || d.pose_skip == 0, s_stage);
-    if (d.pack != nullptr && !d.p.disableClassicalObs) {
-        __syncthreads();  // the agent threads' self columns
-        packed_head<A_T, ROWS>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
-    }
+        STEP_PHASE(5);
+        // ---- collectPartnerObsSystem, :188-240: here, or in k_partner_rows on a stream of its own beside the road kernels ----
+        if (OBS && !d.p.disableClassicalObs && !d.split_partner && !d.pack_only)
+            partner_rows<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_hgt, s_etype, s_id, !moving || d.pose_skip == 0, s_stage);
+        if (OBS && d.pack != nullptr && !d.p.disableClassicalObs) {
+            __syncthreads();  // the agent threads' self columns
+            packed_head<A_T, ROWS>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
+        }
 #ifdef GD_CLOCKS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    STEP_PHASE(6);
+        STEP_PHASE(6);
+        if (MODE == WS_WARMUP) __syncthreads();  // (the next step's publish rewrites the LDS arrays)
+    } while (MODE == WS_WARMUP && ++it < last);
 }
 
 // The same rows as a kernel of their own: the engine runs it on a second stream while the road kernels (which do not read the
@@ -800,10 +850,19 @@ void step_clocks_read(unsigned long long *out) {  // and zero them; out[8..11] =
 template <int A_T>
 static void launch_all(const DevSim &d, hipStream_t st, int which, bool move) {
     const dim3 grid(d.W), block(A_T);
+    const bool warmup = d.gate_any && d.warm_k > 0;  // a device-driven reset pass with the warm-up (gd_episode_set_warmup)
     switch (which) {
-    case KERNEL_RESET: hipLaunchKernelGGL(k_reset_worlds<A_T>, grid, block, 0, st, d); break;
+    case KERNEL_RESET:
+        if (warmup) hipLaunchKernelGGL((k_world_step<A_T, false, false, WS_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
+        else hipLaunchKernelGGL(k_reset_worlds<A_T>, grid, block, 0, st, d);
+        break;
     case KERNEL_PADDING: hipLaunchKernelGGL(k_init_padding_rows<A_T>, grid, block, 0, st, d); break;
     case KERNEL_STATE:
+        if (warmup && !move) {  // the state kernel of the reset pass behind the warm-up
+            if (d.pack != nullptr && d.pack_rows) hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
+            else hipLaunchKernelGGL((k_world_step<A_T, false, false, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
+            break;
+        }
         if (d.pack != nullptr && d.pack_rows) {  // gd_attach_packed_rows
             if (move) hipLaunchKernelGGL((k_world_step<A_T, true, true>), grid, dim3(STEP_THREADS), 0, st, d);
             else hipLaunchKernelGGL((k_world_step<A_T, false, true>), grid, dim3(STEP_THREADS), 0, st, d);

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
+#include "expert.hpp"
 #include "pack_cols.hpp"
 
 namespace gd {
@@ -156,32 +157,8 @@ __global__ __launch_bounds__(256) void k_pack_relayout(const float *__restrict__
     __builtin_nontemporal_store(vv, reinterpret_cast<f4 *>(out) + g);
 }
 
-// ---- expert-action export and log playback ----
-// GPUDriveTorchEnv.get_expert_actions() (reference gpudrive/env/env_torch.py:1445-1509) slices the
-// expert trajectory rows ([pos 182 | vel 182 | yaw 91 | valid 91 | inferred action 910],
-// gpudrive/datatypes/trajectory.py:24-41) and clamps the inferred actions per dynamics model:
-//   classic / bicycle : columns 0..2, accel in [-6, 6], steer in [-0.3, 0.3]
-//   delta_local       : columns 0..2, dx, dy in [-6, 6], dyaw in [-pi, pi]
-//   state             : (x, y, 1, yaw, vx, vy, 0, 0, 0, 0)
-// torch.clamp = min(max(x, lo), hi) with NaN propagated.
+// ---- expert-action export and log playback: the columns come from expert_action (expert.hpp) ----
 constexpr int T = GD_EPISODE_LEN;
-constexpr float kPiF = 3.14159265358979323846f;  // torch.pi rounded to fp32
-
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
-
-// columns of the action the caller would feed for time step t of agent row `tr` (1456 floats)
-__device__ __forceinline__ void expert_action(const float *tr, int t, int model, float *act /*3 or 10*/) {
-    const float *inf = tr + 6 * T + t * 10;
-    if (model == GD_DYNAMICS_STATE) {
-        act[0] = tr[2 * t]; act[1] = tr[2 * t + 1]; act[2] = 1.f; act[3] = tr[4 * T + t];
-        act[4] = tr[2 * T + 2 * t]; act[5] = tr[2 * T + 2 * t + 1];
-        act[6] = 0.f; act[7] = 0.f; act[8] = 0.f; act[9] = 0.f;
-    } else if (model == GD_DYNAMICS_DELTA_LOCAL) {
-        act[0] = clampf(inf[0], -6.f, 6.f); act[1] = clampf(inf[1], -6.f, 6.f); act[2] = clampf(inf[2], -kPiF, kPiF);
-    } else {
-        act[0] = clampf(inf[0], -6.f, 6.f); act[1] = clampf(inf[1], -0.3f, 0.3f); act[2] = inf[2];
-    }
-}
 
 __global__ __launch_bounds__(256) void k_expert_actions(DevSim d, float *actions, float *pos, float *vel, float *yaw, int *valid) {
     const size_t n = (size_t)d.W * d.A * T;  // one thread per (world, agent, time step)

@@ -22,6 +22,20 @@ from . import _capi
 REWARD_TYPES = {"weighted_combination": _capi.EPISODE_REWARD_WEIGHTED, "sparse_on_goal_achieved": _capi.EPISODE_REWARD_SPARSE,
                 "reward_conditioned": _capi.EPISODE_REWARD_CONDITIONED, "distance_to_logs": _capi.EPISODE_REWARD_LOG_DISTANCE}
 CONDITION_MODES = {"random": _capi.CONDITION_RANDOM, "preset": _capi.CONDITION_PRESET, "fixed": _capi.CONDITION_FIXED}
+WARMUP_SCOPES = {"reset_worlds": _capi.WARMUP_RESET_WORLDS, "all_worlds": _capi.WARMUP_ALL_WORLDS}
+
+
+def check_warmup(init_steps, warmup):
+    """(init_steps, scope code) for the warm-up of the device auto-reset; ValueError for init_steps outside [0, 90] (or not
+    an integer) and for an unknown scope.  Host only."""
+    if isinstance(init_steps, bool) or not isinstance(init_steps, (int, np.integer)):
+        raise ValueError("init_steps must be an integer in [0, %d], got %r" % (_capi.INIT_STEPS_MAX, init_steps))
+    if not 0 <= int(init_steps) <= _capi.INIT_STEPS_MAX:
+        raise ValueError("init_steps must be in [0, %d] (the expert trajectory has 91 steps), got %d"
+                         % (_capi.INIT_STEPS_MAX, init_steps))
+    if warmup not in WARMUP_SCOPES:
+        raise ValueError("unknown warmup scope %r (one of %s)" % (warmup, sorted(WARMUP_SCOPES)))
+    return int(init_steps), WARMUP_SCOPES[warmup]
 # bounds of (collision, goal_achieved, off_road), gpudrive/env/config.py:103-113
 DEFAULT_LB = (-1.0, 1.0, -1.0)
 DEFAULT_UB = (0.0, 2.0, 0.0)
@@ -57,11 +71,18 @@ def resolve_condition(condition_mode, agent_type=None, lb=DEFAULT_LB, ub=DEFAULT
 class EpisodeTracker:
     def __init__(self, sim, collision_weight=-0.5, goal_achieved_weight=1.0, off_road_weight=-0.5,
                  reward_type="weighted_combination", auto_reset=True, *, condition_mode="random", agent_type=None,
-                 reward_weight_lb=DEFAULT_LB, reward_weight_ub=DEFAULT_UB, log_distance_weight=0.01, seed=0):
+                 reward_weight_lb=DEFAULT_LB, reward_weight_ub=DEFAULT_UB, log_distance_weight=0.01, seed=0,
+                 init_steps=0, warmup="reset_worlds"):
         """reward_type: a key of REWARD_TYPES.  reward_conditioned: `condition_mode` / `agent_type` say how the weights of
         every world are drawn, now and whenever the tracker resets a world (see `set_reward_weights`); `reward_weight_lb`
         / `_ub` are the (collision, goal_achieved, off_road) bounds of "random" and of the presets; `seed` keys "random".
-        distance_to_logs: `log_distance_weight` scales the distance term."""
+        distance_to_logs: `log_distance_weight` scales the distance term.
+        init_steps: the reference's warm-up (`init_steps`, 0..90): every world the tracker resets is then advanced that many
+        steps with the logged actions, on the device, before its observations are written.  warmup: "reset_worlds" (only
+        the worlds reset in this step) or "all_worlds" (the reference as it is: every world, whenever any world is reset).
+        The episode bookkeeping is unchanged.  The setting belongs to the simulator: a tracker built later replaces it."""
+        self.init_steps, warm_scope = check_warmup(init_steps, warmup)
+        self.warmup = warmup
         if reward_type not in REWARD_TYPES:
             raise ValueError("unknown reward_type %r (one of %s)" % (reward_type, sorted(REWARD_TYPES)))
         self.sim = sim
@@ -102,6 +123,7 @@ class EpisodeTracker:
         if reward_type == "reward_conditioned":
             self._set_condition(self.cfg, condition_mode, agent_type)
             self.set_reward_weights(condition_mode=condition_mode, agent_type=agent_type)  # draw 0 of every world
+        _capi.check(self._L.gd_episode_set_warmup(sim._h, self.init_steps, warm_scope), "gd_episode_set_warmup")
 
     def _set_condition(self, cfg, condition_mode, agent_type):
         mode, w = resolve_condition(condition_mode, agent_type, self._lb, self._ub)

@@ -16,7 +16,7 @@ from itertools import product
 
 import torch
 
-from .episode import EpisodeTracker
+from .episode import EpisodeTracker, check_warmup
 from .harness import default_action_values
 
 _DYNAMICS_NAMES = {0: "classic", 1: "bicycle", 2: "delta_local", 3: "state"}
@@ -37,11 +37,16 @@ _default_table = action_table  # (the constructor's argument of the same name sh
 
 
 class DeviceLearnerEnv:
-    def __init__(self, sim, action_table=None, only=True, **tracker_kwargs):
+    def __init__(self, sim, action_table=None, only=True, init_steps=0, warmup="reset_worlds", **tracker_kwargs):
         """sim: a SimManager.  action_table: float32 [n, 3] (default: `action_table()` of the simulator's dynamics model).
-        only: the raw partner / road rows are not written any more (nothing but the learner rows).  tracker_kwargs go to
-        `EpisodeTracker` (reward weights, reward_type, auto_reset, ...); "reward_conditioned" is not supported here (its
-        [N, D + 3] layout is a separate feature).  Arguments are checked before anything reaches the device (ValueError)."""
+        only: the raw partner / road rows are not written any more (nothing but the learner rows).  init_steps / warmup:
+        the reference's warm-up (its PPO config sets init_steps 11): with init_steps > 0 construction and `resample()`
+        reset every world and advance it that many steps with the logged actions (PufferGPUDrive.__init__ /
+        resample_scenario_batch through env.reset), and the worlds `step()` resets are warmed on the device (see
+        `EpisodeTracker`).  tracker_kwargs go to `EpisodeTracker` (reward weights, reward_type, auto_reset, ...);
+        "reward_conditioned" is not supported here (its [N, D + 3] layout is a separate feature).  Arguments are checked
+        before anything reaches the device (ValueError)."""
+        check_warmup(init_steps, warmup)
         if tracker_kwargs.get("reward_type") == "reward_conditioned":
             raise ValueError("DeviceLearnerEnv: reward_type='reward_conditioned' ([N, D + 3] rows) is not supported; "
                              "use EpisodeTracker with packed_observations(reward_weights=...)")
@@ -54,9 +59,20 @@ class DeviceLearnerEnv:
             action_table = _default_table(_DYNAMICS_NAMES[int(sim._params.dynamicsModel)])
         self.sim = sim
         self.only = bool(only)
-        self._tracker_kwargs = dict(tracker_kwargs)
+        self.init_steps = int(init_steps)
+        self._tracker_kwargs = dict(tracker_kwargs, init_steps=self.init_steps, warmup=warmup)
         self.table = action_table.to(device=sim._device, dtype=torch.float32).contiguous()
+        if self.init_steps > 0:
+            sim.reset(list(range(sim._W)))
         self._setup()
+        self._warm_up()
+
+    def _warm_up(self):
+        """The host warm-up of construction and resample (env.reset -> advance_sim_with_log_playback).  It runs after the
+        rows are attached: attaching runs a reset pass, whose collision re-run on the warmed state the reference does not
+        have."""
+        if self.init_steps > 0:
+            self.sim.advance_log_playback(self.init_steps)
 
     def _setup(self):
         """Tracker (it captures the controlled mask), learner rows from that mask, the row buffer, the flat outputs."""
@@ -98,8 +114,9 @@ class DeviceLearnerEnv:
 
     def resample(self, scenes):
         """A new batch of scenes (the reference's resample_scenario_batch, env_puffer.py:438-453): set_maps, the controlled
-        mask derived again, the learner rows set from it, the row buffer attached again, the storage emptied.  Returns the
-        [N, D] observations of the new worlds."""
+        mask derived again, the learner rows set from it, the row buffer attached again, the warm-up (init_steps), the
+        storage emptied.  Returns the [N, D] observations of the new worlds."""
         self.sim.set_maps(scenes)
         self._setup()
+        self._warm_up()
         return self.reset()

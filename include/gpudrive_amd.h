@@ -272,6 +272,19 @@ typedef struct gd_episode_buffers {
 /* With GD_EPISODE_REWARD_CONDITIONED a finished world's reward_weights are redrawn in cfg->condition_mode by the same kernel,
  * before the reset pass, so the observation of the reset world carries its new weights (env_puffer.py:375-390). */
 int gd_episode_step(gd_sim *sim, const gd_episode_config *cfg, const gd_episode_buffers *buffers);
+/* Warm-up of the device auto-reset (the reference's init_steps: GPUDriveTorchEnv.reset -> advance_sim_with_log_playback,
+ * gpudrive/env/env_torch.py:403-452, 1274-1293, also for the worlds PufferGPUDrive.step() resets, env_puffer.py:375-390).
+ * With init_steps = k > 0 the reset pass that gd_episode_step launches with auto_reset advances every warmed world k state steps
+ * (movement, collision, reward, step counter, done) after resetting the flagged ones; step t feeds every agent slot the logged
+ * action of time t (what gd_advance_log_playback writes), and the observations are written once, at the end.  Scopes:
+ *   GD_WARMUP_RESET_WORLDS: the worlds reset in this step, each ending bit for bit as gd_reset of it + gd_advance_log_playback(k)
+ *                           leaves it; every other world is untouched.
+ *   GD_WARMUP_ALL_WORLDS:   the reference as it is: when any world was reset, EVERY world is advanced k steps, as gd_reset(list) +
+ *                           gd_advance_log_playback(k) do (the latter steps the whole batch).
+ * The episode bookkeeping is unchanged (episode lengths count learner steps only).  k = 0 (the default) launches nothing extra.
+ * Neither gd_reset nor any other reset pass is affected.  init_steps outside [0, 90] or an unknown scope: GD_ERR_INVALID. */
+enum { GD_WARMUP_RESET_WORLDS = 0, GD_WARMUP_ALL_WORLDS = 1 };
+int gd_episode_set_warmup(gd_sim *sim, int32_t init_steps, int32_t scope);
 /* Draw the reward weights of the listed worlds (host array of n world indices; NULL = every world) in cfg->condition_mode
  * into buffers->reward_weights and count the draw in buffers->weight_draws (EpisodeTracker.set_reward_weights, the
  * reference's _set_reward_weights(env_idx_list, condition_mode, agent_type), env_torch.py:247-401). */
@@ -298,7 +311,8 @@ int gd_attach_bev(gd_sim *sim, float *bev);
  * exist (must stay 0), 30 = agents whose road rows were left in place because their pose bits had not changed, since the last
  * read, 31 = BEV rasters painted by the last pass that rasterised (the others could not have changed and were left in
  * place), 44 = agents whose LiDAR returns the last pass marked for tracing (likewise), 45 = action indices outside the table
- * that gd_set_discrete_actions met since the simulator was created.  Otherwise GD_ERR_INVALID. */
+ * that gd_set_discrete_actions met since the simulator was created, 46 = worlds the warm-up of the device auto-reset
+ * (gd_episode_set_warmup) advanced since the simulator was created.  Otherwise GD_ERR_INVALID. */
 int gd_stat(gd_sim *sim, int32_t which, int64_t *out);
 
 /* Timing hooks for the bench: HIP events around the named kernel on the engine's stream (a fixed ring of event pairs,

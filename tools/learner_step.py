@@ -9,7 +9,10 @@
 Milliseconds per learner step (CUDA events over --steps steps after --warmup, the step repeated as a PPO rollout calls it),
 the kernel times of the row writers (the state step, which writes the ego + partner columns, and the road kernel; HIP events
 around every launch, steps kernel by kernel), and the bytes of both observation buffers.  bench.py's workload builders are
-imported, not changed.  tools/learner_step.py [--worlds 1024] [--steps 50] [--warmup 10]"""
+imported, not changed.  --init-steps k: both paths warm every world k steps at setup and every world they reset on the
+device (EpisodeTracker / DeviceLearnerEnv init_steps; --warmup-scope picks the scope).  --reset-at n: before the timing the
+worlds are advanced by log playback so that their episodes end at step n of the timed window (default: no advance, as
+before).  tools/learner_step.py [--worlds 1024] [--steps 50] [--warmup 10] [--init-steps 0] [--reset-at -1]"""
 import argparse
 import json
 import os
@@ -67,16 +70,27 @@ def main():
     ap.add_argument("--worlds", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--init-steps", type=int, default=0)
+    ap.add_argument("--warmup-scope", default="reset_worlds", choices=("reset_worlds", "all_worlds"))
+    ap.add_argument("--reset-at", type=int, default=-1)
     args = ap.parse_args()
+    k = args.init_steps
+    # log-playback steps before the timing: the episode (91 - k learner steps after the setup's warm-up) ends at step
+    # reset_at of the timed window, which follows the --warmup untimed steps
+    pre = 0 if args.reset_at < 0 else max(0, 91 - k - args.warmup - args.reset_at - 1)
     gen = torch.Generator(device="cuda").manual_seed(0)
     table = action_table("classic").cuda()
     res = dict(tool="tools/learner_step.py", workload=WORKLOAD, worlds=args.worlds, steps=args.steps, warmup=args.warmup,
-               source_stamp=bench.source_stamp())
+               init_steps=k, warmup_scope=args.warmup_scope, reset_at=args.reset_at, source_stamp=bench.source_stamp())
 
     # (a) full direct pack + torch decode + gathers
     sim, A = make(args.worlds)
     assert sim.direct_pack(only=True)
-    tr = EpisodeTracker(sim)
+    if k > 0:
+        sim.advance_log_playback(k)  # (a fresh simulator: what DeviceLearnerEnv's setup does)
+    if pre > 0:
+        sim.advance_log_playback(pre)
+    tr = EpisodeTracker(sim, init_steps=k, warmup=args.warmup_scope)
     slots = tr.controlled_agent_mask.view(-1).nonzero().squeeze(1)  # setup: the one sync
     N = int(slots.numel())
     D = 6 + (A - 1) * 6 + 200 * 13
@@ -99,13 +113,18 @@ def main():
 
     # (b) DeviceLearnerEnv
     sim, A = make(args.worlds)
-    env = DeviceLearnerEnv(sim)
+    env = DeviceLearnerEnv(sim, init_steps=k, warmup=args.warmup_scope)
     assert env.num_agents == N
+    if pre > 0:
+        sim.advance_log_playback(pre)
 
     def step_b():
         return env.step(idx)
 
+    w0 = sim.stat(46)
     res["b_ms_per_step"] = timed(step_b, args.steps, args.warmup)
+    res["b_worlds_warmed"] = sim.stat(46) - w0
+    res["b_episodes"] = env.pop_stats().get("num_completed_episodes", 0)
     res["b_kernels_ms"] = kernel_ms(sim, step_b, args.steps)
     res["b_obs_bytes"] = N * D * 4
     sim.close()
