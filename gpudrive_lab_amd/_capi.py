@@ -105,7 +105,7 @@ SYMBOLS = [
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_episode_step", "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
-    "gd_set_learner_rows", "gd_attach_packed_rows", "gd_set_discrete_actions",
+    "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
     "gd_kernel_timing_enable", "gd_kernel_timing_read", "gd_debug_get_state", "gd_debug_set_state", "gd_debug_road_path",
     "gd_host_world_build", "gd_host_world_free", "gd_scene_cache_write",
@@ -162,6 +162,7 @@ def lib():
     L.gd_episode_set_warmup.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.gd_set_learner_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_attach_packed_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    L.gd_attach_packed_rows_conditioned.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     L.gd_set_discrete_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_pack_observations_conditioned.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.gd_scene_cache_write.argtypes = [C.c_char_p, C.c_float, C.c_char_p]

@@ -807,7 +807,7 @@ struct gd_sim {
         launch(gd::KERNEL_PADDING, false);
         // the packed observation's rows of padding agents come from the raw padding rows just written (the live agents' rows are
         // written by the reset pass that follows every rebuild)
-        if (d.pack && d.pack_rows) gd::launch_pack_obs_rows(d, stream, d.pack);
+        if (d.pack && d.pack_rows) gd::launch_pack_obs_rows(d, stream, d.pack, d.pack_weights);
         else if (d.pack) gd::launch_pack_obs(d, stream, d.pack);
     }
 
@@ -818,27 +818,31 @@ struct gd_sim {
         d.pack = nullptr;
         d.pack_only = 0;
         d.pack_rows = 0;
+        d.pack_weights = nullptr;
         HIP_CHECK(hipMemsetAsync(d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(W) * A, stream));
         reset_flagged(false);
     }
 
     // attach `out` as the packed buffer: everything once from the raw tensors (the padding agents' rows never change between
     // rebuilds); then every pass of the step kernels writes the live agents' rows in place.  Every pose stamp dies: the next
-    // pass writes every live agent's road columns, whatever was skipped before.  rows: out is [n_rows][D] (learner rows).
-    void attach_packed(float *out, bool only, bool rows) {
+    // pass writes every live agent's road columns, whatever was skipped before.  rows: out is [n_rows][D] (learner rows);
+    // weights (with rows): out is [n_rows][D + 3], the conditioned rows with the slots' reward weights.
+    void attach_packed(float *out, bool only, bool rows, const float *weights = nullptr) {
         HIP_CHECK(hipStreamSynchronize(stream));
         drop_graph();
         d.pack = nullptr;
         d.pack_only = 0;
         d.pack_rows = 0;
+        d.pack_weights = nullptr;
         HIP_CHECK(hipMemsetAsync(d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(W) * A, stream));
         reset_flagged(false);  // raw tensors up to date (a previous pack_only attachment left them stale)
-        if (rows) gd::launch_pack_obs_rows(d, stream, out);
+        if (rows) gd::launch_pack_obs_rows(d, stream, out, weights);
         else gd::launch_pack_obs(d, stream, out);
         HIP_CHECK(hipGetLastError());
         d.pack = out;
         d.pack_only = only ? 1 : 0;
         d.pack_rows = rows ? 1 : 0;
+        d.pack_weights = rows ? weights : nullptr;
     }
 
     // the packed observation can be written where the rows are produced by every road path -- the linear scan, set order
@@ -1332,6 +1336,18 @@ int gd_attach_packed_rows(gd_sim *s, float *out, int64_t out_bytes, int32_t only
     if (!s->direct_pack_supported())
         return fail(GD_ERR_UNSUPPORTED, "gd_attach_packed_rows: not available with disableClassicalObs or GPUDRIVE_LINEAR_LEGACY=1");
     return guarded([&]() { s->attach_packed(out, only != 0, true); });
+}
+
+int gd_attach_packed_rows_conditioned(gd_sim *s, float *out, int64_t out_bytes, int32_t only, const float *weights) {
+    if (!s || !out || !weights)
+        return fail(GD_ERR_INVALID, "gd_attach_packed_rows_conditioned: null argument (gd_attach_packed(sim, NULL, 0, 0) detaches)");
+    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, "gd_attach_packed_rows_conditioned: no learner rows set (gd_set_learner_rows)");
+    const int64_t R = 6 + static_cast<int64_t>(s->A - 1) * 6 + GD_MAP_OBS_K * 13 + 3;
+    if (out_bytes < static_cast<int64_t>(s->d.n_rows) * R * 4)
+        return fail(GD_ERR_INVALID, "gd_attach_packed_rows_conditioned: output buffer too small");
+    if (!s->direct_pack_supported())
+        return fail(GD_ERR_UNSUPPORTED, "gd_attach_packed_rows_conditioned: not available with disableClassicalObs or GPUDRIVE_LINEAR_LEGACY=1");
+    return guarded([&]() { s->attach_packed(out, only != 0, true, weights); });
 }
 
 int gd_set_discrete_actions(gd_sim *s, const int64_t *indices, const float *table, int32_t n_actions) {

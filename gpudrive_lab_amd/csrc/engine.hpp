@@ -205,6 +205,9 @@ struct DevSim {
     int warm_all;             // 1: GD_WARMUP_ALL_WORLDS (every world is warmed when any was flagged), 0: the flagged worlds only
     int32_t *warm_flags;      // [W] 1: the last warm-up launch that ran advanced this world
     unsigned long long *warm_count;  // [1] worlds warmed since the simulator was created (gd_stat 46)
+    // conditioned learner rows (gd_attach_packed_rows_conditioned), with pack_rows: the [W][A][3] reward weights, and the
+    // attached buffer is [n_rows][D + 3] = ego 6 | the slot's 3 weights | partners | road points; null otherwise
+    const float *pack_weights;
 };
 
 void launch_kernel(const DevSim &d, hipStream_t st, int which, bool move);
@@ -219,7 +222,8 @@ void launch_set_log_actions(const DevSim &d, hipStream_t st, int t);
 void launch_episode_step(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b);  // episode.hip
 void launch_draw_weights(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b,
                          const int32_t *worlds, int n);  // episode.hip
-void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out);  // pack_obs.hip: learner rows only ([n_rows][D])
+void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out,
+                          const float *weights);  // pack_obs.hip: learner rows only ([n_rows][D], or [n_rows][D + 3] with weights)
 void launch_learner_rows(hipStream_t st, const uint8_t *mask, size_t slots, int32_t *row_of_slot, int32_t *slot_of_row,
                          int32_t *count);  // learner.hip
 void launch_discrete_actions(const DevSim &d, hipStream_t st, const int64_t *indices, const float *table, int n_actions);  // learner.hip

@@ -69,7 +69,19 @@ __device__ __forceinline__ float block_sum(float v, float *scratch, int a) {
     return r;
 }
 
+// weight columns 6..8 of slot i's conditioned learner row (gd_attach_packed_rows_conditioned), if it has one: a redraw reaches
+// every row at once -- also the rows of padding and Static slots, whose heads no step rewrites
 template <int A_T>
+__device__ __forceinline__ void cond_row_weights(const DevSim &d, size_t i, const float *wt) {
+    constexpr int R = 6 + (A_T - 1) * 6 + GD_MAP_OBS_K * 13 + 3;
+    const int r = d.row_of_slot[i];
+    if (r < 0) return;
+    float *o = d.pack + (size_t)r * R + 6;
+    o[0] = wt[0]; o[1] = wt[1]; o[2] = wt[2];
+}
+
+// COND: conditioned learner rows are attached with b.reward_weights as their weights; the redraw rewrites their weight columns
+template <int A_T, bool COND = false>
 __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_config c, gd_episode_buffers b) {
     const int w = blockIdx.x, a = threadIdx.x;
     const size_t i = (size_t)w * A_T + a;
@@ -128,7 +140,10 @@ __global__ __launch_bounds__(A_T) void k_episode_step(DevSim d, gd_episode_confi
     if (world_done) {
         const bool redraw = c.reward_type == GD_EPISODE_REWARD_CONDITIONED && c.auto_reset;
         const int draw = redraw ? b.weight_draws[w] : 0;  // read before the barriers of block_sum, incremented after them
-        if (redraw) draw_weights(c, w, draw, a, b.reward_weights + i * 3);  // this step's reward has read the old ones
+        if (redraw) {
+            draw_weights(c, w, draw, a, b.reward_weights + i * 3);  // this step's reward has read the old ones
+            if (COND) cond_row_weights<A_T>(d, i, b.reward_weights + i * 3);
+        }
         const float fc = controlled ? 1.f : 0.f;
         float sums[8];
         sums[0] = block_sum<A_T>(fc * ret, scratch, a);
@@ -192,15 +207,42 @@ __global__ __launch_bounds__(A_T) void k_draw_weights(gd_episode_config c, gd_ep
     if (a == 0) b.weight_draws[w] = draw + 1;
 }
 
+// ... while conditioned learner rows are attached with b.reward_weights as their weights: their weight columns too
+template <int A_T>
+__global__ __launch_bounds__(A_T) void k_draw_weights_rows(DevSim d, gd_episode_config c, gd_episode_buffers b, const int32_t *worlds) {
+    const int w = worlds ? worlds[blockIdx.x] : (int)blockIdx.x, a = threadIdx.x;
+    const size_t i = (size_t)w * A_T + a;
+    const int draw = b.weight_draws[w];
+    draw_weights(c, w, draw, a, b.reward_weights + i * 3);
+    cond_row_weights<A_T>(d, i, b.reward_weights + i * 3);
+    __syncthreads();
+    if (a == 0) b.weight_draws[w] = draw + 1;
+}
+
+// the attached conditioned learner rows take their weights from b.reward_weights
+bool cond_rows_of(const DevSim &d, const gd_episode_buffers &b) {
+    return d.pack != nullptr && d.pack_rows && d.pack_weights != nullptr && d.pack_weights == b.reward_weights;
+}
+
 }  // namespace
 
 void launch_draw_weights(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b,
                          const int32_t *worlds, int n) {
+    if (cond_rows_of(d, b)) {
+        if (d.A == 64) hipLaunchKernelGGL(k_draw_weights_rows<64>, dim3(n), dim3(64), 0, st, d, c, b, worlds);
+        else hipLaunchKernelGGL(k_draw_weights_rows<128>, dim3(n), dim3(128), 0, st, d, c, b, worlds);
+        return;
+    }
     if (d.A == 64) hipLaunchKernelGGL(k_draw_weights<64>, dim3(n), dim3(64), 0, st, c, b, worlds);
     else hipLaunchKernelGGL(k_draw_weights<128>, dim3(n), dim3(128), 0, st, c, b, worlds);
 }
 
 void launch_episode_step(const DevSim &d, hipStream_t st, const gd_episode_config &c, const gd_episode_buffers &b) {
+    if (c.reward_type == GD_EPISODE_REWARD_CONDITIONED && c.auto_reset && cond_rows_of(d, b)) {
+        if (d.A == 64) hipLaunchKernelGGL((k_episode_step<64, true>), dim3(d.W), dim3(64), 0, st, d, c, b);
+        else hipLaunchKernelGGL((k_episode_step<128, true>), dim3(d.W), dim3(128), 0, st, d, c, b);
+        return;
+    }
     if (d.A == 64) hipLaunchKernelGGL(k_episode_step<64>, dim3(d.W), dim3(64), 0, st, d, c, b);
     else hipLaunchKernelGGL(k_episode_step<128>, dim3(d.W), dim3(128), 0, st, d, c, b);
 }

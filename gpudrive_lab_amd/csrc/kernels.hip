@@ -300,12 +300,17 @@ __device__ __forceinline__ void partner_rows(const DevSim &d, int w, int n, int 
 // r exactly as partner_rows does and normalises it, the block is laid out in LDS and leaves as whole 16-byte pieces.
 // `s_self`: the agents' raw self-observation columns 0..6 (speed, length, width, -, goal x, goal y, collided), [A][8].
 // ROWS (gd_attach_packed_rows): the head goes to the agent's learner row (DevSim::row_of_slot), none for an agent without one.
-template <int A_T, bool ROWS>
+// COND (gd_attach_packed_rows_conditioned, with ROWS): the row's pitch is D + 3 and its head is ego | the slot's 3 weights
+// (DevSim::pack_weights) | partners, 6 A + 3 floats at any 16-byte phase: the first pass stages ego | weights | 63 partners
+// (387 floats), the second 64 partners (384), and each leaves through store_span (pack_cols.hpp), which writes exactly the
+// head's own dwords -- the road kernels own the rest of the row.
+template <int A_T, bool ROWS, bool COND = false>
 __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a, const float *s_px, const float *s_py,
                                             const float *s_qw, const float *s_qz, const float *s_speed, const float *s_len,
                                             const float *s_wid, const float *s_self) {
-    constexpr int D = 6 + (A_T - 1) * 6 + K * 13;
-    __shared__ __attribute__((aligned(16))) float s_head[STEP_THREADS / 64][64 * 6];
+    static_assert(ROWS || !COND, "the conditioned layout exists for the learner rows only");
+    constexpr int D = 6 + (A_T - 1) * 6 + K * 13, PITCH = COND ? D + 3 : D;
+    __shared__ __attribute__((aligned(16))) float s_head[STEP_THREADS / 64][COND ? 64 * 6 + 4 : 64 * 6];
     const int wave = a >> 6, lane = a & 63;
     float *stage = s_head[wave];
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -316,14 +321,18 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
             if (r < 0) continue;
             prow = (size_t)r;
         }
-        float *out = d.pack + prow * D;
+        float *out = d.pack + prow * PITCH;
 #pragma unroll
         for (int h = 0; h < A_T / 64; h++) {
             const int r = h * 64 + lane;
-            float *o = stage + lane * 6;
+            float *o = stage + lane * 6 + (COND && h == 0 && lane > 0 ? 3 : 0);  // (COND: the weights follow the ego columns)
             if (r == 0) {
 #pragma unroll
                 for (int c = 0; c < 6; c++) o[c] = pack_ego_col(s_self + ego * 8, c);
+                if (COND) {
+                    const float *wt = d.pack_weights + ((size_t)w * A_T + ego) * 3;
+                    o[6] = wt[0]; o[7] = wt[1]; o[8] = wt[2];
+                }
             } else {
                 const int k = r - 1;
                 float raw[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // zero_nonexist() / zero(): the columns the pack reads are all zero
@@ -344,8 +353,12 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
                 pack_partner_row(raw, o);
             }
             wave_sync();
-            for (int q = lane; q < 64 * 6 / 4; q += 64)
-                __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(out + h * (64 * 6) + q * 4));
+            if (COND) {
+                store_span(stage, out + (h == 0 ? 0 : h * (64 * 6) + 3), h == 0 ? 64 * 6 + 3 : 64 * 6, lane, 64);
+            } else {
+                for (int q = lane; q < 64 * 6 / 4; q += 64)
+                    __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(out + h * (64 * 6) + q * 4));
+            }
             wave_sync();
         }
     }
@@ -365,7 +378,8 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
 //                    as in WS_STEP.
 enum { WS_STEP = 0, WS_WARMUP = 1, WS_AFTER_WARMUP = 2 };
 
-template <int A_T, bool MOVE, bool ROWS = false, int MODE = WS_STEP>
+// COND (gd_attach_packed_rows_conditioned): the conditioned learner rows (packed_head).
+template <int A_T, bool MOVE, bool ROWS = false, int MODE = WS_STEP, bool COND = false>
 __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     constexpr bool OBS = MODE != WS_WARMUP;  // the observation phases
     const int w = blockIdx.x, a = threadIdx.x;
@@ -799,7 +813,7 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
             partner_rows<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_hgt, s_etype, s_id, !moving || d.pose_skip == 0, s_stage);
         if (OBS && d.pack != nullptr && !d.p.disableClassicalObs) {
             __syncthreads();  // the agent threads' self columns
-            packed_head<A_T, ROWS>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
+            packed_head<A_T, ROWS, COND>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
         }
 #ifdef GD_CLOCKS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -859,8 +873,15 @@ static void launch_all(const DevSim &d, hipStream_t st, int which, bool move) {
     case KERNEL_PADDING: hipLaunchKernelGGL(k_init_padding_rows<A_T>, grid, block, 0, st, d); break;
     case KERNEL_STATE:
         if (warmup && !move) {  // the state kernel of the reset pass behind the warm-up
-            if (d.pack != nullptr && d.pack_rows) hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
+            if (d.pack != nullptr && d.pack_rows && d.pack_weights)
+                hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP, true>), grid, dim3(STEP_THREADS), 0, st, d);
+            else if (d.pack != nullptr && d.pack_rows) hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
             else hipLaunchKernelGGL((k_world_step<A_T, false, false, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
+            break;
+        }
+        if (d.pack != nullptr && d.pack_rows && d.pack_weights) {  // gd_attach_packed_rows_conditioned
+            if (move) hipLaunchKernelGGL((k_world_step<A_T, true, true, WS_STEP, true>), grid, dim3(STEP_THREADS), 0, st, d);
+            else hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_STEP, true>), grid, dim3(STEP_THREADS), 0, st, d);
             break;
         }
         if (d.pack != nullptr && d.pack_rows) {  // gd_attach_packed_rows

@@ -480,7 +480,9 @@ __device__ __forceinline__ void order_waves(const DevSim &d, int count, unsigned
 // ROWS (gd_attach_packed_rows): the packed rows go to the agent's learner row (DevSim::row_of_slot), none for an agent without one
 // (with pack_only such an agent writes nothing).
 template <bool PACK> struct RowsGeo { static constexpr int AB = PACK ? 3 : 5; };
-template <int A_T, bool PACK = false, bool ROWS = false>
+// COND (gd_attach_packed_rows_conditioned, with ROWS): the rows are [D + 3] (ego | 3 weights | partners | roads): an agent's
+// road block starts 3 floats later, at any 16-byte phase, and leaves through store_span (pack_cols.hpp).
+template <int A_T, bool PACK = false, bool ROWS = false, bool COND = false>
 __global__ __launch_bounds__(256) void k_map_rows(DevSim d) {
     constexpr int ROWS_AB = RowsGeo<PACK>::AB;
     constexpr int U = GD_ROWS_PER_THREAD;  // entries per thread (256 apart): independent load chains in flight
@@ -595,6 +597,13 @@ __global__ __launch_bounds__(256) void k_map_rows(DevSim d) {
         __syncthreads();
         constexpr int PACK_ROAD0 = 6 + (A_T - 1) * 6, PACK_D = PACK_ROAD0 + K * 13, PPA13 = K * 13 / 4;
         static_assert(PACK_ROAD0 % 4 == 0 && PACK_D % 4 == 0, "whole 16-byte pieces");
+        if (COND) {
+#pragma unroll
+            for (int ag = 0; ag < ROWS_AB; ag++) {  // (s_on, s_prow: workgroup-uniform)
+                if (s_on[ag] != 0 && s_prow[ag] >= 0)
+                    store_span(s_rows + ag * (K * 13), d.pack + (size_t)s_prow[ag] * (PACK_D + 3) + PACK_ROAD0 + 3, K * 13, threadIdx.x, 256);
+            }
+        } else
         for (int q = threadIdx.x; q < RB * 13 / 4; q += 256) {
             const int ag = q / PPA13;
             if (ROWS) {
@@ -1075,7 +1084,9 @@ __device__ unsigned long long g_set_clk[8];
 #endif
 // ROWS (gd_attach_packed_rows, with PACK): the packed rows go to the agent's learner row (DevSim::row_of_slot), none for an agent
 // without one (with pack_only such an agent selects but writes no rows).
-template <int A_T, int NW, bool FUSE, bool PACK = false, bool ROWS = false>
+// COND (gd_attach_packed_rows_conditioned, with ROWS): the rows are [D + 3] (ego | 3 weights | partners | roads): an agent's
+// road block starts 3 floats later, at any 16-byte phase, and each pass of 64 rows leaves through store_span (pack_cols.hpp).
+template <int A_T, int NW, bool FUSE, bool PACK = false, bool ROWS = false, bool COND = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GD_SET_WPE))) void k_map_obs_set(DevSim d) {
     static_assert(FUSE || !PACK, "the packed rows are written by the fused write-out");
     using S = SetSel<A_T>;
@@ -1528,9 +1539,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(GD_SET_
             if (ROWS && prow < 0) continue;
             pack_road_row(raw, stage + lane * 13);
             wave_sync();
-            float *pout = d.pack + (ROWS ? (size_t)prow : i) * (size_t)PACK_D + PACK_ROAD0 + p * (64 * 13);
-            for (int q = lane; q < nrows * 13 / 4; q += 64)
-                __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
+            if (COND) {
+                store_span(stage, d.pack + (size_t)prow * (PACK_D + 3) + PACK_ROAD0 + 3 + p * (64 * 13), nrows * 13, lane, 64);
+            } else {
+                float *pout = d.pack + (ROWS ? (size_t)prow : i) * (size_t)PACK_D + PACK_ROAD0 + p * (64 * 13);
+                for (int q = lane; q < nrows * 13 / 4; q += 64)
+                    __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
+            }
             wave_sync();
         }
         if (lane == 0)
@@ -1564,6 +1579,11 @@ void launch_map_obs(const DevSim &d, hipStream_t st, bool move) {
         if (d.set_group_count == 0) return;
         const dim3 grid(d.set_group_count);
         if (d.set_fused_rows) {
+            if (d.pack != nullptr && d.pack_rows && d.pack_weights) {
+                if (d.A == 64) hipLaunchKernelGGL((k_map_obs_set<64, 4, true, true, true, true>), grid, dim3(256), 0, st, d);
+                else hipLaunchKernelGGL((k_map_obs_set<128, 4, true, true, true, true>), grid, dim3(256), 0, st, d);
+                return;
+            }
             if (d.pack != nullptr && d.pack_rows) {
                 if (d.A == 64) hipLaunchKernelGGL((k_map_obs_set<64, 4, true, true, true>), grid, dim3(256), 0, st, d);
                 else hipLaunchKernelGGL((k_map_obs_set<128, 4, true, true, true>), grid, dim3(256), 0, st, d);
@@ -1590,6 +1610,11 @@ void launch_map_obs(const DevSim &d, hipStream_t st, bool move) {
     if (d.pack != nullptr) {
         constexpr int AB = RowsGeo<true>::AB;
         const dim3 pgrid((unsigned int)((agents + AB - 1) / AB + 7) / 8 * 8);
+        if (d.pack_rows && d.pack_weights) {
+            if (d.A == 64) hipLaunchKernelGGL((k_map_rows<64, true, true, true>), pgrid, dim3(256), 0, st, d);
+            else hipLaunchKernelGGL((k_map_rows<128, true, true, true>), pgrid, dim3(256), 0, st, d);
+            return;
+        }
         if (d.pack_rows) {
             if (d.A == 64) hipLaunchKernelGGL((k_map_rows<64, true, true>), pgrid, dim3(256), 0, st, d);
             else hipLaunchKernelGGL((k_map_rows<128, true, true>), pgrid, dim3(256), 0, st, d);

@@ -71,7 +71,9 @@ static_assert(64 % GD_LIN_BLK == 0, "whole blocks per pass");
 
 // ROWS (gd_attach_packed_rows): the packed rows go to the agent's learner row (DevSim::row_of_slot); an agent without one
 // stores no packed rows, and with pack_only nothing at all, so it is not visited.
-template <int A_T, bool PACK, bool ROWS = false>
+// COND (gd_attach_packed_rows_conditioned, with ROWS): the rows are [D + 3] (ego | 3 weights | partners | roads): an agent's road
+// block starts 3 floats later, at any 16-byte phase, and each pass of 64 rows leaves through store_span (pack_cols.hpp).
+template <int A_T, bool PACK, bool ROWS = false, bool COND = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE))) void k_map_obs_linear(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     const int tid = threadIdx.x;
@@ -241,9 +243,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GD_LIN_WPE)
                 if (pk) {  // (gd_attach_packed) the same rows in the packed observation's 13 normalised columns (pack_cols.hpp)
                     pack_road_row(raw, stage + lane * 13);
                     wave_sync();
-                    float *pout = d.pack + prow * (size_t)PACK_D + PACK_ROAD0 + pz * (64 * 13);
-                    for (int q = lane; q < nrows * 13 / 4; q += 64)
-                        __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
+                    if (COND) {
+                        store_span(stage, d.pack + prow * (size_t)(PACK_D + 3) + PACK_ROAD0 + 3 + pz * (64 * 13), nrows * 13, lane, 64);
+                    } else {
+                        float *pout = d.pack + prow * (size_t)PACK_D + PACK_ROAD0 + pz * (64 * 13);
+                        for (int q = lane; q < nrows * 13 / 4; q += 64)
+                            __builtin_nontemporal_store(*reinterpret_cast<const f4 *>(stage + q * 4), reinterpret_cast<f4 *>(pout + q * 4));
+                    }
                     wave_sync();
                 }
             }
@@ -267,6 +273,11 @@ void launch_map_obs_linear(const DevSim &d0, hipStream_t st, bool move) {
     }
     if (d.lin_blocks == 0) return;
     const dim3 grid(d.lin_blocks);
+    if (d.pack != nullptr && d.pack_rows && d.pack_weights) {
+        if (d.A == 64) hipLaunchKernelGGL((k_map_obs_linear<64, true, true, true>), grid, dim3(256), 0, st, d);
+        else hipLaunchKernelGGL((k_map_obs_linear<128, true, true, true>), grid, dim3(256), 0, st, d);
+        return;
+    }
     if (d.pack != nullptr && d.pack_rows) {
         if (d.A == 64) hipLaunchKernelGGL((k_map_obs_linear<64, true, true>), grid, dim3(256), 0, st, d);
         else hipLaunchKernelGGL((k_map_obs_linear<128, true, true>), grid, dim3(256), 0, st, d);

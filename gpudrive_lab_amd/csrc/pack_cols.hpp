@@ -64,4 +64,29 @@ __device__ __forceinline__ void pack_partner_row(const float *raw, float *o) {
     for (int c = 0; c < 6; c++) o[c] = pack_partner_col(raw[c], c);
 }
 
+// A span of n floats staged at `src` (LDS) stored to `dst` (global) at any dword alignment: the conditioned learner rows
+// (gd_attach_packed_rows_conditioned) have the odd pitch D + 3, so row r starts at float r (D + 3) = -r (mod 4) and its road
+// block at 3 - r (mod 4).  The <= 3 floats in front of dst's first 16-byte boundary and the <= 3 behind its last one leave as
+// single dwords, everything between as aligned 16-byte pieces.  LDS is read a dword at a time: the shifted 16-byte reads
+// would be misaligned (ds_read_b128 off a 16-byte boundary replays).  Threads tid, tid + nt, ... share the work; every dword
+// of [dst, dst + n) is written exactly once and nothing outside it, so neighbouring spans of other workgroups never race.
+// (tests/test_conditioned_rows.py restates the arithmetic.)
+__device__ __forceinline__ void store_span(const float *src, float *dst, int n, int tid, int nt) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const int phase = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3);
+    const int head = min((4 - phase) & 3, n);  // single dwords in front of the first boundary
+    const int body = (n - head) >> 2;          // whole 16-byte pieces
+    const int edge = n - body * 4;             // single dwords in all: head + tail, <= 6
+    const float *s = src + head;
+    f4 *o = reinterpret_cast<f4 *>(dst + head);
+    for (int q = tid; q < body; q += nt) {
+        const f4 v = {s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]};
+        __builtin_nontemporal_store(v, o + q);
+    }
+    for (int e = tid; e < edge; e += nt) {
+        const int k = e < head ? e : e + body * 4;
+        __builtin_nontemporal_store(src[k], dst + k);
+    }
+}
+
 }  // namespace gd

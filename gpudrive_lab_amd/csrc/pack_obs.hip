@@ -36,8 +36,12 @@ __device__ __forceinline__ float pack_element(const float *self, const float *pa
 }
 
 // ROWS (gd_attach_packed_rows): one workgroup per learner row, blockIdx.x; out is [n_rows][D] and row r is slot slot_of_row[r].
-template <int A_T, bool ROWS = false>
+// COND (gd_attach_packed_rows_conditioned, with ROWS): out is [n_rows][D + 3], the conditioned row ego 6 | the slot's 3 weights
+// (DevSim::pack_weights) | partners | roads.  Its odd pitch leaves the row at any 16-byte phase: it is laid out in LDS and
+// leaves through store_span (pack_cols.hpp), which writes exactly the row's own dwords.
+template <int A_T, bool ROWS = false, bool COND = false>
 __global__ __launch_bounds__(256) void k_pack_obs(DevSim d, float *out) {
+    static_assert(ROWS || !COND, "the conditioned layout exists for the learner rows only");
     constexpr int D = 6 + (A_T - 1) * 6 + K * 13;
     static_assert(D % 4 == 0 && (K * 9) % 4 == 0, "rows are whole float4 groups");
     constexpr int Q = D / 4, NP = (A_T - 1) * 9, NR = K * 9;
@@ -54,6 +58,17 @@ __global__ __launch_bounds__(256) void k_pack_obs(DevSim d, float *out) {
         const float4 *rsrc = reinterpret_cast<const float4 *>(d.agent_map + agent * NR);
         for (int t = tid; t < NR / 4; t += 256) reinterpret_cast<float4 *>(s_road)[t] = rsrc[t];
         __syncthreads();
+        if constexpr (COND) {
+            constexpr int R = D + 3;
+            __shared__ float s_row[R];
+            const float *wt = d.pack_weights + agent * 3;
+            for (int j = tid; j < R; j += 256)
+                s_row[j] = j < 6 ? pack_ego_col(s_self, j) : j < 9 ? wt[j - 6] : pack_element<A_T>(s_self, s_partner, s_road, j - 3);
+            __syncthreads();
+            store_span(s_row, out + orow * R, R, tid, 256);
+            __syncthreads();
+            continue;
+        }
         for (int q = tid; q < Q; q += 256) {
             float4 v;
             v.x = pack_element<A_T>(s_self, s_partner, s_road, 4 * q + 0);
@@ -199,8 +214,15 @@ void launch_pack_obs(const DevSim &d, hipStream_t st, float *out) {
     else hipLaunchKernelGGL(k_pack_obs<128>, dim3(d.W, GD_PACK_PARTS), dim3(256), 0, st, d, out);
 }
 
-void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out) {
+void launch_pack_obs_rows(const DevSim &d, hipStream_t st, float *out, const float *weights) {
     if (d.n_rows == 0) return;
+    if (weights) {  // the conditioned rows
+        DevSim dc = d;
+        dc.pack_weights = weights;
+        if (d.A == 64) hipLaunchKernelGGL((k_pack_obs<64, true, true>), dim3(d.n_rows), dim3(256), 0, st, dc, out);
+        else hipLaunchKernelGGL((k_pack_obs<128, true, true>), dim3(d.n_rows), dim3(256), 0, st, dc, out);
+        return;
+    }
     if (d.A == 64) hipLaunchKernelGGL((k_pack_obs<64, true>), dim3(d.n_rows), dim3(256), 0, st, d, out);
     else hipLaunchKernelGGL((k_pack_obs<128, true>), dim3(d.n_rows), dim3(256), 0, st, d, out);
 }

@@ -11,12 +11,17 @@ truncations and masks of the same N rows.  Here nothing is gathered after the fa
   - the episode kernel writes the four flat outputs through the same map (`EpisodeTracker` with learner rows).
 
 One step is therefore: indices in, flat tensors out, no host synchronisation and nothing sized by padding slots.  The rows are
-fixed until `resample()`; the tensors returned are the same buffers every step (overwritten in place)."""
+fixed until `resample()`; the tensors returned are the same buffers every step (overwritten in place).
+
+`ConditionedLearnerEnv` is the same loop for the reward-conditioned policy (reward_type "reward_conditioned"): its rows are
+[N, D + 3] = ego 6 | the slot's 3 reward weights | partners | road points, written in place by the same kernels
+(`direct_pack_rows(reward_weights=...)`); the weights the tracker redraws for the worlds it resets reach the rows on the
+device."""
 from itertools import product
 
 import torch
 
-from .episode import EpisodeTracker, check_warmup
+from .episode import DEFAULT_LB, DEFAULT_UB, EpisodeTracker, check_warmup, resolve_condition
 from .harness import default_action_values
 
 _DYNAMICS_NAMES = {0: "classic", 1: "bicycle", 2: "delta_local", 3: "state"}
@@ -36,6 +41,15 @@ def action_table(dynamics_model):
 _default_table = action_table  # (the constructor's argument of the same name shadows it)
 
 
+def _check_table(who, table):
+    """ValueError unless `table` is None (the default table) or a [n, 3] tensor with n >= 1.  Host only."""
+    if table is None:
+        return
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != 3 or table.shape[0] < 1:
+        raise ValueError("%s: action_table must be a [n, 3] tensor, got %s"
+                         % (who, tuple(table.shape) if isinstance(table, torch.Tensor) else type(table)))
+
+
 class DeviceLearnerEnv:
     def __init__(self, sim, action_table=None, only=True, init_steps=0, warmup="reset_worlds", **tracker_kwargs):
         """sim: a SimManager.  action_table: float32 [n, 3] (default: `action_table()` of the simulator's dynamics model).
@@ -44,18 +58,18 @@ class DeviceLearnerEnv:
         reset every world and advance it that many steps with the logged actions (PufferGPUDrive.__init__ /
         resample_scenario_batch through env.reset), and the worlds `step()` resets are warmed on the device (see
         `EpisodeTracker`).  tracker_kwargs go to `EpisodeTracker` (reward weights, reward_type, auto_reset, ...);
-        "reward_conditioned" is not supported here (its [N, D + 3] layout is a separate feature).  Arguments are checked
-        before anything reaches the device (ValueError)."""
+        "reward_conditioned" is not supported here: its [N, D + 3] rows are `ConditionedLearnerEnv`'s.  Arguments are
+        checked before anything reaches the device (ValueError)."""
         check_warmup(init_steps, warmup)
         if tracker_kwargs.get("reward_type") == "reward_conditioned":
             raise ValueError("DeviceLearnerEnv: reward_type='reward_conditioned' ([N, D + 3] rows) is not supported; "
-                             "use EpisodeTracker with packed_observations(reward_weights=...)")
-        if action_table is not None:
-            if not isinstance(action_table, torch.Tensor) or action_table.dim() != 2 or action_table.shape[1] != 3 \
-                    or action_table.shape[0] < 1:
-                raise ValueError("DeviceLearnerEnv: action_table must be a [n, 3] tensor, got %s"
-                                 % (tuple(action_table.shape) if isinstance(action_table, torch.Tensor) else type(action_table),))
-        else:
+                             "use ConditionedLearnerEnv")
+        _check_table(type(self).__name__, action_table)
+        self._init(sim, action_table, only, init_steps, warmup, tracker_kwargs)
+
+    def _init(self, sim, action_table, only, init_steps, warmup, tracker_kwargs):
+        """Everything after the argument checks: the first access to the simulator."""
+        if action_table is None:
             action_table = _default_table(_DYNAMICS_NAMES[int(sim._params.dynamicsModel)])
         self.sim = sim
         self.only = bool(only)
@@ -81,7 +95,7 @@ class DeviceLearnerEnv:
         self.controlled_agent_mask = self.tracker.controlled_agent_mask
         n = sim.set_learner_rows(self.controlled_agent_mask)  # the one host synchronisation, at setup
         self.num_agents = n
-        self.obs = sim.direct_pack_rows(only=self.only)
+        self.obs = self._attach()
         dev = self.table.device
         m = max(n, 1)  # (real allocations for n = 0)
         self.rewards = torch.zeros((m,), dtype=torch.float32, device=dev)[:n]
@@ -91,6 +105,10 @@ class DeviceLearnerEnv:
         b = self.tracker._bufs
         b.reward_rows, b.terminal_rows = self.rewards.data_ptr(), self.terminals.data_ptr()
         b.truncated_rows, b.mask_rows = self.truncations.data_ptr(), self.masks.data_ptr()
+
+    def _attach(self):
+        """Attach the row buffer the step's kernels write (after the learner rows are set); returns it."""
+        return self.sim.direct_pack_rows(only=self.only)
 
     def reset(self):
         """Empty the episode storage (PufferGPUDrive.reset, env_puffer.py:200-233) and return the [N, D] observations of
@@ -120,3 +138,45 @@ class DeviceLearnerEnv:
         self._setup()
         self._warm_up()
         return self.reset()
+
+
+class ConditionedLearnerEnv(DeviceLearnerEnv):
+    def __init__(self, sim, action_table=None, only=True, init_steps=0, warmup="reset_worlds", *, condition_mode="random",
+                 agent_type=None, **tracker_kwargs):
+        """`DeviceLearnerEnv` for the reward-conditioned policy (reward_type "reward_conditioned", gpudrive/networks/
+        late_fusion.py:104-110): `obs` is [N, D + 3] = ego 6 | the slot's 3 reward weights | partners | road points
+        (env_torch.py:756-810), `packed_observations(reward_weights=reward_weights_tensor)[mask]` bit for bit, written in
+        place by the step's kernels.  condition_mode / agent_type: how the tracker draws every world's weights, at
+        construction and for every world it resets ("random", "preset" with a preset name, "fixed" with a [3] tensor; see
+        `EpisodeTracker`).  tracker_kwargs go to `EpisodeTracker`; a reward_type other than "reward_conditioned" is refused.
+        Arguments are checked before anything reaches the device (ValueError)."""
+        check_warmup(init_steps, warmup)
+        rt = tracker_kwargs.pop("reward_type", "reward_conditioned")
+        if rt != "reward_conditioned":
+            raise ValueError("ConditionedLearnerEnv: reward_type must be 'reward_conditioned', got %r (DeviceLearnerEnv "
+                             "takes the others)" % (rt,))
+        lb = tracker_kwargs.get("reward_weight_lb", DEFAULT_LB)
+        ub = tracker_kwargs.get("reward_weight_ub", DEFAULT_UB)
+        if len(tuple(lb)) != 3 or len(tuple(ub)) != 3:
+            raise ValueError("reward_weight_lb / reward_weight_ub need three components (collision, goal_achieved, off_road)")
+        resolve_condition(condition_mode, agent_type, lb, ub)
+        _check_table(type(self).__name__, action_table)
+        self.condition_mode, self.agent_type = condition_mode, agent_type
+        self._init(sim, action_table, only, init_steps, warmup,
+                   dict(tracker_kwargs, reward_type="reward_conditioned", condition_mode=condition_mode, agent_type=agent_type))
+
+    def _attach(self):
+        return self.sim.direct_pack_rows(only=self.only, reward_weights=self.tracker.reward_weights_tensor)
+
+    @property
+    def reward_weights_tensor(self):
+        """[W, A, 3] float32: every agent slot's (collision, goal_achieved, off_road) weights, the tracker's tensor."""
+        return self.tracker.reward_weights_tensor
+
+    def set_reward_weights(self, worlds=None, condition_mode=None, agent_type=None):
+        """New weights for the listed worlds (None: all), `EpisodeTracker.set_reward_weights`; condition_mode None: the
+        environment's own mode and agent_type.  The rows' weight columns follow on the device.  Returns
+        `reward_weights_tensor`."""
+        if condition_mode is None:
+            condition_mode, agent_type = self.condition_mode, self.agent_type
+        return self.tracker.set_reward_weights(worlds, condition_mode=condition_mode, agent_type=agent_type)

@@ -403,23 +403,34 @@ class SimManager:
         self._learner_mask = None
         self._n_rows = None
 
-    def direct_pack_rows(self, only=True, out=None):
+    def direct_pack_rows(self, only=True, out=None, reward_weights=None):
         """Extension: `direct_pack()` for the learner rows only.  From now on every step / reset pass writes the packed row
         of learner row r into row r of the returned [n_rows, D] tensor -- `packed_observations()[mask]`, bit for bit -- and
         no packed row for any other slot.  `only=True`: the raw partner / road rows are not written either, and
         `packed_observations()` raises NotImplementedError while the buffer is attached.  Replaces a `direct_pack()`
-        buffer; `direct_pack_off()` detaches it."""
+        buffer; `direct_pack_off()` detaches it.
+        reward_weights: a [W, A, 3] float32 device tensor (EpisodeTracker.reward_weights_tensor): the rows of the
+        reward-conditioned policy instead, [n_rows, D + 3] = `packed_observations(reward_weights=...)[mask]`, bit for bit.
+        The tracker's redraws of these weights reach the rows' weight columns on the device."""
         import torch
         n = getattr(self, "_n_rows", None)
         if n is None:
             raise ValueError("direct_pack_rows: set the learner rows first (set_learner_rows)")
         D = 6 + (self._A - 1) * 6 + kMaxAgentMapObservationsCount * 13
+        if reward_weights is not None:
+            wt = reward_weights
+            assert wt.is_cuda and wt.is_contiguous() and wt.dtype == torch.float32 and tuple(wt.shape) == (self._W, self._A, 3)
+            D += 3
         if out is None:
             out = torch.empty((max(n, 1), D), dtype=torch.float32, device=self._device)  # (a real allocation for n = 0)
         assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() >= n * D and out.numel() > 0
         self._bind_stream()
-        _capi.check(self._L.gd_attach_packed_rows(self._h, out.data_ptr(), out.numel() * 4, 1 if only else 0),
-                    "gd_attach_packed_rows")
+        if reward_weights is not None:
+            _capi.check(self._L.gd_attach_packed_rows_conditioned(self._h, out.data_ptr(), out.numel() * 4, 1 if only else 0,
+                                                                  wt.data_ptr()), "gd_attach_packed_rows_conditioned")
+        else:
+            _capi.check(self._L.gd_attach_packed_rows(self._h, out.data_ptr(), out.numel() * 4, 1 if only else 0),
+                        "gd_attach_packed_rows")
         if getattr(self, "_direct", None) is not None:  # replaced
             self._packed = self._direct = None
         self._direct_rows = out

@@ -189,6 +189,13 @@ int gd_set_learner_rows(gd_sim *sim, const uint8_t *mask, int32_t n_rows);
  * raw rows are stale, and there is no [W][A][D] buffer to copy from).  GD_ERR_INVALID without learner rows;
  * GD_ERR_UNSUPPORTED where gd_attach_packed is. */
 int gd_attach_packed_rows(gd_sim *sim, float *out, int64_t out_bytes, int32_t only);
+/* gd_attach_packed_rows for the reward-conditioned policy: out is [n_rows][D + 3] f32, contiguous, and learner row r is row
+ * slot_of_row[r] of gd_pack_observations_conditioned(weights) bit for bit -- ego 6 | the slot's 3 weights | partners | road
+ * points -- after every step and every reset pass.  weights: the [W][A][3] device tensor the episode tracker keeps
+ * (gd_episode_buffers.reward_weights); gd_episode_step's redraw of reset worlds and gd_episode_draw_weights given that same
+ * pointer also rewrite the weight columns of the learner rows of the worlds they draw.  Weights changed any other way reach
+ * a row when its head is next written.  Every other rule of gd_attach_packed_rows applies; weights = NULL is GD_ERR_INVALID. */
+int gd_attach_packed_rows_conditioned(gd_sim *sim, float *out, int64_t out_bytes, int32_t only, const float *weights);
 /* Discrete actions decoded on the device: action[slot_of_row[r]][0..3) = table[indices[r]] for every learner row r, what
  * _apply_actions + _copy_actions_to_simulator do with a [N] index tensor for classic, bicycle and delta_local
  * (gpudrive/env/env_torch.py:615-664).  indices: device int64 [n_rows]; table: device f32 [n_actions][3].  Other slots are

@@ -12,7 +12,13 @@ around every launch, steps kernel by kernel), and the bytes of both observation 
 imported, not changed.  --init-steps k: both paths warm every world k steps at setup and every world they reset on the
 device (EpisodeTracker / DeviceLearnerEnv init_steps; --warmup-scope picks the scope).  --reset-at n: before the timing the
 worlds are advanced by log playback so that their episodes end at step n of the timed window (default: no advance, as
-before).  tools/learner_step.py [--worlds 1024] [--steps 50] [--warmup 10] [--init-steps 0] [--reset-at -1]"""
+before).
+
+--reward-type reward_conditioned times the reward-conditioned learner's [N, D + 3] rows two ways instead:
+  (a) DeviceLearnerEnv's [N, D] rows with the conditioned tracker, then the torch assembly: index_select of the weights by the
+      slot index (computed once at setup) and torch.cat into [N, D + 3];
+  (b) ConditionedLearnerEnv.step: the rows written as [N, D + 3] by the step's kernels.
+tools/learner_step.py [--worlds 1024] [--steps 50] [--warmup 10] [--init-steps 0] [--reset-at -1] [--reward-type T]"""
 import argparse
 import json
 import os
@@ -25,7 +31,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from gpudrive_lab_amd.episode import EpisodeTracker  # noqa: E402
-from gpudrive_lab_amd.learner import DeviceLearnerEnv, action_table  # noqa: E402
+from gpudrive_lab_amd.learner import ConditionedLearnerEnv, DeviceLearnerEnv, action_table  # noqa: E402
 
 WORKLOAD = "ppo_default"
 
@@ -65,6 +71,55 @@ def kernel_ms(sim, step, steps):
     return out
 
 
+def conditioned(args, res, table, idx_for, pre):
+    """(a) [N, D] rows + torch assembly, (b) ConditionedLearnerEnv; both with the conditioned tracker."""
+    k = args.init_steps
+    sim, A = make(args.worlds)
+    D = 6 + (A - 1) * 6 + 200 * 13
+    # DeviceLearnerEnv refuses reward_conditioned at its front door (the rows it writes are [N, D]); its setup takes it
+    env = DeviceLearnerEnv.__new__(DeviceLearnerEnv)
+    env._init(sim, None, True, k, args.warmup_scope, dict(reward_type="reward_conditioned"))
+    if pre > 0:
+        sim.advance_log_playback(pre)
+    N = env.num_agents
+    idx = idx_for(N)
+    slots = env.controlled_agent_mask.view(-1).nonzero().squeeze(1)  # setup: the one sync
+    wflat = env.tracker.reward_weights_tensor.view(-1, 3)
+    obs = torch.empty((N, D + 3), dtype=torch.float32, device="cuda")
+
+    def step_a():
+        rows, r, t, u, m = env.step(idx)
+        torch.cat((rows[:, :6], wflat.index_select(0, slots), rows[:, 6:]), 1, out=obs)
+        return obs, r, t, u, m
+
+    res["rows"] = N
+    res["a_ms_per_step"] = timed(step_a, args.steps, args.warmup)
+    res["a_kernels_ms"] = kernel_ms(sim, step_a, args.steps)
+    res["a_obs_bytes"] = N * (2 * D + 3) * 4
+    sim.close()
+    del sim, env, obs, wflat
+    torch.cuda.empty_cache()
+
+    sim, A = make(args.worlds)
+    env = ConditionedLearnerEnv(sim, init_steps=k, warmup=args.warmup_scope)
+    assert env.num_agents == N
+    if pre > 0:
+        sim.advance_log_playback(pre)
+
+    def step_b():
+        return env.step(idx)
+
+    w0 = sim.stat(46)
+    res["b_ms_per_step"] = timed(step_b, args.steps, args.warmup)
+    res["b_worlds_warmed"] = sim.stat(46) - w0
+    res["b_episodes"] = env.pop_stats().get("num_completed_episodes", 0)
+    res["b_kernels_ms"] = kernel_ms(sim, step_b, args.steps)
+    res["b_obs_bytes"] = N * (D + 3) * 4
+    sim.close()
+    res["b_over_a"] = res["b_ms_per_step"] / res["a_ms_per_step"]
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worlds", type=int, default=1024)
@@ -73,6 +128,7 @@ def main():
     ap.add_argument("--init-steps", type=int, default=0)
     ap.add_argument("--warmup-scope", default="reset_worlds", choices=("reset_worlds", "all_worlds"))
     ap.add_argument("--reset-at", type=int, default=-1)
+    ap.add_argument("--reward-type", default="weighted_combination", choices=("weighted_combination", "reward_conditioned"))
     args = ap.parse_args()
     k = args.init_steps
     # log-playback steps before the timing: the episode (91 - k learner steps after the setup's warm-up) ends at step
@@ -82,6 +138,10 @@ def main():
     table = action_table("classic").cuda()
     res = dict(tool="tools/learner_step.py", workload=WORKLOAD, worlds=args.worlds, steps=args.steps, warmup=args.warmup,
                init_steps=k, warmup_scope=args.warmup_scope, reset_at=args.reset_at, source_stamp=bench.source_stamp())
+    if args.reward_type == "reward_conditioned":
+        res["reward_type"] = args.reward_type
+        conditioned(args, res, table, lambda n: torch.randint(0, table.shape[0], (n,), device="cuda", generator=gen), pre)
+        return
 
     # (a) full direct pack + torch decode + gathers
     sim, A = make(args.worlds)
