@@ -2,7 +2,8 @@
 """Benchmark driver of the MI355X-native GPUDrive step engine (the `headless` counterpart,
 reference src/headless.cpp:125-155).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W            # the headline figure alone
+    python bench.py --gpus N --steps K --warmup W --full     # ... and everything else the benchmark measures
 
 One "step" = one pass of the hot path (movement -> collision -> reward/done -> self / partner /
 k-NN road observations) over every world of the rank, with seeded random actions already resident
@@ -11,25 +12,29 @@ in HBM, and a reset of all worlds every 91 steps (episode length).  Prints ONE J
 Workload (BASELINE.json configs[1]): 1024 worlds x 64 agents per GPU, classic bicycle dynamics,
 63-partner + 200-road-point k-NN observation, radius 50, collisions ignored.  Primary: the seeded
 synthetic exact-64 scenes of SURVEY.md section 8d (64 live agents, 4096 road segments per world).
-Secondary (reported under "other_workloads"): the committed Waymo scenes tiled round-robin.
 
-Two stretches of K steps per workload, back to back on the same simulator:
-  1. the TIMED REGION (`ms_per_step`, `value`): `step()` exactly as a user calls it -- the step's kernels replayed from
-     the captured hipGraph, no instrumentation;
-  2. the same K steps again with HIP events on the engine's stream around every launch (`gd_kernel_timing_*`: the
-     kernels are then launched one by one): `kernels`, `roofline.avg_kernel_us`, and that stretch's own wall clock
-     `ms_per_step_events`, which the kernel averages add up to.
-Each stretch starts at the first step of an episode (after untimed spin-up steps, `spin_up_steps` in the line), so that it
-holds K // 91 episode resets in every run (`timed_region.episode_resets`).
-With N > 1 ranks a further stretch measures BASELINE configs[3]'s observation all-gather (RCCL), overlapped
-with the following step (`allgather` in the line; `--gather none` skips it).  `--headless` adds the two FPS lines of the
-reference's own benchmark CLI (src/headless.cpp:145-155) on stderr.
+A plain run builds the primary workload's simulator (or that of each workload an explicit `--workloads` names), runs the W
+warm-up steps and times the K steps of the TIMED REGION (`ms_per_step`, `value`): `step()` exactly as a user calls it -- the
+step's kernels replayed from the captured hipGraph, no instrumentation.  It starts at the first step of an episode (after
+untimed spin-up steps, `spin_up_steps` in the line), so that it holds K // 91 episode resets in every run.  Then
+`--dump-outputs` writes what the primary's last step handed its caller, and the line is printed.
+
+`--full` adds, for every workload of `--workloads` (default: the primary and 14 others, reported under "other_workloads"):
+  - the same K steps again with HIP events on the engine's stream around every launch (`gd_kernel_timing_*`: the kernels
+    are then launched one by one): `kernels`, `roofline`, `other_rooflines`, and that stretch's own wall clock
+    `ms_per_step_events`, which the kernel averages add up to;
+  - with N > 1 ranks, a stretch that measures BASELINE configs[3]'s observation all-gather (RCCL), overlapped with the
+    following step (`allgather` in the line; `--gather none` skips it);
+and after them the CPU port of the reference algorithm on the host (`cpu_baseline`; `--no-cpu-baseline` skips it).
+`--headless` adds the two FPS lines of the reference's own benchmark CLI (src/headless.cpp:145-155) on stderr.
 """
+import atexit
 import argparse
 import gc
 import hashlib
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -67,7 +72,9 @@ KEEP_GC = os.environ.get("GPUDRIVE_BENCH_KEEP_GC") == "1"
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 EPISODE = 91
-
+PRIMARY = "synthetic"
+FULL_WORKLOADS = ("synthetic,waymo,cfg3,lidar,bev,rl_loop,synthetic_128,waymo_raw,synthetic_set,waymo_set,cfg3_set,"
+                  "synthetic_linear,waymo_linear,ppo_default,rl_loop_set")
 
 
 def source_stamp():
@@ -129,9 +136,21 @@ def params_for(workload):
     return kw
 
 
+_SCENE_DIR = []
+
+
+def scene_dir():
+    """A directory of this process's own for the synthetic scenes, removed when it exits: every run writes the scenes it
+    times, none reads what an earlier run left behind."""
+    if not _SCENE_DIR:
+        _SCENE_DIR.append(tempfile.mkdtemp(prefix="gpudrive_amd_bench_scenes_"))
+        atexit.register(shutil.rmtree, _SCENE_DIR[0], True)
+    return _SCENE_DIR[0]
+
+
 def scenes_for(workload, worlds, rank, agents=64):
     if scene_family(workload) in ("synthetic", "rl_loop"):
-        d = os.path.join(tempfile.gettempdir(), "gpudrive_amd_bench_scenes" + ("" if agents == 64 else "_%d" % agents))
+        d = os.path.join(scene_dir(), "agents_%d" % agents)
         paths = synth.write_scenes(d, [rank * 1000 + i for i in range(8)], n_agents=agents)
         return [paths[i % len(paths)] for i in range(worlds)]
     return sharding.scene_list_for_rank(WAYMO, worlds, rank)
@@ -327,8 +346,25 @@ def _bench_workload(name, args, rank, local_rank, world, device):
                               raw_rows=not direct)
     elapsed = sharding.reduce_max(local_elapsed, device)
     elapsed_min = -sharding.reduce_max(-local_elapsed, device)
-    # ---- 2. the same K steps again with HIP events around every kernel launch (kernel by kernel); a few untimed steps
-    # first so that nothing of the switch (event creation, first plain launches) lands in the stretch ----
+    total_live = sharding.reduce_sum(live, device)
+    res = dict(
+        workload=name, seconds=elapsed, ms_per_step=1e3 * elapsed / args.steps,
+        ms_per_step_min_rank=1e3 * elapsed_min / args.steps,
+        knn_order=knn_order,
+        live_agents_per_rank=live, road_entities_per_rank=roads, init_seconds=init_s,
+        agent_steps_per_s=total_live * args.steps / elapsed,
+        padded_agent_steps_per_s=world * args.worlds * args.agents * args.steps / elapsed,
+        timed_region=dict(graph_steps=graph_steps, plain_steps=plain_steps, episode_resets=args.steps // EPISODE),
+        dump_outputs=dumped,
+        worlds=args.worlds, packed_observation="written by the step (gd_attach_packed, raw partner / road rows not written)" if direct
+        else ("second pass over the raw tensors (k_pack_obs)" if tracker is not None else None),
+    )
+    if not args.full:  # a plain run: the timed region is all it measures
+        res.update(gc_ms_in_timed_stretches=gc_ms[0], spin_up_steps=spin_steps[0], engine=engine_counters(sim, name))
+        sim.close()
+        return res
+    # ---- 2. (--full) the same K steps again with HIP events around every kernel launch (kernel by kernel); a few untimed
+    # steps first so that nothing of the switch (event creation, first plain launches) lands in the stretch ----
     sim.kernel_timing(True)
     k = run_steps(sim, batches, all_worlds, 3, start=k, tracker=tracker)
     # the sums are zeroed after the spin-up and the alignment steps, right before the barrier and t0: `launches` == K
@@ -336,20 +372,7 @@ def _bench_workload(name, args, rank, local_rank, world, device):
     k, ev_elapsed = timed_stretch(k, pre_t0=lambda: (sim.kernel_timing(True), sim.stat(30)))  # (reading the skip counter zeroes it)
     ev_elapsed = sharding.reduce_max(ev_elapsed, device)
     rows_skipped = sim.stat(30)  # agents whose road rows were left in place over the events stretch (pose bits unchanged)
-    total_live = sharding.reduce_sum(live, device)
-    res = dict(
-        workload=name, seconds=elapsed, ms_per_step=1e3 * elapsed / args.steps,
-        ms_per_step_events=1e3 * ev_elapsed / args.steps,
-        ms_per_step_min_rank=1e3 * elapsed_min / args.steps,
-        knn_order=knn_order,
-        live_agents_per_rank=live, road_entities_per_rank=roads, init_seconds=init_s,
-        agent_steps_per_s=total_live * args.steps / elapsed,
-        padded_agent_steps_per_s=world * args.worlds * args.agents * args.steps / elapsed,
-        timed_region=dict(graph_steps=graph_steps, plain_steps=plain_steps, episode_resets=args.steps // EPISODE),
-        gc_ms_in_timed_stretches=gc_ms[0], spin_up_steps=spin_steps[0], dump_outputs=dumped,
-        worlds=args.worlds, packed_observation="written by the step (gd_attach_packed, raw partner / road rows not written)" if direct
-        else ("second pass over the raw tensors (k_pack_obs)" if tracker is not None else None),
-    )
+    res.update(ms_per_step_events=1e3 * ev_elapsed / args.steps, gc_ms_in_timed_stretches=gc_ms[0], spin_up_steps=spin_steps[0])
     road_kernel = "k_map_obs_linear" if linear else "k_map_obs+k_map_rows"
     names = {0: "k_world_step", 1: road_kernel}
     if workload == "lidar":
@@ -476,18 +499,25 @@ def _bench_workload(name, args, rank, local_rank, world, device):
     res["live_agents_with_roads_in_reach"] = int((amap[..., 6] > 0).any(dim=-1).sum().item())
     res["kernels_sum_us"] = sum(v["avg_us"] for v in kt.values())
     res["overlapped_kernels"] = overlapped
-    res["engine"] = dict(graph_steps=sim.stat(0), plain_steps=sim.stat(1), graph_captures=sim.stat(2),
-                         set_order_rows_fused=sim.stat(3), set_order_agents_per_wave=sim.stat(4),
-                         road_kernel_agents_per_wave=sim.stat(6), rank_audit_violations=sim.stat(21),
-                         schedule_env={k: os.environ[k] for k in ("GPUDRIVE_NO_GRAPH", "GPUDRIVE_SET_FUSED_ROWS",
-                                                                   "GPUDRIVE_SET_AGENTS_PER_WAVE") if k in os.environ})
+    res["engine"] = engine_counters(sim, name)
     # ---- BASELINE configs[3]: observation all-gather over RCCL, overlapped with the next step ----
-    if res["engine"]["rank_audit_violations"] != 0:  # an index of the rank path left its array (clamped on the device): no number of this run counts
-        raise SystemExit("bench.py: %s: the rank path's bounds audit counted %d violations (gd_stat 21)" % (name, res["engine"]["rank_audit_violations"]))
     if world > 1 and args.gather != "none" and name == args.workloads.split(",")[0]:
         res["allgather"] = gather_stretch(sim, batches, all_worlds, args, k, device, world)
     sim.close()
     return res
+
+
+def engine_counters(sim, name):
+    """The engine's own counters at the end of a workload's run; a run in which the rank path's bounds audit counted a
+    violation (an index left its array and was clamped on the device) ends here: no number of it counts."""
+    eng = dict(graph_steps=sim.stat(0), plain_steps=sim.stat(1), graph_captures=sim.stat(2),
+               set_order_rows_fused=sim.stat(3), set_order_agents_per_wave=sim.stat(4),
+               road_kernel_agents_per_wave=sim.stat(6), rank_audit_violations=sim.stat(21),
+               schedule_env={k: os.environ[k] for k in ("GPUDRIVE_NO_GRAPH", "GPUDRIVE_SET_FUSED_ROWS",
+                                                         "GPUDRIVE_SET_AGENTS_PER_WAVE") if k in os.environ})
+    if eng["rank_audit_violations"] != 0:
+        raise SystemExit("bench.py: %s: the rank path's bounds audit counted %d violations (gd_stat 21)" % (name, eng["rank_audit_violations"]))
+    return eng
 
 
 def gather_stretch(sim, batches, all_worlds, args, k, device, world):
@@ -632,16 +662,20 @@ def main():
     ap.add_argument("--worlds", type=int, default=1024, help="worlds per GPU")
     ap.add_argument("--agents", type=int, default=64, choices=(64, 128))
     ap.add_argument("--roofline-steps", type=int, default=0, help="ignored (kept for old command lines): kernels are timed over the timed steps themselves")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline figure: every workload of --workloads (default: all of them), "
+                         "HIP-event kernel times and roofline figures from a second stretch of the K steps, the all-gather stretch "
+                         "with N > 1 ranks, and the CPU baseline.  Without it a run times the primary workload's K steps alone")
     ap.add_argument("--gather", default="compact", choices=("none", "raw", "compact"),
-                    help="N > 1 only: after the timed region, a stretch with the observation all-gather of BASELINE configs[3] "
+                    help="--full, N > 1 only: after the timed region, a stretch with the observation all-gather of BASELINE configs[3] "
                          "(raw = every agent slot's packed observation, compact = controlled agents only), overlapped with the next step")
     ap.add_argument("--gather-payload", default="packed", choices=("packed", "raw_rows"),
                     help="what the all-gather stretch sends: the packed, normalised observation (6 + (A - 1) * 6 + 200 * 13 floats per "
                          "agent) or the exported self / partner / road rows it is made of (8 + (A - 1) * 9 + 200 * 9 floats: a quarter fewer bytes)")
     ap.add_argument("--gather-steps", type=int, default=30)
-    ap.add_argument("--workloads", default="synthetic,waymo,cfg3,lidar,bev,rl_loop,synthetic_128,waymo_raw,synthetic_set,waymo_set,cfg3_set,"
-                                            "synthetic_linear,waymo_linear,ppo_default,rl_loop_set",
-                    help="first = primary; synthetic | waymo | cfg3 | lidar (Waymo tiles + 360-degree LiDAR) | bev | rl_loop | "
+    ap.add_argument("--workloads", default=None,
+                    help="default: %s alone, with --full %s.  " % (PRIMARY, FULL_WORKLOADS) +
+                         "First = primary; synthetic | waymo | cfg3 | lidar (Waymo tiles + 360-degree LiDAR) | bev | rl_loop | "
                          "waymo_raw (the Waymo tiles with unreduced polylines, the setting of the reference's C++ tests); "
                          "a _128 suffix = 128 agent slots per world (the fork's kMaxAgentCount), a _set suffix = the same scenes "
                          "in set order (knn_order 1), a _linear suffix = the same scenes with the linear road selection (the "
@@ -661,7 +695,7 @@ def main():
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="--dry-run only: this rank leaves with exit code 3 after the ranks were counted (tests of the launch path's exit code, with or without a GPU)")
     ap.add_argument("--headless", action="store_true",
                     help="also print the reference CLI's two lines (src/headless.cpp:145-155) for the primary workload on stderr")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--dist-backend", default=None, choices=(None, "nccl", "gloo"),
                     help="default: nccl (RCCL); gloo + --single-device rehearses the N>1 path on one GPU")
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -672,6 +706,8 @@ def main():
     ap.add_argument("--knn-order", type=int, default=0, choices=(0, 1),
                     help="0 = reference heap order (default, elementwise parity); 1 = same row set, in the engine's own (grid-cell) order")
     args = ap.parse_args()
+    if args.workloads is None:
+        args.workloads = FULL_WORKLOADS if args.full else PRIMARY
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves, as CHILD processes
     # (torch.distributed.run, one rank per GPU, rendezvous on 127.0.0.1) and BEFORE anything here touches the GPU -- a
@@ -760,7 +796,7 @@ def main():
     results = [bench_workload(w, args, rank, local_rank, world, device) for w in args.workloads.split(",")]
     primary = results[0]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     dist_info = None
     if torch.distributed.is_initialized():
@@ -793,32 +829,36 @@ def main():
             "padded_agent_steps_per_s": primary["padded_agent_steps_per_s"],
             "timed_region": "step() as a user calls it: the step's kernels replayed from the captured hipGraph (%d graph / %d plain "
                             "steps), no instrumentation" % (primary["timed_region"]["graph_steps"], primary["timed_region"]["plain_steps"]),
-            "ms_per_step_events": primary["ms_per_step_events"],
             "gc_ms_in_timed_stretches": primary["gc_ms_in_timed_stretches"],
             "spin_up": "%g ms of untimed steps before each timed stretch (%d steps on the primary workload): after the idle world "
                        "build the GPU delays its first work by 10-90 ms in about one stretch of twelve" % (args.spin_ms, primary["spin_up_steps"]),
             "python_gc": "left alone (GPUDRIVE_BENCH_KEEP_GC=1)" if KEEP_GC else "collected before and disabled during each timed stretch",
-            "kernels_sum_us": primary["kernels_sum_us"],
-            "roofline": primary["roofline"],
-            "kernels": primary["kernels"],
-            "overlapped_kernels": primary["overlapped_kernels"],
-            "kernel_times": "HIP events around every launch of a second stretch of the same K steps right after the timed region "
-                            "(kernels launched one by one; its wall clock is ms_per_step_events)",
-            "other_rooflines": primary.get("other_rooflines"),
             "engine": dict(primary.get("engine", {}), source_stamp=source_stamp()),
             "distributed": dist_info,
-            "allgather": primary.get("allgather"),
-            "cpu_baseline": cpu,
             "other_workloads": [
                 {k: r[k] for k in ("workload", "knn_order", "worlds", "packed_observation", "agent_steps_per_s", "padded_agent_steps_per_s", "ms_per_step",
                                    "ms_per_step_events", "gc_ms_in_timed_stretches", "spin_up_steps", "overlapped_kernels", "kernels_sum_us", "live_agents_per_rank", "live_agents_with_roads_in_reach", "road_entities_per_rank",
-                                   "roofline", "kernels", "other_rooflines")}
+                                   "roofline", "kernels", "other_rooflines") if k in r}
                 for r in results[1:]],
             "dump_outputs": primary["dump_outputs"],
             "init_seconds": primary["init_seconds"],
             "live_agents_per_rank": primary["live_agents_per_rank"],
-            "live_agents_with_roads_in_reach": primary["live_agents_with_roads_in_reach"],
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "ms_per_step_events": primary["ms_per_step_events"],
+                "kernels_sum_us": primary["kernels_sum_us"],
+                "roofline": primary["roofline"],
+                "kernels": primary["kernels"],
+                "overlapped_kernels": primary["overlapped_kernels"],
+                "kernel_times": "HIP events around every launch of a second stretch of the same K steps right after the timed region "
+                                "(kernels launched one by one; its wall clock is ms_per_step_events)",
+                "other_rooflines": primary.get("other_rooflines"),
+                "allgather": primary.get("allgather"),
+                "cpu_baseline": cpu,
+                "live_agents_with_roads_in_reach": primary["live_agents_with_roads_in_reach"],
+            })
         print(json.dumps(line), flush=True)
         if args.headless:
             # the reference CLI's two lines (src/headless.cpp:145-155): FPS = steps * worlds / s, and its "Agent-Normalized

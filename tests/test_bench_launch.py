@@ -163,7 +163,7 @@ def test_dumped_outputs_do_not_depend_on_the_spin_up(tmp_path):
     lines = []
     for spin, d in (("0", "a"), ("200", "b")):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
-                            "--workloads", "synthetic", "--worlds", "64", "--no-cpu-baseline", "--spin-ms", spin,
+                            "--full", "--workloads", "synthetic", "--worlds", "64", "--no-cpu-baseline", "--spin-ms", spin,
                             "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
@@ -176,3 +176,48 @@ def test_dumped_outputs_do_not_depend_on_the_spin_up(tmp_path):
         x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
         assert x.dtype in (np.float32, np.float64) and x.shape[0] == 64
         assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), f
+
+
+def test_every_run_writes_the_scenes_it_times_and_removes_them():
+    """No run reads what an earlier run left behind: each process writes the synthetic scenes into a directory of its own,
+    which is gone when it exits."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    code = "import bench; p = bench.scenes_for('synthetic', 16, 0); print(p[0]); print(len(set(p)))"
+    seen = []
+    for _ in range(2):
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        path, distinct = r.stdout.split()[-2:]
+        assert int(distinct) == 8 and path.endswith(".json")
+        assert not os.path.exists(os.path.dirname(path)), path
+        seen.append(path)
+    assert seen[0] != seen[1]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_primary_workload_alone_and_dumps_what_a_full_run_dumps(tmp_path):
+    """Without --full a run times the primary workload and nothing else: its line has the headline figure and none of the
+    kernel times, rooflines, other workloads or CPU baseline that --full adds, and --dump-outputs writes the same arrays,
+    bit for bit, as a --full run with the same arguments."""
+    import numpy as np
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--workloads", "synthetic", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                            "--worlds", "64", "--dump-outputs", str(tmp_path / mode), *extra],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[mode] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["full"] is False and full["full"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "config"):
+        assert plain[k] == full[k], k
+    assert plain["steps"] == 7 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["other_workloads"] == [] and plain["engine"]["rank_audit_violations"] == 0
+    for k in ("ms_per_step_events", "kernels", "roofline", "other_rooflines", "cpu_baseline", "allgather"):
+        assert k not in plain and k in full, k
+    assert full["kernels"]["k_world_step"]["launches"] == 7
+    a, b = plain["dump_outputs"], full["dump_outputs"]
+    assert a["files"] == b["files"] and a["worlds"] == b["worlds"]
+    for f in a["files"]:
+        x, y = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8)), f

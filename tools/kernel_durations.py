@@ -9,7 +9,7 @@ out = os.path.join(root, "gpurun_out", "kd_tmp")
 subprocess.run(["rm", "-rf", out]); os.makedirs(out)
 env = dict(os.environ, GPUDRIVE_DEV="1", GPUDRIVE_AMD_LIB=os.path.join(root, "build", "expt", "expt_%s.so" % expt), TMPDIR="/tmp")
 subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", out, "--", "python3", os.path.join(root, "bench.py"), "--steps", "60", "--warmup", "10",
-                "--no-cpu-baseline", "--workloads", wl], env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=root)
+                "--full", "--no-cpu-baseline", "--workloads", wl], env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=root)
 rows = []
 for f in glob.glob(out + "/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):

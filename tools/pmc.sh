@@ -16,7 +16,7 @@ GROUPS_=(
 )
 i=0
 for G in "${GROUPS_[@]}"; do
-  rocprofv3 --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --steps 3 --warmup 1 --roofline-steps 1 --no-cpu-baseline "$@" > $OUT/bench_g$i.log 2>$OUT/err_g$i.log
+  rocprofv3 --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --full --steps 3 --warmup 1 --roofline-steps 1 --no-cpu-baseline "$@" > $OUT/bench_g$i.log 2>$OUT/err_g$i.log
   i=$((i+1))
 done
 python3 - <<PY

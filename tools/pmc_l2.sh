@@ -6,7 +6,7 @@ OUT=gpurun_out/pmc_l2
 rm -rf $OUT; mkdir -p $OUT
 i=0
 for G in "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TOTAL_ACCESSES_sum" "TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_READ_sum"; do
-  rocprofv3 --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --steps 4 --warmup 2 --spin-ms 0 --no-align --no-cpu-baseline "$@" > $OUT/bench_g$i.log 2>$OUT/err_g$i.log
+  rocprofv3 --pmc $G --output-format csv -d $OUT/g$i -- python3 bench.py --full --steps 4 --warmup 2 --spin-ms 0 --no-align --no-cpu-baseline "$@" > $OUT/bench_g$i.log 2>$OUT/err_g$i.log
   i=$((i+1))
 done
 python3 - <<PY

@@ -7,7 +7,7 @@ export GPUDRIVE_DEV=1 GPUDRIVE_AMD_LIB=$GRAFT_REPO_ROOT/build/expt/expt_diag.so
 [ -f "$GPUDRIVE_AMD_LIB" ] || { echo "build it first: tools/build_expt.sh diag -DGD_DIAG"; exit 1; }
 for D in ${PHASES:-1 2 3 4 5 0}; do
   OUT=gpurun_out/phase_$D; rm -rf $OUT; mkdir -p $OUT
-  GPUDRIVE_RANK_DBG=$D rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline --workloads synthetic > $OUT/bench.json 2>$OUT/err.log
+  GPUDRIVE_RANK_DBG=$D rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --workloads synthetic > $OUT/bench.json 2>$OUT/err.log
   python3 - <<PY
 import csv,glob
 for f in glob.glob("$OUT/**/*kernel_stats.csv", recursive=True):

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/trace_tmp
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --steps 91 --warmup 10 --no-cpu-baseline "$@" > $OUT/bench.json 2>$OUT/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 bench.py --full --steps 91 --warmup 10 --no-cpu-baseline "$@" > $OUT/bench.json 2>$OUT/err.log
 python3 - <<PY
 import csv,glob
 for f in glob.glob("$OUT/**/*kernel_stats.csv", recursive=True):

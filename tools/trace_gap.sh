@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/gap
 rm -rf $OUT; mkdir -p $OUT
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --workloads synthetic,waymo,cfg3,lidar > $OUT/plain.json 2>$OUT/plain.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --workloads synthetic,waymo,cfg3,lidar > $OUT/plain.json 2>$OUT/plain.err
 python3 - <<PY
 import json
 d=json.loads(open("$OUT/plain.json").read().strip().splitlines()[-1])
@@ -13,7 +13,7 @@ def show(w, ms, k): print("%-10s ms/step %.3f  kernels %s" % (w, ms, {n:round(v[
 show("synthetic", d["ms_per_step"], d["kernels"])
 for w in d["other_workloads"]: show(w["workload"], w["ms_per_step"], w["kernels"])
 PY
-rocprofv3 --hip-trace --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --workloads waymo > $OUT/traced.json 2>$OUT/traced.err
+rocprofv3 --hip-trace --kernel-trace --output-format csv -d $OUT/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --workloads waymo > $OUT/traced.json 2>$OUT/traced.err
 python3 - <<PY
 import csv,glob,collections
 api=[]
