@@ -99,11 +99,20 @@ class GdEpisodeBuffersRows(GdEpisodeBuffers):
     _fields_ = [(n, C.c_void_p) for n in ("reward_rows", "terminal_rows", "truncated_rows", "mask_rows")]
 
 
+class GdRecordBuffers(C.Structure):
+    """gd_record_buffers: the expert trajectory recorder's outputs and running state (device pointers; kernel_ms: host)."""
+    _fields_ = ([("row_slot", C.c_void_p), ("n_rows", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("obs", "actions", "dead_mask", "partner_mask", "road_mask", "ego_global_pos",
+                                           "ego_global_rot", "dead", "goal_achieved", "off_road", "veh_collision",
+                                           "any_alive")] +
+                [("kernel_ms", C.POINTER(C.c_float))])
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
-    "gd_expert_actions", "gd_advance_log_playback", "gd_episode_step", "gd_sync",
+    "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_episode_step", "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
@@ -168,6 +177,7 @@ def lib():
     L.gd_scene_cache_write.argtypes = [C.c_char_p, C.c_float, C.c_char_p]
     L.gd_expert_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gd_advance_log_playback.argtypes = [C.c_void_p, C.c_int32]
+    L.gd_record_expert.argtypes = [C.c_void_p, C.POINTER(GdRecordBuffers), C.c_int32]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

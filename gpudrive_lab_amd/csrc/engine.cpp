@@ -1401,6 +1401,51 @@ int gd_advance_log_playback(gd_sim *s, int32_t init_steps) {
     });
 }
 
+int gd_record_expert(gd_sim *s, const gd_record_buffers *b, int32_t n_steps) {
+    if (!s || !b) return fail(GD_ERR_INVALID, "gd_record_expert: null argument");
+    if (!b->row_slot || !b->obs || !b->actions || !b->dead_mask || !b->partner_mask || !b->road_mask || !b->ego_global_pos ||
+        !b->ego_global_rot || !b->dead || !b->goal_achieved || !b->off_road || !b->veh_collision || !b->any_alive)
+        return fail(GD_ERR_INVALID, "gd_record_expert: every buffer is required");
+    if (b->n_rows < 0) return fail(GD_ERR_INVALID, "gd_record_expert: n_rows must be >= 0");
+    if (n_steps < 1 || n_steps > GD_EPISODE_LEN)
+        return fail(GD_ERR_INVALID, "gd_record_expert: the expert trajectory has 91 steps, n_steps must be in [1, 91]");
+    if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
+        return fail(GD_ERR_INVALID, "gd_record_expert: the State dynamics model's actions have 10 columns, the dataset's have 3");
+    if (s->d.pack && s->d.pack_only)
+        return fail(GD_ERR_UNSUPPORTED, "gd_record_expert: a packed buffer is attached with only = 1: the raw rows are stale");
+    return guarded([&]() {
+        std::vector<hipEvent_t> ev;  // the optional diagnostic: a pair around every recorder launch
+        auto mark = [&]() {
+            if (!b->kernel_ms) return;
+            hipEvent_t e;
+            HIP_CHECK(hipEventCreate(&e));
+            ev.push_back(e);
+            HIP_CHECK(hipEventRecord(e, s->stream));
+        };
+        for (int t = 0; t <= n_steps; t++) {
+            mark();
+            gd::launch_record(s->d, s->stream, *b, t, t < n_steps);
+            HIP_CHECK(hipGetLastError());
+            mark();
+            if (t == n_steps) break;
+            gd::launch_set_log_actions(s->d, s->stream, t);
+            HIP_CHECK(hipGetLastError());
+            s->step();
+        }
+        if (b->kernel_ms) {
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            float sum = 0.f;
+            for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+                float ms = 0.f;
+                HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                sum += ms;
+            }
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+            *b->kernel_ms = sum;
+        }
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

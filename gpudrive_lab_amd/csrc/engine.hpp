@@ -228,5 +228,6 @@ void launch_learner_rows(hipStream_t st, const uint8_t *mask, size_t slots, int3
                          int32_t *count);  // learner.hip
 void launch_discrete_actions(const DevSim &d, hipStream_t st, const int64_t *indices, const float *table, int n_actions);  // learner.hip
 void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out);  // pack_obs.hip
+void launch_record(const DevSim &d, hipStream_t st, const gd_record_buffers &b, int t, bool pre);  // record.hip
 
 }  // namespace gd

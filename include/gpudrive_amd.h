@@ -215,6 +215,42 @@ int gd_expert_actions(gd_sim *sim, float *actions, int32_t action_cols, float *p
  * t = 0 .. init_steps-1 write the expert action of step t into action[:, :, :cols] of every agent slot
  * (env_torch.py:645-664) and step.  init_steps >= 91 is GD_ERR_INVALID (the reference raises ValueError). */
 int gd_advance_log_playback(gd_sim *sim, int32_t init_steps);
+/* Expert trajectory recorder: the imitation-learning dataset of save_trajectory (gpudrive/integrations/il/storage.py:10-109;
+ * read by baselines/il/il.py:71-84) written on the device.  Replaces its Python loop over every controlled agent inside the
+ * loop over 91 steps (storage.py:47-56: seven indexed tensor copies per agent and step) and the per-step get_dones / get_obs /
+ * get_road_mask / get_partner_mask / get_infos round trips (storage.py:60-80) by one kernel launch per time index between the
+ * steps of a log playback, with no host synchronisation inside the episode.  All pointers are device pointers owned by the
+ * caller; N = n_rows, A = max_agents, D = 6 + (A-1)*6 + 200*13; the time pitch is always 91.  The caller fills the defaults of
+ * storage.py:29-35 first (obs / actions / global 0, dead_mask 1, partner_mask 2, road_mask 1) and zeroes the running state:
+ * only live rows are written. */
+typedef struct gd_record_buffers {
+    const int32_t *row_slot;  /* [N] world * A + agent of every recorded row (cont_agent_mask.nonzero() order, storage.py:25);
+                               * a value outside [0, W * A) leaves its row untouched */
+    int32_t n_rows;
+    float *obs;               /* [N][91][D] the packed observation, bit for bit row row_slot[n] of gd_pack_observations */
+    float *actions;           /* [N][91][3] the logged action fed at that step (gd_expert_actions' columns) */
+    uint8_t *dead_mask;       /* [N][91] bool: the row was done BEFORE step t (storage.py:56) */
+    uint8_t *partner_mask;    /* [N][91][A-1] 0 a partner that acts, 1 a Static one with a non-zero packed row, 2 nobody
+                               * (env_torch.py:1224-1253) */
+    uint8_t *road_mask;       /* [N][91][200] bool: road row is padding (id -1, env_torch.py:1255-1272) */
+    float *ego_global_pos;    /* [N][91][2] absolute_self_observation columns 0, 1 */
+    float *ego_global_rot;    /* [N][91][1] absolute_self_observation column 7 */
+    /* running state, read and written: zero before the call */
+    uint8_t *dead;            /* [N] */
+    float *goal_achieved, *off_road, *veh_collision;  /* [N] sums of info columns 3 / 0 / 1 + 2, clamped to 1 (storage.py:75-80) */
+    int32_t *any_alive;       /* [92] 1 where some recorded row was alive before step t: iteration t of the reference's loop
+                               * exists (its `break`, storage.py:82-89); their sum is the number of iterations it runs */
+    /* optional diagnostic, HOST pointer: the summed duration of the recorder's launches in ms from events around each of
+     * them.  Non-NULL makes the call synchronise at its end. */
+    float *kernel_ms;
+} gd_record_buffers;
+/* For t in [0, n_steps): record time index t, write the logged action of step t into every agent slot (what
+ * gd_advance_log_playback does) and step; then the bookkeeping of the last step.  With n_steps < 91 the result is the prefix
+ * [0, n_steps) of the full recording (dead flags and accumulators as they stand after n_steps steps).  It does not reset: the
+ * caller does.  GD_ERR_INVALID: a null pointer, n_rows < 0, n_steps outside [1, 91], the State dynamics model (its actions
+ * have 10 columns; the dataset's have 3).  GD_ERR_UNSUPPORTED while a packed buffer is attached with only != 0 (the raw rows
+ * the observation is computed from are stale). */
+int gd_record_expert(gd_sim *sim, const gd_record_buffers *buffers, int32_t n_steps);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
