@@ -1563,6 +1563,19 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
         return GD_OK;
     }
 #endif
+#ifdef GD_CLOCKS
+    if (s && out && which >= 1000 && which < 1256) {  // k_knn_replay's phase clocks of the last selection (map_obs_rank.hip ReplayClock): rk_hist[256 + k]
+        *out = 0;
+        if (s->rk_alloc) {
+            int32_t v = 0;
+            (void)hipStreamSynchronize(s->stream);
+            if (hipMemcpy(&v, s->d.rk_hist + 256 + (which - 1000), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(GD_ERR_DEVICE, "gd_stat: reading the replay clocks failed");
+            *out = v;
+        }
+        return GD_OK;
+    }
+#endif
 #if defined(GD_DIAG) || defined(GD_CLOCKS)
     constexpr int32_t kLastStat = 20;
 #else

@@ -180,7 +180,7 @@ struct DevSim {
     float *rk_kt;          // [W][A][GD_RANK_KT] key at sorted slot 16 j (16 j < n), then the largest key at j = ceil(n / 16)
     uint32_t *rk_heap;     // [W][A][GD_RANK_HEAP_DW] the replayed heap array as rank pairs
     uint16_t *rk_cpe;      // [W][A][NCP] rank on top of the heap at every checkpoint of this selection
-    int32_t *rk_hist;      // [544] replay order: 256 bin counts, 256 bin starts, the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT)
+    int32_t *rk_hist;      // [544] replay order: 256 bin counts, [256..511] unused (-DGD_CLOCKS: k_knn_replay's phase clocks), the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT)
     int32_t *rk_ticket;    // [W][A] bin << 20 | place inside the bin (bit 30: fell back after taking it); -1 = not on the rank path this step; < -1: why
     int32_t *rk_order;     // [W][A] agents on the rank path, most candidates first
     int32_t *rk_list;      // [8][W][A] agents on the rank path, one list per XCD that scanned them (counts: rk_hist[528..535])

@@ -36,6 +36,7 @@
 
 #include "engine.hpp"
 #include "gd_math.hpp"
+#include "rank_heap.hpp"
 
 namespace gd {
 
@@ -944,16 +945,22 @@ __global__ __launch_bounds__(64, CAP_T > CAP ? 2 : 4) void k_knn_rank(DevSim d) 
 // wave is as fast alone on its SIMD as beside a second one; measured at 1024 x 64 (us): 64 per wave 458, 32 per wave (two
 // waves per SIMD) 492, 16 per wave 674; Waymo tiles 245 / 256 / 261 (tools/build_expt.sh awr32 -DGD_RANK_AWR=32)
 constexpr int AWR = GD_RANK_AWR;
+// (the same bytes are read and written as dwords and as halves: both types may alias, or the compiler is free to move a pair's
+// load over the store of one of its halves -- with make_heap's straight-line groups it did)
+typedef unsigned int __attribute__((may_alias)) heap_u32;
+typedef unsigned short __attribute__((may_alias)) heap_u16;
 struct RankHeap {
-    unsigned int *pr;  // this lane's column
+    heap_u32 *pr;  // this lane's column
     __device__ __forceinline__ unsigned int pair(int j) const { return pr[j * AWR]; }
     __device__ __forceinline__ unsigned int get(int g) const {
-        return reinterpret_cast<const unsigned short *>(pr + (g >> 1) * AWR)[g & 1];
+        return reinterpret_cast<const heap_u16 *>(pr + (g >> 1) * AWR)[g & 1];
     }
     __device__ __forceinline__ void set(int g, unsigned int v) const {
-        reinterpret_cast<unsigned short *>(pr + (g >> 1) * AWR)[g & 1] = (unsigned short)v;
+        reinterpret_cast<heap_u16 *>(pr + (g >> 1) * AWR)[g & 1] = (unsigned short)v;
     }
+    __device__ __forceinline__ void set_pair(int j, unsigned int v) const { pr[j * AWR] = v; }
 };
+static_assert(rank_heap::NPAIR == 128, "s_pair of k_knn_replay");
 
 // Replay order: the agents on the rank path sorted by candidate count, longest first (counting sort over 256 bins: k_knn_rank
 // takes a ticket in its bin, every workgroup of this kernel turns the bin counts into starts for itself -- 256 loads and a
@@ -979,6 +986,9 @@ __global__ __launch_bounds__(256) void k_knn_order(DevSim d) {
         for (int x = 0; x < 8; x++) d.rk_hist[528 + x] = 0;  // the next selection's lists of ranked agents start empty
         d.rk_hist[GD_RH_LONG] = 0;
     }
+#ifdef GD_CLOCKS
+    if (blockIdx.x == 0) d.rk_hist[256 + tl] = 0;  // k_knn_replay's phase clocks of this selection
+#endif
     __syncthreads();
     const int t = blockIdx.x * 256 + tl;
     if (t >= d.live_count) return;
@@ -988,15 +998,39 @@ __global__ __launch_bounds__(256) void k_knn_order(DevSim d) {
     d.rk_order[audited(d, s_start[(ticket >> 20) & 255] + (ticket & 0xfffff), d.W * d.A)] = i;
 }
 
+#ifdef GD_CLOCKS
+// -DGD_CLOCKS: ticks of the constant 100 MHz clock (s_memrealtime; s_memtime counts shader cycles, whose rate moves) per phase of
+// a replay wave -- 0 set-up (order, candidate count), 1 fill, 2 make_heap, 3 the rounds, 4 the heap's write-out -- kept per
+// launch in rk_hist[256..]: seven values (the phases, 1 if the wave ran the copy for equal keys, the total) for each of the
+// first 32 waves, which hold the longest agents; [480] waves on the equal-key copy, [481] waves that ran, [482] the longest
+// total of any wave, [483] of any wave on the equal-key copy, [484] of any other wave.  k_knn_order zeroes them;
+// gd_stat 1000 + k reads rk_hist[256 + k] (tools/replay_clocks.py).
+struct ReplayClock {
+    unsigned int prev, first, ph[5];
+    __device__ __forceinline__ void start() { first = prev = (unsigned int)__builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void mark(int n) {
+        const unsigned int t = (unsigned int)__builtin_amdgcn_s_memrealtime();
+        ph[n] = t - prev;
+        prev = t;
+    }
+};
+#define GD_RPHASE(n) rclk.mark(n)
+#else
+#define GD_RPHASE(n)
+#endif
 __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;
     const int lane = threadIdx.x;
+#ifdef GD_CLOCKS
+    ReplayClock rclk;
+    rclk.start();
+#endif
     if (blockIdx.x == 0)  // the bin counts of this selection have been read by every workgroup of k_knn_order: ready for the next
         for (int k = 0; k < 4; k++) d.rk_hist[k * 64 + lane] = 0;
     const int li = blockIdx.x * AWR + lane;
     constexpr int NPAIR = 128;  // pairs 0..K/2 hold the heap; K/2 + 1 .. 127 stay 0: the "children" of slots beyond the heap
     __shared__ unsigned int s_pair[NPAIR * AWR];
-    const RankHeap H{s_pair + (lane % AWR)};
+    const RankHeap H{reinterpret_cast<heap_u32 *>(s_pair) + (lane % AWR)};
     int i = 0, n = 0, has_tie = 0, is_long = 0;
     if (lane < AWR && li < d.rk_hist[512]) {
         i = d.rk_order[li];
@@ -1013,51 +1047,32 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
     const int tsh = is_long ? 6 : 5;             // log2 (candidates between its checkpoints)
 
     // ---- the first K candidates are roads 0..K-1 in order (src/knn.hpp:112-120) ----
+    // All 25 blocks of the agent's first K ranks are requested together and waited for once (one at a time they were 25 memory
+    // round trips in series in front of every wave's first round; k_knn_rank wrote the rows with streaming stores, so most
+    // of them come from HBM).  Every lane loads, idle ones too (they read a row that exists: their own or row 0).
+    const bool wave_ties = __ballot(on && has_tie) != 0ull;
+    GD_RPHASE(0);
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(E);
-        if (lane < AWR) {
-            H.pr[0] = 0u;
-            for (int j = K / 2; j < NPAIR; j++) H.pr[j * AWR] = 0u;
-        }
-#pragma clang loop unroll(disable)
-        for (int k = 0; k < K / 8; k++) {
-            const uint4 v = on ? stream_load(src + k) : make_uint4(0u, 0u, 0u, 0u);
-            const unsigned int wd[4] = {v.x, v.y, v.z, v.w};
+        unsigned int w[K / 2];
 #pragma unroll
-            for (int c = 0; c < 4; c++) {
-                if (lane < AWR) {
-                    H.set(k * 8 + c * 2 + 1, wd[c] & 0xffffu);
-                    H.set(k * 8 + c * 2 + 2, wd[c] >> 16);
-                }
-            }
+        for (int k = 0; k < K / 8; k++) {
+            const uint4 v = stream_load(src + k);
+            w[k * 4 + 0] = v.x;
+            w[k * 4 + 1] = v.y;
+            w[k * 4 + 2] = v.z;
+            w[k * 4 + 3] = v.w;
         }
+        if (lane < AWR) rank_heap::fill_pairs<K>(H, w);  // whole pairs; pair 0's low half, slot K + 1 and pairs K/2 + 1 .. 127: 0
     }
+    GD_RPHASE(1);
     // ---- make_heap, src/binary_heap.hpp:170-185: parents K/2 .. 1, each __adjust_heap(hole, len = K, value) ----
+    // (rank_heap.hpp: the sifts of one tree level in groups of eight, straight-line, two levels per LDS round trip)
     if (on) {
-#pragma clang loop unroll(disable)
-        for (int g = K / 2; g >= 1; g--) {
-            const unsigned int x = H.get(g);
-            int h = g;
-            while (2 * h + 1 <= K) {  // both children exist: take the larger one (the right one unless it is smaller)
-                const unsigned int p2 = H.pair(h);
-                const unsigned int kl = p2 & 0xffffu, kr = p2 >> 16;
-                const bool right = !rank_lt(kr, kl, tm);
-                H.set(h, right ? kr : kl);
-                h = 2 * h + (right ? 1 : 0);
-            }
-            if (2 * h == K) {  // a lone left child
-                H.set(h, H.get(K));
-                h = K;
-            }
-            while (h > g) {  // __push_heap towards the sift's own top
-                const unsigned int pv = H.get(h >> 1);
-                if (!rank_lt(pv, x, tm)) break;
-                H.set(h, pv);
-                h >>= 1;
-            }
-            H.set(h, x);
-        }
+        if (wave_ties) rank_heap::make_heap<K, true>(H, tm);
+        else rank_heap::make_heap<K, false>(H, tm);
     }
+    GD_RPHASE(2);
     unsigned int r[8];             // slots 1..7 (tree levels 0..2) live in registers during the replay; r[1] is heap[0]
 #pragma unroll
     for (int j = 1; j < 8; j++) r[j] = H.get(j);
@@ -1225,8 +1240,9 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
             if (p0 + TILE - 1 < n && (after & ((1 << tsh) - 1)) == 0) cpe[after >> tsh] = (unsigned short)r[1];
         }
     };
-    if (__ballot(on && has_tie) != 0ull) replay(std::true_type{});
+    if (wave_ties) replay(std::true_type{});
     else replay(std::false_type{});
+    GD_RPHASE(3);
 #ifdef GD_CLOCKS
     {
         const int tot_ins = wave_sum(n_ins), tot_cand = wave_sum(on ? n - K : 0), longest = wave_max(on ? n - K : 0);
@@ -1255,6 +1271,22 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
             stream_store(v, reinterpret_cast<uint4 *>(out + j));
         }
     }
+#ifdef GD_CLOCKS
+    GD_RPHASE(4);
+    if (lane == 0) {
+        const int total = (int)(rclk.prev - rclk.first);
+        if (blockIdx.x < 32) {
+            int *row = d.rk_hist + 256 + blockIdx.x * 7;
+            for (int k = 0; k < 5; k++) row[k] = (int)rclk.ph[k];
+            row[5] = wave_ties ? 1 : 0;
+            row[6] = total;
+        }
+        atomicAdd(&d.rk_hist[480], wave_ties ? 1 : 0);
+        atomicAdd(&d.rk_hist[481], 1);
+        atomicMax(&d.rk_hist[482], total);
+        atomicMax(&d.rk_hist[wave_ties ? 483 : 484], total);
+    }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------------------------
