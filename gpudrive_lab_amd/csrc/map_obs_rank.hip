@@ -1001,9 +1001,12 @@ __global__ __launch_bounds__(256) void k_knn_order(DevSim d) {
 #ifdef GD_CLOCKS
 // -DGD_CLOCKS: ticks of the constant 100 MHz clock (s_memrealtime; s_memtime counts shader cycles, whose rate moves) per phase of
 // a replay wave -- 0 set-up (order, candidate count), 1 fill, 2 make_heap, 3 the rounds, 4 the heap's write-out -- kept per
-// launch in rk_hist[256..]: seven values (the phases, 1 if the wave ran the copy for equal keys, the total) for each of the
-// first 32 waves, which hold the longest agents; [480] waves on the equal-key copy, [481] waves that ran, [482] the longest
-// total of any wave, [483] of any wave on the equal-key copy, [484] of any other wave.  k_knn_order zeroes them;
+// launch in rk_hist[256..]: seven values (the phases; bit 0: the wave ran the copy for equal keys, bits 1..9: its blocks in
+// the equal-key form, bits 10..19: in the checked form, bits 20..: its blocks; the total) for each of the first 32 waves,
+// which hold the longest agents; [480] waves on the equal-key copy, [481] waves that ran, [482] the longest total of any wave,
+// [483] of any wave on the equal-key copy, [484] of any other wave; over the launch [485] blocks in the equal-key form, [486]
+// blocks of the waves on the equal-key copy, [487] blocks in the checked form, [488] inserts (lanes) in rounds of the checked
+// form, [489] those of them redone in the equal-key form.  k_knn_order zeroes them;
 // gd_stat 1000 + k reads rk_hist[256 + k] (tools/replay_clocks.py).
 struct ReplayClock {
     unsigned int prev, first, ph[5];
@@ -1051,6 +1054,7 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
     // round trips in series in front of every wave's first round; k_knn_rank wrote the rows with streaming stores, so most
     // of them come from HBM).  Every lane loads, idle ones too (they read a row that exists: their own or row 0).
     const bool wave_ties = __ballot(on && has_tie) != 0ull;
+    rank_heap::TieTrack tt{rank_heap::NO_TIE};  // this lane's heap: elements with a non-zero tie field (rank_heap.hpp)
     GD_RPHASE(0);
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(E);
@@ -1064,12 +1068,18 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
             w[k * 4 + 3] = v.w;
         }
         if (lane < AWR) rank_heap::fill_pairs<K>(H, w);  // whole pairs; pair 0's low half, slot K + 1 and pairs K/2 + 1 .. 127: 0
+        // equal keys among the first K of some lane (rare even in a wave with equal keys: an OR over the registers tells)
+        if (wave_ties && __ballot(on && rank_heap::any_tie(w, tm)) != 0ull) {
+            tt = rank_heap::track_of(w, tm);
+            if (!on) tt.tg = rank_heap::NO_TIE;
+        }
     }
+    const bool heap_ties = __ballot(tt.tl()) != 0ull;  // make_heap compares equal keys
     GD_RPHASE(1);
     // ---- make_heap, src/binary_heap.hpp:170-185: parents K/2 .. 1, each __adjust_heap(hole, len = K, value) ----
     // (rank_heap.hpp: the sifts of one tree level in groups of eight, straight-line, two levels per LDS round trip)
     if (on) {
-        if (wave_ties) rank_heap::make_heap<K, true>(H, tm);
+        if (heap_ties) rank_heap::make_heap<K, true>(H, tm);
         else rank_heap::make_heap<K, false>(H, tm);
     }
     GD_RPHASE(2);
@@ -1088,133 +1098,32 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
     const uint4 *blocks = reinterpret_cast<const uint4 *>(E + K);  // K * 2 bytes: 16-byte aligned
     uint4 cur = on ? (GD_NT_REPLAY_LOAD ? stream_load(blocks) : blocks[0]) : make_uint4(0u, 0u, 0u, 0u);
     uint4 nxt = on ? (GD_NT_REPLAY_LOAD ? stream_load(blocks + 1) : blocks[1]) : make_uint4(0u, 0u, 0u, 0u);
-    // Two copies of the loop.  When none of the wave's agents has two candidates with one key (k_knn_rank reports it), every
-    // rank's tie field is 0, a plain integer compare IS the key compare, "the larger child" is a max and the values along
-    // the pop's path and the push's chain are medians of three (the moved children are non-increasing down the path, the
-    // chain towards the leaf): about a third fewer instructions per insert.  The other copy compares ranks without their
-    // tie field and selects.
+    // Two copies of the loop, each over rank_heap.hpp's rounds.  When none of the wave's agents has two candidates with one
+    // key (k_knn_rank reports it), every rank's tie field is 0 and every block of eight rounds runs the plain form (integer
+    // compares, max / med3 / min).  The other copy decides per block, wave-uniformly (rank_heap.hpp Form): the form for equal
+    // keys (compare without the tie field, select; about 1.2 x the plain one) only where a candidate of the block has a
+    // non-zero tie field -- the second and later members of a group of equal keys; the checked form -- plain rounds, each
+    // redone in the equal-key form if it met a tied rank -- while some lane holds such an element in its heap (TieTrack);
+    // the plain form otherwise.  One lane in 200 has such a group at all, but a wave that ran the equal-key form throughout
+    // because of that lane was the kernel's last wave in every launch.
 #ifdef GD_CLOCKS
     int n_ins = 0;  // inserts of this lane's agent (gd_stat 20: total over the agents; 19: their candidates beyond K; 18: rounds of the first wave)
+    int blk_all = 0, blk_ties = 0, blk_checked = 0;  // blocks of this wave, those in the equal-key form, those in the checked form
+    int n_chk = 0, n_redo = 0;                       // rounds of the checked form with an insert in this lane; those that met a tied rank
+    const auto wave_any = [&](bool f) -> bool {
+        const bool a = __ballot(f) != 0ull;
+        n_chk++;
+        n_redo += a ? 1 : 0;
+        return a;
+    };
+#else
+    const auto wave_any = [](bool f) -> bool { return __ballot(f) != 0ull; };  // over the lanes that insert in this round
 #endif
-    auto replay = [&](auto ties_tag) {
-        constexpr bool TIES = decltype(ties_tag)::value;
-        auto lt = [&](unsigned int a, unsigned int b) -> bool { return TIES ? rank_lt(a, b, tm) : a < b; };
-        auto larger = [&](unsigned int kl, unsigned int kr, bool &right) -> unsigned int {
-            right = !lt(kr, kl);  // the right child unless it is smaller (src/binary_heap.hpp __adjust_heap)
-            return TIES ? (right ? kr : kl) : max(kl, kr);
-        };
-        auto med3 = [](unsigned int a, unsigned int b, unsigned int c) -> unsigned int {
-            return max(min(a, b), min(max(a, b), c));  // the backend folds this into v_med3_u32
-        };
+    auto replay = [&](auto mixed_tag) {
+        constexpr bool MIXED = decltype(mixed_tag)::value;
         // The ranks arrive eight at a time (16 bytes), two blocks ahead.  An outer loop per block: the request for block b + 2
         // is issued at the top and its registers are not touched for eight rounds (inside one flat loop the compiler copied the
         // freshly requested block into place at once, i.e. waited a memory round trip every eighth round: a quarter of the kernel)
-        // One insert: candidate rank y goes through pop_heap / push_heap (called for the lanes whose candidate passes the
-        // reference's test `cmp(current, heap[0])`, src/knn.hpp:138-143)
-        auto insert = [&](const unsigned int y) {
-            {
-#ifdef GD_CLOCKS
-                n_ins++;
-#endif
-                // pop_heap: the hole goes from the root to the bottom of the (K - 1)-element heap along the larger child.
-                // Levels 0 and 1 are decided in registers (slots 1..7 live there during the replay); below that three, then two
-                // levels per LDS round trip: a node's children pair, its grandchildren pairs (and great-grandchildren pairs)
-                // are fetched together (pairs beyond the heap hold 0, which loses every comparison).  The ancestors of slot K that the push will meet are
-                // requested now as well and patched where the pop's path went through them.
-                int g[8];
-                unsigned int ck[7];
-                bool right0, right1;
-                ck[0] = larger(r[2], r[3], right0);
-                const unsigned int hl = right0 ? r[6] : r[4], hr = right0 ? r[7] : r[5];
-                ck[1] = larger(hl, hr, right1);
-                g[0] = 1;
-                g[1] = 2 + (right0 ? 1 : 0);
-                g[2] = 2 * g[1] + (right1 ? 1 : 0);
-                const unsigned int q12 = H.get(12), q25 = H.get(25), q50 = H.get(50), q100 = H.get(100);
-                // (two round trips: three levels below slot g[2] -- its children pair, both grandchildren pairs and all four
-                // great-grandchildren pairs, seven dwords at constant offsets from one address -- then two levels below
-                // g[5].  Round 3 and the first half of round 4 went two, two and one level: a round trip more per insert,
-                // and the inserts of the agent with the most candidates are the kernel's duration: 452 -> 435 us)
-                {
-                    const int g2 = g[2];
-                    const unsigned int pc = H.pair(g2), pl = H.pair(2 * g2), pr2 = H.pair(2 * g2 + 1);
-                    const unsigned int p0 = H.pair(4 * g2), p1 = H.pair(4 * g2 + 1), p2 = H.pair(4 * g2 + 2), p3 = H.pair(4 * g2 + 3);
-                    bool ra, rb, rc;
-                    ck[2] = larger(pc & 0xffffu, pc >> 16, ra);
-                    g[3] = 2 * g2 + (ra ? 1 : 0);
-                    const unsigned int pg = ra ? pr2 : pl;
-                    ck[3] = larger(pg & 0xffffu, pg >> 16, rb);
-                    g[4] = 2 * g[3] + (rb ? 1 : 0);
-                    const unsigned int pa = rb ? p1 : p0, pb = rb ? p3 : p2;
-                    const unsigned int pgg = ra ? pb : pa;
-                    ck[4] = larger(pgg & 0xffffu, pgg >> 16, rc);
-                    g[5] = 2 * g[4] + (rc ? 1 : 0);
-                }
-                {
-                    const unsigned int pc = H.pair(g[5]), pl = H.pair(2 * g[5]), pr2 = H.pair(2 * g[5] + 1);
-                    bool ra, rb;
-                    ck[5] = larger(pc & 0xffffu, pc >> 16, ra);
-                    g[6] = 2 * g[5] + (ra ? 1 : 0);
-                    const unsigned int pg = ra ? pr2 : pl;
-                    ck[6] = larger(pg & 0xffffu, pg >> 16, rb);
-                    g[7] = 2 * g[6] + (rb ? 1 : 0);
-                }
-                // the old last element climbs back from the leaf hole past every moved child that is smaller; the moved
-                // children are non-increasing down the path, so "it passes level l" is monotone in l and the value that
-                // ends up on level l is the median of (child moved from l, child moved from l + 1 ... ) -- see above
-                unsigned int v[8];
-                if (TIES) {
-                    bool c[7];
-#pragma unroll
-                    for (int l = 0; l < 7; l++) c[l] = lt(ck[l], last);
-#pragma unroll
-                    for (int l = 0; l < 8; l++) {
-                        if (l == 0) v[l] = c[0] ? last : ck[0];
-                        else if (l == 7) v[l] = c[6] ? ck[6] : last;
-                        else v[l] = c[l - 1] ? ck[l - 1] : (c[l] ? last : ck[l]);
-                    }
-                } else {
-                    v[0] = max(ck[0], last);
-#pragma unroll
-                    for (int l = 1; l < 7; l++) v[l] = med3(ck[l - 1], ck[l], last);
-                    v[7] = min(ck[6], last);
-                }
-                r[1] = v[0];
-                r[2] = right0 ? r[2] : v[1];
-                r[3] = right0 ? v[1] : r[3];
-#pragma unroll
-                for (int j = 4; j < 8; j++) r[j] = g[2] == j ? v[2] : r[j];
-#pragma unroll
-                for (int l = 3; l < 8; l++)
-                    if (l < 6 || g[l] < K) H.set(g[l], v[l]);  // levels 3..5 are always inside the heap
-                // push_heap: the new element climbs from slot K along 100, 50, 25, 12, 6, 3, 1
-                static_assert(K == 200, "ancestor chain of slot K");
-                const unsigned int qv[7] = {r[1], r[3], r[6], g[3] == 12 ? v[3] : q12, g[4] == 25 ? v[4] : q25,
-                                            g[5] == 50 ? v[5] : q50, g[6] == 100 ? v[6] : q100};
-                constexpr int chain[7] = {1, 3, 6, 12, 25, 50, 100};
-                if (TIES) {
-                    bool pp[7];
-#pragma unroll
-                    for (int u = 0; u < 7; u++) pp[u] = lt(qv[u], y);
-                    r[1] = pp[0] ? y : r[1];
-                    r[3] = pp[1] ? (pp[0] ? qv[0] : y) : r[3];
-                    r[6] = pp[2] ? (pp[1] ? qv[1] : y) : r[6];
-#pragma unroll
-                    for (int u = 3; u < 7; u++)
-                        if (pp[u]) H.set(chain[u], pp[u - 1] ? qv[u - 1] : y);
-                    last = pp[6] ? qv[6] : y;
-                } else {
-                    // chain position u receives its parent's value if that is below y, y if only its own is, and keeps its
-                    // own otherwise: the median of (parent, own, y), the chain being non-increasing towards the leaf
-                    r[1] = max(qv[0], y);
-                    r[3] = med3(qv[0], qv[1], y);
-                    r[6] = med3(qv[1], qv[2], y);
-#pragma unroll
-                    for (int u = 3; u < 7; u++) H.set(chain[u], med3(qv[u - 1], qv[u], y));
-                    last = min(qv[6], y);
-                }
-            }
-        };
         // A tile of 32 candidates (what lies between two checkpoints) is four blocks of eight, each block's rounds unrolled:
         // a round takes its rank out of the block's registers with one instruction, and the checkpoint is written once per
         // tile (round 3 shifted the block by 16 bits and tested for the checkpoint in every round: a dozen instructions of ~130)
@@ -1229,11 +1138,28 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
                 // a merge with the old value would wait for the data
                 nxt = GD_NT_REPLAY_LOAD ? stream_load(blocks + ((pb - K) >> 3) + 2) : blocks[((pb - K) >> 3) + 2];
                 const unsigned int wd[4] = {w8.x, w8.y, w8.z, w8.w};
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const unsigned int y = (k & 1) ? wd[k >> 1] >> 16 : wd[k >> 1] & 0xffffu;
-                    if (pb + k < n && lt(y, r[1])) insert(y);
+                const int left = n - pb;  // candidates of this lane's agent from here on (idle lanes: n = 0)
+                int ins;
+                // (slack beyond n and idle lanes do not count: `left`, `on`)
+                if (MIXED && __ballot(on && rank_heap::block_has_tie(wd, left, tm)) != 0ull) {
+                    ins = rank_heap::block_rounds<K, rank_heap::TIES>(H, r, last, wd, left, tm, tt);
+#ifdef GD_CLOCKS
+                    blk_ties++;
+#endif
+                } else if (MIXED && __ballot(tt.tl()) != 0ull) {
+                    ins = rank_heap::block_rounds<K, rank_heap::CHECKED>(H, r, last, wd, left, tm, tt, wave_any);
+#ifdef GD_CLOCKS
+                    blk_checked++;
+#endif
+                } else {
+                    ins = rank_heap::block_rounds<K, rank_heap::PLAIN>(H, r, last, wd, left, tm, tt);
                 }
+#ifdef GD_CLOCKS
+                n_ins += ins;
+                blk_all++;
+#else
+                (void)ins;
+#endif
             }
             // after candidate (p0 - K) + 32: a checkpoint of every standard agent, of a long list at every second tile
             const int after = p0 - K + TILE;
@@ -1273,18 +1199,24 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
     }
 #ifdef GD_CLOCKS
     GD_RPHASE(4);
+    const int w_chk = wave_sum(n_chk), w_redo = wave_sum(n_redo);
     if (lane == 0) {
         const int total = (int)(rclk.prev - rclk.first);
         if (blockIdx.x < 32) {
             int *row = d.rk_hist + 256 + blockIdx.x * 7;
             for (int k = 0; k < 5; k++) row[k] = (int)rclk.ph[k];
-            row[5] = wave_ties ? 1 : 0;
+            row[5] = (wave_ties ? 1 : 0) | (blk_ties << 1) | (blk_checked << 10) | (blk_all << 20);  // (at most 2552 / 8 blocks)
             row[6] = total;
         }
         atomicAdd(&d.rk_hist[480], wave_ties ? 1 : 0);
         atomicAdd(&d.rk_hist[481], 1);
         atomicMax(&d.rk_hist[482], total);
         atomicMax(&d.rk_hist[wave_ties ? 483 : 484], total);
+        atomicAdd(&d.rk_hist[485], blk_ties);
+        atomicAdd(&d.rk_hist[486], wave_ties ? blk_all : 0);
+        atomicAdd(&d.rk_hist[487], blk_checked);
+        atomicAdd(&d.rk_hist[488], w_chk);
+        atomicAdd(&d.rk_hist[489], w_redo);
     }
 #endif
 }
