@@ -108,11 +108,32 @@ class GdRecordBuffers(C.Structure):
                 [("kernel_ms", C.POINTER(C.c_float))])
 
 
+IL_MAX_SHARDS = 8
+
+
+class GdIlShard(C.Structure):
+    """gd_il_shard: one recorded episode batch of the device expert dataset (device pointers)."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "actions", "dead_mask", "partner_mask", "road_mask", "keep")] + [("n_rows", C.c_int32)]
+
+
+class GdIlDataset(C.Structure):
+    _fields_ = [("shard", GdIlShard * IL_MAX_SHARDS), ("n_shards", C.c_int32), ("max_agents", C.c_int32),
+                ("rollout_len", C.c_int32), ("pred_len", C.c_int32)]
+
+
+class GdIlBatchBuffers(C.Structure):
+    """gd_il_batch_buffers: the index, the selection and the five outputs of one batch (device pointers)."""
+    _fields_ = [("entries", C.c_void_p), ("n_entries", C.c_int64), ("sel", C.c_void_p), ("batch", C.c_int32),
+                ("bad_indices", C.c_void_p), ("obs", C.c_void_p), ("actions", C.c_void_p), ("partner_mask", C.c_void_p),
+                ("road_mask", C.c_void_p), ("data_idx", C.c_void_p)]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
-    "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_episode_step", "gd_sync",
+    "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_episode_step",
+    "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
     "gd_set_stream", "gd_attach_bev", "gd_stat",
@@ -178,6 +199,8 @@ def lib():
     L.gd_expert_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gd_advance_log_playback.argtypes = [C.c_void_p, C.c_int32]
     L.gd_record_expert.argtypes = [C.c_void_p, C.POINTER(GdRecordBuffers), C.c_int32]
+    L.gd_il_index.argtypes = [C.POINTER(GdIlDataset), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gd_il_batch.argtypes = [C.POINTER(GdIlDataset), C.POINTER(GdIlBatchBuffers), C.c_void_p]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

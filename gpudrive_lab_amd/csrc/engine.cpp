@@ -1446,6 +1446,64 @@ int gd_record_expert(gd_sim *s, const gd_record_buffers *b, int32_t n_steps) {
     });
 }
 
+namespace {
+
+// what gd_il_index and gd_il_batch both require of the dataset table; rows: the source rows of every shard together
+const char *il_dataset_error(const gd_il_dataset *ds, int64_t *rows) {
+    if (!ds) return "null argument";
+    if (ds->max_agents != 64 && ds->max_agents != 128) return "max_agents must be 64 or 128";
+    if (ds->rollout_len < 1 || ds->pred_len < 1 || ds->rollout_len + ds->pred_len > GD_EPISODE_LEN)
+        return "rollout_len >= 1, pred_len >= 1 and rollout_len + pred_len <= 91 are required";
+    if (ds->n_shards < 0 || ds->n_shards > GD_IL_MAX_SHARDS) return "0 to 8 shards";
+    *rows = 0;
+    for (int i = 0; i < ds->n_shards; i++) {
+        const gd_il_shard &sh = ds->shard[i];
+        if (sh.n_rows < 0) return "a shard's n_rows must be >= 0";
+        if (!sh.obs || !sh.actions || !sh.dead_mask || !sh.partner_mask || !sh.road_mask || !sh.keep)
+            return "every array of every shard is required";
+        if (reinterpret_cast<uintptr_t>(sh.obs) % 16 != 0 || reinterpret_cast<uintptr_t>(sh.road_mask) % 8 != 0)
+            return "obs must be 16-byte aligned and road_mask 8-byte aligned";
+        *rows += sh.n_rows;
+    }
+    if (*rows > INT32_MAX / GD_EPISODE_LEN) return "too many rows";
+    return nullptr;
+}
+
+}  // namespace
+
+int gd_il_index(const gd_il_dataset *ds, int32_t *counts, int32_t *kept, const int64_t *entry_offset, const int64_t *kept_ordinal,
+                int32_t *entries, void *stream) {
+    int64_t rows = 0;
+    if (const char *e = il_dataset_error(ds, &rows)) return fail(GD_ERR_INVALID, std::string("gd_il_index: ") + e);
+    if (entries ? (!entry_offset || !kept_ordinal) : (!counts || !kept))
+        return fail(GD_ERR_INVALID, "gd_il_index: counts and kept (first launch) or entry_offset, kept_ordinal and entries "
+                                    "(second launch) are required");
+    return guarded([&]() {
+        gd::launch_il_index(*ds, static_cast<hipStream_t>(stream), rows, counts, kept, entry_offset, kept_ordinal, entries);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_il_batch(const gd_il_dataset *ds, const gd_il_batch_buffers *b, void *stream) {
+    int64_t rows = 0;
+    if (const char *e = il_dataset_error(ds, &rows)) return fail(GD_ERR_INVALID, std::string("gd_il_batch: ") + e);
+    if (!b) return fail(GD_ERR_INVALID, "gd_il_batch: null argument");
+    if (b->batch < 0 || b->n_entries < 0) return fail(GD_ERR_INVALID, "gd_il_batch: batch and n_entries must be >= 0");
+    if (b->batch > INT32_MAX / 64) return fail(GD_ERR_INVALID, "gd_il_batch: batch too large for one launch");
+    if (!b->entries || !b->sel || !b->bad_indices || !b->obs || !b->actions || !b->partner_mask || !b->road_mask || !b->data_idx)
+        return fail(GD_ERR_INVALID, "gd_il_batch: every buffer is required");
+    if (reinterpret_cast<uintptr_t>(b->obs) % 16 != 0 || reinterpret_cast<uintptr_t>(b->road_mask) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(b->entries) % 16 != 0)
+        return fail(GD_ERR_INVALID, "gd_il_batch: obs and entries must be 16-byte aligned and road_mask 8-byte aligned");
+    // developer switch for the sweep tools/il_batches.py records (NOTEBOOK.md): workgroups per sample
+    int split = 0;
+    if (const char *e = std::getenv("GPUDRIVE_IL_SPLIT")) split = std::min(64, std::max(1, std::atoi(e)));
+    return guarded([&]() {
+        gd::launch_il_batch(*ds, static_cast<hipStream_t>(stream), *b, split);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

@@ -87,6 +87,11 @@ class ExpertEpisode:
         np.savez_compressed(glob, ego_global_pos=host(self.ego_global_pos), ego_global_rot=host(self.ego_global_rot))
         return main, glob
 
+    def dataset(self, **kw):
+        """The `DeviceExpertDataset` over this episode where it lies (il_dataset.py; rollout_len = 5, pred_len = 1)."""
+        from .il_dataset import DeviceExpertDataset
+        return DeviceExpertDataset(self, **kw)
+
 
 class ExpertRecorder:
     def __init__(self, sim, mask=None):

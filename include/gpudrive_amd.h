@@ -251,6 +251,60 @@ typedef struct gd_record_buffers {
  * have 10 columns; the dataset's have 3).  GD_ERR_UNSUPPORTED while a packed buffer is attached with only != 0 (the raw rows
  * the observation is computed from are stale). */
 int gd_record_expert(gd_sim *sim, const gd_record_buffers *buffers, int32_t n_steps);
+/* Device expert dataset: the consumer of the recorder's arrays.  Replaces the reference's ExpertDataset
+ * (gpudrive/integrations/il/dataloader.py:5-71, 183-211; built and iterated by baselines/il/il.py:70-97, unpacked by
+ * il.py:248-263): its padded second copy of every array (dataloader.py:10, 46-54), its Python list of valid (row, time)
+ * pairs (dataloader.py:66-71) and the per-sample slicing in DataLoader workers (dataloader.py:183-205), by an index built on
+ * the device and one kernel that gathers a batch.  Needs no simulator: every pointer is a device pointer owned by the caller,
+ * `stream` is a hipStream_t (NULL: the default stream).  T = 91, A = max_agents (64 or 128), D = 6 + (A-1)*6 + 200*13,
+ * R = rollout_len, P = pred_len with R >= 1, P >= 1, R + P <= 91 (outside it the reference switches to an unrelated flat mode).
+ * A shard is one recorded episode batch; shards are never concatenated. */
+#define GD_IL_MAX_SHARDS 8
+typedef struct gd_il_shard {
+    const float *obs;             /* [n_rows][91][D], 16-byte aligned */
+    const float *actions;         /* [n_rows][91][3] */
+    const uint8_t *dead_mask;     /* [n_rows][91] bool */
+    const uint8_t *partner_mask;  /* [n_rows][91][A-1] 0 / 1 / 2 */
+    const uint8_t *road_mask;     /* [n_rows][91][200] bool, 8-byte aligned */
+    const uint8_t *keep;          /* [n_rows] bool: the rows ExpertEpisode.save() writes (storage.py:86-98) */
+    int32_t n_rows;
+} gd_il_shard;
+typedef struct gd_il_dataset {
+    gd_il_shard shard[GD_IL_MAX_SHARDS];
+    int32_t n_shards;             /* 0..8 */
+    int32_t max_agents;           /* 64 or 128 */
+    int32_t rollout_len, pred_len;
+} gd_il_dataset;
+/* The valid-sample index (dataloader.py:16-23, 66-71), in two launches with the caller's prefix sums between them.  A source
+ * row is a (shard, local row) pair; g counts them through the shards in order.  valid[g][t] = !dead_mask && !(|a1| > 0.5f ||
+ * |a0| > 5.f || |a2| > 0.2f) (strict, fp32; a NaN does not invalidate).  The samples of row g are the idx2 in [0, 91 - P] with
+ * keep[g] && valid[g][idx2 + P - 1], ascending.
+ *   entries == NULL: counts[g] = the number of samples of row g, kept[g] = keep[g] (both int32 [rows]).
+ *   entries != NULL: entry_offset[g] (int64: the exclusive prefix sum of counts) and kept_ordinal[g] (int64: the exclusive
+ *       prefix sum of kept, idx1 of the reference after save() dropped the other rows) are read, and row g's entries written
+ *       at entries[entry_offset[g] ...] as int32 x 4 {shard, local row, idx2, idx1}.
+ * GD_ERR_INVALID: a null pointer, R / P out of range, A not 64 or 128, a negative row count, more than 8 shards, a
+ * misaligned obs or road_mask. */
+int gd_il_index(const gd_il_dataset *ds, int32_t *counts, int32_t *kept, const int64_t *entry_offset,
+                const int64_t *kept_ordinal, int32_t *entries, void *stream);
+typedef struct gd_il_batch_buffers {
+    const int32_t *entries;   /* [n_entries][4] gd_il_index's */
+    int64_t n_entries;
+    const int64_t *sel;       /* [batch] positions into entries, any order, repeats allowed */
+    int32_t batch;
+    int32_t *bad_indices;     /* [1] incremented once for every sel outside [0, n_entries) */
+    /* outputs; every byte of each is written by every call */
+    float *obs;               /* [batch][R][D] rows at times idx2 - R + 1 .. idx2, zeros where the time is < 0; 16-byte aligned */
+    float *actions;           /* [batch][P][3] actions at times idx2 .. idx2 + P - 1 */
+    uint8_t *partner_mask;    /* [batch][R][A-1] bool: stored value == 2; true where the time is < 0.  Any alignment */
+    uint8_t *road_mask;       /* [batch][R][200] bool; true where the time is < 0; 8-byte aligned */
+    int64_t *data_idx;        /* [batch][2] (idx1, idx2) */
+} gd_il_batch_buffers;
+/* One training batch (dataloader.py:183-205 for every sample, then the DataLoader's collate and the copy to the device):
+ * one launch, no host synchronisation.  A sel outside [0, n_entries) gives an all-padding sample (obs 0, actions 0, masks
+ * true, data_idx (-1, -1)) and counts in bad_indices.  GD_ERR_INVALID as above, and for batch < 0, batch > 2^25 - 1 or
+ * n_entries < 0. */
+int gd_il_batch(const gd_il_dataset *ds, const gd_il_batch_buffers *buffers, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
