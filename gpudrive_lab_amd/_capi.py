@@ -128,11 +128,29 @@ class GdIlBatchBuffers(C.Structure):
                 ("road_mask", C.c_void_p), ("data_idx", C.c_void_p)]
 
 
+IL_FUTURE_OTHER, IL_FUTURE_EGO = range(2)
+
+
+class GdIlFuture(C.Structure):
+    """gd_il_future: the per-shard ego poses (device pointers), the future step, the experiment and the 2 x 9 bin edges."""
+    _fields_ = [("ego_global_pos", C.c_void_p * IL_MAX_SHARDS), ("ego_global_rot", C.c_void_p * IL_MAX_SHARDS),
+                ("future_step", C.c_int32), ("exp", C.c_int32), ("xbins", C.c_double * 9), ("ybins", C.c_double * 9)]
+
+
+class GdIlFutureBuffers(C.Structure):
+    """gd_il_future_buffers: the index, the selection and the eight outputs of one linear-probing batch (device pointers)."""
+    _fields_ = [("entries", C.c_void_p), ("n_entries", C.c_int64), ("sel", C.c_void_p), ("batch", C.c_int32),
+                ("bad_indices", C.c_void_p), ("obs", C.c_void_p), ("actions", C.c_void_p), ("valid_mask", C.c_void_p),
+                ("ego_mask", C.c_void_p), ("partner_mask", C.c_void_p), ("road_mask", C.c_void_p), ("future_mask", C.c_void_p),
+                ("future_pos", C.c_void_p)]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
-    "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_episode_step",
+    "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_il_future_batch",
+    "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -201,6 +219,7 @@ def lib():
     L.gd_record_expert.argtypes = [C.c_void_p, C.POINTER(GdRecordBuffers), C.c_int32]
     L.gd_il_index.argtypes = [C.POINTER(GdIlDataset), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gd_il_batch.argtypes = [C.POINTER(GdIlDataset), C.POINTER(GdIlBatchBuffers), C.c_void_p]
+    L.gd_il_future_batch.argtypes = [C.POINTER(GdIlDataset), C.POINTER(GdIlFuture), C.POINTER(GdIlFutureBuffers), C.c_void_p]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -1504,6 +1504,37 @@ int gd_il_batch(const gd_il_dataset *ds, const gd_il_batch_buffers *b, void *str
     });
 }
 
+int gd_il_future_batch(const gd_il_dataset *ds, const gd_il_future *fu, const gd_il_future_buffers *b, void *stream) {
+    int64_t rows = 0;
+    if (const char *e = il_dataset_error(ds, &rows)) return fail(GD_ERR_INVALID, std::string("gd_il_future_batch: ") + e);
+    if (!fu || !b) return fail(GD_ERR_INVALID, "gd_il_future_batch: null argument");
+    if (fu->future_step < 1 || fu->future_step > GD_EPISODE_LEN - 1)
+        return fail(GD_ERR_INVALID, "gd_il_future_batch: future_step must be 1..90");
+    if (fu->exp != GD_IL_FUTURE_OTHER && fu->exp != GD_IL_FUTURE_EGO) return fail(GD_ERR_INVALID, "gd_il_future_batch: unknown exp");
+    for (const double *edges : {fu->xbins, fu->ybins})
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(edges[i]) || (i && !(edges[i - 1] < edges[i])))
+                return fail(GD_ERR_INVALID, "gd_il_future_batch: the bin edges must be finite and strictly increasing");
+    for (int i = 0; i < ds->n_shards; i++)
+        if (!fu->ego_global_pos[i] || !fu->ego_global_rot[i])
+            return fail(GD_ERR_INVALID, "gd_il_future_batch: ego_global_pos and ego_global_rot of every shard are required");
+    if (b->batch < 0 || b->n_entries < 0) return fail(GD_ERR_INVALID, "gd_il_future_batch: batch and n_entries must be >= 0");
+    if (b->batch > INT32_MAX / 64) return fail(GD_ERR_INVALID, "gd_il_future_batch: batch too large for one launch");
+    if (!b->entries || !b->sel || !b->bad_indices || !b->obs || !b->actions || !b->valid_mask || !b->ego_mask || !b->partner_mask ||
+        !b->road_mask || !b->future_mask || !b->future_pos)
+        return fail(GD_ERR_INVALID, "gd_il_future_batch: every buffer is required");
+    if (reinterpret_cast<uintptr_t>(b->obs) % 16 != 0 || reinterpret_cast<uintptr_t>(b->road_mask) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(b->entries) % 16 != 0 || reinterpret_cast<uintptr_t>(b->future_pos) % 8 != 0)
+        return fail(GD_ERR_INVALID, "gd_il_future_batch: obs and entries must be 16-byte aligned, road_mask and future_pos "
+                                    "8-byte aligned");
+    int split = 0;  // (gd_il_batch's developer switch)
+    if (const char *e = std::getenv("GPUDRIVE_IL_SPLIT")) split = std::min(64, std::max(1, std::atoi(e)));
+    return guarded([&]() {
+        gd::launch_il_future(*ds, *fu, static_cast<hipStream_t>(stream), *b, split);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

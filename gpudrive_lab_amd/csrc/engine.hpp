@@ -233,5 +233,7 @@ void launch_il_index(const gd_il_dataset &ds, hipStream_t st, int64_t rows, int3
                      const int64_t *entry_offset, const int64_t *kept_ordinal, int32_t *entries);  // il_batch.hip
 void launch_il_batch(const gd_il_dataset &ds, hipStream_t st, const gd_il_batch_buffers &b,
                      int split);  // il_batch.hip (split: workgroups per sample, 0: the default)
+void launch_il_future(const gd_il_dataset &ds, const gd_il_future &fu, hipStream_t st, const gd_il_future_buffers &b,
+                      int split);  // il_batch.hip
 
 }  // namespace gd

@@ -7,10 +7,17 @@ one kernel (`gd_il_batch`) into the five tensors baselines/il/il.py:248-263 unpa
 zero prefix, the action targets, both masks and the sample indices.  The recorded arrays are neither copied nor padded, and
 several recorded episodes (shards) train together without being concatenated.
 
-Not here: `use_tom` (`other_pos`, `aux_mask`; the reference cannot run it, dataloader.py:34 against :73) and the flat 2-D mode
-the reference falls into when rollout_len + pred_len > 91 (a ValueError here)."""
-import ctypes as C
+`DeviceFutureDataset` is the third consumer of the same recording: the linear-probing dataset, the reference's `FutureDataset`
+(gpudrive/integrations/il/linear_probing/dataloader.py, unpacked by baselines/il/linear_probing.py:173).  Same shards, same
+index; `batch()` is one kernel (`gd_il_future_batch`) that returns the window, the targets and the masks together with the
+future mask and the 64-class future position labels, which it computes per sample from the recorded ego pose.
 
+Not here: `use_tom` of `ExpertDataset` (the reference cannot run it, dataloader.py:34 against :73) and the flat 2-D mode the
+reference falls into when rollout_len + pred_len > 91 (a ValueError here)."""
+import ctypes as C
+import math
+
+import numpy as np
 import torch
 
 from . import _capi
@@ -18,6 +25,7 @@ from .recorder import EPISODE_LEN, ROAD_POINTS, packed_width
 
 MAX_SHARDS = _capi.IL_MAX_SHARDS
 _FIELDS = ("obs", "actions", "dead_mask", "partner_mask", "road_mask", "keep")
+_POSE_FIELDS = ("ego_global_pos", "ego_global_rot")
 _AGENTS_OF_WIDTH = {packed_width(A): A for A in (64, 128)}
 
 
@@ -33,16 +41,19 @@ def _check_batch_size(batch_size):
         raise ValueError("DeviceExpertDataset.batches: batch_size must be a positive int, got %r" % (batch_size,))
 
 
-def _check_shard(i, ep):
-    """One shard's six tensors, checked without touching them; returns (tensors, N, A)."""
+def _check_shard(i, ep, who="DeviceExpertDataset", pose=False):
+    """One shard's six tensors (and the two of the ego pose, if asked for), checked without touching them; returns
+    (tensors, N, A)."""
     get = (lambda k: ep.get(k)) if isinstance(ep, dict) else (lambda k: getattr(ep, k, None))
-    t = {k: get(k) for k in _FIELDS}
-    what = "DeviceExpertDataset: shard %d " % i
+    t = {k: get(k) for k in _FIELDS + (_POSE_FIELDS if pose else ())}
+    what = "%s: shard %d " % (who, i)
     for k, v in t.items():
         if not isinstance(v, torch.Tensor):
             raise ValueError(what + "%s must be a tensor, got %s" % (k, type(v).__name__))
     want = dict(obs=torch.float32, actions=torch.float32, dead_mask=torch.bool, partner_mask=torch.uint8,
                 road_mask=torch.bool, keep=torch.bool)
+    if pose:
+        want.update(ego_global_pos=torch.float32, ego_global_rot=torch.float32)
     for k, dt in want.items():
         if t[k].dtype != dt:
             raise ValueError(what + "%s must be %s, got %s" % (k, dt, t[k].dtype))
@@ -52,6 +63,8 @@ def _check_shard(i, ep):
     N, A = int(obs.shape[0]), _AGENTS_OF_WIDTH[int(obs.shape[2])]
     shapes = dict(actions=(N, EPISODE_LEN, 3), dead_mask=(N, EPISODE_LEN), partner_mask=(N, EPISODE_LEN, A - 1),
                   road_mask=(N, EPISODE_LEN, ROAD_POINTS), keep=(N,))
+    if pose:
+        shapes.update(ego_global_pos=(N, EPISODE_LEN, 2), ego_global_rot=(N, EPISODE_LEN, 1))
     for k, shp in shapes.items():
         if tuple(t[k].shape) != shp:
             raise ValueError(what + "%s must be %s beside obs %s, got %s" % (k, shp, tuple(obs.shape), tuple(t[k].shape)))
@@ -64,6 +77,8 @@ def _check_shard(i, ep):
 
 
 class DeviceExpertDataset:
+    _POSE = False  # whether a shard must carry the ego pose as well (DeviceFutureDataset)
+
     def __init__(self, episodes, rollout_len=5, pred_len=1):
         """episodes: one `ExpertEpisode`, or a dict of the same device tensors (obs, actions, dead_mask, partner_mask,
         road_mask, keep), or a list of up to 8 of either: the shards, in the order the reference would concatenate their files
@@ -76,7 +91,7 @@ class DeviceExpertDataset:
             raise ValueError("DeviceExpertDataset: at most %d shards, got %d" % (MAX_SHARDS, len(episodes)))
         if not episodes:
             raise ValueError("DeviceExpertDataset: no episode given")
-        shards = [_check_shard(i, ep) for i, ep in enumerate(episodes)]
+        shards = [_check_shard(i, ep, type(self).__name__, self._POSE) for i, ep in enumerate(episodes)]
         agents = {A for _, _, A in shards}
         if len(agents) != 1:
             raise ValueError("DeviceExpertDataset: the shards' observation widths give different agent slot counts: %s"
@@ -145,31 +160,37 @@ class DeviceExpertDataset:
         return (((batch, R, self.obs_width), torch.float32), ((batch, P, 3), torch.float32), ((batch, R, A - 1), torch.bool),
                 ((batch, R, ROAD_POINTS), torch.bool), ((batch, 2), torch.int64))
 
+    _OUT_NAMES = ("obs", "actions", "partner_mask", "road_mask", "data_idx")
+    _OUT_ALIGNED = ((0, 16), (3, 8))  # (output, bytes): what the kernel's wide stores need
+    _OUT_ALIGNED_TEXT = "out obs must be 16-byte aligned and road_mask 8-byte aligned"
+
+    def _outputs(self, sel, out):
+        """sel and the out= tensors of `batch()` checked; returns (B, the outputs, allocated unless given)."""
+        who = type(self).__name__
+        if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int64 or sel.dim() != 1 or sel.device != self.device \
+                or not sel.is_contiguous():
+            raise ValueError("%s.batch: sel must be a contiguous [B] int64 tensor on %s" % (who, self.device))
+        B = int(sel.shape[0])
+        want = self.batch_shapes(B)
+        if out is None:
+            return B, tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in want)
+        if not isinstance(out, (tuple, list)) or len(out) != len(want):
+            raise ValueError("%s.batch: out must be the %s tensors of a batch" % (who, {5: "five", 8: "eight"}[len(want)]))
+        for name, o, (shape, dt) in zip(self._OUT_NAMES, out, want):
+            if not isinstance(o, torch.Tensor) or o.dtype != dt or o.device != self.device or tuple(o.shape) != shape \
+                    or not o.is_contiguous():
+                raise ValueError("%s.batch: out %s must be a contiguous %s %s tensor on %s" % (who, name, dt, shape, self.device))
+        if B and any(out[i].data_ptr() % n for i, n in self._OUT_ALIGNED):
+            raise ValueError("%s.batch: %s" % (who, self._OUT_ALIGNED_TEXT))
+        return B, tuple(out)
+
     def batch(self, sel, out=None):
         """Gather the samples at positions `sel` ([B] int64 on the device; any order, repeats allowed) of the index:
         (obs [B, R, D] f32, actions [B, P, 3] f32, partner_mask [B, R, A - 1] bool, road_mask [B, R, 200] bool,
         data_idx [B, 2] int64), what baselines/il/il.py:248-263 unpacks.  One launch on torch's current stream, no host
         synchronisation.  A position outside [0, len) gives an all-padding sample (obs 0, actions 0, masks True, data_idx
         (-1, -1)) and counts in `bad_indices`.  out: the five tensors of an earlier call with the same B, to be overwritten."""
-        if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int64 or sel.dim() != 1 or sel.device != self.device \
-                or not sel.is_contiguous():
-            raise ValueError("DeviceExpertDataset.batch: sel must be a contiguous [B] int64 tensor on %s" % self.device)
-        B = int(sel.shape[0])
-        want = self.batch_shapes(B)
-        if out is None:
-            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in want)
-        else:
-            if not isinstance(out, (tuple, list)) or len(out) != 5:
-                raise ValueError("DeviceExpertDataset.batch: out must be the five tensors of a batch")
-            names = ("obs", "actions", "partner_mask", "road_mask", "data_idx")
-            for name, o, (shape, dt) in zip(names, out, want):
-                if not isinstance(o, torch.Tensor) or o.dtype != dt or o.device != self.device or tuple(o.shape) != shape \
-                        or not o.is_contiguous():
-                    raise ValueError("DeviceExpertDataset.batch: out %s must be a contiguous %s %s tensor on %s"
-                                     % (name, dt, shape, self.device))
-            if B and (out[0].data_ptr() % 16 or out[3].data_ptr() % 8):
-                raise ValueError("DeviceExpertDataset.batch: out obs must be 16-byte aligned and road_mask 8-byte aligned")
-            out = tuple(out)
+        B, out = self._outputs(sel, out)
         if B == 0:
             return out
         b = _capi.GdIlBatchBuffers()
@@ -200,3 +221,80 @@ class DeviceExpertDataset:
             order = torch.arange(self._len, device=self.device)
         for sel in self.batch_selections(order, batch_size, drop_last):
             yield self.batch(sel)
+
+
+def _check_future(future_step, exp, xy_range):
+    """The arguments of DeviceFutureDataset that are its own; returns (exp code, xbins, ybins)."""
+    if not isinstance(future_step, int) or isinstance(future_step, bool) or not 1 <= future_step <= EPISODE_LEN - 1:
+        raise ValueError("DeviceFutureDataset: future_step must be an int in [1, 90], got %r" % (future_step,))
+    if exp not in ("other", "ego"):
+        raise ValueError("DeviceFutureDataset: exp must be 'other' or 'ego', got %r" % (exp,))
+    ranges = ((-0.05, 0.05), (-0.05, 0.05))  # dataloader.py:161-162
+    if xy_range is not None:
+        if exp == "other":
+            raise ValueError("DeviceFutureDataset: xy_range is for exp='ego' only (the reference ignores it for 'other', "
+                             "dataloader.py:53)")
+        try:
+            ranges = tuple((float(lo), float(hi)) for lo, hi in xy_range)
+        except (TypeError, ValueError):
+            ranges = ()
+        if len(ranges) != 2 or not all(math.isfinite(lo) and math.isfinite(hi) and lo < hi for lo, hi in ranges):
+            raise ValueError("DeviceFutureDataset: xy_range must be ((xlo, xhi), (ylo, yhi)), finite with lo < hi, got %r"
+                             % (xy_range,))
+    bins = [np.linspace(lo, hi, 9) for lo, hi in ranges]
+    for b in bins:
+        if not (np.isfinite(b).all() and (np.diff(b) > 0).all()):
+            raise ValueError("DeviceFutureDataset: xy_range %r gives bin edges that do not increase" % (xy_range,))
+    return (_capi.IL_FUTURE_OTHER if exp == "other" else _capi.IL_FUTURE_EGO), bins[0], bins[1]
+
+
+class DeviceFutureDataset(DeviceExpertDataset):
+    _POSE = True
+    OUT_NAMES = {"other": ("obs", "actions", "valid_mask", "ego_mask", "partner_mask", "road_mask", "aux_mask", "other_pos"),
+                 "ego": ("obs", "actions", "valid_mask", "ego_mask", "partner_mask", "road_mask", "future_valid_mask", "ego_pos")}
+    _OUT_ALIGNED = ((0, 16), (5, 8), (7, 8))
+    _OUT_ALIGNED_TEXT = "out obs must be 16-byte aligned, road_mask and the labels 8-byte aligned"
+
+    def __init__(self, episodes, rollout_len=5, pred_len=1, future_step=1, exp="other", xy_range=None):
+        """episodes: as `DeviceExpertDataset`, every shard with `ego_global_pos` [N, 91, 2] and `ego_global_rot` [N, 91, 1]
+        (f32, contiguous) as well.  future_step: 1..90.  exp: 'other' (the partners' positions future_step ahead, in the
+        ego's current frame) or 'ego' (the ego's own displacement).  xy_range: ((xlo, xhi), (ylo, yhi)) of the 8 x 8 classes,
+        'ego' only; (-0.05, 0.05) for both without it.  The index is `DeviceExpertDataset`'s."""
+        code, xbins, ybins = _check_future(future_step, exp, xy_range)
+        self.future_step, self.exp, self.xbins, self.ybins = future_step, exp, xbins, ybins
+        self._OUT_NAMES = self.OUT_NAMES[exp]
+        super().__init__(episodes, rollout_len=rollout_len, pred_len=pred_len)
+        f = self._future = _capi.GdIlFuture()
+        f.future_step, f.exp = future_step, code
+        f.xbins[:], f.ybins[:] = xbins.tolist(), ybins.tolist()
+        for i, t in enumerate(self._shards):
+            f.ego_global_pos[i], f.ego_global_rot[i] = t["ego_global_pos"].data_ptr(), t["ego_global_rot"].data_ptr()
+
+    def batch_shapes(self, batch):
+        """(shape, dtype) of the eight outputs of `batch()` for `batch` samples."""
+        R, P, A = self.rollout_len, self.pred_len, self.max_agents
+        future = (batch, A - 1) if self.exp == "other" else (batch,)
+        return (((batch, R, self.obs_width), torch.float32), ((batch, P, 3), torch.float32), ((batch,), torch.bool),
+                ((batch, R), torch.bool), ((batch, R, A - 1), torch.bool), ((batch, R, ROAD_POINTS), torch.bool),
+                (future, torch.bool), (future, torch.int64))
+
+    def batch(self, sel, out=None):
+        """The samples at positions `sel` of the index as the eight tensors baselines/il/linear_probing.py:173 unpacks:
+        (obs [B, R, D] f32, actions [B, P, 3] f32, valid_mask [B] bool, ego_mask [B, R] bool, partner_mask [B, R, A - 1] bool,
+        road_mask [B, R, 200] bool, then for exp='other' aux_mask [B, A - 1] bool and other_pos [B, A - 1] int64, for exp='ego'
+        future_valid_mask [B] bool and ego_pos [B] int64).  obs, actions, partner_mask and road_mask are what
+        `DeviceExpertDataset.batch(sel)` gives.  One launch on torch's current stream, no host synchronisation.  A position
+        outside [0, len) gives that padding, False in valid_mask, ego_mask and future_valid_mask, True in aux_mask and the
+        class of (0, 0) as label, and counts in `bad_indices`.  out: the eight tensors of an earlier call with the same B."""
+        B, out = self._outputs(sel, out)
+        if B == 0:
+            return out
+        b = _capi.GdIlFutureBuffers()
+        b.entries, b.n_entries, b.sel, b.batch = self._entries.data_ptr(), self._len, sel.data_ptr(), B
+        b.bad_indices = self.bad_indices.data_ptr()
+        (b.obs, b.actions, b.valid_mask, b.ego_mask, b.partner_mask, b.road_mask, b.future_mask,
+         b.future_pos) = (o.data_ptr() for o in out)
+        with torch.cuda.device(self.device):
+            _capi.check(self._L.gd_il_future_batch(C.byref(self._ds), C.byref(self._future), C.byref(b), self._stream()),
+                        "gd_il_future_batch")
+        return out

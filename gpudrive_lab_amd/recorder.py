@@ -92,6 +92,12 @@ class ExpertEpisode:
         from .il_dataset import DeviceExpertDataset
         return DeviceExpertDataset(self, **kw)
 
+    def future_dataset(self, **kw):
+        """The `DeviceFutureDataset` over this episode where it lies: linear-probing batches with future position labels
+        (il_dataset.py; rollout_len = 5, pred_len = 1, future_step = 1, exp = 'other')."""
+        from .il_dataset import DeviceFutureDataset
+        return DeviceFutureDataset(self, **kw)
+
 
 class ExpertRecorder:
     def __init__(self, sim, mask=None):

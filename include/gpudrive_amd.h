@@ -305,6 +305,54 @@ typedef struct gd_il_batch_buffers {
  * true, data_idx (-1, -1)) and counts in bad_indices.  GD_ERR_INVALID as above, and for batch < 0, batch > 2^25 - 1 or
  * n_entries < 0. */
 int gd_il_batch(const gd_il_dataset *ds, const gd_il_batch_buffers *buffers, void *stream);
+/* Linear-probing batches from the same recording and the same index: the reference's FutureDataset
+ * (gpudrive/integrations/il/linear_probing/dataloader.py:6-230; unpacked by baselines/il/linear_probing.py:173) without its
+ * padded copy of obs, its [N][91][A-1] arrays of transformed positions and its per-sample slicing.  A label is computed per
+ * sample inside the gather, in fp32 in the reference's operation order (no fused multiply-add, correctly rounded division,
+ * cos / sin evaluated in double and rounded once).  F = future_step, (n, idx2) the sample's source row and current time,
+ * valid[n][t] gd_il_index's flag, pos / rot the ego's recorded pose (gd_record_buffers' ego_global_pos / ego_global_rot).
+ *   cls(v, b)  = clamp(#{i : b[i] <= (double)v} - 1, 0, 7); a NaN v gives 7 (numpy.digitize)
+ *   label(x, y) = cls(x, xbins) * 8 + cls(y, ybins);  norm(v) = 2 * ((v - (-1000)) / 2000) - 1
+ *   GD_IL_FUTURE_EGO: future_mask [batch] = valid[n][idx2] && idx2 + F < 91 && valid[n][idx2 + F]; future_pos [batch] =
+ *     label(0, 0) where idx2 + F >= 91, else with d = pos[idx2 + F] - pos[idx2], c = cos(rot[idx2]), s = sin(rot[idx2]):
+ *     label(norm(d.x * c + d.y * s), norm((-d.x) * s + d.y * c)).
+ *   GD_IL_FUTURE_OTHER, per partner column j: future_mask [batch][A-1] = partner_mask[n][idx2][j] != 0 || idx2 + F >= 91 ||
+ *     partner_mask[n][idx2 + F][j] != 0; future_pos [batch][A-1] = label(0, 0) where the mask is true, else with
+ *     p = obs[n][idx2 + F][6 + 6j + 1 .. + 3) * 1000, e = pos[idx2 + F], c / s = cos / sin(rot[idx2 + F]):
+ *     g = ((e.x + p.x * c) - p.y * s, (e.y + p.x * s) + p.y * c), d = g - pos[idx2], c2 / s2 = cos / sin(-rot[idx2]):
+ *     label(norm(d.x * c2 + d.y * s2), norm((-d.x) * s2 + d.y * c2)) -- the reference's rotation by +rot[idx2]
+ *     (dataloader.py:105-109), reproduced. */
+enum { GD_IL_FUTURE_OTHER = 0,  /* exp='other': the partners' positions F steps ahead, in the ego's current frame */
+       GD_IL_FUTURE_EGO = 1 };  /* exp='ego': the ego's own displacement over F steps */
+typedef struct gd_il_future {
+    const float *ego_global_pos[GD_IL_MAX_SHARDS];  /* per shard of the dataset: [n_rows][91][2] */
+    const float *ego_global_rot[GD_IL_MAX_SHARDS];  /* per shard of the dataset: [n_rows][91][1] */
+    int32_t future_step;          /* F, 1..90 */
+    int32_t exp;                  /* GD_IL_FUTURE_* */
+    double xbins[9], ybins[9];    /* the bin edges, strictly increasing (numpy.linspace(lo, hi, 9); the reference's default
+                                   * is (-0.05, 0.05) for both) */
+} gd_il_future;
+typedef struct gd_il_future_buffers {
+    const int32_t *entries;   /* as gd_il_batch_buffers */
+    int64_t n_entries;
+    const int64_t *sel;
+    int32_t batch;
+    int32_t *bad_indices;
+    /* outputs, in the order linear_probing.py:173 unpacks them; every byte of each is written by every call */
+    float *obs;               /* [batch][R][D] as gd_il_batch's, bit for bit; 16-byte aligned */
+    float *actions;           /* [batch][P][3] as gd_il_batch's */
+    uint8_t *valid_mask;      /* [batch] bool: valid[n][idx2 + P - 1] (true for every sample of the index) */
+    uint8_t *ego_mask;        /* [batch][R] bool: valid[n][idx2 - R + 1 + r], false where the time is < 0 */
+    uint8_t *partner_mask;    /* [batch][R][A-1] bool as gd_il_batch's.  Any alignment */
+    uint8_t *road_mask;       /* [batch][R][200] bool as gd_il_batch's; 8-byte aligned */
+    uint8_t *future_mask;     /* OTHER: [batch][A-1] bool (aux_mask), any alignment; EGO: [batch] bool (future_valid_mask) */
+    int64_t *future_pos;      /* OTHER: [batch][A-1] (other_pos); EGO: [batch] (ego_pos); classes 0..63 */
+} gd_il_future_buffers;
+/* One linear-probing batch: one launch, no host synchronisation.  A sel outside [0, n_entries) gives gd_il_batch's padding
+ * in obs, actions, partner_mask and road_mask, false in valid_mask, ego_mask and the EGO future_mask, true in the OTHER
+ * future_mask, label(0, 0) in future_pos, and counts in bad_indices.  GD_ERR_INVALID as gd_il_batch, and for a null pose
+ * pointer of a shard, F outside [1, 90], an unknown exp, and bin edges that are not finite and strictly increasing. */
+int gd_il_future_batch(const gd_il_dataset *ds, const gd_il_future *future, const gd_il_future_buffers *buffers, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
