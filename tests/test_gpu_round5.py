@@ -481,7 +481,7 @@ def test_bev_rasters_left_in_place_are_the_rasters_a_repaint_would_produce(monke
             for s in (skip, plain, orc):
                 s.reset([0, 3])
         if step == 19:
-            assert P.compare_bev(skip, orc) > 0.001   # (the oracle has no debug_set_state: it leaves here)
+            assert P.compare_bev(skip, orc) > 0.001   # (the oracle is not teleported at step 20, OracleSim.set_state notwithstanding: it leaves here)
         if step == 20:
             st = skip.debug_get_state()
             st[:, 1:3, 0] += 8.0
