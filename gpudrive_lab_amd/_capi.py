@@ -145,11 +145,29 @@ class GdIlFutureBuffers(C.Structure):
                 ("future_pos", C.c_void_p)]
 
 
+class GdRollout(C.Structure):
+    """gd_rollout: the sizes, the storage and the counters of the device rollout buffer (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("batch_size", "num_rows", "obs_width", "action_width")] +
+                [(n, C.c_void_p) for n in ("obs", "actions", "logprobs", "rewards", "dones", "values", "row", "ord", "count",
+                                           "dst", "state")])
+
+
+ROLLOUT_STATE = ("ptr", "step", "dropped", "bad_positions")  # gd_rollout.state
+
+
+class GdRolloutBatch(C.Structure):
+    """gd_rollout_batch: the permutation, the advantages, the minibatch geometry and the seven outputs (device pointers)."""
+    _fields_ = ([("idxs", C.c_void_p), ("advantages", C.c_void_p)] +
+                [(n, C.c_int32) for n in ("num_minibatches", "minibatch_rows", "bptt_horizon", "first", "n", "split")] +
+                [(n, C.c_void_p) for n in ("obs", "actions", "logprobs", "dones", "values", "advantages_out", "returns")])
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_il_future_batch",
+    "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -220,6 +238,11 @@ def lib():
     L.gd_il_index.argtypes = [C.POINTER(GdIlDataset), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gd_il_batch.argtypes = [C.POINTER(GdIlDataset), C.POINTER(GdIlBatchBuffers), C.c_void_p]
     L.gd_il_future_batch.argtypes = [C.POINTER(GdIlDataset), C.POINTER(GdIlFuture), C.POINTER(GdIlFutureBuffers), C.c_void_p]
+    L.gd_rollout_store.argtypes = [C.POINTER(GdRollout)] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
+    L.gd_rollout_sort.argtypes = [C.POINTER(GdRollout), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gd_rollout_gae.argtypes = [C.POINTER(GdRollout), C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]
+    L.gd_rollout_gather.argtypes = [C.POINTER(GdRollout), C.POINTER(GdRolloutBatch), C.c_void_p]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -1535,6 +1535,94 @@ int gd_il_future_batch(const gd_il_dataset *ds, const gd_il_future *fu, const gd
     });
 }
 
+namespace {
+
+bool misaligned(const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n != 0; }
+
+// what every gd_rollout_* entry point requires of the buffer table
+const char *rollout_error(const gd_rollout *ro) {
+    if (!ro) return "null argument";
+    if (ro->batch_size < 1 || ro->num_rows < 1 || ro->obs_width < 1 || ro->action_width < 1)
+        return "batch_size, num_rows, obs_width and action_width must be >= 1";
+    if (ro->num_rows > (1 << 20)) return "num_rows above 2^20";
+    if (ro->batch_size > (1 << 22)) return "batch_size above 2^22";
+    if ((int64_t)ro->batch_size * std::max(ro->obs_width, ro->action_width) > ((int64_t)1 << 40)) return "storage above 2^40 elements";
+    if (!ro->obs || !ro->actions || !ro->logprobs || !ro->rewards || !ro->dones || !ro->values || !ro->row || !ro->ord ||
+        !ro->count || !ro->dst || !ro->state)
+        return "every buffer is required";
+    if (misaligned(ro->actions, 8)) return "actions must be 8-byte aligned";
+    for (const void *p : {(const void *)ro->obs, (const void *)ro->logprobs, (const void *)ro->rewards, (const void *)ro->dones,
+                          (const void *)ro->values, (const void *)ro->row, (const void *)ro->ord, (const void *)ro->count,
+                          (const void *)ro->dst, (const void *)ro->state})
+        if (misaligned(p, 4)) return "float and int32 buffers must be 4-byte aligned";
+    return nullptr;
+}
+
+}  // namespace
+
+int gd_rollout_store(const gd_rollout *ro, const float *obs, const float *value, const int64_t *action, const float *logprob,
+                     const float *reward, const uint8_t *done, const uint8_t *mask, int32_t streaming, void *stream) {
+    if (const char *e = rollout_error(ro)) return fail(GD_ERR_INVALID, std::string("gd_rollout_store: ") + e);
+    if (!obs || !value || !action || !logprob || !reward || !done || !mask)
+        return fail(GD_ERR_INVALID, "gd_rollout_store: every input is required");
+    if (misaligned(obs, 4) || misaligned(value, 4) || misaligned(logprob, 4) || misaligned(reward, 4) || misaligned(action, 8))
+        return fail(GD_ERR_INVALID, "gd_rollout_store: float inputs must be 4-byte aligned and action 8-byte aligned");
+    return guarded([&]() {
+        gd::launch_rollout_store(*ro, static_cast<hipStream_t>(stream), obs, value, action, logprob, reward, done, mask,
+                                 streaming != 0);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_rollout_sort(const gd_rollout *ro, const int64_t *offset, int64_t *idxs, void *stream) {
+    if (const char *e = rollout_error(ro)) return fail(GD_ERR_INVALID, std::string("gd_rollout_sort: ") + e);
+    if (!offset || !idxs) return fail(GD_ERR_INVALID, "gd_rollout_sort: offset and idxs are required");
+    if (misaligned(offset, 8) || misaligned(idxs, 8)) return fail(GD_ERR_INVALID, "gd_rollout_sort: offset and idxs must be 8-byte aligned");
+    return guarded([&]() {
+        gd::launch_rollout_sort(*ro, static_cast<hipStream_t>(stream), offset, idxs);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_rollout_gae(const gd_rollout *ro, const int64_t *idxs, float gamma, float gae_lambda, float *delta, float *coef,
+                   float *advantages, void *stream) {
+    if (const char *e = rollout_error(ro)) return fail(GD_ERR_INVALID, std::string("gd_rollout_gae: ") + e);
+    if (!idxs || !delta || !coef || !advantages) return fail(GD_ERR_INVALID, "gd_rollout_gae: every buffer is required");
+    if (misaligned(idxs, 8) || misaligned(delta, 4) || misaligned(coef, 4) || misaligned(advantages, 4))
+        return fail(GD_ERR_INVALID, "gd_rollout_gae: idxs must be 8-byte aligned, delta, coef and advantages 4-byte aligned");
+    if (!std::isfinite(gamma) || !std::isfinite(gae_lambda) || !std::isfinite(gamma * gae_lambda))
+        return fail(GD_ERR_INVALID, "gd_rollout_gae: gamma, gae_lambda and their product must be finite");
+    return guarded([&]() {
+        gd::launch_rollout_gae(*ro, static_cast<hipStream_t>(stream), idxs, gamma, gae_lambda, delta, coef, advantages);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_rollout_gather(const gd_rollout *ro, const gd_rollout_batch *b, void *stream) {
+    if (const char *e = rollout_error(ro)) return fail(GD_ERR_INVALID, std::string("gd_rollout_gather: ") + e);
+    if (!b) return fail(GD_ERR_INVALID, "gd_rollout_gather: null argument");
+    if (b->num_minibatches < 1 || b->minibatch_rows < 1 || b->bptt_horizon < 1 ||
+        (int64_t)b->num_minibatches * b->minibatch_rows * b->bptt_horizon != ro->batch_size)
+        return fail(GD_ERR_INVALID, "gd_rollout_gather: num_minibatches * minibatch_rows * bptt_horizon must be batch_size");
+    if (b->first < 0 || b->n < 1 || b->n > b->num_minibatches - b->first)
+        return fail(GD_ERR_INVALID, "gd_rollout_gather: [first, first + n) must lie inside the minibatches");
+    if (b->split < 0 || b->split > 64) return fail(GD_ERR_INVALID, "gd_rollout_gather: split must be 0..64");
+    // one launch of 256-lane workgroups: samples * split workgroups must stay below 2^24 (2^32 lanes)
+    if ((int64_t)b->n * b->minibatch_rows * b->bptt_horizon * std::max(b->split, 1) >= ((int64_t)1 << 24))
+        return fail(GD_ERR_INVALID, "gd_rollout_gather: samples * split must be below 2^24");
+    if (!b->idxs || !b->advantages || !b->obs || !b->actions || !b->logprobs || !b->dones || !b->values || !b->advantages_out ||
+        !b->returns)
+        return fail(GD_ERR_INVALID, "gd_rollout_gather: every buffer is required");
+    if (misaligned(b->idxs, 8) || misaligned(b->actions, 8) || misaligned(b->advantages, 4) || misaligned(b->obs, 4) ||
+        misaligned(b->logprobs, 4) || misaligned(b->dones, 4) || misaligned(b->values, 4) || misaligned(b->advantages_out, 4) ||
+        misaligned(b->returns, 4))
+        return fail(GD_ERR_INVALID, "gd_rollout_gather: idxs and actions must be 8-byte aligned, float buffers 4-byte aligned");
+    return guarded([&]() {
+        gd::launch_rollout_gather(*ro, static_cast<hipStream_t>(stream), *b);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

@@ -235,5 +235,12 @@ void launch_il_batch(const gd_il_dataset &ds, hipStream_t st, const gd_il_batch_
                      int split);  // il_batch.hip (split: workgroups per sample, 0: the default)
 void launch_il_future(const gd_il_dataset &ds, const gd_il_future &fu, hipStream_t st, const gd_il_future_buffers &b,
                       int split);  // il_batch.hip
+void launch_rollout_store(const gd_rollout &ro, hipStream_t st, const float *obs, const float *value, const int64_t *action,
+                          const float *logprob, const float *reward, const uint8_t *done, const uint8_t *mask,
+                          bool streaming);  // rollout.hip
+void launch_rollout_sort(const gd_rollout &ro, hipStream_t st, const int64_t *offset, int64_t *idxs);  // rollout.hip
+void launch_rollout_gae(const gd_rollout &ro, hipStream_t st, const int64_t *idxs, float gamma, float gae_lambda, float *delta,
+                        float *coef, float *adv);  // rollout.hip
+void launch_rollout_gather(const gd_rollout &ro, hipStream_t st, const gd_rollout_batch &b);  // rollout.hip
 
 }  // namespace gd

@@ -1,0 +1,294 @@
+"""The device rollout buffer: PPO experience stored, ordered, turned into advantages and cut into minibatches on the device.
+
+`DeviceRollout` is the reference's `Experience` with `compute_gae` (gpudrive/integrations/puffer/ppo.py:530-666, used by
+ppo.py:108-260) for the tensors `DeviceLearnerEnv.step` returns.  The reference takes every step's tensors to the host
+(`torch.where(mask)[0].cpu()`, five `.cpu().numpy()` copies, a Python list of (env_id, step) tuples), sorts the tuples in
+Python, runs the advantages as a serial host loop and copies everything back.  Here
+
+  - `store` is two launches without a host synchronisation (`gd_rollout_store`): a scan of the mask places the live rows,
+  - `full` answers from a host upper bound of the write position and reads the device only once the bound reaches the batch,
+  - `sort_training_data` needs no sort: an entry's place is the prefix sum of the per-row counts plus its ordinal in its row
+    (`gd_rollout_sort`),
+  - `compute_gae` runs one chain per run between dones (`gd_rollout_gae`; the rule is in csrc/gae_chain.hpp),
+  - `minibatch` and `flatten_batch` are one gather kernel (`gd_rollout_gather`).
+
+The loop:
+
+    while not ro.full:
+        ro.store(obs, value, action, logprob, rewards, terminals, masks)   # before the step that overwrites them
+        obs, rewards, terminals, truncations, masks = env.step(action)
+    ro.sort_training_data(); ro.compute_gae(gamma, gae_lambda)
+    obs, actions, logprobs, dones, values, advantages, returns = ro.minibatch(mb)
+
+Environment i of the reference's `env_id` is row i (pufferlib's `PufferEnv.recv` hands a native environment `range(N)`).
+
+Not here: the LSTM state, `cpu_offload`, `returns_np` (the reference adds sorted advantages to unsorted values there,
+ppo.py:660: a logging quirk, not a training input), and the training loop, losses and logging themselves."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _capi
+
+MAX_ROWS = 1 << 20
+MAX_BATCH = 1 << 22  # gd_rollout's limit, so that every kernel covers the batch with one launch
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def check_rollout_args(batch_size, minibatch_size, bptt_horizon, num_rows, obs_width, action_shape, device, lstm=None,
+                       cpu_offload=False):
+    """The constructor's arguments checked on the host (ValueError); returns (minibatch_size, num_minibatches,
+    minibatch_rows, action_shape as a tuple, torch.device).  The divisibility rules are `Experience.__init__`'s
+    (ppo.py:582-592)."""
+    who = "DeviceRollout: "
+    if lstm is not None:
+        raise ValueError(who + "lstm state is not built")
+    if cpu_offload:
+        raise ValueError(who + "cpu_offload is not built (the storage is on the device)")
+    if minibatch_size is None:
+        minibatch_size = batch_size
+    for name, v in (("batch_size", batch_size), ("minibatch_size", minibatch_size), ("bptt_horizon", bptt_horizon),
+                    ("num_rows", num_rows), ("obs_width", obs_width)):
+        if not _is_int(v) or v < 1:
+            raise ValueError(who + "%s must be a positive int, got %r" % (name, v))
+    if batch_size % minibatch_size:
+        raise ValueError(who + "batch_size must be divisible by minibatch_size")
+    if minibatch_size % bptt_horizon:
+        raise ValueError(who + "minibatch_size must be divisible by bptt_horizon")
+    if batch_size > MAX_BATCH:
+        raise ValueError(who + "batch_size must be at most %d (one launch covers the batch), got %d" % (MAX_BATCH, batch_size))
+    if obs_width > 2 ** 31 - 1:
+        raise ValueError(who + "obs_width must fit an int32")
+    if num_rows > MAX_ROWS:
+        raise ValueError(who + "num_rows must be at most %d, got %d" % (MAX_ROWS, num_rows))
+    try:
+        shape = tuple(action_shape)
+    except TypeError:
+        shape = None
+    if shape is None or not all(_is_int(v) and v >= 1 for v in shape):
+        raise ValueError(who + "action_shape must be a tuple of positive ints, got %r" % (action_shape,))
+    width = int(np.prod(shape, dtype=np.int64)) if shape else 1
+    if batch_size * max(obs_width, width) > 2 ** 40:
+        raise ValueError(who + "the storage would exceed 2^40 elements")
+    try:
+        dev = torch.device(device)
+    except (RuntimeError, TypeError) as e:
+        raise ValueError(who + "device: %s" % e)
+    if dev.type != "cuda":
+        raise ValueError(who + "the buffer lives on the GPU (there is no host path), got device %r" % (device,))
+    return minibatch_size, batch_size // minibatch_size, minibatch_size // bptt_horizon, shape, dev
+
+
+class DeviceRollout:
+    def __init__(self, batch_size, minibatch_size=None, bptt_horizon=1, *, num_rows, obs_width, action_shape=(),
+                 device="cuda", lstm=None, cpu_offload=False, streaming_stores=False, gather_split=0, storage=None):
+        """batch_size, minibatch_size (None: batch_size), bptt_horizon: `Experience.__init__`'s, with its divisibility
+        rules.  num_rows: N, the rows of every step's inputs.  obs_width: any positive width (D of `DeviceLearnerEnv`, D + 3 of
+        `ConditionedLearnerEnv`).  action_shape: the shape of one action, () for one index.  lstm / cpu_offload: refused.
+        streaming_stores: `store` writes the observation rows with non-temporal stores.  gather_split: workgroups per sample
+        of `minibatch` / `flatten_batch`, 1..64 (0: the library's default).  storage: a dict of caller-allocated tensors for
+        any of obs, actions, logprobs, rewards, dones, values (contiguous, on the device, of the public shapes and dtypes),
+        used in place of the zero-filled ones the constructor would allocate.  Every argument is checked before anything
+        reaches the device (ValueError)."""
+        (self.minibatch_size, self.num_minibatches, self.minibatch_rows, self.action_shape,
+         dev) = check_rollout_args(batch_size, minibatch_size, bptt_horizon, num_rows, obs_width, action_shape, device, lstm,
+                                   cpu_offload)
+        self.batch_size, self.bptt_horizon, self.num_rows, self.obs_width = batch_size, bptt_horizon, num_rows, obs_width
+        self.streaming_stores = bool(streaming_stores)
+        if not _is_int(gather_split) or not 0 <= gather_split <= 64:
+            raise ValueError("DeviceRollout: gather_split must be an int in [0, 64], got %r" % (gather_split,))
+        self.gather_split = gather_split
+        if storage is not None and (not isinstance(storage, dict) or set(storage) - set(self.STORAGE_NAMES)):
+            raise ValueError("DeviceRollout: storage must be a dict with keys out of %s" % (self.STORAGE_NAMES,))
+        self._given = storage or {}
+        self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._action_width = int(np.prod(self.action_shape, dtype=np.int64)) if self.action_shape else 1
+        B, N = batch_size, num_rows
+        self.obs = self._alloc("obs", (B, obs_width), torch.float32)
+        self.actions = self._alloc("actions", (B,) + self.action_shape, torch.int64)
+        self.logprobs = self._alloc("logprobs", (B,), torch.float32)
+        self.rewards = self._alloc("rewards", (B,), torch.float32)
+        self.dones = self._alloc("dones", (B,), torch.float32)
+        self.values = self._alloc("values", (B,), torch.float32)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)  # noqa: E731
+        self._row, self._ord = z((B,), torch.int32), z((B,), torch.int32)
+        self._count, self._dst = z((N,), torch.int32), z((N,), torch.int32)
+        self.state = z((4,), torch.int32)  # ptr, step, dropped, bad_positions
+        self.idxs = z((B,), torch.int64)
+        self.advantages = z((B,), torch.float32)
+        self._delta, self._coef = z((B,), torch.float32), z((B,), torch.float32)
+        r = self._ro = _capi.GdRollout()
+        r.batch_size, r.num_rows, r.obs_width, r.action_width = B, N, obs_width, self._action_width
+        for name, t in (("obs", self.obs), ("actions", self.actions), ("logprobs", self.logprobs), ("rewards", self.rewards),
+                        ("dones", self.dones), ("values", self.values), ("row", self._row), ("ord", self._ord),
+                        ("count", self._count), ("dst", self._dst), ("state", self.state)):
+            setattr(r, name, t.data_ptr())
+        self._L = _capi.lib()
+        self._ptr_bound = 0     # host upper bound of the device ptr
+        self.host_reads = 0     # reads of the device ptr by `full`
+        self._sorted = self._has_gae = False
+
+    STORAGE_NAMES = ("obs", "actions", "logprobs", "rewards", "dones", "values")
+
+    def _alloc(self, name, shape, dtype):
+        """One public storage tensor: the caller's (`storage=`), or zeros as the reference's."""
+        t = self._given.get(name)
+        if t is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device \
+                or not t.is_contiguous():
+            raise ValueError("DeviceRollout: storage[%r] must be a contiguous %s tensor of shape %s on %s"
+                             % (name, dtype, tuple(shape), self.device))
+        return t
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # the counters, as 0-d views of `state` on the device (reading one is a host synchronisation)
+    ptr = property(lambda self: self.state[0])
+    step = property(lambda self: self.state[1])
+    dropped = property(lambda self: self.state[2])
+    bad_positions = property(lambda self: self.state[3])
+
+    @property
+    def nbytes(self):
+        """What the object allocates: the storage, the per-entry and per-row bookkeeping, idxs, the advantages and their
+        two scratch arrays, the counters.  `flatten_batch` allocates its own second copy on top; `minibatch` one minibatch."""
+        ts = (self.obs, self.actions, self.logprobs, self.rewards, self.dones, self.values, self._row, self._ord, self._count,
+              self._dst, self.state, self.idxs, self.advantages, self._delta, self._coef)
+        return sum(t.numel() * t.element_size() for t in ts)
+
+    def _input(self, name, t, dtype, shapes):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) not in shapes or t.device != self.device \
+                or not t.is_contiguous():
+            raise ValueError("DeviceRollout.store: %s must be a contiguous %s tensor of shape %s on %s"
+                             % (name, dtype, " or ".join(map(str, shapes)), self.device))
+        return t.data_ptr()
+
+    def store(self, obs, value, action, logprob, reward, done, mask):
+        """One step of experience (ppo.py:606-620 with env_id[i] = i): the live rows `where(mask)[0]`, ascending, cut to the
+        first batch_size - ptr, land at [ptr, ptr + k) in that order; ptr += k, step += 1 (also with nothing live), and a
+        live row that did not fit counts in `dropped`.  obs [N, obs_width] f32, value [N] or [N, 1] f32, action
+        [N, *action_shape] int64, logprob / reward [N] f32, done / mask [N] bool.  Two launches on torch's current stream, no
+        host synchronisation.
+
+        The inputs are read when the launches run, not when `store` returns.  The learner env's buffers are overwritten in
+        place by the next `env.step`, so the contract is: `store` is enqueued BEFORE `env.step(actions)` on the same stream."""
+        N = self.num_rows
+        ptrs = (self._input("obs", obs, torch.float32, ((N, self.obs_width),)),
+                self._input("value", value, torch.float32, ((N,), (N, 1))),
+                self._input("action", action, torch.int64, ((N,) + self.action_shape,)),
+                self._input("logprob", logprob, torch.float32, ((N,),)),
+                self._input("reward", reward, torch.float32, ((N,),)),
+                self._input("done", done, torch.bool, ((N,),)),
+                self._input("mask", mask, torch.bool, ((N,),)))
+        with torch.cuda.device(self.device):
+            _capi.check(self._L.gd_rollout_store(C.byref(self._ro), *ptrs, int(self.streaming_stores), self._stream()),
+                        "gd_rollout_store")
+        self._ptr_bound = min(self._ptr_bound + N, self.batch_size)
+        self._sorted = self._has_gae = False
+
+    @property
+    def full(self):
+        """ptr >= batch_size (ppo.py:602-604) without a synchronisation per step: False from the host bound while it is
+        below batch_size; once it reaches it, the 4-byte device ptr is read (counted in `host_reads`) and replaces the bound."""
+        if self._ptr_bound < self.batch_size:
+            return False
+        self._ptr_bound = int(self.state[0].item())
+        self.host_reads += 1
+        return self._ptr_bound >= self.batch_size
+
+    def sort_training_data(self):
+        """`idxs`, device int64 [batch_size]: the permutation the reference's `sorted` over (env_id, step) gives
+        (ppo.py:622-625), by row, then by step.  RuntimeError unless the buffer is full (the reference's reshape throws there
+        too).  Resets ptr, step and the per-row counts, like the reference; the storage itself stays until the next `store`
+        overwrites it, so `compute_gae` and the minibatches come before the next rollout.  The tensor returned is the object's
+        own and is rewritten by the next call."""
+        if not self.full:
+            raise RuntimeError("DeviceRollout.sort_training_data: the buffer is not full")
+        with torch.cuda.device(self.device):
+            offset = (torch.cumsum(self._count, 0, dtype=torch.int64) - self._count).contiguous()
+            _capi.check(self._L.gd_rollout_sort(C.byref(self._ro), offset.data_ptr(), self.idxs.data_ptr(), self._stream()),
+                        "gd_rollout_sort")
+        self._ptr_bound = 0
+        self._sorted, self._has_gae = True, False
+        return self.idxs
+
+    def compute_gae(self, gamma, gae_lambda):
+        """The advantages in sorted order, float32 [batch_size] on the device (`advantages`): the rule of
+        csrc/gae_chain.hpp, the serial loop over the whole sorted batch (it runs from one row's last entry into the next
+        row's first, as the reference's does) as independent chains between dones.  gamma and gae_lambda are rounded to
+        float32 first.  RuntimeError before `sort_training_data`."""
+        if not self._sorted:
+            raise RuntimeError("DeviceRollout.compute_gae: call sort_training_data first")
+        try:
+            g, lam = float(np.float32(gamma)), float(np.float32(gae_lambda))
+        except (TypeError, ValueError):
+            raise ValueError("DeviceRollout.compute_gae: gamma and gae_lambda must be numbers")
+        with torch.cuda.device(self.device):
+            _capi.check(self._L.gd_rollout_gae(C.byref(self._ro), self.idxs.data_ptr(), g, lam, self._delta.data_ptr(),
+                                               self._coef.data_ptr(), self.advantages.data_ptr(), self._stream()),
+                        "gd_rollout_gae")
+        self._has_gae = True
+        return self.advantages
+
+    OUT_NAMES = ("obs", "actions", "logprobs", "dones", "values", "advantages", "returns")
+
+    def batch_shapes(self, n=None):
+        """(shape, dtype) of the seven outputs of `minibatch` (n None), or of `flatten_batch` over n minibatches."""
+        lead = () if n is None else (n,)
+        rows, h, mbs = self.minibatch_rows, self.bptt_horizon, self.minibatch_size
+        f = torch.float32
+        return ((lead + (rows, h, self.obs_width), f), (lead + (rows, h) + self.action_shape, torch.int64),
+                (lead + (rows, h), f), (lead + (rows, h), f), (lead + (mbs,), f), (lead + (mbs,), f), (lead + (mbs,), f))
+
+    def _gather(self, first, n, out, split=0):
+        b = _capi.GdRolloutBatch()
+        b.idxs, b.advantages = self.idxs.data_ptr(), self.advantages.data_ptr()
+        b.num_minibatches, b.minibatch_rows, b.bptt_horizon = self.num_minibatches, self.minibatch_rows, self.bptt_horizon
+        b.first, b.n, b.split = first, n, split
+        b.obs, b.actions, b.logprobs, b.dones, b.values, b.advantages_out, b.returns = (o.data_ptr() for o in out)
+        with torch.cuda.device(self.device):
+            _capi.check(self._L.gd_rollout_gather(C.byref(self._ro), C.byref(b), self._stream()), "gd_rollout_gather")
+        return out
+
+    def _ready(self, who):
+        if not (self._sorted and self._has_gae):
+            raise RuntimeError("DeviceRollout.%s: call sort_training_data and compute_gae first" % who)
+
+    def minibatch(self, mb, out=None):
+        """Minibatch `mb` as (obs [rows, bptt, obs_width], actions [rows, bptt, *action_shape], logprobs [rows, bptt],
+        dones [rows, bptt], values [minibatch_size], advantages [minibatch_size], returns [minibatch_size]): slice mb of the
+        reference's b_* tensors after flatten_batch (ppo.py:646-666), gathered by one launch without the second copy of the
+        observations.  out: the seven tensors of an earlier call, to be overwritten (every byte is written)."""
+        self._ready("minibatch")
+        if not _is_int(mb) or not 0 <= mb < self.num_minibatches:
+            raise ValueError("DeviceRollout.minibatch: mb must be an int in [0, %d), got %r" % (self.num_minibatches, mb))
+        want = self.batch_shapes()
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in want)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != len(want):
+                raise ValueError("DeviceRollout.minibatch: out must be the seven tensors of a minibatch")
+            for name, o, (shape, dt) in zip(self.OUT_NAMES, out, want):
+                if not isinstance(o, torch.Tensor) or o.dtype != dt or o.device != self.device or tuple(o.shape) != shape \
+                        or not o.is_contiguous():
+                    raise ValueError("DeviceRollout.minibatch: out %s must be a contiguous %s %s tensor on %s"
+                                     % (name, dt, shape, self.device))
+            out = tuple(out)
+        return self._gather(mb, 1, out, self.gather_split)
+
+    def flatten_batch(self):
+        """The reference's flatten_batch (ppo.py:646-666): sets b_obs, b_actions, b_logprobs, b_dones ([num_minibatches,
+        rows, bptt, ...]) and b_values, b_advantages, b_returns ([num_minibatches, minibatch_size]) by the same kernel over
+        all minibatches at once.  This is the reference's memory trade -- a second copy of the observations, after which the
+        minibatches are views; `minibatch` is the alternative that allocates one minibatch."""
+        self._ready("flatten_batch")
+        out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in self.batch_shapes(self.num_minibatches))
+        (self.b_obs, self.b_actions, self.b_logprobs, self.b_dones, self.b_values, self.b_advantages,
+         self.b_returns) = self._gather(0, self.num_minibatches, out, self.gather_split)
+        return out

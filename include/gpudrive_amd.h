@@ -353,6 +353,66 @@ typedef struct gd_il_future_buffers {
  * future_mask, label(0, 0) in future_pos, and counts in bad_indices.  GD_ERR_INVALID as gd_il_batch, and for a null pose
  * pointer of a shard, F outside [1, 90], an unknown exp, and bin edges that are not finite and strictly increasing. */
 int gd_il_future_batch(const gd_il_dataset *ds, const gd_il_future *future, const gd_il_future_buffers *buffers, void *stream);
+/* Device rollout buffer: the consumer of the learner rows on the PPO side.  Replaces the reference's Experience and
+ * compute_gae (gpudrive/integrations/puffer/ppo.py:530-666, used by ppo.py:108-260): store's host copy of the live indices
+ * and of five arrays per step (ppo.py:606-620), the Python sorted() over (env_id, step) tuples (ppo.py:622-644), the serial
+ * host loop of the advantages (ppo.py:239-245) and flatten_batch's copies back to the device (ppo.py:646-666).  Needs no
+ * simulator: every pointer is a device pointer owned by the caller, `stream` is a hipStream_t (NULL: the default stream).
+ * B = batch_size, N = num_rows, D = obs_width (any positive width), AW = action_width (the product of the action shape, 1 for
+ * a scalar action).  env_id[i] = i: row i of a step's inputs is environment i. */
+typedef struct gd_rollout {
+    int32_t batch_size, num_rows, obs_width, action_width;
+    /* the storage, in the order the entries were stored */
+    float *obs;        /* [B][D]; 16-byte pieces are used where D % 4 == 0 and the pointer is 16-byte aligned */
+    int64_t *actions;  /* [B][AW] */
+    float *logprobs;   /* [B] */
+    float *rewards;    /* [B] */
+    float *dones;      /* [B] 0.0f or 1.0f */
+    float *values;     /* [B] */
+    int32_t *row;      /* [B] the entry's row (env_id) */
+    int32_t *ord;      /* [B] how many entries of that row were stored before it in this rollout */
+    int32_t *count;    /* [N] entries of each row in this rollout */
+    int32_t *dst;      /* [N] scratch of one store: the storage position of each row, -1 where nothing is stored */
+    int32_t *state;    /* [4] ptr, step, dropped (live rows that did not fit, never reset), bad_positions (positions outside
+                        * [0, B) met by sort, gae or gather, never reset; 0 unless a caller hands in a foreign idxs) */
+} gd_rollout;
+/* One step (ppo.py:606-620): the live rows are the i with mask[i] != 0, ascending, cut to the first B - ptr of them; they
+ * land at [ptr, ptr + k) in that order.  ptr += k, step += 1 (also when nothing is live), dropped += the live rows that did
+ * not fit.  Two launches, no host synchronisation, no atomics: one workgroup scans the mask and writes dst, the scalars, row,
+ * ord and count, then a workgroup per row copies its D floats.  The inputs are read when the launches run: enqueue the call
+ * before whatever overwrites them on the same stream.  obs [N][D], value / logprob / reward [N], action [N][AW] int64,
+ * done / mask [N] bool.  streaming != 0: the observation rows are stored non-temporally.  GD_ERR_INVALID: a null pointer, a
+ * size < 1, num_rows > 2^20, B > 2^22 (every kernel covers the batch with one launch), B * max(D, AW) > 2^40. */
+int gd_rollout_store(const gd_rollout *ro, const float *obs, const float *value, const int64_t *action, const float *logprob,
+                     const float *reward, const uint8_t *done, const uint8_t *mask, int32_t streaming, void *stream);
+/* The permutation of ppo.py:622-625, sorted by (row, step), without a sort: idxs[offset[row[p]] + ord[p]] = p for every
+ * p in [0, B), with offset [N] int64 the exclusive prefix sum of count (the caller's, as gd_il_index's offsets are).  Then
+ * ptr = 0, step = 0 and count[] = 0 (ppo.py:641-643).  The storage must be full (ptr == B): the caller checks.  One launch. */
+int gd_rollout_sort(const gd_rollout *ro, const int64_t *offset, int64_t *idxs, void *stream);
+/* The advantages in sorted order (ppo.py:239-245), [B] float32: the rule of csrc/gae_chain.hpp, which states the operation
+ * order and the two float corner cases in which cutting the chain at a done differs from the serial loop.  gamma and
+ * gae_lambda are float32 already.  delta, coef: [B] float32 scratch, written whole.  Two launches: the terms through idxs,
+ * then one chain per run between dones; no workgroup waits on another.  A batch without a done is one chain of B, walked by
+ * one lane.  GD_ERR_INVALID: a null pointer, gamma or gae_lambda not finite. */
+int gd_rollout_gae(const gd_rollout *ro, const int64_t *idxs, float gamma, float gae_lambda, float *delta, float *coef,
+                   float *advantages, void *stream);
+typedef struct gd_rollout_batch {
+    const int64_t *idxs;        /* [B] gd_rollout_sort's */
+    const float *advantages;    /* [B] gd_rollout_gae's, in sorted order */
+    int32_t num_minibatches, minibatch_rows, bptt_horizon;  /* B = num_minibatches * minibatch_rows * bptt_horizon */
+    int32_t first, n;           /* the minibatches [first, first + n) are gathered */
+    int32_t split;              /* workgroups per sample, 1..64; 0: the default */
+    /* outputs, [n][minibatch_rows][bptt_horizon] each; every byte of each is written by every call */
+    float *obs;                 /* [..][D]; 16-byte pieces where D % 4 == 0 and both obs pointers are 16-byte aligned */
+    int64_t *actions;           /* [..][AW] */
+    float *logprobs, *dones, *values, *advantages_out, *returns;
+} gd_rollout_batch;
+/* Minibatches as flatten_batch lays them out (ppo.py:646-666): sample (m, r, h) has the sorted position
+ * s = (r * num_minibatches + first + m) * bptt_horizon + h and the storage position p = idxs[s]; it takes obs, actions,
+ * logprobs, dones and values at p, advantages at s, and returns = advantages[s] + values[p] (one fp32 add).  One launch, no
+ * host synchronisation.  A p outside [0, B) gives zeros and counts in state[3].  GD_ERR_INVALID: a null pointer, sizes that
+ * do not multiply to B, [first, first + n) outside the minibatches, split outside 0..64, samples * split >= 2^24. */
+int gd_rollout_gather(const gd_rollout *ro, const gd_rollout_batch *batch, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
