@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "dev_mem.hpp"
 #include "engine.hpp"
 #include "gd_math.hpp"
 #include "scene.hpp"
@@ -84,11 +85,68 @@ int64_t spec_bytes(const TensorSpec &s) {
     return n;
 }
 
+// runtime handles that destroy themselves (hipEvent_t and hipStream_t are pointers to opaque structs)
+struct HandleDelete {
+    void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+    void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+    void operator()(int32_t *pinned) const { (void)hipHostFree(pinned); }
+};
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, HandleDelete>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, HandleDelete>;
+using PinnedFlags = std::unique_ptr<int32_t, HandleDelete>;
+
+Event make_event(unsigned flags = hipEventDefault) {
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+    return Event(e);
+}
+
 struct EventPair {
-    hipEvent_t start, stop;
+    Event start, stop;
+};
+
+// What rebuild_worlds keeps of one world on the host, to repack the batch's arrays on set_maps / deleteAgents.
+struct WorldHost {
+    std::vector<float> xy, aux;    // road points, road records
+    int agents = 0;                // live agents (shape[w][0])
+    std::vector<int32_t> resp;     // response type of every agent slot (who can move at all)
+    std::vector<gd::RoadBox> boxes;
+    gd::GridHdr grid{};            // grid over the collidable boxes
+    std::vector<int32_t> cell_off, cell_items;
+    gd::GridHdr rgrid{};           // grid over all roads (set-order selection)
+    std::vector<int32_t> rcell_off;
+    std::vector<uint16_t> rcell_items;
+};
+
+// A device array of T that rebuild_worlds may have to grow: n entries are written and kReadable more must exist behind them;
+// when that does not fit, the array is reallocated (contents gone) with room for n + n / 8 + kPad.
+struct Float8 { float v[8]; };
+template <typename T, size_t kReadable, size_t kPad>
+struct Growable {
+    gd::DevMem mem;
+    // `view` is the kernels' pointer to the array: written here, so that it never holds an address that was returned (null
+    // while the owner is empty, i.e. when the allocation threw).  True when the array was reallocated.
+    template <typename V>
+    bool fit(size_t n, V *&view) {
+        view = nullptr;
+        const bool grew = mem.reserve((n + kReadable) * sizeof(T), (n + n / 8 + kPad) * sizeof(T));
+        view = static_cast<V *>(mem.get());
+        return grew;
+    }
+    void upload(const void *src, size_t n) const {
+        if (n) HIP_CHECK(hipMemcpy(mem.get(), src, n * sizeof(T), hipMemcpyHostToDevice));
+    }
 };
 
 }  // namespace
+
+// dev_mem.hpp's two hooks
+void *gd::dev_alloc(size_t bytes) {
+    void *p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    return p;
+}
+void gd::dev_free(void *p) noexcept { (void)hipFree(p); }
 
 struct gd_sim {
     gd_config cfg{};
@@ -96,32 +154,37 @@ struct gd_sim {
     int W = 0, A = 0;
     hipStream_t stream = nullptr;
     gd::DevSim d{};
-    void *exported[GD_T_COUNT] = {};
-    bool owned[GD_T_COUNT] = {};
-    std::vector<void *> internal;
+    // Members are declared so that what is left after ~gd_sim's synchronise may go in any order: device memory, pinned
+    // memory, events and the side stream each return themselves.
+    void *exported[GD_T_COUNT] = {};        // views: the engine's own tensors (exported_mem) or the caller's (borrowed)
+    gd::DevMem exported_mem[GD_T_COUNT];
+    std::vector<gd::DevMem> internal;       // fixed-size arrays, allocated once (alloc_internal)
     std::vector<std::string> scenes;
     std::vector<int32_t> deleted;  // host mirror [W][A]
-    // per-world host road data (kept to repack the CSR on set_maps / deleteAgents)
-    std::vector<std::vector<float>> w_xy, w_aux;
-    std::vector<int> w_agents;  // live agents per world (shape[w][0])
+    std::vector<WorldHost> world_host;  // per-world host road data (kept to repack the CSR on set_maps / deleteAgents)
     int cu_count = 256;
-    std::vector<std::vector<gd::RoadBox>> w_boxes;
-    std::vector<gd::GridHdr> w_grid;
-    std::vector<std::vector<int32_t>> w_cell_off, w_cell_items;
-    std::vector<gd::GridHdr> w_rgrid;                    // grid over all roads (set-order selection)
-    std::vector<std::vector<int32_t>> w_rcell_off;
-    std::vector<std::vector<uint16_t>> w_rcell_items;
-    size_t rcell_cap = 0, ritem_cap = 0;
-    void *d_rcell_off = nullptr, *d_rcell_items = nullptr, *d_rcell_xy = nullptr, *d_rcell_pos = nullptr;
-    size_t cell_cap = 0, item_cap = 0;
-    void *d_cell_off = nullptr, *d_cell_items = nullptr, *d_cell_hdr = nullptr;
-    size_t road_cap = 0, box_cap = 0, blk_cap = 0;
-    void *d_road_blk = nullptr;
-    void *d_road_xy = nullptr, *d_road_aux = nullptr, *d_road_rec = nullptr, *d_boxes = nullptr;
+    // The arrays a rebuild may grow, each with its rule: <entry, readable entries behind the last one, padding>.
+    // k_map_obs requests chunks of 32 roads up to 256 roads past a world's last one, and the fused set-order write-out
+    // reads road_rec[first road of the world] even for a world without roads: the road arrays always end in 320 readable
+    // pad entries (also when a rebuild fits the old capacity, and when no world has a road)
+    Growable<float2, 320, 640> road_xy;
+    Growable<Float8, 320, 640> road_aux, road_rec;
+    Growable<gd::RoadBox, 0, 64> boxes;
+    Growable<int32_t, 0, 64> cell_off, cell_items;
+    Growable<float4, 0, 64> cell_hdr;
+    Growable<int32_t, 0, 64> rcell_off;
+    Growable<uint16_t, 64, 128> rcell_items, rcell_pos;
+    Growable<float2, 64, 128> rcell_xy;
+    Growable<float4, 0, 64> road_blk;
+    // per-world tables the engine uploads and the kernels only read (DevSim holds const views of them)
+    int32_t *d_road_off = nullptr, *d_box_off = nullptr, *d_blk_off = nullptr;
+    gd::GridHdr *d_grid = nullptr, *d_rgrid = nullptr;
+    float4 *d_road_bbox = nullptr;
+    float *d_road_rbmax = nullptr;
     // pinned flag staging ring
     static constexpr int kRing = 8;
-    int32_t *h_flags[kRing] = {};
-    hipEvent_t flag_ev[kRing] = {};
+    PinnedFlags h_flags[kRing];
+    Event flag_ev[kRing];
     int ring_pos = 0;
     // kernel timing
     // A fixed ring of event pairs per kernel, created when timing is switched on: a launch re-records the oldest pair
@@ -131,14 +194,13 @@ struct gd_sim {
     static constexpr size_t kEvRing = 32;
     // second stream for the partner rows (k_partner_rows beside the road kernels): forked and joined with events, also
     // inside the captured step graph
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Stream side;
+    Event ev_fork, ev_join;
     size_t lin_cap = 0;        // entries of d.lin_list / d.lin_list_dyn
     // learner rows (gd_set_learner_rows): both maps, [W * A] each, and the row count the map kernel returns; d.row_of_slot /
     // d.slot_of_row point at them while rows are set
     int32_t *d_row_of_slot = nullptr, *d_slot_of_row = nullptr, *d_row_count = nullptr;
     int32_t *d_lin_list = nullptr, *d_lin_list_dyn = nullptr;
-    std::vector<std::vector<int32_t>> w_resp;  // response type of every agent slot (who can move at all)
     bool full_pass_next = false;  // the next step's road pass takes every live agent (state was written from outside)
     int64_t lin_static_agents = 0;   // live agents that are not on the step passes' list (response type Static)
     int64_t host_skipped = 0;        // ... counted as left in place once per step pass (gd_stat 30 adds the device's counters)
@@ -152,51 +214,45 @@ struct gd_sim {
     bool ensure_rank_buffers() {
         if (rk_alloc) return true;
         const size_t WA = static_cast<size_t>(W) * A;
-        const size_t first = internal.size();
+        // into local owners and a local copy of the kernels' view: published together when every allocation succeeded
+        std::vector<gd::DevMem> mine;
+        gd::DevSim n = d;
         try {
+            alloc_into(mine, n.rk_E, WA * GD_RANK_CAP + 64);  // the replay prefetches up to 24 entries past a row
+            alloc_into(mine, n.rk_spc, WA * GD_RANK_SPL);
             // developer switch for the test of the path below: the device "runs out of memory" in the middle of the allocations
-            if (std::getenv("GPUDRIVE_RANK_ALLOC_FAIL") != nullptr) {
-                d.rk_E = alloc_internal<uint16_t>(WA * GD_RANK_CAP + 64);
-                d.rk_spc = alloc_internal<uint16_t>(WA * GD_RANK_SPL);
+            if (std::getenv("GPUDRIVE_RANK_ALLOC_FAIL") != nullptr)
                 throw HipError("GPUDRIVE_RANK_ALLOC_FAIL: simulated allocation failure of the rank replay's buffers");
-            }
-            d.rk_E = alloc_internal<uint16_t>(WA * GD_RANK_CAP + 64);  // the replay prefetches up to 24 entries past a row
-            d.rk_spc = alloc_internal<uint16_t>(WA * GD_RANK_SPL);
-            d.rk_kt = alloc_internal<float>(WA * GD_RANK_KT);
-            d.rk_heap = alloc_internal<uint32_t>(WA * GD_RANK_HEAP_DW);
-            d.rk_cpe = alloc_internal<uint16_t>(WA * GD_RANK_NCP);
-            d.rk_n = alloc_internal<int32_t>(WA);
-            d.rk_fallback = alloc_internal<int32_t>(WA / 32);
-            d.rk_streak = alloc_internal<int32_t>(WA / 32);
-            d.cp_road = alloc_internal<uint16_t>(2 * WA * GD_RANK_NCP);
-            d.cp_T = alloc_internal<float>(2 * WA * GD_RANK_NCP);
-            d.cp_hdr = alloc_internal<float4>(2 * WA);
-            d.rk_words = alloc_internal<uint32_t>(WA * GD_RANK_NCH);
-            d.rk_tl = alloc_internal<float>(WA);
-            d.rk_hist = alloc_internal<int32_t>(544);
-            d.rk_ticket = alloc_internal<int32_t>(WA);
-            d.rk_order = alloc_internal<int32_t>(WA);
-            d.rk_list = alloc_internal<int32_t>(8 * WA);
+            alloc_into(mine, n.rk_kt, WA * GD_RANK_KT);
+            alloc_into(mine, n.rk_heap, WA * GD_RANK_HEAP_DW);
+            alloc_into(mine, n.rk_cpe, WA * GD_RANK_NCP);
+            alloc_into(mine, n.rk_n, WA);
+            alloc_into(mine, n.rk_fallback, WA / 32);
+            alloc_into(mine, n.rk_streak, WA / 32);
+            alloc_into(mine, n.cp_road, 2 * WA * GD_RANK_NCP);
+            alloc_into(mine, n.cp_T, 2 * WA * GD_RANK_NCP);
+            alloc_into(mine, n.cp_hdr, 2 * WA);
+            alloc_into(mine, n.rk_words, WA * GD_RANK_NCH);
+            alloc_into(mine, n.rk_tl, WA);
+            alloc_into(mine, n.rk_hist, 544);
+            alloc_into(mine, n.rk_ticket, WA);
+            alloc_into(mine, n.rk_order, WA);
+            alloc_into(mine, n.rk_list, 8 * WA);
             // the long list: room for a quarter of the agent slots (an agent beyond that takes the fallback)
-            d.rk_nlong = static_cast<int>(std::max<size_t>(WA / 4, 64));
-            d.rk_longlist = alloc_internal<int32_t>(d.rk_nlong);
-            d.rk_longslot = alloc_internal<int32_t>(WA);
-            d.rk_E_long = alloc_internal<uint16_t>(static_cast<size_t>(d.rk_nlong) * GD_RANK_CAP_LONG + 64);  // (+ the replay's prefetch)
-            d.rk_kt_long = alloc_internal<float>(static_cast<size_t>(d.rk_nlong) * GD_RANK_KT_LONG);
-        } catch (const HipError &) {
+            n.rk_nlong = static_cast<int>(std::max<size_t>(WA / 4, 64));
+            alloc_into(mine, n.rk_longlist, n.rk_nlong);
+            alloc_into(mine, n.rk_longslot, WA);
+            alloc_into(mine, n.rk_E_long, static_cast<size_t>(n.rk_nlong) * GD_RANK_CAP_LONG + 64);  // (+ the replay's prefetch)
+            alloc_into(mine, n.rk_kt_long, static_cast<size_t>(n.rk_nlong) * GD_RANK_KT_LONG);
+            internal.reserve(internal.size() + mine.size());
+        } catch (const HipError &) {  // `mine` returns what was allocated; d never saw it
             (void)hipGetLastError();
-            for (size_t k = first; k < internal.size(); k++) (void)hipFree(internal[k]);
-            internal.resize(first);
             rk_possible = false;
             d.rk_on = 0;
-            d.rk_nlong = 0;
-            // nothing may point at what was just returned
-            d.rk_E = nullptr; d.rk_spc = nullptr; d.rk_kt = nullptr; d.rk_heap = nullptr; d.rk_cpe = nullptr; d.rk_n = nullptr;
-            d.rk_fallback = nullptr; d.rk_streak = nullptr; d.cp_road = nullptr; d.cp_T = nullptr; d.cp_hdr = nullptr;
-            d.rk_words = nullptr; d.rk_tl = nullptr; d.rk_hist = nullptr; d.rk_ticket = nullptr; d.rk_order = nullptr;
-            d.rk_list = nullptr; d.rk_longlist = nullptr; d.rk_longslot = nullptr; d.rk_E_long = nullptr; d.rk_kt_long = nullptr;
             return false;
         }
+        for (gd::DevMem &m : mine) internal.push_back(std::move(m));
+        d = n;
         rk_alloc = true;
         return true;
     }
@@ -207,49 +263,31 @@ struct gd_sim {
     double ev_ms[gd::KERNEL_TIMED] = {};
     int64_t ev_launches[gd::KERNEL_TIMED] = {};
 
-    ~gd_sim() {
+    ~gd_sim() {  // what is about order: nothing returns itself while the device still works, and the graph goes first
         (void)hipDeviceSynchronize();
         if (step_graph) (void)hipGraphExecDestroy(step_graph);
-        if (side) (void)hipStreamDestroy(side);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        for (int i = 0; i < GD_T_COUNT; i++)
-            if (owned[i] && exported[i]) (void)hipFree(exported[i]);
-        for (void *p : internal) (void)hipFree(p);
-        if (d_road_xy) (void)hipFree(d_road_xy);
-        if (d_road_aux) (void)hipFree(d_road_aux);
-        if (d_road_rec) (void)hipFree(d_road_rec);
-        if (d_boxes) (void)hipFree(d_boxes);
-        if (d_road_blk) (void)hipFree(d_road_blk);
-        if (d_cell_off) (void)hipFree(d_cell_off);
-        if (d_cell_items) (void)hipFree(d_cell_items);
-        if (d_cell_hdr) (void)hipFree(d_cell_hdr);
-        if (d_rcell_off) (void)hipFree(d_rcell_off);
-        if (d_rcell_items) (void)hipFree(d_rcell_items);
-        if (d_rcell_xy) (void)hipFree(d_rcell_xy);
-        if (d_rcell_pos) (void)hipFree(d_rcell_pos);
-        for (int i = 0; i < kRing; i++) {
-            if (h_flags[i]) (void)hipHostFree(h_flags[i]);
-            if (flag_ev[i]) (void)hipEventDestroy(flag_ev[i]);
-        }
-        for (auto &pool : ev_pool)
-            for (auto &e : pool) { (void)hipEventDestroy(e.start); (void)hipEventDestroy(e.stop); }
     }
 
+    // a zero-filled array of `count` T (at least 16 bytes), owned by `into`
+    template <typename T>
+    static void alloc_into(std::vector<gd::DevMem> &into, T *&field, size_t count) {
+        const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+        into.emplace_back(bytes);  // owned from here on: a failing memset must not leak it
+        HIP_CHECK(hipMemset(into.back().get(), 0, bytes));
+        field = static_cast<T *>(into.back().get());
+    }
     template <typename T>
     T *alloc_internal(size_t count) {
-        void *p = nullptr;
-        HIP_CHECK(hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)));
-        internal.push_back(p);  // owned from here on: a failing memset must not leak it
-        HIP_CHECK(hipMemset(p, 0, std::max<size_t>(count * sizeof(T), 16)));
-        return static_cast<T *>(p);
+        T *p = nullptr;
+        alloc_into(internal, p, count);
+        return p;
     }
 
     void collect_timing(int k, size_t keep = 0) {  // read the oldest pairs until `keep` are left
         while (ev_used[k] > keep) {
             const EventPair &e = ev_pool[k][ev_head[k]];
             float ms = 0.f;
-            if (hipEventSynchronize(e.stop) == hipSuccess && hipEventElapsedTime(&ms, e.start, e.stop) == hipSuccess) {
+            if (hipEventSynchronize(e.stop.get()) == hipSuccess && hipEventElapsedTime(&ms, e.start.get(), e.stop.get()) == hipSuccess) {
                 ev_ms[k] += ms;
                 ev_launches[k]++;
             }
@@ -261,18 +299,18 @@ struct gd_sim {
     void launch(int which, bool move, hipStream_t stream_override = nullptr) {
         hipStream_t stream = stream_override ? stream_override : this->stream;
         const bool timed = timing && which < gd::KERNEL_TIMED && !d.gate_any;  // gated reset passes are mostly empty launches
-        EventPair ep{};
+        const EventPair *ep = nullptr;
         if (timed) {
             // ring full: read the older half (those launches finished long ago; the host stays well ahead of the GPU)
             if (ev_used[which] == ev_pool[which].size()) collect_timing(which, ev_pool[which].size() / 2);
-            ep = ev_pool[which][(ev_head[which] + ev_used[which]) % ev_pool[which].size()];
+            ep = &ev_pool[which][(ev_head[which] + ev_used[which]) % ev_pool[which].size()];
             ev_used[which]++;
-            HIP_CHECK(hipEventRecord(ep.start, stream));
+            HIP_CHECK(hipEventRecord(ep->start.get(), stream));
         }
         if (which == gd::KERNEL_BEV) gd::launch_bev(d, stream);
         else if (which == gd::KERNEL_LIDAR) gd::launch_lidar(d, stream);
         else gd::launch_kernel(d, stream, which, move);
-        if (timed) HIP_CHECK(hipEventRecord(ep.stop, stream));
+        if (timed) HIP_CHECK(hipEventRecord(ep->stop.get(), stream));
         HIP_CHECK(hipGetLastError());
     }
 
@@ -373,10 +411,10 @@ struct gd_sim {
         // waits for it at the join.
         const bool fork = d.split_partner && !params.disableClassicalObs;
         if (fork) {
-            HIP_CHECK(hipEventRecord(ev_fork, stream));
-            HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
-            launch(gd::KERNEL_PARTNER, move, side);
-            HIP_CHECK(hipEventRecord(ev_join, side));
+            HIP_CHECK(hipEventRecord(ev_fork.get(), stream));
+            HIP_CHECK(hipStreamWaitEvent(side.get(), ev_fork.get(), 0));
+            launch(gd::KERNEL_PARTNER, move, side.get());
+            HIP_CHECK(hipEventRecord(ev_join.get(), side.get()));
         }
         if (!params.disableClassicalObs) launch(gd::KERNEL_MAP_OBS, move);
         if (!params.disableClassicalObs && d.bev) {  // collectBevObservationsSystem, src/sim.cpp:879-884 (opt-in)
@@ -385,16 +423,16 @@ struct gd_sim {
         if (params.enableLidar) {  // lidarSystem, src/sim.cpp:895-913
             launch(gd::KERNEL_LIDAR, move);
         }
-        if (fork) HIP_CHECK(hipStreamWaitEvent(stream, ev_join, 0));
+        if (fork) HIP_CHECK(hipStreamWaitEvent(stream, ev_join.get(), 0));
     }
 
     void upload_flags(int32_t *dst, const std::vector<int32_t> &flags) {
         const int slot = ring_pos;
         ring_pos = (ring_pos + 1) % kRing;
-        HIP_CHECK(hipEventSynchronize(flag_ev[slot]));
-        std::memcpy(h_flags[slot], flags.data(), sizeof(int32_t) * W);
-        HIP_CHECK(hipMemcpyAsync(dst, h_flags[slot], sizeof(int32_t) * W, hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipEventRecord(flag_ev[slot], stream));
+        HIP_CHECK(hipEventSynchronize(flag_ev[slot].get()));
+        std::memcpy(h_flags[slot].get(), flags.data(), sizeof(int32_t) * W);
+        HIP_CHECK(hipMemcpyAsync(dst, h_flags[slot].get(), sizeof(int32_t) * W, hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipEventRecord(flag_ev[slot].get(), stream));
     }
 
     // (Re)build the listed worlds on the host and upload their init-time rows:
@@ -527,56 +565,42 @@ struct gd_sim {
             st.scenario_id.insert(st.scenario_id.end(), hw->scenario_id, hw->scenario_id + 32);
             st.shape.push_back(hw->num_agents);
             st.shape.push_back(hw->num_roads);
-            w_xy[w] = hw->road_xy;
-            w_agents[w] = hw->num_agents;
-            w_resp[w] = hw->resp;
-            w_aux[w] = hw->road_aux;
-            w_boxes[w] = hw->boxes;
-            w_grid[w] = gd::GridHdr{hw->grid_ox, hw->grid_oy, 1.f / hw->grid_cell, hw->grid_nx, hw->grid_ny, 0, 0, 0};
-            w_cell_off[w] = hw->cell_off;
-            w_cell_items[w] = hw->cell_items;
-            build_road_grid(w);
+            WorldHost &host = world_host[w];
+            host.xy = hw->road_xy;
+            host.agents = hw->num_agents;
+            host.resp = hw->resp;
+            host.aux = hw->road_aux;
+            host.boxes = hw->boxes;
+            host.grid = gd::GridHdr{hw->grid_ox, hw->grid_oy, 1.f / hw->grid_cell, hw->grid_nx, hw->grid_ny, 0, 0, 0};
+            host.cell_off = hw->cell_off;
+            host.cell_items = hw->cell_items;
+            build_road_grid(host);
             rebuilt[w] = 1;
         }
         flush(run_start, run_len);
         // repack the road CSR
+        std::vector<WorldHost> &wh = world_host;
         std::vector<int32_t> road_off(W + 1, 0), box_off(W + 1, 0);
         for (int w = 0; w < W; w++) {
-            road_off[w + 1] = road_off[w] + static_cast<int32_t>(w_xy[w].size() / 2);
-            box_off[w + 1] = box_off[w] + static_cast<int32_t>(w_boxes[w].size());
+            road_off[w + 1] = road_off[w] + static_cast<int32_t>(wh[w].xy.size() / 2);
+            box_off[w + 1] = box_off[w] + static_cast<int32_t>(wh[w].boxes.size());
         }
         const size_t nroad = road_off[W], nbox = box_off[W];
-        // k_map_obs requests chunks of 32 roads up to 256 roads past a world's last one, and the fused set-order write-out
-        // reads road_rec[first road of the world] even for a world without roads: the arrays always end in 320 readable
-        // pad entries (also when a rebuild fits the old capacity, and when no world has a road)
-        if (nroad + 320 > road_cap || !d_road_xy) {
-            if (d_road_xy) (void)hipFree(d_road_xy);
-            if (d_road_aux) (void)hipFree(d_road_aux);
-            if (d_road_rec) (void)hipFree(d_road_rec);
-            road_cap = nroad + nroad / 8 + 640;
-            HIP_CHECK(hipMalloc(&d_road_xy, road_cap * sizeof(float) * 2));
-            HIP_CHECK(hipMalloc(&d_road_aux, road_cap * sizeof(float) * 8));
-            HIP_CHECK(hipMalloc(&d_road_rec, road_cap * sizeof(float) * 8));
-            HIP_CHECK(hipMemset(d_road_xy, 0, road_cap * sizeof(float) * 2));
-            HIP_CHECK(hipMemset(d_road_aux, 0, road_cap * sizeof(float) * 8));
-            HIP_CHECK(hipMemset(d_road_rec, 0, road_cap * sizeof(float) * 8));
-        }
-        if (nbox > box_cap) {
-            if (d_boxes) (void)hipFree(d_boxes);
-            box_cap = nbox + nbox / 8 + 64;
-            HIP_CHECK(hipMalloc(&d_boxes, box_cap * sizeof(gd::RoadBox)));
-        }
+        if (road_xy.fit(nroad, d.road_xy)) HIP_CHECK(hipMemset(road_xy.mem.get(), 0, road_xy.mem.bytes()));
+        if (road_aux.fit(nroad, d.road_aux)) HIP_CHECK(hipMemset(road_aux.mem.get(), 0, road_aux.mem.bytes()));
+        if (road_rec.fit(nroad, d.road_rec)) HIP_CHECK(hipMemset(road_rec.mem.get(), 0, road_rec.mem.bytes()));
+        boxes.fit(nbox, d.boxes);
         {
             std::vector<float> xy(nroad * 2), aux(nroad * 8);
-            std::vector<gd::RoadBox> boxes(nbox);
+            std::vector<gd::RoadBox> bx(nbox);
             for (int w = 0; w < W; w++) {
-                std::copy(w_xy[w].begin(), w_xy[w].end(), xy.begin() + static_cast<size_t>(road_off[w]) * 2);
-                std::copy(w_aux[w].begin(), w_aux[w].end(), aux.begin() + static_cast<size_t>(road_off[w]) * 8);
-                std::copy(w_boxes[w].begin(), w_boxes[w].end(), boxes.begin() + box_off[w]);
+                std::copy(wh[w].xy.begin(), wh[w].xy.end(), xy.begin() + static_cast<size_t>(road_off[w]) * 2);
+                std::copy(wh[w].aux.begin(), wh[w].aux.end(), aux.begin() + static_cast<size_t>(road_off[w]) * 8);
+                std::copy(wh[w].boxes.begin(), wh[w].boxes.end(), bx.begin() + box_off[w]);
             }
             if (nroad) {
-                HIP_CHECK(hipMemcpy(d_road_xy, xy.data(), xy.size() * sizeof(float), hipMemcpyHostToDevice));
-                HIP_CHECK(hipMemcpy(d_road_aux, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice));
+                road_xy.upload(xy.data(), nroad);
+                road_aux.upload(aux.data(), nroad);
                 // the row kernel's 32-byte record: aux is (qw, qz, d0, d1, d2, type, id, mapType); d2 is a function of the
                 // type (validated while staging), which the kernel restores
                 std::vector<float> rec(nroad * 8);
@@ -589,59 +613,49 @@ struct gd_sim {
                     const float row[8] = {xy[r * 2], xy[r * 2 + 1], a[0], a[1], a[2], a[3], a[6], fb};
                     std::copy(row, row + 8, rec.begin() + r * 8);
                 }
-                HIP_CHECK(hipMemcpy(d_road_rec, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+                road_rec.upload(rec.data(), nroad);
             }
             HIP_CHECK(hipMemsetAsync(d.sel_hdr, 0xff, sizeof(float4) * 2 * static_cast<size_t>(W) * d.A, stream));  // count -1: nothing selected yet (ordered before the kernels of this stream)
-            if (nbox) HIP_CHECK(hipMemcpy(d_boxes, boxes.data(), nbox * sizeof(gd::RoadBox), hipMemcpyHostToDevice));
+            boxes.upload(bx.data(), nbox);
         }
         {
             size_t ncell = 0, nitem = 0;
+            std::vector<gd::GridHdr> hdr(W);
             for (int w = 0; w < W; w++) {
-                w_grid[w].cell_base = static_cast<int>(ncell);
-                w_grid[w].item_base = static_cast<int>(nitem);
-                ncell += w_cell_off[w].size();
-                nitem += w_cell_items[w].size();
+                wh[w].grid.cell_base = static_cast<int>(ncell);
+                wh[w].grid.item_base = static_cast<int>(nitem);
+                hdr[w] = wh[w].grid;
+                ncell += wh[w].cell_off.size();
+                nitem += wh[w].cell_items.size();
             }
-            if (ncell > cell_cap) {
-                if (d_cell_off) (void)hipFree(d_cell_off);
-                cell_cap = ncell + ncell / 8 + 64;
-                HIP_CHECK(hipMalloc(&d_cell_off, cell_cap * sizeof(int32_t)));
-            }
-            if (nitem > item_cap) {
-                if (d_cell_items) (void)hipFree(d_cell_items);
-                if (d_cell_hdr) (void)hipFree(d_cell_hdr);
-                item_cap = nitem + nitem / 8 + 64;
-                HIP_CHECK(hipMalloc(&d_cell_items, item_cap * sizeof(int32_t)));
-                HIP_CHECK(hipMalloc(&d_cell_hdr, item_cap * sizeof(float) * 4));
-            }
+            cell_off.fit(ncell, d.cell_off);
+            cell_items.fit(nitem, d.cell_items);
+            cell_hdr.fit(nitem, d.cell_hdr);
             std::vector<int32_t> co(ncell), ci(nitem);
             for (int w = 0; w < W; w++) {
-                std::copy(w_cell_off[w].begin(), w_cell_off[w].end(), co.begin() + w_grid[w].cell_base);
-                std::copy(w_cell_items[w].begin(), w_cell_items[w].end(), ci.begin() + w_grid[w].item_base);
+                std::copy(wh[w].cell_off.begin(), wh[w].cell_off.end(), co.begin() + hdr[w].cell_base);
+                std::copy(wh[w].cell_items.begin(), wh[w].cell_items.end(), ci.begin() + hdr[w].item_base);
             }
-            if (ncell) HIP_CHECK(hipMemcpy(d_cell_off, co.data(), ncell * sizeof(int32_t), hipMemcpyHostToDevice));
-            if (nitem) HIP_CHECK(hipMemcpy(d_cell_items, ci.data(), nitem * sizeof(int32_t), hipMemcpyHostToDevice));
+            cell_off.upload(co.data(), ncell);
+            cell_items.upload(ci.data(), nitem);
             {
                 std::vector<float> ch(nitem * 4);
                 for (int w = 0; w < W; w++) {
-                    const std::vector<int32_t> &items = w_cell_items[w];
+                    const std::vector<int32_t> &items = wh[w].cell_items;
                     for (size_t i = 0; i < items.size(); i++) {
-                        const gd::RoadBox &b = w_boxes[w][items[i]];
-                        float *o = &ch[(static_cast<size_t>(w_grid[w].item_base) + i) * 4];
+                        const gd::RoadBox &b = wh[w].boxes[items[i]];
+                        float *o = &ch[(static_cast<size_t>(hdr[w].item_base) + i) * 4];
                         // (centre, bounding radius, entity type | local box index << 8): what the cull needs and where the box is
                         const uint32_t packed = (static_cast<uint32_t>(static_cast<int>(b.type)) & 0xffu) | (static_cast<uint32_t>(items[i]) << 8);
                         o[0] = b.cx; o[1] = b.cy; o[2] = b.radius;
                         std::memcpy(&o[3], &packed, sizeof(packed));
                     }
                 }
-                if (nitem) HIP_CHECK(hipMemcpy(d_cell_hdr, ch.data(), ch.size() * sizeof(float), hipMemcpyHostToDevice));
+                cell_hdr.upload(ch.data(), nitem);
             }
-            HIP_CHECK(hipMemcpy(const_cast<gd::GridHdr *>(d.grid), w_grid.data(), sizeof(gd::GridHdr) * W, hipMemcpyHostToDevice));
-            d.cell_off = static_cast<const int32_t *>(d_cell_off);
-            d.cell_items = static_cast<const int32_t *>(d_cell_items);
-            d.cell_hdr = static_cast<const float4 *>(d_cell_hdr);
+            HIP_CHECK(hipMemcpy(d_grid, hdr.data(), sizeof(gd::GridHdr) * W, hipMemcpyHostToDevice));
         }
-        HIP_CHECK(hipMemcpy(const_cast<int32_t *>(d.road_off), road_off.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_road_off, road_off.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
         upload_road_grids();
         {
             // longest-first launch order of the road kernel: its time per world grows with the road count (the kernel
@@ -658,11 +672,7 @@ struct gd_sim {
             HIP_CHECK(hipMemcpy(d.wave_order, waves.data(), sizeof(int32_t) * waves.size(), hipMemcpyHostToDevice));
             HIP_CHECK(hipMemsetAsync(d.wave_cost, 0, sizeof(uint32_t) * waves.size(), stream));
         }
-        HIP_CHECK(hipMemcpy(const_cast<int32_t *>(d.box_off), box_off.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
-        d.road_xy = static_cast<const float2 *>(d_road_xy);
-        d.road_aux = static_cast<const float4 *>(d_road_aux);
-        d.road_rec = static_cast<const float4 *>(d_road_rec);
-        d.boxes = static_cast<const float4 *>(d_boxes);
+        HIP_CHECK(hipMemcpy(d_box_off, box_off.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(d.rebuilt_flags, rebuilt.data(), sizeof(int32_t) * W, hipMemcpyHostToDevice));
         choose_set_schedule();
         {
@@ -671,25 +681,28 @@ struct gd_sim {
             std::vector<float> bb(static_cast<size_t>(W) * 4);
             for (int w = 0; w < W; w++) {
                 float lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
-                for (size_t r = 0; r * 2 < w_xy[w].size(); r++) {
-                    lo_x = std::min(lo_x, w_xy[w][2 * r]); hi_x = std::max(hi_x, w_xy[w][2 * r]);
-                    lo_y = std::min(lo_y, w_xy[w][2 * r + 1]); hi_y = std::max(hi_y, w_xy[w][2 * r + 1]);
+                const std::vector<float> &xy = wh[w].xy;
+                for (size_t r = 0; r * 2 < xy.size(); r++) {
+                    lo_x = std::min(lo_x, xy[2 * r]); hi_x = std::max(hi_x, xy[2 * r]);
+                    lo_y = std::min(lo_y, xy[2 * r + 1]); hi_y = std::max(hi_y, xy[2 * r + 1]);
                 }
                 bb[w * 4 + 0] = lo_x; bb[w * 4 + 1] = lo_y; bb[w * 4 + 2] = hi_x; bb[w * 4 + 3] = hi_y;
             }
-            HIP_CHECK(hipMemcpy(const_cast<float4 *>(d.road_bbox), bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(d_road_bbox, bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
             std::vector<float> rbmax(W, 0.f);  // (road_aux: qw qz d0 d1 | d2 type id mapType)
-            for (int w = 0; w < W; w++)
-                for (size_t r = 0; r * 8 < w_aux[w].size(); r++)
-                    rbmax[w] = std::max(rbmax[w], std::sqrt(w_aux[w][r * 8 + 2] * w_aux[w][r * 8 + 2] + w_aux[w][r * 8 + 3] * w_aux[w][r * 8 + 3]));
-            HIP_CHECK(hipMemcpy(const_cast<float *>(d.road_rbmax), rbmax.data(), rbmax.size() * sizeof(float), hipMemcpyHostToDevice));
+            for (int w = 0; w < W; w++) {
+                const std::vector<float> &aux = wh[w].aux;
+                for (size_t r = 0; r * 8 < aux.size(); r++)
+                    rbmax[w] = std::max(rbmax[w], std::sqrt(aux[r * 8 + 2] * aux[r * 8 + 2] + aux[r * 8 + 3] * aux[r * 8 + 3]));
+            }
+            HIP_CHECK(hipMemcpy(d_road_rbmax, rbmax.data(), rbmax.size() * sizeof(float), hipMemcpyHostToDevice));
             // the circle around every GD_LIN_BLK consecutive road points of a world (centre of their bounding box, the largest
             // distance from it to one of them, rounded up)
             std::vector<int32_t> boff(W + 1, 0);
-            for (int w = 0; w < W; w++) boff[w + 1] = boff[w] + static_cast<int32_t>((w_xy[w].size() / 2 + GD_LIN_BLK - 1) / GD_LIN_BLK);
+            for (int w = 0; w < W; w++) boff[w + 1] = boff[w] + static_cast<int32_t>((wh[w].xy.size() / 2 + GD_LIN_BLK - 1) / GD_LIN_BLK);
             std::vector<float> blk(static_cast<size_t>(boff[W]) * 4 + 4, 0.f);
             for (int w = 0; w < W; w++) {
-                const std::vector<float> &xy = w_xy[w];
+                const std::vector<float> &xy = wh[w].xy;
                 const size_t nr = xy.size() / 2;
                 for (size_t b = 0; b * GD_LIN_BLK < nr; b++) {
                     const size_t r_lo = b * GD_LIN_BLK, r_hi = std::min(nr, r_lo + GD_LIN_BLK);
@@ -706,14 +719,9 @@ struct gd_sim {
                     o[0] = cx; o[1] = cy; o[2] = rad * 1.0001f + 1e-3f; o[3] = 0.f;
                 }
             }
-            if (blk.size() / 4 > blk_cap || !d_road_blk) {
-                if (d_road_blk) (void)hipFree(d_road_blk);
-                blk_cap = blk.size() / 4 + blk.size() / 32 + 64;
-                HIP_CHECK(hipMalloc(&d_road_blk, blk_cap * sizeof(float) * 4));
-            }
-            HIP_CHECK(hipMemcpy(d_road_blk, blk.data(), blk.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(const_cast<int32_t *>(d.blk_off), boff.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
-            d.road_blk = static_cast<const float4 *>(d_road_blk);
+            road_blk.fit(blk.size() / 4, d.road_blk);  // (never empty: one spare circle behind the last world's)
+            road_blk.upload(blk.data(), blk.size() / 4);
+            HIP_CHECK(hipMemcpy(d_blk_off, boff.data(), sizeof(int32_t) * (W + 1), hipMemcpyHostToDevice));
             // no row written before this call describes the worlds as they are now (roads, agent slots): every pose stamp dies
             HIP_CHECK(hipMemsetAsync(d.pose_stamp, 0xff, sizeof(uint4) * static_cast<size_t>(W) * A, stream));
             HIP_CHECK(hipMemsetAsync(d.bev_dirty, 1, sizeof(int32_t) * static_cast<size_t>(W) * A, stream));
@@ -728,7 +736,7 @@ struct gd_sim {
             // world with at least K roads from one full generation of k_map_obs workgroups on.  GPUDRIVE_RANK_MIN_ROADS
             // pins the threshold.
             int groups = 0;
-            for (int w = 0; w < W; w++) groups += (w_agents[w] + 31) / 32;
+            for (int w = 0; w < W; w++) groups += (wh[w].agents + 31) / 32;
             const char *pin = std::getenv("GPUDRIVE_RANK_MIN_ROADS");
             d.rk_min_roads = pin ? std::atoi(pin) : (groups >= 4 * cu_count ? GD_MAP_OBS_K : 1536);
             // Worlds of every size take it since round 4 (agents whose candidates overflow the standard ranking's 1272 go to the
@@ -750,7 +758,7 @@ struct gd_sim {
             live.reserve(static_cast<size_t>(W) * A);
             for (int a = 0; a < A; a++)  // agent-major: consecutive workgroups belong to different worlds
                 for (int w = 0; w < W; w++)
-                    if (a < w_agents[w]) live.push_back(w * A + a);
+                    if (a < wh[w].agents) live.push_back(w * A + a);
             d.live_count = static_cast<int>(live.size());
             if (!live.empty()) HIP_CHECK(hipMemcpy(d.live_list, live.data(), sizeof(int32_t) * live.size(), hipMemcpyHostToDevice));
             // likewise the set-order road kernel's workgroups (4 waves x set_apw agents each)
@@ -758,7 +766,7 @@ struct gd_sim {
             const int per = 4 * d.set_apw;
             for (int g = 0; g * per < A; g++)  // group-major: consecutive workgroups belong to different worlds
                 for (int w = 0; w < W; w++)
-                    if (g * per < w_agents[w]) groups.push_back(w << 8 | g);
+                    if (g * per < wh[w].agents) groups.push_back(w << 8 | g);
             d.set_group_count = static_cast<int>(groups.size());
             if (!groups.empty()) HIP_CHECK(hipMemcpy(d.set_groups, groups.data(), sizeof(int32_t) * groups.size(), hipMemcpyHostToDevice));
         }
@@ -777,8 +785,8 @@ struct gd_sim {
                 std::vector<int32_t> seq[8];
                 for (int w = 0; w < W; w++) {
                     std::vector<int32_t> mine;
-                    for (int a = 0; a < w_agents[w]; a++)
-                        if (!dyn_only || w_resp[w][a] != gd::RESP_Static) mine.push_back(w << 8 | a);
+                    for (int a = 0; a < wh[w].agents; a++)
+                        if (!dyn_only || wh[w].resp[a] != gd::RESP_Static) mine.push_back(w << 8 | a);
                     if (mine.empty()) continue;
                     int c = w % 8;
                     for (int k = 0; k < 8; k++)
@@ -856,8 +864,8 @@ struct gd_sim {
 
     // Uniform grid over the (x, y) of ALL roads of world w: cells of at least 16 m, at most 64 x 64 of them; a road
     // belongs to the cell its point falls into, and a cell lists its roads in ascending index.
-    void build_road_grid(int w) {
-        const std::vector<float> &xy = w_xy[w];
+    static void build_road_grid(WorldHost &world) {
+        const std::vector<float> &xy = world.xy;
         const size_t n = xy.size() / 2;
         gd::GridHdr g{0.f, 0.f, 1.f, 1, 1, 0, 0, 0};
         std::vector<int32_t> off(2, 0);
@@ -885,56 +893,45 @@ struct gd_sim {
             std::vector<int32_t> fill(off.begin(), off.end() - 1);
             for (size_t r = 0; r < n; r++) items[fill[cell_of[r]]++] = static_cast<uint16_t>(r);  // ascending r within a cell
         }
-        w_rgrid[w] = g;
-        w_rcell_off[w] = std::move(off);
-        w_rcell_items[w] = std::move(items);
+        world.rgrid = g;
+        world.rcell_off = std::move(off);
+        world.rcell_items = std::move(items);
     }
 
     void upload_road_grids() {
         size_t ncell = 0, nitem = 0;
+        std::vector<gd::GridHdr> hdr(W);
         for (int w = 0; w < W; w++) {
-            w_rgrid[w].cell_base = static_cast<int>(ncell);
-            w_rgrid[w].item_base = static_cast<int>(nitem);
-            ncell += w_rcell_off[w].size();
-            nitem += w_rcell_items[w].size();
+            world_host[w].rgrid.cell_base = static_cast<int>(ncell);
+            world_host[w].rgrid.item_base = static_cast<int>(nitem);
+            hdr[w] = world_host[w].rgrid;
+            ncell += world_host[w].rcell_off.size();
+            nitem += world_host[w].rcell_items.size();
         }
-        if (ncell > rcell_cap) {
-            if (d_rcell_off) (void)hipFree(d_rcell_off);
-            rcell_cap = ncell + ncell / 8 + 64;
-            HIP_CHECK(hipMalloc(&d_rcell_off, rcell_cap * sizeof(int32_t)));
-        }
-        if (nitem + 64 > ritem_cap) {
-            if (d_rcell_items) (void)hipFree(d_rcell_items);
-            if (d_rcell_xy) (void)hipFree(d_rcell_xy);
-            if (d_rcell_pos) (void)hipFree(d_rcell_pos);
-            ritem_cap = nitem + nitem / 8 + 128;
-            HIP_CHECK(hipMalloc(&d_rcell_items, ritem_cap * sizeof(uint16_t)));
-            HIP_CHECK(hipMalloc(&d_rcell_xy, ritem_cap * sizeof(float) * 2));
-            HIP_CHECK(hipMalloc(&d_rcell_pos, ritem_cap * sizeof(uint16_t)));
-        }
+        rcell_off.fit(ncell, d.rcell_off);
+        rcell_items.fit(nitem, d.rcell_items);
+        rcell_xy.fit(nitem, d.rcell_xy);
+        rcell_pos.fit(nitem, d.rcell_pos);
         std::vector<int32_t> co(ncell);
         std::vector<uint16_t> ci(nitem);
         std::vector<float> cxy(nitem * 2);
         std::vector<uint16_t> cpos(nitem);  // (a world's items are its roads, one each: item_base is also its first road)
         for (int w = 0; w < W; w++) {
-            std::copy(w_rcell_off[w].begin(), w_rcell_off[w].end(), co.begin() + w_rgrid[w].cell_base);
-            std::copy(w_rcell_items[w].begin(), w_rcell_items[w].end(), ci.begin() + w_rgrid[w].item_base);
-            for (size_t k = 0; k < w_rcell_items[w].size(); k++) {
-                const size_t r = w_rcell_items[w][k], o = (static_cast<size_t>(w_rgrid[w].item_base) + k) * 2;
-                cxy[o] = w_xy[w][2 * r];
-                cxy[o + 1] = w_xy[w][2 * r + 1];
-                cpos[static_cast<size_t>(w_rgrid[w].item_base) + r] = static_cast<uint16_t>(k);
+            const WorldHost &x = world_host[w];
+            std::copy(x.rcell_off.begin(), x.rcell_off.end(), co.begin() + hdr[w].cell_base);
+            std::copy(x.rcell_items.begin(), x.rcell_items.end(), ci.begin() + hdr[w].item_base);
+            for (size_t k = 0; k < x.rcell_items.size(); k++) {
+                const size_t r = x.rcell_items[k], o = (static_cast<size_t>(hdr[w].item_base) + k) * 2;
+                cxy[o] = x.xy[2 * r];
+                cxy[o + 1] = x.xy[2 * r + 1];
+                cpos[static_cast<size_t>(hdr[w].item_base) + r] = static_cast<uint16_t>(k);
             }
         }
-        if (ncell) HIP_CHECK(hipMemcpy(d_rcell_off, co.data(), ncell * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (nitem) HIP_CHECK(hipMemcpy(d_rcell_items, ci.data(), nitem * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (nitem) HIP_CHECK(hipMemcpy(d_rcell_xy, cxy.data(), nitem * 2 * sizeof(float), hipMemcpyHostToDevice));
-        if (nitem) HIP_CHECK(hipMemcpy(d_rcell_pos, cpos.data(), nitem * sizeof(uint16_t), hipMemcpyHostToDevice));
-        d.rcell_xy = static_cast<const float2 *>(d_rcell_xy);
-        d.rcell_pos = static_cast<const uint16_t *>(d_rcell_pos);
-        HIP_CHECK(hipMemcpy(const_cast<gd::GridHdr *>(d.rgrid), w_rgrid.data(), sizeof(gd::GridHdr) * W, hipMemcpyHostToDevice));
-        d.rcell_off = static_cast<const int32_t *>(d_rcell_off);
-        d.rcell_items = static_cast<const uint16_t *>(d_rcell_items);
+        rcell_off.upload(co.data(), ncell);
+        rcell_items.upload(ci.data(), nitem);
+        rcell_xy.upload(cxy.data(), nitem);
+        rcell_pos.upload(cpos.data(), nitem);
+        HIP_CHECK(hipMemcpy(d_rgrid, hdr.data(), sizeof(gd::GridHdr) * W, hipMemcpyHostToDevice));
         // the roads changed: no previous selection bounds the next one
         std::vector<float> prev(static_cast<size_t>(W) * A * 4, 0.f);
         for (size_t i = 0; i < static_cast<size_t>(W) * A; i++) prev[i * 4 + 2] = INFINITY;
@@ -1047,25 +1044,12 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
             s->scenes.emplace_back(scenes[w]);
         }
         s->deleted.assign(static_cast<size_t>(W) * A, -1);  // src/sim.cpp:1003-1006
-        s->w_xy.resize(W);
-        s->w_agents.assign(W, 0);
-        s->w_aux.resize(W);
-        s->w_boxes.resize(W);
-        s->w_grid.resize(W);
-        s->w_cell_off.resize(W);
-        s->w_cell_items.resize(W);
-        s->w_rgrid.resize(W);
-        s->w_rcell_off.resize(W);
-        s->w_rcell_items.resize(W);
+        s->world_host.resize(W);
         for (int id = 0; id < GD_T_COUNT; id++) {
             if (id == GD_T_BEV && !cfg->alloc_bev && !cfg->external[id]) continue;
             const int64_t bytes = spec_bytes(tensor_spec(id, W, A));
-            if (cfg->external[id]) {
-                s->exported[id] = cfg->external[id];
-            } else {
-                HIP_CHECK(hipMalloc(&s->exported[id], bytes));
-                s->owned[id] = true;
-            }
+            if (!cfg->external[id]) s->exported_mem[id] = gd::DevMem(bytes);
+            s->exported[id] = cfg->external[id] ? cfg->external[id] : s->exported_mem[id].get();
             HIP_CHECK(hipMemset(s->exported[id], 0, bytes));
         }
         gd::DevSim &d = s->d;
@@ -1075,9 +1059,11 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         d.knn_order = cfg->knn_order;
         // (not on the legacy null stream: it synchronises with every blocking stream and cannot be captured)
         d.split_partner = (s->stream != nullptr && std::getenv("GPUDRIVE_SPLIT_PARTNER") != nullptr) ? 1 : 0;
-        HIP_CHECK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+        hipStream_t side = nullptr;
+        HIP_CHECK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+        s->side.reset(side);
+        s->ev_fork = make_event(hipEventDisableTiming);
+        s->ev_join = make_event(hipEventDisableTiming);
         d.step_dbg = 0;
 #ifdef GD_DIAG
         if (const char *e = std::getenv("GPUDRIVE_STEP_DBG")) d.step_dbg = std::atoi(e);
@@ -1134,19 +1120,19 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         d.rebuilt_flags = s->alloc_internal<int32_t>(W);
         d.any_reset = s->alloc_internal<int32_t>(1);
         d.gate_any = 0;
-        d.road_off = s->alloc_internal<int32_t>(W + 1);
+        d.road_off = s->d_road_off = s->alloc_internal<int32_t>(W + 1);
         d.live_list = s->alloc_internal<int32_t>(WA);
         d.live_count = 0;
         d.set_groups = s->alloc_internal<int32_t>(WA);
         d.set_group_count = 0;
         d.wave_order = s->alloc_internal<int32_t>(static_cast<size_t>(W) * (A / GD_MAP_OBS_AW));
         d.wave_cost = s->alloc_internal<uint32_t>(static_cast<size_t>(W) * (A / GD_MAP_OBS_AW));
-        d.box_off = s->alloc_internal<int32_t>(W + 1);
-        d.grid = s->alloc_internal<gd::GridHdr>(W);
-        d.rgrid = s->alloc_internal<gd::GridHdr>(W);
+        d.box_off = s->d_box_off = s->alloc_internal<int32_t>(W + 1);
+        d.grid = s->d_grid = s->alloc_internal<gd::GridHdr>(W);
+        d.rgrid = s->d_rgrid = s->alloc_internal<gd::GridHdr>(W);
         d.knn_prev = s->alloc_internal<float4>(WA);
-        d.road_bbox = s->alloc_internal<float4>(W);
-        d.road_rbmax = s->alloc_internal<float>(W);
+        d.road_bbox = s->d_road_bbox = s->alloc_internal<float4>(W);
+        d.road_rbmax = s->d_road_rbmax = s->alloc_internal<float>(W);
         d.bev_dirty = s->alloc_internal<int32_t>(WA);
         d.bev_list = s->alloc_internal<int32_t>(WA);
         d.bev_count = s->alloc_internal<int32_t>(2);
@@ -1164,7 +1150,6 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         s->d_lin_list_dyn = s->alloc_internal<int32_t>(s->lin_cap);
         d.lin_list = s->d_lin_list; d.lin_list_dyn = s->d_lin_list_dyn;
         d.lin_blocks = 0; d.lin_blocks_dyn = 0; d.lin_dyn_off = 0;
-        s->w_resp.resize(W);
         d.lin_on = std::getenv("GPUDRIVE_LINEAR_LEGACY") == nullptr ? 1 : 0;
         d.pose_stamp = s->alloc_internal<uint4>(WA);
         d.pose_skip = std::getenv("GPUDRIVE_NO_POSE_SKIP") == nullptr ? 1 : 0;
@@ -1173,7 +1158,7 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         s->d_slot_of_row = s->alloc_internal<int32_t>(WA);
         s->d_row_count = s->alloc_internal<int32_t>(1);
         d.bad_actions = s->alloc_internal<unsigned long long>(1);
-        d.blk_off = s->alloc_internal<int32_t>(W + 1);
+        d.blk_off = s->d_blk_off = s->alloc_internal<int32_t>(W + 1);
         d.warm_k = 0;
         d.warm_all = 0;
         d.warm_flags = s->alloc_internal<int32_t>(W);
@@ -1189,8 +1174,10 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         if (const char *e = std::getenv("GPUDRIVE_RANK_DBG")) d.rk_dbg = std::atoi(e);
 #endif
         for (int i = 0; i < gd_sim::kRing; i++) {
-            HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&s->h_flags[i]), sizeof(int32_t) * W, hipHostMallocDefault));
-            HIP_CHECK(hipEventCreateWithFlags(&s->flag_ev[i], hipEventDisableTiming));
+            void *pinned = nullptr;
+            HIP_CHECK(hipHostMalloc(&pinned, sizeof(int32_t) * W, hipHostMallocDefault));
+            s->h_flags[i].reset(static_cast<int32_t *>(pinned));
+            s->flag_ev[i] = make_event(hipEventDisableTiming);
         }
         std::vector<int> all(W);
         for (int w = 0; w < W; w++) all[w] = w;
@@ -1414,13 +1401,11 @@ int gd_record_expert(gd_sim *s, const gd_record_buffers *b, int32_t n_steps) {
     if (s->d.pack && s->d.pack_only)
         return fail(GD_ERR_UNSUPPORTED, "gd_record_expert: a packed buffer is attached with only = 1: the raw rows are stale");
     return guarded([&]() {
-        std::vector<hipEvent_t> ev;  // the optional diagnostic: a pair around every recorder launch
+        std::vector<Event> ev;  // the optional diagnostic: a pair around every recorder launch
         auto mark = [&]() {
             if (!b->kernel_ms) return;
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreate(&e));
-            ev.push_back(e);
-            HIP_CHECK(hipEventRecord(e, s->stream));
+            ev.push_back(make_event());
+            HIP_CHECK(hipEventRecord(ev.back().get(), s->stream));
         };
         for (int t = 0; t <= n_steps; t++) {
             mark();
@@ -1437,10 +1422,9 @@ int gd_record_expert(gd_sim *s, const gd_record_buffers *b, int32_t n_steps) {
             float sum = 0.f;
             for (size_t i = 0; i + 1 < ev.size(); i += 2) {
                 float ms = 0.f;
-                HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                HIP_CHECK(hipEventElapsedTime(&ms, ev[i].get(), ev[i + 1].get()));
                 sum += ms;
             }
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
             *b->kernel_ms = sum;
         }
     });
@@ -1680,15 +1664,13 @@ int gd_episode_draw_weights(gd_sim *s, const gd_episode_config *cfg, const gd_ep
             return;
         }
         // an explicit call outside the step path: a temporary device copy of the list, waited for before it is freed
-        int32_t *dl = nullptr;
-        HIP_CHECK(hipMalloc(&dl, list.size() * sizeof(int32_t)));
-        hipError_t e = hipMemcpyAsync(dl, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s->stream);
+        const gd::DevMem dl(list.size() * sizeof(int32_t));
+        hipError_t e = hipMemcpyAsync(dl.get(), list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s->stream);
         if (e == hipSuccess) {
-            gd::launch_draw_weights(s->d, s->stream, *cfg, *b, dl, static_cast<int>(list.size()));
+            gd::launch_draw_weights(s->d, s->stream, *cfg, *b, static_cast<const int32_t *>(dl.get()), static_cast<int>(list.size()));
             e = hipGetLastError();
         }
-        const hipError_t es = hipStreamSynchronize(s->stream);
-        HIP_CHECK(hipFree(dl));
+        const hipError_t es = hipStreamSynchronize(s->stream);  // before dl goes, whatever failed
         HIP_CHECK(e);
         HIP_CHECK(es);
     });
@@ -1704,7 +1686,7 @@ int gd_set_stream(gd_sim *s, void *stream) {
     return guarded([&]() {
         HIP_CHECK(hipStreamSynchronize(s->stream));
         s->drop_graph();
-        HIP_CHECK(hipStreamSynchronize(s->side));
+        HIP_CHECK(hipStreamSynchronize(s->side.get()));
         s->stream = static_cast<hipStream_t>(stream);
         s->d.split_partner = (s->stream != nullptr && std::getenv("GPUDRIVE_SPLIT_PARTNER") != nullptr) ? 1 : 0;
     });
@@ -1851,10 +1833,7 @@ int gd_kernel_timing_enable(gd_sim *s, int32_t enable) {
             s->ev_ms[k] = 0;
             s->ev_launches[k] = 0;
             while (enable && s->ev_pool[k].size() < gd_sim::kEvRing) {  // every event exists before the first timed launch
-                EventPair n{};
-                HIP_CHECK(hipEventCreate(&n.start));
-                HIP_CHECK(hipEventCreate(&n.stop));
-                s->ev_pool[k].push_back(n);
+                s->ev_pool[k].push_back(EventPair{make_event(), make_event()});  // (a failing second one returns the first)
             }
         }
         s->timing = enable != 0;

@@ -28,6 +28,9 @@ extern "C" {
 #define GD_ERR_INVALID (-1)   /* bad argument */
 #define GD_ERR_IO (-2)        /* scene file missing / unreadable (reference: assert, src/MapReader.cpp:40) */
 #define GD_ERR_PARSE (-3)     /* malformed scene JSON (reference: nlohmann exception -> abort) */
+/* After gd_create, gd_set_maps or gd_delete_agents returns GD_ERR_DEVICE (e.g. the device is out of memory in the middle
+ * of a rebuild) the worlds are not in a usable state: the only supported calls on that simulator are gd_destroy and
+ * gd_last_error.  gd_destroy is always safe: the engine never keeps a device address it has returned. */
 #define GD_ERR_DEVICE (-4)    /* HIP runtime failure, no gfx950 device */
 #define GD_ERR_UNSUPPORTED (-5)
 

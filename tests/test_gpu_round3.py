@@ -301,7 +301,10 @@ def test_config5_lidar_at_1024_worlds(oracle_mod):
 def test_rebuild_into_existing_capacity_keeps_the_pad(oracle_mod, tmp_path):
     """k_map_obs prefetches up to 256 roads past a world's last one and the fused set-order write-out reads the first
     record of a world without roads: the arrays must end in readable pad entries also when set_maps / deleteAgents
-    rebuild into the capacity of an earlier, larger road set, and when no world has a road at all."""
+    rebuild into the capacity of an earlier, larger road set, and when no world has a road at all.
+    The second sequence starts small and makes every array GROW after creation (2 x 128 roads leave room for 928 road
+    entries, 352 boxes, 416 road-grid items, 83 block circles; 2 x 1024 roads need 2048 + 320, 2048, 2048 + 64, 129), then
+    reuses the grown arrays (2 x 1120 roads fit the 2944 entries) and shrinks in place."""
     def scene(name, n_poly, pts, seed):
         p = tmp_path / (name + ".json")
         p.write_text(json.dumps(synth.make_scene(seed, n_agents=6, n_polylines=n_poly, pts_per_polyline=pts)))
@@ -311,10 +314,12 @@ def test_rebuild_into_existing_capacity_keeps_the_pad(oracle_mod, tmp_path):
     edge = scene("edge", 8, 141, 3)      # 1120 roads: above `big`, inside its capacity + slack
     none = scene("none", 0, 2, 4)        # no roads at all
     kw = dict(BENCH, observationRadius=60.0)
-    for order in (0, 1):
-        gpu = P.make_gpu_sim([big, big], max_agents=64, knn_order=order, **kw)
-        orc = P.make_oracle_sim(oracle_mod, [big, big], max_agents=64, **kw)
-        for new in ([small, small], [edge, edge], [none, small], [none, none], [big, none]):
+    shrinking = ([big, big], [small, small], [edge, edge], [none, small], [none, none], [big, none])
+    growing = ([small, small], [big, big], [edge, edge], [small, none])
+    for order, (first, *rest) in ((0, shrinking), (1, shrinking), (0, growing), (1, growing)):
+        gpu = P.make_gpu_sim(first, max_agents=64, knn_order=order, **kw)
+        orc = P.make_oracle_sim(oracle_mod, first, max_agents=64, **kw)
+        for new in rest:
             gpu.set_maps(new)
             orc.set_maps(new)
             if order == 0:
