@@ -1607,6 +1607,29 @@ int gd_rollout_gather(const gd_rollout *ro, const gd_rollout_batch *b, void *str
     });
 }
 
+int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
+                      float *logprob, float *entropy, float *value, float *logits_out, void *stream) {
+    if (!p || !obs || !actions || !logprob || !entropy || !value || (!u && !deterministic))
+        return fail(GD_ERR_INVALID, "gd_policy_forward: null argument");
+    if (p->max_agents != 64 && p->max_agents != 128) return fail(GD_ERR_INVALID, "gd_policy_forward: max_agents must be 64 or 128");
+    if (p->ego_width != 6 && p->ego_width != 9) return fail(GD_ERR_INVALID, "gd_policy_forward: ego_width must be 6 or 9");
+    if (p->n_actions < 1 || p->n_actions > 1024) return fail(GD_ERR_INVALID, "gd_policy_forward: n_actions must be in [1, 1024]");
+    if (p->num_rows < 1 || p->num_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_policy_forward: num_rows must be in [1, 2^20]");
+    if (!p->blob || !p->features || !p->logits) return fail(GD_ERR_INVALID, "gd_policy_forward: blob, features and logits are required");
+    if (p->blob_floats != gd::policy_blob_floats(p->ego_width, p->n_actions))
+        return fail(GD_ERR_INVALID, "gd_policy_forward: blob_floats is not the layout's size for this ego_width and n_actions");
+    if (misaligned(p->blob, 16) || misaligned(p->features, 16))
+        return fail(GD_ERR_INVALID, "gd_policy_forward: blob and features must be 16-byte aligned");
+    if (misaligned(actions, 8) || misaligned(obs, 4) || (u && misaligned(u, 4)) || misaligned(p->logits, 4) || misaligned(logprob, 4) ||
+        misaligned(entropy, 4) || misaligned(value, 4) || (logits_out && misaligned(logits_out, 4)))
+        return fail(GD_ERR_INVALID, "gd_policy_forward: actions must be 8-byte aligned, float buffers 4-byte aligned");
+    return guarded([&]() {
+        gd::launch_policy_forward(*p, static_cast<hipStream_t>(stream), obs, u, deterministic != 0, actions, logprob, entropy, value,
+                                  logits_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

@@ -242,5 +242,8 @@ void launch_rollout_sort(const gd_rollout &ro, hipStream_t st, const int64_t *of
 void launch_rollout_gae(const gd_rollout &ro, hipStream_t st, const int64_t *idxs, float gamma, float gae_lambda, float *delta,
                         float *coef, float *adv);  // rollout.hip
 void launch_rollout_gather(const gd_rollout &ro, hipStream_t st, const gd_rollout_batch &b);  // rollout.hip
+long long policy_blob_floats(int ego_width, int n_actions);  // policy.hip: the size of gd_policy.blob
+void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs, const float *u, bool deterministic,
+                           int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out);  // policy.hip
 
 }  // namespace gd

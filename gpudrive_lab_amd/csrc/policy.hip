@@ -1,0 +1,259 @@
+// Device policy forward (gd_policy_forward): the reference's late-fusion actor-critic in eval mode
+// (gpudrive/networks/late_fusion.py:170-210) on learner rows, float32 throughout, as three launches:
+//   k_policy_embed   a wave per observation row.  Each embedder is computed TRANSPOSED on v_mfma_f32_32x32x2_f32: the 64
+//                    features are the accumulator rows (two tiles of 32), 32 entities sit on the lanes.  Layer 1 takes the
+//                    weights as the A operand and the entity rows as B straight from global memory (dword loads, so a row
+//                    that starts at any dword phase needs no care); LayerNorm reduces over a lane's 32 registers plus one swap
+//                    of the two lane halves; tanh is elementwise; the accumulator is then the B operand of the second 64 x 64
+//                    layer with no lane movement: register r of tile t holds feature 32t + (r&3) + 8(r>>2) + 4(lane>>5), so
+//                    k-step (t, r) contracts the features F and F + 4 and the packed A operand holds W2[.][F + 4(lane>>5)].
+//                    The running max over entity tiles stays in registers; lanes past the entity count never enter it.  The
+//                    second layer's bias is added after the max (x -> fl(x + b) is monotonic, so the result is the same).
+//                    The ego embedding (one entity) is plain lane-per-feature arithmetic.  Writes features [N][192].
+//   k_policy_tail    a wave per 32 rows: hidden^T = Ws . features^T (192 -> 128, four accumulator tiles), which is again the
+//                    B operand of [actor; critic] . hidden^T, one tile of 32 outputs at a time.  Writes the logits and value.
+//   k_policy_sample  a lane per row runs policy_rule.hpp on the row's logits.
+// The weights come packed in lane order (gd_policy.blob; the layout is PolicyLayout below and gpudrive_lab_amd/policy.py).
+// An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation
+// (-ffp-contract=off).  No LDS, no atomics; every byte of every output is stored on every call.
+#include <hip/hip_runtime.h>
+
+#include "engine.hpp"
+#include "policy_rule.hpp"
+
+namespace gd {
+
+namespace {
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int F = 64, HID = 128, FEAT = 192, ROADS = 200, ROAD_K = 13, PARTNER_K = 6;
+constexpr float LN_EPS = 1e-5f;
+
+// offsets into the blob, in floats
+struct PolicyLayout {
+    int ego_w1, ego_b1, ego_g, ego_b, ego_w2t, ego_b2;
+    int emb_w1[2], emb_b1[2], emb_g[2], emb_b[2], emb_w2[2], emb_b2[2];  // 0: partner, 1: road
+    int sh_w, sh_b, ac_w, ac_b, tiles, total;
+};
+
+PolicyLayout policy_layout(int ego_width, int n_actions) {
+    PolicyLayout L;
+    int o = 0;
+    auto take = [&](int n) { const int at = o; o += n; return at; };
+    L.ego_w1 = take(F * ego_width), L.ego_b1 = take(F), L.ego_g = take(F), L.ego_b = take(F), L.ego_w2t = take(F * F), L.ego_b2 = take(F);
+    for (int e = 0; e < 2; e++) {
+        L.emb_w1[e] = take(2 * (e ? 7 : 3) * 64), L.emb_b1[e] = take(F), L.emb_g[e] = take(F), L.emb_b[e] = take(F);
+        L.emb_w2[e] = take(2 * 32 * 64), L.emb_b2[e] = take(F);
+    }
+    L.tiles = (n_actions + 1 + 31) / 32;
+    L.sh_w = take(4 * 96 * 64), L.sh_b = take(HID), L.ac_w = take(L.tiles * 64 * 64), L.ac_b = take(L.tiles * 32);
+    L.total = o;
+    return L;
+}
+
+// accumulator register r of lane half h holds this row of a 32 x 32 tile
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// One embedder over `count` entity rows of K floats at x (K = 6: KS = 3 k-steps; K = 13: KS = 7, the 14th column is zero in
+// both operands): the pooled 64 features, bias included, to out[0..64).
+template <int K, int KS>
+__device__ __forceinline__ void embed_pool(const float *__restrict__ x, int count, const float *__restrict__ w1a,
+                                           const float *__restrict__ b1, const float *__restrict__ g, const float *__restrict__ be,
+                                           const float *__restrict__ w2a, const float *__restrict__ b2, float *__restrict__ out,
+                                           int lane) {
+    const int h = lane >> 5, col = lane & 31;
+    float w1[2][KS], w2[2][32];
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+#pragma unroll
+        for (int s = 0; s < KS; s++) w1[t][s] = w1a[(t * KS + s) * 64 + lane];
+#pragma unroll
+        for (int q = 0; q < 32; q++) w2[t][q] = w2a[(t * 32 + q) * 64 + lane];
+    }
+    f16v best[2];
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) best[t][r] = -INFINITY;
+
+    for (int base = 0; base < count; base += 32) {
+        const int e = base + col;
+        const bool live = e < count;
+        float xs[KS];
+#pragma unroll
+        for (int s = 0; s < KS; s++) xs[s] = (live && KS * h + s < K) ? x[(size_t)e * K + KS * h + s] : 0.f;
+        f16v a[2];
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) a[t][r] = b1[32 * t + acc_row(r, h)];
+#pragma unroll
+            for (int s = 0; s < KS; s++) a[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[t][s], xs[s], a[t], 0, 0, 0);
+        }
+        // LayerNorm over the 64 features of this lane's entity: 32 here, 32 in the other lane half
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) sum = sum + a[t][r];
+        sum = sum + __shfl_xor(sum, 32);
+        const float mean = sum * (1.f / 64.f);
+        float sq = 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                a[t][r] = a[t][r] - mean;
+                sq = sq + a[t][r] * a[t][r];
+            }
+        sq = sq + __shfl_xor(sq, 32);
+        const float rstd = 1.f / sqrtf(sq * (1.f / 64.f) + LN_EPS);
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int f = 32 * t + acc_row(r, h);
+                a[t][r] = tanhf((a[t][r] * rstd) * g[f] + be[f]);
+            }
+        f16v o[2];
+#pragma unroll
+        for (int t2 = 0; t2 < 2; t2++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) o[t2][r] = 0.f;
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[t2][t * 16 + r], a[t][r], o[t2], 0, 0, 0);
+        }
+        if (live) {
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) best[t][r] = fmaxf(best[t][r], o[t][r]);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            float v = best[t][r];
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
+            const int f = 32 * t + acc_row(r, h);
+            if (col == 0) out[f] = v + b2[f];
+        }
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
+                                                      float *__restrict__ features) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.num_rows) return;  // wave-uniform; nothing below synchronises across waves
+    const int partners = p.max_agents - 1, ew = p.ego_width;
+    const size_t width = (size_t)ew + (size_t)PARTNER_K * partners + (size_t)ROAD_K * ROADS;
+    const float *__restrict__ x = obs + (size_t)row * width;
+    const float *__restrict__ w = p.blob;
+    float *__restrict__ out = features + (size_t)row * FEAT;
+
+    // ego: lane f is feature f
+    {
+        float a = w[L.ego_b1 + lane];
+        for (int k = 0; k < ew; k++) a = a + w[L.ego_w1 + lane * ew + k] * x[k];
+        const float mean = wave_sum(a) * (1.f / 64.f);
+        const float d = a - mean;
+        const float rstd = 1.f / sqrtf(wave_sum(d * d) * (1.f / 64.f) + LN_EPS);
+        const float t = tanhf((d * rstd) * w[L.ego_g + lane] + w[L.ego_b + lane]);
+        float o = w[L.ego_b2 + lane];
+        for (int f = 0; f < F; f++) o = o + w[L.ego_w2t + f * F + lane] * __shfl(t, f);
+        out[lane] = o;
+    }
+    embed_pool<PARTNER_K, 3>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0], w + L.emb_w2[0],
+                             w + L.emb_b2[0], out + F, lane);
+    embed_pool<ROAD_K, 7>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1], w + L.emb_b[1],
+                          w + L.emb_w2[1], w + L.emb_b2[1], out + 2 * F, lane);
+}
+
+__global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L, const float *__restrict__ features,
+                                                    float *__restrict__ logits, float *__restrict__ logits_out,
+                                                    float *__restrict__ value) {
+    const int lane = threadIdx.x, h = lane >> 5;
+    const int row = blockIdx.x * 32 + (lane & 31);
+    const int n = p.num_rows, na = p.n_actions;
+    const int rc = row < n ? row : n - 1;  // a lane past the end computes the last row again and stores nothing
+    const float *__restrict__ w = p.blob;
+    // lane half h contracts the features [96h, 96h + 96): 24 aligned 16-byte loads
+    const f4 *__restrict__ fp = reinterpret_cast<const f4 *>(features + (size_t)rc * FEAT + 96 * h);
+    f16v hid[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) hid[t][r] = w[L.sh_b + 32 * t + acc_row(r, h)];
+    for (int c = 0; c < 24; c++) {
+        const f4 v = fp[c];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                hid[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[L.sh_w + (t * 96 + 4 * c + j) * 64 + lane], v[j], hid[t], 0, 0, 0);
+    }
+    for (int i = 0; i < L.tiles; i++) {
+        const float *__restrict__ wa = w + L.ac_w + (size_t)i * 64 * 64 + lane;
+        f16v acc;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[(t * 16 + r) * 64], hid[t][r], acc, 0, 0, 0);
+        if (row < n) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int a = 32 * i + acc_row(r, h);
+                const float v = acc[r] + w[L.ac_b + a];
+                if (a < na) {
+                    logits[(size_t)row * na + a] = v;
+                    if (logits_out) logits_out[(size_t)row * na + a] = v;
+                } else if (a == na) {
+                    value[row] = v;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
+                                                      int deterministic, int64_t *__restrict__ actions,
+                                                      float *__restrict__ logprob, float *__restrict__ entropy) {
+    const int row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= n) return;
+    const float *__restrict__ l = logits + (size_t)row * na;
+    const policy_rule::Draw d = policy_rule::draw(na, [&](int k) { return l[k]; }, deterministic ? 0.f : u[row], deterministic != 0);
+    actions[row] = d.action;
+    logprob[row] = d.logprob;
+    entropy[row] = d.entropy;
+}
+
+}  // namespace
+
+long long policy_blob_floats(int ego_width, int n_actions) { return policy_layout(ego_width, n_actions).total; }
+
+void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs, const float *u, bool deterministic,
+                           int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out) {
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows;
+    hipLaunchKernelGGL(k_policy_embed, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features);
+    hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits, logits_out, value);
+    hipLaunchKernelGGL(k_policy_sample, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, u,
+                       deterministic ? 1 : 0, actions, logprob, entropy);
+}
+
+}  // namespace gd

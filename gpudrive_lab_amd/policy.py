@@ -1,0 +1,249 @@
+"""The device policy forward: the reference's late-fusion actor-critic on learner rows, between `env.step` and `ro.store`.
+
+`DevicePolicy` is the reference's `NeuralNet.forward` under `torch.no_grad()` (gpudrive/networks/late_fusion.py:170-210, the
+middle of the rollout loop gpudrive/integrations/puffer/ppo.py:129-199) as one C call (`gd_policy_forward`, three launches,
+csrc/policy.hip): both set embedders on float32 MFMA with the LayerNorm, the tanh, the second layer and the max-pool in
+registers, so none of the [N, 200, 64] and [N, A-1, 64] intermediates exists; then 192 -> 128 -> n_actions + 1 over tiles of
+32 rows; then the action rule.  Float32 throughout: the logprob stored in the rollout is later compared with torch's own
+float32 recomputation in the PPO ratio.
+
+    pol = DevicePolicy.from_state_dict(net.state_dict(), max_agents=128, ego_width=6)   # 9: ConditionedLearnerEnv rows
+    while not ro.full:
+        u = torch.rand(N, device="cuda", generator=g)
+        actions, logprob, entropy, value = pol(obs, u)        # or pol(obs, deterministic=True); out=... reuses buffers
+        ro.store(obs, value, actions, logprob, rewards, terminals, masks)
+        obs, rewards, terminals, truncations, masks = env.step(actions)
+
+EVAL MODE.  The forward is the module in eval mode: dropout is the identity.  The reference's rollout does not call
+`.eval()` and its yaml has dropout 0.01, so its own rollout forward drops 1 % of the embedder activations and of the hidden
+vector at random; this class does not reproduce that noise.
+
+The network rule and the action rule are stated in include/gpudrive_amd.h (`gd_policy`) and csrc/policy_rule.hpp.  The
+draw is this project's: `torch.multinomial`'s random stream cannot be reproduced, so the action is a function of one
+uniform u in [0, 1) per row -- the first k whose running sum of exp(l - max l), in ascending k, exceeds u times the whole sum.
+The max-pools run over ALL A - 1 partner rows and all 200 road rows, padding rows included, as the reference's do.
+Observations must be finite.
+
+Not here: a bf16 or fp8 forward, the backward pass, the losses, LSTM state, GELU, `vbd_in_obs`, more than 1024 actions."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _capi
+
+INPUT_DIM, HIDDEN_DIM, ROADS, ROAD_K, PARTNER_K = 64, 128, 200, 13, 6
+FEATURES = 3 * INPUT_DIM
+MAX_ACTIONS = 1024
+MAX_ROWS = 1 << 20
+EMBEDDERS = ("ego_embed", "partner_embed", "road_map_embed")
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def obs_width(max_agents, ego_width):
+    return ego_width + PARTNER_K * (max_agents - 1) + ROAD_K * ROADS
+
+
+def expected_shapes(ego_width, n_actions):
+    """The state dict of the supported module, by the reference's own names, in the order the packer concatenates it."""
+    shapes = {}
+    for name, k in zip(EMBEDDERS, (ego_width, PARTNER_K, ROAD_K)):
+        shapes[name + ".0.weight"], shapes[name + ".0.bias"] = (INPUT_DIM, k), (INPUT_DIM,)
+        shapes[name + ".1.weight"], shapes[name + ".1.bias"] = (INPUT_DIM,), (INPUT_DIM,)
+        shapes[name + ".4.weight"], shapes[name + ".4.bias"] = (INPUT_DIM, INPUT_DIM), (INPUT_DIM,)
+    shapes["shared_embed.0.weight"], shapes["shared_embed.0.bias"] = (HIDDEN_DIM, FEATURES), (HIDDEN_DIM,)
+    shapes["actor.weight"], shapes["actor.bias"] = (n_actions, HIDDEN_DIM), (n_actions,)
+    shapes["critic.weight"], shapes["critic.bias"] = (1, HIDDEN_DIM), (1,)
+    return shapes
+
+
+def check_policy_args(state_dict, max_agents, ego_width, act_func="tanh", vbd_in_obs=False):
+    """Everything `DevicePolicy` refuses, checked on the host before anything reaches the device (ValueError).  Returns
+    n_actions."""
+    who = "DevicePolicy: "
+    if act_func != "tanh":
+        raise ValueError(who + "act_func %r is not built (tanh only)" % (act_func,))
+    if vbd_in_obs:
+        raise ValueError(who + "vbd_in_obs is not built")
+    if not _is_int(max_agents) or max_agents not in (64, 128):
+        raise ValueError(who + "max_agents must be 64 or 128, got %r" % (max_agents,))
+    if not _is_int(ego_width) or ego_width not in (6, 9):
+        raise ValueError(who + "ego_width must be 6 or 9, got %r" % (ego_width,))
+    if not hasattr(state_dict, "keys") or not hasattr(state_dict, "__getitem__"):
+        raise ValueError(who + "state_dict must be a mapping of names to tensors")
+    keys = set(state_dict.keys())
+    if "actor.weight" not in keys:
+        raise ValueError(who + "missing key 'actor.weight'")
+    aw = state_dict["actor.weight"]
+    if not isinstance(aw, torch.Tensor) or aw.dim() != 2:
+        raise ValueError(who + "actor.weight must be a [n_actions, %d] tensor" % HIDDEN_DIM)
+    n_actions = int(aw.shape[0])
+    if not 1 <= n_actions <= MAX_ACTIONS:
+        raise ValueError(who + "n_actions must be in [1, %d], got %d" % (MAX_ACTIONS, n_actions))
+    want = expected_shapes(ego_width, n_actions)
+    missing, extra = sorted(set(want) - keys), sorted(keys - set(want))
+    if missing:
+        raise ValueError(who + "missing key(s) %s" % ", ".join(map(repr, missing)))
+    if extra:
+        raise ValueError(who + "unexpected key(s) %s" % ", ".join(map(repr, extra)))
+    for name, shape in want.items():
+        t = state_dict[name]
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError(who + "%s must be a tensor of shape %s (input_dim %d, hidden_dim %d), got %s"
+                             % (name, shape, INPUT_DIM, HIDDEN_DIM, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
+        if t.dtype != torch.float32:
+            raise ValueError(who + "%s must be float32, got %s" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError(who + "%s must be contiguous" % name)
+    return n_actions
+
+
+def _acc_row(r, h):
+    return (r & 3) + 8 * (r >> 2) + 4 * h
+
+
+def pack_index(ego_width, n_actions):
+    """The layout of `gd_policy.blob` as an index: blob = flat[pack_index], where flat is the state dict's tensors flattened
+    and concatenated in `expected_shapes` order, followed by one zero (the index of every padding element).  int64 numpy."""
+    shapes = expected_shapes(ego_width, n_actions)
+    base, o = {}, 0
+    for name, shape in shapes.items():
+        base[name] = o
+        o += int(np.prod(shape))
+    zero = o
+    lane = np.arange(64)
+    c, h = lane & 31, lane >> 5
+    acc = np.array([[_acc_row(r, hh) for hh in (0, 1)] for r in range(16)])  # [r][h]
+    parts = []
+
+    def nat(name):
+        parts.append(base[name] + np.arange(int(np.prod(shapes[name]))))
+
+    e = EMBEDDERS[0]
+    nat(e + ".0.weight"), nat(e + ".0.bias"), nat(e + ".1.weight"), nat(e + ".1.bias")
+    parts.append((base[e + ".4.weight"] + np.arange(64)[None, :] * 64 + np.arange(64)[:, None]).reshape(-1))  # [in][out]
+    nat(e + ".4.bias")
+    for e, k, ks in ((EMBEDDERS[1], PARTNER_K, 3), (EMBEDDERS[2], ROAD_K, 7)):
+        t, s = np.arange(2)[:, None, None], np.arange(ks)[None, :, None]
+        col = ks * h[None, None, :] + s + 0 * t
+        idx = base[e + ".0.weight"] + (32 * t + c[None, None, :]) * k + col
+        parts.append(np.where(col < k, idx, zero).reshape(-1))
+        nat(e + ".0.bias"), nat(e + ".1.weight"), nat(e + ".1.bias")
+        t2, t, r = np.arange(2)[:, None, None, None], np.arange(2)[None, :, None, None], np.arange(16)[None, None, :, None]
+        col = 32 * t + acc[r, h[None, None, None, :]]
+        parts.append((base[e + ".4.weight"] + (32 * t2 + c[None, None, None, :]) * 64 + col).reshape(-1))
+        nat(e + ".4.bias")
+    t, s = np.arange(4)[:, None, None], np.arange(96)[None, :, None]
+    parts.append((base["shared_embed.0.weight"] + (32 * t + c[None, None, :]) * FEATURES + 96 * h[None, None, :] + s).reshape(-1))
+    nat("shared_embed.0.bias")
+    tiles = (n_actions + 1 + 31) // 32
+    i, t, r = np.arange(tiles)[:, None, None, None], np.arange(4)[None, :, None, None], np.arange(16)[None, None, :, None]
+    a = 32 * i + c[None, None, None, :] + 0 * t + 0 * r
+    col = 32 * t + acc[r, h[None, None, None, :]] + 0 * i
+    idx = np.where(a < n_actions, base["actor.weight"] + a * HIDDEN_DIM + col,
+                   np.where(a == n_actions, base["critic.weight"] + col, zero))
+    parts.append(idx.reshape(-1))
+    a = np.arange(tiles * 32)
+    parts.append(np.where(a < n_actions, base["actor.bias"] + a, np.where(a == n_actions, base["critic.bias"], zero)))
+    return np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in parts])
+
+
+class DevicePolicy:
+    def __init__(self, state_dict, max_agents=128, ego_width=6, *, device="cuda", act_func="tanh", vbd_in_obs=False):
+        """state_dict: the reference module's (`ego_embed.0/1/4`, `partner_embed.0/1/4`, `road_map_embed.0/1/4`: Linear,
+        LayerNorm with affine, Linear; `shared_embed.0`, `actor`, `critic`), float32, with input_dim 64, hidden_dim 128 and
+        1 <= n_actions <= 1024.  max_agents: 64 or 128.  ego_width: 6, or 9 for reward-conditioned rows.  Anything else --
+        other widths, an activation other than tanh, vbd_in_obs, more than 1024 actions (the 8000-entry delta table), a
+        missing or extra key, a wrong shape or dtype -- is a ValueError raised before anything reaches the device.  The
+        forward is the module in eval mode (see the module docstring)."""
+        self.n_actions = check_policy_args(state_dict, max_agents, ego_width, act_func, vbd_in_obs)
+        self.max_agents, self.ego_width = max_agents, ego_width
+        self.obs_width = obs_width(max_agents, ego_width)
+        try:
+            dev = torch.device(device)
+        except (RuntimeError, TypeError) as e:
+            raise ValueError("DevicePolicy: device: %s" % e)
+        if dev.type != "cuda":
+            raise ValueError("DevicePolicy: the policy runs on the GPU (there is no host path), got device %r" % (device,))
+        self._L = _capi.lib()
+        self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self._names = tuple(expected_shapes(ego_width, self.n_actions))
+        self._index = torch.from_numpy(pack_index(ego_width, self.n_actions)).to(self.device)
+        self._zero = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.blob = torch.empty(self._index.numel(), dtype=torch.float32, device=self.device)
+        self._features = self._logits = None
+        self._rows = 0
+        self._pack(state_dict)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, max_agents=128, ego_width=6, **kw):
+        return cls(state_dict, max_agents, ego_width, **kw)
+
+    def _pack(self, sd):
+        with torch.no_grad():
+            flat = torch.cat([sd[k].detach().to(self.device).reshape(-1) for k in self._names] + [self._zero])
+            torch.index_select(flat, 0, self._index, out=self.blob)
+
+    def load_state_dict(self, state_dict):
+        """Re-pack after an optimiser step: the same keys, shapes and dtypes (ValueError otherwise).  For tensors already on
+        the device this is a concatenation and one gather on the device, on torch's current stream."""
+        if check_policy_args(state_dict, self.max_agents, self.ego_width) != self.n_actions:
+            raise ValueError("DevicePolicy.load_state_dict: n_actions must stay %d" % self.n_actions)
+        self._pack(state_dict)
+
+    def _tensor(self, name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device \
+                or not t.is_contiguous():
+            raise ValueError("DevicePolicy: %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), self.device))
+        return t
+
+    OUT_NAMES = ("actions", "logprob", "entropy", "value")
+
+    def __call__(self, obs, u=None, deterministic=False, out=None, logits_out=None):
+        """obs [N, obs_width] float32, contiguous, on the device.  u [N] float32 in [0, 1) (required unless deterministic).
+        Returns (actions int64 [N], logprob, entropy, value float32 [N]).  out: those four tensors of an earlier call, to be
+        overwritten (every byte is written); logits_out: [N, n_actions] float32 to receive the logits.  Three launches on
+        torch's current stream, no host synchronisation; with out= and an N seen before, no allocation either, so the call can
+        be captured in a graph.  The features and logits scratch belongs to the object (it grows with the largest N seen), so
+        a DevicePolicy serves ONE stream at a time: calls on two streams need two objects or an event between them."""
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[1] != self.obs_width:
+            raise ValueError("DevicePolicy: obs must be a [N, %d] tensor (max_agents %d, ego_width %d)"
+                             % (self.obs_width, self.max_agents, self.ego_width))
+        n = int(obs.shape[0])
+        if not 1 <= n <= MAX_ROWS:
+            raise ValueError("DevicePolicy: N must be in [1, %d], got %d" % (MAX_ROWS, n))
+        self._tensor("obs", obs, torch.float32, (n, self.obs_width))
+        deterministic = bool(deterministic)
+        if u is None:
+            if not deterministic:
+                raise ValueError("DevicePolicy: u is required unless deterministic=True")
+        else:
+            self._tensor("u", u, torch.float32, (n,))
+        f = torch.float32
+        want = (((n,), torch.int64), ((n,), f), ((n,), f), ((n,), f))
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in want)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 4:
+                raise ValueError("DevicePolicy: out must be the four tensors (actions, logprob, entropy, value)")
+            out = tuple(self._tensor("out " + name, o, dt, shape) for name, o, (shape, dt) in zip(self.OUT_NAMES, out, want))
+        if logits_out is not None:
+            self._tensor("logits_out", logits_out, f, (n, self.n_actions))
+        if n > self._rows:
+            self._features = torch.empty((n, FEATURES), dtype=f, device=self.device)
+            self._logits = torch.empty((n, self.n_actions), dtype=f, device=self.device)
+            self._rows = n
+        p = _capi.GdPolicy()
+        p.num_rows, p.max_agents, p.ego_width, p.n_actions = n, self.max_agents, self.ego_width, self.n_actions
+        p.blob, p.blob_floats = self.blob.data_ptr(), self.blob.numel()
+        p.features, p.logits = self._features.data_ptr(), self._logits.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(self._L.gd_policy_forward(C.byref(p), obs.data_ptr(), None if u is None else u.data_ptr(),
+                                                  int(deterministic), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                                  out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(),
+                                                  stream), "gd_policy_forward")
+        return out

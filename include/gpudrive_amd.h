@@ -416,6 +416,55 @@ typedef struct gd_rollout_batch {
  * host synchronisation.  A p outside [0, B) gives zeros and counts in state[3].  GD_ERR_INVALID: a null pointer, sizes that
  * do not multiply to B, [first, first + n) outside the minibatches, split outside 0..64, samples * split >= 2^24. */
 int gd_rollout_gather(const gd_rollout *ro, const gd_rollout_batch *batch, void *stream);
+/* Device policy forward: the producer of actions, logprobs and values between the learner step and the rollout buffer.
+ * Replaces the reference's NeuralNet.forward under no_grad (gpudrive/networks/late_fusion.py:170-210, called by
+ * gpudrive/integrations/puffer/ppo.py:150-160) and its chain of torch operators over [N][200][64] and [N][A-1][64]
+ * intermediates.  Needs no simulator: every pointer is a device pointer owned by the caller, `stream` is a hipStream_t.
+ * N = num_rows, A = max_agents, EW = ego_width, NA = n_actions, D = EW + 6 (A - 1) + 200 * 13.
+ *
+ * The network rule (float32 throughout; the module in EVAL mode, dropout is the identity):
+ *   ego      = L2e(tanh(LN(L1e(obs[0 .. EW)))))                                        [64]
+ *   partner  = max over ALL A - 1 rows j of L2p(tanh(LN(L1p(obs[EW + 6 j .. + 6)))))   [64]  (padding rows included)
+ *   road     = max over ALL 200 rows j of L2r(tanh(LN(L1r(obs[EW + 6 (A-1) + 13 j .. + 13)))))   [64]
+ *   hidden   = Ws [ego, partner, road] + bs                                            [128] (no activation)
+ *   logits   = Wa hidden + ba   [NA];   value = Wc hidden + bc
+ *   LN(x)    = (x - mean) * (1 / sqrt(var + 1e-5)) * g + b, var the biased variance, sqrt and division correctly rounded.
+ * The matrix products are v_mfma_f32_32x32x2_f32 chains (one fmaf per term, float32 in and out); the summation order
+ * differs from a BLAS's, the precision does not.  Observations must be finite.
+ *
+ * The action rule is csrc/policy_rule.hpp, stated there in full: with m = max l, p[k] = expf(l[k] - m) and S the sum of p in
+ * ascending k, the sampled action is the first k whose running sum exceeds u[row] * S (the last k if none does), the
+ * deterministic action is the first index of the maximum; logprob = (l[a] - m) - logf(S); entropy = -sum q exp(q) with
+ * q = l - m - logf(S).
+ *
+ * blob: the weights packed once in the order the kernels read them (gpudrive_lab_amd/policy.py `pack_index` is the
+ * statement of the layout; acc(r, h) = (r & 3) + 8 (r >> 2) + 4 h is the accumulator row of register r in lane half h,
+ * lane = 0..63, h = lane >> 5, c = lane & 31), in floats, in this order:
+ *   ego:      W1 [64][EW], b1 [64], g [64], b [64], W2 transposed [in 64][out 64], b2 [64]
+ *   partner:  W1 as [t 2][s 3][lane] = W1[32 t + c][3 h + s];  b1, g, b [64];  W2 as [t2 2][t 2][r 16][lane] =
+ *             W2[32 t2 + c][32 t + acc(r, h)];  b2 [64]
+ *   road:     the same with [t 2][s 7][lane] = W1[32 t + c][7 h + s], zero where 7 h + s == 13
+ *   shared:   Ws as [t 4][s 96][lane] = Ws[32 t + c][96 h + s];  bs [128]
+ *   heads:    [actor; critic] (NA + 1 rows, zero rows up to T = ceil((NA + 1) / 32) tiles) as [i T][t 4][r 16][lane] =
+ *             W[32 i + c][32 t + acc(r, h)];  the biases [32 T] */
+typedef struct gd_policy {
+    int32_t num_rows;     /* N, 1 .. 2^20 */
+    int32_t max_agents;   /* A: 64 or 128 */
+    int32_t ego_width;    /* 6, or 9 for reward-conditioned rows */
+    int32_t n_actions;    /* 1 .. 1024 */
+    const float *blob;    /* blob_floats floats, 16-byte aligned */
+    int64_t blob_floats;  /* checked against the layout's size for (ego_width, n_actions) */
+    float *features;      /* [N][192] scratch, 16-byte aligned: ego, partner, road */
+    float *logits;        /* [N][NA] scratch: the logits the action rule reads */
+} gd_policy;
+/* One forward: three launches on `stream`, no host synchronisation, no allocation, no atomics.  obs [N][D] float32 at any
+ * 4-byte alignment (rows of odd width start at every dword phase; entity rows are read with 4-byte loads).  u [N] float32 in
+ * [0, 1), required unless deterministic != 0.  Outputs, every byte written by every call: actions [N] int64, logprob,
+ * entropy, value [N] float32; logits_out [N][NA] float32, or NULL for not written.
+ * GD_ERR_INVALID: a null pointer, max_agents not 64 or 128, ego_width not 6 or 9, n_actions outside [1, 1024], num_rows
+ * outside [1, 2^20], blob_floats not the layout's size, a misaligned pointer. */
+int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
+                      float *logprob, float *entropy, float *value, float *logits_out, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
