@@ -168,12 +168,20 @@ class GdPolicy(C.Structure):
                 [("blob", C.c_void_p), ("blob_floats", C.c_int64), ("features", C.c_void_p), ("logits", C.c_void_p)])
 
 
+class GdPolicyGrad(C.Structure):
+    """gd_policy_grad: what gd_policy_evaluate saves for gd_policy_backward, and the backward's weights and scratch (device
+    pointers)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("features", "logits", "winners", "params", "rowstat", "partials")] +
+                [("grad_floats", C.c_int64), ("num_partials", C.c_int32), ("reserved", C.c_int32)])
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_il_future_batch",
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
+    "gd_policy_evaluate", "gd_policy_backward",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -250,6 +258,8 @@ def lib():
                                  C.c_void_p]
     L.gd_rollout_gather.argtypes = [C.POINTER(GdRollout), C.POINTER(GdRolloutBatch), C.c_void_p]
     L.gd_policy_forward.argtypes = [C.POINTER(GdPolicy), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+    L.gd_policy_evaluate.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad)] + [C.c_void_p] * 6
+    L.gd_policy_backward.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad)] + [C.c_void_p] * 7
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -1630,6 +1630,53 @@ int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int3
     });
 }
 
+// the checks gd_policy_evaluate and gd_policy_backward share; nullptr when everything is in order
+static const char *policy_grad_problem(const gd_policy *p, const gd_policy_grad *g) {
+    if (p->max_agents != 64 && p->max_agents != 128) return "max_agents must be 64 or 128";
+    if (p->ego_width != 6 && p->ego_width != 9) return "ego_width must be 6 or 9";
+    if (p->n_actions < 1 || p->n_actions > 1024) return "n_actions must be in [1, 1024]";
+    if (p->num_rows < 1 || p->num_rows > (1 << 20)) return "num_rows must be in [1, 2^20]";
+    if (!g->features || !g->logits || !g->winners) return "features, logits and winners are required";
+    if (misaligned(g->features, 16) || misaligned(g->logits, 4)) return "features must be 16-byte aligned, logits 4-byte aligned";
+    return nullptr;
+}
+
+int gd_policy_evaluate(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions, float *logprob,
+                       float *entropy, float *value, void *stream) {
+    if (!p || !g || !obs || !actions || !logprob || !entropy || !value) return fail(GD_ERR_INVALID, "gd_policy_evaluate: null argument");
+    if (const char *why = policy_grad_problem(p, g)) return fail(GD_ERR_INVALID, std::string("gd_policy_evaluate: ") + why);
+    if (!p->blob) return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob is required");
+    if (p->blob_floats != gd::policy_blob_floats(p->ego_width, p->n_actions))
+        return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob_floats is not the layout's size for this ego_width and n_actions");
+    if (misaligned(p->blob, 16)) return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob must be 16-byte aligned");
+    if (misaligned(actions, 8) || misaligned(obs, 4) || misaligned(logprob, 4) || misaligned(entropy, 4) || misaligned(value, 4))
+        return fail(GD_ERR_INVALID, "gd_policy_evaluate: actions must be 8-byte aligned, float buffers 4-byte aligned");
+    return guarded([&]() {
+        gd_policy q = *p;
+        q.features = g->features, q.logits = g->logits;
+        gd::launch_policy_evaluate(q, static_cast<hipStream_t>(stream), obs, actions, g->winners, logprob, entropy, value);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_policy_backward(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
+                       const float *d_logprob, const float *d_entropy, const float *d_value, float *grad, void *stream) {
+    if (!p || !g || !obs || !actions || !d_logprob || !d_entropy || !d_value || !grad)
+        return fail(GD_ERR_INVALID, "gd_policy_backward: null argument");
+    if (const char *why = policy_grad_problem(p, g)) return fail(GD_ERR_INVALID, std::string("gd_policy_backward: ") + why);
+    if (!g->params || !g->rowstat || !g->partials) return fail(GD_ERR_INVALID, "gd_policy_backward: params, rowstat and partials are required");
+    if (g->num_partials < 1 || g->num_partials > 1024) return fail(GD_ERR_INVALID, "gd_policy_backward: num_partials must be in [1, 1024]");
+    if (g->grad_floats != gd::policy_grad_floats(p->ego_width, p->n_actions))
+        return fail(GD_ERR_INVALID, "gd_policy_backward: grad_floats is not the parameter count for this ego_width and n_actions");
+    if (misaligned(actions, 8) || misaligned(obs, 4) || misaligned(d_logprob, 4) || misaligned(d_entropy, 4) || misaligned(d_value, 4) ||
+        misaligned(grad, 4) || misaligned(g->params, 4) || misaligned(g->rowstat, 4) || misaligned(g->partials, 4))
+        return fail(GD_ERR_INVALID, "gd_policy_backward: actions must be 8-byte aligned, float buffers 4-byte aligned");
+    return guarded([&]() {
+        gd::launch_policy_backward(*p, *g, static_cast<hipStream_t>(stream), obs, actions, d_logprob, d_entropy, d_value, grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

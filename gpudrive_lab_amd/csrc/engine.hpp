@@ -245,5 +245,10 @@ void launch_rollout_gather(const gd_rollout &ro, hipStream_t st, const gd_rollou
 long long policy_blob_floats(int ego_width, int n_actions);  // policy.hip: the size of gd_policy.blob
 void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs, const float *u, bool deterministic,
                            int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out);  // policy.hip
+void launch_policy_evaluate(const gd_policy &p, hipStream_t st, const float *obs, const int64_t *actions, unsigned char *winners,
+                            float *logprob, float *entropy, float *value);  // policy.hip; p.features, p.logits: the saved buffers
+long long policy_grad_floats(int ego_width, int n_actions);  // policy_grad.hip: the size of the flat parameter gradient
+void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, hipStream_t st, const float *obs, const int64_t *actions,
+                            const float *d_logprob, const float *d_entropy, const float *d_value, float *grad);  // policy_grad.hip
 
 }  // namespace gd

@@ -58,11 +58,15 @@ __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >
 
 // One embedder over `count` entity rows of K floats at x (K = 6: KS = 3 k-steps; K = 13: KS = 7, the 14th column is zero in
 // both operands): the pooled 64 features, bias included, to out[0..64).
-template <int K, int KS>
+// REC (gd_policy_evaluate) also records the winner of every feature to win[0..64): the LOWEST entity index among the entities
+// whose float32 output equals the pooled maximum.  A lane keeps, per accumulator register, the first entity tile (0..6) that
+// raised its running max -- 3 bits, 8 registers to a dword -- so the index is tile * 32 + lane; the lanes that hold the wave's
+// maximum then take the minimum of their indices.  The value path is the same instructions with and without REC.
+template <int K, int KS, bool REC>
 __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int count, const float *__restrict__ w1a,
                                            const float *__restrict__ b1, const float *__restrict__ g, const float *__restrict__ be,
                                            const float *__restrict__ w2a, const float *__restrict__ b2, float *__restrict__ out,
-                                           int lane) {
+                                           unsigned char *__restrict__ win, int lane) {
     const int h = lane >> 5, col = lane & 31;
     float w1[2][KS], w2[2][32];
 #pragma unroll
@@ -77,6 +81,7 @@ __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int coun
     for (int t = 0; t < 2; t++)
 #pragma unroll
         for (int r = 0; r < 16; r++) best[t][r] = -INFINITY;
+    unsigned first[2][2] = {{0u, 0u}, {0u, 0u}};  // REC: [t][r >> 3], 3 bits per register
 
     for (int base = 0; base < count; base += 32) {
         const int e = base + col;
@@ -129,6 +134,15 @@ __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int coun
                     o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2[t2][t * 16 + r], a[t][r], o[t2], 0, 0, 0);
         }
         if (live) {
+            if constexpr (REC) {
+                const unsigned tile = (unsigned)base >> 5;
+#pragma unroll
+                for (int t = 0; t < 2; t++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++)
+                        if (o[t][r] > best[t][r])
+                            first[t][r >> 3] = (first[t][r >> 3] & ~(7u << (3 * (r & 7)))) | (tile << (3 * (r & 7)));
+            }
 #pragma unroll
             for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -144,6 +158,13 @@ __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int coun
             for (int d = 1; d < 32; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
             const int f = 32 * t + acc_row(r, h);
             if (col == 0) out[f] = v + b2[f];
+            if constexpr (REC) {
+                // every live lane's best is at most v; a lane with no live entity holds -inf and never equals it
+                int idx = best[t][r] == v ? (int)(((first[t][r >> 3] >> (3 * (r & 7))) & 7u) * 32u) + col : 255;
+#pragma unroll
+                for (int d = 1; d < 32; d <<= 1) idx = min(idx, __shfl_xor(idx, d));
+                if (col == 0) win[f] = (unsigned char)idx;
+            }
         }
 }
 
@@ -153,8 +174,9 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+template <bool REC>
 __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
-                                                      float *__restrict__ features) {
+                                                      float *__restrict__ features, unsigned char *__restrict__ winners) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= p.num_rows) return;  // wave-uniform; nothing below synchronises across waves
@@ -176,10 +198,11 @@ __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout 
         for (int f = 0; f < F; f++) o = o + w[L.ego_w2t + f * F + lane] * __shfl(t, f);
         out[lane] = o;
     }
-    embed_pool<PARTNER_K, 3>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0], w + L.emb_w2[0],
-                             w + L.emb_b2[0], out + F, lane);
-    embed_pool<ROAD_K, 7>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1], w + L.emb_b[1],
-                          w + L.emb_w2[1], w + L.emb_b2[1], out + 2 * F, lane);
+    unsigned char *__restrict__ win = REC ? winners + (size_t)row * (2 * F) : nullptr;
+    embed_pool<PARTNER_K, 3, REC>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0],
+                                  w + L.emb_w2[0], w + L.emb_b2[0], out + F, win, lane);
+    embed_pool<ROAD_K, 7, REC>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1],
+                               w + L.emb_b[1], w + L.emb_w2[1], w + L.emb_b2[1], out + 2 * F, REC ? win + F : nullptr, lane);
 }
 
 __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L, const float *__restrict__ features,
@@ -242,6 +265,20 @@ __global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float
     entropy[row] = d.entropy;
 }
 
+// gd_policy_evaluate: the action rule on GIVEN actions, a lane per row.  An action outside [0, na) is clamped (memory safety
+// only; such a row's logprob is that of the clamped action).
+__global__ __launch_bounds__(64) void k_policy_evaluate(int n, int na, const float *__restrict__ logits,
+                                                        const int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                        float *__restrict__ entropy) {
+    const int row = blockIdx.x * 64 + threadIdx.x;
+    if (row >= n) return;
+    const float *__restrict__ l = logits + (size_t)row * na;
+    const int64_t a = actions[row];
+    const policy_rule::Draw d = policy_rule::evaluate(na, [&](int k) { return l[k]; }, (int)(a < 0 ? 0 : a >= na ? na - 1 : a));
+    logprob[row] = d.logprob;
+    entropy[row] = d.entropy;
+}
+
 }  // namespace
 
 long long policy_blob_floats(int ego_width, int n_actions) { return policy_layout(ego_width, n_actions).total; }
@@ -250,10 +287,23 @@ void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs,
                            int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out) {
     const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
     const int n = p.num_rows;
-    hipLaunchKernelGGL(k_policy_embed, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features);
+    hipLaunchKernelGGL(k_policy_embed<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features,
+                       (unsigned char *)nullptr);
     hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits, logits_out, value);
     hipLaunchKernelGGL(k_policy_sample, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, u,
                        deterministic ? 1 : 0, actions, logprob, entropy);
+}
+
+// p.features and p.logits are the caller-owned buffers of gd_policy_grad here
+void launch_policy_evaluate(const gd_policy &p, hipStream_t st, const float *obs, const int64_t *actions, unsigned char *winners,
+                            float *logprob, float *entropy, float *value) {
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows;
+    hipLaunchKernelGGL(k_policy_embed<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features, winners);
+    hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits,
+                       (float *)nullptr, value);
+    hipLaunchKernelGGL(k_policy_evaluate, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, actions,
+                       logprob, entropy);
 }
 
 }  // namespace gd

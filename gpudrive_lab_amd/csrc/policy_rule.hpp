@@ -71,5 +71,45 @@ GD_POLICY_FN Draw draw(int n, Load load, float u, bool deterministic) {
     return d;
 }
 
+// The row statistics of the training side: m = max l, logS = logf(S) and H = the entropy, by draw()'s operations in draw()'s
+// order.  The one statement of them outside draw(): evaluate() below and the backward's rule (policy_grad_rule.hpp) both call
+// it, so that logprob and entropy of an evaluated action equal draw()'s bit for bit (the GPU tests compare them).  draw()
+// keeps its own loops: it also needs the index of the maximum and the running sum, and its kernel stays compiled as it was.
+struct RowStats {
+    float m, logS, H;
+};
+
+template <class Load>
+GD_POLICY_FN RowStats row_stats(int n, Load load) {
+    float m = load(0);
+    for (int k = 1; k < n; k++) {
+        const float l = load(k);
+        if (l > m) m = l;
+    }
+    float S = 0.f;
+    for (int k = 0; k < n; k++) S = S + expf(load(k) - m);
+    RowStats s;
+    s.m = m;
+    s.logS = logf(S);
+    float e = 0.f;
+    for (int k = 0; k < n; k++) {
+        const float q = (load(k) - m) - s.logS;
+        e = e + (q * expf(q));
+    }
+    s.H = -e;
+    return s;
+}
+
+// The training-side rule (gd_policy_evaluate): logprob and entropy of a GIVEN action a in [0, n).  Nothing is drawn.
+template <class Load>
+GD_POLICY_FN Draw evaluate(int n, Load load, int a) {
+    const RowStats s = row_stats(n, load);
+    Draw d;
+    d.action = a;
+    d.logprob = (load(a) - s.m) - s.logS;
+    d.entropy = s.H;
+    return d;
+}
+
 }  // namespace policy_rule
 }  // namespace gd

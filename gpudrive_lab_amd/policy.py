@@ -24,11 +24,17 @@ uniform u in [0, 1) per row -- the first k whose running sum of exp(l - max l), 
 The max-pools run over ALL A - 1 partner rows and all 200 road rows, padding rows included, as the reference's do.
 Observations must be finite.
 
-Not here: a bf16 or fp8 forward, the backward pass, the losses, LSTM state, GELU, `vbd_in_obs`, more than 1024 actions."""
+`TrainablePolicy` (below) is the training side: the same network as a differentiable torch module, its forward for given
+actions (`gd_policy_evaluate`) and its backward to parameter gradients (`gd_policy_backward`, csrc/policy_grad.hip) in HIP.
+
+Not here: a bf16 or fp8 forward, the losses, gradient clipping and the optimiser (the caller's torch code), a gradient with
+respect to the observations, LSTM state, GELU, `vbd_in_obs`, more than 1024 actions."""
 import ctypes as C
 
 import numpy as np
 import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _capi
 
@@ -60,10 +66,9 @@ def expected_shapes(ego_width, n_actions):
     return shapes
 
 
-def check_policy_args(state_dict, max_agents, ego_width, act_func="tanh", vbd_in_obs=False):
+def check_policy_args(state_dict, max_agents, ego_width, act_func="tanh", vbd_in_obs=False, who="DevicePolicy: "):
     """Everything `DevicePolicy` refuses, checked on the host before anything reaches the device (ValueError).  Returns
     n_actions."""
-    who = "DevicePolicy: "
     if act_func != "tanh":
         raise ValueError(who + "act_func %r is not built (tanh only)" % (act_func,))
     if vbd_in_obs:
@@ -247,3 +252,179 @@ class DevicePolicy:
                                                   out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(),
                                                   stream), "gd_policy_forward")
         return out
+
+
+DEFAULT_PARTIALS = 256
+MAX_PARTIALS = 1024
+ROWSTAT = 8         # floats per row of the backward's scratch (csrc/policy_grad.hip)
+_ALLOCATIONS = 64   # an upper bound on the tensors one forward plus backward allocates; torch rounds each up to 512 bytes
+
+
+def grad_floats(ego_width, n_actions):
+    """The number of parameters: the length of the flat gradient, in `expected_shapes` order."""
+    return sum(int(np.prod(s)) for s in expected_shapes(ego_width, n_actions).values())
+
+
+class _Evaluate(torch.autograd.Function):
+    """gd_policy_evaluate forward, gd_policy_backward backward.  What the backward needs beyond the inputs -- the flat
+    weights, the features, the logits and the pool winners -- belongs to this call's context, not to the module."""
+
+    @staticmethod
+    def forward(ctx, mod, obs, action, *params):
+        n, na, dev, f = int(obs.shape[0]), mod.n_actions, obs.device, torch.float32
+        L = _capi.lib()
+        with torch.no_grad():
+            flat = torch.cat([p.reshape(-1) for p in params] + [mod._zero])
+            blob = torch.index_select(flat, 0, mod._index)
+        features = torch.empty((n, FEATURES), dtype=f, device=dev)
+        logits = torch.empty((n, na), dtype=f, device=dev)
+        winners = torch.empty((n, 2 * INPUT_DIM), dtype=torch.uint8, device=dev)
+        logprob, entropy, value = (torch.empty(n, dtype=f, device=dev) for _ in range(3))
+        p, g = mod._structs(n, features, logits, winners)
+        p.blob, p.blob_floats = blob.data_ptr(), blob.numel()
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _capi.check(L.gd_policy_evaluate(C.byref(p), C.byref(g), obs.data_ptr(), action.data_ptr(), logprob.data_ptr(),
+                                             entropy.data_ptr(), value.data_ptr(), stream), "gd_policy_evaluate")
+        ctx.save_for_backward(obs, action, *params)  # (torch's version check then catches an optimiser step before backward)
+        ctx.mod, ctx.kept = mod, (flat, features, logits, winners)
+        return logprob, entropy, value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_logprob, d_entropy, d_value):
+        obs, action = ctx.saved_tensors[:2]
+        mod = ctx.mod
+        flat, features, logits, winners = ctx.kept
+        n, dev, f = int(obs.shape[0]), obs.device, torch.float32
+        ups = [d.to(f).contiguous() for d in (d_logprob, d_entropy, d_value)]
+        total = flat.numel() - 1
+        P = mod.partials
+        rowstat = torch.empty((n, ROWSTAT), dtype=f, device=dev)
+        partials = torch.empty((P, total), dtype=f, device=dev)
+        grad = torch.empty(total, dtype=f, device=dev)
+        p, g = mod._structs(n, features, logits, winners)
+        g.params, g.rowstat, g.partials = flat.data_ptr(), rowstat.data_ptr(), partials.data_ptr()
+        g.grad_floats, g.num_partials = total, P
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _capi.check(_capi.lib().gd_policy_backward(C.byref(p), C.byref(g), obs.data_ptr(), action.data_ptr(),
+                                                       ups[0].data_ptr(), ups[1].data_ptr(), ups[2].data_ptr(),
+                                                       grad.data_ptr(), stream), "gd_policy_backward")
+        views, o = [], 0
+        for shape in mod._shapes:
+            k = int(np.prod(shape))
+            views.append(grad[o:o + k].view(shape))
+            o += k
+        return (None, None, None) + tuple(views)
+
+
+class TrainablePolicy(nn.Module):
+    """The late-fusion actor-critic as a differentiable torch module whose forward for given actions and whose backward to
+    parameter gradients run in HIP: the step of the reference's update that `DeviceRollout.minibatch` feeds
+    (`data.policy(obs, action=atn)` under autograd and `loss.backward()`, gpudrive/integrations/puffer/ppo.py:261-332).
+
+        tp = TrainablePolicy.from_state_dict(net.state_dict(), max_agents=128, ego_width=6, device="cuda")
+        opt = torch.optim.Adam(tp.parameters(), lr=3e-4)
+        _, newlogprob, entropy, newvalue = tp(b_obs, b_actions)
+        loss = ...                                  # the reference's own lines, in torch
+        opt.zero_grad(); loss.backward(); torch.nn.utils.clip_grad_norm_(tp.parameters(), 0.5); opt.step()
+        pol.load_state_dict(tp.state_dict())        # the rollout's DevicePolicy follows
+
+    The parameters carry the reference module's key names and shapes, so `state_dict()` loads into and from the reference
+    `NeuralNet`, and any torch optimiser works.  The logits are bit-identical to `DevicePolicy`'s for the same weights and
+    observations, so evaluating the actions it sampled returns its logprob exactly: the first epoch's PPO ratio is 1.
+
+    NO DROPOUT.  `dropout` must be 0.0.  The reference trains in train mode with the puffer yaml's dropout 0.01 (1 % of the
+    embedder activations and of the hidden vector zeroed at random, the rest scaled by 1 / 0.99); this class does not
+    reproduce that noise, as `DevicePolicy` does not (its EVAL MODE note).  `.train()` and `.eval()` behave alike.
+
+    The max-pools pass a pooled feature's gradient to one entity, the lowest index among those that attain the float32
+    maximum (torch's `max(dim=1)` makes the same choice).  `obs` gets no gradient.
+
+    partials: P, the number of workgroups that sum over the rows (workgroup p takes rows p, p + P, ..) and of partial
+    gradients the last kernel adds in order.  The sums are deterministic for a given P.  The default, 256, is one workgroup
+    on each compute unit of an MI355X -- the kernel keeps its sums in registers and fits one workgroup to a unit, so more
+    adds reduction work and scratch (P times the parameters, 52 MB at 91 actions) but no parallelism; fewer rows than P
+    leaves the extra workgroups storing zeros."""
+
+    def __init__(self, state_dict, max_agents=128, ego_width=6, *, dropout=0.0, partials=None, device=None, act_func="tanh",
+                 vbd_in_obs=False):
+        super().__init__()
+        who = "TrainablePolicy: "
+        if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or dropout != 0.0:
+            raise ValueError(who + "dropout must be 0.0 (the kernels have no dropout), got %r" % (dropout,))
+        if partials is None:
+            partials = DEFAULT_PARTIALS
+        if not _is_int(partials) or not 1 <= partials <= MAX_PARTIALS:
+            raise ValueError(who + "partials must be an int in [1, %d], got %r" % (MAX_PARTIALS, partials))
+        self.n_actions = check_policy_args(state_dict, max_agents, ego_width, act_func, vbd_in_obs, who=who)
+        self.max_agents, self.ego_width, self.partials = max_agents, ego_width, partials
+        self.obs_width = obs_width(max_agents, ego_width)
+        if device is not None:
+            try:
+                device = torch.device(device)
+            except (RuntimeError, TypeError) as e:
+                raise ValueError(who + "device: %s" % e)
+        shapes = expected_shapes(ego_width, self.n_actions)
+        self._names, self._shapes = tuple(shapes), tuple(shapes.values())
+        for name in self._names:  # e.g. ego_embed.0.weight: plain containers under the reference's names
+            *path, leaf = name.split(".")
+            at = self
+            for part in path:
+                if part not in at._modules:
+                    at.add_module(part, nn.Module())
+                at = at._modules[part]
+            at.register_parameter(leaf, nn.Parameter(state_dict[name].detach().to(device=device, copy=True)))
+        self.register_buffer("_index", torch.from_numpy(pack_index(ego_width, self.n_actions)).to(device), persistent=False)
+        self.register_buffer("_zero", torch.zeros(1, dtype=torch.float32, device=device), persistent=False)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, max_agents=128, ego_width=6, **kw):
+        return cls(state_dict, max_agents, ego_width, **kw)
+
+    def _structs(self, n, features, logits, winners):
+        p, g = _capi.GdPolicy(), _capi.GdPolicyGrad()
+        p.num_rows, p.max_agents, p.ego_width, p.n_actions = n, self.max_agents, self.ego_width, self.n_actions
+        g.features, g.logits, g.winners = features.data_ptr(), logits.data_ptr(), winners.data_ptr()
+        return p, g
+
+    def nbytes(self, n):
+        """An upper bound on what one forward plus backward of n rows allocates, in bytes: n times the per-row share --
+        features, logits, the three outputs, the contiguous copies of their three upstream gradients, the backward's row
+        scratch, in float32, and 128 winner bytes -- plus a part that does not depend on n: the flat weights, the blob, the
+        flat gradient, `partials` times the gradient, the `.grad` tensors of a first backward, and the allocator's rounding."""
+        G = grad_floats(self.ego_width, self.n_actions)
+        per_row = 4 * (FEATURES + self.n_actions + 3 + 3 + ROWSTAT) + 2 * INPUT_DIM
+        fixed = 4 * ((G + 1) + int(self._index.numel()) + G + self.partials * G + G) + 512 * _ALLOCATIONS
+        return n * per_row + fixed
+
+    def forward(self, obs, action):
+        """obs [N, obs_width] float32 and action [N] int64, contiguous, on the parameters' GPU.  Returns (action, logprob,
+        entropy, value) like the reference's `forward(obs, action=atn)`; logprob, entropy and value [N] float32 are
+        differentiable with respect to the parameters (once).  An action outside [0, n_actions) is clamped into it, for
+        memory safety only.  Three launches on torch's current stream, and three more in the backward; no host
+        synchronisation.  Sampling is `DevicePolicy`'s: action is required."""
+        who = "TrainablePolicy: "
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[1] != self.obs_width:
+            raise ValueError(who + "obs must be a [N, %d] tensor (max_agents %d, ego_width %d)"
+                             % (self.obs_width, self.max_agents, self.ego_width))
+        if obs.requires_grad:
+            raise ValueError(who + "obs must not require grad (there is no gradient with respect to the observations)")
+        n = int(obs.shape[0])
+        if not 1 <= n <= MAX_ROWS:
+            raise ValueError(who + "N must be in [1, %d], got %d" % (MAX_ROWS, n))
+        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device.type != "cuda":
+            raise ValueError(who + "obs must be a contiguous float32 tensor on the GPU (there is no host path)")
+        if not isinstance(action, torch.Tensor) or action.dtype != torch.int64 or tuple(action.shape) != (n,) \
+                or action.device != obs.device or not action.is_contiguous() or action.requires_grad:
+            raise ValueError(who + "action must be a contiguous int64 tensor of shape (%d,) on %s" % (n, obs.device))
+        params = []
+        for name, shape in zip(self._names, self._shapes):
+            p = self.get_parameter(name)
+            if p.device != obs.device or p.dtype != torch.float32 or tuple(p.shape) != shape or not p.is_contiguous():
+                raise ValueError(who + "parameter %s must be a contiguous float32 tensor of shape %s on %s"
+                                 % (name, shape, obs.device))
+            params.append(p)
+        logprob, entropy, value = _Evaluate.apply(self, obs, action, *params)
+        return action, logprob, entropy, value

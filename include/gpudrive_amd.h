@@ -465,6 +465,49 @@ typedef struct gd_policy {
  * outside [1, 2^20], blob_floats not the layout's size, a misaligned pointer. */
 int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
                       float *logprob, float *entropy, float *value, float *logits_out, void *stream);
+/* Device policy backward: the training side of gd_policy -- the network's forward for GIVEN actions and its backward to
+ * parameter gradients (the reference's `data.policy(obs, action=atn)` under autograd and `loss.backward()`,
+ * gpudrive/integrations/puffer/ppo.py:261-332).  The loss arithmetic, advantage normalisation, gradient clipping and the
+ * optimiser stay with the caller.  Every pointer is a device pointer owned by the caller; G = grad_floats is the number of
+ * parameters; the flat layout of `params` and of `grad` is the state dict's: for ego, partner, road in turn W1 [64][K]
+ * (K = EW, 6, 13), b1 [64], LayerNorm weight [64] and bias [64], W2 [64][64], b2 [64]; then Ws [128][192], bs [128],
+ * Wa [NA][128], ba [NA], Wc [128], bc [1]; each row-major (gpudrive_lab_amd/policy.py `expected_shapes`). */
+typedef struct gd_policy_grad {
+    float *features;       /* [N][192], 16-byte aligned: written by evaluate, read by backward */
+    float *logits;         /* [N][NA]: written by evaluate, read by backward */
+    uint8_t *winners;      /* [N][128]: per pooled feature the entity that attained the max, 64 partner indices then 64 road
+                            * indices.  Written by evaluate, read by backward */
+    const float *params;   /* backward only: G floats, the weights in the flat layout above (the same values as p->blob) */
+    float *rowstat;        /* backward only: [N][8] scratch */
+    float *partials;       /* backward only: [num_partials][G] scratch */
+    int64_t grad_floats;   /* backward only: G, checked against the parameter count for (ego_width, n_actions) */
+    int32_t num_partials;  /* backward only: P, 1 .. 1024 */
+    int32_t reserved;
+} gd_policy_grad;
+/* The training-side forward: the network, the blob and the arithmetic of gd_policy_forward (the same two kernels, so the
+ * logits are bit-identical to its logits), then logprob and entropy of the GIVEN actions [N] int64 by the action rule's
+ * formulas (csrc/policy_rule.hpp `evaluate`; nothing is drawn): evaluating the actions a forward sampled returns that
+ * forward's logprob, entropy and value bit for bit.  An action outside [0, NA) is clamped into it, for memory safety only.
+ * p->features and p->logits are not used: features, logits and winners go to g's buffers, every byte written by every call.
+ * The winner of a pooled feature is the LOWEST entity index among the entities that attain the float32 maximum; padding rows
+ * take part, as in the forward.  For finite observations every winner is below the set's size (A - 1, 200).  A pooled feature
+ * that is NaN (non-finite observations are outside the contract) has no entity equal to its maximum: its winner is the
+ * sentinel 255, which gd_policy_backward clamps to the set's last entity, for memory safety only.  Three launches on `stream`, no host synchronisation, no allocation, no atomics.
+ * GD_ERR_INVALID: as gd_policy_forward, for p's ranges, null pointers and alignment. */
+int gd_policy_evaluate(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions, float *logprob,
+                       float *entropy, float *value, void *stream);
+/* The backward of one gd_policy_evaluate call with the same p, g, obs and actions: grad [G] float32 = the gradient, with
+ * respect to every parameter, of sum_r (d_logprob[r] logprob[r] + d_entropy[r] entropy[r] + d_value[r] value[r]), the three
+ * upstream gradients being float32 [N].  dlogits follow csrc/policy_grad_rule.hpp.  The max-pools pass a feature's gradient to
+ * its recorded winner alone; obs gets no gradient.  Every element of grad, rowstat and partials is stored by every call;
+ * nothing relies on a zeroed buffer.  The sums over rows are deterministic and use no atomics: workgroup p of P sums the rows
+ * p, p + P, .. in ascending order into partials[p], and grad[e] = partials[0][e] + partials[1][e] + .. in that order, so the
+ * bits depend on P but not on the run.  p->blob, p->features and p->logits are not used.  Three launches on `stream`, no host
+ * synchronisation, no allocation.
+ * GD_ERR_INVALID: a null pointer, p's ranges as in gd_policy_forward, num_partials outside [1, 1024], grad_floats not the
+ * parameter count, a misaligned pointer. */
+int gd_policy_backward(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
+                       const float *d_logprob, const float *d_entropy, const float *d_value, float *grad, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
