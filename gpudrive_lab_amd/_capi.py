@@ -175,13 +175,28 @@ class GdPolicyGrad(C.Structure):
                 [("grad_floats", C.c_int64), ("num_partials", C.c_int32), ("reserved", C.c_int32)])
 
 
+PPO_STATS = ("policy_loss", "value_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "grad_norm")  # gd_ppo.stats
+
+
+class GdPPO(C.Structure):
+    """gd_ppo: the hyper-parameters, the device scalars, the optimiser state and the scratch of the device PPO update (device
+    pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("num_rows", "ego_width", "n_actions", "norm_adv", "clip_vloss")] +
+                [(n, C.c_float) for n in ("clip_coef", "vf_clip_coef", "ent_coef", "vf_coef", "max_grad_norm", "eps",
+                                          "stats_scale")] +
+                [("beta1", C.c_double), ("beta2", C.c_double), ("grad_floats", C.c_int64), ("blob_floats", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("lr", "step", "beta_pow", "params", "exp_avg", "exp_avg_sq", "blob", "blob_of",
+                                           "stats", "stats_sum", "scal", "newlogprob", "entropy", "newvalue", "d_logprob",
+                                           "d_entropy", "d_value", "grad")])
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
     "gd_step", "gd_reset", "gd_set_maps", "gd_delete_agents", "gd_tensor", "gd_pack_observations", "gd_attach_packed",
     "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_il_future_batch",
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
-    "gd_policy_evaluate", "gd_policy_backward",
+    "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -260,6 +275,9 @@ def lib():
     L.gd_policy_forward.argtypes = [C.POINTER(GdPolicy), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
     L.gd_policy_evaluate.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad)] + [C.c_void_p] * 6
     L.gd_policy_backward.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad)] + [C.c_void_p] * 7
+    L.gd_ppo_loss.argtypes = [C.POINTER(GdPPO)] + [C.c_void_p] * 11
+    L.gd_ppo_adam.argtypes = [C.POINTER(GdPPO), C.c_void_p, C.c_void_p]
+    L.gd_ppo_update.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), C.POINTER(GdPPO)] + [C.c_void_p] * 7
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

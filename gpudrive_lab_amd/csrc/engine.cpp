@@ -1641,16 +1641,24 @@ static const char *policy_grad_problem(const gd_policy *p, const gd_policy_grad 
     return nullptr;
 }
 
+// everything gd_policy_evaluate refuses; nullptr when everything is in order
+static const char *policy_evaluate_problem(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
+                                           const float *logprob, const float *entropy, const float *value) {
+    if (!p || !g || !obs || !actions || !logprob || !entropy || !value) return "null argument";
+    if (const char *why = policy_grad_problem(p, g)) return why;
+    if (!p->blob) return "blob is required";
+    if (p->blob_floats != gd::policy_blob_floats(p->ego_width, p->n_actions))
+        return "blob_floats is not the layout's size for this ego_width and n_actions";
+    if (misaligned(p->blob, 16)) return "blob must be 16-byte aligned";
+    if (misaligned(actions, 8) || misaligned(obs, 4) || misaligned(logprob, 4) || misaligned(entropy, 4) || misaligned(value, 4))
+        return "actions must be 8-byte aligned, float buffers 4-byte aligned";
+    return nullptr;
+}
+
 int gd_policy_evaluate(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions, float *logprob,
                        float *entropy, float *value, void *stream) {
-    if (!p || !g || !obs || !actions || !logprob || !entropy || !value) return fail(GD_ERR_INVALID, "gd_policy_evaluate: null argument");
-    if (const char *why = policy_grad_problem(p, g)) return fail(GD_ERR_INVALID, std::string("gd_policy_evaluate: ") + why);
-    if (!p->blob) return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob is required");
-    if (p->blob_floats != gd::policy_blob_floats(p->ego_width, p->n_actions))
-        return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob_floats is not the layout's size for this ego_width and n_actions");
-    if (misaligned(p->blob, 16)) return fail(GD_ERR_INVALID, "gd_policy_evaluate: blob must be 16-byte aligned");
-    if (misaligned(actions, 8) || misaligned(obs, 4) || misaligned(logprob, 4) || misaligned(entropy, 4) || misaligned(value, 4))
-        return fail(GD_ERR_INVALID, "gd_policy_evaluate: actions must be 8-byte aligned, float buffers 4-byte aligned");
+    if (const char *why = policy_evaluate_problem(p, g, obs, actions, logprob, entropy, value))
+        return fail(GD_ERR_INVALID, std::string("gd_policy_evaluate: ") + why);
     return guarded([&]() {
         gd_policy q = *p;
         q.features = g->features, q.logits = g->logits;
@@ -1659,20 +1667,114 @@ int gd_policy_evaluate(const gd_policy *p, const gd_policy_grad *g, const float 
     });
 }
 
-int gd_policy_backward(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
-                       const float *d_logprob, const float *d_entropy, const float *d_value, float *grad, void *stream) {
-    if (!p || !g || !obs || !actions || !d_logprob || !d_entropy || !d_value || !grad)
-        return fail(GD_ERR_INVALID, "gd_policy_backward: null argument");
-    if (const char *why = policy_grad_problem(p, g)) return fail(GD_ERR_INVALID, std::string("gd_policy_backward: ") + why);
-    if (!g->params || !g->rowstat || !g->partials) return fail(GD_ERR_INVALID, "gd_policy_backward: params, rowstat and partials are required");
-    if (g->num_partials < 1 || g->num_partials > 1024) return fail(GD_ERR_INVALID, "gd_policy_backward: num_partials must be in [1, 1024]");
+// everything gd_policy_backward refuses; nullptr when everything is in order
+static const char *policy_backward_problem(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
+                                           const float *d_logprob, const float *d_entropy, const float *d_value,
+                                           const float *grad) {
+    if (!p || !g || !obs || !actions || !d_logprob || !d_entropy || !d_value || !grad) return "null argument";
+    if (const char *why = policy_grad_problem(p, g)) return why;
+    if (!g->params || !g->rowstat || !g->partials) return "params, rowstat and partials are required";
+    if (g->num_partials < 1 || g->num_partials > 1024) return "num_partials must be in [1, 1024]";
     if (g->grad_floats != gd::policy_grad_floats(p->ego_width, p->n_actions))
-        return fail(GD_ERR_INVALID, "gd_policy_backward: grad_floats is not the parameter count for this ego_width and n_actions");
+        return "grad_floats is not the parameter count for this ego_width and n_actions";
     if (misaligned(actions, 8) || misaligned(obs, 4) || misaligned(d_logprob, 4) || misaligned(d_entropy, 4) || misaligned(d_value, 4) ||
         misaligned(grad, 4) || misaligned(g->params, 4) || misaligned(g->rowstat, 4) || misaligned(g->partials, 4))
-        return fail(GD_ERR_INVALID, "gd_policy_backward: actions must be 8-byte aligned, float buffers 4-byte aligned");
+        return "actions must be 8-byte aligned, float buffers 4-byte aligned";
+    return nullptr;
+}
+
+int gd_policy_backward(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
+                       const float *d_logprob, const float *d_entropy, const float *d_value, float *grad, void *stream) {
+    if (const char *why = policy_backward_problem(p, g, obs, actions, d_logprob, d_entropy, d_value, grad))
+        return fail(GD_ERR_INVALID, std::string("gd_policy_backward: ") + why);
     return guarded([&]() {
         gd::launch_policy_backward(*p, *g, static_cast<hipStream_t>(stream), obs, actions, d_logprob, d_entropy, d_value, grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything gd_ppo_loss refuses; nullptr when everything is in order
+static const char *ppo_loss_problem(const gd_ppo *o, const float *newlogprob, const float *entropy, const float *newvalue,
+                                    const float *old_logprob, const float *old_value, const float *adv, const float *ret,
+                                    const float *d_logprob, const float *d_entropy, const float *d_value) {
+    if (!o || !newlogprob || !entropy || !newvalue || !old_logprob || !old_value || !adv || !ret || !d_logprob || !d_entropy ||
+        !d_value)
+        return "null argument";
+    if (o->num_rows < 1 || o->num_rows > (1 << 20)) return "num_rows must be in [1, 2^20]";
+    if (o->norm_adv && o->num_rows < 2) return "norm_adv needs at least two rows (the unbiased variance of one is undefined)";
+    if (!o->stats || !o->stats_sum) return "stats and stats_sum are required";
+    if (misaligned(newlogprob, 4) || misaligned(entropy, 4) || misaligned(newvalue, 4) || misaligned(old_logprob, 4) ||
+        misaligned(old_value, 4) || misaligned(adv, 4) || misaligned(ret, 4) || misaligned(d_logprob, 4) ||
+        misaligned(d_entropy, 4) || misaligned(d_value, 4) || misaligned(o->stats, 4) || misaligned(o->stats_sum, 4))
+        return "float buffers must be 4-byte aligned";
+    return nullptr;
+}
+
+int gd_ppo_loss(const gd_ppo *ppo, const float *newlogprob, const float *entropy, const float *newvalue, const float *old_logprob,
+                const float *old_value, const float *adv, const float *ret, float *d_logprob, float *d_entropy, float *d_value,
+                void *stream) {
+    if (const char *why = ppo_loss_problem(ppo, newlogprob, entropy, newvalue, old_logprob, old_value, adv, ret, d_logprob, d_entropy,
+                                           d_value))
+        return fail(GD_ERR_INVALID, std::string("gd_ppo_loss: ") + why);
+    return guarded([&]() {
+        gd::launch_ppo_loss(*ppo, static_cast<hipStream_t>(stream), newlogprob, entropy, newvalue, old_logprob, old_value, adv, ret,
+                            d_logprob, d_entropy, d_value);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything gd_ppo_adam refuses; nullptr when everything is in order
+static const char *ppo_adam_problem(const gd_ppo *o, const float *grad) {
+    if (!o || !grad) return "null argument";
+    if (o->ego_width != 6 && o->ego_width != 9) return "ego_width must be 6 or 9";
+    if (o->n_actions < 1 || o->n_actions > 1024) return "n_actions must be in [1, 1024]";
+    if (o->grad_floats != gd::policy_grad_floats(o->ego_width, o->n_actions))
+        return "grad_floats is not the parameter count for this ego_width and n_actions";
+    if (o->blob_floats != gd::policy_blob_floats(o->ego_width, o->n_actions))
+        return "blob_floats is not the layout's size for this ego_width and n_actions";
+    if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0)) return "betas must be in [0, 1)";
+    if (!(o->eps > 0.f) || !(o->max_grad_norm > 0.f)) return "eps and max_grad_norm must be positive";
+    if (!o->lr || !o->step || !o->beta_pow || !o->params || !o->exp_avg || !o->exp_avg_sq || !o->blob || !o->blob_of || !o->stats ||
+        !o->stats_sum || !o->scal)
+        return "lr, step, beta_pow, params, exp_avg, exp_avg_sq, blob, blob_of, stats, stats_sum and scal are required";
+    if (misaligned(o->beta_pow, 8) || misaligned(grad, 4) || misaligned(o->lr, 4) || misaligned(o->step, 4) || misaligned(o->params, 4) ||
+        misaligned(o->exp_avg, 4) || misaligned(o->exp_avg_sq, 4) || misaligned(o->blob, 4) || misaligned(o->blob_of, 4) ||
+        misaligned(o->stats, 4) || misaligned(o->stats_sum, 4) || misaligned(o->scal, 4))
+        return "beta_pow must be 8-byte aligned, the other buffers 4-byte aligned";
+    return nullptr;
+}
+
+int gd_ppo_adam(const gd_ppo *ppo, const float *grad, void *stream) {
+    if (const char *why = ppo_adam_problem(ppo, grad)) return fail(GD_ERR_INVALID, std::string("gd_ppo_adam: ") + why);
+    return guarded([&]() {
+        gd::launch_ppo_adam(*ppo, static_cast<hipStream_t>(stream), grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs, const int64_t *actions,
+                  const float *old_logprob, const float *old_value, const float *adv, const float *ret, void *stream) {
+    if (!p || !g || !ppo) return fail(GD_ERR_INVALID, "gd_ppo_update: null argument");
+    const gd_ppo &o = *ppo;
+    const char *why = policy_evaluate_problem(p, g, obs, actions, o.newlogprob, o.entropy, o.newvalue);
+    if (!why) why = ppo_loss_problem(ppo, o.newlogprob, o.entropy, o.newvalue, old_logprob, old_value, adv, ret, o.d_logprob,
+                                     o.d_entropy, o.d_value);
+    if (!why) why = policy_backward_problem(p, g, obs, actions, o.d_logprob, o.d_entropy, o.d_value, o.grad);
+    if (!why) why = ppo_adam_problem(ppo, o.grad);
+    if (!why && (p->num_rows != o.num_rows || p->ego_width != o.ego_width || p->n_actions != o.n_actions))
+        why = "num_rows, ego_width and n_actions of the policy and of ppo differ";
+    if (!why && (p->blob != o.blob || g->params != o.params))
+        why = "the policy's blob and params must be ppo's (the optimiser step updates both in place)";
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_ppo_update: ") + why);
+    return guarded([&]() {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        gd_policy q = *p;
+        q.features = g->features, q.logits = g->logits;
+        gd::launch_policy_evaluate(q, st, obs, actions, g->winners, o.newlogprob, o.entropy, o.newvalue);
+        gd::launch_ppo_loss(o, st, o.newlogprob, o.entropy, o.newvalue, old_logprob, old_value, adv, ret, o.d_logprob, o.d_entropy,
+                            o.d_value);
+        gd::launch_policy_backward(*p, *g, st, obs, actions, o.d_logprob, o.d_entropy, o.d_value, o.grad);
+        gd::launch_ppo_adam(o, st, o.grad);
         HIP_CHECK(hipGetLastError());
     });
 }

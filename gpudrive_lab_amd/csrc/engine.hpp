@@ -250,5 +250,9 @@ void launch_policy_evaluate(const gd_policy &p, hipStream_t st, const float *obs
 long long policy_grad_floats(int ego_width, int n_actions);  // policy_grad.hip: the size of the flat parameter gradient
 void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, hipStream_t st, const float *obs, const int64_t *actions,
                             const float *d_logprob, const float *d_entropy, const float *d_value, float *grad);  // policy_grad.hip
+void launch_ppo_loss(const gd_ppo &o, hipStream_t st, const float *newlogprob, const float *entropy, const float *newvalue,
+                     const float *old_logprob, const float *old_value, const float *adv, const float *ret, float *d_logprob,
+                     float *d_entropy, float *d_value);  // ppo.hip (one launch)
+void launch_ppo_adam(const gd_ppo &o, hipStream_t st, const float *grad);  // ppo.hip (two launches)
 
 }  // namespace gd

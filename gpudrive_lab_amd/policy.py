@@ -27,8 +27,9 @@ Observations must be finite.
 `TrainablePolicy` (below) is the training side: the same network as a differentiable torch module, its forward for given
 actions (`gd_policy_evaluate`) and its backward to parameter gradients (`gd_policy_backward`, csrc/policy_grad.hip) in HIP.
 
-Not here: a bf16 or fp8 forward, the losses, gradient clipping and the optimiser (the caller's torch code), a gradient with
-respect to the observations, LSTM state, GELU, `vbd_in_obs`, more than 1024 actions."""
+Not here: a bf16 or fp8 forward, a gradient with respect to the observations, LSTM state, GELU, `vbd_in_obs`, more than 1024
+actions.  The losses, gradient clipping and the optimiser on the device are `gpudrive_lab_amd.ppo.DevicePPO` (ppo.py), which
+runs the whole minibatch update as one C call; `TrainablePolicy` remains for callers who write those lines in torch."""
 import ctypes as C
 
 import numpy as np

@@ -23,7 +23,8 @@ The loop:
 Environment i of the reference's `env_id` is row i (pufferlib's `PufferEnv.recv` hands a native environment `range(N)`).
 
 Not here: the LSTM state, `cpu_offload`, `returns_np` (the reference adds sorted advantages to unsorted values there,
-ppo.py:660: a logging quirk, not a training input), and the training loop, losses and logging themselves."""
+ppo.py:660: a logging quirk, not a training input) and logging.  The training loop and the losses over these minibatches are
+`gpudrive_lab_amd.ppo.DevicePPO.train` (ppo.py)."""
 import ctypes as C
 
 import numpy as np

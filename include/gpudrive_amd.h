@@ -508,6 +508,65 @@ int gd_policy_evaluate(const gd_policy *p, const gd_policy_grad *g, const float 
  * parameter count, a misaligned pointer. */
 int gd_policy_backward(const gd_policy *p, const gd_policy_grad *g, const float *obs, const int64_t *actions,
                        const float *d_logprob, const float *d_entropy, const float *d_value, float *grad, void *stream);
+/* Device PPO update: the rest of one minibatch update around gd_policy_evaluate and gd_policy_backward -- the reference's loss
+ * with its three upstream gradients, clip_grad_norm_ and Adam (gpudrive/integrations/puffer/ppo.py:282-332).  The rule, with
+ * every rounding and the order of every sum, is csrc/ppo_rule.hpp.  Every pointer is a device pointer owned by the caller, and
+ * every value that changes between calls (the learning rate, the step count, the running products of the betas) lives on the
+ * device, so a sequence of calls never depends on a host value that changes.  G = grad_floats, M = num_rows. */
+typedef struct gd_ppo {
+    int32_t num_rows;       /* M, 1 .. 2^20 (at least 2 with norm_adv) */
+    int32_t ego_width;      /* 6 or 9: with n_actions it fixes G and the blob's size */
+    int32_t n_actions;      /* 1 .. 1024 */
+    int32_t norm_adv;       /* != 0: advantages normalised per minibatch */
+    int32_t clip_vloss;     /* != 0: the clipped value loss */
+    float clip_coef, vf_clip_coef, ent_coef, vf_coef;
+    float max_grad_norm;    /* > 0 */
+    float eps;              /* Adam's, > 0 */
+    float stats_scale;      /* every call adds stats_scale * its statistics into stats_sum */
+    double beta1, beta2;    /* in [0, 1) */
+    int64_t grad_floats;    /* G, checked against the parameter count for (ego_width, n_actions) */
+    int64_t blob_floats;    /* checked against the layout's size */
+    const float *lr;        /* [1] the learning rate */
+    int32_t *step;          /* [1] optimiser steps taken */
+    double *beta_pow;       /* [2] beta1^step, beta2^step (1, 1 before the first step), 8-byte aligned */
+    float *params;          /* [G + 1] the weights in gd_policy_grad's flat layout; element G is a zero nobody writes */
+    float *exp_avg;         /* [G] Adam's first moment */
+    float *exp_avg_sq;      /* [G] Adam's second moment */
+    float *blob;            /* gd_policy.blob: every updated weight is stored here too; padding entries are never written */
+    const int32_t *blob_of; /* [G] blob_of[e]: the one place of parameter e in blob (the inverse of the layout) */
+    float *stats;           /* [7] the last call's policy_loss, value_loss, entropy, old_approx_kl, approx_kl, clipfrac
+                             * (gd_ppo_loss) and grad_norm (gd_ppo_adam) */
+    float *stats_sum;       /* [7] running sums of stats_scale * stats; the caller zeroes them when it reads them */
+    float *scal;            /* [4] scratch of gd_ppo_adam: total, coef, bc1, rbc2 from its first launch to its second */
+    /* scratch of gd_ppo_update only: */
+    float *newlogprob, *entropy, *newvalue;   /* [M] each: what gd_policy_evaluate returns */
+    float *d_logprob, *d_entropy, *d_value;   /* [M] each: the upstream gradients */
+    float *grad;                              /* [G] the gradient */
+} gd_ppo;
+/* The loss: from newlogprob, entropy, newvalue (gd_policy_evaluate's outputs), the stored old_logprob and old_value, the
+ * advantages and the returns, all [M] float32, the upstream gradients d_logprob, d_entropy, d_value [M] float32 of
+ * mean(pg) - ent_coef mean(entropy) + vf_coef v_loss (every element stored), stats[0..6), and stats_scale * stats added into
+ * stats_sum[0..6).  One launch on `stream` (a single workgroup: the sums have one fixed order), no host synchronisation, no
+ * allocation, no atomics.  Uses of ppo: the hyper-parameters, num_rows, stats, stats_sum.
+ * GD_ERR_INVALID: a null pointer, num_rows outside [1, 2^20], num_rows < 2 with norm_adv, a misaligned pointer. */
+int gd_ppo_loss(const gd_ppo *ppo, const float *newlogprob, const float *entropy, const float *newvalue, const float *old_logprob,
+                const float *old_value, const float *adv, const float *ret, float *d_logprob, float *d_entropy, float *d_value,
+                void *stream);
+/* Gradient clipping and one Adam step on grad [G] float32: the norm, the coefficient, the moments and the weights by the rule;
+ * each updated weight is stored to params[e] and to blob[blob_of[e]] by the same lane, so the forward's packed weights follow
+ * without a re-pack; stats[6] = the norm before clipping (and stats_sum[6]); step and beta_pow advance by one.  Two launches on
+ * `stream`: the first (one workgroup) leaves the step's scalars in scal, the second (a lane per parameter) reads them.  No
+ * host synchronisation, no allocation, no atomics.
+ * GD_ERR_INVALID: a null pointer, ego_width not 6 or 9, n_actions outside [1, 1024], grad_floats or blob_floats not the
+ * layout's, betas outside [0, 1), eps or max_grad_norm not positive, a misaligned pointer. */
+int gd_ppo_adam(const gd_ppo *ppo, const float *grad, void *stream);
+/* One whole minibatch update as one call: gd_policy_evaluate(p, g, obs, actions) into ppo's row scratch, gd_ppo_loss,
+ * gd_policy_backward into ppo->grad, gd_ppo_adam -- nine launches on `stream`, no host synchronisation, no allocation, no
+ * atomics; the results are bit for bit those of the four calls.  p->blob must be ppo->blob, g->params ppo->params, and the sizes
+ * of p, g and ppo must agree.
+ * GD_ERR_INVALID: whatever the four calls refuse, or a disagreement between p, g and ppo; before any launch. */
+int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs, const int64_t *actions,
+                  const float *old_logprob, const float *old_value, const float *adv, const float *ret, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
