@@ -190,6 +190,12 @@ class GdPPO(C.Structure):
                                            "d_entropy", "d_value", "grad")])
 
 
+class GdDropout(C.Structure):
+    """gd_dropout: the seed, the device call counter, the word evaluate leaves for backward, the threshold and the scale of
+    the training-mode masks (csrc/dropout_rule.hpp)."""
+    _fields_ = [("seed", C.c_uint64), ("call", C.c_void_p), ("used", C.c_void_p), ("threshold", C.c_uint32), ("scale", C.c_float)]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -197,6 +203,7 @@ SYMBOLS = [
     "gd_expert_actions", "gd_advance_log_playback", "gd_record_expert", "gd_il_index", "gd_il_batch", "gd_il_future_batch",
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
+    "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -278,6 +285,11 @@ def lib():
     L.gd_ppo_loss.argtypes = [C.POINTER(GdPPO)] + [C.c_void_p] * 11
     L.gd_ppo_adam.argtypes = [C.POINTER(GdPPO), C.c_void_p, C.c_void_p]
     L.gd_ppo_update.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), C.POINTER(GdPPO)] + [C.c_void_p] * 7
+    D = C.POINTER(GdDropout)
+    L.gd_policy_forward_dropout.argtypes = [C.POINTER(GdPolicy), D, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+    L.gd_policy_evaluate_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), D] + [C.c_void_p] * 6
+    L.gd_policy_backward_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), D] + [C.c_void_p] * 7
+    L.gd_ppo_update_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), C.POINTER(GdPPO), D] + [C.c_void_p] * 7
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -1607,22 +1607,29 @@ int gd_rollout_gather(const gd_rollout *ro, const gd_rollout_batch *b, void *str
     });
 }
 
-int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
-                      float *logprob, float *entropy, float *value, float *logits_out, void *stream) {
-    if (!p || !obs || !actions || !logprob || !entropy || !value || (!u && !deterministic))
-        return fail(GD_ERR_INVALID, "gd_policy_forward: null argument");
-    if (p->max_agents != 64 && p->max_agents != 128) return fail(GD_ERR_INVALID, "gd_policy_forward: max_agents must be 64 or 128");
-    if (p->ego_width != 6 && p->ego_width != 9) return fail(GD_ERR_INVALID, "gd_policy_forward: ego_width must be 6 or 9");
-    if (p->n_actions < 1 || p->n_actions > 1024) return fail(GD_ERR_INVALID, "gd_policy_forward: n_actions must be in [1, 1024]");
-    if (p->num_rows < 1 || p->num_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_policy_forward: num_rows must be in [1, 2^20]");
-    if (!p->blob || !p->features || !p->logits) return fail(GD_ERR_INVALID, "gd_policy_forward: blob, features and logits are required");
+// everything gd_policy_forward refuses; nullptr when everything is in order
+static const char *policy_forward_problem(const gd_policy *p, const float *obs, const float *u, int32_t deterministic,
+                                          const int64_t *actions, const float *logprob, const float *entropy, const float *value,
+                                          const float *logits_out) {
+    if (!p || !obs || !actions || !logprob || !entropy || !value || (!u && !deterministic)) return "null argument";
+    if (p->max_agents != 64 && p->max_agents != 128) return "max_agents must be 64 or 128";
+    if (p->ego_width != 6 && p->ego_width != 9) return "ego_width must be 6 or 9";
+    if (p->n_actions < 1 || p->n_actions > 1024) return "n_actions must be in [1, 1024]";
+    if (p->num_rows < 1 || p->num_rows > (1 << 20)) return "num_rows must be in [1, 2^20]";
+    if (!p->blob || !p->features || !p->logits) return "blob, features and logits are required";
     if (p->blob_floats != gd::policy_blob_floats(p->ego_width, p->n_actions))
-        return fail(GD_ERR_INVALID, "gd_policy_forward: blob_floats is not the layout's size for this ego_width and n_actions");
-    if (misaligned(p->blob, 16) || misaligned(p->features, 16))
-        return fail(GD_ERR_INVALID, "gd_policy_forward: blob and features must be 16-byte aligned");
+        return "blob_floats is not the layout's size for this ego_width and n_actions";
+    if (misaligned(p->blob, 16) || misaligned(p->features, 16)) return "blob and features must be 16-byte aligned";
     if (misaligned(actions, 8) || misaligned(obs, 4) || (u && misaligned(u, 4)) || misaligned(p->logits, 4) || misaligned(logprob, 4) ||
         misaligned(entropy, 4) || misaligned(value, 4) || (logits_out && misaligned(logits_out, 4)))
-        return fail(GD_ERR_INVALID, "gd_policy_forward: actions must be 8-byte aligned, float buffers 4-byte aligned");
+        return "actions must be 8-byte aligned, float buffers 4-byte aligned";
+    return nullptr;
+}
+
+int gd_policy_forward(const gd_policy *p, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
+                      float *logprob, float *entropy, float *value, float *logits_out, void *stream) {
+    if (const char *why = policy_forward_problem(p, obs, u, deterministic, actions, logprob, entropy, value, logits_out))
+        return fail(GD_ERR_INVALID, std::string("gd_policy_forward: ") + why);
     return guarded([&]() {
         gd::launch_policy_forward(*p, static_cast<hipStream_t>(stream), obs, u, deterministic != 0, actions, logprob, entropy, value,
                                   logits_out);
@@ -1752,9 +1759,10 @@ int gd_ppo_adam(const gd_ppo *ppo, const float *grad, void *stream) {
     });
 }
 
-int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs, const int64_t *actions,
-                  const float *old_logprob, const float *old_value, const float *adv, const float *ret, void *stream) {
-    if (!p || !g || !ppo) return fail(GD_ERR_INVALID, "gd_ppo_update: null argument");
+// everything gd_ppo_update refuses of non-null p, g and ppo; nullptr when everything is in order
+static const char *ppo_update_problem(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs,
+                                      const int64_t *actions, const float *old_logprob, const float *old_value, const float *adv,
+                                      const float *ret) {
     const gd_ppo &o = *ppo;
     const char *why = policy_evaluate_problem(p, g, obs, actions, o.newlogprob, o.entropy, o.newvalue);
     if (!why) why = ppo_loss_problem(ppo, o.newlogprob, o.entropy, o.newvalue, old_logprob, old_value, adv, ret, o.d_logprob,
@@ -1765,7 +1773,15 @@ int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo
         why = "num_rows, ego_width and n_actions of the policy and of ppo differ";
     if (!why && (p->blob != o.blob || g->params != o.params))
         why = "the policy's blob and params must be ppo's (the optimiser step updates both in place)";
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_ppo_update: ") + why);
+    return why;
+}
+
+int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs, const int64_t *actions,
+                  const float *old_logprob, const float *old_value, const float *adv, const float *ret, void *stream) {
+    if (!p || !g || !ppo) return fail(GD_ERR_INVALID, "gd_ppo_update: null argument");
+    const gd_ppo &o = *ppo;
+    if (const char *why = ppo_update_problem(p, g, ppo, obs, actions, old_logprob, old_value, adv, ret))
+        return fail(GD_ERR_INVALID, std::string("gd_ppo_update: ") + why);
     return guarded([&]() {
         hipStream_t st = static_cast<hipStream_t>(stream);
         gd_policy q = *p;
@@ -1774,6 +1790,77 @@ int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo
         gd::launch_ppo_loss(o, st, o.newlogprob, o.entropy, o.newvalue, old_logprob, old_value, adv, ret, o.d_logprob, o.d_entropy,
                             o.d_value);
         gd::launch_policy_backward(*p, *g, st, obs, actions, o.d_logprob, o.d_entropy, o.d_value, o.grad);
+        gd::launch_ppo_adam(o, st, o.grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything the *_dropout calls refuse of d; nullptr when everything is in order
+static const char *dropout_problem(const gd_dropout *d) {
+    if (!d->call || !d->used) return "dropout: call and used are required";
+    if (misaligned(d->call, 8) || misaligned(d->used, 8)) return "dropout: call and used must be 8-byte aligned";
+    if (d->threshold < 1 || d->threshold > 65535) return "dropout: threshold must be in [1, 65535]";
+    if (!std::isfinite(d->scale)) return "dropout: scale must be finite";
+    return nullptr;
+}
+
+int gd_policy_forward_dropout(const gd_policy *p, const gd_dropout *d, const float *obs, const float *u, int32_t deterministic,
+                              int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out, void *stream) {
+    if (!d) return gd_policy_forward(p, obs, u, deterministic, actions, logprob, entropy, value, logits_out, stream);
+    const char *why = policy_forward_problem(p, obs, u, deterministic, actions, logprob, entropy, value, logits_out);
+    if (!why) why = dropout_problem(d);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_policy_forward_dropout: ") + why);
+    return guarded([&]() {
+        gd::launch_policy_forward(*p, *d, static_cast<hipStream_t>(stream), obs, u, deterministic != 0, actions, logprob, entropy,
+                                  value, logits_out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_policy_evaluate_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_dropout *d, const float *obs,
+                               const int64_t *actions, float *logprob, float *entropy, float *value, void *stream) {
+    if (!d) return gd_policy_evaluate(p, g, obs, actions, logprob, entropy, value, stream);
+    const char *why = policy_evaluate_problem(p, g, obs, actions, logprob, entropy, value);
+    if (!why) why = dropout_problem(d);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_policy_evaluate_dropout: ") + why);
+    return guarded([&]() {
+        gd_policy q = *p;
+        q.features = g->features, q.logits = g->logits;
+        gd::launch_policy_evaluate(q, *d, static_cast<hipStream_t>(stream), obs, actions, g->winners, logprob, entropy, value);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_policy_backward_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_dropout *d, const float *obs,
+                               const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
+                               float *grad, void *stream) {
+    if (!d) return gd_policy_backward(p, g, obs, actions, d_logprob, d_entropy, d_value, grad, stream);
+    const char *why = policy_backward_problem(p, g, obs, actions, d_logprob, d_entropy, d_value, grad);
+    if (!why) why = dropout_problem(d);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_policy_backward_dropout: ") + why);
+    return guarded([&]() {
+        gd::launch_policy_backward(*p, *g, *d, static_cast<hipStream_t>(stream), obs, actions, d_logprob, d_entropy, d_value, grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const gd_dropout *d, const float *obs,
+                          const int64_t *actions, const float *old_logprob, const float *old_value, const float *adv,
+                          const float *ret, void *stream) {
+    if (!d) return gd_ppo_update(p, g, ppo, obs, actions, old_logprob, old_value, adv, ret, stream);
+    if (!p || !g || !ppo) return fail(GD_ERR_INVALID, "gd_ppo_update_dropout: null argument");
+    const gd_ppo &o = *ppo;
+    const char *why = ppo_update_problem(p, g, ppo, obs, actions, old_logprob, old_value, adv, ret);
+    if (!why) why = dropout_problem(d);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_ppo_update_dropout: ") + why);
+    return guarded([&]() {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        gd_policy q = *p;
+        q.features = g->features, q.logits = g->logits;
+        gd::launch_policy_evaluate(q, *d, st, obs, actions, g->winners, o.newlogprob, o.entropy, o.newvalue);
+        gd::launch_ppo_loss(o, st, o.newlogprob, o.entropy, o.newvalue, old_logprob, old_value, adv, ret, o.d_logprob, o.d_entropy,
+                            o.d_value);
+        gd::launch_policy_backward(*p, *g, *d, st, obs, actions, o.d_logprob, o.d_entropy, o.d_value, o.grad);
         gd::launch_ppo_adam(o, st, o.grad);
         HIP_CHECK(hipGetLastError());
     });

@@ -247,6 +247,15 @@ void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs,
                            int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out);  // policy.hip
 void launch_policy_evaluate(const gd_policy &p, hipStream_t st, const float *obs, const int64_t *actions, unsigned char *winners,
                             float *logprob, float *entropy, float *value);  // policy.hip; p.features, p.logits: the saved buffers
+// the training-mode masks of dropout_rule.hpp: the same launches on the DROP instantiations
+void launch_policy_forward(const gd_policy &p, const gd_dropout &d, hipStream_t st, const float *obs, const float *u,
+                           bool deterministic, int64_t *actions, float *logprob, float *entropy, float *value,
+                           float *logits_out);  // policy.hip
+void launch_policy_evaluate(const gd_policy &p, const gd_dropout &d, hipStream_t st, const float *obs, const int64_t *actions,
+                            unsigned char *winners, float *logprob, float *entropy, float *value);  // policy.hip
+void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, const gd_dropout &d, hipStream_t st, const float *obs,
+                            const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
+                            float *grad);  // policy_grad.hip
 long long policy_grad_floats(int ego_width, int n_actions);  // policy_grad.hip: the size of the flat parameter gradient
 void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, hipStream_t st, const float *obs, const int64_t *actions,
                             const float *d_logprob, const float *d_entropy, const float *d_value, float *grad);  // policy_grad.hip

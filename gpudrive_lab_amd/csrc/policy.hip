@@ -16,14 +16,27 @@
 // The weights come packed in lane order (gd_policy.blob; the layout is PolicyLayout below and gpudrive_lab_amd/policy.py).
 // An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation
 // (-ffp-contract=off).  No LDS, no atomics; every byte of every output is stored on every call.
+// Training-mode dropout (gd_policy_forward_dropout, gd_policy_evaluate_dropout) is the same three launches on the DROP
+// instantiations of k_policy_embed and k_policy_tail, which mask the four sites by dropout_rule.hpp, and on k_policy_sample_drop /
+// k_policy_evaluate_drop, which also advance the call index; without DROP the code is unchanged.
 #include <hip/hip_runtime.h>
 
+#include "dropout_rule.hpp"
 #include "engine.hpp"
 #include "policy_rule.hpp"
 
 namespace gd {
 
 namespace {
+
+namespace DR = dropout_rule;
+
+// DROP: the training-mode mask of one call (dropout_rule.hpp); `call` is the value of gd_dropout.call the kernel read
+struct DropCall {
+    DR::Args a;
+    uint64_t call;
+    uint32_t row;
+};
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -62,11 +75,13 @@ __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >
 // whose float32 output equals the pooled maximum.  A lane keeps, per accumulator register, the first entity tile (0..6) that
 // raised its running max -- 3 bits, 8 registers to a dword -- so the index is tile * 32 + lane; the lanes that hold the wave's
 // maximum then take the minimum of their indices.  The value path is the same instructions with and without REC.
-template <int K, int KS, bool REC>
+// DROP: the tanh outputs are masked before the second layer -- per (t, m) one Philox call covers the registers 8 m .. 8 m + 7 of
+// a[t] (dropout_rule.hpp), four calls per lane and entity tile; winners are then recorded on the masked outputs.
+template <int K, int KS, bool REC, bool DROP>
 __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int count, const float *__restrict__ w1a,
                                            const float *__restrict__ b1, const float *__restrict__ g, const float *__restrict__ be,
                                            const float *__restrict__ w2a, const float *__restrict__ b2, float *__restrict__ out,
-                                           unsigned char *__restrict__ win, int lane) {
+                                           unsigned char *__restrict__ win, int lane, const DropCall &dc, uint32_t site) {
     const int h = lane >> 5, col = lane & 31;
     float w1[2][KS], w2[2][32];
 #pragma unroll
@@ -122,6 +137,16 @@ __device__ __forceinline__ void embed_pool(const float *__restrict__ x, int coun
                 const int f = 32 * t + acc_row(r, h);
                 a[t][r] = tanhf((a[t][r] * rstd) * g[f] + be[f]);
             }
+        if constexpr (DROP) {
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+#pragma unroll
+                for (int m = 0; m < 2; m++) {
+                    const DR::Out o = DR::draw(dc.a.seed, dc.call, dc.row, site, (uint32_t)e, (uint32_t)((((t << 1) | m) << 1) | h));
+#pragma unroll
+                    for (int k = 0; k < 8; k++) a[t][8 * m + k] = DR::apply(a[t][8 * m + k], DR::kept(o, k, dc.a.threshold), dc.a.scale);
+                }
+        }
         f16v o[2];
 #pragma unroll
         for (int t2 = 0; t2 < 2; t2++) {
@@ -174,12 +199,16 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-template <bool REC>
+// DROP: da and callp are the rule's values and the device word that holds the call index; without DROP they are not read
+template <bool REC, bool DROP>
 __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
-                                                      float *__restrict__ features, unsigned char *__restrict__ winners) {
+                                                      float *__restrict__ features, unsigned char *__restrict__ winners,
+                                                      DR::Args da, const uint64_t *__restrict__ callp) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= p.num_rows) return;  // wave-uniform; nothing below synchronises across waves
+    DropCall dc{da, 0, (uint32_t)row};
+    if constexpr (DROP) dc.call = *callp;
     const int partners = p.max_agents - 1, ew = p.ego_width;
     const size_t width = (size_t)ew + (size_t)PARTNER_K * partners + (size_t)ROAD_K * ROADS;
     const float *__restrict__ x = obs + (size_t)row * width;
@@ -193,21 +222,26 @@ __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout 
         const float mean = wave_sum(a) * (1.f / 64.f);
         const float d = a - mean;
         const float rstd = 1.f / sqrtf(wave_sum(d * d) * (1.f / 64.f) + LN_EPS);
-        const float t = tanhf((d * rstd) * w[L.ego_g + lane] + w[L.ego_b + lane]);
+        float t = tanhf((d * rstd) * w[L.ego_g + lane] + w[L.ego_b + lane]);
+        if constexpr (DROP)
+            t = DR::apply(t, DR::kept(dc.a.seed, dc.call, dc.row, DR::SITE_EGO, 0, lane, dc.a.threshold), dc.a.scale);
         float o = w[L.ego_b2 + lane];
         for (int f = 0; f < F; f++) o = o + w[L.ego_w2t + f * F + lane] * __shfl(t, f);
         out[lane] = o;
     }
     unsigned char *__restrict__ win = REC ? winners + (size_t)row * (2 * F) : nullptr;
-    embed_pool<PARTNER_K, 3, REC>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0],
-                                  w + L.emb_w2[0], w + L.emb_b2[0], out + F, win, lane);
-    embed_pool<ROAD_K, 7, REC>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1],
-                               w + L.emb_b[1], w + L.emb_w2[1], w + L.emb_b2[1], out + 2 * F, REC ? win + F : nullptr, lane);
+    embed_pool<PARTNER_K, 3, REC, DROP>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0],
+                                        w + L.emb_w2[0], w + L.emb_b2[0], out + F, win, lane, dc, DR::SITE_PARTNER);
+    embed_pool<ROAD_K, 7, REC, DROP>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1],
+                                     w + L.emb_b[1], w + L.emb_w2[1], w + L.emb_b2[1], out + 2 * F, REC ? win + F : nullptr, lane, dc,
+                                     DR::SITE_ROAD);
 }
 
+// DROP: hidden is masked after the 192 -> 128 product with its bias, before the heads: eight Philox calls per lane
+template <bool DROP>
 __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L, const float *__restrict__ features,
                                                     float *__restrict__ logits, float *__restrict__ logits_out,
-                                                    float *__restrict__ value) {
+                                                    float *__restrict__ value, DR::Args da, const uint64_t *__restrict__ callp) {
     const int lane = threadIdx.x, h = lane >> 5;
     const int row = blockIdx.x * 32 + (lane & 31);
     const int n = p.num_rows, na = p.n_actions;
@@ -227,6 +261,17 @@ __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L,
 #pragma unroll
             for (int t = 0; t < 4; t++)
                 hid[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[L.sh_w + (t * 96 + 4 * c + j) * 64 + lane], v[j], hid[t], 0, 0, 0);
+    }
+    if constexpr (DROP) {
+        const uint64_t call = *callp;
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                const DR::Out o = DR::draw(da.seed, call, (uint32_t)rc, DR::SITE_SHARED, 0, (uint32_t)((((t << 1) | m) << 1) | h));
+#pragma unroll
+                for (int k = 0; k < 8; k++) hid[t][8 * m + k] = DR::apply(hid[t][8 * m + k], DR::kept(o, k, da.threshold), da.scale);
+            }
     }
     for (int i = 0; i < L.tiles; i++) {
         const float *__restrict__ wa = w + L.ac_w + (size_t)i * 64 * 64 + lane;
@@ -253,9 +298,17 @@ __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L,
     }
 }
 
-__global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
-                                                      int deterministic, int64_t *__restrict__ actions,
-                                                      float *__restrict__ logprob, float *__restrict__ entropy) {
+// The last launch of a masked call also advances the call index: ONE lane (row 0) stores *call + 1, and for evaluate the
+// index it consumed to *used.  No other lane of this launch reads either word.
+__device__ __forceinline__ void advance_call(uint64_t *__restrict__ callp, uint64_t *__restrict__ used) {
+    const uint64_t c = *callp;
+    if (used) *used = c;
+    *callp = c + 1;
+}
+
+__device__ __forceinline__ void policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
+                                              int deterministic, int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                              float *__restrict__ entropy) {
     const int row = blockIdx.x * 64 + threadIdx.x;
     if (row >= n) return;
     const float *__restrict__ l = logits + (size_t)row * na;
@@ -265,11 +318,25 @@ __global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float
     entropy[row] = d.entropy;
 }
 
+__global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
+                                                      int deterministic, int64_t *__restrict__ actions,
+                                                      float *__restrict__ logprob, float *__restrict__ entropy) {
+    policy_sample(n, na, logits, u, deterministic, actions, logprob, entropy);
+}
+
+__global__ __launch_bounds__(64) void k_policy_sample_drop(int n, int na, const float *__restrict__ logits,
+                                                           const float *__restrict__ u, int deterministic,
+                                                           int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                           float *__restrict__ entropy, uint64_t *__restrict__ callp) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) advance_call(callp, nullptr);
+    policy_sample(n, na, logits, u, deterministic, actions, logprob, entropy);
+}
+
 // gd_policy_evaluate: the action rule on GIVEN actions, a lane per row.  An action outside [0, na) is clamped (memory safety
 // only; such a row's logprob is that of the clamped action).
-__global__ __launch_bounds__(64) void k_policy_evaluate(int n, int na, const float *__restrict__ logits,
-                                                        const int64_t *__restrict__ actions, float *__restrict__ logprob,
-                                                        float *__restrict__ entropy) {
+__device__ __forceinline__ void policy_evaluate(int n, int na, const float *__restrict__ logits,
+                                                const int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                float *__restrict__ entropy) {
     const int row = blockIdx.x * 64 + threadIdx.x;
     if (row >= n) return;
     const float *__restrict__ l = logits + (size_t)row * na;
@@ -279,6 +346,22 @@ __global__ __launch_bounds__(64) void k_policy_evaluate(int n, int na, const flo
     entropy[row] = d.entropy;
 }
 
+__global__ __launch_bounds__(64) void k_policy_evaluate(int n, int na, const float *__restrict__ logits,
+                                                        const int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                        float *__restrict__ entropy) {
+    policy_evaluate(n, na, logits, actions, logprob, entropy);
+}
+
+__global__ __launch_bounds__(64) void k_policy_evaluate_drop(int n, int na, const float *__restrict__ logits,
+                                                             const int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                             float *__restrict__ entropy, uint64_t *__restrict__ callp,
+                                                             uint64_t *__restrict__ used) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) advance_call(callp, used);
+    policy_evaluate(n, na, logits, actions, logprob, entropy);
+}
+
+DR::Args drop_args(const gd_dropout &d) { return DR::Args{d.seed, d.threshold, d.scale}; }
+
 }  // namespace
 
 long long policy_blob_floats(int ego_width, int n_actions) { return policy_layout(ego_width, n_actions).total; }
@@ -287,11 +370,27 @@ void launch_policy_forward(const gd_policy &p, hipStream_t st, const float *obs,
                            int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out) {
     const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
     const int n = p.num_rows;
-    hipLaunchKernelGGL(k_policy_embed<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features,
-                       (unsigned char *)nullptr);
-    hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits, logits_out, value);
+    hipLaunchKernelGGL((k_policy_embed<false, false>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features,
+                       (unsigned char *)nullptr, DR::Args{}, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_policy_tail<false>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits, logits_out,
+                       value, DR::Args{}, (const uint64_t *)nullptr);
     hipLaunchKernelGGL(k_policy_sample, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, u,
                        deterministic ? 1 : 0, actions, logprob, entropy);
+}
+
+// The masked forward: the same three launches on the DROP instantiations.  d.call is advanced by the last launch (the struct
+// declares it const because callers only ever read it; the device owns the word).
+void launch_policy_forward(const gd_policy &p, const gd_dropout &d, hipStream_t st, const float *obs, const float *u,
+                           bool deterministic, int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out) {
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows;
+    const DR::Args da = drop_args(d);
+    hipLaunchKernelGGL((k_policy_embed<false, true>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features,
+                       (unsigned char *)nullptr, da, d.call);
+    hipLaunchKernelGGL(k_policy_tail<true>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits, logits_out,
+                       value, da, d.call);
+    hipLaunchKernelGGL(k_policy_sample_drop, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, u,
+                       deterministic ? 1 : 0, actions, logprob, entropy, const_cast<uint64_t *>(d.call));
 }
 
 // p.features and p.logits are the caller-owned buffers of gd_policy_grad here
@@ -299,11 +398,25 @@ void launch_policy_evaluate(const gd_policy &p, hipStream_t st, const float *obs
                             float *logprob, float *entropy, float *value) {
     const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
     const int n = p.num_rows;
-    hipLaunchKernelGGL(k_policy_embed<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features, winners);
-    hipLaunchKernelGGL(k_policy_tail, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits,
-                       (float *)nullptr, value);
+    hipLaunchKernelGGL((k_policy_embed<true, false>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features, winners,
+                       DR::Args{}, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_policy_tail<false>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits,
+                       (float *)nullptr, value, DR::Args{}, (const uint64_t *)nullptr);
     hipLaunchKernelGGL(k_policy_evaluate, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, actions,
                        logprob, entropy);
+}
+
+void launch_policy_evaluate(const gd_policy &p, const gd_dropout &d, hipStream_t st, const float *obs, const int64_t *actions,
+                            unsigned char *winners, float *logprob, float *entropy, float *value) {
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows;
+    const DR::Args da = drop_args(d);
+    hipLaunchKernelGGL((k_policy_embed<true, true>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, p, L, obs, p.features, winners,
+                       da, d.call);
+    hipLaunchKernelGGL(k_policy_tail<true>, dim3((unsigned)((n + 31) / 32)), dim3(64), 0, st, p, L, p.features, p.logits,
+                       (float *)nullptr, value, da, d.call);
+    hipLaunchKernelGGL(k_policy_evaluate_drop, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, actions,
+                       logprob, entropy, const_cast<uint64_t *>(d.call), d.used);
 }
 
 }  // namespace gd

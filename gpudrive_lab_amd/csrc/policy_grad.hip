@@ -17,14 +17,28 @@
 // The weights are read in the state dict's natural layout (gd_policy_grad.params), which is also the layout of grad.
 // No atomics: every sum has one owner and a fixed order, so equal inputs give equal bits.  Accumulations are fmaf; everything
 // else rounds every operation (-ffp-contract=off).  Every byte of rowstat, partials and grad is stored on every call.
+// Training-mode dropout (gd_policy_backward_dropout) is the DROP instantiation of k_pg_accumulate: the masks of
+// the evaluate call whose index is in gd_dropout.used are recomputed (dropout_rule.hpp; a lane is a feature at all four sites,
+// so one Philox call per lane and site) -- the recomputed hidden and tanh outputs are masked before they enter dWa, dWc and
+// dW2, and the gradients that pass a mask (dhidden, the gradient at the tanh's output) are multiplied by mask * scale.
 #include <hip/hip_runtime.h>
 
+#include "dropout_rule.hpp"
 #include "engine.hpp"
 #include "policy_grad_rule.hpp"
 
 namespace gd {
 
 namespace {
+
+namespace DR = dropout_rule;
+
+// DROP: the mask of one row of one call
+struct DropCall {
+    DR::Args a;
+    uint64_t call;
+    uint32_t row;
+};
 
 constexpr int F = 64, HID = 128, FEAT = 192, ROADS = 200, MAX_ACTIONS = 1024;
 constexpr int NT = 256, NW = 4, OWN = F / NW;  // lanes and waves of k_pg_accumulate; pooled features a wave owns
@@ -135,10 +149,10 @@ __device__ __forceinline__ void entity_backward(const EmbedW<K> &w, EmbedAcc<K> 
 }
 
 // One set embedder of one row: the OWN pooled features of wave wv, each at its winner
-template <int K>
+template <int K, bool DROP>
 __device__ __forceinline__ void set_backward(const EmbedW<K> &w, EmbedAcc<K> &a, const float *__restrict__ rows, int count,
                                              const unsigned char *__restrict__ win, const float *__restrict__ dpool,
-                                             const float *__restrict__ w2, int wv, int lane) {
+                                             const float *__restrict__ w2, int wv, int lane, const DropCall &dc, uint32_t site) {
     // lane l holds winners[l]; the next entity's row and W2 element are loaded while this one is worked on (at 1 wave per SIMD
     // nothing else hides the latency)
     const int mine = win[lane];
@@ -166,10 +180,17 @@ __device__ __forceinline__ void set_backward(const EmbedW<K> &w, EmbedAcc<K> &a,
         float nrm, t, rstd;
         entity_forward<K>(w, x, nrm, t, rstd);
         const float dp = dpool[j];
+        float tm = t, dt = dp * w2j;
+        if constexpr (DROP) {
+            // the winner's mask, feature f = lane (the index clamped as `entity` clamps it)
+            const int e = __shfl(mine, j);
+            const bool keep = DR::kept(dc.a.seed, dc.call, dc.row, site, (uint32_t)(e < count ? e : count - 1), lane, dc.a.threshold);
+            tm = DR::apply(t, keep, dc.a.scale), dt = DR::apply(dt, keep, dc.a.scale);
+        }
         // (a.w2 is indexed by the loop counter: select instead of a dynamic register index)
 #pragma unroll
-        for (int qq = 0; qq < OWN; qq++) a.w2[qq] = qq == q ? fmaf(dp, t, a.w2[qq]) : a.w2[qq];
-        entity_backward<K>(w, a, x, nrm, t, rstd, dp * w2j);
+        for (int qq = 0; qq < OWN; qq++) a.w2[qq] = qq == q ? fmaf(dp, tm, a.w2[qq]) : a.w2[qq];
+        entity_backward<K>(w, a, x, nrm, t, rstd, dt);
     }
 }
 
@@ -193,11 +214,14 @@ __device__ __forceinline__ void store_set(float (*red)[F], const EmbedAcc<K> &a,
     store_wave_sum(red, a.be, part + L.be[e], 1, wv, lane);
 }
 
-template <int EW>
+// DROP: da and usedp are the rule's values and the device word that holds the evaluate call's index; without DROP they are
+// not read
+template <int EW, bool DROP>
 __global__ __launch_bounds__(NT) void k_pg_accumulate(int n, int partners, int na, const float *__restrict__ prm,
                                                       const float *__restrict__ obs, const float *__restrict__ features, const float *__restrict__ logits,
                                                       const unsigned char *__restrict__ winners,
-                                                      const float *__restrict__ rowstat, float *__restrict__ partials) {
+                                                      const float *__restrict__ rowstat, float *__restrict__ partials, DR::Args da,
+                                                      const uint64_t *__restrict__ usedp) {
     __shared__ float s_f[FEAT], s_df[FEAT], s_hid[HID], s_dh[HID], s_dl[MAX_ACTIONS + 8];
     __shared__ float s_red[NW][F];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -230,8 +254,16 @@ __global__ __launch_bounds__(NT) void k_pg_accumulate(int n, int partners, int n
     load_embed<EW>(w_ego, a_ego, prm, L, 0, lane);
     load_embed<6>(w_par, a_par, prm, L, 1, lane);
     load_embed<13>(w_road, a_road, prm, L, 2, lane);
+    DropCall dc{da, 0, 0};
+    if constexpr (DROP) dc.call = *usedp;
 
     for (int row = blockIdx.x; row < n; row += P) {
+        // DROP: lanes i and 128 + i both hold the mask of hidden feature i
+        bool keep_h = true;
+        if constexpr (DROP) {
+            dc.row = (uint32_t)row;
+            keep_h = DR::kept(dc.a.seed, dc.call, dc.row, DR::SITE_SHARED, 0, tid & (HID - 1), dc.a.threshold);
+        }
         // the row's features and dlogits
         if (tid < FEAT) s_f[tid] = features[(size_t)row * FEAT + tid];
         {
@@ -251,6 +283,7 @@ __global__ __launch_bounds__(NT) void k_pg_accumulate(int n, int partners, int n
             float h = prm[L.bs + tid];
 #pragma unroll 16
             for (int j = 0; j < FEAT; j++) h = fmaf(wr[j], s_f[j], h);
+            if constexpr (DROP) h = DR::apply(h, keep_h, dc.a.scale);
             s_hid[tid] = h;
         } else {
             // [Wa; Wc] as NA + 1 rows, eight at a time with no remainder loop: past the end the row index stays at the critic's
@@ -265,6 +298,7 @@ __global__ __launch_bounds__(NT) void k_pg_accumulate(int n, int partners, int n
                     d = fmaf(prm[(k < na ? L.wa + k * HID : L.wc) + i], s_dl[k], d);
                 }
             }
+            if constexpr (DROP) d = DR::apply(d, keep_h, dc.a.scale);
             s_dh[i] = d;
         }
         __syncthreads();
@@ -328,13 +362,19 @@ __global__ __launch_bounds__(NT) void k_pg_accumulate(int n, int partners, int n
             float dt = 0.f;
 #pragma unroll 16
             for (int j = 0; j < F; j++) dt = fmaf(s_df[j], prm[L.w2[0] + j * F + lane], dt);
+            float tm = t;
+            if constexpr (DROP) {
+                const bool keep = DR::kept(dc.a.seed, dc.call, dc.row, DR::SITE_EGO, 0, lane, dc.a.threshold);
+                tm = DR::apply(t, keep, dc.a.scale), dt = DR::apply(dt, keep, dc.a.scale);
+            }
 #pragma unroll
-            for (int q = 0; q < OWN; q++) a_ego.w2[q] = fmaf(s_df[wv + NW * q], t, a_ego.w2[q]);
+            for (int q = 0; q < OWN; q++) a_ego.w2[q] = fmaf(s_df[wv + NW * q], tm, a_ego.w2[q]);
             if (wv == 0) entity_backward<EW>(w_ego, a_ego, xe, nrm, t, rstd, dt);
         }
         const unsigned char *__restrict__ win = winners + (size_t)row * (2 * F);
-        set_backward<6>(w_par, a_par, x + EW, partners, win, s_df + F, prm + L.w2[1], wv, lane);
-        set_backward<13>(w_road, a_road, x + EW + 6 * partners, ROADS, win + F, s_df + 2 * F, prm + L.w2[2], wv, lane);
+        set_backward<6, DROP>(w_par, a_par, x + EW, partners, win, s_df + F, prm + L.w2[1], wv, lane, dc, DR::SITE_PARTNER);
+        set_backward<13, DROP>(w_road, a_road, x + EW + 6 * partners, ROADS, win + F, s_df + 2 * F, prm + L.w2[2], wv, lane, dc,
+                               DR::SITE_ROAD);
         // (the next row's first stage writes s_f and s_dl only, which nothing above reads after the last barrier)
     }
 
@@ -375,11 +415,29 @@ void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, hipStre
     hipLaunchKernelGGL(k_pg_stats, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, na, g.logits, actions, d_logprob, d_entropy,
                        d_value, g.rowstat);
     if (p.ego_width == 6)
-        hipLaunchKernelGGL(k_pg_accumulate<6>, dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
-                           g.features, g.logits, g.winners, g.rowstat, g.partials);
+        hipLaunchKernelGGL((k_pg_accumulate<6, false>), dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
+                           g.features, g.logits, g.winners, g.rowstat, g.partials, DR::Args{}, (const uint64_t *)nullptr);
     else
-        hipLaunchKernelGGL(k_pg_accumulate<9>, dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
-                           g.features, g.logits, g.winners, g.rowstat, g.partials);
+        hipLaunchKernelGGL((k_pg_accumulate<9, false>), dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
+                           g.features, g.logits, g.winners, g.rowstat, g.partials, DR::Args{}, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(k_pg_reduce, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, st, L.total, P, g.partials, grad);
+}
+
+// The masked backward: the masks of the evaluate call whose index is *d.used
+void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, const gd_dropout &d, hipStream_t st, const float *obs,
+                            const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
+                            float *grad) {
+    const GradLayout L = grad_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows, na = p.n_actions, P = g.num_partials;
+    const DR::Args da{d.seed, d.threshold, d.scale};
+    hipLaunchKernelGGL(k_pg_stats, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, na, g.logits, actions, d_logprob, d_entropy,
+                       d_value, g.rowstat);
+    if (p.ego_width == 6)
+        hipLaunchKernelGGL((k_pg_accumulate<6, true>), dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
+                           g.features, g.logits, g.winners, g.rowstat, g.partials, da, (const uint64_t *)d.used);
+    else
+        hipLaunchKernelGGL((k_pg_accumulate<9, true>), dim3((unsigned)P), dim3(NT), 0, st, n, p.max_agents - 1, na, g.params, obs,
+                           g.features, g.logits, g.winners, g.rowstat, g.partials, da, (const uint64_t *)d.used);
     hipLaunchKernelGGL(k_pg_reduce, dim3((unsigned)((L.total + 255) / 256)), dim3(256), 0, st, L.total, P, g.partials, grad);
 }
 

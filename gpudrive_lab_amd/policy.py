@@ -14,9 +14,12 @@ float32 recomputation in the PPO ratio.
         ro.store(obs, value, actions, logprob, rewards, terminals, masks)
         obs, rewards, terminals, truncations, masks = env.step(actions)
 
-EVAL MODE.  The forward is the module in eval mode: dropout is the identity.  The reference's rollout does not call
-`.eval()` and its yaml has dropout 0.01, so its own rollout forward drops 1 % of the embedder activations and of the hidden
-vector at random; this class does not reproduce that noise.
+DROPOUT.  Without a rule the forward is the module in eval mode: dropout is the identity.  The reference's rollout does not
+call `.eval()` and its yaml has dropout 0.01, so its own rollout forward drops 1 % of the embedder activations and of the
+hidden vector at random.  `dropout_rule=DropoutRule(p, seed)` (dropout.py) gives that forward: the four sites are masked in
+the kernels by this project's counter-based rule (csrc/dropout_rule.hpp; `nn.Dropout`'s own stream cannot be reproduced),
+on every call while `pol.training` is true -- `deterministic=True` does not switch the masks off, as it does not in the
+reference.  `pol.eval()` is the unmasked forward again, `pol.train()` the masked one.
 
 The network rule and the action rule are stated in include/gpudrive_amd.h (`gd_policy`) and csrc/policy_rule.hpp.  The
 draw is this project's: `torch.multinomial`'s random stream cannot be reproduced, so the action is a function of one
@@ -38,6 +41,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _capi
+from .dropout import check_rule
 
 INPUT_DIM, HIDDEN_DIM, ROADS, ROAD_K, PARTNER_K = 64, 128, 200, 13, 6
 FEATURES = 3 * INPUT_DIM
@@ -158,14 +162,16 @@ def pack_index(ego_width, n_actions):
 
 
 class DevicePolicy:
-    def __init__(self, state_dict, max_agents=128, ego_width=6, *, device="cuda", act_func="tanh", vbd_in_obs=False):
+    def __init__(self, state_dict, max_agents=128, ego_width=6, *, device="cuda", act_func="tanh", vbd_in_obs=False,
+                 dropout_rule=None):
         """state_dict: the reference module's (`ego_embed.0/1/4`, `partner_embed.0/1/4`, `road_map_embed.0/1/4`: Linear,
         LayerNorm with affine, Linear; `shared_embed.0`, `actor`, `critic`), float32, with input_dim 64, hidden_dim 128 and
         1 <= n_actions <= 1024.  max_agents: 64 or 128.  ego_width: 6, or 9 for reward-conditioned rows.  Anything else --
         other widths, an activation other than tanh, vbd_in_obs, more than 1024 actions (the 8000-entry delta table), a
-        missing or extra key, a wrong shape or dtype -- is a ValueError raised before anything reaches the device.  The
-        forward is the module in eval mode (see the module docstring)."""
+        missing or extra key, a wrong shape or dtype -- is a ValueError raised before anything reaches the device.
+        dropout_rule: None (the module in eval mode) or a `DropoutRule` on the same device (see the module docstring)."""
         self.n_actions = check_policy_args(state_dict, max_agents, ego_width, act_func, vbd_in_obs)
+        check_rule(dropout_rule, "DevicePolicy: ")
         self.max_agents, self.ego_width = max_agents, ego_width
         self.obs_width = obs_width(max_agents, ego_width)
         try:
@@ -176,6 +182,8 @@ class DevicePolicy:
             raise ValueError("DevicePolicy: the policy runs on the GPU (there is no host path), got device %r" % (device,))
         self._L = _capi.lib()
         self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        self.dropout_rule = check_rule(dropout_rule, "DevicePolicy: ", self.device)
+        self.training = True
         self._names = tuple(expected_shapes(ego_width, self.n_actions))
         self._index = torch.from_numpy(pack_index(ego_width, self.n_actions)).to(self.device)
         self._zero = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -187,6 +195,15 @@ class DevicePolicy:
     @classmethod
     def from_state_dict(cls, state_dict, max_agents=128, ego_width=6, **kw):
         return cls(state_dict, max_agents, ego_width, **kw)
+
+    def train(self, mode=True):
+        """With a dropout rule: mask every call (the default, as the reference's rollout does).  Returns self."""
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        """The unmasked forward, whether or not there is a dropout rule.  Returns self."""
+        return self.train(False)
 
     def _pack(self, sd):
         with torch.no_grad():
@@ -213,7 +230,8 @@ class DevicePolicy:
         Returns (actions int64 [N], logprob, entropy, value float32 [N]).  out: those four tensors of an earlier call, to be
         overwritten (every byte is written); logits_out: [N, n_actions] float32 to receive the logits.  Three launches on
         torch's current stream, no host synchronisation; with out= and an N seen before, no allocation either, so the call can
-        be captured in a graph.  The features and logits scratch belongs to the object (it grows with the largest N seen), so
+        be captured in a graph.  With a dropout rule and `training`, the call consumes the rule's call index and advances
+        it on the device.  The features and logits scratch belongs to the object (it grows with the largest N seen), so
         a DevicePolicy serves ONE stream at a time: calls on two streams need two objects or an event between them."""
         if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[1] != self.obs_width:
             raise ValueError("DevicePolicy: obs must be a [N, %d] tensor (max_agents %d, ego_width %d)"
@@ -248,10 +266,13 @@ class DevicePolicy:
         p.features, p.logits = self._features.data_ptr(), self._logits.data_ptr()
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(self._L.gd_policy_forward(C.byref(p), obs.data_ptr(), None if u is None else u.data_ptr(),
-                                                  int(deterministic), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                                  out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(),
-                                                  stream), "gd_policy_forward")
+            args = (obs.data_ptr(), None if u is None else u.data_ptr(), int(deterministic), out[0].data_ptr(), out[1].data_ptr(),
+                    out[2].data_ptr(), out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(), stream)
+            if self.dropout_rule is not None and self.training:
+                d = self.dropout_rule.struct()
+                _capi.check(self._L.gd_policy_forward_dropout(C.byref(p), C.byref(d), *args), "gd_policy_forward_dropout")
+            else:
+                _capi.check(self._L.gd_policy_forward(C.byref(p), *args), "gd_policy_forward")
         return out
 
 
@@ -283,12 +304,19 @@ class _Evaluate(torch.autograd.Function):
         logprob, entropy, value = (torch.empty(n, dtype=f, device=dev) for _ in range(3))
         p, g = mod._structs(n, features, logits, winners)
         p.blob, p.blob_floats = blob.data_ptr(), blob.numel()
+        rule = mod.dropout_rule if mod.training else None
+        # the call index this forward consumes belongs to this call's context: a later forward does not disturb its backward
+        used = None if rule is None else torch.empty(1, dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(L.gd_policy_evaluate(C.byref(p), C.byref(g), obs.data_ptr(), action.data_ptr(), logprob.data_ptr(),
-                                             entropy.data_ptr(), value.data_ptr(), stream), "gd_policy_evaluate")
+            args = (obs.data_ptr(), action.data_ptr(), logprob.data_ptr(), entropy.data_ptr(), value.data_ptr(), stream)
+            if rule is None:
+                _capi.check(L.gd_policy_evaluate(C.byref(p), C.byref(g), *args), "gd_policy_evaluate")
+            else:
+                d = rule.struct(used)
+                _capi.check(L.gd_policy_evaluate_dropout(C.byref(p), C.byref(g), C.byref(d), *args), "gd_policy_evaluate_dropout")
         ctx.save_for_backward(obs, action, *params)  # (torch's version check then catches an optimiser step before backward)
-        ctx.mod, ctx.kept = mod, (flat, features, logits, winners)
+        ctx.mod, ctx.kept, ctx.drop = mod, (flat, features, logits, winners), (rule, used)
         return logprob, entropy, value
 
     @staticmethod
@@ -309,9 +337,15 @@ class _Evaluate(torch.autograd.Function):
         g.grad_floats, g.num_partials = total, P
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(_capi.lib().gd_policy_backward(C.byref(p), C.byref(g), obs.data_ptr(), action.data_ptr(),
-                                                       ups[0].data_ptr(), ups[1].data_ptr(), ups[2].data_ptr(),
-                                                       grad.data_ptr(), stream), "gd_policy_backward")
+            args = (obs.data_ptr(), action.data_ptr(), ups[0].data_ptr(), ups[1].data_ptr(), ups[2].data_ptr(), grad.data_ptr(),
+                    stream)
+            rule, used = ctx.drop
+            if rule is None:
+                _capi.check(_capi.lib().gd_policy_backward(C.byref(p), C.byref(g), *args), "gd_policy_backward")
+            else:
+                d = rule.struct(used)
+                _capi.check(_capi.lib().gd_policy_backward_dropout(C.byref(p), C.byref(g), C.byref(d), *args),
+                            "gd_policy_backward_dropout")
         views, o = [], 0
         for shape in mod._shapes:
             k = int(np.prod(shape))
@@ -336,9 +370,12 @@ class TrainablePolicy(nn.Module):
     `NeuralNet`, and any torch optimiser works.  The logits are bit-identical to `DevicePolicy`'s for the same weights and
     observations, so evaluating the actions it sampled returns its logprob exactly: the first epoch's PPO ratio is 1.
 
-    NO DROPOUT.  `dropout` must be 0.0.  The reference trains in train mode with the puffer yaml's dropout 0.01 (1 % of the
-    embedder activations and of the hidden vector zeroed at random, the rest scaled by 1 / 0.99); this class does not
-    reproduce that noise, as `DevicePolicy` does not (its EVAL MODE note).  `.train()` and `.eval()` behave alike.
+    DROPOUT.  The reference trains in train mode with the puffer yaml's dropout 0.01 (1 % of the embedder activations and of
+    the hidden vector zeroed at random, the rest scaled by 1 / 0.99).  `dropout_rule=DropoutRule(p, seed)` gives that: in
+    `.train()` the forward and its backward mask the four sites by the rule (csrc/dropout_rule.hpp); in `.eval()`, and
+    without a rule, they are the unmasked path.  Each forward consumes one call index of the rule and keeps it in its own
+    autograd context, so two forwards before one backward still work.  The numeric `dropout` must stay 0.0: it would promise
+    `nn.Dropout`'s own random stream, which cannot be reproduced.
 
     The max-pools pass a pooled feature's gradient to one entity, the lowest index among those that attain the float32
     maximum (torch's `max(dim=1)` makes the same choice).  `obs` gets no gradient.
@@ -350,11 +387,13 @@ class TrainablePolicy(nn.Module):
     leaves the extra workgroups storing zeros."""
 
     def __init__(self, state_dict, max_agents=128, ego_width=6, *, dropout=0.0, partials=None, device=None, act_func="tanh",
-                 vbd_in_obs=False):
+                 vbd_in_obs=False, dropout_rule=None):
         super().__init__()
         who = "TrainablePolicy: "
         if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or dropout != 0.0:
-            raise ValueError(who + "dropout must be 0.0 (the kernels have no dropout), got %r" % (dropout,))
+            raise ValueError(who + "dropout must be 0.0 (nn.Dropout's random stream cannot be reproduced; pass "
+                             "dropout_rule=DropoutRule(p, seed) for training-mode masks), got %r" % (dropout,))
+        self.dropout_rule = check_rule(dropout_rule, who)
         if partials is None:
             partials = DEFAULT_PARTIALS
         if not _is_int(partials) or not 1 <= partials <= MAX_PARTIALS:
@@ -427,5 +466,7 @@ class TrainablePolicy(nn.Module):
                 raise ValueError(who + "parameter %s must be a contiguous float32 tensor of shape %s on %s"
                                  % (name, shape, obs.device))
             params.append(p)
+        if self.dropout_rule is not None and self.training:
+            check_rule(self.dropout_rule, who, obs.device)
         logprob, entropy, value = _Evaluate.apply(self, obs, action, *params)
         return action, logprob, entropy, value

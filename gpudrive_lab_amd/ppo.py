@@ -16,8 +16,12 @@ synchronisation or an allocation.  The rule -- every rounding, the order of ever
 Every parameter has exactly one place in the packed weights the forward reads (`gd_policy.blob`), so the Adam kernel stores
 each updated weight to the flat layout and to the blob, and `ppo.policy` follows the optimiser with no re-pack.
 
-Not here: `target_kl` (it needs a host read per epoch; the yaml's is null), dropout (the kernels have none: see
-`TrainablePolicy`), the explained variance (the reference computes it from `returns_np`, which rollout.py documents as a
+Training-mode dropout (the yaml's `network.dropout: 0.01`, live in the reference's rollout and update alike) is
+`dropout_rule=DropoutRule(p, seed)` (dropout.py): the update's evaluate and backward mask the four sites by the rule, and
+`ppo.policy` is handed the same rule, so the rollout and the updates draw from one stream of call indices.
+
+Not here: `target_kl` (it needs a host read per epoch; the yaml's is null), torch's own dropout stream (the numeric
+`dropout` stays 0.0), the explained variance (the reference computes it from `returns_np`, which rollout.py documents as a
 quirk), LSTM state, weight decay, amsgrad, a bf16 path."""
 import ctypes as C
 import math
@@ -26,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from .dropout import check_rule
 from .policy import (DEFAULT_PARTIALS, FEATURES, INPUT_DIM, MAX_PARTIALS, MAX_ROWS, ROWSTAT, DevicePolicy, _is_int,
                      check_policy_args, expected_shapes, grad_floats, pack_index)
 
@@ -50,7 +55,7 @@ def _number(v):
 
 def check_ppo_args(state_dict, max_agents, ego_width, minibatch_size, learning_rate, betas, eps, clip_coef, clip_vloss,
                    vf_clip_coef, norm_adv, ent_coef, vf_coef, max_grad_norm, target_kl, partials, dropout=0.0, act_func="tanh",
-                   vbd_in_obs=False):
+                   vbd_in_obs=False, dropout_rule=None):
     """Everything `DevicePPO` refuses, checked on the host before anything reaches the device (ValueError).  Returns
     (n_actions, partials)."""
     who = "DevicePPO: "
@@ -58,7 +63,9 @@ def check_ppo_args(state_dict, max_agents, ego_width, minibatch_size, learning_r
     if target_kl is not None:
         raise ValueError(who + "target_kl is not built (it needs a host read per epoch); pass None")
     if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or dropout != 0.0:
-        raise ValueError(who + "dropout must be 0.0 (the kernels have no dropout), got %r" % (dropout,))
+        raise ValueError(who + "dropout must be 0.0 (nn.Dropout's random stream cannot be reproduced; pass "
+                         "dropout_rule=DropoutRule(p, seed) for training-mode masks), got %r" % (dropout,))
+    check_rule(dropout_rule, who)
     if not _is_int(minibatch_size) or not 1 <= minibatch_size <= MAX_ROWS:
         raise ValueError(who + "minibatch_size must be an int in [1, %d], got %r" % (MAX_ROWS, minibatch_size))
     if norm_adv and minibatch_size < 2:
@@ -126,16 +133,22 @@ class DevicePPO:
     def __init__(self, state_dict, max_agents=128, ego_width=6, minibatch_size=8192, *, learning_rate=3e-4, betas=(0.9, 0.999),
                  eps=1e-5, clip_coef=0.2, clip_vloss=False, vf_clip_coef=0.2, norm_adv=True, ent_coef=1e-4, vf_coef=0.3,
                  max_grad_norm=0.5, target_kl=None, partials=None, device="cuda", dropout=0.0, act_func="tanh",
-                 vbd_in_obs=False):
+                 vbd_in_obs=False, dropout_rule=None):
         """state_dict, max_agents, ego_width: `DevicePolicy`'s.  minibatch_size: M, the rows of every `update`.  The
         hyper-parameters carry the reference config's names and the puffer yaml's defaults; Adam is `torch.optim.Adam(lr,
         betas, eps)` without weight decay or amsgrad.  partials: `TrainablePolicy`'s (None: 256).  Everything is allocated
         here, once (`nbytes`), except the minibatch buffers of `train`, which its first call adds.  Anything not built is a
-        ValueError raised before anything reaches the device."""
+        ValueError raised before anything reaches the device.
+        dropout_rule: None, or a `DropoutRule` on the same device: every `update` then masks its forward and backward by the
+        rule, and `policy` is handed the same rule, so the rollout forwards and the updates consume ONE stream of call indices
+        in the order they are enqueued -- they share a CUDA stream (torch's current one), or the caller orders them by events.
+        The rule's counter is the rule's own allocation; nothing is allocated per update."""
         self.n_actions, self.partials = check_ppo_args(state_dict, max_agents, ego_width, minibatch_size, learning_rate, betas,
                                                        eps, clip_coef, clip_vloss, vf_clip_coef, norm_adv, ent_coef, vf_coef,
-                                                       max_grad_norm, target_kl, partials, dropout, act_func, vbd_in_obs)
-        self.policy = DevicePolicy(state_dict, max_agents, ego_width, device=device)
+                                                       max_grad_norm, target_kl, partials, dropout, act_func, vbd_in_obs,
+                                                       dropout_rule)
+        self.policy = DevicePolicy(state_dict, max_agents, ego_width, device=device, dropout_rule=dropout_rule)
+        self.dropout_rule = dropout_rule
         self.max_agents, self.ego_width, self.minibatch_size = max_agents, ego_width, minibatch_size
         self.obs_width, self.device = self.policy.obs_width, self.policy.device
         self.learning_rate, self.betas, self.eps = float(learning_rate), (float(betas[0]), float(betas[1])), float(eps)
@@ -187,6 +200,9 @@ class DevicePPO:
         o.stats, o.stats_sum, o.scal = self.stats.data_ptr(), self.stats_sum.data_ptr(), self._scal.data_ptr()
         (o.newlogprob, o.entropy, o.newvalue, o.d_logprob, o.d_entropy, o.d_value) = (t.data_ptr() for t in self._rows)
         o.grad = self.grad.data_ptr()
+        # the index an update's evaluate consumes, for its own backward
+        self._used = None if dropout_rule is None else new((1,), torch.int64, fill=0)
+        self._d = None if dropout_rule is None else dropout_rule.struct(self._used)
 
     @property
     def nbytes(self):
@@ -199,14 +215,19 @@ class DevicePPO:
         """One minibatch update on the tensors `DeviceRollout.minibatch` returns (its `dones` is not used): obs
         [rows, bptt, obs_width] or [M, obs_width] float32, actions [rows, bptt] or [M] int64, the stored logprobs and values,
         the advantages and the returns [rows, bptt] or [M] float32, M = rows * bptt = minibatch_size, contiguous, on the
-        device.  Nine launches on torch's current stream, no host synchronisation, no allocation.  Afterwards the weights,
+        device.  Nine launches on torch's current stream, no host synchronisation, no allocation; with a dropout rule the
+        update consumes one call index.  Afterwards the weights,
         the moments, `policy.blob`, `grad`, `winners` and `stats` are the update's; nothing is returned."""
         ptrs = check_update_args(self.minibatch_size, self.obs_width, self.device, obs, actions, logprobs, values, advantages,
                                  returns)
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(self._L.gd_ppo_update(C.byref(self._p), C.byref(self._g), C.byref(self._o), *ptrs, stream),
-                        "gd_ppo_update")
+            if self._d is None:
+                _capi.check(self._L.gd_ppo_update(C.byref(self._p), C.byref(self._g), C.byref(self._o), *ptrs, stream),
+                            "gd_ppo_update")
+            else:
+                _capi.check(self._L.gd_ppo_update_dropout(C.byref(self._p), C.byref(self._g), C.byref(self._o), C.byref(self._d),
+                                                          *ptrs, stream), "gd_ppo_update_dropout")
         self._updates += 1
 
     def train(self, ro, update_epochs=4):

@@ -567,6 +567,41 @@ int gd_ppo_adam(const gd_ppo *ppo, const float *grad, void *stream);
  * GD_ERR_INVALID: whatever the four calls refuse, or a disagreement between p, g and ppo; before any launch. */
 int gd_ppo_update(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const float *obs, const int64_t *actions,
                   const float *old_logprob, const float *old_value, const float *adv, const float *ret, void *stream);
+/* Training-mode dropout of the device policy: the reference trains (and rolls out) with its four nn.Dropout layers live --
+ * after the tanh of each of the three embedders and after shared_embed's linear.  torch's random stream cannot be reproduced,
+ * so the mask is this project's rule, csrc/dropout_rule.hpp, stated there in full: whether an element is kept is a pure
+ * function of (seed, call, row, site, entity, feature) through Philox4x32-10 cut into 16-bit fields; an element is dropped
+ * iff its field < threshold; a kept element is x * scale, a dropped one +0.  `call` indexes the masked forward / evaluate
+ * calls; it lives on the device (as gd_ppo's step does), so a sequence of calls never depends on a host value that changes:
+ * every kernel of a call reads *call, and one lane of the call's last launch stores *call + 1 (the library writes the word;
+ * callers only read it, or set it between calls).  gd_policy_evaluate_dropout also stores the index it consumed to *used,
+ * which is what gd_policy_backward_dropout reads: the backward recomputes the masks of ITS evaluate call. */
+typedef struct gd_dropout {
+    uint64_t seed;
+    const uint64_t *call;   /* device: the index the next forward / evaluate consumes */
+    uint64_t *used;         /* device: evaluate stores the index it consumed; backward reads it */
+    uint32_t threshold;     /* T */
+    float scale;            /* 1 / (1 - p) */
+} gd_dropout;
+/* The four calls with the masks applied: the arguments, outputs, launch counts (3 / 3 / 3 / 9) and refusals of
+ * gd_policy_forward, gd_policy_evaluate, gd_policy_backward and gd_ppo_update, plus d.  d == NULL is exactly the existing
+ * function: the same kernels, the same bits.  Otherwise the forward and evaluate mask the four sites at index *d->call and
+ * advance it by one (evaluate stores the consumed index to *d->used; the forward does not touch used); the backward masks at
+ * index *d->used and writes neither word; gd_ppo_update_dropout is evaluate, loss, backward, Adam with the backward reading
+ * the index its own evaluate stored.  Winners are recorded on the masked outputs.  No host synchronisation, no allocation, no
+ * atomics; no workgroup reads a word another workgroup of the same launch writes.
+ * GD_ERR_INVALID, before any launch: whatever the existing call refuses; with d != NULL a null or not 8-byte aligned call or
+ * used, threshold outside [1, 65535], a scale that is not finite. */
+int gd_policy_forward_dropout(const gd_policy *p, const gd_dropout *d, const float *obs, const float *u, int32_t deterministic,
+                              int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out, void *stream);
+int gd_policy_evaluate_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_dropout *d, const float *obs,
+                               const int64_t *actions, float *logprob, float *entropy, float *value, void *stream);
+int gd_policy_backward_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_dropout *d, const float *obs,
+                               const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
+                               float *grad, void *stream);
+int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const gd_dropout *d, const float *obs,
+                          const int64_t *actions, const float *old_logprob, const float *old_value, const float *adv,
+                          const float *ret, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.

@@ -16,7 +16,11 @@ The per-kernel split takes two more steps, the second without a device:
   1. rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/policy_backward.py --runs 1 --calls 20 --only a
   2. tools/policy_backward.py --merge FILE --kernel-stats DIR/.../*_kernel_stats.csv
      adds `kernel_average_us` (the AverageNs column of the k_policy_* and k_pg_* rows) to the JSON line in FILE.
-tools/policy_backward.py [--rows 8192] [--agents 128] [--actions 91] [--partials 256] [--runs 3] [--calls 50] [--out FILE]"""
+--dropout P: (a) runs in train mode with dropout_rule=DropoutRule(P, 0) (gd_policy_evaluate_dropout and
+gd_policy_backward_dropout), (b) in train mode with nn.Dropout(P), and a third side (a0), the same TrainablePolicy in eval
+mode (the same build without the masks), joins the alternation; the gradients of (a) and (b) are then not compared.
+tools/policy_backward.py [--rows 8192] [--agents 128] [--actions 91] [--partials 256] [--runs 3] [--calls 50] [--dropout P]
+                         [--out FILE]"""
 import argparse
 import csv
 import json
@@ -32,21 +36,22 @@ import torch  # noqa: E402
 from torch import nn  # noqa: E402
 
 import bench  # noqa: E402
+from gpudrive_lab_amd.dropout import DropoutRule  # noqa: E402
 from gpudrive_lab_amd.policy import TrainablePolicy, obs_width  # noqa: E402
 
 EGO = 6
 
 
 class LateFusion(nn.Module):
-    def __init__(self, agents, actions):
+    def __init__(self, agents, actions, dropout=0.0):
         super().__init__()
         self.agents = agents
 
         def embed(k):
-            return nn.Sequential(nn.Linear(k, 64), nn.LayerNorm(64), nn.Tanh(), nn.Dropout(0.0), nn.Linear(64, 64))
+            return nn.Sequential(nn.Linear(k, 64), nn.LayerNorm(64), nn.Tanh(), nn.Dropout(dropout), nn.Linear(64, 64))
 
         self.ego_embed, self.partner_embed, self.road_map_embed = embed(EGO), embed(6), embed(13)
-        self.shared_embed = nn.Sequential(nn.Linear(192, 128), nn.Dropout(0.0))
+        self.shared_embed = nn.Sequential(nn.Linear(192, 128), nn.Dropout(dropout))
         self.actor, self.critic = nn.Linear(128, actions), nn.Linear(128, 1)
 
     def forward(self, obs, action):
@@ -94,7 +99,7 @@ def merge(path, stats):
         res = json.loads(f.readline())
     with open(stats) as f:
         rows = [r for r in csv.DictReader(f) if re.search(r"k_policy_|k_pg_", r["Name"])]
-    res["kernel_average_us"] = {re.search(r"k_(policy|pg)_\w+(<\w+>)?", r["Name"]).group(0): float(r["AverageNs"]) / 1e3 for r in rows}
+    res["kernel_average_us"] = {re.search(r"k_(policy|pg)_\w+(<[\w, ]+>)?", r["Name"]).group(0): float(r["AverageNs"]) / 1e3 for r in rows}
     res["kernel_sum_us"] = sum(res["kernel_average_us"].values())
     line = json.dumps(res)
     print(line)
@@ -110,6 +115,7 @@ def arguments():
     ap.add_argument("--partials", type=int, default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--dropout", type=float, default=None)
     ap.add_argument("--only", choices=("a", "b"), default=None)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--merge", default=None)
@@ -128,13 +134,16 @@ def main(args):
     obs[:, EGO + 6 * (A - 1):].view(N, 200, 13)[:, 170:] = 0
     action = torch.randint(0, NA, (N,), device="cuda", generator=g)
     ups = [torch.randn(N, device="cuda", generator=g) / N for _ in range(3)]
-    net = LateFusion(A, NA).cuda()
+    P = args.dropout
+    res["dropout"] = P
+    net = LateFusion(A, NA, dropout=P or 0.0).cuda()
     with torch.no_grad():
         for m in net.modules():
             if isinstance(m, nn.Linear):
                 m.weight.normal_(0.0, m.in_features ** -0.5, generator=g)
                 m.bias.normal_(0.0, 0.1, generator=g)
-    tp = TrainablePolicy.from_state_dict(net.state_dict(), max_agents=A, ego_width=EGO, device="cuda", partials=args.partials)
+    tp = TrainablePolicy.from_state_dict(net.state_dict(), max_agents=A, ego_width=EGO, device="cuda", partials=args.partials,
+                                         dropout_rule=None if P is None else DropoutRule(P, 0))
     res["partials"] = tp.partials
 
     def step(mod):
@@ -153,18 +162,25 @@ def main(args):
         a()
     if args.only != "a":
         b()
-    if args.only is None:
+    if args.only is None and P is None:
         res["max_relative_gradient_difference"] = {
             k: float((p.grad - q.grad).abs().max() / q.grad.abs().max())
             for (k, p), (_, q) in zip(tp.named_parameters(), net.named_parameters())}
-    a_us, b_us = [], []
+    a_us, b_us, a0_us = [], [], []
     for _ in range(args.runs):
         if args.only != "b":
             a_us.append(timed(a, args.calls))
+            if P is not None:
+                tp.eval()
+                a0_us.append(timed(a, args.calls))
+                tp.train()
         if args.only != "a":
             b_us.append(timed(b, args.calls))
     if a_us:
         res.update(a=summary(a_us), a_peak_bytes=peak_rise(a), a_nbytes=tp.nbytes(N))
+    if a0_us:
+        res["a0"] = summary(a0_us)
+        res["a_over_a0"] = res["a"]["median"] / res["a0"]["median"]
     if b_us:
         res.update(b=summary(b_us), b_peak_bytes=peak_rise(b))
     if a_us and b_us:

@@ -16,7 +16,10 @@ The per-kernel split takes two more steps, the second without a device:
   1. rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/policy_forward.py --runs 1 --calls 50
   2. tools/policy_forward.py --merge FILE --kernel-stats DIR/.../*_kernel_stats.csv
      adds `kernel_average_us` (the AverageNs column of the k_policy_* rows) to the JSON line in FILE and rewrites it.
-tools/policy_forward.py [--rows 4435] [--agents 128] [--actions 91] [--runs 3] [--calls 200] [--out FILE]"""
+--dropout P: (a) runs with dropout_rule=DropoutRule(P, 0) (gd_policy_forward_dropout), (b) in train mode with nn.Dropout(P),
+and a third side (a0), the same DevicePolicy in eval mode (the same build without the masks), joins the alternation;
+`a_over_a0` is the forward's slowdown over its own dropout-off path.  The logits of (a) and (b) are then not compared.
+tools/policy_forward.py [--rows 4435] [--agents 128] [--actions 91] [--runs 3] [--calls 200] [--dropout P] [--out FILE]"""
 import argparse
 import csv
 import json
@@ -32,6 +35,7 @@ import torch  # noqa: E402
 from torch import nn  # noqa: E402
 
 import bench  # noqa: E402
+from gpudrive_lab_amd.dropout import DropoutRule  # noqa: E402
 from gpudrive_lab_amd.policy import DevicePolicy, obs_width  # noqa: E402
 
 MFMA_CEILING, COPY_CEILING = 155e12, 6.29e12
@@ -105,6 +109,7 @@ def arguments():
     ap.add_argument("--actions", type=int, default=91)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--dropout", type=float, default=None)
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--merge", default=None)
     ap.add_argument("--out", default=None)
@@ -120,25 +125,37 @@ def main(args):
     obs = torch.rand((N, D), device="cuda", generator=g) * 2 - 1
     obs[:, EGO:EGO + 6 * (A - 1)].view(N, A - 1, 6)[:, A - 9:] = 0
     obs[:, EGO + 6 * (A - 1):].view(N, 200, 13)[:, 170:] = 0
-    net = LateFusion(A, NA).cuda().eval()
+    P = args.dropout
+    res["dropout"] = P
+    net = LateFusion(A, NA, dropout=P or 0.0).cuda()
+    net.train(P is not None)
     with torch.no_grad():
         for m in net.modules():
             if isinstance(m, nn.Linear):
                 m.weight.normal_(0.0, m.in_features ** -0.5, generator=g)
                 m.bias.normal_(0.0, 0.1, generator=g)
-    pol = DevicePolicy.from_state_dict(net.state_dict(), max_agents=A, ego_width=EGO)
+    pol = DevicePolicy.from_state_dict(net.state_dict(), max_agents=A, ego_width=EGO,
+                                       dropout_rule=None if P is None else DropoutRule(P, 0))
     u = torch.rand(N, device="cuda", generator=g)
     out = pol(obs, u)
     with torch.no_grad():
         logits_a = torch.empty((N, NA), device="cuda")
         pol(obs, u, out=out, logits_out=logits_a)
-        logits_b, _ = net.logits_value(obs)
-        res["max_logit_difference"] = float((logits_a - logits_b).abs().max())
-        a_us, b_us = [], []
+        if P is None:
+            logits_b, _ = net.logits_value(obs)
+            res["max_logit_difference"] = float((logits_a - logits_b).abs().max())
+        a_us, b_us, a0_us = [], [], []
         for _ in range(args.runs):
             a_us.append(timed(lambda: pol(obs, u, out=out), args.calls))
+            if P is not None:
+                pol.eval()
+                a0_us.append(timed(lambda: pol(obs, u, out=out), args.calls))
+                pol.train()
             b_us.append(timed(lambda: net(obs), args.calls))
     res.update(a=summary(a_us), b=summary(b_us))
+    if P is not None:
+        res["a0"] = summary(a0_us)
+        res["a_over_a0"] = res["a"]["median"] / res["a0"]["median"]
     res["b_over_a"] = res["b"]["median"] / res["a"]["median"]
     res["a_outside_b_range_on_the_fast_side"] = res["a"]["hi"] < res["b"]["lo"]
     flop = 2.0 * N * ((A - 1) * (6 * 64 + 64 * 64) + 200 * (13 * 64 + 64 * 64) + EGO * 64 + 64 * 64 + 192 * 128 + 128 * (NA + 1))

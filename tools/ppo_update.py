@@ -12,7 +12,11 @@ values are the initial policy's own, perturbed by +-0.01, the advantages are N(0
 --runs each: device events around --calls updates after a warm-up of 10.  Reported: the median and the range of the
 microseconds per update, and whether (a)'s range lies wholly below (b)'s.  Run it at --rows 8192 (the reference's minibatch)
 and at --rows 512, where the launch count dominates.
-tools/ppo_update.py [--rows 8192] [--agents 128] [--actions 91] [--partials 256] [--runs 3] [--calls 50] [--out FILE]"""
+--dropout P: (a) is DevicePPO(dropout_rule=DropoutRule(P, 0)) (gd_ppo_update_dropout); (b) becomes eager torch -- the plain
+torch.nn module in train mode with nn.Dropout(P), the same loss lines, clip_grad_norm_ and Adam; and a third side (a0), a
+DevicePPO without the rule (the same build without the masks), joins the alternation.  The parameters are then not compared.
+tools/ppo_update.py [--rows 8192] [--agents 128] [--actions 91] [--partials 256] [--runs 3] [--calls 50] [--dropout P]
+                    [--out FILE]"""
 import argparse
 import json
 import os
@@ -26,6 +30,7 @@ import torch  # noqa: E402
 from torch import nn  # noqa: E402
 
 import bench  # noqa: E402
+from gpudrive_lab_amd.dropout import DropoutRule  # noqa: E402
 from gpudrive_lab_amd.policy import DevicePolicy, TrainablePolicy, obs_width  # noqa: E402
 from gpudrive_lab_amd.ppo import DevicePPO  # noqa: E402
 from policy_backward import EGO, LateFusion, summary, timed  # noqa: E402
@@ -43,6 +48,7 @@ def arguments():
     ap.add_argument("--partials", type=int, default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--dropout", type=float, default=None)
     ap.add_argument("--out", default=None)
     return ap.parse_args()
 
@@ -56,15 +62,19 @@ def main(args):
     obs = torch.rand((N, D), device="cuda", generator=g) * 2 - 1
     obs[:, EGO:EGO + 6 * (A - 1)].view(N, A - 1, 6)[:, A - 9:] = 0
     obs[:, EGO + 6 * (A - 1):].view(N, 200, 13)[:, 170:] = 0
-    net = LateFusion(A, NA).cuda()
+    P = args.dropout
+    res["dropout"] = P
+    net = LateFusion(A, NA, dropout=P or 0.0).cuda()
     with torch.no_grad():
         for m in net.modules():
             if isinstance(m, nn.Linear):
                 m.weight.normal_(0.0, m.in_features ** -0.5, generator=g)
                 m.bias.normal_(0.0, 0.1, generator=g)
-    sd = net.state_dict()
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
     ppo = DevicePPO(sd, max_agents=A, ego_width=EGO, minibatch_size=N, learning_rate=LR, betas=BETAS, eps=EPS,
-                    max_grad_norm=MAX_NORM, partials=args.partials, **YAML)
+                    max_grad_norm=MAX_NORM, partials=args.partials, dropout_rule=None if P is None else DropoutRule(P, 0), **YAML)
+    ppo0 = None if P is None else DevicePPO(sd, max_agents=A, ego_width=EGO, minibatch_size=N, learning_rate=LR, betas=BETAS,
+                                            eps=EPS, max_grad_norm=MAX_NORM, partials=args.partials, **YAML)
     res["partials"], res["a_nbytes"] = ppo.partials, ppo.nbytes
     action, logprob, _, value = ppo.policy(obs, torch.rand(N, device="cuda", generator=g))
     sign = (torch.arange(N, device="cuda") % 2).float() * 2 - 1
@@ -74,13 +84,26 @@ def main(args):
 
     tp = TrainablePolicy.from_state_dict(sd, max_agents=A, ego_width=EGO, device="cuda", partials=args.partials)
     pol = DevicePolicy.from_state_dict(sd, max_agents=A, ego_width=EGO)
-    opt = torch.optim.Adam(tp.parameters(), lr=LR, betas=BETAS, eps=EPS)
+    opt = torch.optim.Adam((tp if P is None else net).parameters(), lr=LR, betas=BETAS, eps=EPS)
     hyper = {k: v for k, v in YAML.items()}
 
     def a():
         ppo.update(obs, action, old_lp, old_v, adv, ret)
 
+    def a0():
+        ppo0.update(obs, action, old_lp, old_v, adv, ret)
+
+    def b_eager():
+        _, newlogprob, entropy, newvalue = net(obs, action)
+        loss, _ = ppo_loss(newlogprob, entropy, newvalue, old_lp, adv, ret, old_v, **hyper)
+        opt.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(net.parameters(), MAX_NORM)
+        opt.step()
+
     def b():
+        if P is not None:
+            return b_eager()
         _, newlogprob, entropy, newvalue = tp(obs, action)
         loss, _ = ppo_loss(newlogprob, entropy, newvalue, old_lp, adv, ret, old_v, **hyper)
         opt.zero_grad()
@@ -91,13 +114,19 @@ def main(args):
 
     a(), b()
     torch.cuda.synchronize()
-    flat = torch.cat([p.detach().reshape(-1) for p in tp.parameters()])
-    res["max_parameter_difference_after_one_update"] = float((ppo.flat[:-1] - flat).abs().max())
-    a_us, b_us = [], []
+    if P is None:
+        flat = torch.cat([p.detach().reshape(-1) for p in tp.parameters()])
+        res["max_parameter_difference_after_one_update"] = float((ppo.flat[:-1] - flat).abs().max())
+    a_us, b_us, a0_us = [], [], []
     for _ in range(args.runs):
         a_us.append(timed(a, args.calls))
+        if P is not None:
+            a0_us.append(timed(a0, args.calls))
         b_us.append(timed(b, args.calls))
     res.update(a=summary(a_us), b=summary(b_us))
+    if P is not None:
+        res["a0"] = summary(a0_us)
+        res["a_over_a0"] = res["a"]["median"] / res["a0"]["median"]
     res["b_over_a"] = res["b"]["median"] / res["a"]["median"]
     res["a_range_wholly_below_b"] = res["a"]["hi"] < res["b"]["lo"]
     res["a_losses"] = ppo.losses()
