@@ -196,6 +196,20 @@ class GdDropout(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("call", C.c_void_p), ("used", C.c_void_p), ("threshold", C.c_uint32), ("scale", C.c_float)]
 
 
+class GdBCPolicy(C.Structure):
+    """gd_bc_policy: the sizes, the packed weights and the chunk scratch of the device BC policy forward (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("max_agents", "num_stack", "fusion_layers", "branch_layers", "head_layers",
+                                          "n_components")] +
+                [("clip_value", C.c_float), ("chunk_rows", C.c_int32), ("blob", C.c_void_p), ("blob_floats", C.c_int64),
+                 ("scratch", C.c_void_p), ("scratch_floats", C.c_int64)])
+
+
+class GdBCOutputs(C.Structure):
+    """gd_bc_outputs: the outputs of one gd_bc_forward (device pointers; NULL: not written)."""
+    _fields_ = [(n, C.c_void_p) for n in ("context", "means", "log_covariances", "covariances", "weights", "actions", "nll",
+                                          "ego_attn_score", "component")]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -204,6 +218,7 @@ SYMBOLS = [
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
+    "gd_bc_forward", "gd_bc_eval_accumulate",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -290,6 +305,9 @@ def lib():
     L.gd_policy_evaluate_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), D] + [C.c_void_p] * 6
     L.gd_policy_backward_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), D] + [C.c_void_p] * 7
     L.gd_ppo_update_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), C.POINTER(GdPPO), D] + [C.c_void_p] * 7
+    L.gd_bc_forward.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
+                                [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs), C.c_void_p])
+    L.gd_bc_eval_accumulate.argtypes = [C.c_int32] + [C.c_void_p] * 5
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

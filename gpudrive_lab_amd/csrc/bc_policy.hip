@@ -1,0 +1,598 @@
+// Device BC policy forward (gd_bc_forward): the reference's EarlyFusionAttnBCNet in eval mode
+// (gpudrive/integrations/il/model/model.py, networks.py) on the tensors DeviceExpertDataset.batch() writes, float32 throughout.
+// A token is the ego (1), a partner (A - 1) or a road point (200): L = A + 200 per sample.  A wave holds 32 tokens TRANSPOSED,
+// as policy.hip does: lane (c = lane & 31, h = lane >> 5) belongs to token c, and its two 16-register accumulators hold the
+// features 32 t + acc(r, h) of that token.  A 64 x 64 Linear is then 64 v_mfma_f32_32x32x2_f32 with the accumulator itself as
+// the B operand (k-step (t, r) contracts the features F and F + 4), LayerNorm a sum over a lane's 32 registers plus one swap of
+// the lane halves, tanh / GELU elementwise.  Per chunk of gd_bc_policy.chunk_rows samples the launches are:
+//   k_bc_embed   a wave per 32 tokens of one kind.  Layer 1 gathers the token's R rows straight from obs [B][R][D] (time is the
+//                slow index inside a token: _unpack_obs's permute), then three more Linear -> LayerNorm -> tanh.  Owns X[b][token].
+//   k_bc_kv      a wave per 32 tokens: K = Wk LN(x) + bk, V = Wv LN(x) + bv.  Owns K[b][token], V[b][token].
+//   k_bc_attn    a wave per 32 queries of one (sample, segment): q = (Wq LN(x) + bq) / 4, then per head a streamed softmax
+//                over the segment's keys in tiles of 32, ascending: S^T = K Q^T is one accumulator (the scores never leave
+//                registers), running max and sum per query, P^T is the B operand of O^T += V^T P^T with no lane movement.
+//                A masked key's score is -FLT_MAX (not -inf), keys past the segment's end do not exist.  Then o_proj + x,
+//                and the MLP (LN, Linear, erf GELU, Linear) + its input.  Owns X[b][its 32 tokens], rewritten in place (no
+//                other wave reads them: keys and values come from K and V).
+//                fusion_attn is one segment of L tokens; ro_attn and rg_attn are two segments of ONE launch.
+//   k_bc_head    a wave per sample, lane per feature, plain arithmetic as policy.hip's ego embedder (one query token has no
+//                tile to fill): both cross attentions (their K / V come from k_bc_kv on the kv_norm'ed tokens), the context,
+//                the GMM head, bc_rule.hpp and every output of the row.
+// 2 F + 2 S + 3 launches per chunk for F fusion and S branch layers.  Every sum has one owner and a fixed order; no atomics;
+// every byte of every output given is stored on every call.  Masks are read with byte loads (their rows have odd pitch).
+// An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation.
+#include <float.h>
+#include <hip/hip_runtime.h>
+
+#include "bc_rule.hpp"
+#include "engine.hpp"
+
+namespace gd {
+
+namespace {
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int F = 64, ROADS = 200, ROAD_K = 13, PARTNER_K = 6, EGO_K = 6, CTX = 192, W64 = F * F;
+constexpr float LN_EPS = 1e-5f;
+constexpr int MAX_HEAD_OUT = 7 * bc_rule::MAX_COMPONENTS;
+
+// offsets inside one self-attention layer, in floats (gpudrive_lab_amd/bc_policy.py `pack_index` states the same order)
+constexpr int S_NG = 0, S_NB = 64, S_QW = 128, S_QB = S_QW + W64, S_KW = S_QB + F, S_KB = S_KW + W64, S_VW = S_KB + F,
+              S_VB = S_VW + W64, S_OW = S_VB + F, S_OB = S_OW + W64, S_MG = S_OB + F, S_MB = S_MG + F, S_W1 = S_MB + F,
+              S_B1 = S_W1 + W64, S_W2 = S_B1 + F, S_B2 = S_W2 + W64, S_SIZE = S_B2 + F;
+// a cross-attention layer: q_norm, kv_norm, then the same fields (q, o and the MLP transposed [in][out], k and v packed)
+constexpr int C_QG = 0, C_QB = 64, C_KVG = 128, C_KVB = 192, C_BODY = 128, C_SIZE = S_SIZE + C_BODY;
+
+struct BCLayout {
+    int net_w0[3], net_rest[3];  // 0: ego, 1: partner, 2: road.  rest: b0, g0, be0, then 3 x (W packed, b, g, be)
+    int self0, cross[2], head_in_w, head_in_b, head_res, head_w, head_b, total;
+};
+
+__host__ __device__ inline int first_steps(int k) { return (k + 1) / 2; }
+
+BCLayout bc_layout(int R, int n_self, int head_layers, int C) {
+    BCLayout L;
+    int o = 0;
+    auto take = [&](int n) { const int at = o; o += n; return at; };
+    const int kin[3] = {EGO_K * R, PARTNER_K * R, ROAD_K * R};
+    for (int e = 0; e < 3; e++) {
+        L.net_w0[e] = take(2 * first_steps(kin[e]) * 64);
+        L.net_rest[e] = take(3 * F + 3 * (W64 + 3 * F));
+    }
+    L.self0 = take(n_self * S_SIZE);
+    L.cross[0] = take(C_SIZE), L.cross[1] = take(C_SIZE);
+    L.head_in_w = take(CTX * F), L.head_in_b = take(F);
+    L.head_res = take(head_layers * (W64 + F));
+    L.head_w = take(F * 7 * C), L.head_b = take(7 * C);
+    L.total = o;
+    return L;
+}
+
+// accumulator register r of lane half h holds this row of a 32 x 32 tile
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// o = W a + b on the transposed tile; w is packed [t2 2][t 2][r 16][lane] = W[32 t2 + c][32 t + acc(r, h)]
+__device__ __forceinline__ void linear64(const f16v (&a)[2], const float *__restrict__ w, const float *__restrict__ b, f16v (&o)[2],
+                                         int lane, int h) {
+#pragma unroll
+    for (int t2 = 0; t2 < 2; t2++) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) o[t2][r] = b[32 * t2 + acc_row(r, h)];
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++)
+                o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[((t2 * 2 + t) * 16 + r) * 64 + lane], a[t][r], o[t2], 0, 0, 0);
+    }
+}
+
+// LayerNorm over the 64 features of this lane's token (32 here, 32 in the other lane half), biased variance, affine; in place
+__device__ __forceinline__ void layer_norm(f16v (&a)[2], const float *__restrict__ g, const float *__restrict__ be, int h) {
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) sum = sum + a[t][r];
+    sum = sum + __shfl_xor(sum, 32);
+    const float mean = sum * (1.f / 64.f);
+    float sq = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            a[t][r] = a[t][r] - mean;
+            sq = sq + a[t][r] * a[t][r];
+        }
+    sq = sq + __shfl_xor(sq, 32);
+    const float rstd = 1.f / sqrtf(sq * (1.f / 64.f) + LN_EPS);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int f = 32 * t + acc_row(r, h);
+            a[t][r] = (a[t][r] * rstd) * g[f] + be[f];
+        }
+}
+
+// a token row of 64 floats (256-byte aligned) <-> the transposed tile: registers 4 q .. 4 q + 3 are 16 contiguous bytes
+__device__ __forceinline__ void load_tok(const float *__restrict__ row, f16v (&a)[2], int h) {
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const f4 v = *reinterpret_cast<const f4 *>(row + 32 * t + 8 * q + 4 * h);
+#pragma unroll
+            for (int j = 0; j < 4; j++) a[t][4 * q + j] = v[j];
+        }
+}
+
+__device__ __forceinline__ void store_tok(float *__restrict__ row, const f16v (&a)[2], int h) {
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            f4 v;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = a[t][4 * q + j];
+            *reinterpret_cast<f4 *>(row + 32 * t + 8 * q + 4 * h) = v;
+        }
+}
+
+__device__ __forceinline__ float gelu_erf(float x) { return (0.5f * x) * (1.f + erff(x * 0.70710678118654752440f)); }
+
+struct BCDims {
+    int A, R, L, D;  // agents, stack, tokens per sample, floats per obs row
+};
+
+// ---- token embedding
+
+template <int KT>
+__device__ __forceinline__ void embed_first(const float *__restrict__ x, int D, int R, int base, int e, const float *__restrict__ w0,
+                                            const float *__restrict__ b0, f16v (&a)[2], int lane, int h) {
+    const int kin = KT * R, ks = first_steps(kin);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) a[t][r] = b0[32 * t + acc_row(r, h)];
+    for (int s = 0; s < ks; s++) {
+        const int k = 2 * s + h;
+        const float xv = k < kin ? x[(size_t)(k / KT) * D + base + e * KT + (k % KT)] : 0.f;
+#pragma unroll
+        for (int t = 0; t < 2; t++) a[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[(t * ks + s) * 64 + lane], xv, a[t], 0, 0, 0);
+    }
+}
+
+// grid (1 + ceil((A - 1) / 32) + 7, rows): tile 0 is the ego, then the partner tiles, then the road tiles
+__global__ __launch_bounds__(64) void k_bc_embed(BCDims d, BCLayout L, const float *__restrict__ blob, const float *__restrict__ obs,
+                                                 float *__restrict__ X) {
+    const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int ptiles = (d.A - 1 + 31) / 32;
+    const int kind = tile == 0 ? 0 : tile <= ptiles ? 1 : 2;
+    const int count = kind == 0 ? 1 : kind == 1 ? d.A - 1 : ROADS;
+    const int e = (kind == 0 ? 0 : kind == 1 ? (tile - 1) * 32 : (tile - 1 - ptiles) * 32) + col;
+    const bool live = e < count;
+    const int ec = live ? e : count - 1;  // a lane past the end computes the last token again and stores nothing
+    const float *__restrict__ x = obs + (size_t)b * d.R * d.D;
+    const float *__restrict__ w0 = blob + L.net_w0[kind];
+    const float *__restrict__ rest = blob + L.net_rest[kind];
+    f16v a[2], o[2];
+    if (kind == 2)
+        embed_first<ROAD_K>(x, d.D, d.R, EGO_K + PARTNER_K * (d.A - 1), ec, w0, rest, a, lane, h);
+    else
+        embed_first<PARTNER_K>(x, d.D, d.R, kind == 0 ? 0 : EGO_K, ec, w0, rest, a, lane, h);
+    layer_norm(a, rest + F, rest + 2 * F, h);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) a[t][r] = tanhf(a[t][r]);
+    for (int i = 0; i < 3; i++) {
+        const float *__restrict__ w = rest + 3 * F + i * (W64 + 3 * F);
+        linear64(a, w, w + W64, o, lane, h);
+        layer_norm(o, w + W64 + F, w + W64 + 2 * F, h);
+#pragma unroll
+        for (int t = 0; t < 2; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) a[t][r] = tanhf(o[t][r]);
+    }
+    const int tok = (kind == 0 ? 0 : kind == 1 ? 1 : d.A) + e;
+    if (live) store_tok(X + ((size_t)b * d.L + tok) * F, a, h);
+}
+
+// ---- attention
+
+struct Seg {
+    int tok0, ntok, tiles;
+    int w;  // k_bc_attn: the layer's offset in the blob.  k_bc_kv: unused
+    int ng, nb, kw, kb, vw, vb;  // k_bc_kv: the norm and the k / v projections, offsets in the blob
+};
+
+struct Segs {
+    Seg s[2];
+    int n;
+};
+
+// grid (sum of tiles, rows)
+__global__ __launch_bounds__(64) void k_bc_kv(BCDims d, Segs sg, const float *__restrict__ blob, const float *__restrict__ X,
+                                              float *__restrict__ Kb, float *__restrict__ Vb) {
+    const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
+    const int b = blockIdx.y;
+    int tile = blockIdx.x;
+    const bool second = tile >= sg.s[0].tiles;
+    const Seg &s = sg.s[second ? 1 : 0];
+    if (second) tile -= sg.s[0].tiles;
+    const int j = tile * 32 + col;
+    const bool live = j < s.ntok;
+    const size_t at = ((size_t)b * d.L + s.tok0 + (live ? j : s.ntok - 1)) * F;
+    f16v x[2], o[2];
+    load_tok(X + at, x, h);
+    layer_norm(x, blob + s.ng, blob + s.nb, h);
+    linear64(x, blob + s.kw, blob + s.kb, o, lane, h);
+    if (live) store_tok(Kb + at, o, h);
+    linear64(x, blob + s.vw, blob + s.vb, o, lane, h);
+    if (live) store_tok(Vb + at, o, h);
+}
+
+// the mask byte of global token g of sample b: the last time index of the dataset's masks
+__device__ __forceinline__ unsigned char token_mask(const BCDims &d, const unsigned char *__restrict__ pm,
+                                                    const unsigned char *__restrict__ rm, int b, int g) {
+    if (g == 0) return 0;
+    if (g < d.A) return pm[((size_t)b * d.R + d.R - 1) * (d.A - 1) + (g - 1)];
+    return rm[((size_t)b * d.R + d.R - 1) * ROADS + (g - d.A)];
+}
+
+constexpr int MAX_TOKENS = 128 + ROADS;
+
+// grid (sum of tiles, rows)
+__global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *__restrict__ blob,
+                                                const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
+                                                float *__restrict__ X, const float *__restrict__ Kb, const float *__restrict__ Vb) {
+    __shared__ unsigned char msk[MAX_TOKENS];
+    const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
+    const int b = blockIdx.y;
+    int tile = blockIdx.x;
+    const bool second = tile >= sg.s[0].tiles;
+    const Seg &s = sg.s[second ? 1 : 0];
+    if (second) tile -= sg.s[0].tiles;
+    const int ntok = s.ntok;
+    for (int j = lane; j < ntok; j += 64) msk[j] = token_mask(d, pm, rm, b, s.tok0 + j);
+    __syncthreads();
+    const float *__restrict__ w = blob + s.w;
+    const int qi = tile * 32 + col;
+    const bool live = qi < ntok;
+    const size_t seg_at = ((size_t)b * d.L + s.tok0) * F;
+    float *__restrict__ xrow = X + seg_at + (size_t)(live ? qi : ntok - 1) * F;
+    f16v x[2], q[2], o[2];
+    load_tok(xrow, x, h);
+    {
+        f16v hn[2] = {x[0], x[1]};
+        layer_norm(hn, w + S_NG, w + S_NB, h);
+        linear64(hn, w + S_QW, w + S_QB, q, lane, h);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) q[t][r] = q[t][r] * 0.25f;  // 16^-1/2
+
+#pragma unroll
+    for (int hd = 0; hd < 4; hd++) {
+        const int t = hd >> 1, rb = 8 * (hd & 1);  // the head's 16 channels are registers rb .. rb + 7 of tile t
+        float m = -INFINITY, l = 0.f;
+        f16v O;
+#pragma unroll
+        for (int r = 0; r < 16; r++) O[r] = 0.f;
+        for (int kb = 0; kb < ntok; kb += 32) {
+            const int key = min(kb + col, ntok - 1);
+            const float *__restrict__ kp = Kb + seg_at + (size_t)key * F + 16 * hd + 4 * h;
+            const f4 k0 = *reinterpret_cast<const f4 *>(kp), k1 = *reinterpret_cast<const f4 *>(kp + 8);
+            f16v sc;
+#pragma unroll
+            for (int r = 0; r < 16; r++) sc[r] = 0.f;
+            // S^T[key][query]: k-step j contracts the channels 16 hd + j and + 4 (then + 8)
+#pragma unroll
+            for (int j = 0; j < 4; j++) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k0[j], q[t][rb + j], sc, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; j++) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(k1[j], q[t][rb + 4 + j], sc, 0, 0, 0);
+            float tm = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int kk = kb + acc_row(r, h);
+                if (kk < ntok) {
+                    if (msk[kk]) sc[r] = -FLT_MAX;
+                    tm = fmaxf(tm, sc[r]);
+                }
+            }
+            tm = fmaxf(tm, __shfl_xor(tm, 32));
+            const float mn = fmaxf(m, tm);  // finite: the first tile always holds a key
+            const float scale = expf(m - mn);
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int kk = kb + acc_row(r, h);
+                const float p = kk < ntok ? expf(sc[r] - mn) : 0.f;
+                sc[r] = p;
+                ps = ps + p;
+            }
+            l = l * scale + ps;
+#pragma unroll
+            for (int r = 0; r < 16; r++) O[r] = O[r] * scale;
+            // O^T[channel][query] += V^T P^T: P's registers are the B operand as they are; rows 16 .. 31 repeat the channels
+            const float *__restrict__ vp = Vb + seg_at + 16 * hd + (col & 15);
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int vk = min(kb + acc_row(r, h), ntok - 1);
+                O = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[(size_t)vk * F], sc[r], O, 0, 0, 0);
+            }
+            m = mn;
+        }
+        const float lt = l + __shfl_xor(l, 32);
+#pragma unroll
+        for (int r = 0; r < 8; r++) o[t][rb + r] = O[r] / lt;
+    }
+
+    f16v y[2], z[2], z1[2];
+    linear64(o, w + S_OW, w + S_OB, y, lane, h);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            y[t][r] = y[t][r] + x[t][r];
+            z[t][r] = y[t][r];
+        }
+    layer_norm(z, w + S_MG, w + S_MB, h);
+    linear64(z, w + S_W1, w + S_B1, z1, lane, h);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) z1[t][r] = gelu_erf(z1[t][r]);
+    linear64(z1, w + S_W2, w + S_B2, z, lane, h);
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) y[t][r] = y[t][r] + z[t][r];
+    if (live) store_tok(xrow, y, h);
+}
+
+// ---- cross attention, context, head, rule: a wave per sample, lane per feature
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
+    return v;
+}
+
+__device__ __forceinline__ float wave_ln(float a, const float *__restrict__ g, const float *__restrict__ be, int lane) {
+    const float mean = wave_sum(a) * (1.f / 64.f);
+    const float dlt = a - mean;
+    const float rstd = 1.f / sqrtf(wave_sum(dlt * dlt) * (1.f / 64.f) + LN_EPS);
+    return (dlt * rstd) * g[lane] + be[lane];
+}
+
+// out[lane] = b[lane] + sum_k wt[k][lane] v[k], ascending k; wt is the weight transposed [in 64][out 64]
+__device__ __forceinline__ float matvec64(const float *__restrict__ wt, const float *__restrict__ b, float v, int lane) {
+    float o = b[lane];
+    for (int k = 0; k < F; k++) o = o + wt[k * F + lane] * __shfl(v, k);
+    return o;
+}
+
+struct BCHeadArgs {
+    int head_layers, C, deterministic;
+    float clip;
+    const float *u, *z, *expert;
+    float *context, *means, *logcov, *cov, *weights, *actions, *nll, *ego_attn_score;
+    int32_t *component;
+};
+
+__global__ __launch_bounds__(64) void k_bc_head(BCDims d, BCLayout L, BCHeadArgs a, const float *__restrict__ blob,
+                                                const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
+                                                const float *__restrict__ X, const float *__restrict__ Kb,
+                                                const float *__restrict__ Vb) {
+    __shared__ float sc[4][ROADS];
+    __shared__ float ctx[CTX];
+    __shared__ float vec[F];
+    __shared__ float raw[MAX_HEAD_OUT];
+    const int lane = threadIdx.x, b = blockIdx.x, hd = lane >> 4;
+    const size_t base = (size_t)b * d.L * F;
+    const float xq = X[base + lane];  // ro_attn's token 0: the query of both cross attentions and the context's first third
+    ctx[lane] = xq;
+    for (int ci = 0; ci < 2; ci++) {
+        const int tok0 = ci ? d.A : 1, nk = ci ? ROADS : d.A - 1;
+        const float *__restrict__ w = blob + L.cross[ci];
+        const float *__restrict__ wb = w + C_BODY;  // the fields S_* of a self layer follow the two norms
+        const float qn = wave_ln(xq, w + C_QG, w + C_QB, lane);
+        vec[lane] = matvec64(wb + S_QW, wb + S_QB, qn, lane) * 0.25f;
+        __syncthreads();
+        for (int j = lane; j < nk; j += 64) {
+            const float *__restrict__ kp = Kb + base + (size_t)(tok0 + j) * F;
+            const bool masked = token_mask(d, pm, rm, b, tok0 + j) != 0;
+            for (int g = 0; g < 4; g++) {
+                float s = 0.f;
+                for (int c = 0; c < 16; c++) s = s + vec[16 * g + c] * kp[16 * g + c];
+                sc[g][j] = masked ? -FLT_MAX : s;
+            }
+        }
+        __syncthreads();
+        for (int g = 0; g < 4; g++) {
+            float m = -INFINITY;
+            for (int j = lane; j < nk; j += 64) m = fmaxf(m, sc[g][j]);
+            m = wave_max(m);
+            float ps = 0.f;
+            for (int j = lane; j < nk; j += 64) {
+                const float p = expf(sc[g][j] - m);
+                sc[g][j] = p;
+                ps = ps + p;
+            }
+            const float S = wave_sum(ps);
+            for (int j = lane; j < nk; j += 64) sc[g][j] = sc[g][j] / S;
+            if (ci == 0 && a.ego_attn_score) {  // the row divided by its own sum, as get_context returns it
+                float ts = 0.f;
+                for (int j = lane; j < nk; j += 64) ts = ts + sc[g][j];
+                const float T = wave_sum(ts);
+                for (int j = lane; j < nk; j += 64) a.ego_attn_score[((size_t)b * 4 + g) * nk + j] = sc[g][j] / T;
+            }
+        }
+        __syncthreads();
+        float o = 0.f;
+        for (int j = 0; j < nk; j++) o = o + sc[hd][j] * Vb[base + (size_t)(tok0 + j) * F + lane];
+        const float y = matvec64(wb + S_OW, wb + S_OB, o, lane) + xq;
+        float zz = wave_ln(y, wb + S_MG, wb + S_MB, lane);
+        zz = gelu_erf(matvec64(wb + S_W1, wb + S_B1, zz, lane));
+        zz = matvec64(wb + S_W2, wb + S_B2, zz, lane);
+        ctx[F * (1 + ci) + lane] = y + zz;
+        __syncthreads();
+    }
+    // the GMM head
+    float hcur = blob[L.head_in_b + lane];
+    for (int k = 0; k < CTX; k++) hcur = hcur + blob[L.head_in_w + k * F + lane] * ctx[k];
+    hcur = fmaxf(hcur, 0.f);
+    for (int i = 0; i < a.head_layers; i++) {
+        const float *__restrict__ w = blob + L.head_res + i * (W64 + F);
+        hcur = hcur + fmaxf(matvec64(w, w + W64, hcur, lane), 0.f);
+    }
+    vec[lane] = hcur;
+    __syncthreads();
+    const int C = a.C, NO = 7 * C;
+    for (int o = lane; o < NO; o += 64) {
+        float r = blob[L.head_b + o];
+        for (int k = 0; k < F; k++) r = r + blob[L.head_w + k * NO + o] * vec[k];
+        raw[o] = r;
+    }
+    __syncthreads();
+    auto load = [&](int k) { return raw[k]; };
+    const bc_rule::Weights ws = bc_rule::weight_stats(C, load);
+    if (a.context)
+        for (int i = lane; i < CTX; i += 64) a.context[(size_t)b * CTX + i] = ctx[i];
+    for (int i = lane; i < 3 * C; i += 64) {
+        const float lc = bc_rule::logcov(C, load, a.clip, i);
+        if (a.means) a.means[(size_t)b * 3 * C + i] = raw[i];
+        if (a.logcov) a.logcov[(size_t)b * 3 * C + i] = lc;
+        if (a.cov) a.cov[(size_t)b * 3 * C + i] = expf(lc);
+    }
+    if (a.weights && lane < C) a.weights[(size_t)b * C + lane] = bc_rule::weight(C, load, ws, lane);
+    if (lane == 0) {
+        const int c = a.deterministic ? bc_rule::mode(C, load, ws) : bc_rule::pick(C, load, ws, a.u[b]);
+        if (a.component) a.component[b] = c;
+        if (a.actions)
+            for (int k = 0; k < 3; k++)
+                a.actions[(size_t)b * 3 + k] = a.deterministic ? raw[3 * c + k] : bc_rule::sampled(C, load, a.clip, c, k, a.z[(size_t)b * 3 + k]);
+        if (a.nll) {
+            const float e[3] = {a.expert[(size_t)b * 3], a.expert[(size_t)b * 3 + 1], a.expert[(size_t)b * 3 + 2]};
+            a.nll[b] = bc_rule::nll(C, load, a.clip, ws, e);
+        }
+    }
+}
+
+// evaluate()'s running sums: one wave; lane i sums the rows i, i + 64, .. in ascending order, then one fixed tree.
+// acc[0] += mean nll; acc[1..3] += mean |pred - expert| per dimension; acc[4..6] += the sums of |pred - expert| where the
+// expert's magnitude exceeds thr[k]; acc[7..9] += their counts; acc[10] += 1 (batches)
+__global__ __launch_bounds__(64) void k_bc_eval_acc(int n, const float *__restrict__ nll, const float *__restrict__ pred,
+                                                    const float *__restrict__ expert, float *__restrict__ acc) {
+    const int lane = threadIdx.x;
+    const float thr[3] = {2.f, 0.035f, 0.023f};
+    float v[10];
+    for (int i = 0; i < 10; i++) v[i] = 0.f;
+    for (int r = lane; r < n; r += 64) {
+        v[0] = v[0] + nll[r];
+        for (int k = 0; k < 3; k++) {
+            const float e = expert[(size_t)r * 3 + k], dlt = fabsf(pred[(size_t)r * 3 + k] - e);
+            v[1 + k] = v[1 + k] + dlt;
+            if (fabsf(e) > thr[k]) v[4 + k] = v[4 + k] + dlt, v[7 + k] = v[7 + k] + 1.f;
+        }
+    }
+    for (int i = 0; i < 10; i++) v[i] = wave_sum(v[i]);
+    if (lane == 0) {
+        for (int i = 0; i < 4; i++) acc[i] = acc[i] + v[i] / (float)n;
+        for (int i = 4; i < 10; i++) acc[i] = acc[i] + v[i];
+        acc[10] = acc[10] + 1.f;
+    }
+}
+
+Seg self_seg(int tok0, int ntok, int w) {
+    Seg s{};
+    s.tok0 = tok0, s.ntok = ntok, s.tiles = (ntok + 31) / 32, s.w = w;
+    s.ng = w + S_NG, s.nb = w + S_NB, s.kw = w + S_KW, s.kb = w + S_KB, s.vw = w + S_VW, s.vb = w + S_VB;
+    return s;
+}
+
+}  // namespace
+
+long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components) {
+    return bc_layout(num_stack, fusion_layers + 2 * branch_layers, head_layers, n_components).total;
+}
+
+long long bc_scratch_floats(int max_agents, int chunk_rows) { return (long long)chunk_rows * 3 * (max_agents + ROADS) * F; }
+
+void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                       const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                       const float *expert_actions, const gd_bc_outputs &out) {
+    const int A = p.max_agents, R = p.num_stack, C = p.n_components;
+    const BCDims d{A, R, A + ROADS, EGO_K + PARTNER_K * (A - 1) + ROAD_K * ROADS};
+    const BCLayout L = bc_layout(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, C);
+    const size_t per = (size_t)p.chunk_rows * d.L * F;
+    float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
+    const int etiles = 1 + (A - 1 + 31) / 32 + (ROADS + 31) / 32;
+    for (int r0 = 0; r0 < n; r0 += p.chunk_rows) {
+        const unsigned rows = (unsigned)std::min(p.chunk_rows, n - r0);
+        const float *o = obs + (size_t)r0 * R * d.D;
+        const unsigned char *pm = partner_mask + (size_t)r0 * R * (A - 1), *rm = road_mask + (size_t)r0 * R * ROADS;
+        hipLaunchKernelGGL(k_bc_embed, dim3((unsigned)etiles, rows), dim3(64), 0, st, d, L, p.blob, o, X);
+        auto layer = [&](const Segs &sg) {
+            unsigned tiles = 0;
+            for (int i = 0; i < sg.n; i++) tiles += (unsigned)sg.s[i].tiles;
+            hipLaunchKernelGGL(k_bc_kv, dim3(tiles, rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
+            hipLaunchKernelGGL(k_bc_attn, dim3(tiles, rows), dim3(64), 0, st, d, sg, p.blob, pm, rm, X, Kb, Vb);
+        };
+        for (int i = 0; i < p.fusion_layers; i++) {
+            Segs sg{};
+            sg.n = 1, sg.s[0] = self_seg(0, d.L, L.self0 + i * S_SIZE);
+            layer(sg);
+        }
+        for (int i = 0; i < p.branch_layers; i++) {
+            Segs sg{};
+            sg.n = 2;
+            sg.s[0] = self_seg(0, A, L.self0 + (p.fusion_layers + i) * S_SIZE);
+            sg.s[1] = self_seg(A, ROADS, L.self0 + (p.fusion_layers + p.branch_layers + i) * S_SIZE);
+            layer(sg);
+        }
+        {
+            Segs sg{};
+            sg.n = 2;
+            for (int ci = 0; ci < 2; ci++) {
+                Seg &s = sg.s[ci];
+                const int w = L.cross[ci], wb = w + C_BODY;
+                s.tok0 = ci ? A : 1, s.ntok = ci ? ROADS : A - 1, s.tiles = (s.ntok + 31) / 32, s.w = w;
+                s.ng = w + C_KVG, s.nb = w + C_KVB, s.kw = wb + S_KW, s.kb = wb + S_KB, s.vw = wb + S_VW, s.vb = wb + S_VB;
+            }
+            hipLaunchKernelGGL(k_bc_kv, dim3((unsigned)(sg.s[0].tiles + sg.s[1].tiles), rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
+        }
+        BCHeadArgs a{};
+        a.head_layers = p.head_layers, a.C = C, a.deterministic = deterministic ? 1 : 0, a.clip = p.clip_value;
+        a.u = u ? u + r0 : nullptr, a.z = z ? z + (size_t)r0 * 3 : nullptr;
+        a.expert = expert_actions ? expert_actions + (size_t)r0 * 3 : nullptr;
+        a.context = out.context ? out.context + (size_t)r0 * CTX : nullptr;
+        a.means = out.means ? out.means + (size_t)r0 * 3 * C : nullptr;
+        a.logcov = out.log_covariances ? out.log_covariances + (size_t)r0 * 3 * C : nullptr;
+        a.cov = out.covariances ? out.covariances + (size_t)r0 * 3 * C : nullptr;
+        a.weights = out.weights ? out.weights + (size_t)r0 * C : nullptr;
+        a.actions = out.actions ? out.actions + (size_t)r0 * 3 : nullptr;
+        a.nll = out.nll ? out.nll + r0 : nullptr;
+        a.ego_attn_score = out.ego_attn_score ? out.ego_attn_score + (size_t)r0 * 4 * (A - 1) : nullptr;
+        a.component = out.component ? out.component + r0 : nullptr;
+        hipLaunchKernelGGL(k_bc_head, dim3(rows), dim3(64), 0, st, d, L, a, p.blob, pm, rm, X, Kb, Vb);
+    }
+}
+
+void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,
+                               float *acc) {
+    hipLaunchKernelGGL(k_bc_eval_acc, dim3(1), dim3(64), 0, st, n, nll, actions, expert_actions, acc);
+}
+
+}  // namespace gd

@@ -1866,6 +1866,59 @@ int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_
     });
 }
 
+// everything gd_bc_forward refuses; nullptr when everything is in order
+static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                                      int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                                      const gd_bc_outputs *out) {
+    if (!p || !obs || !partner_mask || !road_mask || !out) return "null argument";
+    if (!deterministic && (!u || !z)) return "u and z are required unless deterministic";
+    if (out->nll && !expert_actions) return "expert_actions is required with out->nll";
+    if (p->max_agents != 64 && p->max_agents != 128) return "max_agents must be 64 or 128";
+    if (p->num_stack < 1 || p->num_stack > 8) return "num_stack must be in [1, 8]";
+    if (p->fusion_layers < 1 || p->fusion_layers > 4 || p->branch_layers < 1 || p->branch_layers > 4)
+        return "fusion_layers and branch_layers must be in [1, 4]";
+    if (p->head_layers < 0 || p->head_layers > 4) return "head_layers must be in [0, 4]";
+    if (p->n_components < 1 || p->n_components > 16) return "n_components must be in [1, 16]";
+    if (!(p->clip_value == p->clip_value)) return "clip_value must not be NaN";
+    if (p->chunk_rows < 1 || p->chunk_rows > 4096) return "chunk_rows must be in [1, 4096]";
+    if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
+    if (!p->blob || !p->scratch) return "blob and scratch are required";
+    if (p->blob_floats != gd::bc_blob_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+        return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
+    if (p->scratch_floats < gd::bc_scratch_floats(p->max_agents, p->chunk_rows))
+        return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 64";
+    if (misaligned(p->blob, 16) || misaligned(p->scratch, 256)) return "blob must be 16-byte aligned, scratch 256-byte aligned";
+    if (misaligned(obs, 4) || (u && misaligned(u, 4)) || (z && misaligned(z, 4)) || (expert_actions && misaligned(expert_actions, 4)) ||
+        misaligned(out->context, 4) || misaligned(out->means, 4) || misaligned(out->log_covariances, 4) ||
+        misaligned(out->covariances, 4) || misaligned(out->weights, 4) || misaligned(out->actions, 4) || misaligned(out->nll, 4) ||
+        misaligned(out->ego_attn_score, 4) || misaligned(out->component, 4))
+        return "float and int32 buffers must be 4-byte aligned";
+    return nullptr;
+}
+
+int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                  int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                  void *stream) {
+    if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out))
+        return fail(GD_ERR_INVALID, std::string("gd_bc_forward: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_forward(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+                              expert_actions, *out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, const float *expert_actions, float *acc, void *stream) {
+    if (!nll || !actions || !expert_actions || !acc) return fail(GD_ERR_INVALID, "gd_bc_eval_accumulate: null argument");
+    if (n < 1 || n > (1 << 20)) return fail(GD_ERR_INVALID, "gd_bc_eval_accumulate: n must be in [1, 2^20]");
+    if (misaligned(nll, 4) || misaligned(actions, 4) || misaligned(expert_actions, 4) || misaligned(acc, 4))
+        return fail(GD_ERR_INVALID, "gd_bc_eval_accumulate: float buffers must be 4-byte aligned");
+    return guarded([&]() {
+        gd::launch_bc_eval_accumulate(static_cast<hipStream_t>(stream), n, nll, actions, expert_actions, acc);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

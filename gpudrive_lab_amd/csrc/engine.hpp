@@ -263,5 +263,12 @@ void launch_ppo_loss(const gd_ppo &o, hipStream_t st, const float *newlogprob, c
                      const float *old_logprob, const float *old_value, const float *adv, const float *ret, float *d_logprob,
                      float *d_entropy, float *d_value);  // ppo.hip (one launch)
 void launch_ppo_adam(const gd_ppo &o, hipStream_t st, const float *grad);  // ppo.hip (two launches)
+long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);  // bc_policy.hip
+long long bc_scratch_floats(int max_agents, int chunk_rows);  // bc_policy.hip: the size of gd_bc_policy.scratch
+void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                       const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                       const float *expert_actions, const gd_bc_outputs &out);  // bc_policy.hip
+void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,
+                               float *acc);  // bc_policy.hip (one launch)
 
 }  // namespace gd

@@ -602,6 +602,61 @@ int gd_policy_backward_dropout(const gd_policy *p, const gd_policy_grad *g, cons
 int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_ppo *ppo, const gd_dropout *d, const float *obs,
                           const int64_t *actions, const float *old_logprob, const float *old_value, const float *adv,
                           const float *ret, void *stream);
+/* Device BC policy forward: the reference's imitation-learning model, EarlyFusionAttnBCNet in eval mode
+ * (gpudrive/integrations/il/model/model.py, networks.py), on the tensors gd_il_batch writes.  Float32 throughout; the matrix
+ * products over token tiles are v_mfma_f32_32x32x2_f32 chains.  network_dim 64, head_dim 64, 4 heads of 16 channels, 4 embedder
+ * layers, tanh, no dropout, action_dim 3, time_dim 1, no aux head.
+ *   tokens: ego (input: its R six-float blocks in time order), partner e (its R six-float rows), road r (its R thirteen-float
+ *           rows), each through 4 x (Linear, LayerNorm, tanh); L = A + 200 tokens, masked entities embedded like any other
+ *   layer:  h = LN(x); q, k, v = Linear(h), q / 4; scores of masked keys replaced by -FLT_MAX (an all-masked row attends
+ *           uniformly); softmax; o_proj; + x; then + MLP (LN, Linear, erf GELU, Linear)
+ *   fusion_layers over all L tokens, mask [0 | partner_mask[:, R-1] | road_mask[:, R-1]]; branch_layers over the first A
+ *   tokens and, separately, over the 200 road tokens; two cross-attention layers with the ego token (token 0) as the one
+ *   query over the partner tokens and over the road tokens; context = [ego | ego_ro | ego_rg]; the GMM head (192 -> 64 ReLU,
+ *   head_layers x (x + ReLU(Linear x)), 64 -> 7 C) and csrc/bc_rule.hpp.
+ * blob: the weights packed once in the order the kernels read them; gpudrive_lab_amd/bc_policy.py `pack_index` states it.
+ * scratch: chunk_rows * 3 * (A + 200) * 64 floats (token, key and value buffers of one chunk of rows); a larger n runs chunk
+ * after chunk on the stream. */
+typedef struct gd_bc_policy {
+    int32_t max_agents;     /* A: 64 or 128 */
+    int32_t num_stack;      /* R: 1 .. 8 */
+    int32_t fusion_layers;  /* num_layer[0]: 1 .. 4 */
+    int32_t branch_layers;  /* num_layer[1]: 1 .. 4 (ro_attn and rg_attn each) */
+    int32_t head_layers;    /* head_num_layers: 0 .. 4 */
+    int32_t n_components;   /* C: 1 .. 16 */
+    float clip_value;       /* the lower clamp of the raw covariances */
+    int32_t chunk_rows;     /* 1 .. 4096: the rows the scratch holds */
+    const float *blob;      /* blob_floats floats, 16-byte aligned */
+    int64_t blob_floats;    /* checked against the layout's size */
+    float *scratch;         /* scratch_floats floats, 256-byte aligned */
+    int64_t scratch_floats; /* at least chunk_rows * 3 * (A + 200) * 64 */
+} gd_bc_policy;
+/* The outputs of one forward (device pointers); NULL: not written.  Every byte of every one given is stored by every call. */
+typedef struct gd_bc_outputs {
+    float *context;          /* [n][192] */
+    float *means;            /* [n][C][3] */
+    float *log_covariances;  /* [n][C][3] the clamped raw values */
+    float *covariances;      /* [n][C][3] their exp */
+    float *weights;          /* [n][C] */
+    float *actions;          /* [n][3] the deterministic action, or the rule's draw from u and z */
+    float *nll;              /* [n] gmm_loss's per-row value for expert_actions (which is then required) */
+    float *ego_attn_score;   /* [n][4][A - 1] ego_ro_attn's attention row divided by its sum */
+    int32_t *component;      /* [n] the component the action came from */
+} gd_bc_outputs;
+/* obs [n][R][D] float32 (D = 6 + 6 (A - 1) + 2600), 4-byte aligned; partner_mask [n][R][A - 1] and road_mask [n][R][200], one
+ * byte per entry (bool or uint8, non-zero: padding), any alignment; only time index R - 1 is read.  u [n] in [0, 1) and z
+ * [n][3] standard normals, required unless deterministic != 0.  expert_actions [n][3], required with out->nll.
+ * 2 fusion_layers + 2 branch_layers + 3 launches per chunk on `stream`, no host synchronisation, no allocation, no atomics.
+ * GD_ERR_INVALID: a null pointer, a value outside the ranges above, n outside [1, 2^20], blob_floats or scratch_floats not
+ * the layout's, a misaligned pointer. */
+int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                  int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                  void *stream);
+/* One batch of the reference's evaluate() (baselines/il/il.py:99-180) added to acc [11] float32 on the device, one launch, fixed
+ * summation order: acc[0] += mean nll; acc[1..3] += mean |actions - expert| per dimension; acc[4..6] += the sums of
+ * |actions - expert| over the rows with |expert_0| > 2, |expert_1| > 0.035, |expert_2| > 0.023; acc[7..9] += those rows' counts;
+ * acc[10] += 1.  n in [1, 2^20]. */
+int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, const float *expert_actions, float *acc, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.

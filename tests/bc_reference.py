@@ -1,0 +1,205 @@
+"""The BC policy (the reference's EarlyFusionAttnBCNet in eval mode) restated in float64 numpy from a state dict, in this
+repository's own words: what gd_bc_forward is held to.  tests/test_bc_policy.py pins this restatement to the reference
+module itself (tests/golden/bc_forward_*.npz).
+
+`wrong=` switches ONE rule to a plausible mistake, so that the tests can show the comparison catches it:
+    "inf_fill"        masked keys are excluded (probability 0; a row with no key left gives a zero attention output) instead of
+                      scoring -FLT_MAX, under which a row with every key masked attends uniformly
+    "normed_residual" the attention residual adds the LayerNorm'ed input instead of the input
+    "entity_major"    a token's R rows are taken by reshaping [R, n, k] to [n, R k] without the permute
+    "tanh_gelu"       the tanh approximation of GELU instead of the erf form"""
+import math
+
+import numpy as np
+
+FLT_MAX = float(np.finfo(np.float32).max)
+COV_MAX = 3.58352
+ROADS, EGO_K, PARTNER_K, ROAD_K, DIM, HEADS = 200, 6, 6, 13, 64, 4
+_erf = np.vectorize(math.erf, otypes=[np.float64])
+
+
+def _sd64(sd):
+    return {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64) for k, v in sd.items()}
+
+
+def layer_norm(x, sd, name):
+    mean = x.mean(-1, keepdims=True)
+    var = ((x - mean) ** 2).mean(-1, keepdims=True)  # biased
+    return (x - mean) / np.sqrt(var + 1e-5) * sd[name + ".weight"] + sd[name + ".bias"]
+
+
+def linear(x, sd, name):
+    return x @ sd[name + ".weight"].T + sd[name + ".bias"]
+
+
+def gelu(x, wrong=None):
+    if wrong == "tanh_gelu":
+        return 0.5 * x * (1.0 + np.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
+    return 0.5 * x * (1.0 + _erf(x / math.sqrt(2.0)))
+
+
+def unpack(obs, A, wrong=None):
+    """obs [B, R, D] -> ego [B, 6 R], partners [B, A - 1, 6 R], roads [B, 200, 13 R]: time is the slow index inside a token."""
+    B, R, _ = obs.shape
+    ego = obs[:, :, :EGO_K].reshape(B, R * EGO_K)
+    out = [ego]
+    at = EGO_K
+    for n, k in ((A - 1, PARTNER_K), (ROADS, ROAD_K)):
+        x = obs[:, :, at:at + n * k].reshape(B, R, n, k)
+        at += n * k
+        out.append(x.reshape(B, n, R * k) if wrong == "entity_major" else x.transpose(0, 2, 1, 3).reshape(B, n, R * k))
+    return out
+
+
+def embed(x, sd, net):
+    for i in range(4):  # Linear -> [dropout: identity] -> LayerNorm -> tanh
+        x = np.tanh(layer_norm(linear(x, sd, "%s.%d" % (net, 4 * i)), sd, "%s.%d" % (net, 4 * i + 2)))
+    return x
+
+
+def attention(xq, xkv, mask, sd, name, wrong=None):
+    """xq [B, N, 64], xkv [B, J, 64] (both already normed), mask [B, J] bool (True: padding).  Returns (o_proj output
+    [B, N, 64], the attention probabilities [B, 4, N, J])."""
+    B, N, _ = xq.shape
+    J = xkv.shape[1]
+    split = lambda t, n: t.reshape(B, n, HEADS, DIM // HEADS).transpose(0, 2, 1, 3)  # noqa: E731
+    q = split(linear(xq, sd, name + ".q_proj"), N) * (DIM // HEADS) ** -0.5
+    k = split(linear(xkv, sd, name + ".k_proj"), J)
+    v = split(linear(xkv, sd, name + ".v_proj"), J)
+    s = np.einsum("bhic,bhjc->bhij", q, k)
+    m = np.broadcast_to(mask[:, None, None, :], s.shape)
+    if wrong == "inf_fill":
+        s = np.where(m, -np.inf, s)
+        top = s.max(-1, keepdims=True)
+        e = np.where(m, 0.0, np.exp(s - np.where(np.isfinite(top), top, 0.0)))
+        tot = e.sum(-1, keepdims=True)
+        p = e / np.where(tot > 0, tot, 1.0)
+    else:
+        s = np.where(m, -FLT_MAX, s)
+        e = np.exp(s - s.max(-1, keepdims=True))
+        p = e / e.sum(-1, keepdims=True)
+    o = np.einsum("bhij,bhjc->bhic", p, v).transpose(0, 2, 1, 3).reshape(B, N, DIM)
+    return linear(o, sd, name + ".o_proj"), p
+
+
+def mlp(x, sd, name, wrong=None):
+    z = linear(layer_norm(x, sd, name + ".0"), sd, name + ".1")
+    return x + linear(gelu(z, wrong), sd, name + ".3")
+
+
+def self_layer(x, mask, sd, name, wrong=None):
+    h = layer_norm(x, sd, name + ".0.module.norm")
+    o, _ = attention(h, h, mask, sd, name + ".0.module.attention", wrong)
+    x = o + (h if wrong == "normed_residual" else x)
+    return mlp(x, sd, name + ".1.module", wrong)
+
+
+def cross_layer(xq, xkv, mask, sd, name, wrong=None):
+    q = layer_norm(xq, sd, name + ".0.module.q_norm")
+    kv = layer_norm(xkv, sd, name + ".0.module.kv_norm")
+    o, p = attention(q, kv, mask, sd, name + ".0.module.attention", wrong)
+    x = o + (q if wrong == "normed_residual" else xq)
+    return mlp(x, sd, name + ".1.module", wrong), p[:, :, 0, :]
+
+
+def clamp_logcov(raw, clip_value):
+    return np.minimum(np.maximum(raw, clip_value), COV_MAX)
+
+
+def forward(sd, obs, partner_mask, road_mask, max_agents, num_layer, head_num_layers, n_components, clip_value, wrong=None):
+    """Everything the module computes for a batch, float64: context [B, 192], ego_attn_score [B, 4, A - 1], raw [B, 7 C], means
+    and log_covariances and covariances [B, C, 3], weights [B, C]."""
+    sd = _sd64(sd)
+    obs = np.asarray(obs, dtype=np.float64)
+    A, C = max_agents, n_components
+    B = obs.shape[0]
+    pm = np.asarray(partner_mask).astype(bool)[:, -1]
+    rm = np.asarray(road_mask).astype(bool)[:, -1]
+    ego, ro, rg = unpack(obs, A, wrong)
+    x = np.concatenate([embed(ego, sd, "ego_state_net")[:, None], embed(ro, sd, "road_object_net"),
+                        embed(rg, sd, "road_graph_net")], axis=1)
+    ego_mask = np.zeros((B, 1), dtype=bool)
+    all_mask, obj_mask = np.concatenate([ego_mask, pm, rm], 1), np.concatenate([ego_mask, pm], 1)
+    for i in range(num_layer[0]):
+        x = self_layer(x, all_mask, sd, "fusion_attn.%d" % i, wrong)
+    objs, roads = x[:, :A], x[:, A:]
+    for i in range(num_layer[1]):
+        objs = self_layer(objs, obj_mask, sd, "ro_attn.%d" % i, wrong)
+    for i in range(num_layer[1]):
+        roads = self_layer(roads, rm, sd, "rg_attn.%d" % i, wrong)
+    ego_tok = objs[:, :1]
+    ego_ro, score = cross_layer(ego_tok, objs[:, 1:], pm, sd, "ego_ro_attn", wrong)
+    ego_rg, _ = cross_layer(ego_tok, roads, rm, sd, "ego_rg_attn", wrong)
+    context = np.concatenate([ego_tok[:, 0], ego_ro[:, 0], ego_rg[:, 0]], axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        score = score / score.sum(-1, keepdims=True)
+    out = head(sd, context, head_num_layers, C, clip_value)
+    out.update(context=context, ego_attn_score=score)
+    return out
+
+
+def head(sd, context, head_num_layers, C, clip_value):
+    sd = _sd64(sd)
+    x = np.maximum(linear(context, sd, "head.input_layer.0"), 0.0)
+    for i in range(head_num_layers):
+        x = x + np.maximum(linear(x, sd, "head.residual_block.%d.0" % i), 0.0)
+    raw = linear(x, sd, "head.head")
+    return mixture(raw, C, clip_value)
+
+
+def mixture(raw, C, clip_value):
+    """The rule's mixture parameters from the head's raw outputs [B, 7 C] (csrc/bc_rule.hpp)."""
+    raw = np.asarray(raw, dtype=np.float64)
+    B = raw.shape[0]
+    means = raw[:, :3 * C].reshape(B, C, 3)
+    logcov = clamp_logcov(raw[:, 3 * C:6 * C], clip_value).reshape(B, C, 3)
+    w = raw[:, 6 * C:]
+    e = np.exp(w - w.max(-1, keepdims=True))
+    return dict(raw=raw, means=means, log_covariances=logcov, covariances=np.exp(logcov), weights=e / e.sum(-1, keepdims=True))
+
+
+def deterministic_action(means, weights):
+    """(component, action [B, 3]): the mean of the FIRST component of maximal weight."""
+    c = np.argmax(weights, axis=-1)  # numpy's argmax returns the first maximum
+    return c, means[np.arange(len(c)), c]
+
+
+def running_sums(weights):
+    return np.cumsum(np.asarray(weights, dtype=np.float64), axis=-1)
+
+
+def sampled_action(means, covariances, weights, u, z):
+    """(component, action): the first k whose running weight sum exceeds u, the last if none does; mean + sqrt(cov) z."""
+    run = running_sums(weights)
+    over = run > np.asarray(u, dtype=np.float64)[:, None]
+    c = np.where(over.any(-1), over.argmax(-1), weights.shape[-1] - 1)
+    r = np.arange(len(c))
+    return c, means[r, c] + np.sqrt(covariances[r, c]) * np.asarray(z, dtype=np.float64)
+
+
+def nll(means, log_covariances, weights, expert):
+    """gmm_loss's per-row value in closed form; expert [B, 3]."""
+    a = np.asarray(expert, dtype=np.float64).reshape(-1, 1, 3)
+    lp = (-0.5 * ((a - means) ** 2 / np.exp(log_covariances)).sum(-1) - 0.5 * log_covariances.sum(-1)
+          - 1.5 * math.log(2.0 * math.pi))
+    wl = lp + np.log(weights + 1e-8)
+    M = wl.max(-1, keepdims=True)
+    return -(M[:, 0] + np.log(np.exp(wl - M).sum(-1)))
+
+
+def evaluate(batches):
+    """The reference's evaluate() (baselines/il/il.py:99-180) from per-batch (nll [B], predicted [B, 3], expert [B, 3]): its eight
+    numbers.  Per-batch means averaged over batches; the std2 figures are global sums over global counts."""
+    thr = tuple(float(np.float32(v)) for v in (2.0, 0.035, 0.023))  # torch compares a float32 tensor with the scalar in float32
+    loss, d, s, n = 0.0, np.zeros(3), np.zeros(3), np.zeros(3)
+    for row_nll, pred, expert in batches:
+        err = np.abs(np.asarray(pred, np.float64) - np.asarray(expert, np.float64))
+        loss += float(np.mean(row_nll))
+        d += err.mean(0)
+        for k in range(3):
+            big = np.abs(np.asarray(expert, np.float64)[:, k]) > thr[k]
+            s[k] += err[big, k].sum()
+            n[k] += big.sum()
+    nb = len(batches)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return [loss / nb, d[0] / nb, d[1] / nb, d[2] / nb, s[0] / n[0], s[1] / n[1], s[2] / n[2], 0.0]
