@@ -5,3 +5,11 @@ module (reference src/bindings.cpp) on top of the C ABI in include/gpudrive_amd.
 `madrona_gpudrive` package re-exports it so existing `gpudrive.env` code imports it unchanged.
 """
 from ._capi import build, lib_path  # noqa: F401
+
+
+def __getattr__(name):
+    # torch is imported only when the module that needs it is asked for
+    if name == "TrainableBCPolicy":
+        from .bc_train import TrainableBCPolicy
+        return TrainableBCPolicy
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -210,6 +210,12 @@ class GdBCOutputs(C.Structure):
                                           "ego_attn_score", "component")]
 
 
+class GdBCGrad(C.Structure):
+    """gd_bc_grad: the scratch and the partial sums of one gd_bc_backward (device pointers)."""
+    _fields_ = [("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("partials", C.c_void_p), ("grad_floats", C.c_int64),
+                ("num_partials", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -218,7 +224,7 @@ SYMBOLS = [
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
-    "gd_bc_forward", "gd_bc_eval_accumulate",
+    "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -307,6 +313,8 @@ def lib():
     L.gd_ppo_update_dropout.argtypes = [C.POINTER(GdPolicy), C.POINTER(GdPolicyGrad), C.POINTER(GdPPO), D] + [C.c_void_p] * 7
     L.gd_bc_forward.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
                                 [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs), C.c_void_p])
+    L.gd_bc_backward.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] +
+                                 [C.c_void_p] * 5)
     L.gd_bc_eval_accumulate.argtypes = [C.c_int32] + [C.c_void_p] * 5
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]

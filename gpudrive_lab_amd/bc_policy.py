@@ -29,7 +29,8 @@ index of each mask is read.  Masked entities are embedded like any other.
 Scratch (the token, key and value buffers) is sized to `chunk_rows` samples and allocated once; a larger B runs chunk after
 chunk on the stream inside the one C call.  `nbytes(B)` states what a call of B rows touches beyond its inputs.
 
-Not here: the backward and any optimiser step for this model; a closed-loop rollout driver or stacked-row evaluator;
+Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); gradient clipping and AdamW on the device for this
+model; a closed-loop rollout driver or stacked-row evaluator;
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
 `ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64; bf16."""
 import ctypes as C

@@ -21,148 +21,15 @@
 // 2 F + 2 S + 3 launches per chunk for F fusion and S branch layers.  Every sum has one owner and a fixed order; no atomics;
 // every byte of every output given is stored on every call.  Masks are read with byte loads (their rows have odd pitch).
 // An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation.
-#include <float.h>
-#include <hip/hip_runtime.h>
-
-#include "bc_rule.hpp"
-#include "engine.hpp"
+// The backward (bc_grad.hip) reruns these kernels per chunk through launch_bc_forward_chunk and launch_bc_self_layer; its
+// SAVE instantiation of the attention kernel also stores the attention output before o_proj and the softmax's row statistics.
+#include "bc_tile.hpp"
 
 namespace gd {
 
 namespace {
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int F = 64, ROADS = 200, ROAD_K = 13, PARTNER_K = 6, EGO_K = 6, CTX = 192, W64 = F * F;
-constexpr float LN_EPS = 1e-5f;
-constexpr int MAX_HEAD_OUT = 7 * bc_rule::MAX_COMPONENTS;
-
-// offsets inside one self-attention layer, in floats (gpudrive_lab_amd/bc_policy.py `pack_index` states the same order)
-constexpr int S_NG = 0, S_NB = 64, S_QW = 128, S_QB = S_QW + W64, S_KW = S_QB + F, S_KB = S_KW + W64, S_VW = S_KB + F,
-              S_VB = S_VW + W64, S_OW = S_VB + F, S_OB = S_OW + W64, S_MG = S_OB + F, S_MB = S_MG + F, S_W1 = S_MB + F,
-              S_B1 = S_W1 + W64, S_W2 = S_B1 + F, S_B2 = S_W2 + W64, S_SIZE = S_B2 + F;
-// a cross-attention layer: q_norm, kv_norm, then the same fields (q, o and the MLP transposed [in][out], k and v packed)
-constexpr int C_QG = 0, C_QB = 64, C_KVG = 128, C_KVB = 192, C_BODY = 128, C_SIZE = S_SIZE + C_BODY;
-
-struct BCLayout {
-    int net_w0[3], net_rest[3];  // 0: ego, 1: partner, 2: road.  rest: b0, g0, be0, then 3 x (W packed, b, g, be)
-    int self0, cross[2], head_in_w, head_in_b, head_res, head_w, head_b, total;
-};
-
-__host__ __device__ inline int first_steps(int k) { return (k + 1) / 2; }
-
-BCLayout bc_layout(int R, int n_self, int head_layers, int C) {
-    BCLayout L;
-    int o = 0;
-    auto take = [&](int n) { const int at = o; o += n; return at; };
-    const int kin[3] = {EGO_K * R, PARTNER_K * R, ROAD_K * R};
-    for (int e = 0; e < 3; e++) {
-        L.net_w0[e] = take(2 * first_steps(kin[e]) * 64);
-        L.net_rest[e] = take(3 * F + 3 * (W64 + 3 * F));
-    }
-    L.self0 = take(n_self * S_SIZE);
-    L.cross[0] = take(C_SIZE), L.cross[1] = take(C_SIZE);
-    L.head_in_w = take(CTX * F), L.head_in_b = take(F);
-    L.head_res = take(head_layers * (W64 + F));
-    L.head_w = take(F * 7 * C), L.head_b = take(7 * C);
-    L.total = o;
-    return L;
-}
-
-// accumulator register r of lane half h holds this row of a 32 x 32 tile
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// o = W a + b on the transposed tile; w is packed [t2 2][t 2][r 16][lane] = W[32 t2 + c][32 t + acc(r, h)]
-__device__ __forceinline__ void linear64(const f16v (&a)[2], const float *__restrict__ w, const float *__restrict__ b, f16v (&o)[2],
-                                         int lane, int h) {
-#pragma unroll
-    for (int t2 = 0; t2 < 2; t2++) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) o[t2][r] = b[32 * t2 + acc_row(r, h)];
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int r = 0; r < 16; r++)
-                o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[((t2 * 2 + t) * 16 + r) * 64 + lane], a[t][r], o[t2], 0, 0, 0);
-    }
-}
-
-// LayerNorm over the 64 features of this lane's token (32 here, 32 in the other lane half), biased variance, affine; in place
-__device__ __forceinline__ void layer_norm(f16v (&a)[2], const float *__restrict__ g, const float *__restrict__ be, int h) {
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) sum = sum + a[t][r];
-    sum = sum + __shfl_xor(sum, 32);
-    const float mean = sum * (1.f / 64.f);
-    float sq = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            a[t][r] = a[t][r] - mean;
-            sq = sq + a[t][r] * a[t][r];
-        }
-    sq = sq + __shfl_xor(sq, 32);
-    const float rstd = 1.f / sqrtf(sq * (1.f / 64.f) + LN_EPS);
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int f = 32 * t + acc_row(r, h);
-            a[t][r] = (a[t][r] * rstd) * g[f] + be[f];
-        }
-}
-
-// a token row of 64 floats (256-byte aligned) <-> the transposed tile: registers 4 q .. 4 q + 3 are 16 contiguous bytes
-__device__ __forceinline__ void load_tok(const float *__restrict__ row, f16v (&a)[2], int h) {
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const f4 v = *reinterpret_cast<const f4 *>(row + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-            for (int j = 0; j < 4; j++) a[t][4 * q + j] = v[j];
-        }
-}
-
-__device__ __forceinline__ void store_tok(float *__restrict__ row, const f16v (&a)[2], int h) {
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            f4 v;
-#pragma unroll
-            for (int j = 0; j < 4; j++) v[j] = a[t][4 * q + j];
-            *reinterpret_cast<f4 *>(row + 32 * t + 8 * q + 4 * h) = v;
-        }
-}
-
-__device__ __forceinline__ float gelu_erf(float x) { return (0.5f * x) * (1.f + erff(x * 0.70710678118654752440f)); }
-
-struct BCDims {
-    int A, R, L, D;  // agents, stack, tokens per sample, floats per obs row
-};
-
 // ---- token embedding
-
-template <int KT>
-__device__ __forceinline__ void embed_first(const float *__restrict__ x, int D, int R, int base, int e, const float *__restrict__ w0,
-                                            const float *__restrict__ b0, f16v (&a)[2], int lane, int h) {
-    const int kin = KT * R, ks = first_steps(kin);
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) a[t][r] = b0[32 * t + acc_row(r, h)];
-    for (int s = 0; s < ks; s++) {
-        const int k = 2 * s + h;
-        const float xv = k < kin ? x[(size_t)(k / KT) * D + base + e * KT + (k % KT)] : 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; t++) a[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[(t * ks + s) * 64 + lane], xv, a[t], 0, 0, 0);
-    }
-}
 
 // grid (1 + ceil((A - 1) / 32) + 7, rows): tile 0 is the ego, then the partner tiles, then the road tiles
 __global__ __launch_bounds__(64) void k_bc_embed(BCDims d, BCLayout L, const float *__restrict__ blob, const float *__restrict__ obs,
@@ -203,17 +70,6 @@ __global__ __launch_bounds__(64) void k_bc_embed(BCDims d, BCLayout L, const flo
 
 // ---- attention
 
-struct Seg {
-    int tok0, ntok, tiles;
-    int w;  // k_bc_attn: the layer's offset in the blob.  k_bc_kv: unused
-    int ng, nb, kw, kb, vw, vb;  // k_bc_kv: the norm and the k / v projections, offsets in the blob
-};
-
-struct Segs {
-    Seg s[2];
-    int n;
-};
-
 // grid (sum of tiles, rows)
 __global__ __launch_bounds__(64) void k_bc_kv(BCDims d, Segs sg, const float *__restrict__ blob, const float *__restrict__ X,
                                               float *__restrict__ Kb, float *__restrict__ Vb) {
@@ -235,20 +91,17 @@ __global__ __launch_bounds__(64) void k_bc_kv(BCDims d, Segs sg, const float *__
     if (live) store_tok(Vb + at, o, h);
 }
 
-// the mask byte of global token g of sample b: the last time index of the dataset's masks
-__device__ __forceinline__ unsigned char token_mask(const BCDims &d, const unsigned char *__restrict__ pm,
-                                                    const unsigned char *__restrict__ rm, int b, int g) {
-    if (g == 0) return 0;
-    if (g < d.A) return pm[((size_t)b * d.R + d.R - 1) * (d.A - 1) + (g - 1)];
-    return rm[((size_t)b * d.R + d.R - 1) * ROADS + (g - d.A)];
-}
+__device__ __forceinline__ float *bc_save_o(float *osave, float *) { return osave; }
+__device__ __forceinline__ float *bc_save_ml(float *, float *ml) { return ml; }
 
-constexpr int MAX_TOKENS = 128 + ROADS;
-
-// grid (sum of tiles, rows)
+// grid (sum of tiles, rows).  Save = (float *osave, float *ml): also store the attention output before o_proj (osave [b][token][64]) and per (token, head) the softmax's final running
+// max and its sum (ml [b][token][8]: m of the four heads, then the four sums), for the backward
+template <class... Save>
 __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *__restrict__ blob,
                                                 const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
-                                                float *__restrict__ X, const float *__restrict__ Kb, const float *__restrict__ Vb) {
+                                                float *__restrict__ X, const float *__restrict__ Kb, const float *__restrict__ Vb,
+                                                Save... save) {
+    constexpr bool SAVE = sizeof...(Save) > 0;
     __shared__ unsigned char msk[MAX_TOKENS];
     const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
     const int b = blockIdx.y;
@@ -330,6 +183,15 @@ __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *
         const float lt = l + __shfl_xor(l, 32);
 #pragma unroll
         for (int r = 0; r < 8; r++) o[t][rb + r] = O[r] / lt;
+        if constexpr (SAVE) {
+            if (live && h == 0) {
+                float *__restrict__ st = bc_save_ml(save...) + ((size_t)b * d.L + s.tok0 + qi) * 8;
+                st[hd] = m, st[4 + hd] = lt;
+            }
+        }
+    }
+    if constexpr (SAVE) {
+        if (live) store_tok(bc_save_o(save...) + seg_at + (size_t)qi * F, o, h);
     }
 
     f16v y[2], z[2], z1[2];
@@ -356,40 +218,6 @@ __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *
 }
 
 // ---- cross attention, context, head, rule: a wave per sample, lane per feature
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
-    return v;
-}
-
-__device__ __forceinline__ float wave_ln(float a, const float *__restrict__ g, const float *__restrict__ be, int lane) {
-    const float mean = wave_sum(a) * (1.f / 64.f);
-    const float dlt = a - mean;
-    const float rstd = 1.f / sqrtf(wave_sum(dlt * dlt) * (1.f / 64.f) + LN_EPS);
-    return (dlt * rstd) * g[lane] + be[lane];
-}
-
-// out[lane] = b[lane] + sum_k wt[k][lane] v[k], ascending k; wt is the weight transposed [in 64][out 64]
-__device__ __forceinline__ float matvec64(const float *__restrict__ wt, const float *__restrict__ b, float v, int lane) {
-    float o = b[lane];
-    for (int k = 0; k < F; k++) o = o + wt[k * F + lane] * __shfl(v, k);
-    return o;
-}
-
-struct BCHeadArgs {
-    int head_layers, C, deterministic;
-    float clip;
-    const float *u, *z, *expert;
-    float *context, *means, *logcov, *cov, *weights, *actions, *nll, *ego_attn_score;
-    int32_t *component;
-};
 
 __global__ __launch_bounds__(64) void k_bc_head(BCDims d, BCLayout L, BCHeadArgs a, const float *__restrict__ blob,
                                                 const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
@@ -515,13 +343,6 @@ __global__ __launch_bounds__(64) void k_bc_eval_acc(int n, const float *__restri
     }
 }
 
-Seg self_seg(int tok0, int ntok, int w) {
-    Seg s{};
-    s.tok0 = tok0, s.ntok = ntok, s.tiles = (ntok + 31) / 32, s.w = w;
-    s.ng = w + S_NG, s.nb = w + S_NB, s.kw = w + S_KW, s.kb = w + S_KB, s.vw = w + S_VW, s.vb = w + S_VB;
-    return s;
-}
-
 }  // namespace
 
 long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components) {
@@ -530,63 +351,69 @@ long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, in
 
 long long bc_scratch_floats(int max_agents, int chunk_rows) { return (long long)chunk_rows * 3 * (max_agents + ROADS) * F; }
 
+void launch_bc_self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows,
+                          int layer, float *X, float *Kb, float *Vb, float *osave, float *ml) {
+    const BCDims d = bc_dims(p);
+    const Segs sg = bc_layer_segs(p, layer);
+    unsigned tiles = 0;
+    for (int i = 0; i < sg.n; i++) tiles += (unsigned)sg.s[i].tiles;
+    hipLaunchKernelGGL(k_bc_kv, dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
+    if (osave)
+        hipLaunchKernelGGL((k_bc_attn<float *, float *>), dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, pm, rm, X, Kb, Vb,
+                           osave, ml);
+    else
+        hipLaunchKernelGGL(k_bc_attn<>, dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, pm, rm, X, Kb, Vb);
+}
+
+void launch_bc_cross_kv(const gd_bc_policy &p, hipStream_t st, int rows, const float *X, float *Kb, float *Vb) {
+    const Segs sg = bc_cross_segs(p);
+    hipLaunchKernelGGL(k_bc_kv, dim3((unsigned)(sg.s[0].tiles + sg.s[1].tiles), (unsigned)rows), dim3(64), 0, st, bc_dims(p), sg, p.blob,
+                       X, Kb, Vb);
+}
+
+void launch_bc_embed(const gd_bc_policy &p, hipStream_t st, const float *obs, int rows, float *X) {
+    const int A = p.max_agents;
+    const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
+    const int etiles = 1 + (A - 1 + 31) / 32 + (ROADS + 31) / 32;
+    hipLaunchKernelGGL(k_bc_embed, dim3((unsigned)etiles, (unsigned)rows), dim3(64), 0, st, bc_dims(p), L, p.blob, obs, X);
+}
+
+// obs, the masks, u, z, expert_actions and every output are the WHOLE call's; the chunk is its rows r0 .. r0 + rows
+void launch_bc_head(const gd_bc_policy &p, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask, int r0,
+                    int rows, bool deterministic, const float *u, const float *z, const float *expert_actions,
+                    const gd_bc_outputs &out, const float *X, const float *Kb, const float *Vb) {
+    const int A = p.max_agents, R = p.num_stack, C = p.n_components;
+    const BCLayout L = bc_layout(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, C);
+    const unsigned char *pm = partner_mask + (size_t)r0 * R * (A - 1), *rm = road_mask + (size_t)r0 * R * ROADS;
+    BCHeadArgs a{};
+    a.head_layers = p.head_layers, a.C = C, a.deterministic = deterministic ? 1 : 0, a.clip = p.clip_value;
+    a.u = u ? u + r0 : nullptr, a.z = z ? z + (size_t)r0 * 3 : nullptr;
+    a.expert = expert_actions ? expert_actions + (size_t)r0 * 3 : nullptr;
+    a.context = out.context ? out.context + (size_t)r0 * CTX : nullptr;
+    a.means = out.means ? out.means + (size_t)r0 * 3 * C : nullptr;
+    a.logcov = out.log_covariances ? out.log_covariances + (size_t)r0 * 3 * C : nullptr;
+    a.cov = out.covariances ? out.covariances + (size_t)r0 * 3 * C : nullptr;
+    a.weights = out.weights ? out.weights + (size_t)r0 * C : nullptr;
+    a.actions = out.actions ? out.actions + (size_t)r0 * 3 : nullptr;
+    a.nll = out.nll ? out.nll + r0 : nullptr;
+    a.ego_attn_score = out.ego_attn_score ? out.ego_attn_score + (size_t)r0 * 4 * (A - 1) : nullptr;
+    a.component = out.component ? out.component + r0 : nullptr;
+    hipLaunchKernelGGL(k_bc_head, dim3((unsigned)rows), dim3(64), 0, st, bc_dims(p), L, a, p.blob, pm, rm, X, Kb, Vb);
+}
+
 void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                        const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                        const float *expert_actions, const gd_bc_outputs &out) {
-    const int A = p.max_agents, R = p.num_stack, C = p.n_components;
-    const BCDims d{A, R, A + ROADS, EGO_K + PARTNER_K * (A - 1) + ROAD_K * ROADS};
-    const BCLayout L = bc_layout(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, C);
+    const BCDims d = bc_dims(p);
     const size_t per = (size_t)p.chunk_rows * d.L * F;
     float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
-    const int etiles = 1 + (A - 1 + 31) / 32 + (ROADS + 31) / 32;
     for (int r0 = 0; r0 < n; r0 += p.chunk_rows) {
-        const unsigned rows = (unsigned)std::min(p.chunk_rows, n - r0);
-        const float *o = obs + (size_t)r0 * R * d.D;
-        const unsigned char *pm = partner_mask + (size_t)r0 * R * (A - 1), *rm = road_mask + (size_t)r0 * R * ROADS;
-        hipLaunchKernelGGL(k_bc_embed, dim3((unsigned)etiles, rows), dim3(64), 0, st, d, L, p.blob, o, X);
-        auto layer = [&](const Segs &sg) {
-            unsigned tiles = 0;
-            for (int i = 0; i < sg.n; i++) tiles += (unsigned)sg.s[i].tiles;
-            hipLaunchKernelGGL(k_bc_kv, dim3(tiles, rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
-            hipLaunchKernelGGL(k_bc_attn, dim3(tiles, rows), dim3(64), 0, st, d, sg, p.blob, pm, rm, X, Kb, Vb);
-        };
-        for (int i = 0; i < p.fusion_layers; i++) {
-            Segs sg{};
-            sg.n = 1, sg.s[0] = self_seg(0, d.L, L.self0 + i * S_SIZE);
-            layer(sg);
-        }
-        for (int i = 0; i < p.branch_layers; i++) {
-            Segs sg{};
-            sg.n = 2;
-            sg.s[0] = self_seg(0, A, L.self0 + (p.fusion_layers + i) * S_SIZE);
-            sg.s[1] = self_seg(A, ROADS, L.self0 + (p.fusion_layers + p.branch_layers + i) * S_SIZE);
-            layer(sg);
-        }
-        {
-            Segs sg{};
-            sg.n = 2;
-            for (int ci = 0; ci < 2; ci++) {
-                Seg &s = sg.s[ci];
-                const int w = L.cross[ci], wb = w + C_BODY;
-                s.tok0 = ci ? A : 1, s.ntok = ci ? ROADS : A - 1, s.tiles = (s.ntok + 31) / 32, s.w = w;
-                s.ng = w + C_KVG, s.nb = w + C_KVB, s.kw = wb + S_KW, s.kb = wb + S_KB, s.vw = wb + S_VW, s.vb = wb + S_VB;
-            }
-            hipLaunchKernelGGL(k_bc_kv, dim3((unsigned)(sg.s[0].tiles + sg.s[1].tiles), rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
-        }
-        BCHeadArgs a{};
-        a.head_layers = p.head_layers, a.C = C, a.deterministic = deterministic ? 1 : 0, a.clip = p.clip_value;
-        a.u = u ? u + r0 : nullptr, a.z = z ? z + (size_t)r0 * 3 : nullptr;
-        a.expert = expert_actions ? expert_actions + (size_t)r0 * 3 : nullptr;
-        a.context = out.context ? out.context + (size_t)r0 * CTX : nullptr;
-        a.means = out.means ? out.means + (size_t)r0 * 3 * C : nullptr;
-        a.logcov = out.log_covariances ? out.log_covariances + (size_t)r0 * 3 * C : nullptr;
-        a.cov = out.covariances ? out.covariances + (size_t)r0 * 3 * C : nullptr;
-        a.weights = out.weights ? out.weights + (size_t)r0 * C : nullptr;
-        a.actions = out.actions ? out.actions + (size_t)r0 * 3 : nullptr;
-        a.nll = out.nll ? out.nll + r0 : nullptr;
-        a.ego_attn_score = out.ego_attn_score ? out.ego_attn_score + (size_t)r0 * 4 * (A - 1) : nullptr;
-        a.component = out.component ? out.component + r0 : nullptr;
-        hipLaunchKernelGGL(k_bc_head, dim3(rows), dim3(64), 0, st, d, L, a, p.blob, pm, rm, X, Kb, Vb);
+        const int rows = std::min(p.chunk_rows, n - r0);
+        const unsigned char *pm = partner_mask + (size_t)r0 * d.R * (d.A - 1), *rm = road_mask + (size_t)r0 * d.R * ROADS;
+        launch_bc_embed(p, st, obs + (size_t)r0 * d.R * d.D, rows, X);
+        for (int i = 0; i < p.fusion_layers + p.branch_layers; i++) launch_bc_self_layer(p, st, pm, rm, rows, i, X, Kb, Vb, nullptr, nullptr);
+        launch_bc_cross_kv(p, st, rows, X, Kb, Vb);
+        launch_bc_head(p, st, partner_mask, road_mask, r0, rows, deterministic, u, z, expert_actions, out, X, Kb, Vb);
     }
 }
 

@@ -1908,6 +1908,38 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     });
 }
 
+int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                   const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
+                   void *stream) {
+    const char *why = nullptr;
+    gd_bc_outputs none{};
+    if (!g || !expert_actions || !grad_nll || !grad)
+        why = "null argument";
+    else if ((why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &none)))
+        ;
+    else if (g->num_partials < 1 || g->num_partials > 4096)
+        why = "num_partials must be in [1, 4096]";
+    else if (g->reserved != 0)
+        why = "reserved must be 0";
+    else if (!g->scratch || !g->partials)
+        why = "scratch and partials are required";
+    else if (g->grad_floats != gd::bc_grad_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+        why = "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
+    else if (g->scratch_floats < gd::bc_grad_scratch_floats(p->max_agents, p->chunk_rows, p->fusion_layers, p->branch_layers, p->blob_floats))
+        why = "grad scratch_floats is below blob_floats rounded up to 64 + chunk_rows * (max_agents + 200) * (64 * (fusion_layers + "
+              "branch_layers + 5) + 16)";
+    else if (misaligned(g->scratch, 256) || misaligned(g->partials, 16) || misaligned(grad, 16))
+        why = "grad scratch must be 256-byte aligned, partials and grad 16-byte aligned";
+    else if (misaligned(grad_nll, 4) || misaligned(nll, 4))
+        why = "float buffers must be 4-byte aligned";
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_backward: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_backward(*p, *g, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll,
+                               grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, const float *expert_actions, float *acc, void *stream) {
     if (!nll || !actions || !expert_actions || !acc) return fail(GD_ERR_INVALID, "gd_bc_eval_accumulate: null argument");
     if (n < 1 || n > (1 << 20)) return fail(GD_ERR_INVALID, "gd_bc_eval_accumulate: n must be in [1, 2^20]");

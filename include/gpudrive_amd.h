@@ -657,6 +657,37 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
  * |actions - expert| over the rows with |expert_0| > 2, |expert_1| > 0.035, |expert_2| > 0.023; acc[7..9] += those rows' counts;
  * acc[10] += 1.  n in [1, 2^20]. */
 int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, const float *expert_actions, float *acc, void *stream);
+/* Device BC policy backward: the gradient of sum_b grad_nll[b] * nll[b] (nll: gd_bc_forward's out->nll, gmm_loss's per-row
+ * value) with respect to every parameter, float32, flat in the state dict's order (gpudrive_lab_amd/bc_policy.py
+ * `expected_shapes`) and each tensor's natural row-major layout.  No gradient with respect to obs.  It follows torch's autograd
+ * of the reference: a masked score receives no gradient (a row whose keys are all masked passes its uniform share to the
+ * values and nothing to queries and keys), the covariance clamp passes the gradient on [clip_value, 3.58352] bounds
+ * included and an exact 0 outside (csrc/bc_grad_rule.hpp), the head's ReLU passes nothing at a pre-activation <= 0.
+ * Memory does not depend on n: per chunk of p->chunk_rows rows the forward is run again by gd_bc_forward's own kernels (the
+ * nll is therefore gd_bc_forward's bit for bit), the inputs of the self-attention layers are kept in `scratch`, and layer by
+ * layer, last to first, the layer's keys, values, attention output and softmax row statistics are recomputed and its
+ * backward runs: scores are rebuilt per 32 x 32 tile from q, k and the statistics, once with a query tile owning dQ and
+ * walking the keys, once with a key tile owning dK and dV and walking the queries.  No tensor with an L x L extent exists.
+ * No atomics: weight gradients are summed by num_partials workgroups, workgroup w over the (row, tile) pairs w, w +
+ * num_partials, .. of a launch in ascending order into partials[w], across chunks; the last launch adds the partials in
+ * index order.  Equal inputs, chunk_rows and num_partials give equal bits.  Every element of scratch that is read, of
+ * partials and of grad is stored by every call. */
+typedef struct gd_bc_grad {
+    float *scratch;         /* scratch_floats floats, 256-byte aligned */
+    int64_t scratch_floats; /* at least blob_floats rounded up to 64 + chunk_rows * (A + 200) * (64 * (fusion_layers +
+                             * branch_layers + 5) + 16) */
+    float *partials;        /* [num_partials][grad_floats], 16-byte aligned */
+    int64_t grad_floats;    /* the parameters' count: checked against the layout's */
+    int32_t num_partials;   /* 1 .. 4096 */
+    int32_t reserved;       /* 0 */
+} gd_bc_grad;
+/* obs, the masks and expert_actions as gd_bc_forward takes them; grad_nll [n] the upstream gradient; nll [n] or NULL receives
+ * the recomputed forward's value; grad [grad_floats], 16-byte aligned.  p->scratch is used as by gd_bc_forward.  No host
+ * synchronisation, no allocation.  GD_ERR_INVALID, before any launch: whatever gd_bc_forward refuses, a null or misaligned
+ * buffer, scratch_floats or grad_floats not the layout's, num_partials outside [1, 4096]. */
+int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                   const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
+                   void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
