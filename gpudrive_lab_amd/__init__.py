@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "TrainableBCPolicy":
         from .bc_train import TrainableBCPolicy
         return TrainableBCPolicy
+    if name == "DeviceBC":
+        from .bc_opt import DeviceBC
+        return DeviceBC
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

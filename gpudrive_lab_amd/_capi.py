@@ -216,6 +216,21 @@ class GdBCGrad(C.Structure):
                 ("num_partials", C.c_int32), ("reserved", C.c_int32)]
 
 
+BC_STATS = ("loss", "dx_loss", "dy_loss", "dyaw_loss", "grad_norm", "max_grad_norm")  # gd_bc_opt.stats
+
+
+class GdBCOpt(C.Structure):
+    """gd_bc_opt: the hyper-parameters, the configuration, the device scalars, the optimiser state and the scratch of the device
+    BC update (device pointers)."""
+    _fields_ = ([(n, C.c_float) for n in ("max_grad_norm", "eps", "weight_decay", "stats_scale")] +
+                [("beta1", C.c_double), ("beta2", C.c_double), ("grad_floats", C.c_int64), ("blob_floats", C.c_int64)] +
+                [(n, C.c_int32) for n in ("num_stack", "fusion_layers", "branch_layers", "head_layers", "n_components",
+                                          "num_tensors", "max_rows", "reserved")] +
+                [(n, C.c_void_p) for n in ("tensor_end", "lr", "step", "beta_pow", "params", "exp_avg", "exp_avg_sq", "blob",
+                                           "blob_of", "stats", "stats_sum", "max_grad_tensor", "tensor_norms", "scal",
+                                           "actions", "nll", "grad_nll", "grad")])
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -224,7 +239,7 @@ SYMBOLS = [
     "gd_rollout_store", "gd_rollout_sort", "gd_rollout_gae", "gd_rollout_gather", "gd_policy_forward",
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
-    "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate",
+    "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
     "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
@@ -316,6 +331,10 @@ def lib():
     L.gd_bc_backward.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] +
                                  [C.c_void_p] * 5)
     L.gd_bc_eval_accumulate.argtypes = [C.c_int32] + [C.c_void_p] * 5
+    L.gd_bc_train_rows.argtypes = [C.POINTER(GdBCOpt), C.c_int32] + [C.c_void_p] * 5
+    L.gd_bc_adamw.argtypes = [C.POINTER(GdBCOpt), C.c_void_p, C.c_void_p]
+    L.gd_bc_update.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.POINTER(GdBCOpt)] + [C.c_void_p] * 3 +
+                               [C.c_int32, C.c_void_p, C.c_void_p])
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -15,7 +15,7 @@ with an L x L extent exists anywhere -- the scores of a (sample, head, 32-query 
     means, cov, weights = bc.gmm_params(obs, pm, rm)              # [B,1,C,3], [B,1,C,3], [B,1,C]
     nll     = bc.nll(obs, pm, rm, expert)                         # [B] (gmm_loss's detached second value)
     stats   = bc.evaluate(ds, batch_size=512)                     # il.py:99-180's eight numbers, ONE host read
-    bc.load_state_dict(sd)                                        # re-pack after an optimiser step
+    bc.load_state_dict(sd)                                        # re-pack after a torch optimiser's step
 
 The state dict carries the reference module's own parameter names (`expected_shapes`), so a `torch.save`d reference model
 loads without renaming.  The draw is this project's: the reference samples the component with `dist.Categorical` and the
@@ -29,8 +29,9 @@ index of each mask is read.  Masked entities are embedded like any other.
 Scratch (the token, key and value buffers) is sized to `chunk_rows` samples and allocated once; a larger B runs chunk after
 chunk on the stream inside the one C call.  `nbytes(B)` states what a call of B rows touches beyond its inputs.
 
-Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); gradient clipping and AdamW on the device for this
-model; a closed-loop rollout driver or stacked-row evaluator;
+Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); the gradient step with clipping and AdamW
+(`bc_opt.DeviceBC`, gd_bc_update, whose `policy` is one of these and follows the optimiser in place); a closed-loop rollout
+driver or stacked-row evaluator;
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
 `ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64; bf16."""
 import ctypes as C

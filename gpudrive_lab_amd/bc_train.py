@@ -8,6 +8,7 @@
     loss = tbp(obs, pm, rm, expert).mean()                        # gmm_loss(...)[0]
     opt.zero_grad(); loss.backward(); torch.nn.utils.clip_grad_norm_(tbp.parameters(), 20); opt.step()
     bc.load_state_dict(tbp.state_dict())                          # a DeviceBCPolicy follows
+(`bc_opt.DeviceBC` is these four lines as one C call, with the evaluation policy following in place.)
 
 `tbp(...)` is `DeviceBCPolicy.nll` bit for bit on the same weights (the same C call).  Its backward is one more C call,
 `gd_bc_backward` (csrc/bc_grad.hip): per chunk of `chunk_rows` rows it runs the forward again with the forward's own kernels,
@@ -22,8 +23,8 @@ masked score receives none (a row whose keys are all masked gives its uniform sh
 and keys), the covariance clamp passes the gradient on [clip_value, 3.58352], bounds included, and an exact 0 outside, the
 head's ReLU passes nothing at a pre-activation <= 0.  `obs` gets no gradient.
 
-Not here: gradient clipping and AdamW on the device (the caller's torch code does them, elementwise over about 0.3 M
-parameters); non-zero dropout; `aux_head` / `use_tom`; `l1_loss` / `focal_loss`; bf16; a gradient with respect to the
+Not here: gradient clipping and AdamW (any torch optimiser works on this module; `bc_opt.DeviceBC` is the whole step on the
+device, gd_bc_update, without it); non-zero dropout; `aux_head` / `use_tom`; `l1_loss` / `focal_loss`; bf16; a gradient with respect to the
 observations; any tuning beyond one wave per workgroup."""
 import ctypes as C
 

@@ -1908,9 +1908,10 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     });
 }
 
-int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
-                   const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
-                   void *stream) {
+// everything gd_bc_backward refuses; nullptr when everything is in order
+static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                                       const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,
+                                       const float *nll, const float *grad) {
     const char *why = nullptr;
     gd_bc_outputs none{};
     if (!g || !expert_actions || !grad_nll || !grad)
@@ -1932,10 +1933,108 @@ int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs,
         why = "grad scratch must be 256-byte aligned, partials and grad 16-byte aligned";
     else if (misaligned(grad_nll, 4) || misaligned(nll, 4))
         why = "float buffers must be 4-byte aligned";
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_backward: ") + why);
+    return why;
+}
+
+int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                   const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
+                   void *stream) {
+    if (const char *why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll, grad))
+        return fail(GD_ERR_INVALID, std::string("gd_bc_backward: ") + why);
     return guarded([&]() {
         gd::launch_bc_backward(*p, *g, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll,
                                grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything gd_bc_train_rows refuses; nullptr when everything is in order
+static const char *bc_train_rows_problem(const gd_bc_opt *o, int32_t n, const float *nll, const float *actions,
+                                         const float *expert_actions, const float *grad_nll) {
+    if (!o || !nll || !actions || !expert_actions || !grad_nll) return "null argument";
+    if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
+    if (!o->stats || !o->stats_sum) return "stats and stats_sum are required";
+    if (misaligned(nll, 4) || misaligned(actions, 4) || misaligned(expert_actions, 4) || misaligned(grad_nll, 4) ||
+        misaligned(o->stats, 4) || misaligned(o->stats_sum, 4))
+        return "float buffers must be 4-byte aligned";
+    return nullptr;
+}
+
+int gd_bc_train_rows(const gd_bc_opt *opt, int32_t n, const float *nll, const float *actions, const float *expert_actions,
+                     float *grad_nll, void *stream) {
+    if (const char *why = bc_train_rows_problem(opt, n, nll, actions, expert_actions, grad_nll))
+        return fail(GD_ERR_INVALID, std::string("gd_bc_train_rows: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_train_rows(*opt, static_cast<hipStream_t>(stream), n, nll, actions, expert_actions, grad_nll);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything gd_bc_adamw refuses; nullptr when everything is in order
+static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
+    if (!o || !grad) return "null argument";
+    if (o->num_stack < 1 || o->num_stack > 8) return "num_stack must be in [1, 8]";
+    if (o->fusion_layers < 1 || o->fusion_layers > 4 || o->branch_layers < 1 || o->branch_layers > 4)
+        return "fusion_layers and branch_layers must be in [1, 4]";
+    if (o->head_layers < 0 || o->head_layers > 4) return "head_layers must be in [0, 4]";
+    if (o->n_components < 1 || o->n_components > 16) return "n_components must be in [1, 16]";
+    if (o->reserved != 0) return "reserved must be 0";
+    if (o->grad_floats != gd::bc_grad_floats(o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+        return "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
+    if (o->blob_floats != gd::bc_blob_floats(o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+        return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
+    if (o->num_tensors != gd::bc_num_tensors(o->fusion_layers, o->branch_layers, o->head_layers))
+        return "num_tensors is not the state dict's tensor count for these layer counts";
+    if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0)) return "betas must be in [0, 1)";
+    if (!(o->eps > 0.f) || !(o->max_grad_norm > 0.f)) return "eps and max_grad_norm must be positive";
+    if (!(o->weight_decay >= 0.f) || !std::isfinite(o->weight_decay)) return "weight_decay must be finite and not negative";
+    if (!o->tensor_end || !o->lr || !o->step || !o->beta_pow || !o->params || !o->exp_avg || !o->exp_avg_sq || !o->blob ||
+        !o->blob_of || !o->stats || !o->stats_sum || !o->max_grad_tensor || !o->tensor_norms || !o->scal)
+        return "tensor_end, lr, step, beta_pow, params, exp_avg, exp_avg_sq, blob, blob_of, stats, stats_sum, max_grad_tensor, "
+               "tensor_norms and scal are required";
+    if (misaligned(o->beta_pow, 8) || misaligned(o->scal, 8) || misaligned(grad, 4) || misaligned(o->tensor_end, 4) ||
+        misaligned(o->lr, 4) || misaligned(o->step, 4) || misaligned(o->params, 4) || misaligned(o->exp_avg, 4) ||
+        misaligned(o->exp_avg_sq, 4) || misaligned(o->blob, 4) || misaligned(o->blob_of, 4) || misaligned(o->stats, 4) ||
+        misaligned(o->stats_sum, 4) || misaligned(o->max_grad_tensor, 4) || misaligned(o->tensor_norms, 4))
+        return "beta_pow and scal must be 8-byte aligned, the other buffers 4-byte aligned";
+    return nullptr;
+}
+
+int gd_bc_adamw(const gd_bc_opt *opt, const float *grad, void *stream) {
+    if (const char *why = bc_adamw_problem(opt, grad)) return fail(GD_ERR_INVALID, std::string("gd_bc_adamw: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_adamw(*opt, static_cast<hipStream_t>(stream), grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs, const uint8_t *partner_mask,
+                 const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream) {
+    if (!p || !g || !opt) return fail(GD_ERR_INVALID, "gd_bc_update: null argument");
+    const gd_bc_opt &o = *opt;
+    gd_bc_outputs out{};
+    out.actions = o.actions, out.nll = o.nll;
+    const char *why = nullptr;
+    if (!expert_actions || !o.actions || !o.nll || !o.grad_nll || !o.grad)
+        why = "null argument (expert_actions, or opt's actions, nll, grad_nll or grad)";
+    if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out);
+    if (!why) why = bc_train_rows_problem(opt, n, o.nll, o.actions, expert_actions, o.grad_nll);
+    if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
+    if (!why) why = bc_adamw_problem(opt, o.grad);
+    if (!why && (o.max_rows < 1 || o.max_rows > (1 << 20))) why = "max_rows must be in [1, 2^20]";
+    if (!why && n > o.max_rows) why = "n is above max_rows (the row scratch holds max_rows rows)";
+    if (!why && (p->num_stack != o.num_stack || p->fusion_layers != o.fusion_layers || p->branch_layers != o.branch_layers ||
+                 p->head_layers != o.head_layers || p->n_components != o.n_components || p->blob_floats != o.blob_floats ||
+                 g->grad_floats != o.grad_floats))
+        why = "the configurations and sizes of the policy, the backward and opt differ";
+    if (!why && p->blob != o.blob) why = "the policy's blob must be opt's (the optimiser step updates it in place)";
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_update: ") + why);
+    return guarded([&]() {
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        gd::launch_bc_forward(*p, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
+        gd::launch_bc_train_rows(o, st, n, o.nll, o.actions, expert_actions, o.grad_nll);
+        gd::launch_bc_backward(*p, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
+        gd::launch_bc_adamw(o, st, o.grad);
         HIP_CHECK(hipGetLastError());
     });
 }

@@ -286,5 +286,10 @@ long long bc_grad_scratch_floats(int max_agents, int chunk_rows, int fusion_laye
 void launch_bc_backward(const gd_bc_policy &p, const gd_bc_grad &g, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                         const unsigned char *road_mask, int n, const float *expert_actions, const float *grad_nll, float *nll,
                         float *grad);
+// bc_opt.hip
+int bc_num_tensors(int fusion_layers, int branch_layers, int head_layers);  // the tensors of the state dict
+void launch_bc_train_rows(const gd_bc_opt &o, hipStream_t st, int n, const float *nll, const float *actions,
+                          const float *expert_actions, float *grad_nll);  // (one launch)
+void launch_bc_adamw(const gd_bc_opt &o, hipStream_t st, const float *grad);  // (three launches)
 
 }  // namespace gd

@@ -688,6 +688,71 @@ typedef struct gd_bc_grad {
 int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                    const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
                    void *stream);
+/* Device BC update: the rest of one gradient step of the reference's imitation learning (baselines/il/il.py:267-303) around
+ * gd_bc_forward and gd_bc_backward -- the step's statistics and the upstream gradient of loss.mean(), clip_grad_norm_, the
+ * reference's get_grad_norm and torch.optim.AdamW (no amsgrad, no maximize).  The rule, with every rounding and the order of
+ * every sum, is csrc/bc_opt_rule.hpp.  Every pointer is a device pointer owned by the caller, and every value that changes
+ * between calls (the learning rate, the step count, the running products of the betas) lives on the device.  G = grad_floats,
+ * T = num_tensors: the flat gradient cut into the state dict's tensors (gpudrive_lab_amd/bc_policy.py `expected_shapes`). */
+typedef struct gd_bc_opt {
+    float max_grad_norm;    /* > 0 */
+    float eps;              /* AdamW's, > 0 */
+    float weight_decay;     /* >= 0, finite */
+    float stats_scale;      /* every call adds stats_scale * its statistics into stats_sum */
+    double beta1, beta2;    /* in [0, 1) */
+    int64_t grad_floats;    /* G, checked against the parameter count of the configuration below */
+    int64_t blob_floats;    /* checked against the layout's size */
+    int32_t num_stack, fusion_layers, branch_layers, head_layers, n_components; /* gd_bc_policy's: they fix G, T and the blob */
+    int32_t num_tensors;    /* T, checked against the layout's (at most 288) */
+    int32_t max_rows;       /* the rows the row scratch below holds, 1 .. 2^20 */
+    int32_t reserved;       /* 0 */
+    const int32_t *tensor_end; /* [T] cumulative element counts: tensor t is [tensor_end[t - 1], tensor_end[t]) */
+    const float *lr;        /* [1] the learning rate */
+    int32_t *step;          /* [1] optimiser steps taken */
+    double *beta_pow;       /* [2] beta1^step, beta2^step (1, 1 before the first step), 8-byte aligned */
+    float *params;          /* [G + 1] the weights in the flat layout; element G is a zero nobody writes */
+    float *exp_avg;         /* [G] AdamW's first moment */
+    float *exp_avg_sq;      /* [G] AdamW's second moment */
+    float *blob;            /* gd_bc_policy.blob: every updated weight is stored here too; padding entries are never written */
+    const int32_t *blob_of; /* [G] blob_of[e]: the one place of parameter e in blob (the inverse of the layout) */
+    float *stats;           /* [6] the last call's loss, dx_loss, dy_loss, dyaw_loss (gd_bc_train_rows), grad_norm (before
+                             * clipping) and max_grad_norm (the largest tensor norm after clipping) (gd_bc_adamw) */
+    float *stats_sum;       /* [6] running sums of stats_scale * stats; the caller zeroes them when it reads them */
+    int32_t *max_grad_tensor; /* [1] the first tensor that attains the largest norm */
+    float *tensor_norms;    /* [T] every tensor's gradient norm before clipping */
+    float *scal;            /* [4 + 2 T] scratch of gd_bc_adamw, 8-byte aligned: total, coef, bc1, rbc2, then the tensors'
+                             * sums of squares as float64 */
+    /* scratch of gd_bc_update only: */
+    float *actions;         /* [max_rows][3] the deterministic actions of the weights before the step */
+    float *nll;             /* [max_rows] */
+    float *grad_nll;        /* [max_rows] */
+    float *grad;            /* [G] the gradient, 16-byte aligned */
+} gd_bc_opt;
+/* The rows of one step: from nll [n] and actions [n][3] (gd_bc_forward's, deterministic) and expert_actions [n][3], stats[0..4)
+ * = the means of nll and of |actions - expert_actions| per dimension, stats_scale * them added into stats_sum[0..4), and
+ * grad_nll[b] = 1 / n for every b < n.  One launch on `stream` (a single workgroup of 256 lanes: the sums have one fixed
+ * order), no host synchronisation, no allocation, no atomics.  Uses of opt: stats_scale, stats, stats_sum.
+ * GD_ERR_INVALID: a null pointer, n outside [1, 2^20], a misaligned pointer. */
+int gd_bc_train_rows(const gd_bc_opt *opt, int32_t n, const float *nll, const float *actions, const float *expert_actions,
+                     float *grad_nll, void *stream);
+/* Gradient clipping and one AdamW step on grad [G] float32: the tensors' norms (tensor_norms, every element stored), the total
+ * norm, the coefficient, the moments and the weights by the rule; each updated weight is stored to params[e] and to
+ * blob[blob_of[e]] by the same lane, so the forward's packed weights follow without a re-pack; stats[4] = the norm before
+ * clipping, stats[5] = the largest tensor norm after it (both also into stats_sum), max_grad_tensor its tensor; step and
+ * beta_pow advance by one.  Three launches on `stream`: a workgroup per tensor, one workgroup that leaves the step's scalars in
+ * scal, a lane per parameter that reads them.  No host synchronisation, no allocation, no atomics; no workgroup reads a word
+ * another workgroup of the same launch writes.
+ * GD_ERR_INVALID, before any launch: a null pointer, a configuration outside gd_bc_policy's ranges, grad_floats, blob_floats or
+ * num_tensors not the layout's, betas outside [0, 1), eps or max_grad_norm not positive, a negative or non-finite
+ * weight_decay, a non-zero reserved, a misaligned pointer. */
+int gd_bc_adamw(const gd_bc_opt *opt, const float *grad, void *stream);
+/* One whole gradient step as one call: gd_bc_forward(p, deterministic) with actions and nll into opt's row scratch,
+ * gd_bc_train_rows, gd_bc_backward(grad_nll of the scratch, nll NULL) into opt->grad, gd_bc_adamw -- on `stream`, no host
+ * synchronisation, no allocation, no atomics; the results are bit for bit those of the four calls.  p->blob must be opt->blob,
+ * the configurations and sizes of p, g and opt must agree, n is in [1, opt->max_rows] and may differ from call to call.
+ * GD_ERR_INVALID: whatever the four calls refuse, or a disagreement between p, g and opt; before any launch. */
+int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs, const uint8_t *partner_mask,
+                 const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
