@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == "DeviceBC":
         from .bc_opt import DeviceBC
         return DeviceBC
+    if name in ("ClosedLoopBC", "ClosedLoopEpisode"):
+        from . import bc_rollout
+        return getattr(bc_rollout, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

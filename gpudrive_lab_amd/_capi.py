@@ -210,6 +210,20 @@ class GdBCOutputs(C.Structure):
                                           "ego_attn_score", "component")]
 
 
+class GdBCRolloutBuffers(C.Structure):
+    """gd_bc_rollout_buffers: the rows, the draws, the window and masks the forward reads, the running state, the results and
+    the optional per-step records of one closed-loop episode (device pointers)."""
+    _fields_ = ([("row_slot", C.c_void_p), ("row_of_slot", C.c_void_p), ("n_rows", C.c_int32), ("deterministic", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("u", "z", "window", "partner_mask", "road_mask", "partner_value", "row_actions",
+                                           "dead", "goal_achieved", "off_road", "veh_collision", "goal_step", "off_road_step",
+                                           "init_goal_dist", "goal_dist", "any_alive", "summary", "actions", "dead_mask",
+                                           "ego_global_pos", "ego_global_rot")])
+
+
+BC_ROLLOUT_SUMMARY = ("off_road_rate", "veh_coll_rate", "goal_rate", "collision_rate", "goal_progress", "goal_count", "n_rows",
+                      "iterations")  # gd_bc_rollout_buffers.summary
+
+
 class GdBCGrad(C.Structure):
     """gd_bc_grad: the scratch and the partial sums of one gd_bc_backward (device pointers)."""
     _fields_ = [("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("partials", C.c_void_p), ("grad_floats", C.c_int64),
@@ -240,7 +254,7 @@ SYMBOLS = [
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
-    "gd_episode_step",
+    "gd_bc_rollout", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -335,6 +349,7 @@ def lib():
     L.gd_bc_adamw.argtypes = [C.POINTER(GdBCOpt), C.c_void_p, C.c_void_p]
     L.gd_bc_update.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.POINTER(GdBCOpt)] + [C.c_void_p] * 3 +
                                [C.c_int32, C.c_void_p, C.c_void_p])
+    L.gd_bc_rollout.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers), C.c_int32]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -30,8 +30,8 @@ Scratch (the token, key and value buffers) is sized to `chunk_rows` samples and 
 chunk on the stream inside the one C call.  `nbytes(B)` states what a call of B rows touches beyond its inputs.
 
 Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); the gradient step with clipping and AdamW
-(`bc_opt.DeviceBC`, gd_bc_update, whose `policy` is one of these and follows the optimiser in place); a closed-loop rollout
-driver or stacked-row evaluator;
+(`bc_opt.DeviceBC`, gd_bc_update, whose `policy` is one of these and follows the optimiser in place); the closed-loop driver
+(`bc_rollout.ClosedLoopBC`, gd_bc_rollout, which calls this forward once per step);
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
 `ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64; bf16."""
 import ctypes as C

@@ -1,0 +1,208 @@
+"""The closed-loop BC driver: one episode with the BC policy in the loop, and its metrics, on the device.
+
+`ClosedLoopBC.run()` is the reference's closed-loop script (baselines/il/test/simulation.py run(), lines 22-135): reset the
+worlds, keep a window of `num_stack` packed observations per controlled agent, ask the policy for an action for every agent
+still alive, write those actions (zeros for everyone else) into the simulator, step, accumulate the off-road / collision /
+goal flags, note the step at which goal and off-road first happened and the distance to the goal at the start and at the end,
+report the rates.  The reference does this with a dozen eager torch ops, a `cat` of the stacked observation, boolean-mask
+gathers (which synchronise) and a scatter per step; here one C call (`gd_bc_rollout`, csrc/bc_rollout.hip) runs the whole
+episode on the simulator's stream with no host synchronisation, no allocation and no atomics inside it.
+
+    bc = DeviceBC(sd, max_agents=128, num_stack=5, ...)            # or a DeviceBCPolicy
+    loop = ClosedLoopBC(sim, bc.policy)                            # follows the optimiser in place
+    ep = loop.run()                                                # 91 steps, deterministic actions
+    ep.summary()                                                   # the eight numbers, ONE host read
+    ep.goal_step / expert_done_step                                # the reference's normalised goal time is the caller's line
+
+Rows are in `mask.nonzero()` order (default: the controlled agents).  The window handed to the policy, and returned as
+`window`, is the one the policy saw at the last iteration that ran.  The policy's forward runs on all N rows every step: dead
+rows are not compacted away, their actions are replaced by zeros.  Iterations after every row is dead (the reference's
+`break`) change no output; `steps` counts the iterations that exist.
+
+Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos, `importance_weight.py` / `intervention.py`,
+compaction of dead rows, the late-fusion PPO policy in this loop.  `remove_agents_by_id` / `partner_portion_test` are the
+caller's `sim.deleteAgents(...)` before `run()`; self-play is a mask with more rows."""
+import ctypes as C
+
+import torch
+
+from . import _capi
+from .recorder import DYNAMICS_STATE, EPISODE_LEN, ROAD_POINTS, packed_width
+
+WHO = "ClosedLoopBC: "
+SUMMARY_NAMES = _capi.BC_ROLLOUT_SUMMARY
+
+# the running state and the results: name -> (dtype, the value run() fills in)
+_ROW_ARRAYS = (("dead", torch.uint8, 0), ("goal_achieved", torch.float32, 0), ("off_road", torch.float32, 0),
+               ("veh_collision", torch.float32, 0), ("goal_step", torch.int32, -1), ("off_road_step", torch.int32, -1),
+               ("init_goal_dist", torch.float32, 0), ("goal_dist", torch.float32, 0))
+# the optional per-step records: name -> (columns per (row, step), dtype, default)
+_STEP_ARRAYS = (("actions", 3, torch.float32, 0), ("dead_mask", 1, torch.bool, 1), ("ego_global_pos", 2, torch.float32, 0),
+                ("ego_global_rot", 1, torch.float32, 0))
+_ITEMSIZE = {torch.float32: 4, torch.int32: 4, torch.bool: 1, torch.uint8: 1}
+
+
+def _check_sim(sim):
+    if int(sim._params.dynamicsModel) == DYNAMICS_STATE:
+        raise ValueError(WHO + "the State dynamics model's actions have 10 columns; the policy's have 3 (classic, bicycle or "
+                         "delta_local)")
+
+
+def _check_mask(sim, mask):
+    if mask is None:
+        return
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or tuple(mask.shape) != (sim._W, sim._A):
+        raise ValueError(WHO + "mask must be a [W, A] = [%d, %d] bool tensor, got %s"
+                         % (sim._W, sim._A, (tuple(mask.shape), mask.dtype) if isinstance(mask, torch.Tensor) else type(mask)))
+
+
+def _check_policy(sim, policy):
+    from .bc_policy import DeviceBCPolicy
+    if not isinstance(policy, DeviceBCPolicy):
+        raise ValueError(WHO + "policy must be a DeviceBCPolicy (DeviceBC(...).policy is one), got %s" % type(policy).__name__)
+    if policy.max_agents != sim._A:
+        raise ValueError(WHO + "policy.max_agents is %d, the simulator's is %d" % (policy.max_agents, sim._A))
+
+
+def _check_steps(n_steps):
+    if isinstance(n_steps, bool) or not isinstance(n_steps, int) or not 1 <= n_steps <= EPISODE_LEN:
+        raise ValueError(WHO + "n_steps must be an int in [1, 91], got %r" % (n_steps,))
+
+
+class ClosedLoopEpisode:
+    """One closed-loop episode, on the device.  N rows in `mask.nonzero()` order:
+    goal_achieved / off_road / veh_collision [N] f32 (clamped to 1); goal_step / off_road_step [N] int32 (the raw step index,
+    -1: never); init_goal_dist / goal_dist [N] f32; dead [N] bool; steps: the iterations the reference's loop runs before its
+    `break` (a 0-d device tensor); window [N, R, D] f32, partner_mask [N, A - 1] bool (`partner_value == 2`), partner_value
+    [N, A - 1] uint8 and road_mask [N, 200] bool as the policy last saw them; with record=True actions [N, 91, 3] (zeros once the
+    row is dead), dead_mask [N, 91] bool (default 1), ego_global_pos [N, 91, 2] and ego_global_rot [N, 91] (live rows only)."""
+
+    def __init__(self, **arrays):
+        self.__dict__.update(arrays)
+
+    def summary(self):
+        """off_road_rate, veh_coll_rate, goal_rate, collision_rate, goal_progress, goal_count, n_rows, iterations as a dict of
+        floats: one host read."""
+        return dict(zip(SUMMARY_NAMES, (float(v) for v in self.summary_tensor.cpu().tolist())))
+
+
+class ClosedLoopBC:
+    def __init__(self, sim, policy, mask=None):
+        """sim: a SimManager (any dynamics model but State).  policy: a `DeviceBCPolicy` with the simulator's max_agents.
+        mask: a [W, A] bool tensor of the agent slots the policy drives; default `controlled_state_tensor() == 1`, the
+        reference's cont_agent_mask.  Every argument is checked before anything reaches the device (ValueError).  One host
+        synchronisation, here, for the number of rows."""
+        _check_sim(sim)
+        _check_mask(sim, mask)
+        _check_policy(sim, policy)
+        self.sim, self.policy = sim, policy
+        self._explicit = mask is not None
+        self._set_rows(mask)
+
+    def _set_rows(self, mask):
+        sim = self.sim
+        if mask is None:
+            mask = sim.controlled_state_tensor().to_torch().squeeze(-1) == 1
+        self.mask = mask.to(sim._device).clone()
+        self.row_slot = self.mask.reshape(-1).nonzero().squeeze(1).to(torch.int32).contiguous()  # (synchronises)
+        self.num_agents = n = int(self.row_slot.shape[0])
+        if n < 1:
+            raise ValueError(WHO + "the mask selects no agent slot")
+        self.row_of_slot = torch.full((sim._W * sim._A,), -1, dtype=torch.int32, device=sim._device)
+        self.row_of_slot[self.row_slot.long()] = torch.arange(n, dtype=torch.int32, device=sim._device)
+
+    @staticmethod
+    def row_nbytes(max_agents, num_stack, record=False):
+        """Bytes one row takes in a run: the window, both masks, the partner value, the action, the running state and, with
+        record, 91 steps of every per-step array."""
+        A, R = max_agents, num_stack
+        n = R * packed_width(A) * 4 + R * (A - 1) + R * ROAD_POINTS + (A - 1) + 3 * 4
+        n += sum(_ITEMSIZE[dt] for _, dt, _ in _ROW_ARRAYS)
+        if record:
+            n += EPISODE_LEN * sum(c * _ITEMSIZE[dt] for _, c, dt, _ in _STEP_ARRAYS)
+        return n
+
+    @staticmethod
+    def nbytes(sim, policy, record=False, mask=None, stochastic=False):
+        """What `run()` will allocate for `sim`, `policy` and `mask` (default: the controlled agents): N rows of `row_nbytes`,
+        any_alive [92] int32 and the summary [8]; with stochastic the draws u [91, N] and z [91, N, 3].  The policy's own blob
+        and scratch are the policy's (`policy.nbytes`).  (Synchronises, for N.)"""
+        _check_sim(sim)
+        _check_mask(sim, mask)
+        _check_policy(sim, policy)
+        if mask is None:
+            mask = sim.controlled_state_tensor().to_torch().squeeze(-1) == 1
+        n = int(mask.sum().item())
+        total = n * ClosedLoopBC.row_nbytes(sim._A, policy.num_stack, record) + (EPISODE_LEN + 1) * 4 + len(SUMMARY_NAMES) * 4
+        if stochastic:
+            total += EPISODE_LEN * n * 4 * 4
+        return total
+
+    def resample(self, scenes):
+        """A new batch of scenes: `set_maps`, then the mask (the controlled agents of the new worlds, unless an explicit mask
+        was given, which is kept) and the rows derived again."""
+        self.sim.set_maps(scenes)
+        self._set_rows(self.mask if self._explicit else None)
+
+    def _policy_struct(self):
+        pol = self.policy
+        p = _capi.GdBCPolicy()
+        p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = pol.max_agents, pol.num_stack, *pol.num_layer
+        p.head_layers, p.n_components, p.clip_value, p.chunk_rows = pol.head_num_layers, pol.n_components, pol.clip_value, pol.chunk_rows
+        p.blob, p.blob_floats = pol.blob.data_ptr(), pol.blob.numel()
+        p.scratch, p.scratch_floats = pol._scratch.data_ptr(), pol._scratch.numel()
+        return p
+
+    @staticmethod
+    def _new(name, shape, dtype, fill, device):
+        """Every array of a run is made here (fill None: need not be initialised)."""
+        return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
+
+    def run(self, n_steps=EPISODE_LEN, deterministic=True, generator=None, record=False):
+        """Reset every world, fill the running state and run `n_steps` steps with the policy in the loop in one C call; returns
+        the `ClosedLoopEpisode`.  n_steps < 91 gives the prefix of the full episode.  deterministic=False: u [n_steps, N] and
+        z [n_steps, N, 3] are drawn from `generator` (a device torch.Generator, required) before the call and consumed per
+        step under csrc/bc_rule.hpp's draw; they are returned as `u` and `z`.  record: also keep the per-step arrays.  No host
+        synchronisation."""
+        _check_steps(n_steps)
+        deterministic = bool(deterministic)
+        if not deterministic and not isinstance(generator, torch.Generator):
+            raise ValueError(WHO + "deterministic=False needs generator=, a torch.Generator on the simulator's device")
+        sim, pol, n, A, T = self.sim, self.policy, self.num_agents, self.sim._A, EPISODE_LEN
+        R, D, dev = pol.num_stack, packed_width(A), sim._device
+        if pol.device != dev:
+            raise ValueError(WHO + "the policy is on %s, the simulator on %s" % (pol.device, dev))
+        b = _capi.GdBCRolloutBuffers()
+        out = {}
+        b.row_slot, b.row_of_slot, b.n_rows, b.deterministic = self.row_slot.data_ptr(), self.row_of_slot.data_ptr(), n, int(deterministic)
+        if not deterministic:
+            out["u"] = torch.rand((n_steps, n), dtype=torch.float32, device=dev, generator=generator)
+            out["z"] = torch.randn((n_steps, n, 3), dtype=torch.float32, device=dev, generator=generator)
+            b.u, b.z = out["u"].data_ptr(), out["z"].data_ptr()
+        new = lambda name, shape, dt, fill: self._new(name, shape, dt, fill, dev)
+        window = new("window", (n, R, D), torch.float32, None)  # (written before it is read: frames 0..R-2 as zeros at t = 0)
+        pm = new("partner_mask", (n, R, A - 1), torch.uint8, 0)
+        rm = new("road_mask", (n, R, ROAD_POINTS), torch.uint8, 0)
+        pv = new("partner_value", (n, A - 1), torch.uint8, 0)
+        row_actions = new("row_actions", (n, 3), torch.float32, 0)
+        b.window, b.partner_mask, b.road_mask = window.data_ptr(), pm.data_ptr(), rm.data_ptr()
+        b.partner_value, b.row_actions = pv.data_ptr(), row_actions.data_ptr()
+        for name, dt, fill in _ROW_ARRAYS:
+            out[name] = new(name, (n,), dt, fill)
+            setattr(b, name, out[name].data_ptr())
+        any_alive = new("any_alive", (T + 1,), torch.int32, 0)
+        summary = new("summary", (len(SUMMARY_NAMES),), torch.float32, 0)
+        b.any_alive, b.summary = any_alive.data_ptr(), summary.data_ptr()
+        if record:
+            for name, c, dt, fill in _STEP_ARRAYS:
+                out[name] = new(name, (n, T) if c == 1 else (n, T, c), dt, fill)
+                setattr(b, name, out[name].data_ptr())
+        p = self._policy_struct()
+        sim.reset(list(range(sim._W)))
+        sim._bind_stream()
+        _capi.check(sim._L.gd_bc_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_bc_rollout")
+        sim._after()
+        out["dead"] = out["dead"].view(torch.bool)
+        return ClosedLoopEpisode(steps=any_alive[:T].sum(), any_alive=any_alive, summary_tensor=summary, window=window,
+                                 partner_mask=pm[:, R - 1].view(torch.bool), road_mask=rm[:, R - 1].view(torch.bool),
+                                 partner_value=pv, row_actions=row_actions, **out)

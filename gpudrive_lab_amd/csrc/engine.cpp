@@ -1908,6 +1908,51 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     });
 }
 
+// The closed-loop episode (bc_rollout.hip): gd_record_expert's loop with the policy where the logged action was.
+int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
+    if (!s || !p || !b) return fail(GD_ERR_INVALID, "gd_bc_rollout: null argument");
+    if (!b->row_slot || !b->row_of_slot || !b->window || !b->partner_mask || !b->road_mask || !b->partner_value || !b->row_actions ||
+        !b->dead || !b->goal_achieved || !b->off_road || !b->veh_collision || !b->goal_step || !b->off_road_step ||
+        !b->init_goal_dist || !b->goal_dist || !b->any_alive || !b->summary)
+        return fail(GD_ERR_INVALID, "gd_bc_rollout: every buffer but the per-step records is required");
+    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_bc_rollout: n_rows must be in [1, 2^20]");
+    if (n_steps < 1 || n_steps > GD_EPISODE_LEN)
+        return fail(GD_ERR_INVALID, "gd_bc_rollout: an episode has 91 steps, n_steps must be in [1, 91]");
+    if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
+        return fail(GD_ERR_INVALID, "gd_bc_rollout: the State dynamics model's actions have 10 columns, the policy's have 3");
+    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, "gd_bc_rollout: the policy's max_agents differs from the simulator's");
+    gd_bc_outputs out{};
+    out.actions = b->row_actions;
+    if (const char *why = bc_forward_problem(p, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic, b->u, b->z,
+                                             nullptr, &out))
+        return fail(GD_ERR_INVALID, std::string("gd_bc_rollout: ") + why);
+    if (misaligned(b->window, 16) || misaligned(b->goal_achieved, 4) || misaligned(b->off_road, 4) || misaligned(b->veh_collision, 4) ||
+        misaligned(b->goal_step, 4) || misaligned(b->off_road_step, 4) || misaligned(b->init_goal_dist, 4) ||
+        misaligned(b->goal_dist, 4) || misaligned(b->any_alive, 4) || misaligned(b->summary, 4) || misaligned(b->row_slot, 4) ||
+        misaligned(b->row_of_slot, 4) || misaligned(b->actions, 4) || misaligned(b->ego_global_pos, 4) ||
+        misaligned(b->ego_global_rot, 4))
+        return fail(GD_ERR_INVALID, "gd_bc_rollout: window must be 16-byte aligned, float and int32 buffers 4-byte aligned");
+    if (s->d.pack && s->d.pack_only)
+        return fail(GD_ERR_UNSUPPORTED, "gd_bc_rollout: a packed buffer is attached with only = 1: the raw rows are stale");
+    return guarded([&]() {
+        const size_t N = static_cast<size_t>(b->n_rows);
+        gd::launch_bc_rollout_post(s->d, s->stream, *b, -1, true);
+        HIP_CHECK(hipGetLastError());
+        for (int t = 0; t < n_steps; t++) {
+            gd::launch_bc_rollout_row(s->d, s->stream, *b, t, p->num_stack);
+            gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
+                                  b->u ? b->u + t * N : nullptr, b->z ? b->z + t * N * 3 : nullptr, nullptr, out);
+            gd::launch_bc_rollout_actions(s->d, s->stream, *b, t);
+            HIP_CHECK(hipGetLastError());
+            s->step();
+            gd::launch_bc_rollout_post(s->d, s->stream, *b, t, t + 1 < n_steps);
+            HIP_CHECK(hipGetLastError());
+        }
+        gd::launch_bc_rollout_summary(s->stream, *b);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 // everything gd_bc_backward refuses; nullptr when everything is in order
 static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,

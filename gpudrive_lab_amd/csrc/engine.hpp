@@ -229,6 +229,11 @@ void launch_learner_rows(hipStream_t st, const uint8_t *mask, size_t slots, int3
 void launch_discrete_actions(const DevSim &d, hipStream_t st, const int64_t *indices, const float *table, int n_actions);  // learner.hip
 void launch_pack_obs_conditioned(const DevSim &d, hipStream_t st, const float *weights, float *out);  // pack_obs.hip
 void launch_record(const DevSim &d, hipStream_t st, const gd_record_buffers &b, int t, bool pre);  // record.hip
+// bc_rollout.hip: the closed-loop BC driver's launches (t = -1 of the post kernel: the start)
+void launch_bc_rollout_row(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t, int num_stack);
+void launch_bc_rollout_actions(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t);
+void launch_bc_rollout_post(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t, bool more);
+void launch_bc_rollout_summary(hipStream_t st, const gd_bc_rollout_buffers &b);
 void launch_il_index(const gd_il_dataset &ds, hipStream_t st, int64_t rows, int32_t *counts, int32_t *kept,
                      const int64_t *entry_offset, const int64_t *kept_ordinal, int32_t *entries);  // il_batch.hip
 void launch_il_batch(const gd_il_dataset &ds, hipStream_t st, const gd_il_batch_buffers &b,

@@ -753,6 +753,53 @@ int gd_bc_adamw(const gd_bc_opt *opt, const float *grad, void *stream);
  * GD_ERR_INVALID: whatever the four calls refuse, or a disagreement between p, g and opt; before any launch. */
 int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs, const uint8_t *partner_mask,
                  const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream);
+/* Closed-loop BC driver: one episode with the BC policy in the loop and its metrics, on the device.  The reference's
+ * closed-loop script (baselines/il/test/simulation.py run(), lines 22-135): a window of R = num_stack packed observations per
+ * controlled agent, an action from the policy for every agent still alive, zeros for everyone else, the step, the off-road /
+ * collision / goal flags, the steps at which goal and off-road first happened, the distance to the goal at the start and at
+ * the end, the rates.  All pointers are device pointers owned by the caller; N = n_rows, A = max_agents,
+ * D = 6 + (A-1)*6 + 200*13, R = the policy's num_stack; the time pitch of the optional records is always 91.  The caller zeroes
+ * dead, the accumulators, the distances and any_alive, fills both step indices with -1, zeroes both masks (only time index
+ * R - 1 is ever written) and fills the optional records with its defaults.  csrc/bc_rollout_rule.hpp states the per-row
+ * arithmetic and the summary's summation order. */
+typedef struct gd_bc_rollout_buffers {
+    const int32_t *row_slot;     /* [N] world * A + agent of every row (mask.nonzero() order), each in [0, W * A) */
+    const int32_t *row_of_slot;  /* [W * A] the inverse: a slot's row, -1 where the slot is no row */
+    int32_t n_rows;              /* 1 .. 2^20 */
+    int32_t deterministic;       /* != 0: the mean of the first component of maximal weight; 0: the rule's draw from u and z */
+    const float *u;              /* [n_steps][N] in [0, 1), required unless deterministic */
+    const float *z;              /* [n_steps][N][3] standard normals, required unless deterministic */
+    float *window;               /* [N][R][D] the last R packed observations, oldest first; zeros before the first step.
+                                  * Need not be initialised. */
+    uint8_t *partner_mask;       /* [N][R][A-1] what gd_bc_forward reads: at time index R - 1, 1 where the partner value is 2 */
+    uint8_t *road_mask;          /* [N][R][200] at time index R - 1, 1 where the road row is padding (id -1) */
+    uint8_t *partner_value;      /* [N][A-1] the recorder's value of the newest frame: 0 acts, 1 Static and non-zero, 2 nobody */
+    float *row_actions;          /* [N][3] the policy's action of every row in the current step (dead rows included) */
+    /* running state and results */
+    uint8_t *dead;               /* [N] */
+    float *goal_achieved, *off_road, *veh_collision;  /* [N] sums of info columns 3 / 0 / 1 + 2, clamped to 1 */
+    int32_t *goal_step, *off_road_step;               /* [N] the first t whose info row, read before step t, is > 0; else -1 */
+    float *init_goal_dist, *goal_dist;                /* [N] sqrtf(x x + y y) of ego columns 3, 4: at t = 0, at the last step */
+    int32_t *any_alive;          /* [92] 1 where some row was alive before step t: iteration t of the reference's loop exists
+                                  * (its `break`); their sum is the number of iterations it runs */
+    float *summary;              /* [8] off_road_rate, veh_coll_rate, goal_rate, collision_rate, goal_progress, goal_count,
+                                  * n_rows, iterations */
+    /* optional per-step records (NULL: not written); only iterations that exist are written */
+    float *actions;              /* [N][91][3] what was written into the simulator for the row: zeros once it is dead */
+    uint8_t *dead_mask;          /* [N][91] the row was dead BEFORE step t */
+    float *ego_global_pos;       /* [N][91][2] absolute_self_observation columns 0, 1, live rows only */
+    float *ego_global_rot;       /* [N][91] absolute_self_observation column 7, live rows only */
+} gd_bc_rollout_buffers;
+/* For t in [0, n_steps), on the simulator's stream: the row kernel for time index t (window, masks, distances, step indices,
+ * records), gd_bc_forward on all N rows into row_actions, the action kernel (action[:, :, :3] of every slot: a live row's
+ * action, zeros for every other slot), the step, the bookkeeping of that step (dead |= done, the accumulators, any_alive[t + 1]);
+ * then the summary.  Iterations after every row is dead change no output (the simulator still steps, with zero actions).  With
+ * n_steps < 91 the result is the prefix of the full episode.  It does not reset: the caller does.  3 launches per step beside the
+ * forward's and the step's, no host synchronisation, no allocation, no atomics.
+ * GD_ERR_INVALID: a null pointer, n_rows outside [1, 2^20], n_steps outside [1, 91], the State dynamics model, a policy whose
+ * max_agents differs from the simulator's, whatever gd_bc_forward refuses.  GD_ERR_UNSUPPORTED while a packed buffer is
+ * attached with only != 0 (the raw rows the observation is computed from are stale). */
+int gd_bc_rollout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers, int32_t n_steps);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
