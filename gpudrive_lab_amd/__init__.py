@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("ClosedLoopBC", "ClosedLoopEpisode"):
         from . import bc_rollout
         return getattr(bc_rollout, name)
+    if name == "DeviceLinearProbe":
+        from .lp_probe import DeviceLinearProbe
+        return DeviceLinearProbe
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -245,6 +245,28 @@ class GdBCOpt(C.Structure):
                                            "actions", "nll", "grad_nll", "grad")])
 
 
+LP_TAP_FUSION, LP_TAP_RO = range(2)
+LP_EARLY, LP_LATE, LP_BASELINE = range(3)
+LP_EVAL_WORDS = 208  # gd_lp_eval_accumulate's acc, int32 words
+LP_PART_INTS = 392   # gd_lp_probe.part_i, words per partial
+LP_STATS = ("loss", "accuracy", "f1_macro", "ood_loss_sum", "ood_correct", "ood_rows", "rows", "bad_labels")  # gd_lp_probe.stats
+
+
+class GdLPProbe(C.Structure):
+    """gd_lp_probe: the configuration, the weights in both layouts, the optimiser state and the scratch of the device linear
+    probe (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("model", "exp", "in_features", "num_partials", "max_agents", "num_stack")] +
+                [("reserved", C.c_int32 * 2), ("eps", C.c_float), ("weight_decay", C.c_float), ("beta1", C.c_double),
+                 ("beta2", C.c_double)] +
+                [(n, C.c_void_p) for n in ("weight", "packed", "exp_avg", "exp_avg_sq", "lr", "step", "beta_pow", "grad", "part_f",
+                                           "part_d", "part_i", "stats", "sums", "counts", "scal")])
+
+
+class GdLPRows(C.Structure):
+    """gd_lp_rows: the optional per-row outputs of the gd_lp_* calls (device pointers; NULL: not written)."""
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "loss_row", "pred")]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -254,7 +276,7 @@ SYMBOLS = [
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
-    "gd_bc_rollout", "gd_episode_step",
+    "gd_bc_rollout", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -350,6 +372,11 @@ def lib():
     L.gd_bc_update.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.POINTER(GdBCOpt)] + [C.c_void_p] * 3 +
                                [C.c_int32, C.c_void_p, C.c_void_p])
     L.gd_bc_rollout.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers), C.c_int32]
+    L.gd_bc_hidden.argtypes = [C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lp = [C.POINTER(GdBCPolicy), C.POINTER(GdLPProbe), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.gd_lp_forward.argtypes = lp + [C.POINTER(GdLPRows), C.c_void_p]
+    L.gd_lp_update.argtypes = lp + [C.c_void_p, C.c_void_p, C.POINTER(GdLPRows), C.c_void_p]
+    L.gd_lp_eval_accumulate.argtypes = lp + [C.c_void_p, C.c_void_p, C.POINTER(GdLPRows), C.c_void_p, C.c_void_p]
     L.gd_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_attach_bev.argtypes = [C.c_void_p, C.c_void_p]
     L.gd_stat.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]

@@ -375,6 +375,40 @@ class DeviceBCPolicy:
                         "gd_bc_forward")
         return res
 
+    def c_struct(self):
+        """A fresh gd_bc_policy over this object's blob and scratch."""
+        p = _capi.GdBCPolicy()
+        p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = self.max_agents, self.num_stack, *self.num_layer
+        p.head_layers, p.n_components, p.clip_value, p.chunk_rows = self.head_num_layers, self.n_components, self.clip_value, self.chunk_rows
+        p.blob, p.blob_floats = self.blob.data_ptr(), self.blob.numel()
+        p.scratch, p.scratch_floats = self._scratch.data_ptr(), self._scratch.numel()
+        return p
+
+    TAPS = {"fusion_attn": _capi.LP_TAP_FUSION, "ro_attn": _capi.LP_TAP_RO}
+
+    def hidden(self, obs, partner_mask, road_mask, tap="fusion_attn", out=None):
+        """The hidden states a linear probe reads (the reference's forward hooks on `fusion_attn` / `ro_attn`,
+        baselines/il/linear_probing.py:68-95): [B, A, 64] float32, tokens 0 .. A - 1 (the ego, then the partners) of the tapped
+        block's last_hidden_state.  One C call (`gd_bc_hidden`): per chunk the forward's own kernels run and stop at the tap -- for
+        'fusion_attn' no branch layer, no cross attention and no head is launched.  out: that tensor of an earlier call.  No host
+        synchronisation; with out= no allocation."""
+        B = self._inputs(obs, partner_mask, road_mask)
+        if tap not in self.TAPS:
+            raise ValueError(WHO + "tap must be 'fusion_attn' or 'ro_attn', got %r" % (tap,))
+        shape = (B, self.max_agents, DIM)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            self._tensor("out", out, (torch.float32,), shape)
+            if out.data_ptr() % 16:
+                raise ValueError(WHO + "out must be 16-byte aligned")
+        p = self.c_struct()
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(self._L.gd_bc_hidden(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
+                                             self.TAPS[tap], out.data_ptr(), stream), "gd_bc_hidden")
+        return out
+
     def __call__(self, obs, partner_mask, road_mask, deterministic=False, u=None, z=None, out=None):
         """obs [B, R, D] float32, partner_mask [B, R, A - 1] and road_mask [B, R, 200] bool or uint8, as
         `DeviceExpertDataset.batch` writes them.  deterministic: the mean of the first component of maximal weight; otherwise

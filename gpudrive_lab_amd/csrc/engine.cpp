@@ -2095,6 +2095,100 @@ int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, con
     });
 }
 
+int gd_bc_hidden(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, int32_t tap,
+                 float *out, void *stream) {
+    gd_bc_outputs none{};
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none);
+    if (!why && tap != GD_LP_TAP_FUSION && tap != GD_LP_TAP_RO) why = "tap must be GD_LP_TAP_FUSION or GD_LP_TAP_RO";
+    if (!why && (!out || misaligned(out, 16))) why = "out is required, 16-byte aligned";
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_hidden: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// everything the three gd_lp_* entries refuse; nullptr when everything is in order.  mode: launch_lp's
+static const char *lp_problem(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask,
+                              const uint8_t *road_mask, int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows,
+                              int mode, const int32_t *acc) {
+    if (!lp || !obs) return "null argument";
+    if (lp->model < GD_LP_EARLY || lp->model > GD_LP_BASELINE) return "model must be GD_LP_EARLY, GD_LP_LATE or GD_LP_BASELINE";
+    if (lp->exp != GD_IL_FUTURE_OTHER && lp->exp != GD_IL_FUTURE_EGO) return "exp must be GD_IL_FUTURE_OTHER or GD_IL_FUTURE_EGO";
+    if (lp->reserved[0] != 0 || lp->reserved[1] != 0) return "reserved must be 0";
+    if (lp->max_agents != 64 && lp->max_agents != 128) return "max_agents must be 64 or 128";
+    if (lp->num_stack < 1 || lp->num_stack > 8) return "num_stack must be in [1, 8]";
+    if (lp->model == GD_LP_BASELINE) {
+        if (p) return "the baseline probe takes no policy";
+        if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
+        if (misaligned(obs, 4)) return "float and int32 buffers must be 4-byte aligned";
+        const int k = (lp->exp == GD_IL_FUTURE_OTHER ? 12 : 6) * lp->num_stack;
+        if (k > 64) return "the baseline probe's in_features (12 num_stack for 'other') must not exceed 64";
+        if (lp->in_features != k) return "in_features must be 6 num_stack ('ego') or 12 num_stack ('other') for the baseline probe";
+    } else {
+        gd_bc_outputs none{};
+        if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none)) return why;
+        if (lp->max_agents != p->max_agents || lp->num_stack != p->num_stack) return "max_agents and num_stack must be the policy's";
+        if (lp->in_features != 64) return "in_features must be 64 with a policy";
+    }
+    if (lp->num_partials < 1 || lp->num_partials > 4096) return "num_partials must be in [1, 4096]";
+    if (!lp->packed || misaligned(lp->packed, 16)) return "packed is required, 16-byte aligned";
+    if (rows && (misaligned(rows->logits, 16) || misaligned(rows->loss_row, 4) || misaligned(rows->pred, 8)))
+        return "logits must be 16-byte aligned, loss_row 4-byte, pred 8-byte";
+    if (mode == 0) {
+        if (!rows || (!rows->logits && !rows->pred)) return "rows with logits or pred is required";
+        if (rows->loss_row) return "loss_row needs labels (gd_lp_update, gd_lp_eval_accumulate)";
+        return nullptr;
+    }
+    if (!mask || !labels || misaligned(labels, 8)) return "mask and labels are required, labels 8-byte aligned";
+    if (!lp->part_f || !lp->part_d || !lp->part_i || misaligned(lp->part_f, 4) || misaligned(lp->part_d, 8) || misaligned(lp->part_i, 4))
+        return "part_f, part_d and part_i are required (4-, 8- and 4-byte aligned)";
+    if (misaligned(lp->stats, 4)) return "float and int32 buffers must be 4-byte aligned";
+    if (mode == 2) return !acc || misaligned(acc, 8) ? "acc is required, 8-byte aligned" : nullptr;
+    if (!(lp->beta1 >= 0.0 && lp->beta1 < 1.0) || !(lp->beta2 >= 0.0 && lp->beta2 < 1.0)) return "betas must be in [0, 1)";
+    if (!(lp->eps > 0.f)) return "eps must be positive";
+    if (!(lp->weight_decay >= 0.f) || !std::isfinite(lp->weight_decay)) return "weight_decay must be finite and not negative";
+    if (!lp->weight || !lp->exp_avg || !lp->exp_avg_sq || !lp->lr || !lp->step || !lp->beta_pow || !lp->grad || !lp->stats || !lp->sums ||
+        !lp->counts || !lp->scal)
+        return "weight, exp_avg, exp_avg_sq, lr, step, beta_pow, grad, stats, sums, counts and scal are required";
+    if (misaligned(lp->beta_pow, 8) || misaligned(lp->sums, 8) || misaligned(lp->weight, 4) || misaligned(lp->exp_avg, 4) ||
+        misaligned(lp->exp_avg_sq, 4) || misaligned(lp->lr, 4) || misaligned(lp->step, 4) || misaligned(lp->grad, 4) ||
+        misaligned(lp->counts, 4) || misaligned(lp->scal, 4))
+        return "beta_pow and sums must be 8-byte aligned, the other buffers 4-byte aligned";
+    return nullptr;
+}
+
+int gd_lp_forward(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                  int32_t n, const gd_lp_rows *rows, void *stream) {
+    if (const char *why = lp_problem(p, lp, obs, partner_mask, road_mask, n, nullptr, nullptr, rows, 0, nullptr))
+        return fail(GD_ERR_INVALID, std::string("gd_lp_forward: ") + why);
+    return guarded([&]() {
+        gd::launch_lp(p, *lp, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, nullptr, nullptr, rows, 0, nullptr);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_lp_update(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                 int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows, void *stream) {
+    if (const char *why = lp_problem(p, lp, obs, partner_mask, road_mask, n, mask, labels, rows, 1, nullptr))
+        return fail(GD_ERR_INVALID, std::string("gd_lp_update: ") + why);
+    return guarded([&]() {
+        gd::launch_lp(p, *lp, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, mask, labels, rows, 1, nullptr);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_lp_eval_accumulate(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask,
+                          const uint8_t *road_mask, int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows,
+                          int32_t *acc, void *stream) {
+    if (const char *why = lp_problem(p, lp, obs, partner_mask, road_mask, n, mask, labels, rows, 2, acc))
+        return fail(GD_ERR_INVALID, std::string("gd_lp_eval_accumulate: ") + why);
+    return guarded([&]() {
+        gd::launch_lp(p, *lp, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, mask, labels, rows, 2, acc);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_episode_step(gd_sim *s, const gd_episode_config *cfg, const gd_episode_buffers *b) {
     if (!s || !cfg || !b) return fail(GD_ERR_INVALID, "gd_episode_step: null argument");
     if (!b->controlled_mask || !b->agent_episode_returns || !b->episode_lengths || !b->collided_in_episode ||

@@ -296,5 +296,12 @@ int bc_num_tensors(int fusion_layers, int branch_layers, int head_layers);  // t
 void launch_bc_train_rows(const gd_bc_opt &o, hipStream_t st, int n, const float *nll, const float *actions,
                           const float *expert_actions, float *grad_nll);  // (one launch)
 void launch_bc_adamw(const gd_bc_opt &o, hipStream_t st, const float *grad);  // (three launches)
+// lp_probe.hip
+void launch_bc_hidden(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                      const unsigned char *road_mask, int n, int tap, float *out);
+// mode 0: logits and / or pred; 1: one gradient step; 2: one batch of the evaluation added to acc.  p: null for the baseline probe
+void launch_lp(const gd_bc_policy *p, const gd_lp_probe &lp, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+               const unsigned char *road_mask, int n, const unsigned char *mask, const int64_t *labels, const gd_lp_rows *rows_out,
+               int mode, int *acc);
 
 }  // namespace gd

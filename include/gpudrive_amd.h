@@ -800,6 +800,76 @@ typedef struct gd_bc_rollout_buffers {
  * max_agents differs from the simulator's, whatever gd_bc_forward refuses.  GD_ERR_UNSUPPORTED while a packed buffer is
  * attached with only != 0 (the raw rows the observation is computed from are stale). */
 int gd_bc_rollout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers, int32_t n_steps);
+/* The hidden states a linear probe reads (the reference's forward hooks, baselines/il/linear_probing.py:68-95): out [n][A][64]
+ * float32, 16-byte aligned, receives tokens 0 .. A - 1 (the ego, then the partners) of the last_hidden_state of the tapped
+ * block -- fusion_attn after its fusion_layers self layers, or ro_attn after its branch_layers more.  Per chunk gd_bc_forward's
+ * own kernels run and stop at the tap (for GD_LP_TAP_FUSION no branch layer, no cross attention and no head is launched), then
+ * one copy launch.  Every byte of out is stored by every call.  No host synchronisation, no allocation.  GD_ERR_INVALID: an
+ * unknown tap, a null or misaligned out, whatever gd_bc_forward refuses. */
+enum { GD_LP_TAP_FUSION = 0, GD_LP_TAP_RO = 1 };
+int gd_bc_hidden(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, int32_t tap,
+                 float *out, void *stream);
+/* Device linear probe: the reference's LinearProbPosition (an nn.Linear(K, 64) over 8 x 8 position classes) trained and scored
+ * on the labels gd_il_future_batch writes (baselines/il/linear_probing.py:169-342).  csrc/lp_rule.hpp states the rule.
+ * model: GD_LP_EARLY reads the fusion_attn tap, GD_LP_LATE the ro_attn tap (K = 64 both), GD_LP_BASELINE reads obs itself (no
+ * policy: p is NULL): for 'ego' the row is obs[b][:][0..6) flattened (K = 6 R), for 'other' [ego 6 | partner j's 6] per time
+ * index (K = 12 R <= 64).  exp: GD_IL_FUTURE_OTHER (the rows of sample b are its A - 1 partner tokens 1 .. A - 1; selected where
+ * the mask byte is 0) or GD_IL_FUTURE_EGO (token 0; selected where the mask byte is not 0).  With a policy max_agents and
+ * num_stack must be the policy's.  Every pointer is a device pointer owned by the caller. */
+enum { GD_LP_EARLY = 0, GD_LP_LATE = 1, GD_LP_BASELINE = 2 };
+enum { GD_LP_EVAL_WORDS = 208 };  /* gd_lp_eval_accumulate's acc, int32 words */
+typedef struct gd_lp_probe {
+    int32_t model, exp;
+    int32_t in_features;   /* K */
+    int32_t num_partials;  /* 1 .. 4096 */
+    int32_t max_agents, num_stack;
+    int32_t reserved[2];   /* 0 */
+    float eps, weight_decay;
+    double beta1, beta2;
+    float *weight;       /* [64 K + 64] head.weight [64][K], then head.bias: the flat layout */
+    float *packed;       /* [4160] the weight in bc_policy.py's `mfma` form, columns K .. 63 zero, then the bias; 16-byte aligned */
+    float *exp_avg;      /* [64 K + 64] */
+    float *exp_avg_sq;   /* [64 K + 64] */
+    const float *lr;     /* [1] */
+    int32_t *step;       /* [1] */
+    double *beta_pow;    /* [2] beta1^step, beta2^step */
+    float *grad;         /* [64 K + 64] the last update's gradient of the mean loss (not written when no row was selected) */
+    float *part_f;       /* [num_partials][64 K + 64] */
+    double *part_d;      /* [num_partials][2] */
+    int32_t *part_i;     /* [num_partials][392] */
+    float *stats;        /* [8] the last non-empty batch: loss, accuracy, macro F1, the OOD rows' loss sum, correct count and count,
+                          * M, bad labels */
+    double *sums;        /* [3] the sums of loss, accuracy and macro F1 over the updates that were not skipped */
+    int32_t *counts;     /* [3] updates made, updates skipped (M == 0), selected rows dropped for a label outside [0, 63] */
+    float *scal;         /* [4] what the reduce launch leaves for the AdamW launch */
+} gd_lp_probe;
+/* Per-row outputs, [n][A - 1] for 'other' and [n] for 'ego'; each may be NULL.  logits [..][64] (16-byte aligned); loss_row:
+ * logsumexp - logit[label] for every row whose label is in [0, 63], selected or not, 0 otherwise; pred: the first index of
+ * the maximum. */
+typedef struct gd_lp_rows {
+    float *logits;
+    float *loss_row;
+    int64_t *pred;
+} gd_lp_rows;
+/* LinearProbPosition.forward / .predict: rows->logits and / or rows->pred (loss_row must be NULL: there are no labels).  The tap's
+ * launches and one row launch per chunk. */
+int gd_lp_forward(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                  int32_t n, const gd_lp_rows *rows, void *stream);
+/* One gradient step as one call: per chunk the tap's launches and the row launch (logits, the row rule, the partial sums of
+ * the gradient and the counters), then the reduce launch (M, grad, stats, the step's scalars) and the AdamW launch, which stores
+ * each weight to `weight` and to its place in `packed`.  mask and labels: aux_mask / other_pos [n][A - 1] or future_valid_mask /
+ * ego_pos [n] as gd_il_future_batch writes them (one byte per mask entry, int64 labels, 8-byte aligned).  M == 0 leaves the
+ * weights, the moments, step and beta_pow untouched and advances counts[1]; the device decides it.  rows: NULL or per-row outputs.
+ * No host synchronisation, no allocation, no atomics. */
+int gd_lp_update(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                 int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows, void *stream);
+/* One batch of the reference's evaluation added to acc (GD_LP_EVAL_WORDS int32 words, 8-byte aligned, zeroed by the caller before
+ * the first batch): words 0 .. 7 are four float64 -- the sums of the batches' loss, accuracy and macro F1 and the sum of loss_row
+ * over the OOD rows; then int32: non-empty batches, empty batches, OOD correct, OOD rows, bad labels, three unused; then the OOD
+ * rows' per-class true positives [64], predicted counts [64] and label counts [64].  Nothing of the optimiser is touched. */
+int gd_lp_eval_accumulate(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask,
+                          const uint8_t *road_mask, int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows,
+                          int32_t *acc, void *stream);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
