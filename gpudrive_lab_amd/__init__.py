@@ -18,6 +18,9 @@ def __getattr__(name):
     if name in ("ClosedLoopBC", "ClosedLoopEpisode"):
         from . import bc_rollout
         return getattr(bc_rollout, name)
+    if name in ("ClosedLoopPPO", "PolicyEpisode"):
+        from . import ppo_rollout
+        return getattr(ppo_rollout, name)
     if name == "DeviceLinearProbe":
         from .lp_probe import DeviceLinearProbe
         return DeviceLinearProbe

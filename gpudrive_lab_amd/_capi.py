@@ -224,6 +224,22 @@ BC_ROLLOUT_SUMMARY = ("off_road_rate", "veh_coll_rate", "goal_rate", "collision_
                       "iterations")  # gd_bc_rollout_buffers.summary
 
 
+class GdPolicyRolloutBuffers(C.Structure):
+    """gd_policy_rollout_buffers: the draws, the action table, the forward's outputs, the running state, the per-world results
+    and the optional per-step records of one closed-loop episode of the late-fusion policy (device pointers)."""
+    _fields_ = ([("n_rows", C.c_int32), ("deterministic", C.c_int32), ("u", C.c_void_p), ("table", C.c_void_p),
+                 ("n_actions", C.c_int32), ("reserved", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("actions", "logprob", "entropy", "value", "live", "goal_achieved", "collided",
+                                           "off_road", "world_active", "episode_lengths", "bad_indices", "any_active",
+                                           "goal_achieved_count", "frac_goal_achieved", "collided_count", "frac_collided",
+                                           "off_road_count", "frac_off_road", "other_count", "frac_other",
+                                           "controlled_per_scene", "summary", "actions_idx", "live_mask", "agent_positions")])
+
+
+POLICY_ROLLOUT_SUMMARY = ("goal_achieved", "collided", "off_road", "other", "n_rows", "worlds_with_rows", "iterations",
+                          "mean_episode_length")  # gd_policy_rollout_buffers.summary
+
+
 class GdBCGrad(C.Structure):
     """gd_bc_grad: the scratch and the partial sums of one gd_bc_backward (device pointers)."""
     _fields_ = [("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("partials", C.c_void_p), ("grad_floats", C.c_int64),
@@ -276,7 +292,7 @@ SYMBOLS = [
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
-    "gd_bc_rollout", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
+    "gd_bc_rollout", "gd_policy_rollout", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -372,6 +388,7 @@ def lib():
     L.gd_bc_update.argtypes = ([C.POINTER(GdBCPolicy), C.POINTER(GdBCGrad), C.POINTER(GdBCOpt)] + [C.c_void_p] * 3 +
                                [C.c_int32, C.c_void_p, C.c_void_p])
     L.gd_bc_rollout.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers), C.c_int32]
+    L.gd_policy_rollout.argtypes = [C.c_void_p, C.POINTER(GdPolicy), C.POINTER(GdPolicyRolloutBuffers), C.c_int32]
     L.gd_bc_hidden.argtypes = [C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lp = [C.POINTER(GdBCPolicy), C.POINTER(GdLPProbe), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_lp_forward.argtypes = lp + [C.POINTER(GdLPRows), C.c_void_p]

@@ -20,7 +20,7 @@ rows are not compacted away, their actions are replaced by zeros.  Iterations af
 `break`) change no output; `steps` counts the iterations that exist.
 
 Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos, `importance_weight.py` / `intervention.py`,
-compaction of dead rows, the late-fusion PPO policy in this loop.  `remove_agents_by_id` / `partner_portion_test` are the
+compaction of dead rows.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
 caller's `sim.deleteAgents(...)` before `run()`; self-play is a mask with more rows."""
 import ctypes as C
 

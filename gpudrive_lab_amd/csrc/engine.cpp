@@ -1953,6 +1953,55 @@ int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers 
     });
 }
 
+// The closed-loop PPO evaluator (policy_rollout.hip): gd_bc_rollout's loop with the late-fusion policy on the learner rows.
+int gd_policy_rollout(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, int32_t n_steps) {
+    if (!s || !p || !b) return fail(GD_ERR_INVALID, "gd_policy_rollout: null argument");
+    if (!b->table || !b->actions || !b->logprob || !b->entropy || !b->value || !b->live || !b->goal_achieved || !b->collided ||
+        !b->off_road || !b->world_active || !b->episode_lengths || !b->bad_indices || !b->any_active || !b->goal_achieved_count ||
+        !b->frac_goal_achieved || !b->collided_count || !b->frac_collided || !b->off_road_count || !b->frac_off_road ||
+        !b->other_count || !b->frac_other || !b->controlled_per_scene || !b->summary)
+        return fail(GD_ERR_INVALID, "gd_policy_rollout: every buffer but u and the per-step records is required");
+    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_policy_rollout: n_rows must be in [1, 2^20]");
+    if (n_steps < 1 || n_steps > GD_EPISODE_LEN)
+        return fail(GD_ERR_INVALID, "gd_policy_rollout: an episode has 91 steps, n_steps must be in [1, 91]");
+    if (b->reserved != 0) return fail(GD_ERR_INVALID, "gd_policy_rollout: reserved must be 0");
+    if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
+        return fail(GD_ERR_UNSUPPORTED, "gd_policy_rollout: the State dynamics model has no discrete action space");
+    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, "gd_policy_rollout: no learner rows set (gd_set_learner_rows)");
+    if (!s->d.pack || !s->d.pack_rows)
+        return fail(GD_ERR_INVALID, "gd_policy_rollout: no learner-row buffer attached (gd_attach_packed_rows)");
+    if (b->n_rows != s->d.n_rows) return fail(GD_ERR_INVALID, "gd_policy_rollout: n_rows differs from the number of learner rows");
+    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's max_agents differs from the simulator's");
+    if (p->ego_width != (s->d.pack_weights ? 9 : 6))
+        return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's ego_width differs from the attached rows' (6, or 9 for conditioned rows)");
+    if (p->num_rows != b->n_rows) return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's num_rows differs from n_rows");
+    if (b->n_actions != p->n_actions) return fail(GD_ERR_INVALID, "gd_policy_rollout: the table's n_actions differs from the policy's");
+    if (const char *why = policy_forward_problem(p, s->d.pack, b->u, b->deterministic, b->actions, b->logprob, b->entropy, b->value,
+                                                 nullptr))
+        return fail(GD_ERR_INVALID, std::string("gd_policy_rollout: ") + why);
+    if (misaligned(b->table, 4) || misaligned(b->goal_achieved, 4) || misaligned(b->collided, 4) || misaligned(b->off_road, 4) ||
+        misaligned(b->episode_lengths, 4) || misaligned(b->bad_indices, 4) || misaligned(b->any_active, 4) ||
+        misaligned(b->goal_achieved_count, 4) || misaligned(b->frac_goal_achieved, 4) || misaligned(b->collided_count, 4) ||
+        misaligned(b->frac_collided, 4) || misaligned(b->off_road_count, 4) || misaligned(b->frac_off_road, 4) ||
+        misaligned(b->other_count, 4) || misaligned(b->frac_other, 4) || misaligned(b->controlled_per_scene, 4) ||
+        misaligned(b->summary, 4) || misaligned(b->actions_idx, 8) || misaligned(b->agent_positions, 4))
+        return fail(GD_ERR_INVALID, "gd_policy_rollout: actions_idx must be 8-byte aligned, float and int32 buffers 4-byte aligned");
+    return guarded([&]() {
+        const size_t N = static_cast<size_t>(b->n_rows);
+        for (int t = 0; t < n_steps; t++) {
+            gd::launch_policy_forward(*p, s->stream, s->d.pack, b->u ? b->u + t * N : nullptr, b->deterministic != 0, b->actions,
+                                      b->logprob, b->entropy, b->value, nullptr);
+            gd::launch_policy_rollout_actions(s->d, s->stream, *b, t);
+            HIP_CHECK(hipGetLastError());
+            s->step();
+            gd::launch_policy_rollout_book(s->d, s->stream, *b, t);
+            HIP_CHECK(hipGetLastError());
+        }
+        gd::launch_policy_rollout_finish(s->d, s->stream, *b, n_steps);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 // everything gd_bc_backward refuses; nullptr when everything is in order
 static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,

@@ -234,6 +234,10 @@ void launch_bc_rollout_row(const DevSim &d, hipStream_t st, const gd_bc_rollout_
 void launch_bc_rollout_actions(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t);
 void launch_bc_rollout_post(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t, bool more);
 void launch_bc_rollout_summary(hipStream_t st, const gd_bc_rollout_buffers &b);
+// policy_rollout.hip: the closed-loop PPO evaluator's launches (finish: the per-world kernel and the summary)
+void launch_policy_rollout_actions(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, int t);
+void launch_policy_rollout_book(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, int t);
+void launch_policy_rollout_finish(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, int n_steps);
 void launch_il_index(const gd_il_dataset &ds, hipStream_t st, int64_t rows, int32_t *counts, int32_t *kept,
                      const int64_t *entry_offset, const int64_t *kept_ordinal, int32_t *entries);  // il_batch.hip
 void launch_il_batch(const gd_il_dataset &ds, hipStream_t st, const gd_il_batch_buffers &b,

@@ -223,6 +223,18 @@ class DevicePolicy:
             raise ValueError("DevicePolicy: %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), self.device))
         return t
 
+    def _struct(self, n):
+        """The gd_policy of a forward on n rows; the features and logits scratch grows here, and nowhere else."""
+        if n > self._rows:
+            self._features = torch.empty((n, FEATURES), dtype=torch.float32, device=self.device)
+            self._logits = torch.empty((n, self.n_actions), dtype=torch.float32, device=self.device)
+            self._rows = n
+        p = _capi.GdPolicy()
+        p.num_rows, p.max_agents, p.ego_width, p.n_actions = n, self.max_agents, self.ego_width, self.n_actions
+        p.blob, p.blob_floats = self.blob.data_ptr(), self.blob.numel()
+        p.features, p.logits = self._features.data_ptr(), self._logits.data_ptr()
+        return p
+
     OUT_NAMES = ("actions", "logprob", "entropy", "value")
 
     def __call__(self, obs, u=None, deterministic=False, out=None, logits_out=None):
@@ -256,14 +268,7 @@ class DevicePolicy:
             out = tuple(self._tensor("out " + name, o, dt, shape) for name, o, (shape, dt) in zip(self.OUT_NAMES, out, want))
         if logits_out is not None:
             self._tensor("logits_out", logits_out, f, (n, self.n_actions))
-        if n > self._rows:
-            self._features = torch.empty((n, FEATURES), dtype=f, device=self.device)
-            self._logits = torch.empty((n, self.n_actions), dtype=f, device=self.device)
-            self._rows = n
-        p = _capi.GdPolicy()
-        p.num_rows, p.max_agents, p.ego_width, p.n_actions = n, self.max_agents, self.ego_width, self.n_actions
-        p.blob, p.blob_floats = self.blob.data_ptr(), self.blob.numel()
-        p.features, p.logits = self._features.data_ptr(), self._logits.data_ptr()
+        p = self._struct(n)
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             args = (obs.data_ptr(), None if u is None else u.data_ptr(), int(deterministic), out[0].data_ptr(), out[1].data_ptr(),

@@ -800,6 +800,58 @@ typedef struct gd_bc_rollout_buffers {
  * max_agents differs from the simulator's, whatever gd_bc_forward refuses.  GD_ERR_UNSUPPORTED while a packed buffer is
  * attached with only != 0 (the raw rows the observation is computed from are stale). */
 int gd_bc_rollout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers, int32_t n_steps);
+/* Closed-loop PPO evaluator: one episode with the late-fusion policy (gd_policy) in the loop and the per-world metrics, on the
+ * device.  The reference's evaluation rollout (examples/experimental/eval_utils.py rollout(), lines 94-227): an action index
+ * from the policy for every controlled agent still live, decoded through the action table, index 0 for everyone else, the
+ * step, the off-road / collision / goal sums of live rows, live &= !done, the step at which every world finished, and per
+ * world the counts and fractions of rows that achieved the goal, collided, went off road, or did none of the three.  All
+ * pointers are device pointers owned by the caller; N = n_rows, the simulator's learner rows (gd_set_learner_rows), whose
+ * [N][D] buffer (gd_attach_packed_rows, or gd_attach_packed_rows_conditioned for ego_width 9) is the observation the forward
+ * reads; W worlds, A = max_agents; the time pitch of the optional records is always 91.  The caller fills live and
+ * world_active with 1, zeroes the accumulators, episode_lengths and bad_indices, sets any_active[0] = 1 and zeroes the rest
+ * of it, and fills the optional records with its defaults (actions_idx -1, live_mask 0, agent_positions 0).
+ * csrc/policy_rollout_rule.hpp states the per-row and per-world arithmetic and the summary's order. */
+typedef struct gd_policy_rollout_buffers {
+    int32_t n_rows;              /* N, 1 .. 2^20: the number of learner rows */
+    int32_t deterministic;       /* != 0: the first index of the largest logit; 0: the action rule's draw from u */
+    const float *u;              /* [n_steps][N] in [0, 1), required unless deterministic */
+    const float *table;          /* [n_actions][3] the action table: row k is what action index k writes */
+    int32_t n_actions;           /* the table's rows; must be the policy's n_actions */
+    int32_t reserved;            /* 0 */
+    /* what every forward writes (all N rows, dead rows too: there is no compaction) */
+    int64_t *actions;            /* [N] */
+    float *logprob, *entropy, *value;  /* [N] each */
+    /* running state and results, per row */
+    uint8_t *live;               /* [N] */
+    float *goal_achieved, *collided, *off_road;  /* [N] raw sums of info columns 3 / 1 + 2 / 0 over the steps the row was live */
+    /* running state and results, per world */
+    uint8_t *world_active;       /* [W] */
+    float *episode_lengths;      /* [W] the first t at which every mask slot of the world is done; 0 if that never happened */
+    int32_t *bad_indices;        /* [W] live rows whose action index was outside the table (added to gd_stat 45 at the end) */
+    int32_t *any_active;         /* [92] 1 where some world was active before step t: iteration t of the reference's loop exists */
+    float *goal_achieved_count, *frac_goal_achieved, *collided_count, *frac_collided, *off_road_count, *frac_off_road,
+        *other_count, *frac_other, *controlled_per_scene;  /* [W] each; a fraction is NaN for a world without rows */
+    float *summary;              /* [8] the totals of the four counts (goal_achieved, collided, off_road, other), n_rows,
+                                  * worlds_with_rows, iterations, mean_episode_length */
+    /* optional per-step records (NULL: not written); only iterations that exist are written */
+    int64_t *actions_idx;        /* [N][91] what the policy chose for the row, -1 once the row is dead */
+    uint8_t *live_mask;          /* [N][91] the row was live BEFORE step t */
+    float *agent_positions;      /* [W][A][91][2] absolute_self_observation columns 0, 1 of every slot AFTER step t */
+} gd_policy_rollout_buffers;
+/* For t in [0, n_steps), on the simulator's stream: gd_policy_forward on all N rows of the attached buffer with u + t * N (or
+ * the deterministic argmax; always the unmasked forward, a dropout rule is neither consulted nor advanced), the action kernel
+ * (action[:, :, :3] of every slot: table[index] for a live row, table[0] for every other slot; a live row's index outside
+ * the table leaves its action as it was and is counted), the step, the bookkeeping kernel (one workgroup per world: the
+ * sums, live &= !done, the world test, episode_lengths, any_active[t + 1], the records); then a per-world kernel (counts and
+ * fractions) and a one-workgroup summary.  Iterations after every world is inactive change no output (the simulator still
+ * steps).  With n_steps < 91 the result is the prefix of the full episode.  It does not reset and does not advance the log
+ * playback: the caller does.  2 launches per step beside the forward's three and the step's, no host synchronisation, no
+ * allocation, no atomics.
+ * GD_ERR_INVALID: a null pointer, n_rows outside [1, 2^20] or not the number of learner rows, n_steps outside [1, 91], no
+ * learner rows or no row buffer attached, a policy whose max_agents, ego_width or num_rows differs from the simulator's and
+ * its buffer's, n_actions different from the policy's, reserved != 0, a misaligned pointer, whatever gd_policy_forward
+ * refuses.  GD_ERR_UNSUPPORTED for the State dynamics model (no discrete action space). */
+int gd_policy_rollout(gd_sim *sim, const gd_policy *policy, const gd_policy_rollout_buffers *buffers, int32_t n_steps);
 /* The hidden states a linear probe reads (the reference's forward hooks, baselines/il/linear_probing.py:68-95): out [n][A][64]
  * float32, 16-byte aligned, receives tokens 0 .. A - 1 (the ego, then the partners) of the last_hidden_state of the tapped
  * block -- fusion_attn after its fusion_layers self layers, or ro_attn after its branch_layers more.  Per chunk gd_bc_forward's
