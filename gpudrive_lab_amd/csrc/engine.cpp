@@ -207,7 +207,7 @@ struct gd_sim {
     bool rk_possible = false;  // reference order, k-NN, not switched off: a batch may take the rank replay
     bool rk_alloc = false;     // its buffers exist
 
-    // 5.7 KB per agent slot for ALL W * A slots (0.37 GB at 1024 x 64, 1.5 GB at 4096 x 64), allocated when a batch first takes
+    // 4.7 KB per agent slot for ALL W * A slots (0.31 GB at 1024 x 64, 1.2 GB at 4096 x 64), allocated when a batch first takes
     // the rank replay and kept for the life of the simulator.  The path is a scheduling choice, never a result: when the
     // device cannot give the memory, what was allocated is returned, the batch stays on k_map_obs (same rows) and the
     // rank replay is not tried again for this simulator.
@@ -232,7 +232,7 @@ struct gd_sim {
             alloc_into(mine, n.cp_road, 2 * WA * GD_RANK_NCP);
             alloc_into(mine, n.cp_T, 2 * WA * GD_RANK_NCP);
             alloc_into(mine, n.cp_hdr, 2 * WA);
-            alloc_into(mine, n.rk_words, WA * GD_RANK_NCH);
+            alloc_into(mine, n.rk_cp, WA * GD_RANK_NCP);
             alloc_into(mine, n.rk_tl, WA);
             alloc_into(mine, n.rk_hist, 544);
             alloc_into(mine, n.rk_ticket, WA);

@@ -18,7 +18,7 @@
 #define GD_RANK_CAP_LONG 2560   // candidates of an agent that the long-list instantiation of the ranking takes (map_obs_rank.hip)
 #define GD_RANK_KT_LONG 164     // its key-table row (CAP_LONG / 16 entries + the last, padded to 16 bytes)
 #define GD_RH_LONG 537          // rk_hist: agents on the long list in this selection
-#define GD_RANK_NCH 320  // candidate words per agent: 32 roads each, kMaxRoadEntityCount = 10,000
+#define GD_RANK_NCH 320  // 32-road words of a world's road bitmap (k_knn_finish): kMaxRoadEntityCount = 10,000
 #define GD_RANK_SPL 256  // sorted slots whose road index k_knn_rank hands on: the K elements the heap ends with have the K smallest
                          // keys, i.e. fewer than K candidates below them and at most 31 equal ones before them: slot < K + 31
 #define GD_RANK_KT 84    // floats per agent of the key table: the candidates' key at every 16th sorted slot (CAP / 16 entries), the
@@ -184,7 +184,8 @@ struct DevSim {
     int32_t *rk_ticket;    // [W][A] bin << 20 | place inside the bin (bit 30: fell back after taking it); -1 = not on the rank path this step; < -1: why
     int32_t *rk_order;     // [W][A] agents on the rank path, most candidates first
     int32_t *rk_list;      // [8][W][A] agents on the rank path, one list per XCD that scanned them (counts: rk_hist[528..535])
-    uint32_t *rk_words;    // [W][A][NCH] candidate bits of 32 roads, one row per agent (k_knn_scan -> k_knn_rank)
+    uint2 *rk_cp;          // [W][A][NCP] the checkpoints that bound this selection's candidates: (first road, running maximum; threshold
+                           // bits), entries behind the agent's last one (0xffffffff, +inf) (k_knn_scan -> k_knn_rank; rank_cand.hpp)
     float *rk_tl;          // [W][A] the last K-th key of the checkpoint set in use (scales the ranking buckets)
     const float4 *road_bbox;  // [W] (min x, min y, max x, max y) over the world's roads
     const float *road_rbmax;  // [W] the largest bounding radius (half diagonal) of a road of the world

@@ -6,8 +6,10 @@
 // agent: 128 agents per CU, one lone wave per SIMD, two generations of workgroups at 1024 x 64).  The heap's
 // behaviour depends only on the OUTCOME of key comparisons, so this file replays it on ranks:
 //
-//   k_knn_scan +  The agent's CANDIDATES (scan: one lane per agent over every road of the world; rank: one wave per agent
-//   k_knn_rank    over its candidates): roads 0..K-1 plus every later
+//   k_knn_scan +  The agent's CANDIDATES (scan: one lane per agent, the set-up -- who takes this path, and the row of checkpoints
+//   k_knn_rank    that bounds the agent's candidates; rank: one wave per agent, which culls the world's blocks of 16 roads
+//                 against that row, scans the surviving blocks in index order and keys what passes: rank_cand.hpp): roads
+//                 0..K-1 plus every later
 //                 road whose key is below a bound that provably is not smaller than the K-th distance the heap holds when
 //                 the reference reaches that road.  The bound comes from the previous selection of the same agent: the
 //                 K-th smallest distance over a fixed prefix of roads is 1-Lipschitz in the agent's position, and the
@@ -36,6 +38,7 @@
 
 #include "engine.hpp"
 #include "gd_math.hpp"
+#include "rank_cand.hpp"
 #include "rank_heap.hpp"
 
 namespace gd {
@@ -109,15 +112,13 @@ __device__ __forceinline__ int wave_max(int v) {
 __device__ __forceinline__ float wave_max_nonneg(float f) { return __int_as_float(wave_max(__float_as_int(f))); }
 __device__ __forceinline__ float wave_min_nonneg(float f) { return __int_as_float(~wave_max(~__float_as_int(f))); }
 __device__ __forceinline__ int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_incl_scan(v), 63); }
+// set bits of a ballot below this lane's own (v_mbcnt_lo / v_mbcnt_hi)
+__device__ __forceinline__ int bits_below_lane(unsigned long long b) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)b, 0u));
+}
 
-// Scratch rows that one kernel writes once and the next reads once (candidate words, ranks, heap arrays, tables): streaming
+// Scratch rows that one kernel writes once and the next reads once (checkpoint rows, ranks, heap arrays, tables): streaming
 // (nt) accesses, so that they take no room from what the step reads again and again (the road arrays, the pose planes).
-#ifndef GD_NT_SCAN_STORE
-#define GD_NT_SCAN_STORE 0
-#endif
-#ifndef GD_NT_WORDS_LOAD
-#define GD_NT_WORDS_LOAD 1
-#endif
 #ifndef GD_NT_FINISH_LOAD
 #define GD_NT_FINISH_LOAD 1
 #endif
@@ -159,13 +160,13 @@ __device__ __forceinline__ int audited(const DevSim &d, int idx, int size) {
 __device__ __forceinline__ bool rank_lt(unsigned int a, unsigned int b, unsigned int tm = 31u) { return (a | tm) < b; }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_knn_scan: one lane per agent, one workgroup (4 waves) per 64 agent slots of a world.  Every road of the world is tested
-// against every agent's bound with the cheap form |p - e|^2 < bound * margin (the margin covers rounding and the squared
-// norm of the stored quaternion, like k_map_obs's scan), 32 roads per candidate word; the roads come through LDS as
-// broadcast reads, so a road costs a wave one LDS instruction and five vector instructions for 64 agents.
+// k_knn_scan: the SET-UP of the selection, one lane per agent, one workgroup (4 waves) per 64 agent slots of a world: which
+// agents take the rank path, and the checkpoints that bound each one's candidates -- first road and threshold of the cheap
+// form |p - e|^2 < bound * margin (the margin covers rounding and the squared norm of the stored quaternion, like k_map_obs's
+// scan) -- from its previous selection, a neighbour's, or made afresh.  The row of checkpoints is what it hands to
+// k_knn_rank (rk_cp, 320 B per agent), which finds the candidates itself (rank_cand.hpp): this kernel used to test every road
+// of the world against every agent and hand over 1280 B of candidate bits.
 // ------------------------------------------------------------------------------------------------------------------
-constexpr int SCAN_TILE = 2048;  // roads staged in LDS at a time
-
 template <int A_T>
 __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
@@ -181,20 +182,13 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     const int r0 = d.road_off[w];
     const int R = d.road_off[w + 1] - r0;
 
-    __shared__ __attribute__((aligned(16))) float2 s_xy[SCAN_TILE];
-    __shared__ unsigned short s_first[NCP][64];  // checkpoint q of lane l: first road it holds for ...
-    __shared__ float s_thr[NCP][64];             // ... and the scan threshold it gives
-    __shared__ int s_ncp[64];                    // checkpoints of lane l; 0: the lane takes no part in the scan
+    __shared__ unsigned short s_first[NCP][64];  // checkpoint q of lane l: first road it holds for (running maximum: rank_cand.hpp) ...
+    __shared__ float s_thr[NCP][64];             // ... and the threshold it gives
+    __shared__ int s_ncp[64];                    // checkpoints of lane l; 0: the agent is not on the rank path
     __shared__ unsigned int s_needy[2];          // the agents to be bounded afresh (bit per lane), as the first wave saw them
-    // (40 KB in all: four workgroups per CU, i.e. every workgroup of a 1024-world launch resident at once -- with 46 KB, three
-    // per CU and a second generation, the kernel took 91 us instead of 61.  What only the set-up before the scan loop needs
-    // therefore lives in the buffers of the loop: the transpose buffer and the road tile)
-    constexpr int TB = 8;
-    __shared__ __attribute__((aligned(16))) unsigned int s_tr[4][TB][65];
-    static_assert(sizeof(float4) * 64 + sizeof(float) * 192 <= sizeof(unsigned int) * 4 * TB * 65 && 4 * 256 * 4 <= sizeof(float2) * SCAN_TILE, "aliases fit");
-    float4 *const s_hdr = reinterpret_cast<float4 *>(&s_tr[0][0][0]);  // where and how many checkpoints lane l's previous selection recorded
-    float *const s_bx = reinterpret_cast<float *>(s_hdr + 64), *const s_by = s_bx + 64, *const s_bm = s_by + 64;  // position and margin of lane l's agent (for the waves that bound it afresh)
-    unsigned int (*const s_hist)[256] = reinterpret_cast<unsigned int (*)[256]>(s_xy);  // per wave: histogram of squared distances of the roads scanned so far
+    __shared__ float4 s_hdr[64];                 // where and how many checkpoints lane l's previous selection recorded
+    __shared__ float s_bx[64], s_by[64], s_bm[64];  // position and margin of lane l's agent (for the waves that bound it afresh)
+    __shared__ unsigned int s_hist[4][256];      // per wave: histogram of squared distances of the roads streamed so far
 
     float ex = 0.f, ey = 0.f;
     if (live) { ex = d.px[i]; ey = d.py[i]; }
@@ -277,12 +271,14 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
                     const unsigned short *cr = d.cp_road + ((size_t)set * WA + src) * NCP;
                     const float *ct = d.cp_T + ((size_t)set * WA + src) * NCP;
                     float t = 1.f;
+                    unsigned int fmax = 0u;  // (rank_cand.hpp: with the running maximum "in force" is a count of entries)
                     for (int q = 0; q < ncp; q++) {
                         t = ct[q];
                         const float reach = sqrtf(t) * 1.0001f + move * 1.0001f + 1e-3f;
                         float thr = reach * reach * 1.0001f * margin;
                         if (!(thr >= 0.f)) thr = __builtin_inff();  // an unusable entry bounds nothing
-                        s_first[q][lane] = cr[q];
+                        fmax = rank_cand::running_max(fmax, cr[q]);
+                        s_first[q][lane] = (unsigned short)fmax;
                         s_thr[q][lane] = thr;
                     }
                     d.rk_tl[i] = t;  // the last K-th key: scales the ranking buckets
@@ -306,6 +302,8 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
         // road points are gathered into the L2 that scanned them, and eight counters are asked instead of one: a thousand
         // workgroups adding to one address at once cost the kernel 10 us)
         ranked = __ballot(ncp > 0);
+        // their place in the list: asked for now, needed at the very end (a trip to the L2 and back behind the work below)
+        if (ranked != 0ull && lane == 0) list_base = atomicAdd(&d.rk_hist[528 + (blockIdx.x & 7)], __popcll(ranked));
     }
     __syncthreads();
     // ---- agents without a usable bound: one wave each streams the world's roads once, in scan order, and keeps a histogram of
@@ -374,54 +372,16 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     }
     const int ncp = s_ncp[lane];
     if (__syncthreads_or(ncp > 0 ? 1 : 0) == 0) return;  // no agent of this workgroup is on the rank path (far, fallback, bypass)
-    int q = -1;  // checkpoint in force for this lane
-    const int nch = (R + 31) >> 5;
-    // A wave takes 16 consecutive chunks of the tile, 8 at a time: the agents' words of a batch are handed over agent-major
-    // (k_knn_rank reads an agent's words as one row) through an LDS transpose, 32 bytes per agent, wave and batch
-    uint32_t *words = d.rk_words + ((size_t)w * A_T + a0) * GD_RANK_NCH;
-    for (int tile = 0; tile < R; tile += SCAN_TILE) {
-        __syncthreads();
-        for (int r = tile + tid; r < min(R, tile + SCAN_TILE); r += 256) s_xy[r - tile] = d.road_xy[r0 + r];
-        __syncthreads();
-        // the place of this workgroup's ranked agents in their list: asked for once the wave's last loads are in (memory
-        // operations complete in order: asked earlier it held up the road loads, asked at the very end nothing hides it)
-        if (wave == 0 && ranked != 0ull && lane == 0 && tile + SCAN_TILE >= R)
-            list_base = atomicAdd(&d.rk_hist[528 + (blockIdx.x & 7)], __popcll(ranked));
-#pragma clang loop unroll(disable)
-        for (int c_first = (tile >> 5) + wave * 16; c_first < (tile >> 5) + wave * 16 + 16 && c_first < nch; c_first += TB) {
-#pragma clang loop unroll(disable)
-            for (int k = 0; k < TB; k++) {
-                const int c = c_first + k;
-                unsigned int wd = 0;
-                if (c < nch) {  // wave-uniform
-                    const int base = c << 5;
-                    while (q + 1 < ncp && (int)s_first[q + 1][lane] <= base) q++;
-                    const float thr = q >= 0 ? s_thr[q][lane] : __builtin_inff();
-                    const float2 *t = s_xy + (base - tile);
-#pragma unroll
-                    for (int j = 31; j >= 0; j--) {
-                        const float2 xy = t[j];  // the same address in every lane: a broadcast read
-                        const float dx = xy.x - ex, dy = xy.y - ey;
-                        const float d2 = __builtin_fmaf(dx, dx, dy * dy);
-                        wd = __builtin_amdgcn_alignbit(wd, __float_as_uint(d2 - thr), 31);  // (wd << 1) | (d2 < thr)
-                    }
-                    if (base < K) wd |= K - base >= 32 ? 0xffffffffu : (1u << (K - base)) - 1u;  // roads below K regardless
-                    const int left = R - base;
-                    if (left < 32) wd &= (1u << left) - 1u;
-                }
-                s_tr[wave][k][lane] = wd;
-            }
-            wave_sync();
-#pragma unroll
-            for (int it = 0; it < TB; it++) {
-                const int ag = it * 8 + (lane >> 3), k = lane & 7;
-#if GD_NT_SCAN_STORE
-                if (c_first + k < nch && s_ncp[ag] > 0) stream_store(s_tr[wave][k][ag], words + (size_t)ag * GD_RANK_NCH + c_first + k);
-#else
-                if (c_first + k < nch && s_ncp[ag] > 0) words[(size_t)ag * GD_RANK_NCH + c_first + k] = s_tr[wave][k][ag];
-#endif
-            }
-            wave_sync();
+    // The checkpoint rows of the agents on the rank path, agent-major (k_knn_rank reads an agent's row as one coalesced
+    // load), whole rows: the entries behind an agent's last checkpoint are never in force
+    {
+        uint2 *rows = d.rk_cp + ((size_t)w * A_T + a0) * NCP;
+        for (int e = tid; e < 64 * NCP; e += 256) {
+            const int ag = e / NCP, q = e - ag * NCP;
+            const int n_ag = s_ncp[ag];
+            if (n_ag > 0)
+                rows[e] = q < n_ag ? make_uint2((unsigned int)s_first[q][ag], __float_as_uint(s_thr[q][ag]))
+                                   : make_uint2(rank_cand::NO_CP, __float_as_uint(__builtin_inff()));
         }
     }
     if (wave == 0 && ranked != 0ull) {
@@ -432,7 +392,9 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_knn_rank: one wave per live agent.  Candidate words -> candidate list, exact keys, ranks.
+// k_knn_rank: one wave per live agent.  Checkpoint row -> candidate list with exact keys (rank_cand.hpp: the blocks of 16
+// consecutive roads that cannot hold a candidate are culled, a lane per block; the surviving blocks are scanned in index
+// order, four per pass, coalesced), ranks.
 // ------------------------------------------------------------------------------------------------------------------
 // 10 KB of LDS per agent, so that sixteen waves fit a CU: the kernel is a chain of LDS and memory round trips, and with two
 // waves per SIMD (20 KB) it waited 46 % of its cycles (profiles/r03: SQ_WAIT_ANY).  A lane keeps its up to 20 candidates
@@ -440,31 +402,42 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
 template <int CAP_T>
 struct RankLds {
     union {
-        unsigned short cidx[CAP_T];       // candidate road indices in road order, while the word expansion hands them to their lanes
+        struct {
+            float ckey[CAP_T];            // the candidates' exact keys and ...
+            unsigned short cidx[CAP_T];   // ... road indices in road order, while the scan hands them to their lanes
+        } c;
         struct {
             float skey[CAP_T];            // the keys in bucket order
             unsigned short spos[CAP_T];   // bucket order -> candidate position
         } s;
         unsigned short spc[CAP_T];        // at the end: sorted slot -> road index
     };
-    unsigned int cnt2[RankGeo<CAP_T>::NB / 2];  // bucket counters, two u16 per word; then cursors: after the scatter the END of each bucket
+    // bucket counters, two u16 per word; then cursors: after the scatter the END of each bucket.  Idle until the bucket
+    // counts, so the cull and the scan keep their tables here: the surviving blocks (block | checkpoints at or before it << 10,
+    // ascending) and the thresholds by that count (entry 0: unbounded)
+    unsigned int cnt2[RankGeo<CAP_T>::NB / 2];
 };
 static_assert(sizeof(RankLds<CAP>) <= 10240 && sizeof(RankLds<CAP_LONG>) <= 20480, "sixteen / eight waves per CU");
+constexpr int LSTN = (GD_MAX_ROAD_ENTITIES + GD_LIN_BLK - 1) / GD_LIN_BLK + 15;  // blocks of the largest world, rounded to a multiple of 4 below
+constexpr int LSTN4 = (LSTN + 3) & ~3;
+static_assert(LSTN4 <= 1024 && NCP < 64 && rank_cand::CHUNK % GD_LIN_BLK == 0 && 64 % GD_LIN_BLK == 0, "block and count share 16 bits; a block inside one chunk; whole blocks per pass");
+constexpr size_t CAND_TABLES = LSTN4 * sizeof(unsigned short) + (NCP + 1) * sizeof(float);
+static_assert(CAND_TABLES <= sizeof(RankLds<CAP>::cnt2) && CAND_TABLES <= sizeof(RankLds<CAP_LONG>::cnt2), "the tables fit the idle counters of both instantiations");
 
 // What the ranking of one agent reads from global memory before it can start, fetched while the previous agent of the
 // wave is being ranked (the fetches are a chain of dependent loads, several microseconds end to end).
-constexpr int WPL = GD_RANK_NCH / 64;  // candidate words per lane
 struct RankIn {
-    int i, state, r0, R, li;  // li: the entry of the list this agent came from (a long list's scratch rows go by it)
+    int i, state, r0, R, b0, li;  // li: the entry of the list this agent came from (a long list's scratch rows go by it)
     float ex, ey, iw, iz, t_last;
-    unsigned int wd[WPL];
+    unsigned int cfirst;  // lane q: checkpoint q of the agent's row (k_knn_scan's rk_cp); lanes from NCP on: never in force
+    float cthr;
 };
 // A value at a wave-uniform address that this kernel does not change, read through the scalar cache.  As vector loads the
 // chain list -> agent -> state / pose waited, at each link, for every store the wave had issued for the previous agent
 // (vector memory operations are counted in order): a fifth of the kernel.
 // INVARIANT (nothing enforces it but the call sites below): the scalar cache is not coherent with this kernel's own vector
 // stores, so an address read through here must never be read AFTER any wave of the same launch has written it.  What is
-// read this way: arrays written by EARLIER kernels only (rk_list, rk_hist[528..], rk_tl, road_off, the pose planes: the
+// read this way: arrays written by EARLIER kernels only (rk_list, rk_hist[528..], rk_tl, road_off, blk_off, the pose planes: the
 // scalar cache is invalidated at every kernel boundary), and rk_n[i] -- which this kernel does rewrite, but only the wave
 // that ranks agent i writes rk_n[i], and it reads it (rank_fetch) before it writes it (end of rank_agent); a cache line
 // shared with another agent's already rewritten entry may be stale for THAT entry, which this wave never looks at.
@@ -484,13 +457,11 @@ __device__ __forceinline__ RankIn rank_fetch(const DevSim &d, const int *list, i
     in.ex = uniform_load(d.px + in.i); in.ey = uniform_load(d.py + in.i);
     in.iw = uniform_load(d.qw + in.i); in.iz = -uniform_load(d.qz + in.i);  // the INVERSE rotation
     in.t_last = uniform_load(d.rk_tl + in.i);
-    const int nch = (in.R + 31) >> 5;
-    const uint32_t *words = d.rk_words + (size_t)in.i * GD_RANK_NCH;  // agent-major: one coalesced read
-#pragma unroll
-    for (int k = 0; k < WPL; k++) {
-        const int c = k * 64 + lane;
-        in.wd[k] = (in.state == 1 && c < nch) ? (GD_NT_WORDS_LOAD ? stream_load(words + c) : words[c]) : 0u;
-    }
+    in.b0 = uniform_load(d.blk_off + w);
+    uint2 cp = make_uint2(rank_cand::NO_CP, __float_as_uint(__builtin_inff()));
+    if (in.state == 1 && lane < NCP) cp = stream_load(d.rk_cp + (size_t)in.i * NCP + (unsigned int)lane);  // agent-major: one coalesced read
+    in.cfirst = cp.x;
+    in.cthr = __uint_as_float(cp.y);
     return in;
 }
 
@@ -516,8 +487,6 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     using G = RankGeo<CAP_T>;
     constexpr int NB = G::NB, NLIN = G::NLIN, NMAX = G::NMAX;
     constexpr unsigned int TM = (1u << G::RSH) - 1u;  // most equal keys before a candidate that its rank can count
-    // The next agent's inputs are requested in the middle of this one, behind the last gather of the keys: vector memory
-    // operations complete in order, so requested up front they (1.3 KB from HBM) were what every gather then waited for.
     if (__builtin_amdgcn_readfirstlane(in.state) != 1) {  // fallback or too far from every road (k_knn_scan)
         nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
         return;
@@ -530,18 +499,107 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     const int group = i / 32;  // 32 consecutive agent slots of a world: the fallback unit (a workgroup of k_map_obs)
     constexpr int NG = G::NG;  // candidates per lane
 
-    // ---- how many candidates?  More than this instantiation ranks: on to the long-list instantiation, or to the fallback ----
-    const int nch = (R + 31) >> 5;
-    {
-        int mine = 0;
+    const float ex = unif(in.ex), ey = unif(in.ey), iw = unif(in.iw), iz = unif(in.iz);
+    // ---- CULL (rank_cand.hpp): lane l takes block b0 + l of the world's road blocks (GD_LIN_BLK consecutive roads inside a
+    // circle, engine.hpp road_blk) and drops it if no road of it can be a candidate under the checkpoint in force for it; the
+    // survivors are listed in ascending order, one ballot per 64 blocks = 1024 roads.  Lane q holds checkpoint q of the row
+    // (first roads non-decreasing: k_knn_scan stores the running maximum), so the checkpoints at or before a block's chunk are
+    // a prefix of the row: those at or before the batch's first chunk are counted by one ballot, and only the few that start
+    // inside the batch are compared lane by lane. ----
+    unsigned short *const lst = reinterpret_cast<unsigned short *>(L.cnt2);
+    float *const tthr = reinterpret_cast<float *>(L.cnt2) + LSTN4 / 2;  // threshold by checkpoints at or before: 0 = unbounded
+    const unsigned int cfirst = in.cfirst;
+    if (lane < NCP) tthr[lane + 1] = in.cthr;
+    if (lane == 63) tthr[0] = __builtin_inff();
+    const float creach = rank_cand::block_reach(in.cthr);  // (lanes from NCP on: +inf, which is also what "no checkpoint" reads)
+    const int nblk = (R + GD_LIN_BLK - 1) / GD_LIN_BLK;
+    const float4 *blk = d.road_blk + uni(in.b0);
+    int nsv = 0;
+    constexpr int CU = 4;  // batches of 64 blocks requested together
+#pragma clang loop unroll(disable)
+    for (int b0 = 0; b0 < nblk; b0 += 64 * CU) {
+        float4 c[CU];
 #pragma unroll
-        for (int k = 0; k < WPL; k++) {
-            const int c = k * 64 + lane;
-            unsigned int wd = k * 64 < nch ? in.wd[k] : 0u;
-            if (k == 0) wd = c < K / 32 ? 0u : (c == K / 32 ? wd & ~((1u << (K % 32)) - 1u) : wd);
-            mine += __popc(wd);
+        for (int u = 0; u < CU; u++) c[u] = blk[(unsigned int)min(b0 + u * 64 + lane, nblk - 1)];
+#pragma unroll
+        for (int u = 0; u < CU; u++) {
+            const int bb = b0 + u * 64;
+            if (bb < nblk) {  // wave-uniform
+                const int b = bb + lane;
+                const unsigned int base = (unsigned int)rank_cand::chunk_base_of_block(b, GD_LIN_BLK);
+                const unsigned int base_lo = (unsigned int)rank_cand::chunk_base_of_block(bb, GD_LIN_BLK);
+                const unsigned int base_hi = (unsigned int)rank_cand::chunk_base_of_block(min(bb + 63, nblk - 1), GD_LIN_BLK);
+                const int nlo = __popcll(__ballot(cfirst <= base_lo)), nhi = __popcll(__ballot(cfirst <= base_hi));
+                int cnt = nlo;
+                for (int q = nlo; q < nhi; q++) cnt += (unsigned int)__builtin_amdgcn_readlane((int)cfirst, q) <= base ? 1 : 0;
+                // the reach of checkpoint cnt - 1; none: lane 63's, +inf
+                const float reach = __int_as_float(__builtin_amdgcn_ds_bpermute(((cnt - 1) & 63) << 2, __float_as_int(creach)));
+                const bool sv = b < nblk && rank_cand::block_survives(b, GD_LIN_BLK, K, c[u].x, c[u].y, c[u].z, ex, ey, reach);
+                const unsigned long long m = __ballot(sv);
+                if (sv) lst[audited(d, nsv + bits_below_lane(m), LSTN4)] = (unsigned short)(b | cnt << 10);
+                nsv += __popcll(m);
+            }
         }
-        const int total = K + wave_sum(mine);
+    }
+    wave_sync();
+    // ---- SCAN of the surviving blocks, four per pass (a quarter of the wave each), in index order: the per-road test
+    // (rank_cand.hpp: k_knn_scan's former expression, bit for bit), the exact key (gd_math.hpp ego_dist2: the reference's
+    // arithmetic), one ballot per pass; (road, key) go to LDS at the candidate's position.  PB passes are requested together,
+    // the next PB before these are keyed.  Roads 0..K-1 are candidates regardless and their blocks always survive, so the
+    // first K positions are their indices.  Writes stop at the buffer's end, the count goes on. ----
+    int nin = 0;
+    {
+        // (PB passes requested together, twice that in flight.  Measured at 1024 x 64, one run of 150 steps each, k_knn_rank with
+        // PB = 2: 420 us, 4: 422, 8: 431 -- the scan does not wait for its own loads)
+        constexpr int BPP = 64 / GD_LIN_BLK, PB = 2;  // blocks per pass
+        const int np = (nsv + BPP - 1) / BPP;
+        const int sub = lane / GD_LIN_BLK, o = lane % GD_LIN_BLK;
+        const float2 *rxy = d.road_xy + r0;
+        struct Batch { int r[PB]; float thr[PB]; float2 xy[PB]; };
+        auto issue = [&](Batch &bt, int p0) {
+#pragma unroll
+            for (int u = 0; u < PB; u++) {
+                const int e = (p0 + u) * BPP + sub;
+                const unsigned int ent = lst[min(e, LSTN4 - 1)];
+                const bool on = e < nsv;
+                const int r = on ? (int)(ent & 1023u) * GD_LIN_BLK + o : R;
+                bt.r[u] = r;
+                bt.thr[u] = tthr[on ? min((int)(ent >> 10), NCP) : 0];
+                bt.xy[u] = rxy[(unsigned int)min(r, R - 1)];
+            }
+        };
+        auto take = [&](const Batch &bt) {
+#pragma unroll
+            for (int u = 0; u < PB; u++) {
+                const bool cand = rank_cand::is_candidate(bt.r[u], K, R, bt.xy[u].x, bt.xy[u].y, ex, ey, bt.thr[u]);
+                const float key = ego_dist2(ex, ey, iw, iz, bt.xy[u].x, bt.xy[u].y);
+                const unsigned long long m = __ballot(cand);
+                const int pos = nin + bits_below_lane(m);
+                if (cand && pos < CAP_T) {
+                    L.c.cidx[pos] = (unsigned short)bt.r[u];
+                    L.c.ckey[pos] = key;
+                }
+                nin += __popcll(m);
+            }
+        };
+        Batch ba, bb;
+        issue(ba, 0);
+#pragma clang loop unroll(disable)
+        for (int p0 = 0; p0 < np; p0 += 2 * PB) {
+            issue(bb, p0 + PB);
+            take(ba);
+            if (p0 + PB >= np) break;
+            issue(ba, p0 + 2 * PB);
+            take(bb);
+        }
+    }
+    wave_sync();
+    // The next agent's inputs are requested here, behind the last road loads of this one: vector memory operations complete
+    // in order, so requested up front they (from HBM) were what every load of the scan then waited for.
+    nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
+    // ---- more candidates than this instantiation ranks: on to the long-list instantiation, or to the fallback ----
+    {
+        const int total = nin;
         // (NMAX = CAP - 8: the sorted key array ends in eight +inf entries that reads past a bucket's end run into.  Round 3
         // took up to CAP candidates; with exactly CAP there was no room for an end marker and the clamp that stood in for it
         // re-read the LAST entry of the last bucket, which is not necessarily its largest: a candidate of that bucket could
@@ -562,78 +620,34 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
                     d.rk_fallback[group] = 1;
                 }
             }
-            nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
             return;
         }
     }
-
-    // ---- candidate words -> road indices in ascending order ----
-    // Roads 0..K-1 are candidates regardless (k_knn_scan sets their bits) and their positions are their indices: written
-    // directly, not bit by bit (the lanes that own those seven words would loop 32 times while the others wait)
-    static_assert(K == 200 && CAP >= 256, "roads 0..K-1: four stores per lane");
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        if (q * 64 + lane < K) L.cidx[q * 64 + lane] = (unsigned short)(q * 64 + lane);
-    int nin = K;
-#pragma unroll
-    for (int k = 0; k < WPL; k++) {
-        if (k * 64 >= nch) break;  // wave-uniform
-        const int c = k * 64 + lane;
-        unsigned int wd = in.wd[k];
-        if (k == 0) wd = c < K / 32 ? 0u : (c == K / 32 ? wd & ~((1u << (K % 32)) - 1u) : wd);
-        const int pc = __popc(wd);
 #ifdef GD_CLOCKS
-        clk.sum[7] += (unsigned int)wave_max(pc) << 8;  // the wave's trips through the loop below (gd_stat 17)
+    clk.sum[7] += (unsigned int)((nsv + 3) / 4) << 8;  // the wave's passes through the scan above (gd_stat 17)
 #endif
-        const int incl = wave_incl_scan(pc);
-        int pos = nin + incl - pc;
-        nin += __builtin_amdgcn_readlane(incl, 63);
-        while (wd) {
-            L.cidx[pos++] = (unsigned short)((c << 5) + __ffs(wd) - 1);
-            wd &= wd - 1u;
-        }
-    }
-    wave_sync();
     // the agent's place in the replay order (k_knn_order: most candidates first).  Taken now: the counter's
     // answer is a trip to the L2 and back that nothing has to wait for until the agent is done
     const int bin = 255 - min(255, (nin - K) / 5);
     int ticket = 0;
     if (lane == 0) ticket = bin << 20 | atomicAdd(&d.rk_hist[bin], 1);
     GD_PHASE(1);
-    if (GD_DIAG_IS(d.rk_dbg, 1)) {
-        nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
-        return;
-    }
+    if (GD_DIAG_IS(d.rk_dbg, 1)) return;
     // where this selection's checkpoints start to apply (their K-th distances are filled in by k_knn_finish): checkpoint 0
     // is the heap of the first K roads (road indices below K are candidates regardless), checkpoint q the heap after
     // candidate K + 32 q - 1, which holds for every road behind that candidate; rounded up to whole 32-road chunks of the scan
     if (lane <= (nin - K) >> G::TSH) {
-        const int road = (int)L.cidx[K - 1 + (lane << G::TSH)];
+        const int road = (int)L.c.cidx[K - 1 + (lane << G::TSH)];
         d.cp_road[(size_t)i * NCP + lane] = (unsigned short)(lane ? min(65535, (road + 1 + 31) & ~31) : (K / 32) * 32);
     }
-    // A lane has 13 candidates on average, 20 at most.  The passes over them go in groups of GQ with one wave-uniform guard
-    // per group and nothing conditional inside (idle lanes work on road 0): a guard per candidate is a branch per candidate,
-    // and the compiler then waits for each load before it issues the next
+    // ---- refill: lane l takes the candidates at positions l, l + 64, ... (road index and key) from LDS into registers ----
+    // A lane has 13 candidates on average, 20 at most.  They are read in groups of GQ with one wave-uniform guard per group;
+    // inside a group every lane reads, and a lane whose position lies beyond the last candidate keeps road 0 and key 0 instead of
+    // the stale entry it read (its values take part in the passes below but never in a count, a store or a rank)
     constexpr int GQ = 5;
     static_assert(NG % GQ == 0, "whole groups");
-    int ci[NG];
-#pragma unroll
-    for (int g0 = 0; g0 < NG; g0 += GQ) {
-#pragma unroll
-        for (int u = 0; u < GQ; u++) ci[g0 + u] = 0;
-        if (g0 * 64 < nin) {  // wave-uniform
-            int v[GQ];
-#pragma unroll
-            for (int u = 0; u < GQ; u++) v[u] = (int)L.cidx[(g0 + u) * 64 + lane];  // (beyond nin: stale, dropped below)
-#pragma unroll
-            for (int u = 0; u < GQ; u++) ci[g0 + u] = (g0 + u) * 64 + lane < nin ? v[u] : 0;
-        }
-    }
-    wave_sync();  // the index buffer becomes the sorted arrays
-    // ---- exact keys (gd_math.hpp ego_dist2: the reference's arithmetic); the gathers of a group are in flight together ----
-    const float ex = unif(in.ex), ey = unif(in.ey), iw = unif(in.iw), iz = unif(in.iz);
     const float kmax = d.radius_key_max;
-    const float2 *rxy = d.road_xy + r0;
+    int ci[NG];
     float key[NG];
     const float t_last = unif(in.t_last);
     float split = (t_last > 0.f && t_last < 1e30f) ? t_last * 1.5f : 1.f;
@@ -642,27 +656,33 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
 #pragma unroll
     for (int g0 = 0; g0 < NG; g0 += GQ) {
 #pragma unroll
-        for (int u = 0; u < GQ; u++) key[g0 + u] = 0.f;
+        for (int u = 0; u < GQ; u++) { ci[g0 + u] = 0; key[g0 + u] = 0.f; }
         if (g0 * 64 < nin) {  // wave-uniform
-            float2 xy[GQ];
+            int v[GQ];
+            float kv[GQ];
 #pragma unroll
-            for (int u = 0; u < GQ; u++) xy[u] = rxy[(unsigned int)ci[g0 + u]];
-            // (all five before the first use: left alone, the scheduler pairs each load with its arithmetic to save registers)
+            for (int u = 0; u < GQ; u++) {  // (beyond nin: stale, dropped below)
+                v[u] = (int)L.c.cidx[(g0 + u) * 64 + lane];
+                kv[u] = L.c.ckey[(g0 + u) * 64 + lane];
+            }
+            // (the ten LDS reads of a group are issued together and are complete here: without this the compiler sank each read
+            // into a per-lane branch on `on` below and kept key[] as one 32-register tuple that it copied at every group -- 624
+            // spilled registers)
             static_assert(GQ == 5, "operand list");
-            asm volatile("" : "+v"(xy[0].x), "+v"(xy[0].y), "+v"(xy[1].x), "+v"(xy[1].y), "+v"(xy[2].x), "+v"(xy[2].y),
-                              "+v"(xy[3].x), "+v"(xy[3].y), "+v"(xy[4].x), "+v"(xy[4].y));
+            asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(kv[0]), "+v"(kv[1]), "+v"(kv[2]), "+v"(kv[3]), "+v"(kv[4]));
 #pragma unroll
             for (int u = 0; u < GQ; u++) {
                 const int g = g0 + u;
-                key[g] = ego_dist2(ex, ey, iw, iz, xy[u].x, xy[u].y);
                 const bool on = g * 64 + lane < nin;
+                ci[g] = on ? v[u] : 0;
+                key[g] = on ? kv[u] : 0.f;
                 nle += ((on & (key[g] <= kmax)) ? 1 : 0) + ((on & (key[g] < split)) ? 1 << 16 : 0);
-                kmax_seen = fmaxf(kmax_seen, on ? key[g] : 0.f);
+                kmax_seen = fmaxf(kmax_seen, key[g]);
                 kmin_seen = fminf(kmin_seen, on ? key[g] : __builtin_inff());
             }
         }
     }
-    nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
+    wave_sync();  // the candidate buffer becomes the sorted arrays
     nle = wave_sum(nle);
     kmax_seen = wave_max_nonneg(kmax_seen);  // keys are sums of squares
     kmin_seen = wave_min_nonneg(kmin_seen);
@@ -922,7 +942,12 @@ __global__ __launch_bounds__(64, CAP_T > CAP ? 2 : 4) void k_knn_rank(DevSim d) 
     for (; t < count; t += stride) {
         RankIn nxt;
         GD_PHASE(0);  // between agents: the buffers change hands
-        rank_agent<A_T, CAP_T>(d, cur, threadIdx.x, L, clk, t + stride, count, list, nxt);
+        // (an opaque copy of the lane, per agent: what the ranking derives from the lane alone -- LDS addresses, row pointers,
+        // positions -- is then computed per agent.  Hoisted out of this loop those values sat in registers, or in scratch,
+        // through every phase, and the kernel has no register to spare)
+        int lane_v = threadIdx.x;
+        asm volatile("" : "+v"(lane_v));
+        rank_agent<A_T, CAP_T>(d, cur, lane_v, L, clk, t + stride, count, list, nxt);
         wave_sync();  // the LDS buffers change hands
         cur = nxt;
     }

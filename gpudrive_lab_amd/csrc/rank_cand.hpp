@@ -1,0 +1,76 @@
+// The rank path's candidate set (map_obs_rank.hip k_knn_scan -> k_knn_rank) as plain C++: the decisions that the kernel and
+// a host program share (tests/rank_cand_model.cpp runs the cull + in-order scan below against a plain loop over every road).
+//
+// An agent's candidates are roads 0..K-1 plus every later road r < R whose cheap squared distance is below the threshold of
+// the CHECKPOINT in force for r.  k_knn_scan leaves a row of checkpoints per agent: first[q] (a multiple of 32) and thr[q];
+// the checkpoint in force for a road is the last q with first[q] <= the base of the road's 32-road chunk, none (q = -1) means
+// unbounded.  k_knn_rank finds the candidates in two steps:
+//
+//   cull  a lane per block of BLK consecutive roads (the circle the engine keeps around every such block, engine.hpp
+//         road_blk): a block is dropped only if no road of it can pass the per-road test.  BLK divides 32 and first[] are
+//         multiples of 32, so a block lies inside one checkpoint's range and is tested against one threshold.
+//   scan  the surviving blocks in index order, every road of them through the per-road test.
+//
+// Why a dropped block holds no candidate.  Let D be the distance from the agent e to a road point p of the block, u = 2^-24.
+// The per-road test computes dx = fl(x - ex) = (x - ex)(1 + d1), |d1| <= u, likewise dy, and d2 = fl(fma(dx, dx, fl(dy dy)))
+// >= D^2 (1 - 4u); it passes only if d2 < thr, so D < sqrt(thr) (1 + 3u).  The block's circle (c, rad) holds p with the
+// host's inflation (rad = computed radius * 1.0001 + 1e-3, engine.cpp: far above the rounding of its own arithmetic), so
+// |c - e| <= D + rad, and the computed |c - e|^2 is at most (1 + 4u) times the true one.  The block test keeps the block
+// unless  fl|c - e|^2 > (reach + rad)^2 * 1.00001  with  reach = fl(sqrt(thr)) * 1.00001 >= sqrt(thr) (1 + 9e-6): every factor
+// of (1 + a few u) above is covered by the two factors of 1.00001, so a block with a passing road is kept.  thr = inf gives
+// reach = inf and keeps every block; a NaN anywhere compares false and keeps the block.
+#pragma once
+
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define GD_RC_FN __host__ __device__ __forceinline__
+#else
+#define GD_RC_FN inline
+#endif
+
+namespace gd {
+namespace rank_cand {
+
+constexpr int CHUNK = 32;                     // roads per chunk: first[] are multiples of it
+constexpr unsigned int NO_CP = 0xffffffffu;   // first[] of a row entry behind the agent's last checkpoint: never in force
+
+GD_RC_FN unsigned int f32_bits(float f) { return __builtin_bit_cast(unsigned int, f); }
+
+// (a) the per-road test, the expression and the sense of the scan it replaces: candidate <=> sign bit of d2 - thr
+GD_RC_FN bool road_passes(float x, float y, float ex, float ey, float thr) {
+    const float dx = x - ex, dy = y - ey;
+    const float d2 = __builtin_fmaf(dx, dx, dy * dy);
+    return (f32_bits(d2 - thr) >> 31) != 0u;
+}
+// roads below K are candidates regardless, roads at or beyond R never
+GD_RC_FN bool is_candidate(int r, int K, int R, float x, float y, float ex, float ey, float thr) {
+    return r < R && (r < K || road_passes(x, y, ex, ey, thr));
+}
+
+// (b) the checkpoint in force for the roads of the chunk that starts at `base`: the scan's rule, q advances while the next
+// entry starts at or before the chunk.  -1: none, the chunk is unbounded.
+GD_RC_FN int cp_in_force(const unsigned int *first, int ncp, int base) {
+    int q = -1;
+    while (q + 1 < ncp && first[q + 1] <= (unsigned int)base) q++;
+    return q;
+}
+// The same as a count: with first[] replaced by its running maximum (what k_knn_scan stores), the entries at or before the
+// chunk are a prefix of the row, and its length is cp_in_force + 1 -- for ANY first[], non-decreasing or not.
+GD_RC_FN unsigned int running_max(unsigned int run, unsigned int first) { return first > run ? first : run; }
+GD_RC_FN int cp_count(const unsigned int *first_max, int n, int base) {
+    int c = 0;
+    for (int q = 0; q < n; q++) c += first_max[q] <= (unsigned int)base ? 1 : 0;
+    return c;
+}
+GD_RC_FN int chunk_base_of_block(int b, int blk) { return (b * blk) & ~(CHUNK - 1); }
+
+// (c) the block test.  `reach` is block_reach(thr of the checkpoint in force for the block), `rad` the host's inflated radius.
+GD_RC_FN float block_reach(float thr) { return sqrtf(thr) * 1.00001f; }
+GD_RC_FN bool block_survives(int b, int blk, int K, float cx, float cy, float rad, float ex, float ey, float reach) {
+    const float dx = cx - ex, dy = cy - ey, rr = reach + rad;
+    return b * blk < K || !(dx * dx + dy * dy > rr * rr * 1.00001f);  // a block with a road below K always survives
+}
+
+}  // namespace rank_cand
+}  // namespace gd
