@@ -95,6 +95,17 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
+// inclusive running maximum over the 64 lanes of non-negative values (the same steps; a lane without a source takes 0)
+__device__ __forceinline__ int wave_incl_max_nonneg(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+
 // Wave-wide max / min / sum on the same DPP steps (lane 63 of the inclusive scan, broadcast): a `__shfl_xor` butterfly is six
 // dependent LDS-crossbar round trips, this is six vector instructions and a readlane.  Lanes without a source keep their own
 // value, which is neutral for max and min.
@@ -112,6 +123,9 @@ __device__ __forceinline__ int wave_max(int v) {
 __device__ __forceinline__ float wave_max_nonneg(float f) { return __int_as_float(wave_max(__float_as_int(f))); }
 __device__ __forceinline__ float wave_min_nonneg(float f) { return __int_as_float(~wave_max(~__float_as_int(f))); }
 __device__ __forceinline__ int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_incl_scan(v), 63); }
+// the active lanes for which `p` holds.  (__ballot goes through a compare of the predicate as an integer with 0, which costs a
+// select and a compare per call where the predicate is a lane mask already)
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 // set bits of a ballot below this lane's own (v_mbcnt_lo / v_mbcnt_hi)
 __device__ __forceinline__ int bits_below_lane(unsigned long long b) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)b, 0u));
@@ -423,6 +437,10 @@ constexpr int LSTN4 = (LSTN + 3) & ~3;
 static_assert(LSTN4 <= 1024 && NCP < 64 && rank_cand::CHUNK % GD_LIN_BLK == 0 && 64 % GD_LIN_BLK == 0, "block and count share 16 bits; a block inside one chunk; whole blocks per pass");
 constexpr size_t CAND_TABLES = LSTN4 * sizeof(unsigned short) + (NCP + 1) * sizeof(float);
 static_assert(CAND_TABLES <= sizeof(RankLds<CAP>::cnt2) && CAND_TABLES <= sizeof(RankLds<CAP_LONG>::cnt2), "the tables fit the idle counters of both instantiations");
+// the cull's table of checkpoints per 32-road chunk (rank_cand.hpp cp_table): entries per lane in the largest world; the scatter's
+// targets (u32) and the table itself (count, reach) side by side in the candidate keys' buffer
+constexpr int CP_EPL = ((GD_MAX_ROAD_ENTITIES + rank_cand::CHUNK - 1) / rank_cand::CHUNK + 63) / 64;
+static_assert(64 * CP_EPL * (sizeof(unsigned int) + sizeof(uint2)) <= sizeof(float) * CAP, "the chunk table fits the candidate keys of both instantiations");
 
 // What the ranking of one agent reads from global memory before it can start, fetched while the previous agent of the
 // wave is being ranked (the fetches are a chain of dependent loads, several microseconds end to end).
@@ -502,10 +520,11 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     const float ex = unif(in.ex), ey = unif(in.ey), iw = unif(in.iw), iz = unif(in.iz);
     // ---- CULL (rank_cand.hpp): lane l takes block b0 + l of the world's road blocks (GD_LIN_BLK consecutive roads inside a
     // circle, engine.hpp road_blk) and drops it if no road of it can be a candidate under the checkpoint in force for it; the
-    // survivors are listed in ascending order, one ballot per 64 blocks = 1024 roads.  Lane q holds checkpoint q of the row
-    // (first roads non-decreasing: k_knn_scan stores the running maximum), so the checkpoints at or before a block's chunk are
-    // a prefix of the row: those at or before the batch's first chunk are counted by one ballot, and only the few that start
-    // inside the batch are compared lane by lane. ----
+    // survivors are listed in ascending order, one ballot per 64 blocks = 1024 roads.  The checkpoint in force comes from a
+    // table built once per agent (rank_cand.hpp cp_table): lane q holds checkpoint q of the row and leaves q + 1 in the entry
+    // of the first chunk it is in force for, a running maximum over the chunks (each lane on consecutive entries, a DPP
+    // max-scan across the lanes) carries it on, and every chunk gets (checkpoints at or before it, the reach of the last of
+    // them).  The table lives in the candidate buffer, which nothing else uses until the scan stores its first candidate. ----
     unsigned short *const lst = reinterpret_cast<unsigned short *>(L.cnt2);
     float *const tthr = reinterpret_cast<float *>(L.cnt2) + LSTN4 / 2;  // threshold by checkpoints at or before: 0 = unbounded
     const unsigned int cfirst = in.cfirst;
@@ -513,84 +532,167 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     if (lane == 63) tthr[0] = __builtin_inff();
     const float creach = rank_cand::block_reach(in.cthr);  // (lanes from NCP on: +inf, which is also what "no checkpoint" reads)
     const int nblk = (R + GD_LIN_BLK - 1) / GD_LIN_BLK;
+    const int nch = rank_cand::chunks_of(R), epl = (nch + 63) >> 6;  // entries per lane: wave-uniform, at most CP_EPL
+    unsigned int *const tmax = reinterpret_cast<unsigned int *>(L.c.ckey);  // [64 * CP_EPL] the scatter's targets
+    uint2 *const tcp = reinterpret_cast<uint2 *>(L.c.ckey + 64 * CP_EPL);   // [64 * CP_EPL] per chunk: (count, reach)
+#pragma unroll
+    for (int u = 0; u < CP_EPL; u++)
+        if (u < epl) tmax[u * 64 + lane] = 0u;
+    wave_sync();
+    if (lane < NCP && rank_cand::cp_table_takes(cfirst, nch)) atomicMax(&tmax[rank_cand::cp_table_chunk(cfirst)], rank_cand::cp_table_entry(lane));
+    wave_sync();
+    {
+        int own[CP_EPL], run = 0;
+#pragma unroll
+        for (int u = 0; u < CP_EPL; u++) own[u] = u < epl ? (int)tmax[lane * epl + u] : 0;
+#pragma unroll
+        for (int u = 0; u < CP_EPL; u++) { run = max(run, own[u]); own[u] = run; }
+        // the largest entry of the lanes below this one: the inclusive scan, taken from the lane before
+        const int before = __builtin_amdgcn_ds_bpermute(((lane - 1) & 63) << 2, wave_incl_max_nonneg(run));
+#pragma unroll
+        for (int u = 0; u < CP_EPL; u++)
+            if (u < epl) {
+                const int cnt = lane ? max(own[u], before) : own[u];
+                // the reach of checkpoint cnt - 1; none: lane 63's, +inf
+                const int reach = __builtin_amdgcn_ds_bpermute(((cnt - 1) & 63) << 2, __float_as_int(creach));
+                tcp[lane * epl + u] = make_uint2((unsigned int)cnt, (unsigned int)reach);
+            }
+    }
+    wave_sync();
     const float4 *blk = d.road_blk + uni(in.b0);
     int nsv = 0;
     constexpr int CU = 4;  // batches of 64 blocks requested together
 #pragma clang loop unroll(disable)
     for (int b0 = 0; b0 < nblk; b0 += 64 * CU) {
         float4 c[CU];
+        uint2 cp[CU];
 #pragma unroll
-        for (int u = 0; u < CU; u++) c[u] = blk[(unsigned int)min(b0 + u * 64 + lane, nblk - 1)];
+        for (int u = 0; u < CU; u++) {
+            const int bc = min(b0 + u * 64 + lane, nblk - 1);
+            c[u] = blk[(unsigned int)bc];
+            cp[u] = tcp[rank_cand::chunk_base_of_block(bc, GD_LIN_BLK) / rank_cand::CHUNK];
+        }
+        // (all requested here, together: left alone the compiler sinks a batch's load into the per-lane branch it makes of the test)
+        static_assert(CU == 4, "operand list");
+        asm volatile("" : "+v"(c[0].x), "+v"(c[0].y), "+v"(c[0].z), "+v"(c[1].x), "+v"(c[1].y), "+v"(c[1].z), "+v"(c[2].x), "+v"(c[2].y), "+v"(c[2].z),
+                     "+v"(c[3].x), "+v"(c[3].y), "+v"(c[3].z));
 #pragma unroll
         for (int u = 0; u < CU; u++) {
             const int bb = b0 + u * 64;
             if (bb < nblk) {  // wave-uniform
                 const int b = bb + lane;
-                const unsigned int base = (unsigned int)rank_cand::chunk_base_of_block(b, GD_LIN_BLK);
-                const unsigned int base_lo = (unsigned int)rank_cand::chunk_base_of_block(bb, GD_LIN_BLK);
-                const unsigned int base_hi = (unsigned int)rank_cand::chunk_base_of_block(min(bb + 63, nblk - 1), GD_LIN_BLK);
-                const int nlo = __popcll(__ballot(cfirst <= base_lo)), nhi = __popcll(__ballot(cfirst <= base_hi));
-                int cnt = nlo;
-                for (int q = nlo; q < nhi; q++) cnt += (unsigned int)__builtin_amdgcn_readlane((int)cfirst, q) <= base ? 1 : 0;
-                // the reach of checkpoint cnt - 1; none: lane 63's, +inf
-                const float reach = __int_as_float(__builtin_amdgcn_ds_bpermute(((cnt - 1) & 63) << 2, __float_as_int(creach)));
-                const bool sv = b < nblk && rank_cand::block_survives(b, GD_LIN_BLK, K, c[u].x, c[u].y, c[u].z, ex, ey, reach);
-                const unsigned long long m = __ballot(sv);
-                if (sv) lst[audited(d, nsv + bits_below_lane(m), LSTN4)] = (unsigned short)(b | cnt << 10);
-                nsv += __popcll(m);
+                const bool sv = b < nblk && rank_cand::block_survives(b, GD_LIN_BLK, K, c[u].x, c[u].y, c[u].z, ex, ey, __uint_as_float(cp[u].y));
+                const unsigned long long m = wave_ballot(sv);
+                const int upto = nsv + __popcll(m);
+                // (bounds audit, wave-uniform: the list holds a block of the largest world each, so this never happens)
+                if (upto <= LSTN4) {
+                    if (sv) lst[nsv + bits_below_lane(m)] = (unsigned short)((unsigned int)b | cp[u].x << 10);
+                    nsv = upto;
+                } else if (lane == 0) {
+                    atomicAdd(&d.rk_hist[GD_RANK_AUDIT], 1);
+                }
             }
         }
     }
     wave_sync();
     // ---- SCAN of the surviving blocks, four per pass (a quarter of the wave each), in index order: the per-road test
     // (rank_cand.hpp: k_knn_scan's former expression, bit for bit), the exact key (gd_math.hpp ego_dist2: the reference's
-    // arithmetic), one ballot per pass; (road, key) go to LDS at the candidate's position.  PB passes are requested together,
-    // the next PB before these are keyed.  Roads 0..K-1 are candidates regardless and their blocks always survive, so the
-    // first K positions are their indices.  Writes stop at the buffer's end, the count goes on. ----
+    // arithmetic), one ballot per pass; (road, key) go to LDS at the candidate's position.  Roads 0..K-1 are candidates
+    // regardless and their blocks always survive, so the first K positions are their indices.  Writes stop at the buffer's
+    // end, the count goes on.
+    // A pass of the main loop holds only the per-road work.  Every pass but the last has four listed blocks, none of them the
+    // world's last (the list ascends), so every road of theirs exists and nothing is clamped per lane; the loop takes four such
+    // passes per trip, straight-line, while the buffer has room for all their roads (one wave-uniform test per trip), with the
+    // list entries read a stage ahead of the thresholds and roads they select (stages of PB passes: entries, then threshold +
+    // road, then test + key).  What is left -- up to four passes with the last one, partial or with the world's partial last
+    // block; all the rest of an agent whose candidates may overflow the buffer -- goes through a guarded copy. ----
     int nin = 0;
     {
-        // (PB passes requested together, twice that in flight.  Measured at 1024 x 64, one run of 150 steps each, k_knn_rank with
-        // PB = 2: 420 us, 4: 422, 8: 431 -- the scan does not wait for its own loads)
+        // (PB passes requested together.  Measured at 1024 x 64, one run of 150 steps each, k_knn_rank with PB = 2: 420 us,
+        // 4: 422, 8: 431 -- the scan does not wait for its own loads)
         constexpr int BPP = 64 / GD_LIN_BLK, PB = 2;  // blocks per pass
-        const int np = (nsv + BPP - 1) / BPP;
+        const int np = (nsv + BPP - 1) / BPP, nfast = np - 1;  // passes; of them with four listed blocks that are not the world's last
         const int sub = lane / GD_LIN_BLK, o = lane % GD_LIN_BLK;
         const float2 *rxy = d.road_xy + r0;
-        struct Batch { int r[PB]; float thr[PB]; float2 xy[PB]; };
-        auto issue = [&](Batch &bt, int p0) {
-#pragma unroll
-            for (int u = 0; u < PB; u++) {
-                const int e = (p0 + u) * BPP + sub;
-                const unsigned int ent = lst[min(e, LSTN4 - 1)];
-                const bool on = e < nsv;
-                const int r = on ? (int)(ent & 1023u) * GD_LIN_BLK + o : R;
-                bt.r[u] = r;
-                bt.thr[u] = tthr[on ? min((int)(ent >> 10), NCP) : 0];
-                bt.xy[u] = rxy[(unsigned int)min(r, R - 1)];
+        auto store = [&](bool cand, int r, float key, unsigned long long m, bool guard) {
+            const int pos = nin + bits_below_lane(m);
+            if (cand && (!guard || pos < CAP_T)) {
+                L.c.cidx[pos] = (unsigned short)r;
+                L.c.ckey[pos] = key;
             }
+            nin += __popcll(m);
         };
-        auto take = [&](const Batch &bt) {
+        int p = 0;
+        if (nfast >= 2 * PB) {
+            // (the list is read as words of two entries and a lane takes its half with a bit-field extract: a 16-bit value carried
+            // round the loop made the compiler shift it with SDWA forms, whose shift counts it kept in two vector registers from
+            // the kernel's first instruction to its last -- five more spilled registers in the ranking behind this)
+            const unsigned int *lsub = reinterpret_cast<const unsigned int *>(L.cnt2) + sub / 2;
+            const unsigned int sh = (unsigned int)(sub & 1) * 16u;
+            const unsigned int o8 = (unsigned int)o * (unsigned int)sizeof(float2);
+            static_assert(BPP == 4, "two words per pass");
+            struct Ents { unsigned int e[PB]; };
+            struct Batch { unsigned int off[PB]; float thr[PB]; float2 xy[PB]; };
+            auto entries = [&](Ents &en, int p0) {  // (a stage beyond the last full pass reads that pass again and is never taken)
 #pragma unroll
-            for (int u = 0; u < PB; u++) {
-                const bool cand = rank_cand::is_candidate(bt.r[u], K, R, bt.xy[u].x, bt.xy[u].y, ex, ey, bt.thr[u]);
-                const float key = ego_dist2(ex, ey, iw, iz, bt.xy[u].x, bt.xy[u].y);
-                const unsigned long long m = __ballot(cand);
-                const int pos = nin + bits_below_lane(m);
-                if (cand && pos < CAP_T) {
-                    L.c.cidx[pos] = (unsigned short)bt.r[u];
-                    L.c.ckey[pos] = key;
+                for (int u = 0; u < PB; u++) en.e[u] = lsub[min(p0 + u, nfast - 1) * (BPP / 2)];
+            };
+            auto issue = [&](Batch &bt, const Ents &en) {
+#pragma unroll
+                for (int u = 0; u < PB; u++) {  // the road's byte offset in the world's points: below 2^20, a scalar base + 32 bits
+                    bt.off[u] = __builtin_amdgcn_ubfe(en.e[u], sh, 10u) * (unsigned int)(GD_LIN_BLK * sizeof(float2)) + o8;
+                    bt.thr[u] = tthr[__builtin_amdgcn_ubfe(en.e[u], sh + 10u, 6u)];
+                    bt.xy[u] = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(rxy) + bt.off[u]);
                 }
-                nin += __popcll(m);
-            }
-        };
-        Batch ba, bb;
-        issue(ba, 0);
+            };
+            auto take = [&](const Batch &bt) {
+#pragma unroll
+                for (int u = 0; u < PB; u++) {
+                    const int r = (int)(bt.off[u] / (unsigned int)sizeof(float2));
+                    __builtin_assume(r >= 0 && r < R);
+                    const bool cand = rank_cand::is_candidate(r, K, R, bt.xy[u].x, bt.xy[u].y, ex, ey, bt.thr[u]);
+                    store(cand, r, ego_dist2(ex, ey, iw, iz, bt.xy[u].x, bt.xy[u].y), wave_ballot(cand), false);
+                }
+            };
+            Ents ea, eb;
+            Batch ba, bb;
+            entries(ea, 0);
+            entries(eb, PB);
+            issue(ba, ea);
 #pragma clang loop unroll(disable)
-        for (int p0 = 0; p0 < np; p0 += 2 * PB) {
-            issue(bb, p0 + PB);
-            take(ba);
-            if (p0 + PB >= np) break;
-            issue(ba, p0 + 2 * PB);
-            take(bb);
+            for (; p + 2 * PB <= nfast && nin + 2 * PB * 64 <= CAP_T; p += 2 * PB) {
+                issue(bb, eb);
+                entries(ea, p + 2 * PB);
+                take(ba);
+                issue(ba, ea);
+                entries(eb, p + 3 * PB);
+                take(bb);
+            }
+        }
+#pragma clang loop unroll(disable)
+        for (; p < np; p += 2 * PB) {  // the guarded copy: every index clamped, the writes stop at the buffer's end
+            int r[2 * PB];
+            float thr[2 * PB];
+            float2 xy[2 * PB];
+#pragma unroll
+            for (int u = 0; u < 2 * PB; u++) {
+                r[u] = R; thr[u] = 0.f; xy[u] = make_float2(0.f, 0.f);
+                if (p + u < np) {  // wave-uniform: a trip of this loop is mostly the one last pass
+                    const int e = (p + u) * BPP + sub;
+                    const unsigned int ent = lst[min(e, LSTN4 - 1)];
+                    const bool on = e < nsv;
+                    r[u] = on ? (int)(ent & 1023u) * GD_LIN_BLK + o : R;
+                    thr[u] = tthr[on ? min((int)(ent >> 10), NCP) : 0];
+                    xy[u] = rxy[(unsigned int)min(r[u], R - 1)];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 2 * PB; u++) {
+                if (p + u < np) {
+                    const bool cand = rank_cand::is_candidate(r[u], K, R, xy[u].x, xy[u].y, ex, ey, thr[u]);
+                    store(cand, r[u], ego_dist2(ex, ey, iw, iz, xy[u].x, xy[u].y), wave_ballot(cand), true);
+                }
+            }
         }
     }
     wave_sync();

@@ -1,5 +1,6 @@
 // The rank path's candidate set (map_obs_rank.hip k_knn_scan -> k_knn_rank) as plain C++: the decisions that the kernel and
-// a host program share (tests/rank_cand_model.cpp runs the cull + in-order scan below against a plain loop over every road).
+// a host program share (tests/rank_cand_model.cpp runs the cull + in-order scan below against a plain loop over every road;
+// tests/rank_cp_table_model.cpp the cull's table of checkpoints per chunk, (b') below, against the counts of (b)).
 //
 // An agent's candidates are roads 0..K-1 plus every later road r < R whose cheap squared distance is below the threshold of
 // the CHECKPOINT in force for r.  k_knn_scan leaves a row of checkpoints per agent: first[q] (a multiple of 32) and thr[q];
@@ -64,6 +65,29 @@ GD_RC_FN int cp_count(const unsigned int *first_max, int n, int base) {
     return c;
 }
 GD_RC_FN int chunk_base_of_block(int b, int blk) { return (b * blk) & ~(CHUNK - 1); }
+
+// (b') the same count for every chunk of a world at once, as a table that k_knn_rank builds once per agent: entry c is
+// cp_count(first_max, n, c * CHUNK).  The row is non-decreasing, so the entries at or before a chunk are a prefix of it and their
+// number is the largest q + 1 among them: checkpoint q leaves q + 1 in the entry of the first chunk it is in force for (SCATTER,
+// a max where several checkpoints start in one chunk), and a running maximum over the chunks carries it to every later chunk
+// (SCAN).  NO_CP and a first road behind the base of the world's last chunk are in force for no chunk of the world and leave
+// nothing.  first[] are multiples of CHUNK in the engine; rounding up keeps the rule equal to cp_count for any value.
+GD_RC_FN int chunks_of(int R) { return (R + CHUNK - 1) / CHUNK; }
+GD_RC_FN unsigned int cp_table_chunk(unsigned int first_max) { return first_max / CHUNK + (first_max % CHUNK ? 1u : 0u); }
+GD_RC_FN bool cp_table_takes(unsigned int first_max, int nchunks) {
+    return first_max != NO_CP && cp_table_chunk(first_max) < (unsigned int)nchunks;
+}
+GD_RC_FN unsigned int cp_table_entry(int q) { return (unsigned int)q + 1u; }
+// `tab`: nchunks entries.  (The kernel zeroes, scatters with an LDS max from lane q, and scans with each lane on consecutive entries.)
+GD_RC_FN void cp_table(unsigned int *tab, int nchunks, const unsigned int *first_max, int n) {
+    for (int c = 0; c < nchunks; c++) tab[c] = 0u;
+    for (int q = 0; q < n; q++)
+        if (cp_table_takes(first_max[q], nchunks)) {
+            unsigned int &e = tab[cp_table_chunk(first_max[q])];
+            e = cp_table_entry(q) > e ? cp_table_entry(q) : e;
+        }
+    for (int c = 1; c < nchunks; c++) tab[c] = tab[c - 1] > tab[c] ? tab[c - 1] : tab[c];
+}
 
 // (c) the block test.  `reach` is block_reach(thr of the checkpoint in force for the block), `rad` the host's inflated radius.
 GD_RC_FN float block_reach(float thr) { return sqrtf(thr) * 1.00001f; }
