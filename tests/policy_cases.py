@@ -19,6 +19,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROADS, ROAD_K, PARTNER_K = REF.ROADS, REF.ROAD_K, REF.PARTNER_K
 EMBEDDERS = ("ego_embed", "partner_embed", "road_map_embed")
 SHAPES = [(n, a, ew, na) for n in (1, 3, 70) for a in (64, 128) for ew in (6, 9) for na in (91, 7)]
+# The action counts at which the tiling of the heads changes -- (n_actions + 1 + 31) / 32 output tiles, the value being output
+# n_actions, and [Wa; Wc] walked eight rows at a time in the backward: 1 (a softmax of one number), 8 (the critic's row opens a
+# group of eight), 31 (the value is the last output of the one tile), 32 (the value sits alone in a second tile), 33, and 1024
+# (33 tiles, the largest count the API takes).  n = 33 is one full wave of k_policy_tail and a single row.  Not a matrix: one
+# list, with 1, 32 and 1024 at both n and (max_agents, ego_width) alternating.
+EDGE_SHAPES = [(3, 64, 6, 1), (33, 128, 9, 1), (3, 128, 9, 32), (33, 64, 6, 32), (3, 64, 6, 1024), (33, 128, 9, 1024),
+               (33, 64, 6, 8), (3, 128, 9, 33), (33, 64, 6, 31), (3, 128, 9, 31)]
+EDGE_ACTIONS = sorted({s[3] for s in EDGE_SHAPES})
 
 
 def obs_width(max_agents, ego_width):
@@ -160,22 +168,24 @@ def stand_in_forward(sd, obs, max_agents, ego_width, dtype):
     return logits.double().numpy(), value.double().numpy()[:, 0]
 
 
-_HOST = [None]
+_HOST = {}
 
 
-def rule_host():
-    """The host program of csrc/policy_rule.hpp, compiled once per session with g++ (no contraction)."""
-    if _HOST[0] is None:
-        out = os.path.join(tempfile.gettempdir(), "gd_policy_rule_host_%d" % os.getuid())
+def rule_host(sanitize=False):
+    """The host program of csrc/policy_rule.hpp, compiled once per session with g++ (no contraction).  sanitize: a second,
+    stand-alone executable with -fsanitize=address,undefined."""
+    if sanitize not in _HOST:
+        out = os.path.join(tempfile.gettempdir(), "gd_policy_rule_host%s_%d" % ("_san" if sanitize else "", os.getuid()))
         src = os.path.join(HERE, "policy_rule_host.cpp")
         hdr = os.path.join(HERE, "..", "gpudrive_lab_amd", "csrc", "policy_rule.hpp")
         if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", out, src])
-        _HOST[0] = out
-    return _HOST[0]
+            flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+            subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + ["-o", out, src])
+        _HOST[sanitize] = out
+    return _HOST[sanitize]
 
 
-def run_rule_host(logits, u, deterministic):
+def run_rule_host(logits, u, deterministic, sanitize=False):
     """(actions int64, logprob f32, entropy f32) of the host program on float32 logits [N, n] and uniforms [N]."""
     logits = np.ascontiguousarray(logits, dtype=np.float32)
     u = np.ascontiguousarray(u, dtype=np.float32)
@@ -184,7 +194,7 @@ def run_rule_host(logits, u, deterministic):
         fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
         with open(fin, "wb") as f:
             f.write(np.array([n, na, int(deterministic)], dtype=np.int32).tobytes() + logits.tobytes() + u.tobytes())
-        subprocess.check_call([rule_host(), fin, fout])
+        subprocess.check_call([rule_host(sanitize), fin, fout])
         raw = open(fout, "rb").read()
     assert len(raw) == 16 * n
     return (np.frombuffer(raw, np.int64, n), np.frombuffer(raw, np.float32, n, 8 * n), np.frombuffer(raw, np.float32, n, 12 * n))

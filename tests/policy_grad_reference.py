@@ -156,21 +156,23 @@ def first_identical_row(rows):
 
 # ---- the rule's host program
 
-_HOST = [None]
+_HOST = {}
 
 
-def rule_host():
-    if _HOST[0] is None:
-        out = os.path.join(tempfile.gettempdir(), "gd_policy_grad_rule_host_%d" % os.getuid())
+def rule_host(sanitize=False):
+    """The compiled host program; sanitize: a second, stand-alone executable with -fsanitize=address,undefined."""
+    if sanitize not in _HOST:
+        out = os.path.join(tempfile.gettempdir(), "gd_policy_grad_rule_host%s_%d" % ("_san" if sanitize else "", os.getuid()))
         src = os.path.join(HERE, "policy_grad_rule_host.cpp")
         hdrs = [os.path.join(HERE, "..", "gpudrive_lab_amd", "csrc", h) for h in ("policy_grad_rule.hpp", "policy_rule.hpp")]
         if not os.path.exists(out) or os.path.getmtime(out) < max(map(os.path.getmtime, [src] + hdrs)):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", out, src])
-        _HOST[0] = out
-    return _HOST[0]
+            flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
+            subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + ["-o", out, src])
+        _HOST[sanitize] = out
+    return _HOST[sanitize]
 
 
-def run_rule_host(logits, actions, d_logprob, d_entropy):
+def run_rule_host(logits, actions, d_logprob, d_entropy, sanitize=False):
     """dlogits [N, n] float32 of the host program."""
     logits = np.ascontiguousarray(logits, dtype=np.float32)
     n, na = logits.shape
@@ -181,7 +183,7 @@ def run_rule_host(logits, actions, d_logprob, d_entropy):
                     np.ascontiguousarray(actions, dtype=np.int32).tobytes() +
                     np.ascontiguousarray(d_logprob, dtype=np.float32).tobytes() +
                     np.ascontiguousarray(d_entropy, dtype=np.float32).tobytes())
-        subprocess.check_call([rule_host(), fin, fout])
+        subprocess.check_call([rule_host(sanitize), fin, fout])
         raw = open(fout, "rb").read()
     assert len(raw) == 4 * n * na
     return np.frombuffer(raw, np.float32).reshape(n, na)

@@ -379,3 +379,67 @@ def test_refused_while_only_the_packed_buffer_is_written():
         assert int(loop.run(n_steps=3).steps) == 3
     finally:
         sim.close()
+
+
+# ---- past one row per lane of the summary
+
+BIG_W = 258  # 258 worlds x 64 slots: more than 256 learner rows, and k_learner_rows scans 16,512 slots, 17 to a lane
+
+
+@pytest.fixture(scope="module")
+def big_twins():
+    """Twin simulators of 258 worlds x 64 slots (the three small scenes, 86 times), built once for this module."""
+    scenes = [TEST_JSON, SCENE_407, SCENE_4] * (BIG_W // 3)
+    assert len(scenes) == BIG_W
+    rsim, tsim = (_sim(64, "classic", REMOVED, "linear", scenes=scenes) for _ in range(2))
+    yield rsim, tsim
+    rsim.close()
+    tsim.close()
+
+
+def test_run_equals_the_reference_loop_on_258_worlds(big_twins):
+    """More than 256 rows, and no multiple of 256: lane l of k_bc_summary's 256 adds rows l, l + 256, ..., several terms to a
+    lane and one term more in the first lanes than in the last.  Every row draws its own u and z, so the replicas of a scene
+    end differently.  The progress sum is a float32 sum of values that are not exactly representable, and it DIFFERS from the
+    same sum taken in other orders (asserted below on the reference loop's outputs): the order of bc_rollout_rule.hpp is what
+    the summary is held to here."""
+    from gpudrive_lab_amd import ClosedLoopBC
+    rsim, tsim = big_twins
+    A, R, model = 64, 1, "classic"
+    pol = _policy(A, R)
+    loop = ClosedLoopBC(rsim, pol)
+    N = loop.num_agents
+    assert N > 256 and N % 256 != 0, N
+    g = torch.Generator(device="cuda").manual_seed(5)
+    ep = loop.run(deterministic=False, generator=g, record=True)
+    r = _loop(tsim, pol, model, R, deterministic=False, u=ep.u, z=ep.z)
+    _compare(ep, r, "258 worlds")
+    host = lambda k: r[k].cpu().numpy()  # noqa: E731
+    # the rows of a world, and what became of them: replicas of one scene must not all end alike
+    ctrl = loop.mask.cpu().numpy()
+    world_of_row = np.nonzero(ctrl)[0]
+    per_world = np.stack([np.bincount(world_of_row, weights=host(k), minlength=BIG_W)
+                          for k in ("goal_achieved", "off_road", "veh_collision")], 1)
+    differ = [len({tuple(row) for row in per_world[s::3].tolist()}) for s in range(3)]
+    assert max(differ) > 1, "the replicas of every scene end alike"
+    # the progress sum, as summary() takes it, in the rule's order and in three others
+    f32 = np.float32
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = (host("goal_dist") / host("init_goal_dist")).astype(f32)
+    ratio[host("goal_achieved").astype(bool)] = 0
+    progress = (f32(1) - ratio).astype(f32)
+    assert np.isfinite(progress).all()
+    ordered = REF.ordered_sum(progress)
+
+    def serial(v):
+        s = f32(0)
+        for x in v:
+            s = f32(s + x)
+        return s
+
+    others = [serial(progress), serial(progress[::-1]), f32(progress.sum(dtype=np.float64))]
+    print("BC ROLLOUT 258 worlds: rows %d (%d to a lane, %d lanes one more) iterations %d, distinct outcomes among the replicas %s, "
+          "progress sum %r in the rule's order, %s in others" % (N, N // 256, N % 256, r["iterations"], differ, float(ordered),
+                                                                  [float(x) for x in others]))
+    assert f32(ordered / f32(N)) == r["summary"][4]
+    assert any(x != ordered for x in others), "the progress sum is the same in every order: the order would not show"

@@ -96,17 +96,21 @@ def _variants(sd, obs, a, ew):
     yield "seeded", sd, obs
     yield "negative_pool", PC.negative_pool_state(sd), obs              # (i)
     yield "last_entity_wins", sd, PC.last_entity_wins(sd, obs, a, ew)   # (ii)
-    yield "tied_actor", PC.tied_actor_state(sd), obs                    # (iii)
+    if sd["actor.bias"].shape[0] > 5:  # (iii) ties actions 3 and 5
+        yield "tied_actor", PC.tied_actor_state(sd), obs
 
 
-@pytest.mark.parametrize("n,a,ew,na", PC.SHAPES, ids=lambda v: str(v))
-def test_forward_against_the_float64_reference(n, a, ew, na):
+def _forward_case(n, a, ew, na, edge=False):
+    """edge: a shape of PC.EDGE_SHAPES -- the value and the logits of the last tile are also judged on their own (same
+    reference, same 8 E), so that a swapped or dropped last tile is named; with one action there is no second action to
+    tie, and logprob and entropy are the host program's bits."""
     from gpudrive_lab_amd.policy import DevicePolicy
     sd0 = PC.state_dict(10 + na + ew, ew, na)
     obs0 = PC.observations(20 + n + a, n, a, ew)
     carver = Carver()
     out, logits_out = _outputs(carver, n, na)
     pol = None
+    worst = 0.0
     for vi, (name, sd, obs) in enumerate(_variants(sd0, obs0, a, ew)):
         what = "%s n=%d A=%d ego=%d actions=%d" % (name, n, a, ew, na)
         want_l, want_v, _ = REF.forward(sd, obs, a, ew)
@@ -132,6 +136,11 @@ def test_forward_against_the_float64_reference(n, a, ew, na):
             if ui == 0:
                 print("policy forward %s: E %.3g, kernel error %.3g, ratio %.2f" % (what, E, err, err / E))
             assert err <= 8 * E, (what, "error %.3g above 8 E = %.3g" % (err, 8 * E))
+            worst = max(worst, err / E)
+            if edge:
+                _check_last_tile(what, na, logits, value, want_l, want_v, E)
+                if na == 1:
+                    _check_one_action(what, logits, u, det, actions, logprob, entropy)
             _check_rule(what + (" det" if det else " u%d" % ui), na, logits, u, det, actions, logprob, entropy)
             if name == "tied_actor" and det:
                 assert (logits[:, 3] == logits[:, 5]).all() and (actions == 3).all(), what
@@ -141,6 +150,39 @@ def test_forward_against_the_float64_reference(n, a, ew, na):
     fresh = pol(d_obs, deterministic=True)
     for g, w in zip(_host(fresh), _host(out)):
         assert np.array_equal(g, w)
+    return worst
+
+
+def _check_last_tile(what, na, logits, value, want_l, want_v, E):
+    """The value (output n_actions: alone in a tile of its own when n_actions is a multiple of 32) and the last 32-wide tile
+    that holds logits, each against the float64 reference by the case's own yardstick."""
+    assert E > 0, (what, "the float32 yardstick is degenerate")
+    err_v = np.abs(value - want_v).max()
+    assert err_v <= 8 * E, (what, "the value (output %d, tile %d): error %.3g above 8 E = %.3g" % (na, na // 32, err_v, 8 * E))
+    lo = 32 * ((na - 1) // 32)
+    err_l = np.abs(logits[:, lo:] - want_l[:, lo:]).max()
+    assert err_l <= 8 * E, (what, "logits %d..%d (tile %d): error %.3g above 8 E = %.3g" % (lo, na - 1, lo // 32, err_l, 8 * E))
+
+
+def _check_one_action(what, logits, u, det, actions, logprob, entropy):
+    """A softmax of one number: expf(0) and logf(1) are exact on the device and on the host, so logprob and entropy are the
+    host program's bits (a zero and a negative zero)."""
+    n = len(logits)
+    a, lp, ent = PC.run_rule_host(logits, np.zeros(n, np.float32) if det else u, det)
+    assert np.array_equal(actions, a) and (actions == 0).all(), what
+    assert np.array_equal(logprob.view(np.int32), lp.view(np.int32)), (what, "logprob is not the host program's bits", logprob)
+    assert np.array_equal(entropy.view(np.int32), ent.view(np.int32)), (what, "entropy is not the host program's bits", entropy)
+
+
+@pytest.mark.parametrize("n,a,ew,na", PC.SHAPES, ids=lambda v: str(v))
+def test_forward_against_the_float64_reference(n, a, ew, na):
+    _forward_case(n, a, ew, na)
+
+
+@pytest.mark.parametrize("n,a,ew,na", PC.EDGE_SHAPES, ids=lambda v: str(v))
+def test_forward_at_the_action_counts_where_the_tiling_changes(n, a, ew, na):
+    worst = _forward_case(n, a, ew, na, edge=True)
+    print("POLICY_EDGE forward n=%d A=%d ego=%d actions=%d: largest error / E %.2f (bound 8)" % (n, a, ew, na, worst))
 
 
 def test_inputs_are_checked():

@@ -141,6 +141,10 @@ def test_the_ego_and_set_masks_are_the_host_programs(ew):
 @pytest.mark.parametrize("p", [0.01, 0.5])
 @pytest.mark.parametrize("n,ew,na", SHAPES, ids=lambda v: str(v))
 def test_forward_and_evaluate_against_the_masked_float64_stand_in(n, ew, na, p):
+    _forward_case(n, ew, na, p)
+
+
+def _forward_case(n, ew, na, p):
     from gpudrive_lab_amd.policy import DevicePolicy
     sd = PC.state_dict(10 + na + ew, ew, na)
     obs_h = PC.observations(20 + n + A, n, A, ew)
@@ -306,6 +310,22 @@ def _compare(what, sd, obs, ew, actions, ups, winners, got, keep, scale):
 @pytest.mark.parametrize("p", [0.01, 0.5])
 @pytest.mark.parametrize("n,ew,na", SHAPES, ids=lambda v: str(v))
 def test_backward_against_float64_autograd_of_the_masked_stand_in(n, ew, na, p):
+    _backward_case(n, ew, na, p)
+
+
+# the action counts where the tiling of the heads changes (tests/policy_cases.py EDGE_SHAPES): the value alone in a second tile,
+# 33 tiles, and a softmax of one number (its actor gradients are exactly zero in float64, E_p is zero and so is the bound)
+EDGE = [(33, 9, 32), (3, 6, 1024), (33, 6, 1)]
+
+
+@pytest.mark.parametrize("n,ew,na", EDGE, ids=lambda v: str(v))
+def test_forward_evaluate_and_backward_at_the_action_counts_where_the_tiling_changes(n, ew, na):
+    assert na in PC.EDGE_ACTIONS
+    _forward_case(n, ew, na, 0.5)
+    _backward_case(n, ew, na, 0.5)
+
+
+def _backward_case(n, ew, na, p):
     sd = PC.state_dict(10 + na + ew, ew, na)
     obs0 = PC.observations(20 + n + A, n, A, ew)
     rule = _rule(p, seed=99)

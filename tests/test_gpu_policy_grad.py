@@ -136,15 +136,16 @@ def _cases(sd, obs, a, ew):
     yield "last_entity_wins", sd, PC.last_entity_wins(sd, obs, a, ew)    # (ii)
     yield "all_padding_partners", sd, GR.all_padding_partners(obs, a, ew)  # (iii)
     yield "copied_winner", sd, GR.copied_winner(sd, obs, a, ew)          # (iv)
-    yield "lifted_actor_bias", GR.lifted_actor_bias(sd), obs             # (v)
+    if sd["actor.bias"].shape[0] > 3:  # (v) lifts action 3
+        yield "lifted_actor_bias", GR.lifted_actor_bias(sd), obs
 
 
-@pytest.mark.parametrize("n,a,ew,na", PC.SHAPES, ids=lambda v: str(v))
-def test_evaluate_and_backward_against_the_float64_reference(n, a, ew, na):
+def _backward_case(n, a, ew, na, P=7):
+    """Returns the largest error / E_p over the case's comparisons."""
     from gpudrive_lab_amd.policy import DevicePolicy
     sd0 = PC.state_dict(10 + na + ew, ew, na)
     obs0 = PC.observations(20 + n + a, n, a, ew)
-    P = 7
+    ratios = []
     raw = Raw(n, a, ew, na, P)
     pol = DevicePolicy.from_state_dict(sd0, max_agents=a, ego_width=ew)
     logits_f = torch.empty((n, na), device="cuda")
@@ -186,14 +187,19 @@ def test_evaluate_and_backward_against_the_float64_reference(n, a, ew, na):
         if n > 3:
             assert (ups[0] == 0).any() and (ups[0] != 0).any(), (what, "some rows clip and some do not")
         got = raw.backward(ups, what)
-        _compare(what, sd, obs, a, ew, h_actions, ups, winners, got)
+        _compare(what, sd, obs, a, ew, h_actions, ups, winners, got, ratios)
+        if na == 1:
+            # a softmax of one number: logprob and entropy are constants, so the float64 reference's actor gradients are
+            # exactly zero, the yardstick E_p is zero there, and the kernel's must be zero as values
+            assert (got["actor.weight"] == 0.0).all() and (got["actor.bias"] == 0.0).all(), (what, "one action")
+            assert np.abs(got["critic.weight"]).max() > 0 and np.abs(got["shared_embed.0.weight"]).max() > 0, what
         if name != "seeded":
             continue
         # (vi) no gradient into logprob and entropy: the actor's gradients are exactly zero, the rest within the bound
         zero = np.zeros(n, dtype=np.float32)
         got6 = raw.backward([zero, zero, ups[2]], what + " (vi)")
         assert (got6["actor.weight"] == 0.0).all() and (got6["actor.bias"] == 0.0).all(), what + " (vi)"
-        _compare(what + " (vi)", sd, obs, a, ew, h_actions, [zero, zero, ups[2]], winners, got6)
+        _compare(what + " (vi)", sd, obs, a, ew, h_actions, [zero, zero, ups[2]], winners, got6, ratios)
         # (vii) rows whose three upstream gradients are zero change no bit: two such rows appended, the same partials (with
         # the rows p, p + P, .. summed in order, the appended rows come last in every workgroup and add zeros)
         more = Raw(n + 2, a, ew, na, P)
@@ -204,6 +210,22 @@ def test_evaluate_and_backward_against_the_float64_reference(n, a, ew, na):
         got7 = more.backward([np.concatenate([u, [0.0, 0.0]]) for u in ups], what + " (vii)")
         for k in got:
             assert np.array_equal(got7[k].view(np.int32), got[k].view(np.int32)), (what, k, "rows without gradient changed bits")
+    return max(ratios)
+
+
+@pytest.mark.parametrize("n,a,ew,na", PC.SHAPES, ids=lambda v: str(v))
+def test_evaluate_and_backward_against_the_float64_reference(n, a, ew, na):
+    _backward_case(n, a, ew, na)
+
+
+@pytest.mark.parametrize("P", [1, 7])
+@pytest.mark.parametrize("n,a,ew,na", PC.EDGE_SHAPES, ids=lambda v: str(v))
+def test_evaluate_and_backward_at_the_action_counts_where_the_tiling_changes(n, a, ew, na, P):
+    """[Wa; Wc] is walked eight rows at a time with no remainder loop: 8, 32 and 1024 put the critic's row first in a group,
+    31 last, 33 second, 1 second of the only group; 1024 uses s_dl to its last index."""
+    worst = _backward_case(n, a, ew, na, P)
+    print("POLICY_EDGE backward n=%d A=%d ego=%d actions=%d partials=%d: largest error / E_p %.2f (bound %d)"
+          % (n, a, ew, na, P, worst, BOUND), flush=True)
 
 
 @pytest.mark.parametrize("a,ew,na", [(64, 6, 91), (128, 9, 7)])

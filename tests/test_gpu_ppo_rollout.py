@@ -394,3 +394,53 @@ def test_refused_without_the_row_buffer():
             ev.run(n_steps=3, deterministic=True)
     finally:
         sim.close()
+
+
+# ---- past one world per lane of the summary
+
+BIG_W = 258  # > 256 and no multiple of it: lanes 0 and 1 of k_pr_summary add two worlds each, the other 254 lanes one
+
+
+@pytest.fixture(scope="module")
+def big_twins():
+    """Twin simulators of 258 worlds x 64 slots (the three small scenes, 86 times), built once for this module."""
+    scenes = [TEST_JSON, SCENE_407, SCENE_4] * (BIG_W // 3)
+    assert len(scenes) == BIG_W
+    rsim, tsim = _sim(64, REMOVED, scenes=scenes), _sim(64, REMOVED, scenes=scenes)
+    yield rsim, tsim
+    rsim.close()
+    tsim.close()
+
+
+def test_run_equals_the_restated_loop_on_258_worlds(big_twins):
+    """W = 258: lane l of the summary's 256 adds worlds l and l + 256, so two lanes add a second term, and k_learner_rows
+    scans 16,512 slots, 17 to a lane, with the last 52 lanes empty.  Every row draws its own u, so the replicas of a scene end
+    differently (asserted below on the restated loop's outputs).  Every summed field is a count or an episode length: integers
+    whose total stays far below 2^24, so the float32 sums are exact in ANY order (asserted) -- what this case holds the
+    summary to is that every world is added exactly once, not the order."""
+    from gpudrive_lab_amd import ClosedLoopPPO
+    rsim, tsim = big_twins
+    A, W = 64, BIG_W
+    chunk = -(-W * A // 1024)
+    assert W > 256 and W % 256 == 2 and chunk == 17 and 1024 - -(-W * A // chunk) == 52
+    pol = _policy(A)
+    ev = ClosedLoopPPO(rsim, pol)
+    N = ev.num_agents
+    g = torch.Generator(device="cuda").manual_seed(5)
+    ep = ev.run(generator=g, record=True)
+    r = _loop(tsim, pol, u=ep.u)
+    assert N == int(r["control_mask"].sum()) and N > 256 and tuple(ep.episode_lengths.shape) == (W,)
+    _compare(ep, r, "258 worlds")
+    world = {k: r[k].cpu().numpy() for k in WORLD}
+    names = ("episode_lengths", "goal_achieved_count", "collided_count", "off_road_count", "other_count")
+    outcome = np.stack([world[k] for k in names], 1)
+    differ = [len({tuple(row) for row in outcome[s::3].tolist()}) for s in range(3)]
+    print("PPO ROLLOUT 258 worlds: rows %d iterations %d, distinct outcomes among the 86 replicas of each scene %s, summary %s"
+          % (N, r["iterations"], differ, r["summary"].tolist()))
+    assert max(differ) > 1, "the replicas of every scene end alike: a wrong order of the worlds would not show"
+    assert len(set(world["episode_lengths"][0::3].tolist())) > 1 or len(set(world["episode_lengths"][2::3].tolist())) > 1
+    for k in ("goal_achieved_count", "collided_count", "off_road_count", "other_count", "controlled_per_scene", "episode_lengths"):
+        v = world[k].astype(np.float64)
+        assert (v == np.round(v)).all() and 0 <= v.sum() < 2 ** 24, (k, "not exactly representable")
+        assert float(REF.ordered_sum(world[k])) == v.sum(), k
+    assert r["summary"][4] == N and r["summary"][5] == W

@@ -28,6 +28,9 @@ C_DEV = 4
 C_E2E = 4
 A = 64
 SHAPES = ((6, 91), (9, 7), (6, 31))
+# the action counts where the tiling of the heads changes (tests/policy_cases.py EDGE_SHAPES)
+EDGE_SHAPES = ((6, 1), (9, 8), (6, 32), (9, 33), (6, 1024))
+EDGE_UPDATES = ((33, 6, 1), (33, 9, 32), (3, 6, 1024))  # (n, ego_width, n_actions) of one whole update
 
 
 def _stream():
@@ -104,7 +107,7 @@ def test_the_loss_kernel_against_the_float64_reference(m):
 
 # ---- gd_ppo_adam
 
-@pytest.mark.parametrize("ew,na", SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("ew,na", SHAPES + EDGE_SHAPES, ids=lambda v: str(v))
 def test_the_optimiser_step_is_the_host_programs_bit_for_bit(ew, na):
     from gpudrive_lab_amd.policy import grad_floats, pack_index
     from gpudrive_lab_amd.ppo import blob_of
@@ -230,10 +233,7 @@ def test_the_first_epochs_ratio_is_exactly_one():
     assert _same(ppo._rows[0], lp) and _same(ppo._rows[2], val), "evaluating the sampled actions returns their logprob and value"
 
 
-@pytest.fixture(scope="module")
-def updated():
-    """One update at n = 70, (6, 91), with `minibatch`'s perturbed old logprobs and values; everything on the host."""
-    n, ew, na = 70, 6, 91
+def _updated(n, ew, na):
     sd, ppo = _ppo(n, ew, na, clip_vloss=True)
     obs, actions, lp, val = _sampled(ppo, n, ew)
     old = GR.minibatch(11, lp.cpu().numpy(), val.cpu().numpy())  # (old_logprob, adv, ret, old_value)
@@ -243,8 +243,13 @@ def updated():
                 winners=ppo.winners.cpu().numpy().copy(), after={k: v.cpu().numpy() for k, v in ppo.state_dict().items()})
 
 
-def test_one_update_moves_the_parameters_as_the_float64_pipeline_does(updated):
-    u = updated
+@pytest.fixture(scope="module")
+def updated():
+    """One update at n = 70, (6, 91), with `minibatch`'s perturbed old logprobs and values; everything on the host."""
+    return _updated(70, 6, 91)
+
+
+def _check_update(u, what="ppo update end to end"):
     obs_h = u["obs"].cpu().numpy()
     kw = dict(norm_adv=True, clip_vloss=True)
     p64, g64 = UR.pipeline(u["sd"], A, u["ew"], obs_h, u["actions"], u["winners"], u["old"], torch.float64, **kw)
@@ -256,14 +261,31 @@ def test_one_update_moves_the_parameters_as_the_float64_pipeline_does(updated):
         ratio = UR.ratio_of(float(np.abs(u["after"][k] - p64[k]).max()), E[k])
         if ratio > worst:
             worst, at = ratio, k
-    print("ppo update end to end: largest error / E %.2f at %s" % (worst, at))
+    print("%s: largest error / E %.2f at %s" % (what, worst, at))
     for k in p64:
         err = float(np.abs(u["after"][k] - p64[k]).max())
         assert err <= C_E2E * E[k], (k, "error %.3g above %d E = %.3g" % (err, C_E2E, C_E2E * E[k]))
         if np.any(g64[k] != 0):
             moved = float(np.abs(u["after"][k].astype(np.float64) - u["sd"][k].double().numpy()).max())
             assert moved > 100 * C_E2E * E[k], (k, "the step is visible", moved, E[k])
-    assert all(np.any(g64[k] != 0) for k in p64), "every tensor has a gradient here"
+    return g64
+
+
+def test_one_update_moves_the_parameters_as_the_float64_pipeline_does(updated):
+    g64 = _check_update(updated)
+    assert all(np.any(g64[k] != 0) for k in g64), "every tensor has a gradient here"
+
+
+@pytest.mark.parametrize("n,ew,na", EDGE_UPDATES, ids=lambda v: str(v))
+def test_one_update_at_the_action_counts_where_the_tiling_changes(n, ew, na):
+    u = _updated(n, ew, na)
+    g64 = _check_update(u, "POLICY_EDGE ppo update n=%d ego=%d actions=%d (bound %d)" % (n, ew, na, C_E2E))
+    for k in g64:
+        if na == 1 and k.startswith("actor."):
+            # a softmax of one number has no gradient: float64 leaves the actor where it was, and so must the device, bit for bit
+            assert not np.any(g64[k] != 0) and _same(u["after"][k], u["sd"][k].numpy()), k
+        else:
+            assert np.any(g64[k] != 0), (k, "the tensor has a gradient here")
 
 
 def test_the_blob_stored_in_place_is_the_repack(updated):

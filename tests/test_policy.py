@@ -92,7 +92,7 @@ def test_the_blob_has_the_size_the_library_expects():
 
 def _rule_cases():
     rng = np.random.default_rng(5)
-    for na in (91, 7, 1, 1024):
+    for na in (91, 7, 1, 1024) + tuple(k for k in PC.EDGE_ACTIONS if k not in (1, 1024)):
         logits = (rng.normal(0.0, 2.0, (40, na))).astype(np.float32)
         logits[0] = 0.0                      # a uniform row: every logit is the maximum
         if na > 5:
@@ -115,6 +115,20 @@ def test_rule_header_on_the_host_equals_the_float64_rule(na, logits):
     # u = 0 takes the first action with any mass, the largest u below 1 the last
     a, _, _ = PC.run_rule_host(logits, PC.edge_uniforms(n), False)
     assert (a[0::2] == 0).all() and (a[1::2] == na - 1).all()
+
+
+def test_rule_host_program_under_the_sanitizers_at_the_edge_action_counts():
+    """The same program as a stand-alone executable built with -fsanitize=address,undefined: it must exit cleanly and give the
+    plain build's bits, at one action, at the counts around a tile of 32 and at 1024."""
+    rng = np.random.default_rng(7)
+    for na in PC.EDGE_ACTIONS:
+        logits = rng.normal(0.0, 2.0, (5, na)).astype(np.float32)
+        for u, det in ((PC.uniforms(na, 5), False), (PC.edge_uniforms(5), False), (PC.uniforms(na, 5), True)):
+            plain, san = PC.run_rule_host(logits, u, det), PC.run_rule_host(logits, u, det, sanitize=True)
+            assert np.array_equal(plain[0], san[0]), na
+            assert all(np.array_equal(p.view(np.int32), q.view(np.int32)) for p, q in zip(plain[1:], san[1:])), na
+        if na == 1:
+            assert (plain[0] == 0).all() and (plain[1].view(np.int32) == 0).all() and (plain[2] == 0).all()
 
 
 # ---- the reference
@@ -243,7 +257,37 @@ def _emulate(blob, obs, max_agents, ew, na):
     return logits, value
 
 
-@pytest.mark.parametrize("max_agents,ego_width,n_actions,n", [(64, 9, 7, 2), (128, 6, 91, 1), (64, 6, 33, 34)])
+# ... and at the action counts where the number of head tiles or the value's place in its tile changes (PC.EDGE_SHAPES)
+_LANE_CASES = [(64, 9, 7, 2), (128, 6, 91, 1), (64, 6, 33, 34),
+               (64, 6, 1, 3), (128, 9, 8, 2), (64, 9, 31, 2), (128, 6, 32, 33), (64, 6, 1024, 2), (64, 9, 1024, 33)]
+
+
+def test_the_lane_order_cases_cover_the_edge_action_counts():
+    assert set(PC.EDGE_ACTIONS) <= {c[2] for c in _LANE_CASES} and PC.EDGE_ACTIONS == [1, 8, 31, 32, 33, 1024]
+    for na in (1, 32, 1024):  # each with both n
+        assert {s[0] for s in PC.EDGE_SHAPES if s[3] == na} == {3, 33}
+
+
+@pytest.mark.parametrize("ew,na", [(6 if i % 2 == 0 else 9, na) for i, na in enumerate(PC.EDGE_ACTIONS)])
+def test_pack_index_and_grad_floats_round_trip_at_the_edge_action_counts(ew, na):
+    """The blob holds every parameter exactly once (the padding entries point at the trailing zero), the head's tiles are
+    (n_actions + 1 + 31) / 32, and the state dict comes back from the packed blob."""
+    from gpudrive_lab_amd.policy import expected_shapes, grad_floats, pack_index
+    sd = PC.state_dict(3, ew, na)
+    shapes = expected_shapes(ew, na)
+    G, index = grad_floats(ew, na), pack_index(ew, na)
+    assert G == sum(v.numel() for v in sd.values()) and list(shapes) == list(sd)
+    tiles = (na + 1 + 31) // 32
+    assert len(index) - len(pack_index(ew, 31)) == (tiles - 1) * (64 * 64 + 32)
+    assert (np.bincount(index, minlength=G + 1)[:G] == 1).all() and (index == G).sum() == len(index) - G
+    flat = np.concatenate([sd[k].numpy().reshape(-1) for k in shapes] + [np.zeros(1, np.float32)])
+    blob = flat[index]
+    back = np.zeros(G + 1, np.float32)
+    back[index] = blob
+    assert np.array_equal(back.view(np.int32), flat.view(np.int32))
+
+
+@pytest.mark.parametrize("max_agents,ego_width,n_actions,n", _LANE_CASES)
 def test_the_packed_blob_read_in_lane_order_gives_the_reference(max_agents, ego_width, n_actions, n):
     from gpudrive_lab_amd.policy import expected_shapes, pack_index
     sd = PC.negative_pool_state(_sd(ego_width, n_actions))

@@ -94,7 +94,7 @@ def test_the_entry_points_check_their_arguments_without_a_device():
 def test_the_library_counts_the_parameters_as_the_state_dict_does():
     from gpudrive_lab_amd.policy import expected_shapes, grad_floats
     L = _capi.lib()
-    for ew, na in ((6, 91), (9, 7), (6, 1), (9, 1024)):
+    for ew, na in ((6, 91), (9, 7), (6, 1), (9, 1024), (9, 8), (6, 31), (9, 32), (6, 33)):
         assert grad_floats(ew, na) == sum(v.numel() for v in PC.state_dict(2, ew, na).values())
         assert list(expected_shapes(ew, na)) == list(PC.state_dict(2, ew, na))
         p, g = _capi.GdPolicy(), _capi.GdPolicyGrad()
@@ -165,7 +165,7 @@ def test_nbytes_is_its_formula():
 
 def _rule_cases():
     rng = np.random.default_rng(6)
-    for na in (91, 7, 1, 1024):
+    for na in (91, 7, 1, 1024) + tuple(k for k in PC.EDGE_ACTIONS if k not in (1, 1024)):
         logits = rng.normal(0.0, 2.0, (40, na)).astype(np.float32)
         logits[0] = 0.0
         yield "seeded", na, logits
@@ -194,6 +194,22 @@ def test_rule_header_on_the_host_equals_the_float64_rule(name, na, logits):
     (torch.tensor(dlp.astype(np.float64)) * q.gather(1, torch.tensor(actions)[:, None])[:, 0]
      + torch.tensor(dent.astype(np.float64)) * -(q.exp() * q).sum(-1)).sum().backward()
     assert np.abs(l.grad.numpy() - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
+
+
+def test_rule_host_program_under_the_sanitizers_at_the_edge_action_counts():
+    """The same program as a stand-alone executable built with -fsanitize=address,undefined: it must exit cleanly and give the
+    plain build's bits; at one action every dlogit is zero."""
+    rng = np.random.default_rng(8)
+    for na in PC.EDGE_ACTIONS:
+        n = 5
+        logits = rng.normal(0.0, 2.0, (n, na)).astype(np.float32)
+        actions = rng.integers(0, na, n)
+        dlp, dent = rng.normal(0, 1, n).astype(np.float32), rng.normal(0, 1, n).astype(np.float32)
+        plain = GR.run_rule_host(logits, actions, dlp, dent)
+        san = GR.run_rule_host(logits, actions, dlp, dent, sanitize=True)
+        assert np.array_equal(plain.view(np.int32), san.view(np.int32)), na
+        if na == 1:
+            assert (plain == 0.0).all()
 
 
 # ---- the reference

@@ -135,7 +135,7 @@ def test_the_entry_points_check_their_arguments_without_a_device():
 def test_blob_of_inverts_pack_index():
     from gpudrive_lab_amd.policy import grad_floats, pack_index
     from gpudrive_lab_amd.ppo import blob_of
-    for ew, na in SHAPES + ((9, 1024),):
+    for ew, na in SHAPES + ((9, 1024),) + tuple((6 if i % 2 == 0 else 9, na) for i, na in enumerate(PC.EDGE_ACTIONS)):
         index, inv, G = pack_index(ew, na), blob_of(ew, na), grad_floats(ew, na)
         assert inv.dtype == np.int32 and inv.shape == (G,)
         assert (np.bincount(index, minlength=G + 1)[:G] == 1).all()
