@@ -234,7 +234,7 @@ struct gd_sim {
             alloc_into(mine, n.cp_hdr, 2 * WA);
             alloc_into(mine, n.rk_cp, WA * GD_RANK_NCP);
             alloc_into(mine, n.rk_tl, WA);
-            alloc_into(mine, n.rk_hist, 544);
+            alloc_into(mine, n.rk_hist, GD_RH_ALLOC);
             alloc_into(mine, n.rk_ticket, WA);
             alloc_into(mine, n.rk_order, WA);
             alloc_into(mine, n.rk_list, 8 * WA);
@@ -945,6 +945,7 @@ struct gd_sim {
         HIP_CHECK(hipMemset(d.rk_fallback, 0, sizeof(int32_t) * (static_cast<size_t>(W) * A / 32)));
         HIP_CHECK(hipMemset(d.rk_streak, 0, sizeof(int32_t) * (static_cast<size_t>(W) * A / 32)));
         HIP_CHECK(hipMemset(d.rk_hist, 0, sizeof(int32_t) * GD_RANK_AUDIT));  // bin counts, the lists of ranked agents: empty (the audit counter behind them keeps counting)
+        HIP_CHECK(hipMemset(d.rk_hist + GD_RH_LONG, 0, sizeof(int32_t) * (GD_RH_SIZE - GD_RH_LONG)));  // the long list: empty; k_knn_rank's cursors: at the lists' heads
     }
 
     void do_reset(const std::vector<int32_t> &flags) {
@@ -1168,6 +1169,10 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         d.rk_on = 0;
         d.rk_dbg = 0;
         d.rk_min_roads = 1536;
+        // GPUDRIVE_RANK_WAVES pins the workgroups of the standard ranking launch (rounded up to a multiple of 8, one share per
+        // XCD): few waves that take many turns each on the small worlds of a test
+        d.rk_waves = 0;
+        if (const char *e = std::getenv("GPUDRIVE_RANK_WAVES")) d.rk_waves = std::min(std::max((std::atoi(e) + 7) / 8 * 8, 8), GD_RANK_GRID);
         s->rk_possible = GD_MAP_OBS_AW == 32 && cfg->knn_order != GD_KNN_SET_ORDER &&
                          params->roadObservationAlgorithm == GD_ROADS_K_NEAREST && std::getenv("GPUDRIVE_NO_RANK_REPLAY") == nullptr;
 #ifdef GD_DIAG
@@ -2361,6 +2366,19 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
             (void)hipStreamSynchronize(s->stream);
             if (hipMemcpy(&v, s->d.rk_hist + 256 + (which - 1000), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
                 return fail(GD_ERR_DEVICE, "gd_stat: reading the replay clocks failed");
+            *out = v;
+        }
+        return GD_OK;
+    }
+#endif
+#ifdef GD_WAVE_CLOCKS
+    if (s && out && which >= 2000 && which < 2000 + 3 * GD_RANK_GRID) {  // k_knn_rank's waves in the last selection (engine.hpp GD_RH_WAVES)
+        *out = 0;
+        if (s->rk_alloc) {
+            int32_t v = 0;
+            (void)hipStreamSynchronize(s->stream);
+            if (hipMemcpy(&v, s->d.rk_hist + GD_RH_WAVES + (which - 2000), sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(GD_ERR_DEVICE, "gd_stat: reading the ranking waves' clocks failed");
             *out = v;
         }
         return GD_OK;

@@ -18,6 +18,24 @@
 #define GD_RANK_CAP_LONG 2560   // candidates of an agent that the long-list instantiation of the ranking takes (map_obs_rank.hip)
 #define GD_RANK_KT_LONG 164     // its key-table row (CAP_LONG / 16 entries + the last, padded to 16 bytes)
 #define GD_RH_LONG 537          // rk_hist: agents on the long list in this selection
+// rk_hist: the cursors k_knn_rank's waves draw their agents from (atomicAdd), one per XCD list, a 128-byte line each (eight
+// XCDs add to eight of them at the same time); zero between selections (k_knn_order, rebuild)
+#define GD_RH_CURSOR 544
+#define GD_RH_CURSOR_STRIDE 32
+#define GD_RH_SIZE (GD_RH_CURSOR + 8 * GD_RH_CURSOR_STRIDE)  // ints of rk_hist in the product build
+#define GD_RANK_GRID (256 * 8 * 4)  // workgroups (= waves) of the standard ranking launch at most: 16 per CU resident (LDS)
+#ifdef GD_CLOCKS
+#define GD_WAVE_CLOCKS
+#endif
+#ifdef GD_WAVE_CLOCKS
+// -DGD_WAVE_CLOCKS (-DGD_CLOCKS includes it; alone it leaves the kernels' code as the product's, where the phase clocks
+// double k_knn_rank's time): behind them, per wave of the standard ranking launch: the 100 MHz clock at its start, at its
+// end, agents ranked (gd_stat 2000 + k reads rk_hist[GD_RH_WAVES + k]; tools/rank_waves.py)
+#define GD_RH_WAVES GD_RH_SIZE
+#define GD_RH_ALLOC (GD_RH_WAVES + 3 * GD_RANK_GRID)
+#else
+#define GD_RH_ALLOC GD_RH_SIZE
+#endif
 #define GD_RANK_NCH 320  // 32-road words of a world's road bitmap (k_knn_finish): kMaxRoadEntityCount = 10,000
 #define GD_RANK_SPL 256  // sorted slots whose road index k_knn_rank hands on: the K elements the heap ends with have the K smallest
                          // keys, i.e. fewer than K candidates below them and at most 31 equal ones before them: slot < K + 31
@@ -180,7 +198,8 @@ struct DevSim {
     float *rk_kt;          // [W][A][GD_RANK_KT] key at sorted slot 16 j (16 j < n), then the largest key at j = ceil(n / 16)
     uint32_t *rk_heap;     // [W][A][GD_RANK_HEAP_DW] the replayed heap array as rank pairs
     uint16_t *rk_cpe;      // [W][A][NCP] rank on top of the heap at every checkpoint of this selection
-    int32_t *rk_hist;      // [544] replay order: 256 bin counts, [256..511] unused (-DGD_CLOCKS: k_knn_replay's phase clocks), the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT)
+    int32_t *rk_hist;      // [GD_RH_ALLOC] replay order: 256 bin counts, [256..511] unused (-DGD_CLOCKS: k_knn_replay's phase clocks), the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT); [537] GD_RH_LONG; from GD_RH_CURSOR on: k_knn_rank's cursors
+    int rk_waves;          // workgroups of the standard ranking launch (GPUDRIVE_RANK_WAVES, a multiple of 8); 0: one per live agent up to GD_RANK_GRID
     int32_t *rk_ticket;    // [W][A] bin << 20 | place inside the bin (bit 30: fell back after taking it); -1 = not on the rank path this step; < -1: why
     int32_t *rk_order;     // [W][A] agents on the rank path, most candidates first
     int32_t *rk_list;      // [8][W][A] agents on the rank path, one list per XCD that scanned them (counts: rk_hist[528..535])

@@ -499,14 +499,21 @@ struct PhaseClock {
 struct PhaseClock {};
 #define GD_PHASE(n)
 #endif
+// A wave asks its list's cursor for the entry it ranks next (lane 0; the answer is lane 0's, taken with readfirstlane).  The
+// cursor changes during the launch: it is read through the atomic's return only, never through uniform_load (INVARIANT above).
+__device__ __forceinline__ int rank_draw(int *cursor, int lane) {
+    int e = 0;
+    if (lane == 0) e = atomicAdd(cursor, 1);
+    return e;
+}
 template <int A_T, int CAP_T>
-__device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, int lane, RankLds<CAP_T> &L, PhaseClock &clk, int next_entry,
+__device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, int lane, RankLds<CAP_T> &L, PhaseClock &clk, int drawn,
                                            int count, const int *list, RankIn &nxt) {
     using G = RankGeo<CAP_T>;
     constexpr int NB = G::NB, NLIN = G::NLIN, NMAX = G::NMAX;
     constexpr unsigned int TM = (1u << G::RSH) - 1u;  // most equal keys before a candidate that its rank can count
     if (__builtin_amdgcn_readfirstlane(in.state) != 1) {  // fallback or too far from every road (k_knn_scan)
-        nxt = rank_fetch<A_T>(d, list, next_entry, count, lane);
+        nxt = rank_fetch<A_T>(d, list, __builtin_amdgcn_readfirstlane(drawn), count, lane);
         return;
     }
     // every lane fetched the same values: as scalars they index through scalar base addresses (a per-lane 64-bit pointer per
@@ -595,6 +602,9 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
         }
     }
     wave_sync();
+    // the next agent's entry (rank_draw, asked for before the table): vector memory answers in order, so the cull's blocks
+    // above waited for it too; from here on it is a scalar
+    const int next_entry = uni(drawn);
     // ---- SCAN of the surviving blocks, four per pass (a quarter of the wave each), in index order: the per-road test
     // (rank_cand.hpp: k_knn_scan's former expression, bit for bit), the exact key (gd_math.hpp ego_dist2: the reference's
     // arithmetic), one ballot per pass; (road, key) go to LDS at the candidate's position.  Roads 0..K-1 are candidates
@@ -1024,24 +1034,50 @@ __global__ __launch_bounds__(64, CAP_T > CAP ? 2 : 4) void k_knn_rank(DevSim d) 
     if (d.gate_any && *d.any_reset == 0) return;
     __shared__ RankLds<CAP_T> L;
     // Which agents a wave takes.  Standard: workgroup b runs on XCD b % 8 and shares out the list of the agents that
-    // k_knn_scan's workgroups on that XCD put on the rank path (rk_list), one entry per wave and turn.  The road points an
+    // k_knn_scan's workgroups on that XCD put on the rank path (rk_list): a wave draws one entry per turn from the list's
+    // cursor (rk_hist[GD_RH_CURSOR ..], zero when the launch starts: k_knn_order of the selection before, the rebuild) until
+    // the draw is at or beyond the list's end.  An agent's cost varies (candidates 351 .. 854 beyond K on the bench scene,
+    // and the same agent slot of the same scene costs the same step after step), and a fixed share of entries t, t + stride, ..
+    // gave every wave eight turns of ONE agent slot: the launch lasted as long as the wave with the dearest slot.  Drawn, a
+    // wave that got cheap agents takes more of them.  The entry for turn n + 1 is drawn at the start of turn n, so its
+    // answer is back long before rank_fetch asks for that agent.  No wave takes from another XCD's list.  The road points an
     // agent gathers (32 KB per world on the bench scene) are then in that XCD's L2 already, and the waves resident at a time
     // work on a few dozen worlds instead of all of them (in agent-major order every generation of waves touched every world:
     // 32 MB against 4 MB of L2 per XCD; HBM bytes of the road observation 2.16 -> 1.36 GB per step).  Long lists: the one
-    // list that the standard launch made of the agents it could not hold.
+    // list that the standard launch made of the agents it could not hold, entries b, b + gridDim.x, .. for wave b.
+    // The cursors are asked only where there is something to share out: thousands of waves adding to one address cost tens
+    // of microseconds.  (Measured with the long list on a cursor of its own: 2048 waves from every XCD on one address, 21 us
+    // with the list EMPTY, as it is in most selections; drawn behind a first turn by index, the unreduced Waymo tiles' step
+    // still went from 0.953 to 0.978 ms.  So the long list keeps its fixed shares.)  A standard list that has a turn for each
+    // wave at most is shared out by index too (the deal it always had; nothing to balance there, and on the Waymo tiles every
+    // wave asking once cost more than the kernel gained); otherwise every turn is drawn -- only half of the standard launch's
+    // waves are resident at a time, and entries kept for the others would wait for the first wave to leave.  A wave with
+    // nothing to take leaves before it asks.
     constexpr bool LONG = RankGeo<CAP_T>::LONG;
-    const int stride = LONG ? (int)gridDim.x : (int)(gridDim.x >> 3);  // (the standard grid is a multiple of 8 workgroups)
-    const int xcd = blockIdx.x & 7;
+    const int xcd = blockIdx.x & 7;  // (the standard grid is a multiple of 8 workgroups)
     const int count = LONG ? min(uniform_load(d.rk_hist + GD_RH_LONG), d.rk_nlong) : uniform_load(d.rk_hist + 528 + xcd);
     const int *list = LONG ? d.rk_longlist : d.rk_list + (size_t)xcd * d.W * A_T;
-    int t = LONG ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
+    int *const cursor = d.rk_hist + GD_RH_CURSOR + xcd * GD_RH_CURSOR_STRIDE;
+    const int share = LONG ? (int)gridDim.x : (int)(gridDim.x >> 3), mine = LONG ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
+    const bool fixed = LONG || count <= share;  // shares by index, no cursor
+#ifdef GD_WAVE_CLOCKS
+    // per wave of the standard launch: the constant 100 MHz clock at its start and at its end, the agents it ranked
+    // (engine.hpp GD_RH_WAVES; tools/rank_waves.py takes the ends from the earliest start of the launch on the wave's XCD)
+    int turns = 0;
+    if (!LONG && threadIdx.x == 0) {
+        d.rk_hist[GD_RH_WAVES + blockIdx.x] = (int)__builtin_amdgcn_s_memrealtime();
+        d.rk_hist[GD_RH_WAVES + 2 * GD_RANK_GRID + blockIdx.x] = 0;
+    }
+#endif
+    if (fixed && mine >= count) return;
+    int t = fixed ? mine : __builtin_amdgcn_readfirstlane(rank_draw(cursor, threadIdx.x));
     RankIn cur = rank_fetch<A_T>(d, list, t, count, threadIdx.x);
     PhaseClock clk;
 #ifdef GD_CLOCKS
     for (int k = 0; k < 8; k++) clk.sum[k] = 0u;
     clk.prev = (unsigned int)__builtin_amdgcn_s_memtime();
 #endif
-    for (; t < count; t += stride) {
+    while (t < count) {
         RankIn nxt;
         GD_PHASE(0);  // between agents: the buffers change hands
         // (an opaque copy of the lane, per agent: what the ranking derives from the lane alone -- LDS addresses, row pointers,
@@ -1049,13 +1085,25 @@ __global__ __launch_bounds__(64, CAP_T > CAP ? 2 : 4) void k_knn_rank(DevSim d) 
         // through every phase, and the kernel has no register to spare)
         int lane_v = threadIdx.x;
         asm volatile("" : "+v"(lane_v));
-        rank_agent<A_T, CAP_T>(d, cur, lane_v, L, clk, t + stride, count, list, nxt);
+        const int drawn = fixed ? t + share : rank_draw(cursor, lane_v);  // the turn after this one
+        rank_agent<A_T, CAP_T>(d, cur, lane_v, L, clk, drawn, count, list, nxt);
         wave_sync();  // the LDS buffers change hands
         cur = nxt;
+        t = __builtin_amdgcn_readfirstlane(nxt.li);
+#ifdef GD_WAVE_CLOCKS
+        turns++;
+#endif
     }
 #ifdef GD_CLOCKS
     if (threadIdx.x == 0)
         for (int k = 0; k < 8; k++) atomicAdd(reinterpret_cast<unsigned int *>(&d.rk_hist[516 + k]), clk.sum[k] >> 8);
+#endif
+#ifdef GD_WAVE_CLOCKS
+    if (!LONG && threadIdx.x == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last agent's stores are part of the wave's time
+        d.rk_hist[GD_RH_WAVES + GD_RANK_GRID + blockIdx.x] = (int)__builtin_amdgcn_s_memrealtime();
+        d.rk_hist[GD_RH_WAVES + 2 * GD_RANK_GRID + blockIdx.x] = turns;
+    }
 #endif
 }
 
@@ -1112,6 +1160,7 @@ __global__ __launch_bounds__(256) void k_knn_order(DevSim d) {
         d.rk_hist[513]++;                // selections so far (k_knn_scan staggers the retries of bypassing groups with it)
         for (int x = 0; x < 8; x++) d.rk_hist[528 + x] = 0;  // the next selection's lists of ranked agents start empty
         d.rk_hist[GD_RH_LONG] = 0;
+        for (int x = 0; x < 8; x++) d.rk_hist[GD_RH_CURSOR + x * GD_RH_CURSOR_STRIDE] = 0;  // ... and k_knn_rank draws them from the head
     }
 #ifdef GD_CLOCKS
     if (blockIdx.x == 0) d.rk_hist[256 + tl] = 0;  // k_knn_replay's phase clocks of this selection
@@ -1539,7 +1588,7 @@ void launch_map_obs_rank(const DevSim &d, hipStream_t st) {
     // the long-list ranking: persistent waves (eight per CU fit) over however many agents the standard launch passed on (none:
     // every wave reads the empty count and leaves)
     const dim3 glong(std::min(std::max(d.rk_nlong, 1), GD_RANK_LONG_GRID));
-    const dim3 gr(std::min((d.live_count + 7) / 8 * 8, 256 * 8 * 4)), g4((d.live_count + 3) / 4), gw(d.W * (d.A / 64));  // rank: 8192 persistent waves, 16 per CU resident (LDS)
+    const dim3 gr(d.rk_waves > 0 ? d.rk_waves : std::min((d.live_count + 7) / 8 * 8, GD_RANK_GRID)), g4((d.live_count + 3) / 4), gw(d.W * (d.A / 64));  // rank: 8192 persistent waves, 16 per CU resident (LDS)
     if (d.A == 64) {
         hipLaunchKernelGGL((k_knn_scan<64>), gw, dim3(256), 0, st, d);
         hipLaunchKernelGGL((k_knn_rank<64, CAP>), gr, dim3(64), 0, st, d);
