@@ -1958,44 +1958,59 @@ int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers 
     });
 }
 
-// The closed-loop PPO evaluator (policy_rollout.hip): gd_bc_rollout's loop with the late-fusion policy on the learner rows.
-int gd_policy_rollout(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, int32_t n_steps) {
-    if (!s || !p || !b) return fail(GD_ERR_INVALID, "gd_policy_rollout: null argument");
+// everything gd_policy_rollout refuses, for gd_policy_rollout_compact too; GD_OK when everything is in order
+static int policy_rollout_problem(const char *who, gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, int32_t n_steps) {
+    const std::string w = std::string(who) + ": ";
+    if (!s || !p || !b) return fail(GD_ERR_INVALID, w + "null argument");
     if (!b->table || !b->actions || !b->logprob || !b->entropy || !b->value || !b->live || !b->goal_achieved || !b->collided ||
         !b->off_road || !b->world_active || !b->episode_lengths || !b->bad_indices || !b->any_active || !b->goal_achieved_count ||
         !b->frac_goal_achieved || !b->collided_count || !b->frac_collided || !b->off_road_count || !b->frac_off_road ||
         !b->other_count || !b->frac_other || !b->controlled_per_scene || !b->summary)
-        return fail(GD_ERR_INVALID, "gd_policy_rollout: every buffer but u and the per-step records is required");
-    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_policy_rollout: n_rows must be in [1, 2^20]");
+        return fail(GD_ERR_INVALID, w + "every buffer but u and the per-step records is required");
+    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, w + "n_rows must be in [1, 2^20]");
     if (n_steps < 1 || n_steps > GD_EPISODE_LEN)
-        return fail(GD_ERR_INVALID, "gd_policy_rollout: an episode has 91 steps, n_steps must be in [1, 91]");
-    if (b->reserved != 0) return fail(GD_ERR_INVALID, "gd_policy_rollout: reserved must be 0");
+        return fail(GD_ERR_INVALID, w + "an episode has 91 steps, n_steps must be in [1, 91]");
+    if (b->reserved != 0) return fail(GD_ERR_INVALID, w + "reserved must be 0");
     if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
-        return fail(GD_ERR_UNSUPPORTED, "gd_policy_rollout: the State dynamics model has no discrete action space");
-    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, "gd_policy_rollout: no learner rows set (gd_set_learner_rows)");
+        return fail(GD_ERR_UNSUPPORTED, w + "the State dynamics model has no discrete action space");
+    if (!s->d.row_of_slot) return fail(GD_ERR_INVALID, w + "no learner rows set (gd_set_learner_rows)");
     if (!s->d.pack || !s->d.pack_rows)
-        return fail(GD_ERR_INVALID, "gd_policy_rollout: no learner-row buffer attached (gd_attach_packed_rows)");
-    if (b->n_rows != s->d.n_rows) return fail(GD_ERR_INVALID, "gd_policy_rollout: n_rows differs from the number of learner rows");
-    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's max_agents differs from the simulator's");
+        return fail(GD_ERR_INVALID, w + "no learner-row buffer attached (gd_attach_packed_rows)");
+    if (b->n_rows != s->d.n_rows) return fail(GD_ERR_INVALID, w + "n_rows differs from the number of learner rows");
+    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, w + "the policy's max_agents differs from the simulator's");
     if (p->ego_width != (s->d.pack_weights ? 9 : 6))
-        return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's ego_width differs from the attached rows' (6, or 9 for conditioned rows)");
-    if (p->num_rows != b->n_rows) return fail(GD_ERR_INVALID, "gd_policy_rollout: the policy's num_rows differs from n_rows");
-    if (b->n_actions != p->n_actions) return fail(GD_ERR_INVALID, "gd_policy_rollout: the table's n_actions differs from the policy's");
+        return fail(GD_ERR_INVALID, w + "the policy's ego_width differs from the attached rows' (6, or 9 for conditioned rows)");
+    if (p->num_rows != b->n_rows) return fail(GD_ERR_INVALID, w + "the policy's num_rows differs from n_rows");
+    if (b->n_actions != p->n_actions) return fail(GD_ERR_INVALID, w + "the table's n_actions differs from the policy's");
     if (const char *why = policy_forward_problem(p, s->d.pack, b->u, b->deterministic, b->actions, b->logprob, b->entropy, b->value,
                                                  nullptr))
-        return fail(GD_ERR_INVALID, std::string("gd_policy_rollout: ") + why);
+        return fail(GD_ERR_INVALID, w + why);
     if (misaligned(b->table, 4) || misaligned(b->goal_achieved, 4) || misaligned(b->collided, 4) || misaligned(b->off_road, 4) ||
         misaligned(b->episode_lengths, 4) || misaligned(b->bad_indices, 4) || misaligned(b->any_active, 4) ||
         misaligned(b->goal_achieved_count, 4) || misaligned(b->frac_goal_achieved, 4) || misaligned(b->collided_count, 4) ||
         misaligned(b->frac_collided, 4) || misaligned(b->off_road_count, 4) || misaligned(b->frac_off_road, 4) ||
         misaligned(b->other_count, 4) || misaligned(b->frac_other, 4) || misaligned(b->controlled_per_scene, 4) ||
         misaligned(b->summary, 4) || misaligned(b->actions_idx, 8) || misaligned(b->agent_positions, 4))
-        return fail(GD_ERR_INVALID, "gd_policy_rollout: actions_idx must be 8-byte aligned, float and int32 buffers 4-byte aligned");
+        return fail(GD_ERR_INVALID, w + "actions_idx must be 8-byte aligned, float and int32 buffers 4-byte aligned");
+    return GD_OK;
+}
+
+// The loop of both evaluators: r == nullptr is gd_policy_rollout's forward on all N rows, otherwise the list in the loop.
+static int policy_rollout_run(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, const gd_policy_rollout_rows *r,
+                              int32_t n_steps) {
     return guarded([&]() {
         const size_t N = static_cast<size_t>(b->n_rows);
         for (int t = 0; t < n_steps; t++) {
-            gd::launch_policy_forward(*p, s->stream, s->d.pack, b->u ? b->u + t * N : nullptr, b->deterministic != 0, b->actions,
-                                      b->logprob, b->entropy, b->value, nullptr);
+            const float *u = b->u ? b->u + t * N : nullptr;
+            if (r) {
+                gd::launch_live_rows(s->stream, b->live, b->n_rows, r->rows, r->count, r->scratch,
+                                     r->live_count ? r->live_count + t : nullptr);
+                gd::launch_policy_forward_rows(*p, nullptr, s->stream, s->d.pack, u, b->deterministic != 0, b->actions, b->logprob,
+                                               b->entropy, b->value, nullptr, r->rows, r->count);
+            } else {
+                gd::launch_policy_forward(*p, s->stream, s->d.pack, u, b->deterministic != 0, b->actions, b->logprob, b->entropy,
+                                          b->value, nullptr);
+            }
             gd::launch_policy_rollout_actions(s->d, s->stream, *b, t);
             HIP_CHECK(hipGetLastError());
             s->step();
@@ -2005,6 +2020,58 @@ int gd_policy_rollout(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buf
         gd::launch_policy_rollout_finish(s->d, s->stream, *b, n_steps);
         HIP_CHECK(hipGetLastError());
     });
+}
+
+// The closed-loop PPO evaluator (policy_rollout.hip): gd_bc_rollout's loop with the late-fusion policy on the learner rows.
+int gd_policy_rollout(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, int32_t n_steps) {
+    if (const int rc = policy_rollout_problem("gd_policy_rollout", s, p, b, n_steps)) return rc;
+    return policy_rollout_run(s, p, b, nullptr, n_steps);
+}
+
+// everything the calls that take a row list refuse of it; nullptr when everything is in order
+static const char *row_list_problem(const int32_t *rows, const int32_t *count) {
+    if (!rows || !count) return "rows and count are required";
+    if (misaligned(rows, 4) || misaligned(count, 4)) return "rows and count must be 4-byte aligned";
+    return nullptr;
+}
+
+int gd_live_rows(const uint8_t *mask, int32_t n, int32_t *rows, int32_t *count, int32_t *scratch, void *stream) {
+    if (!mask || !scratch) return fail(GD_ERR_INVALID, "gd_live_rows: null argument");
+    if (const char *why = row_list_problem(rows, count)) return fail(GD_ERR_INVALID, std::string("gd_live_rows: ") + why);
+    if (misaligned(scratch, 4)) return fail(GD_ERR_INVALID, "gd_live_rows: scratch must be 4-byte aligned");
+    if (n < 1 || n > (1 << 20)) return fail(GD_ERR_INVALID, "gd_live_rows: n must be in [1, 2^20]");
+    return guarded([&]() {
+        gd::launch_live_rows(static_cast<hipStream_t>(stream), mask, n, rows, count, scratch, nullptr);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_policy_forward_rows(const gd_policy *p, const gd_dropout *d, const float *obs, const float *u, int32_t deterministic,
+                           int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out, const int32_t *rows,
+                           const int32_t *count, void *stream) {
+    const char *why = policy_forward_problem(p, obs, u, deterministic, actions, logprob, entropy, value, logits_out);
+    if (!why && d) why = dropout_problem(d);
+    if (!why) why = row_list_problem(rows, count);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_policy_forward_rows: ") + why);
+    return guarded([&]() {
+        gd::launch_policy_forward_rows(*p, d, static_cast<hipStream_t>(stream), obs, u, deterministic != 0, actions, logprob, entropy,
+                                       value, logits_out, rows, count);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// gd_policy_rollout with gd_live_rows and gd_policy_forward_rows in the loop.  The list is checked first: it needs no simulator.
+int gd_policy_rollout_compact(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buffers *b, const gd_policy_rollout_rows *r,
+                              int32_t n_steps) {
+    const char *who = "gd_policy_rollout_compact";
+    if (!s || !p || !b || !r) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
+    const char *why = row_list_problem(r->rows, r->count);
+    if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
+    if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
+    if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    if (const int rc = policy_rollout_problem(who, s, p, b, n_steps)) return rc;
+    return policy_rollout_run(s, p, b, r, n_steps);
 }
 
 // everything gd_bc_backward refuses; nullptr when everything is in order

@@ -282,6 +282,13 @@ void launch_policy_forward(const gd_policy &p, const gd_dropout &d, hipStream_t 
                            float *logits_out);  // policy.hip
 void launch_policy_evaluate(const gd_policy &p, const gd_dropout &d, hipStream_t st, const float *obs, const int64_t *actions,
                             unsigned char *winners, float *logprob, float *entropy, float *value);  // policy.hip
+// the forward on a device-resident row list (d: null for the unmasked forward); grids sized for p.num_rows
+void launch_policy_forward_rows(const gd_policy &p, const gd_dropout *d, hipStream_t st, const float *obs, const float *u,
+                                bool deterministic, int64_t *actions, float *logprob, float *entropy, float *value,
+                                float *logits_out, const int32_t *rows, const int32_t *count);  // policy.hip
+// live_rows.hip: mask -> ascending row list and its length (count_copy: a second place for the length, or null); two launches
+void launch_live_rows(hipStream_t st, const uint8_t *mask, int n, int32_t *rows, int32_t *count, int32_t *scratch,
+                      int32_t *count_copy);
 void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, const gd_dropout &d, hipStream_t st, const float *obs,
                             const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
                             float *grad);  // policy_grad.hip

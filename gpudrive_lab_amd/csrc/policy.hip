@@ -19,6 +19,11 @@
 // Training-mode dropout (gd_policy_forward_dropout, gd_policy_evaluate_dropout) is the same three launches on the DROP
 // instantiations of k_policy_embed and k_policy_tail, which mask the four sites by dropout_rule.hpp, and on k_policy_sample_drop /
 // k_policy_evaluate_drop, which also advance the call index; without DROP the code is unchanged.
+// The forward on a row list (gd_policy_forward_rows) is the same three launches on sibling kernels, k_policy_embed_rows,
+// k_policy_tail_rows and k_policy_sample_rows[_drop], which share the bodies above and differ in the index arithmetic only: a
+// wave (a lane column, a lane) is a POSITION of the device-resident list, reads the list's length and returns when it is past
+// it, computes row rows[position], keeps the scratch by position and stores the outputs of that row alone.  A row's result
+// never depends on the rows beside it, so a listed row gets the full forward's bits.
 #include <hip/hip_runtime.h>
 
 #include "dropout_rule.hpp"
@@ -199,21 +204,21 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// One wave's row: observation row `row` (which is also what the dropout rule is keyed on) to features[slot] (and, REC,
+// winners[slot]).  The full forward's slot is the row; the forward on a row list stores by list position.
 // DROP: da and callp are the rule's values and the device word that holds the call index; without DROP they are not read
 template <bool REC, bool DROP>
-__global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
-                                                      float *__restrict__ features, unsigned char *__restrict__ winners,
-                                                      DR::Args da, const uint64_t *__restrict__ callp) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= p.num_rows) return;  // wave-uniform; nothing below synchronises across waves
+__device__ __forceinline__ void policy_embed_row(const gd_policy p, const PolicyLayout L, const float *__restrict__ obs,
+                                                 float *__restrict__ features, unsigned char *__restrict__ winners,
+                                                 const DR::Args da, const uint64_t *__restrict__ callp, int lane, int row,
+                                                 int slot) {
     DropCall dc{da, 0, (uint32_t)row};
     if constexpr (DROP) dc.call = *callp;
     const int partners = p.max_agents - 1, ew = p.ego_width;
     const size_t width = (size_t)ew + (size_t)PARTNER_K * partners + (size_t)ROAD_K * ROADS;
     const float *__restrict__ x = obs + (size_t)row * width;
     const float *__restrict__ w = p.blob;
-    float *__restrict__ out = features + (size_t)row * FEAT;
+    float *__restrict__ out = features + (size_t)slot * FEAT;
 
     // ego: lane f is feature f
     {
@@ -229,7 +234,7 @@ __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout 
         for (int f = 0; f < F; f++) o = o + w[L.ego_w2t + f * F + lane] * __shfl(t, f);
         out[lane] = o;
     }
-    unsigned char *__restrict__ win = REC ? winners + (size_t)row * (2 * F) : nullptr;
+    unsigned char *__restrict__ win = REC ? winners + (size_t)slot * (2 * F) : nullptr;
     embed_pool<PARTNER_K, 3, REC, DROP>(x + ew, partners, w + L.emb_w1[0], w + L.emb_b1[0], w + L.emb_g[0], w + L.emb_b[0],
                                         w + L.emb_w2[0], w + L.emb_b2[0], out + F, win, lane, dc, DR::SITE_PARTNER);
     embed_pool<ROAD_K, 7, REC, DROP>(x + ew + PARTNER_K * partners, ROADS, w + L.emb_w1[1], w + L.emb_b1[1], w + L.emb_g[1],
@@ -237,18 +242,51 @@ __global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout 
                                      DR::SITE_ROAD);
 }
 
+template <bool REC, bool DROP>
+__global__ __launch_bounds__(256) void k_policy_embed(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
+                                                      float *__restrict__ features, unsigned char *__restrict__ winners,
+                                                      DR::Args da, const uint64_t *__restrict__ callp) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.num_rows) return;  // wave-uniform; nothing below synchronises across waves
+    policy_embed_row<REC, DROP>(p, L, obs, features, winners, da, callp, lane, row, row);
+}
+
+// The list's length as the kernels of the forward on a row list read it: never above N, the size of the list's array
+__device__ __forceinline__ int list_count(const int32_t *__restrict__ count, int n) {
+    const int c = *count;
+    return c < n ? c : n;
+}
+
+// The embed kernel on a row list: the wave of list position q takes row rows[q] and stores features[q].  A wave past the
+// list's length, or whose entry is no row, returns at once.
+template <bool DROP>
+__global__ __launch_bounds__(256) void k_policy_embed_rows(gd_policy p, PolicyLayout L, const float *__restrict__ obs,
+                                                           float *__restrict__ features, DR::Args da,
+                                                           const uint64_t *__restrict__ callp, const int32_t *__restrict__ rows,
+                                                           const int32_t *__restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int pos = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= list_count(count, p.num_rows)) return;  // wave-uniform
+    const int row = rows[pos];
+    if (row < 0 || row >= p.num_rows) return;
+    policy_embed_row<false, DROP>(p, L, obs, features, nullptr, da, callp, lane, row, pos);
+}
+
+// One wave's 32 rows, a row to a lane column: the features of slot `fslot`, the dropout rule keyed on `drow`, and, where
+// `store`, the scratch logits to slot `lslot` and the outputs to row `orow`.  The full forward: fslot = drow = the row clamped
+// to the last one, lslot = orow = the row.
 // DROP: hidden is masked after the 192 -> 128 product with its bias, before the heads: eight Philox calls per lane
 template <bool DROP>
-__global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L, const float *__restrict__ features,
-                                                    float *__restrict__ logits, float *__restrict__ logits_out,
-                                                    float *__restrict__ value, DR::Args da, const uint64_t *__restrict__ callp) {
-    const int lane = threadIdx.x, h = lane >> 5;
-    const int row = blockIdx.x * 32 + (lane & 31);
-    const int n = p.num_rows, na = p.n_actions;
-    const int rc = row < n ? row : n - 1;  // a lane past the end computes the last row again and stores nothing
+__device__ __forceinline__ void policy_tail_rows(const gd_policy p, const PolicyLayout L, const float *__restrict__ features,
+                                                 float *__restrict__ logits, float *__restrict__ logits_out,
+                                                 float *__restrict__ value, const DR::Args da, const uint64_t *__restrict__ callp,
+                                                 int lane, int fslot, int drow, bool store, int lslot, int orow) {
+    const int h = lane >> 5;
+    const int na = p.n_actions;
     const float *__restrict__ w = p.blob;
     // lane half h contracts the features [96h, 96h + 96): 24 aligned 16-byte loads
-    const f4 *__restrict__ fp = reinterpret_cast<const f4 *>(features + (size_t)rc * FEAT + 96 * h);
+    const f4 *__restrict__ fp = reinterpret_cast<const f4 *>(features + (size_t)fslot * FEAT + 96 * h);
     f16v hid[4];
 #pragma unroll
     for (int t = 0; t < 4; t++)
@@ -268,7 +306,7 @@ __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L,
         for (int t = 0; t < 4; t++)
 #pragma unroll
             for (int m = 0; m < 2; m++) {
-                const DR::Out o = DR::draw(da.seed, call, (uint32_t)rc, DR::SITE_SHARED, 0, (uint32_t)((((t << 1) | m) << 1) | h));
+                const DR::Out o = DR::draw(da.seed, call, (uint32_t)drow, DR::SITE_SHARED, 0, (uint32_t)((((t << 1) | m) << 1) | h));
 #pragma unroll
                 for (int k = 0; k < 8; k++) hid[t][8 * m + k] = DR::apply(hid[t][8 * m + k], DR::kept(o, k, da.threshold), da.scale);
             }
@@ -282,20 +320,50 @@ __global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L,
         for (int t = 0; t < 4; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[(t * 16 + r) * 64], hid[t][r], acc, 0, 0, 0);
-        if (row < n) {
+        if (store) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int a = 32 * i + acc_row(r, h);
                 const float v = acc[r] + w[L.ac_b + a];
                 if (a < na) {
-                    logits[(size_t)row * na + a] = v;
-                    if (logits_out) logits_out[(size_t)row * na + a] = v;
+                    logits[(size_t)lslot * na + a] = v;
+                    if (logits_out) logits_out[(size_t)orow * na + a] = v;
                 } else if (a == na) {
-                    value[row] = v;
+                    value[orow] = v;
                 }
             }
         }
     }
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(64) void k_policy_tail(gd_policy p, PolicyLayout L, const float *__restrict__ features,
+                                                    float *__restrict__ logits, float *__restrict__ logits_out,
+                                                    float *__restrict__ value, DR::Args da, const uint64_t *__restrict__ callp) {
+    const int lane = threadIdx.x;
+    const int row = blockIdx.x * 32 + (lane & 31);
+    const int n = p.num_rows;
+    const int rc = row < n ? row : n - 1;  // a lane past the end computes the last row again and stores nothing
+    policy_tail_rows<DROP>(p, L, features, logits, logits_out, value, da, callp, lane, rc, rc, row < n, row, row);
+}
+
+// The tail kernel on a row list: lane column c of workgroup g is list position q = 32 g + c: features[q] in, the scratch
+// logits[q] and the outputs of row rows[q] out.  A position past the list's length computes the last position again and
+// stores nothing, as does an entry that is no row (its features are whatever the scratch held).
+template <bool DROP>
+__global__ __launch_bounds__(64) void k_policy_tail_rows(gd_policy p, PolicyLayout L, const float *__restrict__ features,
+                                                         float *__restrict__ logits, float *__restrict__ logits_out,
+                                                         float *__restrict__ value, DR::Args da, const uint64_t *__restrict__ callp,
+                                                         const int32_t *__restrict__ rows, const int32_t *__restrict__ count) {
+    const int lane = threadIdx.x;
+    const int pos = blockIdx.x * 32 + (lane & 31);
+    const int cnt = list_count(count, p.num_rows);
+    if ((int)blockIdx.x * 32 >= cnt) return;  // wave-uniform; cnt >= 1 below
+    const int pc = pos < cnt ? pos : cnt - 1;
+    const int row = rows[pc];
+    const bool valid = row >= 0 && row < p.num_rows;
+    policy_tail_rows<DROP>(p, L, features, logits, logits_out, value, da, callp, lane, pc, valid ? row : 0, pos < cnt && valid, pc,
+                           valid ? row : 0);
 }
 
 // The last launch of a masked call also advances the call index: ONE lane (row 0) stores *call + 1, and for evaluate the
@@ -306,16 +374,53 @@ __device__ __forceinline__ void advance_call(uint64_t *__restrict__ callp, uint6
     *callp = c + 1;
 }
 
+// policy_rule.hpp on the logits l of one row: its draw u[row], its three outputs
+__device__ __forceinline__ void policy_sample_row(int na, const float *__restrict__ l, const float *__restrict__ u,
+                                                  int deterministic, int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                  float *__restrict__ entropy, int row) {
+    const policy_rule::Draw d = policy_rule::draw(na, [&](int k) { return l[k]; }, deterministic ? 0.f : u[row], deterministic != 0);
+    actions[row] = d.action;
+    logprob[row] = d.logprob;
+    entropy[row] = d.entropy;
+}
+
 __device__ __forceinline__ void policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
                                               int deterministic, int64_t *__restrict__ actions, float *__restrict__ logprob,
                                               float *__restrict__ entropy) {
     const int row = blockIdx.x * 64 + threadIdx.x;
     if (row >= n) return;
-    const float *__restrict__ l = logits + (size_t)row * na;
-    const policy_rule::Draw d = policy_rule::draw(na, [&](int k) { return l[k]; }, deterministic ? 0.f : u[row], deterministic != 0);
-    actions[row] = d.action;
-    logprob[row] = d.logprob;
-    entropy[row] = d.entropy;
+    policy_sample_row(na, logits + (size_t)row * na, u, deterministic, actions, logprob, entropy, row);
+}
+
+// The sample kernels on a row list: the lane of list position q reads the scratch logits[q] and writes row rows[q].  The
+// masked call's advances the call index whatever the list's length: the grid is sized for N >= 1.
+__device__ __forceinline__ void policy_sample_rows(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
+                                                   int deterministic, int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                   float *__restrict__ entropy, const int32_t *__restrict__ rows,
+                                                   const int32_t *__restrict__ count) {
+    const int pos = blockIdx.x * 64 + threadIdx.x;
+    if (pos >= list_count(count, n)) return;
+    const int row = rows[pos];
+    if (row < 0 || row >= n) return;
+    policy_sample_row(na, logits + (size_t)pos * na, u, deterministic, actions, logprob, entropy, row);
+}
+
+__global__ __launch_bounds__(64) void k_policy_sample_rows(int n, int na, const float *__restrict__ logits,
+                                                           const float *__restrict__ u, int deterministic,
+                                                           int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                           float *__restrict__ entropy, const int32_t *__restrict__ rows,
+                                                           const int32_t *__restrict__ count) {
+    policy_sample_rows(n, na, logits, u, deterministic, actions, logprob, entropy, rows, count);
+}
+
+__global__ __launch_bounds__(64) void k_policy_sample_rows_drop(int n, int na, const float *__restrict__ logits,
+                                                                const float *__restrict__ u, int deterministic,
+                                                                int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                                float *__restrict__ entropy, uint64_t *__restrict__ callp,
+                                                                const int32_t *__restrict__ rows,
+                                                                const int32_t *__restrict__ count) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) advance_call(callp, nullptr);
+    policy_sample_rows(n, na, logits, u, deterministic, actions, logprob, entropy, rows, count);
 }
 
 __global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
@@ -391,6 +496,31 @@ void launch_policy_forward(const gd_policy &p, const gd_dropout &d, hipStream_t 
                        value, da, d.call);
     hipLaunchKernelGGL(k_policy_sample_drop, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, p.n_actions, p.logits, u,
                        deterministic ? 1 : 0, actions, logprob, entropy, const_cast<uint64_t *>(d.call));
+}
+
+// The forward on a row list (gd_policy_forward_rows): the three launches with the full forward's grids -- the host does not
+// know the list's length -- on the kernels that take a list position for a row.  d: null for the unmasked forward.
+void launch_policy_forward_rows(const gd_policy &p, const gd_dropout *d, hipStream_t st, const float *obs, const float *u,
+                                bool deterministic, int64_t *actions, float *logprob, float *entropy, float *value,
+                                float *logits_out, const int32_t *rows, const int32_t *count) {
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    const int n = p.num_rows;
+    const dim3 embed((unsigned)((n + 3) / 4)), tail((unsigned)((n + 31) / 32)), sample((unsigned)((n + 63) / 64));
+    if (d) {
+        const DR::Args da = drop_args(*d);
+        hipLaunchKernelGGL(k_policy_embed_rows<true>, embed, dim3(256), 0, st, p, L, obs, p.features, da, d->call, rows, count);
+        hipLaunchKernelGGL(k_policy_tail_rows<true>, tail, dim3(64), 0, st, p, L, p.features, p.logits, logits_out, value, da,
+                           d->call, rows, count);
+        hipLaunchKernelGGL(k_policy_sample_rows_drop, sample, dim3(64), 0, st, n, p.n_actions, p.logits, u, deterministic ? 1 : 0,
+                           actions, logprob, entropy, const_cast<uint64_t *>(d->call), rows, count);
+    } else {
+        hipLaunchKernelGGL(k_policy_embed_rows<false>, embed, dim3(256), 0, st, p, L, obs, p.features, DR::Args{},
+                           (const uint64_t *)nullptr, rows, count);
+        hipLaunchKernelGGL(k_policy_tail_rows<false>, tail, dim3(64), 0, st, p, L, p.features, p.logits, logits_out, value,
+                           DR::Args{}, (const uint64_t *)nullptr, rows, count);
+        hipLaunchKernelGGL(k_policy_sample_rows, sample, dim3(64), 0, st, n, p.n_actions, p.logits, u, deterministic ? 1 : 0,
+                           actions, logprob, entropy, rows, count);
+    }
 }
 
 // p.features and p.logits are the caller-owned buffers of gd_policy_grad here

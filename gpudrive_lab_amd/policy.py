@@ -161,6 +161,58 @@ def pack_index(ego_width, n_actions):
     return np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in parts])
 
 
+def live_rows_scratch_ints(n):
+    """The int32 words of `gd_live_rows`' scratch for n rows: one per block of `_capi.LIVE_ROWS_BLOCK` rows."""
+    return (n + _capi.LIVE_ROWS_BLOCK - 1) // _capi.LIVE_ROWS_BLOCK
+
+
+class LiveRows:
+    """A device-resident list of rows: `rows` int32 [N], of which the first `count[0]` are the list, ascending; `count` int32
+    [1]; `scratch`, which `live_rows` needs.  Nothing on the host knows the length.  A new one lists no row (count 0).
+    new: who makes the three arrays, as new(name, shape, dtype, fill, device) (fill None: need not be initialised)."""
+
+    def __init__(self, n, device, new=None):
+        if not _is_int(n) or not 1 <= n <= MAX_ROWS:
+            raise ValueError("LiveRows: N must be an int in [1, %d], got %r" % (MAX_ROWS, n))
+        if new is None:
+            new = lambda name, shape, dt, fill, dev: (torch.empty(shape, dtype=dt, device=dev) if fill is None  # noqa: E731
+                                                      else torch.full(shape, fill, dtype=dt, device=dev))
+        self.n = n
+        self.rows = new("rows", (n,), torch.int32, None, device)
+        self.count = new("rows_count", (1,), torch.int32, 0, device)
+        self.scratch = new("rows_scratch", (live_rows_scratch_ints(n),), torch.int32, None, device)
+
+    @staticmethod
+    def nbytes(n):
+        """Bytes a LiveRows of n rows holds: rows, count and scratch."""
+        return 4 * (n + 1 + live_rows_scratch_ints(n))
+
+
+def live_rows(mask, out=None):
+    """mask: a contiguous bool or uint8 tensor [N] on the GPU, 1 <= N <= 2^20; a byte that is not zero is a live row.  Returns
+    the `LiveRows` of the rows whose byte is set, in ascending order (`gd_live_rows`, csrc/live_rows.hip).  out: a LiveRows of
+    the same N and device to be overwritten; then nothing is allocated.  Two launches on torch's current stream, no host
+    synchronisation, no atomics: equal masks give equal bytes.  `rows[count:]` is not written."""
+    who = "live_rows: "
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 \
+            or not mask.is_contiguous():
+        raise ValueError(who + "mask must be a contiguous bool or uint8 tensor of shape [N]")
+    n = int(mask.shape[0])
+    if not 1 <= n <= MAX_ROWS:
+        raise ValueError(who + "N must be in [1, %d], got %d" % (MAX_ROWS, n))
+    if mask.device.type != "cuda":
+        raise ValueError(who + "mask must be on the GPU (there is no host path), got %s" % mask.device)
+    if out is None:
+        out = LiveRows(n, mask.device)
+    elif not isinstance(out, LiveRows) or out.n != n or out.rows.device != mask.device:
+        raise ValueError(who + "out must be a LiveRows of N = %d on %s" % (n, mask.device))
+    with torch.cuda.device(mask.device):
+        stream = C.c_void_p(torch.cuda.current_stream(mask.device).cuda_stream)
+        _capi.check(_capi.lib().gd_live_rows(mask.data_ptr(), n, out.rows.data_ptr(), out.count.data_ptr(), out.scratch.data_ptr(),
+                                             stream), "gd_live_rows")
+    return out
+
+
 class DevicePolicy:
     def __init__(self, state_dict, max_agents=128, ego_width=6, *, device="cuda", act_func="tanh", vbd_in_obs=False,
                  dropout_rule=None):
@@ -237,10 +289,14 @@ class DevicePolicy:
 
     OUT_NAMES = ("actions", "logprob", "entropy", "value")
 
-    def __call__(self, obs, u=None, deterministic=False, out=None, logits_out=None):
+    def __call__(self, obs, u=None, deterministic=False, out=None, logits_out=None, rows=None):
         """obs [N, obs_width] float32, contiguous, on the device.  u [N] float32 in [0, 1) (required unless deterministic).
         Returns (actions int64 [N], logprob, entropy, value float32 [N]).  out: those four tensors of an earlier call, to be
-        overwritten (every byte is written); logits_out: [N, n_actions] float32 to receive the logits.  Three launches on
+        overwritten (every listed row is written: without rows= that is every byte); logits_out: [N, n_actions] float32 to
+        receive the logits.  rows: None for all N rows, or a `LiveRows` of this N (`live_rows(mask)`): the forward then runs on
+        the listed rows only (`gd_policy_forward_rows`), reads obs[r] and u[r] and writes index r of every output with the bits
+        the full forward gives that row; out= and logits_out keep their bytes at rows that are not listed, and with out=None
+        the fresh outputs are zero there.  The list's length stays on the device.  Three launches on
         torch's current stream, no host synchronisation; with out= and an N seen before, no allocation either, so the call can
         be captured in a graph.  With a dropout rule and `training`, the call consumes the rule's call index and advances
         it on the device.  The features and logits scratch belongs to the object (it grows with the largest N seen), so
@@ -251,7 +307,12 @@ class DevicePolicy:
         n = int(obs.shape[0])
         if not 1 <= n <= MAX_ROWS:
             raise ValueError("DevicePolicy: N must be in [1, %d], got %d" % (MAX_ROWS, n))
+        if rows is not None and (not isinstance(rows, LiveRows) or rows.n != n):
+            raise ValueError("DevicePolicy: rows must be a LiveRows of N = %d (live_rows(mask)), got %s"
+                             % (n, "one of N = %d" % rows.n if isinstance(rows, LiveRows) else type(rows).__name__))
         self._tensor("obs", obs, torch.float32, (n, self.obs_width))
+        if rows is not None and rows.rows.device != self.device:
+            raise ValueError("DevicePolicy: rows is on %s, the policy on %s" % (rows.rows.device, self.device))
         deterministic = bool(deterministic)
         if u is None:
             if not deterministic:
@@ -261,7 +322,8 @@ class DevicePolicy:
         f = torch.float32
         want = (((n,), torch.int64), ((n,), f), ((n,), f), ((n,), f))
         if out is None:
-            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in want)
+            make = torch.empty if rows is None else torch.zeros  # (rows that are not listed are not written)
+            out = tuple(make(shape, dtype=dt, device=self.device) for shape, dt in want)
         else:
             if not isinstance(out, (tuple, list)) or len(out) != 4:
                 raise ValueError("DevicePolicy: out must be the four tensors (actions, logprob, entropy, value)")
@@ -273,7 +335,12 @@ class DevicePolicy:
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             args = (obs.data_ptr(), None if u is None else u.data_ptr(), int(deterministic), out[0].data_ptr(), out[1].data_ptr(),
                     out[2].data_ptr(), out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(), stream)
-            if self.dropout_rule is not None and self.training:
+            masked = self.dropout_rule is not None and self.training
+            if rows is not None:
+                d = C.byref(self.dropout_rule.struct()) if masked else None
+                _capi.check(self._L.gd_policy_forward_rows(C.byref(p), d, *args[:-1], rows.rows.data_ptr(), rows.count.data_ptr(),
+                                                           stream), "gd_policy_forward_rows")
+            elif masked:
                 d = self.dropout_rule.struct()
                 _capi.check(self._L.gd_policy_forward_dropout(C.byref(p), C.byref(d), *args), "gd_policy_forward_dropout")
             else:

@@ -21,10 +21,14 @@ Rows are the simulator's learner rows, in `mask.nonzero()` order (default: the c
 and attaches its own [N, D] row buffer with only=True, so it OWNS the simulator's learner rows.  A simulator serves one of
 `DeviceLearnerEnv` / `ClosedLoopPPO` at a time; evaluation normally has its own simulator, on held-out scenes.  The forward is
 always the unmasked one (the reference's `load_policy` returns `policy.eval()`): a `DropoutRule` on the policy is neither
-consulted nor advanced.  It runs on all N rows every step: dead rows are not compacted away, their index is replaced by 0.
+consulted nor advanced.  By default it runs on all N rows every step and a dead row's index is replaced by 0;
+`run(compact=True)` puts the list of live rows in the loop instead (`gd_policy_rollout_compact`: per step `gd_live_rows` on
+`live`, then the forward on that list), so a step costs what its live rows cost.  Every result is the same bit for bit, except
+that `actions`, `logprob`, `entropy` and `value` of a dead row are those of its last live step, and the episode gains
+`live_count` [91].  It is opt-in.
 Iterations after every world is done (the reference's `break`) change no output; `steps` counts the iterations that exist.
 
-Not here: rendering / `sim_state_frames` and `center_on_ego`, `multi_policy_rollout.py`, compaction of dead rows, the
+Not here: rendering / `sim_state_frames` and `center_on_ego`, `multi_policy_rollout.py`, the
 delta_local table (8000 actions is beyond `DevicePolicy`'s 1024), the CSV / dataframe of `evaluate_policy` (`evaluate()`
 returns the columns as numpy arrays)."""
 import ctypes as C
@@ -130,7 +134,9 @@ class PolicyEpisode:
     `break` (a 0-d device tensor); any_active [92].  actions / logprob / entropy / value [N]: the last forward's outputs.
     With deterministic=False u [n_steps, N].  With record=True actions_idx [N, 91] int64 (-1 once the row is dead, and for
     iterations that do not exist), live_mask [N, 91] bool (live before step t) and agent_positions [W, A, 91, 2] (the
-    absolute position of every slot after step t)."""
+    absolute position of every slot after step t).  With compact=True live_count [91] int32: the rows live before step t, the
+    length of the list step t's forward ran on, and live_rows, the `LiveRows` the call used (the last step's list); actions /
+    logprob / entropy / value of a dead row are its last live step's."""
 
     def __init__(self, **arrays):
         self.__dict__.update(arrays)
@@ -188,9 +194,10 @@ class ClosedLoopPPO:
         return n
 
     @staticmethod
-    def nbytes(sim, policy, record=False, mask=None, stochastic=False):
+    def nbytes(sim, policy, record=False, mask=None, stochastic=False, compact=False):
         """What `run()` will allocate for `sim`, `policy` and `mask` (default: the controlled agents): N rows of `row_nbytes`,
-        W worlds of `world_nbytes`, any_active [92] int32 and the summary [8]; with stochastic the draws u [91, N].  The
+        W worlds of `world_nbytes`, any_active [92] int32 and the summary [8]; with stochastic the draws u [91, N]; with
+        compact the row list, its count and scratch (`LiveRows.nbytes(N)`) and live_count [91] int32.  The
         [N, D] row buffer is the constructor's, the blob and the features / logits scratch the policy's.  (Synchronises,
         for N.)"""
         _check_sim(sim)
@@ -203,6 +210,9 @@ class ClosedLoopPPO:
                  + (EPISODE_LEN + 1) * 4 + len(SUMMARY_NAMES) * 4)
         if stochastic:
             total += EPISODE_LEN * n * 4
+        if compact:
+            from .policy import LiveRows
+            total += LiveRows.nbytes(n) + EPISODE_LEN * 4
         return total
 
     def resample(self, scenes):
@@ -216,12 +226,14 @@ class ClosedLoopPPO:
         """Every array of a run is made here (fill None: need not be initialised)."""
         return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
 
-    def run(self, n_steps=EPISODE_LEN, deterministic=False, generator=None, record=False):
+    def run(self, n_steps=EPISODE_LEN, deterministic=False, generator=None, record=False, compact=False):
         """Reset every world, advance the log playback by init_steps, and run `n_steps` steps with the policy in the loop in
         ONE C call; returns the `PolicyEpisode`.  n_steps < 91 gives the prefix of the full episode.  deterministic=False (the
         reference's default): u [n_steps, N] is drawn from `generator` (a device torch.Generator, required) before the call,
         step t consumes u[t] under csrc/policy_rule.hpp's draw, and it is returned as `u`; deterministic=True takes the
-        first index of the largest logit.  record: also keep the per-step arrays.  No host synchronisation."""
+        first index of the largest logit.  record: also keep the per-step arrays.  compact: run every step's forward on the
+        list of the rows still live (see the module docstring); the episode then has live_count [91] int32, the length of step
+        t's list, 0 for t >= n_steps.  No host synchronisation."""
         _check_steps(n_steps)
         deterministic = bool(deterministic)
         if not deterministic and not isinstance(generator, torch.Generator):
@@ -254,26 +266,38 @@ class ClosedLoopPPO:
             out["agent_positions"] = new("agent_positions", (W, A, T, 2), torch.float32, 0)
             b.agent_positions = out["agent_positions"].data_ptr()
         p = pol._struct(n)  # (the policy's own scratch, grown to N by the policy's own rule)
+        if compact:
+            from .policy import LiveRows
+            out["live_rows"] = lr = LiveRows(n, dev, new=self._new)  # (kept with the episode: the call is still running)
+            out["live_count"] = new("live_count", (T,), torch.int32, 0)
+            r = _capi.GdPolicyRolloutRows()
+            r.rows, r.count, r.scratch = lr.rows.data_ptr(), lr.count.data_ptr(), lr.scratch.data_ptr()
+            r.live_count = out["live_count"].data_ptr()
         sim.reset(list(range(W)))
         if self.init_steps > 0:
             sim.advance_log_playback(self.init_steps)
         sim._bind_stream()
-        _capi.check(sim._L.gd_policy_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_policy_rollout")
+        if compact:
+            _capi.check(sim._L.gd_policy_rollout_compact(sim._h, C.byref(p), C.byref(b), C.byref(r), n_steps),
+                        "gd_policy_rollout_compact")
+        else:
+            _capi.check(sim._L.gd_policy_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_policy_rollout")
         sim._after()
         out["live"] = out["live"].view(torch.bool)
         out["world_active"] = out["world_active"].view(torch.bool)
         return PolicyEpisode(steps=any_active[:n_steps].sum(), any_active=any_active, summary_tensor=summary, **out)
 
-    def evaluate(self, scene_batches, n_steps=EPISODE_LEN, deterministic=False, generator=None):
+    def evaluate(self, scene_batches, n_steps=EPISODE_LEN, deterministic=False, generator=None, compact=False):
         """The loop of the reference's `evaluate_policy` (eval_utils.py:308-358): for every batch of scenes (each a list of W
         paths) `resample(batch)` and `run()`, the per-world results concatenated in batch order.  Returns a dict of the
         reference's column names -> float32 numpy arrays of one entry per world and batch, and "scene" -> the paths; all
-        results are read back together, in ONE host read at the end (`resample` synchronises once per batch, for the rows)."""
+        results are read back together, in ONE host read at the end (`resample` synchronises once per batch, for the rows).
+        compact: every `run()` with the list of live rows in the loop; the columns are the same."""
         scenes, cols = [], []
         for batch in scene_batches:
             batch = list(batch)
             self.resample(batch)
-            ep = self.run(n_steps=n_steps, deterministic=deterministic, generator=generator)
+            ep = self.run(n_steps=n_steps, deterministic=deterministic, generator=generator, compact=compact)
             scenes.extend(batch)
             cols.append(torch.stack([getattr(ep, src) for _, src in EVALUATE_COLUMNS]))
         if not cols:

@@ -852,6 +852,48 @@ typedef struct gd_policy_rollout_buffers {
  * its buffer's, n_actions different from the policy's, reserved != 0, a misaligned pointer, whatever gd_policy_forward
  * refuses.  GD_ERR_UNSUPPORTED for the State dynamics model (no discrete action space). */
 int gd_policy_rollout(gd_sim *sim, const gd_policy *policy, const gd_policy_rollout_buffers *buffers, int32_t n_steps);
+/* Live rows: the forward on a device-resident list of rows whose length only the device knows, so that a rollout stops paying
+ * for rows that are done.  Nothing here synchronises with the host, allocates, or uses an atomic.
+ *
+ * gd_live_rows: mask [n] bytes -> rows[0 .. *count) = the indices i with mask[i] != 0, ascending; rows[*count .. n) is not
+ * written; count is ONE int32 on the device.  scratch: one int32 per block of GD_LIVE_ROWS_BLOCK rows, that is
+ * (n + GD_LIVE_ROWS_BLOCK - 1) / GD_LIVE_ROWS_BLOCK of them (1024 cover every n).  Two launches on `stream`; equal input gives
+ * equal bytes.  GD_ERR_INVALID, before any launch: a null pointer, rows, count or scratch not 4-byte aligned, n outside
+ * [1, 2^20]. */
+#define GD_LIVE_ROWS_BLOCK 1024
+int gd_live_rows(const uint8_t *mask, int32_t n, int32_t *rows, int32_t *count, int32_t *scratch, void *stream);
+/* gd_policy_forward (d == NULL) or gd_policy_forward_dropout on the rows of a list: rows [N] int32 of which the first *count
+ * are read, count one int32 on the device (gd_live_rows writes both).  For a listed row r the call reads obs[r] and u[r] and
+ * writes actions[r], logprob[r], entropy[r], value[r] and logits_out[r], every bit what the full forward (the masked one at the
+ * same call index) writes for that row: no result of a row depends on which rows share its wave, and the dropout rule is keyed
+ * on r, not on the position in the list.  Rows that are not listed are NOT written, in any output.  The grids are sized for
+ * p->num_rows and every wave whose positions are past *count returns at once; p->features and p->logits are indexed by position
+ * and hold nothing specified afterwards.  With d the call index advances by exactly one per call, also when *count == 0.  An
+ * entry outside [0, N) is skipped and a count above N is read as N, for memory safety only; entries must be distinct (a row
+ * listed twice is written by two waves).  Three launches, no LDS.
+ * GD_ERR_INVALID, before any launch: whatever gd_policy_forward / gd_policy_forward_dropout refuse, a null or not 4-byte aligned
+ * rows or count. */
+int gd_policy_forward_rows(const gd_policy *p, const gd_dropout *d, const float *obs, const float *u, int32_t deterministic,
+                           int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out, const int32_t *rows,
+                           const int32_t *count, void *stream);
+/* gd_policy_rollout with the list in the loop.  Device pointers owned by the caller; N = buffers->n_rows. */
+typedef struct gd_policy_rollout_rows {
+    int32_t *rows;               /* [N] the list of the current step */
+    int32_t *count;              /* [1] its length */
+    int32_t *scratch;            /* gd_live_rows' scratch for n = N */
+    int32_t *live_count;         /* [91] the length of step t's list (the rows live before step t), or NULL; entries
+                                  * t >= n_steps are not written */
+    int32_t reserved;            /* 0 */
+} gd_policy_rollout_rows;
+/* For t in [0, n_steps): gd_live_rows on buffers->live (its second launch also stores live_count[t]), gd_policy_forward_rows
+ * on that list with u + t * N, then the action kernel, the step and the bookkeeping kernel of gd_policy_rollout, and its two
+ * kernels at the end: 2 launches per step more than gd_policy_rollout.  Every result gd_policy_rollout defines is the same,
+ * bit for bit; actions, logprob, entropy and value of a row hold the forward of the last step the row was live at (the action
+ * kernel reads the index of live rows only).  GD_ERR_INVALID / GD_ERR_UNSUPPORTED: whatever gd_policy_rollout refuses; a null
+ * rows argument, a null or not 4-byte aligned rows, count or scratch, a live_count that is not 4-byte aligned,
+ * reserved != 0. */
+int gd_policy_rollout_compact(gd_sim *sim, const gd_policy *policy, const gd_policy_rollout_buffers *buffers,
+                              const gd_policy_rollout_rows *rows, int32_t n_steps);
 /* The hidden states a linear probe reads (the reference's forward hooks, baselines/il/linear_probing.py:68-95): out [n][A][64]
  * float32, 16-byte aligned, receives tokens 0 .. A - 1 (the ego, then the partners) of the last_hidden_state of the tapped
  * block -- fusion_attn after its fusion_layers self layers, or ro_attn after its branch_layers more.  Per chunk gd_bc_forward's

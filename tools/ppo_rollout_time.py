@@ -14,7 +14,15 @@ synchronises).  Also timed, with events, on the same simulator and rows: 91 forw
 the simulator alone; what is left of (a) is the reset, the two kernels per step and the two at the end.  Reported too: whether
 (a) and (b) agree in every per-world result, the launches of (a) beside the simulator's own, what `nbytes` says run() allocates
 and what torch's allocator saw.
-tools/ppo_rollout_time.py [--worlds 1024] [--runs 5] [--out FILE]"""
+tools/ppo_rollout_time.py [--worlds 1024] [--runs 5] [--out FILE]
+
+--compact times something else, one JSON line again: run() and run(compact=True) -- the forward on the list of live rows
+(gd_policy_rollout_compact) -- in alternation, --runs each after a warm-up of either, with device events, at the same
+ppo_default workload (collision behaviour IGNORE) and at that workload under AgentRemoved, one simulator each.  Per workload:
+the two sets of times, whether every per-world result and per-row sum agrees, and the mean of live_count / N over the 91 steps
+(from a record=True run's live_mask, so that it can be measured without the compact call too).  --skip-compact leaves
+run(compact=True) out: the same file then runs on a commit that has no such call, for the yardstick.
+tools/ppo_rollout_time.py --compact [--skip-compact] [--worlds 1024] [--runs 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -84,6 +92,54 @@ def composition(sim, ev, pol, u):
     for k in ("goal_achieved", "collided", "off_road", "other"):
         r["frac_" + k] = r[k + "_count"] / controlled
     return r
+
+
+def compact_main(args):
+    """run() against run(compact=True) at ppo_default under IGNORE and under AgentRemoved."""
+    _, order, A = bench.split_workload(WORKLOAD)
+    scenes = bench.scenes_for(WORKLOAD, args.worlds, 0, agents=A)
+    res = dict(tool="tools/ppo_rollout_time.py --compact", workload=WORKLOAD, worlds=args.worlds, slots=A, steps=T, runs=args.runs,
+               source_stamp=bench.source_stamp(), compact_timed=not args.skip_compact, workloads={})
+    for name, behaviour in (("ignore", 2), ("agent_removed", 1)):
+        kw = dict(bench.params_for(WORKLOAD), collisionBehaviour=behaviour)
+        sim = bench.make_sim(scenes, kw, A, 0, knn_order=order)
+        pol = DevicePolicy.from_state_dict(PC.state_dict(11, 6, 91), max_agents=A, ego_width=6)
+        ev = ClosedLoopPPO(sim, pol)
+        N = ev.num_agents
+        seeded = lambda **k: ev.run(generator=torch.Generator(device="cuda").manual_seed(0), **k)  # noqa: E731
+        rec = seeded(record=True)
+        live = rec.live_mask.sum(0).float()  # [91]: the rows live before step t (0 for iterations that do not exist)
+        out = dict(rows=N, iterations=int(rec.steps), mean_live_fraction=float(live.mean()) / N,
+                   live_fraction_at=dict((str(t), float(live[t]) / N) for t in (0, 10, 30, 60, 90)), episode=rec.summary())
+        del rec
+        ep = seeded()
+        if not args.skip_compact:
+            epc = seeded(compact=True)
+        torch.cuda.synchronize()
+        a_ms, c_ms = [], []
+        for _ in range(args.runs):
+            ms, ep = event_ms(seeded)
+            a_ms.append(ms)
+            if not args.skip_compact:
+                ms, epc = event_ms(lambda: seeded(compact=True))
+                c_ms.append(ms)
+        out["run"] = summary(a_ms)
+        if not args.skip_compact:
+            out["compact"] = summary(c_ms)
+            out["compact_over_run"] = out["compact"]["median"] / out["run"]["median"]
+            out["mean_live_count_over_rows"] = float(epc.live_count.float().mean()) / N
+            out["same_results"] = all(
+                torch.equal(torch.nan_to_num(getattr(ep, k), nan=-1.0), torch.nan_to_num(getattr(epc, k), nan=-1.0))
+                for k in WORLD_RESULTS + ("episode_lengths", "goal_achieved", "collided", "off_road", "summary_tensor"))
+            out["launches_beside_the_steps"] = dict(run=T * (3 + 2) + 2, compact=T * (2 + 3 + 2) + 2)
+        res["workloads"][name] = out
+        sim.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
 
 
 def main(args):
@@ -158,6 +214,8 @@ if __name__ == "__main__":
     ap.add_argument("--worlds", type=int, default=1024)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--compact", action="store_true", help="time run() against run(compact=True) instead")
+    ap.add_argument("--skip-compact", action="store_true", help="with --compact: time run() alone (a commit without the call)")
     a = ap.parse_args()
     with torch.cuda.stream(torch.cuda.Stream()):  # (the step graph is captured on a stream of torch's own, as in bench.py)
-        main(a)
+        (compact_main if a.compact else main)(a)
