@@ -232,8 +232,9 @@ struct gd_sim {
             alloc_into(mine, n.cp_road, 2 * WA * GD_RANK_NCP);
             alloc_into(mine, n.cp_T, 2 * WA * GD_RANK_NCP);
             alloc_into(mine, n.cp_hdr, 2 * WA);
-            alloc_into(mine, n.rk_cp, WA * GD_RANK_NCP);
-            alloc_into(mine, n.rk_tl, WA);
+            alloc_into(mine, n.rk_cpf, WA * GD_RANK_NCP);
+            alloc_into(mine, n.rk_cpt, WA * GD_RANK_NCP);
+            alloc_into(mine, n.rk_rec, WA);
             alloc_into(mine, n.rk_hist, GD_RH_ALLOC);
             alloc_into(mine, n.rk_ticket, WA);
             alloc_into(mine, n.rk_order, WA);
@@ -1173,6 +1174,13 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         // XCD): few waves that take many turns each on the small worlds of a test
         d.rk_waves = 0;
         if (const char *e = std::getenv("GPUDRIVE_RANK_WAVES")) d.rk_waves = std::min(std::max((std::atoi(e) + 7) / 8 * 8, 8), GD_RANK_GRID);
+        // GPUDRIVE_RANK_SCAN_ROWS=1: k_knn_scan writes a checkpoint row for every ranked agent and workgroup b takes world b,
+        // as before the ranking read an agent's own checkpoints itself (A/B runs; the twin of tests/test_gpu_rank_setup.py)
+        d.rk_scan_rows = 0;
+        if (const char *e = std::getenv("GPUDRIVE_RANK_SCAN_ROWS")) d.rk_scan_rows = std::atoi(e) != 0 ? 1 : 0;
+        // where a list of the standard ranking is drawn from its cursor, the waves the device holds at a time empty it: those
+        // behind them (the launch has a wave per live agent, up to GD_RANK_GRID) leave without asking
+        d.rk_resident = std::max(gd::rank_resident_waves(A) / 8, 1);
         s->rk_possible = GD_MAP_OBS_AW == 32 && cfg->knn_order != GD_KNN_SET_ORDER &&
                          params->roadObservationAlgorithm == GD_ROADS_K_NEAREST && std::getenv("GPUDRIVE_NO_RANK_REPLAY") == nullptr;
 #ifdef GD_DIAG
@@ -2502,6 +2510,17 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
         if (hipMemcpy(&v, s->d.warm_count, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
             return fail(GD_ERR_DEVICE, "gd_stat: reading the warm-up counter failed");
         *out = static_cast<int64_t>(v);
+        return GD_OK;
+    }
+    if (s && out && which == 22) {  // checkpoint rows k_knn_scan wrote in the last selection (engine.hpp GD_RH_ROWS)
+        *out = 0;
+        if (s->rk_alloc) {
+            int32_t v = 0;
+            (void)hipStreamSynchronize(s->stream);
+            if (hipMemcpy(&v, s->d.rk_hist + GD_RH_ROWS, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(GD_ERR_DEVICE, "gd_stat: reading the row counter failed");
+            *out = v;
+        }
         return GD_OK;
     }
     if (s && out && which == 21) {  // bounds audit of the rank path (engine.hpp GD_RANK_AUDIT): violations since the buffers exist

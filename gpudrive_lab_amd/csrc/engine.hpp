@@ -18,6 +18,7 @@
 #define GD_RANK_CAP_LONG 2560   // candidates of an agent that the long-list instantiation of the ranking takes (map_obs_rank.hip)
 #define GD_RANK_KT_LONG 164     // its key-table row (CAP_LONG / 16 entries + the last, padded to 16 bytes)
 #define GD_RH_LONG 537          // rk_hist: agents on the long list in this selection
+#define GD_RH_ROWS 538          // rk_hist: checkpoint rows k_knn_scan wrote for the ranked agents of the last selection (gd_stat 22)
 // rk_hist: the cursors k_knn_rank's waves draw their agents from (atomicAdd), one per XCD list, a 128-byte line each (eight
 // XCDs add to eight of them at the same time); zero between selections (k_knn_order, rebuild)
 #define GD_RH_CURSOR 544
@@ -36,6 +37,7 @@
 #else
 #define GD_RH_ALLOC GD_RH_SIZE
 #endif
+#define GD_RK_REC_ROW (1 << 16)  // rk_rec.z: the agent's checkpoints are the row in rk_cpf / rk_cpt (a donor's, bounded afresh, GPUDRIVE_RANK_SCAN_ROWS)
 #define GD_RANK_NCH 320  // 32-road words of a world's road bitmap (k_knn_finish): kMaxRoadEntityCount = 10,000
 #define GD_RANK_SPL 256  // sorted slots whose road index k_knn_rank hands on: the K elements the heap ends with have the K smallest
                          // keys, i.e. fewer than K candidates below them and at most 31 equal ones before them: slot < K + 31
@@ -198,14 +200,18 @@ struct DevSim {
     float *rk_kt;          // [W][A][GD_RANK_KT] key at sorted slot 16 j (16 j < n), then the largest key at j = ceil(n / 16)
     uint32_t *rk_heap;     // [W][A][GD_RANK_HEAP_DW] the replayed heap array as rank pairs
     uint16_t *rk_cpe;      // [W][A][NCP] rank on top of the heap at every checkpoint of this selection
-    int32_t *rk_hist;      // [GD_RH_ALLOC] replay order: 256 bin counts, [256..511] unused (-DGD_CLOCKS: k_knn_replay's phase clocks), the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT); [537] GD_RH_LONG; from GD_RH_CURSOR on: k_knn_rank's cursors
+    int32_t *rk_hist;      // [GD_RH_ALLOC] replay order: 256 bin counts, [256..511] unused (-DGD_CLOCKS: k_knn_replay's phase clocks), the number of agents on the rank path, selections so far; [514..526] counters of developer builds; [528..535] entries of rk_list; [536] bounds audit (GD_RANK_AUDIT); [537] GD_RH_LONG; [538] checkpoint rows written (GD_RH_ROWS); from GD_RH_CURSOR on: k_knn_rank's cursors
     int rk_waves;          // workgroups of the standard ranking launch (GPUDRIVE_RANK_WAVES, a multiple of 8); 0: one per live agent up to GD_RANK_GRID
     int32_t *rk_ticket;    // [W][A] bin << 20 | place inside the bin (bit 30: fell back after taking it); -1 = not on the rank path this step; < -1: why
     int32_t *rk_order;     // [W][A] agents on the rank path, most candidates first
     int32_t *rk_list;      // [8][W][A] agents on the rank path, one list per XCD that scanned them (counts: rk_hist[528..535])
-    uint2 *rk_cp;          // [W][A][NCP] the checkpoints that bound this selection's candidates: (first road, running maximum; threshold
-                           // bits), entries behind the agent's last one (0xffffffff, +inf) (k_knn_scan -> k_knn_rank; rank_cand.hpp)
-    float *rk_tl;          // [W][A] the last K-th key of the checkpoint set in use (scales the ranking buckets)
+    uint16_t *rk_cpf;      // [W][A][NCP] the checkpoint rows k_knn_scan makes for the agents that are not bounded by their own (rk_rec):
+    float *rk_cpt;         // first road (running maximum) and threshold of the agent's checkpoints (k_knn_scan -> k_knn_rank; rank_cand.hpp)
+    float4 *rk_rec;        // [W][A] k_knn_scan's record for k_knn_rank.  An agent bounded by its own checkpoints has no row there --
+                           // the ranking wave makes it from cp_road / cp_T of `set` itself: (move, margin, checkpoints | set << 8, -).
+                           // With a row: (move, the last K-th key of the checkpoints in use: scales the ranking buckets, GD_RK_REC_ROW, -)
+    int rk_scan_rows;      // GPUDRIVE_RANK_SCAN_ROWS=1: k_knn_scan writes every agent's row and takes world b in workgroup b (A/B runs, twin tests)
+    int rk_resident;       // waves of the standard ranking that the device holds at a time per XCD list (occupancy query at creation)
     const float4 *road_bbox;  // [W] (min x, min y, max x, max y) over the world's roads
     const float *road_rbmax;  // [W] the largest bounding radius (half diagonal) of a road of the world
     int32_t *rk_n;         // [W][A] candidates | in-radius candidates << 16; 0 = not on the rank path this step; 1 << 30 = too far from every road
@@ -233,6 +239,7 @@ struct DevSim {
 void launch_kernel(const DevSim &d, hipStream_t st, int which, bool move);
 void launch_map_obs(const DevSim &d, hipStream_t st, bool move);  // map_obs.hip
 void launch_map_obs_rank(const DevSim &d, hipStream_t st);  // map_obs_rank.hip
+int rank_resident_waves(int A);  // map_obs_rank.hip: workgroups of the standard ranking that fit the device at a time (GD_RANK_GRID: the query failed)
 void launch_map_obs_linear(const DevSim &d, hipStream_t st, bool move);  // map_obs_linear.hip
 void launch_bev(const DevSim &d, hipStream_t st);      // bev_lidar.hip
 void launch_lidar(const DevSim &d, hipStream_t st);    // bev_lidar.hip

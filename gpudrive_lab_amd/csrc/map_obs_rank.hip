@@ -177,15 +177,23 @@ __device__ __forceinline__ bool rank_lt(unsigned int a, unsigned int b, unsigned
 // k_knn_scan: the SET-UP of the selection, one lane per agent, one workgroup (4 waves) per 64 agent slots of a world: which
 // agents take the rank path, and the checkpoints that bound each one's candidates -- first road and threshold of the cheap
 // form |p - e|^2 < bound * margin (the margin covers rounding and the squared norm of the stored quaternion, like k_map_obs's
-// scan) -- from its previous selection, a neighbour's, or made afresh.  The row of checkpoints is what it hands to
-// k_knn_rank (rk_cp, 320 B per agent), which finds the candidates itself (rank_cand.hpp): this kernel used to test every road
-// of the world against every agent and hand over 1280 B of candidate bits.
+// scan) -- from its previous selection, a neighbour's, or made afresh.  What it hands to k_knn_rank, which finds the candidates
+// itself (rank_cand.hpp), is a 16-byte record per agent (rk_rec) and, only for an agent that borrows a neighbour's checkpoints or
+// is bounded afresh, the row of checkpoints (rk_cpf / rk_cpt, 240 B).  An agent bounded by its own checkpoints -- every agent of
+// an ordinary step -- has its row made by the wave that ranks it, from the checkpoints where they lie: copying them here, one
+// lane per agent and one entry per trip, was a third of this kernel, writing the rows out and reading them back another.
+// Which XCD's list a workgroup fills is dealt (rank_cand.hpp deal_block).
 // ------------------------------------------------------------------------------------------------------------------
 template <int A_T>
 __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     constexpr int HALVES = A_T / 64;
     const int w = blockIdx.x / HALVES, a0 = (blockIdx.x % HALVES) * 64;
+    // which XCD's list this workgroup appends to: dealt, so that every list gets the same mix of worlds when scenes repeat with a
+    // period (rank_cand.hpp deal_block, deal_list).  The workgroup itself stays on the XCD that the step's other kernels keep its world on
+    // (workgroup b on XCD b % 8: the pose planes and checkpoint headers it reads are in that L2)
+    const int xl = d.rk_scan_rows ? (int)(blockIdx.x & 7) : rank_cand::deal_list((int)blockIdx.x, (int)gridDim.x);
+    if (blockIdx.x == 0 && threadIdx.x == 0) d.rk_hist[GD_RH_ROWS] = 0;  // k_knn_order counts this selection's rows (gd_stat 22)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int n = d.shape[w * 2 + 0];
     if (a0 >= n) return;
@@ -198,7 +206,8 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
 
     __shared__ unsigned short s_first[NCP][64];  // checkpoint q of lane l: first road it holds for (running maximum: rank_cand.hpp) ...
     __shared__ float s_thr[NCP][64];             // ... and the threshold it gives
-    __shared__ int s_ncp[64];                    // checkpoints of lane l; 0: the agent is not on the rank path
+    __shared__ int s_ncp[64];                    // checkpoints of lane l; 0: the agent is not on the rank path, or needs no row:
+                                                 // it is bounded by its own checkpoints, which its ranking wave reads where they are
     __shared__ unsigned int s_needy[2];          // the agents to be bounded afresh (bit per lane), as the first wave saw them
     __shared__ float4 s_hdr[64];                 // where and how many checkpoints lane l's previous selection recorded
     __shared__ float s_bx[64], s_by[64], s_bm[64];  // position and margin of lane l's agent (for the waves that bound it afresh)
@@ -207,6 +216,8 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     float ex = 0.f, ey = 0.f;
     if (live) { ex = d.px[i]; ey = d.py[i]; }
     unsigned long long ranked = 0ull;  // wave 0: its lanes whose agents take the rank path ...
+    bool own_cp = false;               // ... and of them those that get no row (s_ncp above)
+    bool listed = false;               // this lane's agent is one of `ranked`
     int list_base = 0;                 // ... and where they go in rk_list
     if (wave == 0) {
         int ncp = 0;
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
                 // prefix of the roads is a function of the position alone, 1-Lipschitz in it, whoever recorded it.  Without
                 // that every road of the world was a candidate for such an agent: beyond the buffers in a world of 10,000
                 // roads (the whole group of 32 to the fallback, a 3 ms step), the longest replay of the launch in smaller ones.
-                if (move > 6.f) {
+                if (move > rank_cand::CP_MOVE_MAX) {
                     float best = move;
                     int donor = -1;
                     for (int j = 0; j < 64; j++) {
@@ -274,35 +285,42 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
                     ncp = 0;
                     reason = bypass ? -5 : -2;  // -2: a world below rk_min_roads (or without K roads)
                     d.rk_fallback[i / 32] = 1;
-                } else if (n_cp <= 0 || move > 6.f) {
+                } else if (n_cp <= 0 || move > rank_cand::CP_MOVE_MAX) {
                     // No usable bound -- the first selection after the worlds were built, a logged agent that reappears
                     // anywhere on the map (src/sim.cpp:370-382) with nobody near: the waves of this workgroup bound it afresh
                     // below (`bound_afresh`).  Round 3 sent such an agent's group to the history replay on keys.
                     ncp = -1;
                     s_bx[lane] = ex; s_by[lane] = ey; s_bm[lane] = margin;
-                } else {
+                } else if (src == i && !d.rk_scan_rows) {
+                    // the common case: bounded by its own checkpoints (of the previous selection or the episode's first), which
+                    // nobody but the wave that ranks this agent writes during the ranking launch, and that one only after it
+                    // has read them (rank_fetch).  The row is a function of those two arrays, `move` and `margin`: lane q of
+                    // the ranking wave makes entry q (rank_cand.hpp cp_threshold, the running maximum as a wave scan)
                     ncp = n_cp;
+                    own_cp = true;
+                    d.rk_rec[i] = make_float4(move, margin, __int_as_float(n_cp | set << 8), 0.f);
+                } else {
+                    // a donor's checkpoints (the wave that ranks the donor overwrites them during the launch), or every row
+                    // (GPUDRIVE_RANK_SCAN_ROWS): copied into the agent's row here
+                    ncp = n_cp;
+                    float t = 1.f;
                     const unsigned short *cr = d.cp_road + ((size_t)set * WA + src) * NCP;
                     const float *ct = d.cp_T + ((size_t)set * WA + src) * NCP;
-                    float t = 1.f;
                     unsigned int fmax = 0u;  // (rank_cand.hpp: with the running maximum "in force" is a count of entries)
                     for (int q = 0; q < ncp; q++) {
                         t = ct[q];
-                        const float reach = sqrtf(t) * 1.0001f + move * 1.0001f + 1e-3f;
-                        float thr = reach * reach * 1.0001f * margin;
-                        if (!(thr >= 0.f)) thr = __builtin_inff();  // an unusable entry bounds nothing
                         fmax = rank_cand::running_max(fmax, cr[q]);
                         s_first[q][lane] = (unsigned short)fmax;
-                        s_thr[q][lane] = thr;
+                        s_thr[q][lane] = rank_cand::cp_threshold(t, move, margin);  // (an unusable entry bounds nothing)
                     }
-                    d.rk_tl[i] = t;  // the last K-th key: scales the ranking buckets
+                    d.rk_rec[i] = make_float4(move, t, __int_as_float(n_cp | GD_RK_REC_ROW), 0.f);  // t: the last K-th key, scales the ranking buckets
                 }
             }
             d.rk_n[i] = state;
             d.rk_ticket[i] = reason;  // k_knn_rank takes a ticket (>= 0) once the agent's ranks exist; < -1: why it fell back
             if (state == RK_FAR) ncp = 0;
         }
-        s_ncp[lane] = ncp;
+        s_ncp[lane] = own_cp ? 0 : ncp;
         {
             // published once, before the barrier: the waves below must all see ONE mask (a wave that finishes an agent rewrites
             // its s_ncp entry, and a late reader of s_ncp would deal the turns differently and skip the barrier behind the loop)
@@ -312,12 +330,13 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
         if (ncp < 0) ncp = 1;  // (bounded afresh below: on the rank path like the others)
         // the agents on the rank path, as a list: k_knn_rank's waves share THEM out, not the live agents (on the Waymo tiles
         // five agents in six are parked out of reach of every road, and a wave that drew three of the others set the pace).
-        // One list per XCD (workgroup b runs on XCD b % 8; k_knn_rank's waves take the list of their own XCD, so an agent's
+        // One list per XCD (dealt: `xl` above; k_knn_rank's waves take the list of their own XCD, so an agent's
         // road points are gathered into the L2 that scanned them, and eight counters are asked instead of one: a thousand
         // workgroups adding to one address at once cost the kernel 10 us)
         ranked = __ballot(ncp > 0);
+        listed = ncp > 0;
         // their place in the list: asked for now, needed at the very end (a trip to the L2 and back behind the work below)
-        if (ranked != 0ull && lane == 0) list_base = atomicAdd(&d.rk_hist[528 + (blockIdx.x & 7)], __popcll(ranked));
+        if (ranked != 0ull && lane == 0) list_base = atomicAdd(&d.rk_hist[528 + xl], __popcll(ranked));
     }
     __syncthreads();
     // ---- agents without a usable bound: one wave each streams the world's roads once, in scan order, and keeps a histogram of
@@ -378,30 +397,32 @@ __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
                 }
                 if (lane == 0) {
                     s_ncp[al] = q;
-                    d.rk_tl[(size_t)w * A_T + a0 + al] = tlast < 1e30f ? tlast : 1.f;  // scales the ranking buckets
+                    // (the last K-th key scales the ranking buckets)
+                    d.rk_rec[(size_t)w * A_T + a0 + al] = make_float4(0.f, tlast < 1e30f ? tlast : 1.f, __int_as_float(q | GD_RK_REC_ROW), 0.f);
                 }
             }
             __syncthreads();
         }
     }
+    if (wave == 0 && ranked != 0ull) {
+        list_base = __builtin_amdgcn_readfirstlane(list_base);
+        if (listed)
+            d.rk_list[(size_t)xl * WA + audited(d, list_base + __popcll(ranked & ((1ull << lane) - 1ull)), (int)WA)] = (int)i;
+    }
     const int ncp = s_ncp[lane];
-    if (__syncthreads_or(ncp > 0 ? 1 : 0) == 0) return;  // no agent of this workgroup is on the rank path (far, fallback, bypass)
+    if (__syncthreads_or(ncp > 0 ? 1 : 0) == 0) return;  // no agent of this workgroup needs a row (far, fallback, bypass, its own checkpoints)
     // The checkpoint rows of the agents on the rank path, agent-major (k_knn_rank reads an agent's row as one coalesced
     // load), whole rows: the entries behind an agent's last checkpoint are never in force
     {
-        uint2 *rows = d.rk_cp + ((size_t)w * A_T + a0) * NCP;
+        unsigned short *rowf = d.rk_cpf + ((size_t)w * A_T + a0) * NCP;
+        float *rowt = d.rk_cpt + ((size_t)w * A_T + a0) * NCP;
         for (int e = tid; e < 64 * NCP; e += 256) {
             const int ag = e / NCP, q = e - ag * NCP;
-            const int n_ag = s_ncp[ag];
-            if (n_ag > 0)
-                rows[e] = q < n_ag ? make_uint2((unsigned int)s_first[q][ag], __float_as_uint(s_thr[q][ag]))
-                                   : make_uint2(rank_cand::NO_CP, __float_as_uint(__builtin_inff()));
+            if (q < s_ncp[ag]) {
+                rowf[e] = s_first[q][ag];
+                rowt[e] = s_thr[q][ag];
+            }
         }
-    }
-    if (wave == 0 && ranked != 0ull) {
-        list_base = __builtin_amdgcn_readfirstlane(list_base);
-        if (ncp > 0)
-            d.rk_list[(size_t)(blockIdx.x & 7) * WA + audited(d, list_base + __popcll(ranked & ((1ull << lane) - 1ull)), (int)WA)] = (int)i;
     }
 }
 
@@ -435,7 +456,7 @@ static_assert(sizeof(RankLds<CAP>) <= 10240 && sizeof(RankLds<CAP_LONG>) <= 2048
 constexpr int LSTN = (GD_MAX_ROAD_ENTITIES + GD_LIN_BLK - 1) / GD_LIN_BLK + 15;  // blocks of the largest world, rounded to a multiple of 4 below
 constexpr int LSTN4 = (LSTN + 3) & ~3;
 static_assert(LSTN4 <= 1024 && NCP < 64 && rank_cand::CHUNK % GD_LIN_BLK == 0 && 64 % GD_LIN_BLK == 0, "block and count share 16 bits; a block inside one chunk; whole blocks per pass");
-constexpr size_t CAND_TABLES = LSTN4 * sizeof(unsigned short) + (NCP + 1) * sizeof(float);
+constexpr size_t CAND_TABLES = LSTN4 * sizeof(unsigned short) + (NCP + 2) * sizeof(float);  // (+ the last K-th key behind the thresholds)
 static_assert(CAND_TABLES <= sizeof(RankLds<CAP>::cnt2) && CAND_TABLES <= sizeof(RankLds<CAP_LONG>::cnt2), "the tables fit the idle counters of both instantiations");
 // the cull's table of checkpoints per 32-road chunk (rank_cand.hpp cp_table): entries per lane in the largest world; the scatter's
 // targets (u32) and the table itself (count, reach) side by side in the candidate keys' buffer
@@ -446,16 +467,23 @@ static_assert(64 * CP_EPL * (sizeof(unsigned int) + sizeof(uint2)) <= sizeof(flo
 // wave is being ranked (the fetches are a chain of dependent loads, several microseconds end to end).
 struct RankIn {
     int i, state, r0, R, b0, li;  // li: the entry of the list this agent came from (a long list's scratch rows go by it)
-    float ex, ey, iw, iz, t_last;
-    unsigned int cfirst;  // lane q: checkpoint q of the agent's row (k_knn_scan's rk_cp); lanes from NCP on: never in force
+    float ex, ey, iw, iz;
+    // lane q below the number of checkpoints: checkpoint q of the agent; the other lanes: never in force.  With a row (rec_pack &
+    // GD_RK_REC_ROW): the entry of k_knn_scan's row, first road (running maximum) and threshold.  Without: the agent's own
+    // cp_road / cp_T entry as recorded; rank_agent makes the row's entry of it (rec_move, the margin in rec_y)
+    unsigned int cfirst;
     float cthr;
+    // k_knn_scan's record (engine.hpp rk_rec): how far the agent is from where its checkpoints were recorded; the margin (no row)
+    // or the last K-th key of the row; checkpoints | set << 8 (no row) or checkpoints | GD_RK_REC_ROW
+    float rec_move, rec_y;
+    int rec_pack;
 };
 // A value at a wave-uniform address that this kernel does not change, read through the scalar cache.  As vector loads the
 // chain list -> agent -> state / pose waited, at each link, for every store the wave had issued for the previous agent
 // (vector memory operations are counted in order): a fifth of the kernel.
 // INVARIANT (nothing enforces it but the call sites below): the scalar cache is not coherent with this kernel's own vector
 // stores, so an address read through here must never be read AFTER any wave of the same launch has written it.  What is
-// read this way: arrays written by EARLIER kernels only (rk_list, rk_hist[528..], rk_tl, road_off, blk_off, the pose planes: the
+// read this way: arrays written by EARLIER kernels only (rk_list, rk_hist[528..], rk_rec, road_off, blk_off, the pose planes: the
 // scalar cache is invalidated at every kernel boundary), and rk_n[i] -- which this kernel does rewrite, but only the wave
 // that ranks agent i writes rk_n[i], and it reads it (rank_fetch) before it writes it (end of rank_agent); a cache line
 // shared with another agent's already rewritten entry may be stale for THAT entry, which this wave never looks at.
@@ -474,12 +502,24 @@ __device__ __forceinline__ RankIn rank_fetch(const DevSim &d, const int *list, i
     in.R = uniform_load(d.road_off + w + 1) - in.r0;
     in.ex = uniform_load(d.px + in.i); in.ey = uniform_load(d.py + in.i);
     in.iw = uniform_load(d.qw + in.i); in.iz = -uniform_load(d.qz + in.i);  // the INVERSE rotation
-    in.t_last = uniform_load(d.rk_tl + in.i);
     in.b0 = uniform_load(d.blk_off + w);
-    uint2 cp = make_uint2(rank_cand::NO_CP, __float_as_uint(__builtin_inff()));
-    if (in.state == 1 && lane < NCP) cp = stream_load(d.rk_cp + (size_t)in.i * NCP + (unsigned int)lane);  // agent-major: one coalesced read
-    in.cfirst = cp.x;
-    in.cthr = __uint_as_float(cp.y);
+    // (k_knn_scan's record: written by the earlier kernel only, so the invariant above holds)
+    const float *rec = reinterpret_cast<const float *>(d.rk_rec + in.i);
+    in.rec_move = uniform_load(rec); in.rec_y = uniform_load(rec + 1); in.rec_pack = __float_as_int(uniform_load(rec + 2));
+    // Lane q reads entry q of the agent's checkpoints, two coalesced loads from wave-uniform bases: of the row k_knn_scan wrote
+    // (rk_cpf / rk_cpt), or of the agent's own checkpoints where the previous selection (set 0) or the episode's first (set 1)
+    // left them.  Set 0's first roads are rewritten during this launch, by this wave alone, in the ranking of this agent:
+    // behind this read.  (Other agents' rows of cp_road must not be read here: their waves may have rewritten them.)
+    const bool has_row = (in.rec_pack & GD_RK_REC_ROW) != 0;
+    const size_t own = ((size_t)((in.rec_pack >> 8) & 1) * d.W * A_T + in.i) * NCP, row = (size_t)in.i * NCP;
+    const unsigned short *pf = has_row ? d.rk_cpf + row : d.cp_road + own;
+    const float *pt = has_row ? d.rk_cpt + row : d.cp_T + own;
+    in.cfirst = rank_cand::NO_CP;
+    in.cthr = __builtin_inff();
+    if (in.state == 1 && lane < min(in.rec_pack & 0xff, NCP)) {
+        in.cfirst = pf[(unsigned int)lane];
+        in.cthr = pt[(unsigned int)lane];
+    }
     return in;
 }
 
@@ -534,10 +574,22 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     // them).  The table lives in the candidate buffer, which nothing else uses until the scan stores its first candidate. ----
     unsigned short *const lst = reinterpret_cast<unsigned short *>(L.cnt2);
     float *const tthr = reinterpret_cast<float *>(L.cnt2) + LSTN4 / 2;  // threshold by checkpoints at or before: 0 = unbounded
-    const unsigned int cfirst = in.cfirst;
-    if (lane < NCP) tthr[lane + 1] = in.cthr;
+    unsigned int cfirst = in.cfirst;
+    float cthr = in.cthr, t_last_in = unif(in.rec_y);  // (with a row: the last K-th key)
+    if (!(uni(in.rec_pack) & GD_RK_REC_ROW)) {
+        // the agent's own checkpoints as recorded (rank_fetch): the row k_knn_scan would have made of them -- the threshold by
+        // the shared rule, the first road as the running maximum over the entries before it, nothing behind the last one
+        const int n_own = min(uni(in.rec_pack) & 0xff, NCP);  // 1 .. NCP
+        const bool have = lane < n_own;
+        t_last_in = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cthr), n_own - 1));  // the last K-th key
+        const unsigned int fmax = (unsigned int)wave_incl_max_nonneg(have ? (int)cfirst : 0);  // (16-bit road indices)
+        cthr = have ? rank_cand::cp_threshold(cthr, unif(in.rec_move), unif(in.rec_y)) : __builtin_inff();
+        cfirst = have ? fmax : rank_cand::NO_CP;
+    }
+    // (behind the thresholds: the last K-th key, kept here for the refill, not in a register)
+    if (lane <= NCP) tthr[lane + 1] = lane < NCP ? cthr : t_last_in;
     if (lane == 63) tthr[0] = __builtin_inff();
-    const float creach = rank_cand::block_reach(in.cthr);  // (lanes from NCP on: +inf, which is also what "no checkpoint" reads)
+    const float creach = rank_cand::block_reach(cthr);  // (lanes from NCP on: +inf, which is also what "no checkpoint" reads)
     const int nblk = (R + GD_LIN_BLK - 1) / GD_LIN_BLK;
     const int nch = rank_cand::chunks_of(R), epl = (nch + 63) >> 6;  // entries per lane: wave-uniform, at most CP_EPL
     unsigned int *const tmax = reinterpret_cast<unsigned int *>(L.c.ckey);  // [64 * CP_EPL] the scatter's targets
@@ -761,7 +813,7 @@ __device__ __forceinline__ void rank_agent(const DevSim &d, const RankIn &in, in
     const float kmax = d.radius_key_max;
     int ci[NG];
     float key[NG];
-    const float t_last = unif(in.t_last);
+    const float t_last = unif(tthr[NCP + 1]);
     float split = (t_last > 0.f && t_last < 1e30f) ? t_last * 1.5f : 1.f;
     int nle = 0, nlow = 0;  // candidates inside the radius / below `split` (second count in the upper half)
     float kmax_seen = 0.f, kmin_seen = __builtin_inff();
@@ -1065,11 +1117,17 @@ __global__ __launch_bounds__(64, CAP_T > CAP ? 2 : 4) void k_knn_rank(DevSim d) 
     // (engine.hpp GD_RH_WAVES; tools/rank_waves.py takes the ends from the earliest start of the launch on the wave's XCD)
     int turns = 0;
     if (!LONG && threadIdx.x == 0) {
-        d.rk_hist[GD_RH_WAVES + blockIdx.x] = (int)__builtin_amdgcn_s_memrealtime();
+        const int now = (int)__builtin_amdgcn_s_memrealtime();
+        d.rk_hist[GD_RH_WAVES + blockIdx.x] = now;
+        d.rk_hist[GD_RH_WAVES + GD_RANK_GRID + blockIdx.x] = now;  // (a wave that leaves at once: no time, no agents)
         d.rk_hist[GD_RH_WAVES + 2 * GD_RANK_GRID + blockIdx.x] = 0;
     }
 #endif
     if (fixed && mine >= count) return;
+    // A drawn list is emptied by the waves the device holds at a time (d.rk_resident per list: the occupancy of this kernel, asked
+    // when the simulator was created).  The launch has a wave per live agent, twice as many at 1024 x 64: those behind the
+    // resident ones used to start when the first left, ask the cursor once each and find the list drawn empty.
+    if (!fixed && mine >= d.rk_resident) return;
     int t = fixed ? mine : __builtin_amdgcn_readfirstlane(rank_draw(cursor, threadIdx.x));
     RankIn cur = rank_fetch<A_T>(d, list, t, count, threadIdx.x);
     PhaseClock clk;
@@ -1170,6 +1228,12 @@ __global__ __launch_bounds__(256) void k_knn_order(DevSim d) {
     if (t >= d.live_count) return;
     const int i = d.live_list[t];
     const int ticket = d.rk_ticket[i];
+    {
+        // rows k_knn_scan wrote for ranked agents (gd_stat 22): none in a selection where every agent kept its own bound, so no
+        // wave adds then (k_knn_scan zeroed the count; a thousand workgroups adding to one address cost it 10 us)
+        const unsigned long long rows = __ballot(ticket >= 0 && (__float_as_int(d.rk_rec[i].z) & GD_RK_REC_ROW) != 0);
+        if (rows != 0ull && (tl & 63) == 0) atomicAdd(&d.rk_hist[GD_RH_ROWS], __popcll(rows));
+    }
     if (ticket < 0) return;  // not on the rank path
     d.rk_order[audited(d, s_start[(ticket >> 20) & 255] + (ticket & 0xfffff), d.W * d.A)] = i;
 }
@@ -1583,6 +1647,18 @@ __global__ __launch_bounds__(256) void k_knn_finish(DevSim d) {
 #ifndef GD_RANK_LONG_GRID
 #define GD_RANK_LONG_GRID 2048  // (an empty launch costs 5 us whatever its size; 256 waves ranked the long lists of the unreduced Waymo tiles in 614 us, 2048 in 157)
 #endif
+int rank_resident_waves(int A) {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    const hipError_t e = A == 64 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_knn_rank<64, CAP>, 64, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_knn_rank<128, CAP>, 64, 0);
+    if (e != hipSuccess || hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return GD_RANK_GRID;  // nothing leaves early: the launch as it was
+    }
+    return std::max(per_cu, 1) * std::max(prop.multiProcessorCount, 1);
+}
+
 void launch_map_obs_rank(const DevSim &d, hipStream_t st) {
     if (d.live_count == 0) return;
     // the long-list ranking: persistent waves (eight per CU fit) over however many agents the standard launch passed on (none:

@@ -1,6 +1,7 @@
 // The rank path's candidate set (map_obs_rank.hip k_knn_scan -> k_knn_rank) as plain C++: the decisions that the kernel and
 // a host program share (tests/rank_cand_model.cpp runs the cull + in-order scan below against a plain loop over every road;
-// tests/rank_cp_table_model.cpp the cull's table of checkpoints per chunk, (b') below, against the counts of (b)).
+// tests/rank_cp_table_model.cpp the cull's table of checkpoints per chunk, (b') below, against the counts of (b);
+// tests/rank_setup_model.cpp the row made of an agent's own checkpoints, (b''), and the deal of worlds to workgroups, (d)).
 //
 // An agent's candidates are roads 0..K-1 plus every later road r < R whose cheap squared distance is below the threshold of
 // the CHECKPOINT in force for r.  k_knn_scan leaves a row of checkpoints per agent: first[q] (a multiple of 32) and thr[q];
@@ -65,6 +66,37 @@ GD_RC_FN int cp_count(const unsigned int *first_max, int n, int base) {
     return c;
 }
 GD_RC_FN int chunk_base_of_block(int b, int blk) { return (b * blk) & ~(CHUNK - 1); }
+
+// (b'') a checkpoint's threshold: `t` is the K-th key a previous selection recorded at the checkpoint, `move` how far the agent
+// is from where it was recorded (the K-th distance over a prefix of the roads is 1-Lipschitz in the position), `margin` covers
+// rounding and the squared norm of the stored quaternion.  An unusable entry (NaN, a negative key) bounds nothing.  k_knn_scan
+// (the rows it writes) and k_knn_rank (the rows it makes of the agent's own checkpoints) call this text, both built with
+// -ffp-contract=off: the same bits.
+GD_RC_FN float cp_threshold(float t, float move, float margin) {
+    const float reach = sqrtf(t) * 1.0001f + move * 1.0001f + 1e-3f;
+    const float thr = reach * reach * 1.0001f * margin;
+    return thr >= 0.f ? thr : __builtin_inff();
+}
+constexpr float CP_MOVE_MAX = 6.f;  // beyond it an agent's own checkpoints are no use (k_knn_scan: a donor's, or bounded afresh)
+
+// (d) which world a workgroup of k_knn_scan takes.  Workgroup b runs on XCD b % 8 and appends its agents to that XCD's list, so
+// with the identity XCD x ranks the worlds x, x + 8, ..: when the scenes are tiled with a period that shares a factor with 8 (the
+// bench's eight scenes, a loader that cycles through its files) one XCD gets every copy of the dearest scene and the ranking
+// lasts as long as that XCD.  The deal rotates the eight blocks of every aligned group of 8 among themselves, group g by
+// r(g) = g + g / 8 + g / 64 (mod 8): a bijection of [0, grid) that maps every aligned group onto itself -- a world still goes
+// to ONE list -- and is the identity on a last partial group.
+GD_RC_FN int deal_rotation(int g) { return (g + (g >> 3) + (g >> 6)) & 7; }
+GD_RC_FN int deal_block(int b, int grid) {
+    if ((b | 7) >= grid) return b;  // the last, partial group
+    return (b & ~7) | ((b + deal_rotation(b >> 3)) & 7);
+}
+// The same deal from the world's side: the list (0..7) that world-block w belongs on, i.e. b % 8 of the b with deal_block(b) = w.
+// k_knn_scan uses this form: workgroup w takes world-block w, on the XCD where the step's other kernels keep that world, and
+// appends to list deal_list(w).
+GD_RC_FN int deal_list(int w, int grid) {
+    if ((w | 7) >= grid) return w & 7;
+    return (w - deal_rotation(w >> 3)) & 7;
+}
 
 // (b') the same count for every chunk of a world at once, as a table that k_knn_rank builds once per agent: entry c is
 // cp_count(first_max, n, c * CHUNK).  The row is non-decreasing, so the entries at or before a chunk are a prefix of it and their

@@ -1064,7 +1064,8 @@ int gd_attach_bev(gd_sim *sim, float *bev);
  * crowded ranking bucket (-DGD_DIAG with GPUDRIVE_RANK_DBG=9) and 10..17 = clock ticks per phase of k_knn_rank, then
  * 18..20 = k_knn_replay's rounds of its first wave / candidates beyond K / inserts (-DGD_CLOCKS; tools/rank_spikes.py),
  * all since the last read.  Every build: 21 = accesses the rank replay's bounds audit found out of range since its buffers
- * exist (must stay 0), 30 = agents whose road rows were left in place because their pose bits had not changed, since the last
+ * exist (must stay 0), 22 = checkpoint rows the rank replay's set-up kernel wrote in the last selection (agents that are not
+ * bounded by their own checkpoints; every ranked agent with GPUDRIVE_RANK_SCAN_ROWS=1), 30 = agents whose road rows were left in place because their pose bits had not changed, since the last
  * read, 31 = BEV rasters painted by the last pass that rasterised (the others could not have changed and were left in
  * place), 44 = agents whose LiDAR returns the last pass marked for tracing (likewise), 45 = action indices outside the table
  * that gd_set_discrete_actions met since the simulator was created, 46 = worlds the warm-up of the device auto-reset
