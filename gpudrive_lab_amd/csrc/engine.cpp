@@ -1178,6 +1178,10 @@ int gd_create(const gd_config *cfg, const gd_params *params, const char *const *
         // as before the ranking read an agent's own checkpoints itself (A/B runs; the twin of tests/test_gpu_rank_setup.py)
         d.rk_scan_rows = 0;
         if (const char *e = std::getenv("GPUDRIVE_RANK_SCAN_ROWS")) d.rk_scan_rows = std::atoi(e) != 0 ? 1 : 0;
+        // GPUDRIVE_RANK_SCAN_KERNEL=1: the set-up of the selection (rank_setup.hpp) as k_knn_scan's launch behind the state step,
+        // as before k_world_step ran it itself (A/B runs; the twin of tests/test_gpu_rank_fold.py)
+        d.rk_scan_kernel = 0;
+        if (const char *e = std::getenv("GPUDRIVE_RANK_SCAN_KERNEL")) d.rk_scan_kernel = std::atoi(e) != 0 ? 1 : 0;
         // where a list of the standard ranking is drawn from its cursor, the waves the device holds at a time empty it: those
         // behind them (the launch has a wave per live agent, up to GD_RANK_GRID) leave without asking
         d.rk_resident = std::max(gd::rank_resident_waves(A) / 8, 1);
@@ -2510,6 +2514,10 @@ int gd_stat(gd_sim *s, int32_t which, int64_t *out) {
         if (hipMemcpy(&v, s->d.warm_count, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
             return fail(GD_ERR_DEVICE, "gd_stat: reading the warm-up counter failed");
         *out = static_cast<int64_t>(v);
+        return GD_OK;
+    }
+    if (s && out && which == 47) {  // 1: the state step runs the set-up of the rank path itself (engine.hpp rank_setup_folded)
+        *out = gd::rank_setup_folded(s->d) ? 1 : 0;
         return GD_OK;
     }
     if (s && out && which == 22) {  // checkpoint rows k_knn_scan wrote in the last selection (engine.hpp GD_RH_ROWS)

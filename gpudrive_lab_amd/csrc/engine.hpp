@@ -211,6 +211,7 @@ struct DevSim {
                            // the ranking wave makes it from cp_road / cp_T of `set` itself: (move, margin, checkpoints | set << 8, -).
                            // With a row: (move, the last K-th key of the checkpoints in use: scales the ranking buckets, GD_RK_REC_ROW, -)
     int rk_scan_rows;      // GPUDRIVE_RANK_SCAN_ROWS=1: k_knn_scan writes every agent's row and takes world b in workgroup b (A/B runs, twin tests)
+    int rk_scan_kernel;    // GPUDRIVE_RANK_SCAN_KERNEL=1: the set-up is k_knn_scan's launch, not part of the state step (rank_setup.hpp; A/B runs, twin tests)
     int rk_resident;       // waves of the standard ranking that the device holds at a time per XCD list (occupancy query at creation)
     const float4 *road_bbox;  // [W] (min x, min y, max x, max y) over the world's roads
     const float *road_rbmax;  // [W] the largest bounding radius (half diagonal) of a road of the world
@@ -235,6 +236,14 @@ struct DevSim {
     // attached buffer is [n_rows][D + 3] = ego 6 | the slot's 3 weights | partners | road points; null otherwise
     const float *pack_weights;
 };
+
+// Whether the state step of a pass runs the set-up of the rank path itself (rank_setup.hpp: launch_kernel picks k_world_step's
+// FOLD instantiation and launch_map_obs_rank starts with k_knn_rank): exactly the passes in which launch_map_obs reaches
+// launch_map_obs_rank and that one launches anything, unless GPUDRIVE_RANK_SCAN_KERNEL=1 keeps the set-up a launch of its own.
+inline bool rank_setup_folded(const DevSim &d) {
+    return d.rk_scan_kernel == 0 && d.rk_on != 0 && d.live_count != 0 && d.p.disableClassicalObs == 0 &&
+           d.p.roadObservationAlgorithm == GD_ROADS_K_NEAREST && d.knn_order != GD_KNN_SET_ORDER;
+}
 
 void launch_kernel(const DevSim &d, hipStream_t st, int which, bool move);
 void launch_map_obs(const DevSim &d, hipStream_t st, bool move);  // map_obs.hip

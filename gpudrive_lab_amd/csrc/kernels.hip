@@ -11,6 +11,7 @@
 #include "gd_math.hpp"
 #include "map_rows.hpp"
 #include "pack_cols.hpp"
+#include "rank_setup.hpp"
 
 namespace gd {
 
@@ -304,15 +305,19 @@ __device__ __forceinline__ void partner_rows(const DevSim &d, int w, int n, int 
 // (DevSim::pack_weights) | partners, 6 A + 3 floats at any 16-byte phase: the first pass stages ego | weights | 63 partners
 // (387 floats), the second 64 partners (384), and each leaves through store_span (pack_cols.hpp), which writes exactly the
 // head's own dwords -- the road kernels own the rest of the row.
-template <int A_T, bool ROWS, bool COND = false>
+// EXT: the waves' staging rows are the caller's (`ext`: HEAD_STAGE<COND> floats per wave, 16-byte aligned; k_world_step's FOLD
+// instantiations keep them in the phase buffer); otherwise LDS of this function's own.
+template <bool COND>
+constexpr int HEAD_STAGE = COND ? 64 * 6 + 4 : 64 * 6;
+template <int A_T, bool ROWS, bool COND = false, bool EXT = false>
 __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a, const float *s_px, const float *s_py,
                                             const float *s_qw, const float *s_qz, const float *s_speed, const float *s_len,
-                                            const float *s_wid, const float *s_self) {
+                                            const float *s_wid, const float *s_self, float *ext = nullptr) {
     static_assert(ROWS || !COND, "the conditioned layout exists for the learner rows only");
     constexpr int D = 6 + (A_T - 1) * 6 + K * 13, PITCH = COND ? D + 3 : D;
-    __shared__ __attribute__((aligned(16))) float s_head[STEP_THREADS / 64][COND ? 64 * 6 + 4 : 64 * 6];
+    __shared__ __attribute__((aligned(16))) float s_head[EXT ? 1 : STEP_THREADS / 64][EXT ? 4 : HEAD_STAGE<COND>];
     const int wave = a >> 6, lane = a & 63;
-    float *stage = s_head[wave];
+    float *stage = EXT ? ext + wave * HEAD_STAGE<COND> : s_head[wave];
     typedef float f4 __attribute__((ext_vector_type(4)));
     for (int ego = wave; ego < n; ego += STEP_THREADS / 64) {
         size_t prow = (size_t)w * A_T + ego;
@@ -379,9 +384,21 @@ __device__ __forceinline__ void packed_head(const DevSim &d, int w, int n, int a
 enum { WS_STEP = 0, WS_WARMUP = 1, WS_AFTER_WARMUP = 2 };
 
 // COND (gd_attach_packed_rows_conditioned): the conditioned learner rows (packed_head).
-template <int A_T, bool MOVE, bool ROWS = false, int MODE = WS_STEP, bool COND = false>
+// FOLD: the pass goes on with the rank path of the reference-order road selection (engine.hpp rank_setup_folded), and this kernel runs
+// that selection's set-up (rank_setup.hpp) -- the former launch of k_knn_scan: same geometry, one workgroup per world on XCD
+// w % 8.  The checkpoint headers are asked for with the first state loads; the decision per agent (`decide_half`, the wave that
+// holds a half's agents) follows the movement, where the step's pose is final and the loads have long arrived, so nothing waits
+// for memory; the rows of the rare agents that borrow a bound or are bounded afresh follow in front of the partner rows, the
+// list entries (an atomicAdd whose answer is waited for) at the very end.  The whole set-up as one block in front of the
+// partner rows, its loads issued there, cost the kernel 23 us (a chain of trips to memory by one wave, three waves at a
+// barrier): more than the launch it replaced; with the loads up front and the atomic behind the decision still 13 us.  LDS: 2 KB per half
+// from the decision to the rows; the rows' 19 KB lie over the phase buffer, which in these instantiations also holds the
+// agents' boxes and the packed head's staging rows (four workgroups per CU as before).  Instantiations without FOLD (set order,
+// linear, batches off the rank path, the warm-up) are as they were.
+template <int A_T, bool MOVE, bool ROWS = false, int MODE = WS_STEP, bool COND = false, bool FOLD = false>
 __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     constexpr bool OBS = MODE != WS_WARMUP;  // the observation phases
+    static_assert(OBS || !FOLD, "the set-up runs where the observation phases do");
     const int w = blockIdx.x, a = threadIdx.x;
     if (!MOVE && d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     const int n = d.shape[w * 2 + 0];
@@ -393,14 +410,20 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     __shared__ float s_px[A_T], s_py[A_T], s_qw[A_T], s_qz[A_T], s_speed[A_T];
     __shared__ float s_len[A_T], s_wid[A_T], s_hgt[A_T], s_rad[A_T];
     __shared__ int s_etype[A_T], s_id[A_T], s_flags[A_T];  // flags: bit0 active, bit1 static
-    __shared__ float s_obb[14][A_T];
+    __shared__ float s_obb_own[FOLD ? 1 : 14][FOLD ? 1 : A_T];
     __shared__ int s_hit[A_T];  // collision flags found by the threads sharing an agent
     __shared__ float s_self[A_T * 8];  // the self-observation rows (packed_head reads them)
     // One staging buffer for three phases that follow each other with workgroup barriers between them: the positions before the
     // movement and who moved at all (the BEV's dirty flags, right after the publish), the road boxes that passed the cull
     // (agent | local box index << 8 | entity type << 28), and the partner rows on their way out.  (Each with LDS of its own,
     // k_world_step<128> took 42,000 bytes: three workgroups per CU instead of four, a second generation for 1024 worlds.)
-    __shared__ __attribute__((aligned(16))) float s_stage[STEP_THREADS * 9];
+    // (FOLD: behind the staging buffer's own floats the agents' boxes, then the packed head's staging rows; the whole of it at
+    // least a rank_setup::Rows)
+    constexpr int STAGE_OBB = STEP_THREADS * 9, STAGE_HEAD = STAGE_OBB + 14 * A_T, STAGE_TENANTS = STAGE_HEAD + (STEP_THREADS / 64) * HEAD_STAGE<COND>;
+    constexpr int STAGE_FLOATS = !FOLD ? STEP_THREADS * 9 : STAGE_TENANTS * sizeof(float) >= sizeof(rank_setup::Rows) ? STAGE_TENANTS : (int)(sizeof(rank_setup::Rows) / sizeof(float));
+    static_assert(STAGE_OBB % 4 == 0 && STAGE_HEAD % 4 == 0, "16-byte aligned tenants");
+    __shared__ __attribute__((aligned(16))) float s_stage[STAGE_FLOATS];
+    float(*const s_obb)[A_T] = FOLD ? reinterpret_cast<float(*)[A_T]>(s_stage + STAGE_OBB) : reinterpret_cast<float(*)[A_T]>(&s_obb_own[0][0]);
     float *const s_opx = s_stage, *const s_opy = s_stage + A_T;
     unsigned long long *const s_moved = reinterpret_cast<unsigned long long *>(s_stage + 2 * A_T);  // a bit per agent slot
     // candidates looked at per trip of the road-box phase: six per thread (2,285 (agent, candidate) items per world on the bench
@@ -409,6 +432,18 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
     static_assert(SVCAP <= STEP_THREADS * 9 && 3 * A_T <= STEP_THREADS * 9, "the staging buffer holds each of its tenants");
     unsigned int *const s_sv = reinterpret_cast<unsigned int *>(s_stage);
     __shared__ int s_nsv[2];
+    __shared__ rank_setup::Half s_half[A_T / 64];  // (FOLD only: the other instantiations never name it)
+    // FOLD: what the set-up reads of the agent and the world, asked for with the state loads below
+    float4 su_h0 = make_float4(0.f, 0.f, 0.f, 0.f), su_h1 = su_h0;
+    int su_streak = 0;
+    rank_setup::WorldIn su_in = {};
+    if constexpr (FOLD) {
+        if (a < A_T) {
+            su_h0 = d.cp_hdr[i]; su_h1 = d.cp_hdr[(size_t)d.W * A_T + i];
+            su_streak = d.rk_streak[i / 32];
+            su_in = rank_setup::world_in(d, w);
+        }
+    }
     __shared__ int s_c0[A_T], s_coff[A_T], s_wtot[A_T / 64];  // road-box candidates: first entry, offset in the world's item list, per-wave totals
 
 #ifdef GD_CLOCKS
@@ -513,6 +548,12 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
                     p_sincos(heading / 2.f, b.qz, b.qw);
                 }
             }
+        }
+
+        // ---- the decision of the road selection's set-up: the pose is final (whole waves: every slot's thread calls) ----
+        rank_setup::Listed su_listed = {};
+        if constexpr (FOLD) {
+            if (a < A_T) su_listed = rank_setup::decide_half<A_T>(d, w, a & ~63, a & 63, b.px, b.py, b.qw, b.qz, live, su_h0, su_h1, su_streak, su_in, s_half[a >> 6]);
         }
 
         STEP_PHASE(1);
@@ -807,17 +848,28 @@ __global__ __launch_bounds__(STEP_THREADS) void k_world_step(DevSim d) {
 #ifdef GD_CLOCKS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
+        // ---- the set-up's rows of checkpoints for the agents of a half that need one (rare; workgroup-uniform: the decision
+        // lies behind the barriers of the pair phases; nobody reads the phase buffer or the boxes any more) ----
+        if constexpr (FOLD) {
+#pragma unroll
+            for (int h = 0; h < A_T / 64; h++)
+                if (rank_setup::rows_needed(s_half[h])) rank_setup::rows_half<A_T>(d, w, h * 64, s_half[h], *reinterpret_cast<rank_setup::Rows *>(s_stage));
+        }
         STEP_PHASE(5);
         // ---- collectPartnerObsSystem, :188-240: here, or in k_partner_rows on a stream of its own beside the road kernels ----
         if (OBS && !d.p.disableClassicalObs && !d.split_partner && !d.pack_only)
             partner_rows<A_T>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_hgt, s_etype, s_id, !moving || d.pose_skip == 0, s_stage);
         if (OBS && d.pack != nullptr && !d.p.disableClassicalObs) {
             __syncthreads();  // the agent threads' self columns
-            packed_head<A_T, ROWS, COND>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self);
+            packed_head<A_T, ROWS, COND, FOLD>(d, w, n, a, s_px, s_py, s_qw, s_qz, s_speed, s_len, s_wid, s_self, FOLD ? s_stage + STAGE_HEAD : nullptr);
         }
 #ifdef GD_CLOCKS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
+        // ---- the set-up's list entries: last, behind every barrier (the wave waits for its atomic alone) ----
+        if constexpr (FOLD) {
+            if (a < A_T) rank_setup::list_half<A_T>(d, w, a & ~63, a & 63, su_listed);
+        }
         STEP_PHASE(6);
         if (MODE == WS_WARMUP) __syncthreads();  // (the next step's publish rewrites the LDS arrays)
     } while (MODE == WS_WARMUP && ++it < last);
@@ -861,6 +913,13 @@ void step_clocks_read(unsigned long long *out) {  // and zero them; out[8..11] =
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
+template <int A_T, bool MOVE, int MODE, bool FOLD>
+static void launch_state(const DevSim &d, hipStream_t st, dim3 grid, int rows) {
+    if (rows == 2) hipLaunchKernelGGL((k_world_step<A_T, MOVE, true, MODE, true, FOLD>), grid, dim3(STEP_THREADS), 0, st, d);
+    else if (rows == 1) hipLaunchKernelGGL((k_world_step<A_T, MOVE, true, MODE, false, FOLD>), grid, dim3(STEP_THREADS), 0, st, d);
+    else hipLaunchKernelGGL((k_world_step<A_T, MOVE, false, MODE, false, FOLD>), grid, dim3(STEP_THREADS), 0, st, d);
+}
+
 template <int A_T>
 static void launch_all(const DevSim &d, hipStream_t st, int which, bool move) {
     const dim3 grid(d.W), block(A_T);
@@ -871,27 +930,21 @@ static void launch_all(const DevSim &d, hipStream_t st, int which, bool move) {
         else hipLaunchKernelGGL(k_reset_worlds<A_T>, grid, block, 0, st, d);
         break;
     case KERNEL_PADDING: hipLaunchKernelGGL(k_init_padding_rows<A_T>, grid, block, 0, st, d); break;
-    case KERNEL_STATE:
+    case KERNEL_STATE: {
+        const bool fold = rank_setup_folded(d);  // this pass's road selection takes the rank path: its set-up runs in here
+        const int rows = d.pack != nullptr && d.pack_rows ? (d.pack_weights ? 2 : 1) : 0;  // gd_attach_packed_rows (1), _conditioned (2)
         if (warmup && !move) {  // the state kernel of the reset pass behind the warm-up
-            if (d.pack != nullptr && d.pack_rows && d.pack_weights)
-                hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP, true>), grid, dim3(STEP_THREADS), 0, st, d);
-            else if (d.pack != nullptr && d.pack_rows) hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
-            else hipLaunchKernelGGL((k_world_step<A_T, false, false, WS_AFTER_WARMUP>), grid, dim3(STEP_THREADS), 0, st, d);
-            break;
+            if (fold) launch_state<A_T, false, WS_AFTER_WARMUP, true>(d, st, grid, rows);
+            else launch_state<A_T, false, WS_AFTER_WARMUP, false>(d, st, grid, rows);
+        } else if (move) {
+            if (fold) launch_state<A_T, true, WS_STEP, true>(d, st, grid, rows);
+            else launch_state<A_T, true, WS_STEP, false>(d, st, grid, rows);
+        } else {
+            if (fold) launch_state<A_T, false, WS_STEP, true>(d, st, grid, rows);
+            else launch_state<A_T, false, WS_STEP, false>(d, st, grid, rows);
         }
-        if (d.pack != nullptr && d.pack_rows && d.pack_weights) {  // gd_attach_packed_rows_conditioned
-            if (move) hipLaunchKernelGGL((k_world_step<A_T, true, true, WS_STEP, true>), grid, dim3(STEP_THREADS), 0, st, d);
-            else hipLaunchKernelGGL((k_world_step<A_T, false, true, WS_STEP, true>), grid, dim3(STEP_THREADS), 0, st, d);
-            break;
-        }
-        if (d.pack != nullptr && d.pack_rows) {  // gd_attach_packed_rows
-            if (move) hipLaunchKernelGGL((k_world_step<A_T, true, true>), grid, dim3(STEP_THREADS), 0, st, d);
-            else hipLaunchKernelGGL((k_world_step<A_T, false, true>), grid, dim3(STEP_THREADS), 0, st, d);
-            break;
-        }
-        if (move) hipLaunchKernelGGL((k_world_step<A_T, true>), grid, dim3(STEP_THREADS), 0, st, d);
-        else hipLaunchKernelGGL((k_world_step<A_T, false>), grid, dim3(STEP_THREADS), 0, st, d);
         break;
+    }
     case KERNEL_MAP_OBS: launch_map_obs(d, st, move); break;
     case KERNEL_PARTNER: hipLaunchKernelGGL(k_partner_rows<A_T>, grid, dim3(STEP_THREADS), 0, st, d); break;
     }

@@ -6,8 +6,9 @@
 // agent: 128 agents per CU, one lone wave per SIMD, two generations of workgroups at 1024 x 64).  The heap's
 // behaviour depends only on the OUTCOME of key comparisons, so this file replays it on ranks:
 //
-//   k_knn_scan +  The agent's CANDIDATES (scan: one lane per agent, the set-up -- who takes this path, and the row of checkpoints
-//   k_knn_rank    that bounds the agent's candidates; rank: one wave per agent, which culls the world's blocks of 16 roads
+//   the set-up +  The agent's CANDIDATES (set-up, rank_setup.hpp: one lane per agent, run by the state step k_world_step -- or by
+//   k_knn_rank    k_knn_scan, a launch of its own, under GPUDRIVE_RANK_SCAN_KERNEL=1 -- who takes this path, and the row of checkpoints
+//                 that bounds the agent's candidates; rank: one wave per agent, which culls the world's blocks of 16 roads
 //                 against that row, scans the surviving blocks in index order and keys what passes: rank_cand.hpp): roads
 //                 0..K-1 plus every later
 //                 road whose key is below a bound that provably is not smaller than the K-th distance the heap holds when
@@ -40,6 +41,7 @@
 #include "gd_math.hpp"
 #include "rank_cand.hpp"
 #include "rank_heap.hpp"
+#include "rank_setup.hpp"
 
 namespace gd {
 
@@ -75,7 +77,7 @@ constexpr int NB = RankGeo<CAP>::NB;
 static_assert(K + (NCP - 1) * TILE >= CAP && K + (NCP - 1) * 64 >= CAP_LONG, "a checkpoint slot for every tile of candidates");
 static_assert(CAP % 64 == 0 && NB % 128 == 0 && CAP < 2047 && CAP_LONG % 640 == 0 && CAP_LONG < 4095, "geometry; less + 1 fits 11 / 12 bits");
 static_assert(SPL >= K + 31 && SPL <= CAP && KT >= CAP / 16 + 1, "every slot the finish looks up; an entry per 16 slots + the last");
-constexpr int RK_FAR = 1 << 30;    // rk_n: no road of the world can be within the agent's radius
+constexpr int RK_FAR = rank_setup::RK_FAR;  // rk_n: no road of the world can be within the agent's radius
 constexpr int RK_TIES = 1 << 30;   // rk_ticket: the agent took its place in the replay order, then fell back (equal keys)
 
 __device__ __forceinline__ void wave_sync() {
@@ -174,256 +176,28 @@ __device__ __forceinline__ int audited(const DevSim &d, int idx, int size) {
 __device__ __forceinline__ bool rank_lt(unsigned int a, unsigned int b, unsigned int tm = 31u) { return (a | tm) < b; }
 
 // ------------------------------------------------------------------------------------------------------------------
-// k_knn_scan: the SET-UP of the selection, one lane per agent, one workgroup (4 waves) per 64 agent slots of a world: which
-// agents take the rank path, and the checkpoints that bound each one's candidates -- first road and threshold of the cheap
-// form |p - e|^2 < bound * margin (the margin covers rounding and the squared norm of the stored quaternion, like k_map_obs's
-// scan) -- from its previous selection, a neighbour's, or made afresh.  What it hands to k_knn_rank, which finds the candidates
-// itself (rank_cand.hpp), is a 16-byte record per agent (rk_rec) and, only for an agent that borrows a neighbour's checkpoints or
-// is bounded afresh, the row of checkpoints (rk_cpf / rk_cpt, 240 B).  An agent bounded by its own checkpoints -- every agent of
-// an ordinary step -- has its row made by the wave that ranks it, from the checkpoints where they lie: copying them here, one
-// lane per agent and one entry per trip, was a third of this kernel, writing the rows out and reading them back another.
-// Which XCD's list a workgroup fills is dealt (rank_cand.hpp deal_block).
+// k_knn_scan: the SET-UP of the selection (rank_setup.hpp) as a launch of its own, one workgroup (4 waves) per 64 agent slots
+// of a world.  The state step runs the same text itself (kernels.hip, the FOLD instantiations of k_world_step) and the rank
+// path then starts with k_knn_rank; this kernel is launched only under GPUDRIVE_RANK_SCAN_KERNEL=1 (A/B runs, twin tests).
 // ------------------------------------------------------------------------------------------------------------------
 template <int A_T>
 __global__ __launch_bounds__(256) void k_knn_scan(DevSim d) {
     if (d.gate_any && *d.any_reset == 0) return;  // device-driven reset pass: nothing was flagged this step
     constexpr int HALVES = A_T / 64;
     const int w = blockIdx.x / HALVES, a0 = (blockIdx.x % HALVES) * 64;
-    // which XCD's list this workgroup appends to: dealt, so that every list gets the same mix of worlds when scenes repeat with a
-    // period (rank_cand.hpp deal_block, deal_list).  The workgroup itself stays on the XCD that the step's other kernels keep its world on
-    // (workgroup b on XCD b % 8: the pose planes and checkpoint headers it reads are in that L2)
-    const int xl = d.rk_scan_rows ? (int)(blockIdx.x & 7) : rank_cand::deal_list((int)blockIdx.x, (int)gridDim.x);
-    if (blockIdx.x == 0 && threadIdx.x == 0) d.rk_hist[GD_RH_ROWS] = 0;  // k_knn_order counts this selection's rows (gd_stat 22)
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = d.shape[w * 2 + 0];
-    if (a0 >= n) return;
-    const int a = a0 + lane;
-    const bool live = a < n;
-    const size_t i = (size_t)w * A_T + a;
-    const size_t WA = (size_t)d.W * A_T;
-    const int r0 = d.road_off[w];
-    const int R = d.road_off[w + 1] - r0;
-
-    __shared__ unsigned short s_first[NCP][64];  // checkpoint q of lane l: first road it holds for (running maximum: rank_cand.hpp) ...
-    __shared__ float s_thr[NCP][64];             // ... and the threshold it gives
-    __shared__ int s_ncp[64];                    // checkpoints of lane l; 0: the agent is not on the rank path, or needs no row:
-                                                 // it is bounded by its own checkpoints, which its ranking wave reads where they are
-    __shared__ unsigned int s_needy[2];          // the agents to be bounded afresh (bit per lane), as the first wave saw them
-    __shared__ float4 s_hdr[64];                 // where and how many checkpoints lane l's previous selection recorded
-    __shared__ float s_bx[64], s_by[64], s_bm[64];  // position and margin of lane l's agent (for the waves that bound it afresh)
-    __shared__ unsigned int s_hist[4][256];      // per wave: histogram of squared distances of the roads streamed so far
-
-    float ex = 0.f, ey = 0.f;
-    if (live) { ex = d.px[i]; ey = d.py[i]; }
-    unsigned long long ranked = 0ull;  // wave 0: its lanes whose agents take the rank path ...
-    bool own_cp = false;               // ... and of them those that get no row (s_ncp above)
-    bool listed = false;               // this lane's agent is one of `ranked`
-    int list_base = 0;                 // ... and where they go in rk_list
+    __shared__ rank_setup::Half s_half;
+    __shared__ rank_setup::Rows s_rows;
+    rank_setup::Listed listed;
     if (wave == 0) {
-        int ncp = 0;
-        // (every lane's own checkpoint headers first, published: an agent without a usable bound of its own borrows one below)
-        float4 h0 = make_float4(0.f, 0.f, __int_as_float(0), 0.f), h1 = h0;
-        if (live) { h0 = d.cp_hdr[i]; h1 = d.cp_hdr[WA + i]; }
-        s_hdr[lane] = h0;
-        wave_sync();
-        if (live) {
-            // too far from every road of the world for any to be within the radius: no rows (a finished agent parked
-            // at the padding position, src/sim.cpp:333-343)
-            const float4 bb = d.road_bbox[w];
-            const float ddx = fmaxf(fmaxf(bb.x - ex, ex - bb.z), 0.f), ddy = fmaxf(fmaxf(bb.y - ey, ey - bb.w), 0.f);
-            const float far = d.p.observationRadius * 1.01f + 1.f;
-            int state = 1, reason = -1;
-            if (R >= K && ddx * ddx + ddy * ddy > far * far) {
-                state = RK_FAR;
-                // every road is beyond the radius: radiusFilter leaves nothing (src/knn.hpp:83-97, 156-157).  No replay, no
-                // checkpoints; the (empty) hand-over to k_map_rows is written here
-                d.sel_hdr[i * 2] = make_float4(ex, ey, d.qw[i], d.qz[i]);
-                d.sel_hdr[i * 2 + 1] = make_float4(__int_as_float(0), __int_as_float(r0), 0.f, 0.f);
-                d.cp_hdr[i] = make_float4(ex, ey, __int_as_float(0), 0.f);
-            } else {
-                // the previous selection's checkpoints, or those of the episode's first selection (a reset puts the agent
-                // back where that one was made): whichever was recorded closer to where the agent is now
-                const int n0 = __float_as_int(h0.z), n1 = __float_as_int(h1.z);
-                const float m0 = n0 > 0 ? sqrtf((ex - h0.x) * (ex - h0.x) + (ey - h0.y) * (ey - h0.y)) : __builtin_inff();
-                const float m1 = n1 > 0 ? sqrtf((ex - h1.x) * (ex - h1.x) + (ey - h1.y) * (ey - h1.y)) : __builtin_inff();
-                int set = m1 < m0 ? 1 : 0;
-                float move = set ? m1 : m0;
-                int n_cp = set ? n1 : n0;
-                size_t src = i;  // the agent whose checkpoint rows bound this selection
-                // An agent far from where its own checkpoints were recorded (a logged agent back from the padding position,
-                // src/sim.cpp:370-382: none at all, or the episode's first ones from somewhere else) borrows those of the
-                // agent of its world whose previous selection was made nearest to where it is now: the K-th distance over a
-                // prefix of the roads is a function of the position alone, 1-Lipschitz in it, whoever recorded it.  Without
-                // that every road of the world was a candidate for such an agent: beyond the buffers in a world of 10,000
-                // roads (the whole group of 32 to the fallback, a 3 ms step), the longest replay of the launch in smaller ones.
-                if (move > rank_cand::CP_MOVE_MAX) {
-                    float best = move;
-                    int donor = -1;
-                    for (int j = 0; j < 64; j++) {
-                        const float4 hj = s_hdr[j];
-                        const float dj = __float_as_int(hj.z) > 0 ? sqrtf((ex - hj.x) * (ex - hj.x) + (ey - hj.y) * (ey - hj.y)) : __builtin_inff();
-                        if (dj < best) { best = dj; donor = j; }
-                    }
-                    if (donor >= 0) {
-                        move = best;
-                        set = 0;
-                        n_cp = __float_as_int(s_hdr[donor].z);
-                        src = (size_t)w * A_T + a0 + donor;
-                    }
-                }
-                const bool eligible = R >= K && R >= d.rk_min_roads && R <= d.rk_max_roads;  // small worlds: k_map_obs is as fast
-                // a group that needed the fallback three selections in a row (agents that overflow even the long list)
-                // stops paying for rank kernels whose work is thrown away; it tries again every 64th selection
-                const int grp = (int)(i / 32);
-                const bool bypass = eligible && d.rk_streak[grp] >= 3 && ((d.rk_hist[513] + grp) & 63) != 0;
-                const float iw = d.qw[i], iz = d.qz[i];
-                const float z2 = iz * iz;
-                const float det = (1.f - 2.f * z2) * (1.f - 2.f * z2) + 4.f * z2 * (iw * iw);
-                const float margin = 1.00001f / fminf(det, 1.f);
-                if (!eligible || bypass) {
-                    state = 0;
-                    ncp = 0;
-                    reason = bypass ? -5 : -2;  // -2: a world below rk_min_roads (or without K roads)
-                    d.rk_fallback[i / 32] = 1;
-                } else if (n_cp <= 0 || move > rank_cand::CP_MOVE_MAX) {
-                    // No usable bound -- the first selection after the worlds were built, a logged agent that reappears
-                    // anywhere on the map (src/sim.cpp:370-382) with nobody near: the waves of this workgroup bound it afresh
-                    // below (`bound_afresh`).  Round 3 sent such an agent's group to the history replay on keys.
-                    ncp = -1;
-                    s_bx[lane] = ex; s_by[lane] = ey; s_bm[lane] = margin;
-                } else if (src == i && !d.rk_scan_rows) {
-                    // the common case: bounded by its own checkpoints (of the previous selection or the episode's first), which
-                    // nobody but the wave that ranks this agent writes during the ranking launch, and that one only after it
-                    // has read them (rank_fetch).  The row is a function of those two arrays, `move` and `margin`: lane q of
-                    // the ranking wave makes entry q (rank_cand.hpp cp_threshold, the running maximum as a wave scan)
-                    ncp = n_cp;
-                    own_cp = true;
-                    d.rk_rec[i] = make_float4(move, margin, __int_as_float(n_cp | set << 8), 0.f);
-                } else {
-                    // a donor's checkpoints (the wave that ranks the donor overwrites them during the launch), or every row
-                    // (GPUDRIVE_RANK_SCAN_ROWS): copied into the agent's row here
-                    ncp = n_cp;
-                    float t = 1.f;
-                    const unsigned short *cr = d.cp_road + ((size_t)set * WA + src) * NCP;
-                    const float *ct = d.cp_T + ((size_t)set * WA + src) * NCP;
-                    unsigned int fmax = 0u;  // (rank_cand.hpp: with the running maximum "in force" is a count of entries)
-                    for (int q = 0; q < ncp; q++) {
-                        t = ct[q];
-                        fmax = rank_cand::running_max(fmax, cr[q]);
-                        s_first[q][lane] = (unsigned short)fmax;
-                        s_thr[q][lane] = rank_cand::cp_threshold(t, move, margin);  // (an unusable entry bounds nothing)
-                    }
-                    d.rk_rec[i] = make_float4(move, t, __int_as_float(n_cp | GD_RK_REC_ROW), 0.f);  // t: the last K-th key, scales the ranking buckets
-                }
-            }
-            d.rk_n[i] = state;
-            d.rk_ticket[i] = reason;  // k_knn_rank takes a ticket (>= 0) once the agent's ranks exist; < -1: why it fell back
-            if (state == RK_FAR) ncp = 0;
-        }
-        s_ncp[lane] = own_cp ? 0 : ncp;
-        {
-            // published once, before the barrier: the waves below must all see ONE mask (a wave that finishes an agent rewrites
-            // its s_ncp entry, and a late reader of s_ncp would deal the turns differently and skip the barrier behind the loop)
-            const unsigned long long nd = __ballot(ncp < 0);
-            if (lane == 0) { s_needy[0] = (unsigned int)nd; s_needy[1] = (unsigned int)(nd >> 32); }
-        }
-        if (ncp < 0) ncp = 1;  // (bounded afresh below: on the rank path like the others)
-        // the agents on the rank path, as a list: k_knn_rank's waves share THEM out, not the live agents (on the Waymo tiles
-        // five agents in six are parked out of reach of every road, and a wave that drew three of the others set the pace).
-        // One list per XCD (dealt: `xl` above; k_knn_rank's waves take the list of their own XCD, so an agent's
-        // road points are gathered into the L2 that scanned them, and eight counters are asked instead of one: a thousand
-        // workgroups adding to one address at once cost the kernel 10 us)
-        ranked = __ballot(ncp > 0);
-        listed = ncp > 0;
-        // their place in the list: asked for now, needed at the very end (a trip to the L2 and back behind the work below)
-        if (ranked != 0ull && lane == 0) list_base = atomicAdd(&d.rk_hist[528 + xl], __popcll(ranked));
+        const size_t i = (size_t)w * A_T + a0 + lane, WA = (size_t)d.W * A_T;
+        listed = rank_setup::decide_half<A_T>(d, w, a0, lane, d.px[i], d.py[i], d.qw[i], d.qz[i], a0 + lane < n, d.cp_hdr[i], d.cp_hdr[WA + i],
+                                              d.rk_streak[i / 32], rank_setup::world_in(d, w), s_half);
     }
     __syncthreads();
-    // ---- agents without a usable bound: one wave each streams the world's roads once, in scan order, and keeps a histogram of
-    // their squared distances (16 buckets per octave: the exponent and four mantissa bits).  At up to 39 road counts spaced
-    // geometrically (the K-th distance falls like the logarithm of the roads seen) the upper edge of the bucket that holds the
-    // K-th smallest distance so far is a bound of the K-th distance from there on -- a checkpoint like those a previous
-    // selection leaves, at most 4.4 % loose, made without one.  About 6 us per such agent. ----
-    {
-        const unsigned long long needy = (unsigned long long)s_needy[0] | (unsigned long long)s_needy[1] << 32;
-        if (needy != 0ull) {  // (workgroup-uniform)
-            constexpr int BASE = (127 - 2) << 4;  // bucket 0: below 2^-2 m^2; bucket 255: 2^13.9 m^2 (118 m) and beyond = unbounded
-            unsigned int *hist = s_hist[wave];
-            int turn = 0;
-            for (unsigned long long rest = needy; rest != 0ull; rest &= rest - 1ull, turn++) {
-                if ((turn & 3) != wave) continue;  // wave-uniform
-                const int al = __ffsll((long long)rest) - 1;
-                const float bx = s_bx[al], by = s_by[al], mg = s_bm[al];
-#pragma unroll
-                for (int k = 0; k < 4; k++) hist[k * 64 + lane] = 0u;
-                if (lane == 0) { s_first[0][al] = (unsigned short)((K / 32) * 32); s_thr[0][al] = __builtin_inff(); }
-                const float ratio = exp2f(log2f(fmaxf((float)R / 256.f, 1.f)) / (float)(NCP - 2));
-                float pf = 256.f, tlast = __builtin_inff();
-                int pq = 256, q = 1;
-                float2 nxt = lane < R ? d.road_xy[r0 + lane] : make_float2(0.f, 0.f);
-                for (int rb = 0; rb < R; rb += 64) {
-                    const float2 xy = nxt;
-                    if (rb + 64 + lane < R) nxt = d.road_xy[r0 + rb + 64 + lane];
-                    if (rb + lane < R) {
-                        const float dx = xy.x - bx, dy = xy.y - by;
-                        const float d2 = __builtin_fmaf(dx, dx, dy * dy);
-                        atomicAdd(&hist[min(255, max(0, (int)(__float_as_uint(d2) >> 19) - BASE))], 1u);
-                    }
-                    if (rb + 64 == pq && q < NCP && pq < R) {  // wave-uniform: roads [0, pq) are in the histogram
-                        wave_sync();
-                        const uint4 h = reinterpret_cast<const uint4 *>(hist)[lane];  // lane l owns buckets 4 l .. 4 l + 3
-                        const int own = (int)(h.x + h.y + h.z + h.w);
-                        const int incl = wave_incl_scan(own), excl = incl - own;
-                        int jb = 0, before = excl;
-                        if (before + (int)h.x < K) { before += (int)h.x; jb = 1;
-                            if (before + (int)h.y < K) { before += (int)h.y; jb = 2;
-                                if (before + (int)h.z < K) { jb = 3; } } }
-                        const unsigned long long cross = __ballot(excl < K && incl >= K);  // exactly one lane: pq >= 256 > K
-                        const int Lc = __ffsll((long long)cross) - 1;
-                        const int bucket = 4 * Lc + __builtin_amdgcn_readlane(jb, Lc);
-                        const float T = bucket >= 255 ? __builtin_inff() : __uint_as_float((unsigned int)(bucket + 1 + BASE) << 19);
-                        if (lane == 0) {
-                            const float reach = sqrtf(T) * 1.0001f + 1e-3f;
-                            float thr = reach * reach * 1.0001f * mg * 1.001f;  // (the squared distances here are the scan's own form)
-                            if (!(thr >= 0.f)) thr = __builtin_inff();
-                            s_first[q][al] = (unsigned short)min(pq, 65535);
-                            s_thr[q][al] = thr;
-                        }
-                        tlast = T;
-                        q++;
-                        pf *= ratio;
-                        pq = max(pq + 64, ((int)pf + 63) & ~63);
-                    }
-                }
-                if (lane == 0) {
-                    s_ncp[al] = q;
-                    // (the last K-th key scales the ranking buckets)
-                    d.rk_rec[(size_t)w * A_T + a0 + al] = make_float4(0.f, tlast < 1e30f ? tlast : 1.f, __int_as_float(q | GD_RK_REC_ROW), 0.f);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (wave == 0 && ranked != 0ull) {
-        list_base = __builtin_amdgcn_readfirstlane(list_base);
-        if (listed)
-            d.rk_list[(size_t)xl * WA + audited(d, list_base + __popcll(ranked & ((1ull << lane) - 1ull)), (int)WA)] = (int)i;
-    }
-    const int ncp = s_ncp[lane];
-    if (__syncthreads_or(ncp > 0 ? 1 : 0) == 0) return;  // no agent of this workgroup needs a row (far, fallback, bypass, its own checkpoints)
-    // The checkpoint rows of the agents on the rank path, agent-major (k_knn_rank reads an agent's row as one coalesced
-    // load), whole rows: the entries behind an agent's last checkpoint are never in force
-    {
-        unsigned short *rowf = d.rk_cpf + ((size_t)w * A_T + a0) * NCP;
-        float *rowt = d.rk_cpt + ((size_t)w * A_T + a0) * NCP;
-        for (int e = tid; e < 64 * NCP; e += 256) {
-            const int ag = e / NCP, q = e - ag * NCP;
-            if (q < s_ncp[ag]) {
-                rowf[e] = s_first[q][ag];
-                rowt[e] = s_thr[q][ag];
-            }
-        }
-    }
+    if (rank_setup::rows_needed(s_half)) rank_setup::rows_half<A_T>(d, w, a0, s_half, s_rows);  // (workgroup-uniform)
+    if (wave == 0) rank_setup::list_half<A_T>(d, w, a0, lane, listed);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1665,12 +1439,14 @@ void launch_map_obs_rank(const DevSim &d, hipStream_t st) {
     // every wave reads the empty count and leaves)
     const dim3 glong(std::min(std::max(d.rk_nlong, 1), GD_RANK_LONG_GRID));
     const dim3 gr(d.rk_waves > 0 ? d.rk_waves : std::min((d.live_count + 7) / 8 * 8, GD_RANK_GRID)), g4((d.live_count + 3) / 4), gw(d.W * (d.A / 64));  // rank: 8192 persistent waves, 16 per CU resident (LDS)
+    // the set-up: run by the state step of this pass (engine.hpp rank_setup_folded), or the launch of its own (GPUDRIVE_RANK_SCAN_KERNEL=1)
+    const bool scan = !rank_setup_folded(d);
     if (d.A == 64) {
-        hipLaunchKernelGGL((k_knn_scan<64>), gw, dim3(256), 0, st, d);
+        if (scan) hipLaunchKernelGGL((k_knn_scan<64>), gw, dim3(256), 0, st, d);
         hipLaunchKernelGGL((k_knn_rank<64, CAP>), gr, dim3(64), 0, st, d);
         if (d.rk_nlong > 0) hipLaunchKernelGGL((k_knn_rank<64, CAP_LONG>), glong, dim3(64), 0, st, d);
     } else {
-        hipLaunchKernelGGL((k_knn_scan<128>), gw, dim3(256), 0, st, d);
+        if (scan) hipLaunchKernelGGL((k_knn_scan<128>), gw, dim3(256), 0, st, d);
         hipLaunchKernelGGL((k_knn_rank<128, CAP>), gr, dim3(64), 0, st, d);
         if (d.rk_nlong > 0) hipLaunchKernelGGL((k_knn_rank<128, CAP_LONG>), glong, dim3(64), 0, st, d);
     }

@@ -1069,7 +1069,9 @@ int gd_attach_bev(gd_sim *sim, float *bev);
  * read, 31 = BEV rasters painted by the last pass that rasterised (the others could not have changed and were left in
  * place), 44 = agents whose LiDAR returns the last pass marked for tracing (likewise), 45 = action indices outside the table
  * that gd_set_discrete_actions met since the simulator was created, 46 = worlds the warm-up of the device auto-reset
- * (gd_episode_set_warmup) advanced since the simulator was created.  Otherwise GD_ERR_INVALID. */
+ * (gd_episode_set_warmup) advanced since the simulator was created, 47 = the state step runs the set-up of the rank replay's
+ * selection itself (1; 0: the rank replay is off for this batch, or GPUDRIVE_RANK_SCAN_KERNEL=1 keeps it a launch of its
+ * own).  Otherwise GD_ERR_INVALID. */
 int gd_stat(gd_sim *sim, int32_t which, int64_t *out);
 
 /* Timing hooks for the bench: HIP events around the named kernel on the engine's stream (a fixed ring of event pairs,
