@@ -249,6 +249,11 @@ class GdPolicyRolloutRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rows", "count", "scratch", "live_count")] + [("reserved", C.c_int32)]
 
 
+class GdBCRolloutRows(C.Structure):
+    """gd_bc_rollout_rows: gd_policy_rollout_rows for the closed-loop BC driver (device pointers)."""
+    _fields_ = [(n, C.c_void_p) for n in ("rows", "count", "scratch", "live_count")] + [("reserved", C.c_int32)]
+
+
 class GdBCGrad(C.Structure):
     """gd_bc_grad: the scratch and the partial sums of one gd_bc_backward (device pointers)."""
     _fields_ = [("scratch", C.c_void_p), ("scratch_floats", C.c_int64), ("partials", C.c_void_p), ("grad_floats", C.c_int64),
@@ -301,7 +306,7 @@ SYMBOLS = [
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
-    "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
+    "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -402,6 +407,10 @@ def lib():
     L.gd_policy_forward_rows.argtypes = [C.POINTER(GdPolicy), D, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 8
     L.gd_policy_rollout_compact.argtypes = [C.c_void_p, C.POINTER(GdPolicy), C.POINTER(GdPolicyRolloutBuffers),
                                             C.POINTER(GdPolicyRolloutRows), C.c_int32]
+    L.gd_bc_forward_rows.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
+                                     [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs)] + [C.c_void_p] * 3)
+    L.gd_bc_rollout_compact.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers),
+                                        C.POINTER(GdBCRolloutRows), C.c_int32]
     L.gd_bc_hidden.argtypes = [C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lp = [C.POINTER(GdBCPolicy), C.POINTER(GdLPProbe), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_lp_forward.argtypes = lp + [C.POINTER(GdLPRows), C.c_void_p]

@@ -16,6 +16,9 @@ with an L x L extent exists anywhere -- the scores of a (sample, head, 32-query 
     nll     = bc.nll(obs, pm, rm, expert)                         # [B] (gmm_loss's detached second value)
     stats   = bc.evaluate(ds, batch_size=512)                     # il.py:99-180's eight numbers, ONE host read
     bc.load_state_dict(sd)                                        # re-pack after a torch optimiser's step
+    lr = live_rows(alive, out=lr)                                 # policy.live_rows: the rows of a [B] byte mask, on the device
+    bc(obs, pm, rm, deterministic=True, out=actions, rows=lr)     # the listed rows only (gd_bc_forward_rows); the others keep
+                                                                  # their bytes, every listed row gets the full forward's bits
 
 The state dict carries the reference module's own parameter names (`expected_shapes`), so a `torch.save`d reference model
 loads without renaming.  The draw is this project's: the reference samples the component with `dist.Categorical` and the
@@ -31,7 +34,8 @@ chunk on the stream inside the one C call.  `nbytes(B)` states what a call of B 
 
 Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); the gradient step with clipping and AdamW
 (`bc_opt.DeviceBC`, gd_bc_update, whose `policy` is one of these and follows the optimiser in place); the closed-loop driver
-(`bc_rollout.ClosedLoopBC`, gd_bc_rollout, which calls this forward once per step);
+(`bc_rollout.ClosedLoopBC`, gd_bc_rollout, which calls this forward once per step, or with compact=True the forward on the list
+of the rows still alive);
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
 `ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64; bf16."""
 import ctypes as C
@@ -329,11 +333,29 @@ class DeviceBCPolicy:
                        weights=lambda s, B: (B, 1, s.n_components), actions=lambda s, B: (B, 1, 3), nll=lambda s, B: (B,),
                        ego_attn_score=lambda s, B: (B, HEADS, s.max_agents - 1), component=lambda s, B: (B,))
 
-    def forward(self, obs, partner_mask, road_mask, want, *, deterministic=True, u=None, z=None, expert_actions=None, out=None):
+    def forward(self, obs, partner_mask, road_mask, want, *, deterministic=True, u=None, z=None, expert_actions=None, out=None,
+                rows=None):
         """The one C call.  want: the names of the outputs to write, out of context, means, log_covariances, covariances,
         weights, actions, nll, ego_attn_score, component (`_OUT_SHAPES`); out: a dict with tensors for some of them, to be
-        overwritten.  Returns a dict of the wanted tensors.  Every check happens before the launch."""
+        overwritten.  Returns a dict of the wanted tensors.  rows: None for all B rows, or a `policy.LiveRows` of this B
+        (`policy.live_rows(mask, out=)`): the forward then runs on the listed rows only (`gd_bc_forward_rows`), reads index r of
+        every input and writes index r of every output with the bits the full forward gives that row; rows that are not
+        listed are not written, so every wanted output must be given in out= and keeps its bytes there.  The list's length
+        stays on the device: every chunk is launched, and the workgroups past the list return at once.  Every check happens
+        before the launch."""
+        from .policy import LiveRows
+        if rows is not None and not isinstance(rows, LiveRows):
+            raise ValueError(WHO + "rows must be a LiveRows (policy.live_rows(mask)), got %s" % type(rows).__name__)
         B = self._inputs(obs, partner_mask, road_mask)
+        if rows is not None:
+            if rows.n != B:
+                raise ValueError(WHO + "rows must be a LiveRows of N = %d, got one of N = %d" % (B, rows.n))
+            if rows.rows.device != self.device:
+                raise ValueError(WHO + "rows is on %s, the policy on %s" % (rows.rows.device, self.device))
+            missing = [name for name in want if (out or {}).get(name) is None]
+            if missing:
+                raise ValueError(WHO + "rows= needs out= for every wanted output (rows that are not listed keep the caller's "
+                                 "bytes), missing: %s" % ", ".join(missing))
         deterministic = bool(deterministic)
         if not deterministic:
             if u is None or z is None:
@@ -368,11 +390,14 @@ class DeviceBCPolicy:
         p.scratch, p.scratch_floats = self._scratch.data_ptr(), self._scratch.numel()
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(self._L.gd_bc_forward(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
-                                              int(deterministic), None if u is None else u.data_ptr(),
-                                              None if z is None else z.data_ptr(),
-                                              None if expert_actions is None else expert_actions.data_ptr(), C.byref(o), stream),
-                        "gd_bc_forward")
+            args = (C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, int(deterministic),
+                    None if u is None else u.data_ptr(), None if z is None else z.data_ptr(),
+                    None if expert_actions is None else expert_actions.data_ptr(), C.byref(o))
+            if rows is not None:
+                _capi.check(self._L.gd_bc_forward_rows(*args, rows.rows.data_ptr(), rows.count.data_ptr(), stream),
+                            "gd_bc_forward_rows")
+            else:
+                _capi.check(self._L.gd_bc_forward(*args, stream), "gd_bc_forward")
         return res
 
     def c_struct(self):
@@ -409,35 +434,38 @@ class DeviceBCPolicy:
                                              self.TAPS[tap], out.data_ptr(), stream), "gd_bc_hidden")
         return out
 
-    def __call__(self, obs, partner_mask, road_mask, deterministic=False, u=None, z=None, out=None):
+    def __call__(self, obs, partner_mask, road_mask, deterministic=False, u=None, z=None, out=None, rows=None):
         """obs [B, R, D] float32, partner_mask [B, R, A - 1] and road_mask [B, R, 200] bool or uint8, as
         `DeviceExpertDataset.batch` writes them.  deterministic: the mean of the first component of maximal weight; otherwise
         u [B] float32 in [0, 1) and z [B, 3] float32 standard normals give the rule's draw.  Returns actions [B, 1, 3]; out: that
-        tensor of an earlier call.  No host synchronisation; with out= no allocation."""
+        tensor of an earlier call.  rows: a `LiveRows` of B (`forward`): only the listed rows are computed and written, out= is then
+        required.  No host synchronisation; with out= no allocation."""
         return self.forward(obs, partner_mask, road_mask, ("actions",), deterministic=deterministic, u=u, z=z,
-                            out=None if out is None else {"actions": out})["actions"]
+                            out=None if out is None else {"actions": out}, rows=rows)["actions"]
 
-    def context(self, obs, partner_mask, road_mask, out=None, ego_attn_score=None):
+    def context(self, obs, partner_mask, road_mask, out=None, ego_attn_score=None, rows=None):
         """get_context's first value, [B, 192] = [ego | ego_ro | ego_rg]; ego_attn_score: a [B, 4, A - 1] float32 tensor to
-        receive its second value."""
+        receive its second value.  rows: as in `forward` (out= is then required)."""
         want, o = ["context"], {"context": out}
         if ego_attn_score is not None:
             want.append("ego_attn_score")
             o["ego_attn_score"] = ego_attn_score
-        return self.forward(obs, partner_mask, road_mask, want, out=o)["context"]
+        return self.forward(obs, partner_mask, road_mask, want, out=o, rows=rows)["context"]
 
-    def gmm_params(self, obs, partner_mask, road_mask, out=None):
-        """(means [B, 1, C, 3], covariances [B, 1, C, 3], weights [B, 1, C]) as GMM.get_gmm_params returns them."""
+    def gmm_params(self, obs, partner_mask, road_mask, out=None, rows=None):
+        """(means [B, 1, C, 3], covariances [B, 1, C, 3], weights [B, 1, C]) as GMM.get_gmm_params returns them.  rows: as in
+        `forward` (out= is then required)."""
         names = ("means", "covariances", "weights")
         if out is not None and (not isinstance(out, (tuple, list)) or len(out) != 3):
             raise ValueError(WHO + "out must be the three tensors (means, covariances, weights)")
-        r = self.forward(obs, partner_mask, road_mask, names, out=None if out is None else dict(zip(names, out)))
+        r = self.forward(obs, partner_mask, road_mask, names, out=None if out is None else dict(zip(names, out)), rows=rows)
         return tuple(r[k] for k in names)
 
-    def nll(self, obs, partner_mask, road_mask, expert_actions, out=None):
-        """gmm_loss's detached per-row value for expert_actions [B, 1, 3] (or [B, 3]): [B] float32."""
+    def nll(self, obs, partner_mask, road_mask, expert_actions, out=None, rows=None):
+        """gmm_loss's detached per-row value for expert_actions [B, 1, 3] (or [B, 3]): [B] float32.  rows: as in `forward`
+        (out= is then required)."""
         return self.forward(obs, partner_mask, road_mask, ("nll",), expert_actions=expert_actions,
-                            out=None if out is None else {"nll": out})["nll"]
+                            out=None if out is None else {"nll": out}, rows=rows)["nll"]
 
     def evaluate(self, ds, batch_size=512):
         """The reference's evaluate() (baselines/il/il.py:99-180): its eight numbers as a dict (`EVAL_NAMES`; tom_loss is 0.0,

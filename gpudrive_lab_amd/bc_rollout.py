@@ -15,12 +15,22 @@ episode on the simulator's stream with no host synchronisation, no allocation an
     ep.goal_step / expert_done_step                                # the reference's normalised goal time is the caller's line
 
 Rows are in `mask.nonzero()` order (default: the controlled agents).  The window handed to the policy, and returned as
-`window`, is the one the policy saw at the last iteration that ran.  The policy's forward runs on all N rows every step: dead
-rows are not compacted away, their actions are replaced by zeros.  Iterations after every row is dead (the reference's
-`break`) change no output; `steps` counts the iterations that exist.
+`window`, is the one the policy saw at the last iteration that ran.  By default the policy's forward runs on all N rows every
+step and a dead row's action is replaced by zeros.  Iterations after every row is dead (the reference's `break`) change no
+output; `steps` counts the iterations that exist.
+
+    ep = loop.run(compact=True)                                    # the forward on the rows still alive only
+    ep.live_count                                                  # [91] int32: how many that was, per step
+
+`run(compact=True)` is the reference's `obs[~dead]`: per step two more launches list the rows with `dead == 0` on the device
+(`gd_live_rows`' kernels on the complement of the byte) and the forward runs on that list (`gd_bc_forward_rows`); the host
+never learns the length, so every chunk of `chunk_rows` list positions is still launched and the workgroups past the list
+return at their first load.  Every result is `run()`'s bit for bit, except `row_actions` of a dead row: the action of the last
+step it was alive at (with `run()`, of the last step).  The row kernel still visits every row -- a dead row's window, masks and
+goal distance keep moving in the reference.
 
 Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos, `importance_weight.py` / `intervention.py`,
-compaction of dead rows.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
+fewer launches for the chunks past the list.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
 caller's `sim.deleteAgents(...)` before `run()`; self-play is a mask with more rows."""
 import ctypes as C
 
@@ -123,10 +133,11 @@ class ClosedLoopBC:
         return n
 
     @staticmethod
-    def nbytes(sim, policy, record=False, mask=None, stochastic=False):
+    def nbytes(sim, policy, record=False, mask=None, stochastic=False, compact=False):
         """What `run()` will allocate for `sim`, `policy` and `mask` (default: the controlled agents): N rows of `row_nbytes`,
-        any_alive [92] int32 and the summary [8]; with stochastic the draws u [91, N] and z [91, N, 3].  The policy's own blob
-        and scratch are the policy's (`policy.nbytes`).  (Synchronises, for N.)"""
+        any_alive [92] int32 and the summary [8]; with stochastic the draws u [91, N] and z [91, N, 3]; with compact the row
+        list, its count and scratch (`LiveRows.nbytes(N)`) and live_count [91] int32.  The policy's own blob and scratch are
+        the policy's (`policy.nbytes`).  (Synchronises, for N.)"""
         _check_sim(sim)
         _check_mask(sim, mask)
         _check_policy(sim, policy)
@@ -136,6 +147,9 @@ class ClosedLoopBC:
         total = n * ClosedLoopBC.row_nbytes(sim._A, policy.num_stack, record) + (EPISODE_LEN + 1) * 4 + len(SUMMARY_NAMES) * 4
         if stochastic:
             total += EPISODE_LEN * n * 4 * 4
+        if compact:
+            from .policy import LiveRows
+            total += LiveRows.nbytes(n) + EPISODE_LEN * 4
         return total
 
     def resample(self, scenes):
@@ -158,11 +172,13 @@ class ClosedLoopBC:
         """Every array of a run is made here (fill None: need not be initialised)."""
         return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
 
-    def run(self, n_steps=EPISODE_LEN, deterministic=True, generator=None, record=False):
+    def run(self, n_steps=EPISODE_LEN, deterministic=True, generator=None, record=False, compact=False):
         """Reset every world, fill the running state and run `n_steps` steps with the policy in the loop in one C call; returns
         the `ClosedLoopEpisode`.  n_steps < 91 gives the prefix of the full episode.  deterministic=False: u [n_steps, N] and
         z [n_steps, N, 3] are drawn from `generator` (a device torch.Generator, required) before the call and consumed per
-        step under csrc/bc_rule.hpp's draw; they are returned as `u` and `z`.  record: also keep the per-step arrays.  No host
+        step under csrc/bc_rule.hpp's draw; they are returned as `u` and `z`.  record: also keep the per-step arrays.  compact:
+        run every step's forward on the list of the rows still alive (`gd_bc_rollout_compact`, see the module docstring); the
+        episode then has live_count [91] int32, the length of step t's list, 0 for t >= n_steps, and `live_rows`.  No host
         synchronisation."""
         _check_steps(n_steps)
         deterministic = bool(deterministic)
@@ -198,9 +214,19 @@ class ClosedLoopBC:
                 out[name] = new(name, (n, T) if c == 1 else (n, T, c), dt, fill)
                 setattr(b, name, out[name].data_ptr())
         p = self._policy_struct()
+        if compact:
+            from .policy import LiveRows
+            out["live_rows"] = lr = LiveRows(n, dev, new=self._new)  # (kept with the episode: the call is still running)
+            out["live_count"] = new("live_count", (T,), torch.int32, 0)
+            r = _capi.GdBCRolloutRows()
+            r.rows, r.count, r.scratch = lr.rows.data_ptr(), lr.count.data_ptr(), lr.scratch.data_ptr()
+            r.live_count = out["live_count"].data_ptr()
         sim.reset(list(range(sim._W)))
         sim._bind_stream()
-        _capi.check(sim._L.gd_bc_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_bc_rollout")
+        if compact:
+            _capi.check(sim._L.gd_bc_rollout_compact(sim._h, C.byref(p), C.byref(b), C.byref(r), n_steps), "gd_bc_rollout_compact")
+        else:
+            _capi.check(sim._L.gd_bc_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_bc_rollout")
         sim._after()
         out["dead"] = out["dead"].view(torch.bool)
         return ClosedLoopEpisode(steps=any_alive[:T].sum(), any_alive=any_alive, summary_tensor=summary, window=window,

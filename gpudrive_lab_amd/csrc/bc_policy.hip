@@ -23,19 +23,51 @@
 // An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation.
 // The backward (bc_grad.hip) reruns these kernels per chunk through launch_bc_forward_chunk and launch_bc_self_layer; its
 // SAVE instantiation of the attention kernel also stores the attention output before o_proj and the softmax's row statistics.
+// The forward on a row list (gd_bc_forward_rows, launch_bc_forward_rows) is the same launches on the kernels' list
+// instantiations (the pack of their last parameters is one BCRows).  A list position q belongs to chunk q / chunk_rows and to
+// scratch slot q % chunk_rows; the workgroup of a slot loads the list's length, returns if its position is past it (or its
+// entry is no row) before it loads, stores to LDS or synchronises anything else, and otherwise computes row rows[q]: X / K / V
+// by slot; obs, the masks, u, z, expert_actions and every output by the row.  No result of a sample depends on the samples
+// beside it, so a listed row gets the full forward's bits.  The host knows no length: every chunk is launched.
 #include "bc_tile.hpp"
 
 namespace gd {
 
 namespace {
 
+// ---- the row list
+
+// A row list on the device and the chunk of it a launch covers: the workgroup of scratch slot s has list position q0 + s
+struct BCRows {
+    const int32_t *rows, *count;
+    int q0, n;
+};
+
+// The sample of scratch slot `slot`.  The four kernels below take the list as a parameter pack that is empty in the full
+// forward, whose sample is the slot itself (those instantiations are the kernels as they were before there was a list).  With a
+// list: row rows[q0 + slot], or -1 where the position is past the list (a length above n is read as n) or the entry is outside
+// [0, n).  Workgroup-uniform; the only loads a workgroup that returns makes.
+__device__ __forceinline__ int bc_sample(int slot) { return slot; }
+__device__ __forceinline__ int bc_sample(int slot, const BCRows &lr) {
+    const int q = lr.q0 + slot, c = *lr.count;
+    if (q >= (c < lr.n ? c : lr.n)) return -1;
+    const int r = lr.rows[q];
+    return r >= 0 && r < lr.n ? r : -1;
+}
+
 // ---- token embedding
 
-// grid (1 + ceil((A - 1) / 32) + 7, rows): tile 0 is the ego, then the partner tiles, then the road tiles
+// grid (1 + ceil((A - 1) / 32) + 7, rows): tile 0 is the ego, then the partner tiles, then the road tiles.  List = (BCRows): obs
+// is the whole call's, X is indexed by slot
+template <class... List>
 __global__ __launch_bounds__(64) void k_bc_embed(BCDims d, BCLayout L, const float *__restrict__ blob, const float *__restrict__ obs,
-                                                 float *__restrict__ X) {
+                                                 float *__restrict__ X, List... lr) {
     const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
-    const int b = blockIdx.y, tile = blockIdx.x;
+    const int slot = blockIdx.y, tile = blockIdx.x;
+    const int b = bc_sample(slot, lr...);
+    if constexpr (sizeof...(List) > 0) {
+        if (b < 0) return;
+    }
     const int ptiles = (d.A - 1 + 31) / 32;
     const int kind = tile == 0 ? 0 : tile <= ptiles ? 1 : 2;
     const int count = kind == 0 ? 1 : kind == 1 ? d.A - 1 : ROADS;
@@ -65,16 +97,20 @@ __global__ __launch_bounds__(64) void k_bc_embed(BCDims d, BCLayout L, const flo
             for (int r = 0; r < 16; r++) a[t][r] = tanhf(o[t][r]);
     }
     const int tok = (kind == 0 ? 0 : kind == 1 ? 1 : d.A) + e;
-    if (live) store_tok(X + ((size_t)b * d.L + tok) * F, a, h);
+    if (live) store_tok(X + ((size_t)slot * d.L + tok) * F, a, h);
 }
 
 // ---- attention
 
-// grid (sum of tiles, rows)
+// grid (sum of tiles, rows).  Reads and writes the scratch only: b is the slot, List = (BCRows) says which slots hold a sample
+template <class... List>
 __global__ __launch_bounds__(64) void k_bc_kv(BCDims d, Segs sg, const float *__restrict__ blob, const float *__restrict__ X,
-                                              float *__restrict__ Kb, float *__restrict__ Vb) {
+                                              float *__restrict__ Kb, float *__restrict__ Vb, List... lr) {
     const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
     const int b = blockIdx.y;
+    if constexpr (sizeof...(List) > 0) {
+        if (bc_sample(b, lr...) < 0) return;
+    }
     int tile = blockIdx.x;
     const bool second = tile >= sg.s[0].tiles;
     const Seg &s = sg.s[second ? 1 : 0];
@@ -95,16 +131,22 @@ __device__ __forceinline__ float *bc_save_o(float *osave, float *) { return osav
 __device__ __forceinline__ float *bc_save_ml(float *, float *ml) { return ml; }
 
 // grid (sum of tiles, rows).  Save = (float *osave, float *ml): also store the attention output before o_proj (osave [b][token][64]) and per (token, head) the softmax's final running
-// max and its sum (ml [b][token][8]: m of the four heads, then the four sums), for the backward
+// max and its sum (ml [b][token][8]: m of the four heads, then the four sums), for the backward.  Save = (BCRows): the forward
+// on a row list, the masks are the whole call's, X / K / V are indexed by slot
 template <class... Save>
 __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *__restrict__ blob,
                                                 const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
                                                 float *__restrict__ X, const float *__restrict__ Kb, const float *__restrict__ Vb,
                                                 Save... save) {
-    constexpr bool SAVE = sizeof...(Save) > 0;
+    constexpr bool SAVE = sizeof...(Save) == 2, LIST = sizeof...(Save) == 1;
     __shared__ unsigned char msk[MAX_TOKENS];
     const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
-    const int b = blockIdx.y;
+    const int slot = blockIdx.y;
+    int b = slot;
+    if constexpr (LIST) {
+        b = bc_sample(slot, save...);
+        if (b < 0) return;
+    }
     int tile = blockIdx.x;
     const bool second = tile >= sg.s[0].tiles;
     const Seg &s = sg.s[second ? 1 : 0];
@@ -115,7 +157,7 @@ __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *
     const float *__restrict__ w = blob + s.w;
     const int qi = tile * 32 + col;
     const bool live = qi < ntok;
-    const size_t seg_at = ((size_t)b * d.L + s.tok0) * F;
+    const size_t seg_at = ((size_t)slot * d.L + s.tok0) * F;
     float *__restrict__ xrow = X + seg_at + (size_t)(live ? qi : ntok - 1) * F;
     f16v x[2], q[2], o[2];
     load_tok(xrow, x, h);
@@ -219,16 +261,22 @@ __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *
 
 // ---- cross attention, context, head, rule: a wave per sample, lane per feature
 
+// grid (rows).  List = (BCRows): the masks and every pointer of `a` are the whole call's, X / K / V are indexed by slot
+template <class... List>
 __global__ __launch_bounds__(64) void k_bc_head(BCDims d, BCLayout L, BCHeadArgs a, const float *__restrict__ blob,
                                                 const unsigned char *__restrict__ pm, const unsigned char *__restrict__ rm,
                                                 const float *__restrict__ X, const float *__restrict__ Kb,
-                                                const float *__restrict__ Vb) {
+                                                const float *__restrict__ Vb, List... lr) {
     __shared__ float sc[4][ROADS];
     __shared__ float ctx[CTX];
     __shared__ float vec[F];
     __shared__ float raw[MAX_HEAD_OUT];
-    const int lane = threadIdx.x, b = blockIdx.x, hd = lane >> 4;
-    const size_t base = (size_t)b * d.L * F;
+    const int lane = threadIdx.x, slot = blockIdx.x, hd = lane >> 4;
+    const int b = bc_sample(slot, lr...);
+    if constexpr (sizeof...(List) > 0) {
+        if (b < 0) return;
+    }
+    const size_t base = (size_t)slot * d.L * F;
     const float xq = X[base + lane];  // ro_attn's token 0: the query of both cross attentions and the context's first third
     ctx[lane] = xq;
     for (int ci = 0; ci < 2; ci++) {
@@ -357,7 +405,7 @@ void launch_bc_self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned 
     const Segs sg = bc_layer_segs(p, layer);
     unsigned tiles = 0;
     for (int i = 0; i < sg.n; i++) tiles += (unsigned)sg.s[i].tiles;
-    hipLaunchKernelGGL(k_bc_kv, dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
+    hipLaunchKernelGGL(k_bc_kv<>, dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb);
     if (osave)
         hipLaunchKernelGGL((k_bc_attn<float *, float *>), dim3(tiles, (unsigned)rows), dim3(64), 0, st, d, sg, p.blob, pm, rm, X, Kb, Vb,
                            osave, ml);
@@ -367,7 +415,7 @@ void launch_bc_self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned 
 
 void launch_bc_cross_kv(const gd_bc_policy &p, hipStream_t st, int rows, const float *X, float *Kb, float *Vb) {
     const Segs sg = bc_cross_segs(p);
-    hipLaunchKernelGGL(k_bc_kv, dim3((unsigned)(sg.s[0].tiles + sg.s[1].tiles), (unsigned)rows), dim3(64), 0, st, bc_dims(p), sg, p.blob,
+    hipLaunchKernelGGL(k_bc_kv<>, dim3((unsigned)(sg.s[0].tiles + sg.s[1].tiles), (unsigned)rows), dim3(64), 0, st, bc_dims(p), sg, p.blob,
                        X, Kb, Vb);
 }
 
@@ -375,7 +423,7 @@ void launch_bc_embed(const gd_bc_policy &p, hipStream_t st, const float *obs, in
     const int A = p.max_agents;
     const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
     const int etiles = 1 + (A - 1 + 31) / 32 + (ROADS + 31) / 32;
-    hipLaunchKernelGGL(k_bc_embed, dim3((unsigned)etiles, (unsigned)rows), dim3(64), 0, st, bc_dims(p), L, p.blob, obs, X);
+    hipLaunchKernelGGL(k_bc_embed<>, dim3((unsigned)etiles, (unsigned)rows), dim3(64), 0, st, bc_dims(p), L, p.blob, obs, X);
 }
 
 // obs, the masks, u, z, expert_actions and every output are the WHOLE call's; the chunk is its rows r0 .. r0 + rows
@@ -398,7 +446,7 @@ void launch_bc_head(const gd_bc_policy &p, hipStream_t st, const unsigned char *
     a.nll = out.nll ? out.nll + r0 : nullptr;
     a.ego_attn_score = out.ego_attn_score ? out.ego_attn_score + (size_t)r0 * 4 * (A - 1) : nullptr;
     a.component = out.component ? out.component + r0 : nullptr;
-    hipLaunchKernelGGL(k_bc_head, dim3((unsigned)rows), dim3(64), 0, st, bc_dims(p), L, a, p.blob, pm, rm, X, Kb, Vb);
+    hipLaunchKernelGGL(k_bc_head<>, dim3((unsigned)rows), dim3(64), 0, st, bc_dims(p), L, a, p.blob, pm, rm, X, Kb, Vb);
 }
 
 void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
@@ -414,6 +462,42 @@ void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, 
         for (int i = 0; i < p.fusion_layers + p.branch_layers; i++) launch_bc_self_layer(p, st, pm, rm, rows, i, X, Kb, Vb, nullptr, nullptr);
         launch_bc_cross_kv(p, st, rows, X, Kb, Vb);
         launch_bc_head(p, st, partner_mask, road_mask, r0, rows, deterministic, u, z, expert_actions, out, X, Kb, Vb);
+    }
+}
+
+// The forward on a row list (gd_bc_forward_rows): every chunk of list positions with the full forward's grids -- the host does
+// not know the list's length -- on the list instantiations; a chunk past the list is workgroups that return at their first load.
+void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                            const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                            const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows, const int32_t *count) {
+    const BCDims d = bc_dims(p);
+    const int A = p.max_agents, C = p.n_components;
+    const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, C);
+    const size_t per = (size_t)p.chunk_rows * d.L * F;
+    float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
+    const unsigned etiles = (unsigned)(1 + (A - 1 + 31) / 32 + (ROADS + 31) / 32);
+    const Segs cross = bc_cross_segs(p);
+    BCHeadArgs a{};
+    a.head_layers = p.head_layers, a.C = C, a.deterministic = deterministic ? 1 : 0, a.clip = p.clip_value;
+    a.u = u, a.z = z, a.expert = expert_actions;
+    a.context = out.context, a.means = out.means, a.logcov = out.log_covariances, a.cov = out.covariances;
+    a.weights = out.weights, a.actions = out.actions, a.nll = out.nll, a.ego_attn_score = out.ego_attn_score;
+    a.component = out.component;
+    for (int q0 = 0; q0 < n; q0 += p.chunk_rows) {
+        const unsigned slots = (unsigned)std::min(p.chunk_rows, n - q0);
+        const BCRows lr{rows, count, q0, n};
+        hipLaunchKernelGGL(k_bc_embed<BCRows>, dim3(etiles, slots), dim3(64), 0, st, d, L, p.blob, obs, X, lr);
+        for (int i = 0; i < p.fusion_layers + p.branch_layers; i++) {
+            const Segs sg = bc_layer_segs(p, i);
+            unsigned tiles = 0;
+            for (int k = 0; k < sg.n; k++) tiles += (unsigned)sg.s[k].tiles;
+            hipLaunchKernelGGL(k_bc_kv<BCRows>, dim3(tiles, slots), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb, lr);
+            hipLaunchKernelGGL(k_bc_attn<BCRows>, dim3(tiles, slots), dim3(64), 0, st, d, sg, p.blob, partner_mask, road_mask, X, Kb, Vb,
+                               lr);
+        }
+        hipLaunchKernelGGL(k_bc_kv<BCRows>, dim3((unsigned)(cross.s[0].tiles + cross.s[1].tiles), slots), dim3(64), 0, st, d, cross, p.blob,
+                           X, Kb, Vb, lr);
+        hipLaunchKernelGGL(k_bc_head<BCRows>, dim3(slots), dim3(64), 0, st, d, L, a, p.blob, partner_mask, road_mask, X, Kb, Vb, lr);
     }
 }
 

@@ -1925,40 +1925,59 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     });
 }
 
-// The closed-loop episode (bc_rollout.hip): gd_record_expert's loop with the policy where the logged action was.
-int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
-    if (!s || !p || !b) return fail(GD_ERR_INVALID, "gd_bc_rollout: null argument");
+// everything gd_bc_rollout refuses, for gd_bc_rollout_compact too; GD_OK when everything is in order
+static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
+    const std::string w = std::string(who) + ": ";
+    if (!s || !p || !b) return fail(GD_ERR_INVALID, w + "null argument");
     if (!b->row_slot || !b->row_of_slot || !b->window || !b->partner_mask || !b->road_mask || !b->partner_value || !b->row_actions ||
         !b->dead || !b->goal_achieved || !b->off_road || !b->veh_collision || !b->goal_step || !b->off_road_step ||
         !b->init_goal_dist || !b->goal_dist || !b->any_alive || !b->summary)
-        return fail(GD_ERR_INVALID, "gd_bc_rollout: every buffer but the per-step records is required");
-    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, "gd_bc_rollout: n_rows must be in [1, 2^20]");
+        return fail(GD_ERR_INVALID, w + "every buffer but the per-step records is required");
+    if (b->n_rows < 1 || b->n_rows > (1 << 20)) return fail(GD_ERR_INVALID, w + "n_rows must be in [1, 2^20]");
     if (n_steps < 1 || n_steps > GD_EPISODE_LEN)
-        return fail(GD_ERR_INVALID, "gd_bc_rollout: an episode has 91 steps, n_steps must be in [1, 91]");
+        return fail(GD_ERR_INVALID, w + "an episode has 91 steps, n_steps must be in [1, 91]");
     if (s->d.p.dynamicsModel == GD_DYNAMICS_STATE)
-        return fail(GD_ERR_INVALID, "gd_bc_rollout: the State dynamics model's actions have 10 columns, the policy's have 3");
-    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, "gd_bc_rollout: the policy's max_agents differs from the simulator's");
+        return fail(GD_ERR_INVALID, w + "the State dynamics model's actions have 10 columns, the policy's have 3");
+    if (p->max_agents != s->A) return fail(GD_ERR_INVALID, w + "the policy's max_agents differs from the simulator's");
     gd_bc_outputs out{};
     out.actions = b->row_actions;
     if (const char *why = bc_forward_problem(p, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic, b->u, b->z,
                                              nullptr, &out))
-        return fail(GD_ERR_INVALID, std::string("gd_bc_rollout: ") + why);
+        return fail(GD_ERR_INVALID, w + why);
     if (misaligned(b->window, 16) || misaligned(b->goal_achieved, 4) || misaligned(b->off_road, 4) || misaligned(b->veh_collision, 4) ||
         misaligned(b->goal_step, 4) || misaligned(b->off_road_step, 4) || misaligned(b->init_goal_dist, 4) ||
         misaligned(b->goal_dist, 4) || misaligned(b->any_alive, 4) || misaligned(b->summary, 4) || misaligned(b->row_slot, 4) ||
         misaligned(b->row_of_slot, 4) || misaligned(b->actions, 4) || misaligned(b->ego_global_pos, 4) ||
         misaligned(b->ego_global_rot, 4))
-        return fail(GD_ERR_INVALID, "gd_bc_rollout: window must be 16-byte aligned, float and int32 buffers 4-byte aligned");
+        return fail(GD_ERR_INVALID, w + "window must be 16-byte aligned, float and int32 buffers 4-byte aligned");
     if (s->d.pack && s->d.pack_only)
-        return fail(GD_ERR_UNSUPPORTED, "gd_bc_rollout: a packed buffer is attached with only = 1: the raw rows are stale");
+        return fail(GD_ERR_UNSUPPORTED, w + "a packed buffer is attached with only = 1: the raw rows are stale");
+    return GD_OK;
+}
+
+// The loop of both drivers (bc_rollout.hip): r == nullptr is gd_bc_rollout's forward on all N rows, otherwise the list of the
+// rows with dead[n] == 0 in the loop.  When iteration t does not exist every row is dead: the list is empty and every
+// workgroup of the forward returns at its first load.
+static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                          int32_t n_steps) {
     return guarded([&]() {
         const size_t N = static_cast<size_t>(b->n_rows);
+        gd_bc_outputs out{};
+        out.actions = b->row_actions;
         gd::launch_bc_rollout_post(s->d, s->stream, *b, -1, true);
         HIP_CHECK(hipGetLastError());
         for (int t = 0; t < n_steps; t++) {
+            const float *u = b->u ? b->u + t * N : nullptr, *z = b->z ? b->z + t * N * 3 : nullptr;
             gd::launch_bc_rollout_row(s->d, s->stream, *b, t, p->num_stack);
-            gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
-                                  b->u ? b->u + t * N : nullptr, b->z ? b->z + t * N * 3 : nullptr, nullptr, out);
+            if (r) {
+                gd::launch_live_rows(s->stream, b->dead, b->n_rows, r->rows, r->count, r->scratch,
+                                     r->live_count ? r->live_count + t : nullptr, true);
+                gd::launch_bc_forward_rows(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u,
+                                           z, nullptr, out, r->rows, r->count);
+            } else {
+                gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
+                                      nullptr, out);
+            }
             gd::launch_bc_rollout_actions(s->d, s->stream, *b, t);
             HIP_CHECK(hipGetLastError());
             s->step();
@@ -1968,6 +1987,12 @@ int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers 
         gd::launch_bc_rollout_summary(s->stream, *b);
         HIP_CHECK(hipGetLastError());
     });
+}
+
+// The closed-loop episode: gd_record_expert's loop with the policy where the logged action was.
+int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
+    if (const int rc = bc_rollout_problem("gd_bc_rollout", s, p, b, n_steps)) return rc;
+    return bc_rollout_run(s, p, b, nullptr, n_steps);
 }
 
 // everything gd_policy_rollout refuses, for gd_policy_rollout_compact too; GD_OK when everything is in order
@@ -2084,6 +2109,33 @@ int gd_policy_rollout_compact(gd_sim *s, const gd_policy *p, const gd_policy_rol
     if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     if (const int rc = policy_rollout_problem(who, s, p, b, n_steps)) return rc;
     return policy_rollout_run(s, p, b, r, n_steps);
+}
+
+int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                       int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                       const int32_t *rows, const int32_t *count, void *stream) {
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
+    if (!why) why = row_list_problem(rows, count);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_forward_rows(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+                                   expert_actions, *out, rows, count);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// gd_bc_rollout with the list of live rows and gd_bc_forward_rows in the loop.  The list is checked first: it needs no simulator.
+int gd_bc_rollout_compact(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                          int32_t n_steps) {
+    const char *who = "gd_bc_rollout_compact";
+    if (!s || !p || !b || !r) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
+    const char *why = row_list_problem(r->rows, r->count);
+    if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
+    if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
+    if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    if (const int rc = bc_rollout_problem(who, s, p, b, n_steps)) return rc;
+    return bc_rollout_run(s, p, b, r, n_steps);
 }
 
 // everything gd_bc_backward refuses; nullptr when everything is in order

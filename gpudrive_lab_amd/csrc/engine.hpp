@@ -302,9 +302,10 @@ void launch_policy_evaluate(const gd_policy &p, const gd_dropout &d, hipStream_t
 void launch_policy_forward_rows(const gd_policy &p, const gd_dropout *d, hipStream_t st, const float *obs, const float *u,
                                 bool deterministic, int64_t *actions, float *logprob, float *entropy, float *value,
                                 float *logits_out, const int32_t *rows, const int32_t *count);  // policy.hip
-// live_rows.hip: mask -> ascending row list and its length (count_copy: a second place for the length, or null); two launches
+// live_rows.hip: mask -> ascending row list and its length (count_copy: a second place for the length, or null); two launches.
+// zero: list the rows whose byte is zero instead of those whose byte is set
 void launch_live_rows(hipStream_t st, const uint8_t *mask, int n, int32_t *rows, int32_t *count, int32_t *scratch,
-                      int32_t *count_copy);
+                      int32_t *count_copy, bool zero = false);
 void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, const gd_dropout &d, hipStream_t st, const float *obs,
                             const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
                             float *grad);  // policy_grad.hip
@@ -320,6 +321,11 @@ long long bc_scratch_floats(int max_agents, int chunk_rows);  // bc_policy.hip: 
 void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                        const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                        const float *expert_actions, const gd_bc_outputs &out);  // bc_policy.hip
+// the forward on a device-resident row list: every chunk of list positions is launched, scratch by position, the rest by row
+void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                            const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                            const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows,
+                            const int32_t *count);  // bc_policy.hip
 void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,
                                float *acc);  // bc_policy.hip (one launch)
 // bc_policy.hip: the forward's launches one by one, for the backward's recomputation (bc_grad.hip).  The masks of

@@ -5,6 +5,7 @@
 //                  shuffle scan over the wave, the four waves through LDS) and stores its indices in order; the last lane of
 //                  the last block stores the total to *count, and to *count_copy when the caller keeps a record of it
 // No atomics: a position is a sum of integers, so equal input gives equal bytes.  rows[*count .. n) is not written.
+// ZERO instantiates both kernels for the complement, the rows whose byte IS zero (gd_bc_rollout_compact lists dead[n] == 0).
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
@@ -16,11 +17,12 @@ namespace {
 constexpr int BLOCK = GD_LIVE_ROWS_BLOCK, LANES = 256, PER_LANE = BLOCK / LANES, WAVES = LANES / 64;
 
 // the lane's four rows: bit j of the result is row base + j
+template <bool ZERO>
 __device__ __forceinline__ unsigned lane_bits(const uint8_t *__restrict__ mask, int n, int base) {
     unsigned bits = 0;
 #pragma unroll
     for (int j = 0; j < PER_LANE; j++)
-        if (base + j < n && mask[base + j] != 0) bits |= 1u << j;
+        if (base + j < n && (mask[base + j] != 0) != ZERO) bits |= 1u << j;
     return bits;
 }
 
@@ -30,10 +32,11 @@ __device__ __forceinline__ int wave_total(int v) {
     return v;
 }
 
+template <bool ZERO>
 __global__ __launch_bounds__(LANES) void k_live_count(const uint8_t *__restrict__ mask, int n, int32_t *__restrict__ scratch) {
     __shared__ int s_wave[WAVES];
     const int tid = threadIdx.x;
-    const int c = wave_total(__popc(lane_bits(mask, n, blockIdx.x * BLOCK + tid * PER_LANE)));
+    const int c = wave_total(__popc(lane_bits<ZERO>(mask, n, blockIdx.x * BLOCK + tid * PER_LANE)));
     if ((tid & 63) == 0) s_wave[tid >> 6] = c;
     __syncthreads();
     if (tid == 0) {
@@ -44,13 +47,14 @@ __global__ __launch_bounds__(LANES) void k_live_count(const uint8_t *__restrict_
     }
 }
 
+template <bool ZERO>
 __global__ __launch_bounds__(LANES) void k_live_write(const uint8_t *__restrict__ mask, int n, const int32_t *__restrict__ scratch,
                                                       int32_t *__restrict__ rows, int32_t *__restrict__ count,
                                                       int32_t *__restrict__ count_copy) {
     __shared__ int s_before[WAVES], s_wave[WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, block = blockIdx.x;
     const int base = block * BLOCK + tid * PER_LANE;
-    const unsigned bits = lane_bits(mask, n, base);
+    const unsigned bits = lane_bits<ZERO>(mask, n, base);
     const int c = __popc(bits);
     int incl = c;  // the inclusive scan of c over the wave
 #pragma unroll
@@ -83,10 +87,17 @@ __global__ __launch_bounds__(LANES) void k_live_write(const uint8_t *__restrict_
 }  // namespace
 
 void launch_live_rows(hipStream_t st, const uint8_t *mask, int n, int32_t *rows, int32_t *count, int32_t *scratch,
-                      int32_t *count_copy) {
+                      int32_t *count_copy, bool zero) {
     const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(k_live_count, dim3(blocks), dim3(LANES), 0, st, mask, n, scratch);
-    hipLaunchKernelGGL(k_live_write, dim3(blocks), dim3(LANES), 0, st, mask, n, (const int32_t *)scratch, rows, count, count_copy);
+    if (zero) {
+        hipLaunchKernelGGL(k_live_count<true>, dim3(blocks), dim3(LANES), 0, st, mask, n, scratch);
+        hipLaunchKernelGGL(k_live_write<true>, dim3(blocks), dim3(LANES), 0, st, mask, n, (const int32_t *)scratch, rows, count,
+                           count_copy);
+    } else {
+        hipLaunchKernelGGL(k_live_count<false>, dim3(blocks), dim3(LANES), 0, st, mask, n, scratch);
+        hipLaunchKernelGGL(k_live_write<false>, dim3(blocks), dim3(LANES), 0, st, mask, n, (const int32_t *)scratch, rows, count,
+                           count_copy);
+    }
 }
 
 }  // namespace gd

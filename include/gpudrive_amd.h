@@ -894,6 +894,40 @@ typedef struct gd_policy_rollout_rows {
  * reserved != 0. */
 int gd_policy_rollout_compact(gd_sim *sim, const gd_policy *policy, const gd_policy_rollout_buffers *buffers,
                               const gd_policy_rollout_rows *rows, int32_t n_steps);
+/* gd_bc_forward on the rows of a list: rows [n] int32 of which the first *count are read, count one int32 on the device
+ * (gd_live_rows writes both).  For a listed row r the call reads obs[r], both masks' row r, u[r], z[r] and expert_actions[r] and
+ * writes index r of every output given (context, means, log_covariances, covariances, weights, actions, nll, ego_attn_score,
+ * component), every bit what gd_bc_forward writes for that row: no result of a sample depends on the samples beside it, and the
+ * draw is keyed on r, not on the position in the list.  Rows that are not listed are NOT written, in any output.  A list
+ * position q belongs to chunk q / chunk_rows and to slot q % chunk_rows of p->scratch, which holds nothing specified afterwards.
+ * The host does not know the length: all ceil(n / chunk_rows) chunks are launched with gd_bc_forward's grids, 2 fusion_layers
+ * + 2 branch_layers + 3 launches each, and every workgroup whose position is past *count returns at its first load.  An entry
+ * outside [0, n) is skipped and a count above n is read as n, for memory safety only; entries must be distinct (a row listed
+ * twice is written by two workgroups).  No host synchronisation, no allocation, no atomics.
+ * GD_ERR_INVALID, before any launch: whatever gd_bc_forward refuses, a null or not 4-byte aligned rows or count. */
+int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                       int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                       const int32_t *rows, const int32_t *count, void *stream);
+/* gd_bc_rollout with the list in the loop.  Device pointers owned by the caller; N = buffers->n_rows. */
+typedef struct gd_bc_rollout_rows {
+    int32_t *rows;               /* [N] the list of the current step */
+    int32_t *count;              /* [1] its length */
+    int32_t *scratch;            /* gd_live_rows' scratch for n = N */
+    int32_t *live_count;         /* [91] the length of step t's list (the rows not dead before step t), or NULL; entries
+                                  * t >= n_steps are not written */
+    int32_t reserved;            /* 0 */
+} gd_bc_rollout_rows;
+/* For t in [0, n_steps): the row kernel of gd_bc_rollout on every row (a dead row's window, masks and goal distance keep
+ * moving), the list of the rows with dead[n] == 0 (gd_live_rows' two launches on the complement of the byte; the second also
+ * stores live_count[t]), gd_bc_forward_rows on that list with u + t * N and z + t * N * 3, then the action kernel, the step and
+ * the bookkeeping kernel of gd_bc_rollout, and its summary at the end: 2 launches per step more than gd_bc_rollout.  When
+ * iteration t does not exist every row is dead, the list is empty and the forward returns at once.  Every output
+ * gd_bc_rollout defines is the same, bit for bit, but row_actions: a dead row's holds the action of the last step the row was
+ * live at, not the last step's (the action kernel reads live rows only; `actions` records zeros for dead rows either way).
+ * GD_ERR_INVALID / GD_ERR_UNSUPPORTED: whatever gd_bc_rollout refuses; a null rows argument, a null or not 4-byte aligned rows,
+ * count or scratch, a live_count that is not 4-byte aligned, reserved != 0. */
+int gd_bc_rollout_compact(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers,
+                          const gd_bc_rollout_rows *rows, int32_t n_steps);
 /* The hidden states a linear probe reads (the reference's forward hooks, baselines/il/linear_probing.py:68-95): out [n][A][64]
  * float32, 16-byte aligned, receives tokens 0 .. A - 1 (the ego, then the partners) of the last_hidden_state of the tapped
  * block -- fusion_attn after its fusion_layers self layers, or ro_attn after its branch_layers more.  Per chunk gd_bc_forward's
