@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("ClosedLoopPPO", "PolicyEpisode"):
         from . import ppo_rollout
         return getattr(ppo_rollout, name)
+    if name in ("ClosedLoopMultiPPO", "MultiPolicyEpisode"):
+        from . import multi_policy_rollout
+        return getattr(multi_policy_rollout, name)
     if name == "DeviceLinearProbe":
         from .lp_probe import DeviceLinearProbe
         return DeviceLinearProbe

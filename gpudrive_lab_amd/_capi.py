@@ -249,6 +249,29 @@ class GdPolicyRolloutRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rows", "count", "scratch", "live_count")] + [("reserved", C.c_int32)]
 
 
+POLICY_SET_MAX = 8    # GD_POLICY_SET_MAX: the policies of one gd_policy_set
+OWNED_ROWS_ALIGN = 32  # every segment of an owned list starts at a multiple of this (csrc/multi_policy_rule.hpp)
+
+
+class GdPolicySet(C.Structure):
+    """gd_policy_set: the policies of one forward on an owned list and the call's own position-indexed scratch (device
+    pointers)."""
+    _fields_ = [("n_policies", C.c_int32), ("reserved", C.c_int32), ("policy", GdPolicy * POLICY_SET_MAX),
+                ("features", C.c_void_p), ("logits", C.c_void_p)]
+
+
+MULTI_POLICY_WORLD = ("goal_achieved_count", "frac_goal_achieved", "collided_count", "frac_collided", "off_road_count",
+                      "frac_off_road", "n_rows")  # gd_multi_policy_buffers: [P][W] each
+MULTI_POLICY_SUMMARY = ("goal_achieved", "collided", "off_road", "n_rows")  # gd_multi_policy_buffers.summary, per policy
+
+
+class GdMultiPolicyBuffers(C.Structure):
+    """gd_multi_policy_buffers: the owners, the owned list and its scratch, the denominator, the per-policy results and the
+    optional record of the segment lengths of one multi-policy episode (device pointers)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("owner", "rows", "start", "count", "scratch", "denominator") + MULTI_POLICY_WORLD
+                 + ("summary", "list_count")] + [("reserved", C.c_int32)])
+
+
 class GdBCRolloutRows(C.Structure):
     """gd_bc_rollout_rows: gd_policy_rollout_rows for the closed-loop BC driver (device pointers)."""
     _fields_ = [(n, C.c_void_p) for n in ("rows", "count", "scratch", "live_count")] + [("reserved", C.c_int32)]
@@ -306,7 +329,8 @@ SYMBOLS = [
     "gd_policy_evaluate", "gd_policy_backward", "gd_ppo_loss", "gd_ppo_adam", "gd_ppo_update",
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
-    "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
+    "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_owned_rows", "gd_policy_forward_owned",
+    "gd_multi_policy_rollout", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -407,6 +431,10 @@ def lib():
     L.gd_policy_forward_rows.argtypes = [C.POINTER(GdPolicy), D, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 8
     L.gd_policy_rollout_compact.argtypes = [C.c_void_p, C.POINTER(GdPolicy), C.POINTER(GdPolicyRolloutBuffers),
                                             C.POINTER(GdPolicyRolloutRows), C.c_int32]
+    L.gd_owned_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    L.gd_policy_forward_owned.argtypes = [C.POINTER(GdPolicySet), C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+    L.gd_multi_policy_rollout.argtypes = [C.c_void_p, C.POINTER(GdPolicySet), C.POINTER(GdPolicyRolloutBuffers),
+                                          C.POINTER(GdMultiPolicyBuffers), C.c_int32]
     L.gd_bc_forward_rows.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
                                      [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs)] + [C.c_void_p] * 3)
     L.gd_bc_rollout_compact.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers),

@@ -2111,6 +2111,113 @@ int gd_policy_rollout_compact(gd_sim *s, const gd_policy *p, const gd_policy_rol
     return policy_rollout_run(s, p, b, r, n_steps);
 }
 
+// everything gd_owned_rows refuses; nullptr when everything is in order
+static const char *owned_rows_problem(const uint8_t *mask, const uint8_t *owner, int32_t n, int32_t n_policies, const int32_t *rows,
+                                      const int32_t *start, const int32_t *count, const int32_t *scratch, const int32_t *count_copy) {
+    if (!mask || !owner || !rows || !start || !count || !scratch) return "null argument";
+    if (misaligned(rows, 4) || misaligned(start, 4) || misaligned(count, 4) || misaligned(scratch, 4) || misaligned(count_copy, 4))
+        return "rows, start, count, scratch and count_copy must be 4-byte aligned";
+    if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
+    if (n_policies < 1 || n_policies > GD_POLICY_SET_MAX) return "n_policies must be in [1, 8]";
+    return nullptr;
+}
+
+int gd_owned_rows(const uint8_t *mask, const uint8_t *owner, int32_t n, int32_t n_policies, int32_t *rows, int32_t *start,
+                  int32_t *count, int32_t *scratch, int32_t *count_copy, void *stream) {
+    if (const char *why = owned_rows_problem(mask, owner, n, n_policies, rows, start, count, scratch, count_copy))
+        return fail(GD_ERR_INVALID, std::string("gd_owned_rows: ") + why);
+    return guarded([&]() {
+        gd::launch_owned_rows(static_cast<hipStream_t>(stream), mask, owner, n, n_policies, rows, start, count, scratch, count_copy);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// The set's policy i as the forward on an owned list runs it: the set's own scratch for the policy's.
+static gd_policy set_policy(const gd_policy_set *set, int i) {
+    gd_policy q = set->policy[i];
+    q.features = set->features, q.logits = set->logits;
+    return q;
+}
+
+// everything gd_policy_forward_owned refuses; nullptr when everything is in order
+static const char *policy_set_problem(const gd_policy_set *set, const float *obs, const float *u, int32_t deterministic,
+                                      const int64_t *actions, const float *logprob, const float *entropy, const float *value,
+                                      const float *logits_out) {
+    if (!set) return "null argument";
+    if (set->n_policies < 1 || set->n_policies > GD_POLICY_SET_MAX) return "n_policies must be in [1, 8]";
+    if (set->reserved != 0) return "the set's reserved must be 0";
+    if (!set->features || !set->logits) return "the set's features and logits are required";
+    for (int i = 0; i < set->n_policies; i++) {
+        const gd_policy q = set_policy(set, i), &f = set->policy[0];
+        if (const char *why = policy_forward_problem(&q, obs, u, deterministic, actions, logprob, entropy, value, logits_out))
+            return why;
+        if (q.num_rows != f.num_rows || q.max_agents != f.max_agents || q.ego_width != f.ego_width || q.n_actions != f.n_actions)
+            return "the policies of a set must agree in num_rows, max_agents, ego_width and n_actions";
+    }
+    return nullptr;
+}
+
+static const char *owned_list_problem(const int32_t *rows, const int32_t *start, const int32_t *count) {
+    if (!rows || !start || !count) return "rows, start and count are required";
+    if (misaligned(rows, 4) || misaligned(start, 4) || misaligned(count, 4)) return "rows, start and count must be 4-byte aligned";
+    return nullptr;
+}
+
+int gd_policy_forward_owned(const gd_policy_set *set, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
+                            float *logprob, float *entropy, float *value, float *logits_out, const int32_t *rows,
+                            const int32_t *start, const int32_t *count, void *stream) {
+    const char *why = policy_set_problem(set, obs, u, deterministic, actions, logprob, entropy, value, logits_out);
+    if (!why) why = owned_list_problem(rows, start, count);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_policy_forward_owned: ") + why);
+    return guarded([&]() {
+        gd::launch_policy_forward_owned(*set, static_cast<hipStream_t>(stream), obs, u, deterministic != 0, actions, logprob, entropy,
+                                        value, logits_out, rows, start, count);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// The multi-policy evaluator: gd_policy_rollout_compact's loop with the owned list for the live list, then the per-policy
+// metrics (multi_policy_rollout.hip).  The set and the list are checked first: they need no simulator.
+int gd_multi_policy_rollout(gd_sim *s, const gd_policy_set *set, const gd_policy_rollout_buffers *b, const gd_multi_policy_buffers *m,
+                            int32_t n_steps) {
+    const std::string w = "gd_multi_policy_rollout: ";
+    if (!s || !set || !b || !m) return fail(GD_ERR_INVALID, w + "null argument");
+    if (set->n_policies < 1 || set->n_policies > GD_POLICY_SET_MAX) return fail(GD_ERR_INVALID, w + "n_policies must be in [1, 8]");
+    const char *why = owned_rows_problem(b->live, m->owner, b->n_rows, set->n_policies, m->rows, m->start, m->count, m->scratch,
+                                         m->list_count);
+    if (!why && (!m->denominator || !m->goal_achieved_count || !m->frac_goal_achieved || !m->collided_count || !m->frac_collided ||
+                 !m->off_road_count || !m->frac_off_road || !m->n_rows || !m->summary))
+        why = "every buffer of gd_multi_policy_buffers but list_count is required";
+    if (!why && (misaligned(m->denominator, 4) || misaligned(m->goal_achieved_count, 4) || misaligned(m->frac_goal_achieved, 4) ||
+                 misaligned(m->collided_count, 4) || misaligned(m->frac_collided, 4) || misaligned(m->off_road_count, 4) ||
+                 misaligned(m->frac_off_road, 4) || misaligned(m->n_rows, 4) || misaligned(m->summary, 4)))
+        why = "the float buffers of gd_multi_policy_buffers must be 4-byte aligned";
+    if (!why && m->reserved != 0) why = "the multi-policy buffers' reserved must be 0";
+    if (why) return fail(GD_ERR_INVALID, w + why);
+    const gd_policy first = set_policy(set, 0);
+    if (const int rc = policy_rollout_problem("gd_multi_policy_rollout", s, &first, b, n_steps)) return rc;
+    if ((why = policy_set_problem(set, s->d.pack, b->u, b->deterministic, b->actions, b->logprob, b->entropy, b->value, nullptr)))
+        return fail(GD_ERR_INVALID, w + why);
+    return guarded([&]() {
+        const size_t N = static_cast<size_t>(b->n_rows);
+        const int P = set->n_policies;
+        for (int t = 0; t < n_steps; t++) {
+            gd::launch_owned_rows(s->stream, b->live, m->owner, b->n_rows, P, m->rows, m->start, m->count, m->scratch,
+                                  m->list_count ? m->list_count + t * P : nullptr);
+            gd::launch_policy_forward_owned(*set, s->stream, s->d.pack, b->u ? b->u + t * N : nullptr, b->deterministic != 0,
+                                            b->actions, b->logprob, b->entropy, b->value, nullptr, m->rows, m->start, m->count);
+            gd::launch_policy_rollout_actions(s->d, s->stream, *b, t);
+            HIP_CHECK(hipGetLastError());
+            s->step();
+            gd::launch_policy_rollout_book(s->d, s->stream, *b, t);
+            HIP_CHECK(hipGetLastError());
+        }
+        gd::launch_policy_rollout_finish(s->d, s->stream, *b, n_steps);
+        gd::launch_multi_policy_finish(s->d, s->stream, *b, *m, P);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
                        int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
                        const int32_t *rows, const int32_t *count, void *stream) {

@@ -306,6 +306,16 @@ void launch_policy_forward_rows(const gd_policy &p, const gd_dropout *d, hipStre
 // zero: list the rows whose byte is zero instead of those whose byte is set
 void launch_live_rows(hipStream_t st, const uint8_t *mask, int n, int32_t *rows, int32_t *count, int32_t *scratch,
                       int32_t *count_copy, bool zero = false);
+// owned_rows.hip: mask and owner -> the list with a segment per policy (multi_policy_rule.hpp); two launches.
+void launch_owned_rows(hipStream_t st, const uint8_t *mask, const uint8_t *owner, int n, int n_policies, int32_t *rows,
+                       int32_t *start, int32_t *count, int32_t *scratch, int32_t *count_copy);
+// policy.hip: the unmasked forward on an owned list, every row with its owner's weights; three launches.
+void launch_policy_forward_owned(const gd_policy_set &ps, hipStream_t st, const float *obs, const float *u, bool deterministic,
+                                 int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out,
+                                 const int32_t *rows, const int32_t *start, const int32_t *count);
+// multi_policy_rollout.hip: the per-policy counts per world and their summary; two launches.
+void launch_multi_policy_finish(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, const gd_multi_policy_buffers &m,
+                                int n_policies);
 void launch_policy_backward(const gd_policy &p, const gd_policy_grad &g, const gd_dropout &d, hipStream_t st, const float *obs,
                             const int64_t *actions, const float *d_logprob, const float *d_entropy, const float *d_value,
                             float *grad);  // policy_grad.hip

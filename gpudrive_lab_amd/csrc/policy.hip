@@ -24,10 +24,15 @@
 // wave (a lane column, a lane) is a POSITION of the device-resident list, reads the list's length and returns when it is past
 // it, computes row rows[position], keeps the scratch by position and stores the outputs of that row alone.  A row's result
 // never depends on the rows beside it, so a listed row gets the full forward's bits.
+// The forward on an owned list (gd_policy_forward_owned) is again the same three launches on sibling kernels,
+// k_policy_embed_owned, k_policy_tail_owned and k_policy_sample_owned: the list has a segment per policy, every segment starts
+// at a multiple of 32 (multi_policy_rule.hpp), so a wave of either kernel lies in ONE segment and takes the weights of that
+// segment's policy -- the blob pointers come by value, the segment index is wave-uniform and the chosen pointer stays scalar.
 #include <hip/hip_runtime.h>
 
 #include "dropout_rule.hpp"
 #include "engine.hpp"
+#include "multi_policy_rule.hpp"
 #include "policy_rule.hpp"
 
 namespace gd {
@@ -35,6 +40,7 @@ namespace gd {
 namespace {
 
 namespace DR = dropout_rule;
+namespace MP = multi_policy_rule;
 
 // DROP: the training-mode mask of one call (dropout_rule.hpp); `call` is the value of gd_dropout.call the kernel read
 struct DropCall {
@@ -423,6 +429,61 @@ __global__ __launch_bounds__(64) void k_policy_sample_rows_drop(int n, int na, c
     policy_sample_rows(n, na, logits, u, deterministic, actions, logprob, entropy, rows, count);
 }
 
+// The owned list as the kernels of gd_policy_forward_owned take it: the policies' blobs, the segmented list and the size of its
+// arrays (n + 32 P positions; features and logits are indexed by position and have as many rows)
+struct OwnedList {
+    const float *blob[GD_POLICY_SET_MAX];
+    const int32_t *rows, *start, *count;
+    int n_policies, positions;
+};
+
+// The embed kernel on an owned list: the wave of position q finds its segment, takes row rows[q] with that segment's weights
+// and stores features[q].  A wave in the padding or past the last segment, or whose entry is no row, returns at once.
+__global__ __launch_bounds__(256) void k_policy_embed_owned(gd_policy p, PolicyLayout L, OwnedList o, const float *__restrict__ obs,
+                                                            float *__restrict__ features) {
+    const int lane = threadIdx.x & 63;
+    const int pos = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (the wave's index: scalar)
+    const int seg = MP::segment_of(pos, o.n_policies, o.start, o.count, o.positions);
+    if (seg < 0) return;  // wave-uniform
+    const int row = o.rows[pos];
+    if (row < 0 || row >= p.num_rows) return;
+    p.blob = o.blob[seg];
+    policy_embed_row<false, false>(p, L, obs, features, nullptr, DR::Args{}, nullptr, lane, row, pos);
+}
+
+// The tail kernel on an owned list: workgroup g covers the positions 32 g .. 32 g + 31, which lie in one segment because every
+// segment starts at a multiple of 32.  A workgroup past its segment's end returns; a lane past the end computes the
+// segment's last position again and stores nothing, as does an entry that is no row.
+__global__ __launch_bounds__(64) void k_policy_tail_owned(gd_policy p, PolicyLayout L, OwnedList o, const float *__restrict__ features,
+                                                          float *__restrict__ logits, float *__restrict__ logits_out,
+                                                          float *__restrict__ value) {
+    const int lane = threadIdx.x;
+    const int first = blockIdx.x * 32;
+    const int seg = MP::segment_of(first, o.n_policies, o.start, o.count, o.positions);
+    if (seg < 0) return;  // wave-uniform
+    const int s = o.start[seg], c = o.count[seg];
+    const int end = c < o.positions - s ? s + c : o.positions;  // (first < end: the segment holds first)
+    const int pos = first + (lane & 31);
+    const int pc = pos < end ? pos : end - 1;
+    const int row = o.rows[pc];
+    const bool valid = row >= 0 && row < p.num_rows;
+    p.blob = o.blob[seg];
+    policy_tail_rows<false>(p, L, features, logits, logits_out, value, DR::Args{}, nullptr, lane, pc, valid ? row : 0,
+                            pos < end && valid, pc, valid ? row : 0);
+}
+
+// The sample kernel on an owned list: the lane of position q reads the scratch logits[q] and writes row rows[q]
+__global__ __launch_bounds__(64) void k_policy_sample_owned(int n, int na, OwnedList o, const float *__restrict__ logits,
+                                                            const float *__restrict__ u, int deterministic,
+                                                            int64_t *__restrict__ actions, float *__restrict__ logprob,
+                                                            float *__restrict__ entropy) {
+    const int pos = blockIdx.x * 64 + threadIdx.x;
+    if (MP::segment_of(pos, o.n_policies, o.start, o.count, o.positions) < 0) return;
+    const int row = o.rows[pos];
+    if (row < 0 || row >= n) return;
+    policy_sample_row(na, logits + (size_t)pos * na, u, deterministic, actions, logprob, entropy, row);
+}
+
 __global__ __launch_bounds__(64) void k_policy_sample(int n, int na, const float *__restrict__ logits, const float *__restrict__ u,
                                                       int deterministic, int64_t *__restrict__ actions,
                                                       float *__restrict__ logprob, float *__restrict__ entropy) {
@@ -521,6 +582,25 @@ void launch_policy_forward_rows(const gd_policy &p, const gd_dropout *d, hipStre
         hipLaunchKernelGGL(k_policy_sample_rows, sample, dim3(64), 0, st, n, p.n_actions, p.logits, u, deterministic ? 1 : 0,
                            actions, logprob, entropy, rows, count);
     }
+}
+
+// The forward on an owned list (gd_policy_forward_owned): three launches whatever the number of policies, with grids sized for
+// the n + 32 P positions of the list's arrays -- the host knows neither the lengths nor the starts.  Always the unmasked forward.
+void launch_policy_forward_owned(const gd_policy_set &ps, hipStream_t st, const float *obs, const float *u, bool deterministic,
+                                 int64_t *actions, float *logprob, float *entropy, float *value, float *logits_out,
+                                 const int32_t *rows, const int32_t *start, const int32_t *count) {
+    gd_policy p = ps.policy[0];
+    p.features = ps.features, p.logits = ps.logits;
+    const PolicyLayout L = policy_layout(p.ego_width, p.n_actions);
+    OwnedList o{};
+    for (int i = 0; i < ps.n_policies; i++) o.blob[i] = ps.policy[i].blob;
+    o.rows = rows, o.start = start, o.count = count, o.n_policies = ps.n_policies;
+    const int q = o.positions = MP::list_positions(p.num_rows, ps.n_policies);
+    hipLaunchKernelGGL(k_policy_embed_owned, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, st, p, L, o, obs, ps.features);
+    hipLaunchKernelGGL(k_policy_tail_owned, dim3((unsigned)((q + 31) / 32)), dim3(64), 0, st, p, L, o, (const float *)ps.features,
+                       ps.logits, logits_out, value);
+    hipLaunchKernelGGL(k_policy_sample_owned, dim3((unsigned)((q + 63) / 64)), dim3(64), 0, st, p.num_rows, p.n_actions, o,
+                       (const float *)ps.logits, u, deterministic ? 1 : 0, actions, logprob, entropy);
 }
 
 // p.features and p.logits are the caller-owned buffers of gd_policy_grad here

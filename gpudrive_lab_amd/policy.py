@@ -213,6 +213,179 @@ def live_rows(mask, out=None):
     return out
 
 
+def owned_rows_positions(n, n_policies):
+    """The positions of an owned list's arrays: n rows and 32 of padding per policy."""
+    return n + _capi.OWNED_ROWS_ALIGN * n_policies
+
+
+class OwnedRows:
+    """A device-resident row list with a segment per policy (`gd_owned_rows`): `rows` int32 [N + 32 P]; `start` int32 [P + 1],
+    every entry a multiple of 32; `count` int32 [P]; segment p is rows[start[p] : start[p] + count[p]], ascending, and the
+    positions from there to start[p + 1] hold -1; `scratch`, which `owned_rows` needs.  Nothing on the host knows the lengths.
+    A new one lists no row.  new: who makes the four arrays, as for `LiveRows`."""
+
+    def __init__(self, n, n_policies, device, new=None):
+        if not _is_int(n) or not 1 <= n <= MAX_ROWS:
+            raise ValueError("OwnedRows: N must be an int in [1, %d], got %r" % (MAX_ROWS, n))
+        if not _is_int(n_policies) or not 1 <= n_policies <= _capi.POLICY_SET_MAX:
+            raise ValueError("OwnedRows: the number of policies must be an int in [1, %d], got %r" % (_capi.POLICY_SET_MAX, n_policies))
+        if new is None:
+            new = lambda name, shape, dt, fill, dev: (torch.empty(shape, dtype=dt, device=dev) if fill is None  # noqa: E731
+                                                      else torch.full(shape, fill, dtype=dt, device=dev))
+        self.n, self.n_policies = n, n_policies
+        self.rows = new("owned_rows", (owned_rows_positions(n, n_policies),), torch.int32, None, device)
+        self.start = new("owned_start", (n_policies + 1,), torch.int32, 0, device)
+        self.count = new("owned_count", (n_policies,), torch.int32, 0, device)
+        self.scratch = new("owned_scratch", (n_policies * live_rows_scratch_ints(n),), torch.int32, None, device)
+
+    @staticmethod
+    def nbytes(n, n_policies):
+        """Bytes an OwnedRows holds: rows, start, count and scratch."""
+        return 4 * (owned_rows_positions(n, n_policies) + 2 * n_policies + 1 + n_policies * live_rows_scratch_ints(n))
+
+
+def owned_rows(mask, owner, n_policies=None, out=None):
+    """mask: a contiguous bool or uint8 tensor [N] on the GPU (a byte that is not zero is a live row); owner: a contiguous uint8
+    tensor [N] on the same device, the policy index of every row (a row whose owner is >= n_policies is listed nowhere).
+    Returns the `OwnedRows` (`gd_owned_rows`, csrc/owned_rows.hip).  out: an OwnedRows of the same N, number of policies and
+    device to be overwritten (n_policies may then be omitted); then nothing is allocated.  Two launches on torch's current
+    stream, no host synchronisation, no atomics: equal input gives equal bytes.  rows[start[P]:] is not written."""
+    who = "owned_rows: "
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 1 \
+            or not mask.is_contiguous():
+        raise ValueError(who + "mask must be a contiguous bool or uint8 tensor of shape [N]")
+    n = int(mask.shape[0])
+    if not 1 <= n <= MAX_ROWS:
+        raise ValueError(who + "N must be in [1, %d], got %d" % (MAX_ROWS, n))
+    if mask.device.type != "cuda":
+        raise ValueError(who + "mask must be on the GPU (there is no host path), got %s" % mask.device)
+    if not isinstance(owner, torch.Tensor) or owner.dtype != torch.uint8 or tuple(owner.shape) != (n,) or not owner.is_contiguous() \
+            or owner.device != mask.device:
+        raise ValueError(who + "owner must be a contiguous uint8 tensor of shape [%d] on %s" % (n, mask.device))
+    if n_policies is None and isinstance(out, OwnedRows):
+        n_policies = out.n_policies
+    if not _is_int(n_policies) or not 1 <= n_policies <= _capi.POLICY_SET_MAX:
+        raise ValueError(who + "n_policies must be an int in [1, %d], got %r" % (_capi.POLICY_SET_MAX, n_policies))
+    if out is None:
+        out = OwnedRows(n, n_policies, mask.device)
+    elif not isinstance(out, OwnedRows) or out.n != n or out.n_policies != n_policies or out.rows.device != mask.device:
+        raise ValueError(who + "out must be an OwnedRows of N = %d and %d policies on %s" % (n, n_policies, mask.device))
+    with torch.cuda.device(mask.device):
+        stream = C.c_void_p(torch.cuda.current_stream(mask.device).cuda_stream)
+        _capi.check(_capi.lib().gd_owned_rows(mask.data_ptr(), owner.data_ptr(), n, n_policies, out.rows.data_ptr(),
+                                              out.start.data_ptr(), out.count.data_ptr(), out.scratch.data_ptr(), None, stream),
+                    "gd_owned_rows")
+    return out
+
+
+def check_policy_set(policies, who):
+    """The policies of one `PolicySet`: 1 to 8 `DevicePolicy` of one shape (ValueError otherwise)."""
+    policies = tuple(policies)
+    if not 1 <= len(policies) <= _capi.POLICY_SET_MAX:
+        raise ValueError(who + "a set holds 1 to %d policies, got %d" % (_capi.POLICY_SET_MAX, len(policies)))
+    for p in policies:
+        if not isinstance(p, DevicePolicy):
+            raise ValueError(who + "every policy must be a DevicePolicy, got %s" % type(p).__name__)
+    first = policies[0]
+    for i, p in enumerate(policies):
+        for k in ("max_agents", "ego_width", "n_actions"):
+            if getattr(p, k) != getattr(first, k):
+                raise ValueError(who + "the policies of a set share one shape: policy %d has %s %d, policy 0 has %d"
+                                 % (i, k, getattr(p, k), getattr(first, k)))
+    return policies
+
+
+class PolicySet:
+    """1 to 8 `DevicePolicy` of one shape (max_agents, ego_width, n_actions) on one device, and the position-indexed scratch
+    of the forward on an owned list (`gd_policy_forward_owned`), in which every row is computed with the weights of its owner:
+    three launches whatever the number of policies.  The policies' blobs are read in place, so the set follows an optimiser
+    that moves them.  The scratch belongs to the set (it grows with the largest N seen): a set serves ONE stream at a time."""
+
+    def __init__(self, policies):
+        self.policies = check_policy_set(policies, "PolicySet: ")
+        first = self.policies[0]
+        for p in self.policies:
+            if p.device != first.device:
+                raise ValueError("PolicySet: the policies are on %s and %s" % (first.device, p.device))
+        self.device, self.max_agents, self.ego_width, self.n_actions = first.device, first.max_agents, first.ego_width, first.n_actions
+        self.obs_width = first.obs_width
+        self._features = self._logits = None
+        self._rows = 0
+
+    def __len__(self):
+        return len(self.policies)
+
+    @staticmethod
+    def scratch_nbytes(n, n_policies, n_actions):
+        """Bytes of the features and logits scratch of a forward on N rows."""
+        return owned_rows_positions(n, n_policies) * (FEATURES + n_actions) * 4
+
+    def _struct(self, n, new=None):
+        """The gd_policy_set of a forward on n rows; the scratch grows here, and nowhere else.  new: who makes the scratch of
+        THIS call instead (as for `LiveRows`; kept by the caller)."""
+        q = owned_rows_positions(n, len(self.policies))
+        if new is not None:
+            features = new("set_features", (q, FEATURES), torch.float32, None, self.device)
+            logits = new("set_logits", (q, self.n_actions), torch.float32, None, self.device)
+        else:
+            if n > self._rows:
+                self._features = torch.empty((q, FEATURES), dtype=torch.float32, device=self.device)
+                self._logits = torch.empty((q, self.n_actions), dtype=torch.float32, device=self.device)
+                self._rows = n
+            features, logits = self._features, self._logits
+        s = _capi.GdPolicySet()
+        s.n_policies = len(self.policies)
+        for i, p in enumerate(self.policies):
+            g = s.policy[i]
+            g.num_rows, g.max_agents, g.ego_width, g.n_actions = n, p.max_agents, p.ego_width, p.n_actions
+            g.blob, g.blob_floats = p.blob.data_ptr(), p.blob.numel()
+        s.features, s.logits = features.data_ptr(), logits.data_ptr()
+        s._keep = (features, logits)
+        return s
+
+    def __call__(self, obs, rows, u=None, deterministic=False, out=None, logits_out=None):
+        """obs [N, obs_width] float32, contiguous, on the device; rows: an `OwnedRows` of this N and this number of policies
+        (`owned_rows(mask, owner)`).  u [N] float32 in [0, 1) (required unless deterministic).  Returns (actions int64 [N],
+        logprob, entropy, value float32 [N]): index r of a row listed under policy p holds the bits `policies[p](obs)` gives
+        that row; out= and logits_out keep their bytes at rows that are not listed, and with out=None the fresh outputs are
+        zero there.  Always the unmasked forward: a dropout rule on a policy is neither consulted nor advanced.  Three launches
+        on torch's current stream, no host synchronisation; with out= and an N seen before, no allocation either."""
+        first, who = self.policies[0], "PolicySet: "
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[1] != self.obs_width:
+            raise ValueError(who + "obs must be a [N, %d] tensor (max_agents %d, ego_width %d)"
+                             % (self.obs_width, self.max_agents, self.ego_width))
+        n = int(obs.shape[0])
+        if not 1 <= n <= MAX_ROWS:
+            raise ValueError(who + "N must be in [1, %d], got %d" % (MAX_ROWS, n))
+        if not isinstance(rows, OwnedRows) or rows.n != n or rows.n_policies != len(self.policies) or rows.rows.device != self.device:
+            raise ValueError(who + "rows must be an OwnedRows of N = %d and %d policies on %s" % (n, len(self.policies), self.device))
+        first._tensor("obs", obs, torch.float32, (n, self.obs_width))
+        deterministic = bool(deterministic)
+        if u is None:
+            if not deterministic:
+                raise ValueError(who + "u is required unless deterministic=True")
+        else:
+            first._tensor("u", u, torch.float32, (n,))
+        f = torch.float32
+        want = (((n,), torch.int64), ((n,), f), ((n,), f), ((n,), f))
+        if out is None:
+            out = tuple(torch.zeros(shape, dtype=dt, device=self.device) for shape, dt in want)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 4:
+                raise ValueError(who + "out must be the four tensors (actions, logprob, entropy, value)")
+            out = tuple(first._tensor("out " + name, o, dt, shape) for name, o, (shape, dt) in zip(DevicePolicy.OUT_NAMES, out, want))
+        if logits_out is not None:
+            first._tensor("logits_out", logits_out, f, (n, self.n_actions))
+        s = self._struct(n)
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            _capi.check(_capi.lib().gd_policy_forward_owned(
+                C.byref(s), obs.data_ptr(), None if u is None else u.data_ptr(), int(deterministic), out[0].data_ptr(),
+                out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), None if logits_out is None else logits_out.data_ptr(),
+                rows.rows.data_ptr(), rows.start.data_ptr(), rows.count.data_ptr(), stream), "gd_policy_forward_owned")
+        return out
+
+
 class DevicePolicy:
     def __init__(self, state_dict, max_agents=128, ego_width=6, *, device="cuda", act_func="tanh", vbd_in_obs=False,
                  dropout_rule=None):

@@ -28,7 +28,8 @@ that `actions`, `logprob`, `entropy` and `value` of a dead row are those of its 
 `live_count` [91].  It is opt-in.
 Iterations after every world is done (the reference's `break`) change no output; `steps` counts the iterations that exist.
 
-Not here: rendering / `sim_state_frames` and `center_on_ego`, `multi_policy_rollout.py`, the
+Several policies in the same worlds (the reference's `multi_policy_rollout.py`) are `multi_policy_rollout.ClosedLoopMultiPPO`.
+Not here: rendering / `sim_state_frames` and `center_on_ego`, the
 delta_local table (8000 actions is beyond `DevicePolicy`'s 1024), the CSV / dataframe of `evaluate_policy` (`evaluate()`
 returns the columns as numpy arrays)."""
 import ctypes as C

@@ -894,6 +894,73 @@ typedef struct gd_policy_rollout_rows {
  * reserved != 0. */
 int gd_policy_rollout_compact(gd_sim *sim, const gd_policy *policy, const gd_policy_rollout_buffers *buffers,
                               const gd_policy_rollout_rows *rows, int32_t n_steps);
+/* Several policies in the same worlds (the reference's gpudrive/utils/multi_policy_rollout.py): every row has an owner, one of
+ * P <= GD_POLICY_SET_MAX policies, and ONE forward of three launches serves them all.  Nothing here synchronises with the
+ * host, allocates, or uses an atomic.  csrc/multi_policy_rule.hpp states the segment arithmetic, the per-policy counts and the
+ * summary's order.
+ *
+ * gd_owned_rows: mask [n] bytes and owner [n] bytes -> one list with a segment per policy.  count[p] = the rows i with
+ * mask[i] != 0 && owner[i] == p; start[0] = 0, start[p + 1] = start[p] + count[p] rounded up to a multiple of 32;
+ * rows[start[p] .. start[p] + count[p]) = those rows, ascending; every position from there up to start[p + 1] holds -1.  rows has
+ * n + 32 P entries, of which those at or past start[P] are not written; start has P + 1 entries, count P.  A row whose owner is
+ * >= P is listed nowhere.  scratch: one int32 per owner and per block of GD_LIVE_ROWS_BLOCK rows, P * ((n + GD_LIVE_ROWS_BLOCK -
+ * 1) / GD_LIVE_ROWS_BLOCK) of them.  count_copy [P], or NULL: a second place for the counts.  Two launches on `stream`; equal
+ * input gives equal bytes.  GD_ERR_INVALID, before any launch: a null pointer (but count_copy), rows, start, count, scratch or
+ * count_copy not 4-byte aligned, n outside [1, 2^20], n_policies outside [1, GD_POLICY_SET_MAX]. */
+#define GD_POLICY_SET_MAX 8
+int gd_owned_rows(const uint8_t *mask, const uint8_t *owner, int32_t n, int32_t n_policies, int32_t *rows, int32_t *start,
+                  int32_t *count, int32_t *scratch, int32_t *count_copy, void *stream);
+/* The policies of one forward on an owned list.  They share num_rows = N, max_agents, ego_width and n_actions (so the layout of
+ * their blobs); of each gd_policy the sizes, blob and blob_floats are read, its own features and logits are not used. */
+typedef struct gd_policy_set {
+    int32_t n_policies;          /* P, 1 .. GD_POLICY_SET_MAX */
+    int32_t reserved;            /* 0 */
+    gd_policy policy[GD_POLICY_SET_MAX];  /* the first P are read */
+    float *features;             /* [N + 32 P][192] scratch indexed by list position, 16-byte aligned */
+    float *logits;               /* [N + 32 P][NA] scratch indexed by list position */
+} gd_policy_set;
+/* gd_policy_forward (always the unmasked forward) on an owned list, every row with the weights of its owner: rows, start and
+ * count as gd_owned_rows writes them.  For a row r listed under p the call reads obs[r] and u[r] and writes actions[r],
+ * logprob[r], entropy[r], value[r] and logits_out[r], every bit what gd_policy_forward of policy p writes for that row.  Rows
+ * that are not listed are NOT written, in any output.  Three launches whatever P is, with grids sized for the N + 32 P
+ * positions; a wave in the padding or past the last segment returns at once; set->features and set->logits hold nothing
+ * specified afterwards.  A position belongs to segment p when start[p] <= q < start[p] + count[p] and q < N + 32 P; an entry
+ * outside [0, N) is skipped: for memory safety only (starts that are no multiples of 32 give a row another policy's weights;
+ * entries must be distinct).  No LDS.
+ * GD_ERR_INVALID, before any launch: whatever gd_policy_forward refuses of any of the P policies (but its features and logits),
+ * n_policies outside [1, GD_POLICY_SET_MAX], reserved != 0, policies that differ in num_rows, max_agents, ego_width or
+ * n_actions, null or misaligned set->features / set->logits, a null or not 4-byte aligned rows, start or count. */
+int gd_policy_forward_owned(const gd_policy_set *set, const float *obs, const float *u, int32_t deterministic, int64_t *actions,
+                            float *logprob, float *entropy, float *value, float *logits_out, const int32_t *rows,
+                            const int32_t *start, const int32_t *count, void *stream);
+/* The episode with P policies in the loop.  Device pointers owned by the caller; N = buffers->n_rows, P = set->n_policies. */
+typedef struct gd_multi_policy_buffers {
+    const uint8_t *owner;        /* [N] the policy index of every row; a row whose owner is >= P is never listed */
+    int32_t *rows;               /* [N + 32 P] the owned list of the current step */
+    int32_t *start;              /* [P + 1] */
+    int32_t *count;              /* [P] */
+    int32_t *scratch;            /* gd_owned_rows' scratch for n = N and P policies */
+    const float *denominator;    /* [W] the reference's controlled_per_scene: what every policy's fractions are divided by */
+    /* per policy and world, [P][W] each: the rows of policy p in world w whose sum is > 0, and count / denominator[w] (NaN for
+     * 0 / 0: kept); n_rows: the rows of policy p in world w */
+    float *goal_achieved_count, *frac_goal_achieved, *collided_count, *frac_collided, *off_road_count, *frac_off_road, *n_rows;
+    float *summary;              /* [P][4] per policy the totals of the three counts (goal_achieved, collided, off_road), n_rows */
+    int32_t *list_count;         /* [91][P] the lengths of step t's segments, or NULL; entries t >= n_steps are not written */
+    int32_t reserved;            /* 0 */
+} gd_multi_policy_buffers;
+/* For t in [0, n_steps), on the simulator's stream: gd_owned_rows on buffers->live and owner (its second launch also stores
+ * list_count[t]), gd_policy_forward_owned on that list with u + t * N, then the action kernel, the step and the bookkeeping
+ * kernel of gd_policy_rollout: 7 launches per step beside the step's own, whatever P is.  Policies own disjoint rows, so the
+ * reference's per-policy accumulators are `buffers`' per-row ones read through owner.  At the end gd_policy_rollout's two
+ * kernels, so that every output gd_policy_rollout defines is produced over all rows (as in gd_policy_rollout_compact: actions,
+ * logprob, entropy and value of a row hold the forward of the last step the row was live at), then a per-world kernel for the
+ * per-policy counts and fractions and a one-workgroup summary.  Iterations after every world is inactive change no output.  With
+ * n_steps < 91 the result is the prefix of the full episode.  It does not reset and does not advance the log playback.
+ * GD_ERR_INVALID / GD_ERR_UNSUPPORTED: whatever gd_policy_rollout refuses (of the set's first policy, whose num_rows must be
+ * n_rows), whatever gd_owned_rows and gd_policy_forward_owned refuse, a null or misaligned buffer of gd_multi_policy_buffers
+ * (but list_count, which may be null), reserved != 0. */
+int gd_multi_policy_rollout(gd_sim *sim, const gd_policy_set *set, const gd_policy_rollout_buffers *buffers,
+                            const gd_multi_policy_buffers *multi, int32_t n_steps);
 /* gd_bc_forward on the rows of a list: rows [n] int32 of which the first *count are read, count one int32 on the device
  * (gd_live_rows writes both).  For a listed row r the call reads obs[r], both masks' row r, u[r], z[r] and expert_actions[r] and
  * writes index r of every output given (context, means, log_covariances, covariances, weights, actions, nll, ego_attn_score,
