@@ -1101,6 +1101,8 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
 #pragma unroll
     for (int j = 1; j < 8; j++) r[j] = H.get(j);
     unsigned int last = H.get(K);  // heap[K - 1], kept in a register as well
+    unsigned int q[4];             // ... and slots 12, 25, 50, 100, the rest of slot K's ancestors (rank_heap.hpp: mirrors, the column keeps them too)
+    rank_heap::load_chain(H, q);
     if (lane < AWR) H.set(K, 0u);
     unsigned short *cpe = d.rk_cpe + (size_t)i * NCP;
     if (on) cpe[0] = (unsigned short)r[1];
@@ -1154,19 +1156,22 @@ __global__ __launch_bounds__(64) void k_knn_replay(DevSim d) {
                 const unsigned int wd[4] = {w8.x, w8.y, w8.z, w8.w};
                 const int left = n - pb;  // candidates of this lane's agent from here on (idle lanes: n = 0)
                 int ins;
-                // (slack beyond n and idle lanes do not count: `left`, `on`)
-                if (MIXED && __ballot(on && rank_heap::block_has_tie(wd, left, tm)) != 0ull) {
-                    ins = rank_heap::block_rounds<K, rank_heap::TIES>(H, r, last, wd, left, tm, tt);
+                // (slack beyond n and idle lanes do not count: `left`, `on`; one block in seventy has such a candidate, so the
+                // wave first asks whether any of the eight ranks of a lane has the field set, slack or not -- an OR of the
+                // four words -- and sorts the ranks by `left` only if one has)
+                if (MIXED && __ballot(on && rank_heap::any_tie(wd, tm)) != 0ull &&
+                    __ballot(on && rank_heap::block_has_tie(wd, left, tm)) != 0ull) {
+                    ins = rank_heap::block_rounds<K, rank_heap::TIES>(H, r, last, q, wd, left, tm, tt);
 #ifdef GD_CLOCKS
                     blk_ties++;
 #endif
                 } else if (MIXED && __ballot(tt.tl()) != 0ull) {
-                    ins = rank_heap::block_rounds<K, rank_heap::CHECKED>(H, r, last, wd, left, tm, tt, wave_any);
+                    ins = rank_heap::block_rounds<K, rank_heap::CHECKED>(H, r, last, q, wd, left, tm, tt, wave_any);
 #ifdef GD_CLOCKS
                     blk_checked++;
 #endif
                 } else {
-                    ins = rank_heap::block_rounds<K, rank_heap::PLAIN>(H, r, last, wd, left, tm, tt);
+                    ins = rank_heap::block_rounds<K, rank_heap::PLAIN>(H, r, last, q, wd, left, tm, tt);
                 }
 #ifdef GD_CLOCKS
                 n_ins += ins;

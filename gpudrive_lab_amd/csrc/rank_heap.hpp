@@ -156,14 +156,19 @@ GD_RH_FN void make_heap(const Heap &H, const unsigned int tm) {
 
 // ---- the rounds: one insert per candidate that passes the reference's test `cmp(current, heap[0])` (src/knn.hpp:138-143) ----
 // During the rounds slots 1..7 (tree levels 0..2) live in `r[1..7]` (r[1] is heap[0]) and slot K in `last`; slot K's place in
-// the column holds 0.
+// the column holds 0.  `q[0..3]` mirror slots 12, 25, 50, 100 -- with 1, 3, 6 the ancestors of slot K, the chain every push
+// climbs.  Those slots are fixed and change only where the round has the new value in a register already (the pop, when its path
+// goes through one of them, and the push's own store), so the round reads none of them back.  The column stays authoritative:
+// every store of the pop and of the push is made as before (the pop reads these slots as halves of pairs), `q` only follows.
 //
 // One insert of candidate rank y: pop_heap, replace last, push_heap.
 // pop_heap: the hole goes from the root to the bottom of the (K - 1)-element heap along the larger child.  Levels 0 and 1 are
 // decided in registers; below that three, then two levels per LDS round trip: a node's children pair, its grandchildren pairs
 // (and great-grandchildren pairs) are fetched together (pairs beyond the heap hold 0, which loses every comparison).  The
-// ancestors of slot K that the push will meet are requested at the start as well and patched where the pop's path went
-// through them.
+// ancestors of slot K that the push will meet come from `q`, patched where the pop's path went through them.  Where the path
+// went is known from the choices made on the way down (slot 6 is the right-left grandchild of the root, 12 the left child of 6,
+// 25 the right child of 12, 50 the left child of 25, 100 the left child of 50): lane masks that exist already, no compare of
+// a slot number.
 // TIES = false: a plain integer compare IS the key compare, "the larger child" is a max and the values along the pop's path
 // and the push's chain are medians of three (the moved children are non-increasing down the path, the chain towards the
 // leaf): about a third fewer instructions per insert.  That holds whenever no two of the heap's elements and y share a key.
@@ -174,14 +179,14 @@ GD_RH_FN void make_heap(const Heap &H, const unsigned int tm) {
 // one of the ranks it COMPARES has a non-zero tie field: the siblings along the pop's path, the ancestors of slot K, slots
 // 1..7, the last element and y.  Their OR is at hand when the round's values are; `any(flag)` is the wave's OR over the
 // inserting lanes (on the device a ballot, so every lane takes the same way).  If it says yes, nothing has been written
-// -- every store and every update of r / last comes after it -- and the function returns false: the caller runs the round in
+// -- every store and every update of r / last / q comes after it -- and the function returns false: the caller runs the round in
 // the TIES form instead.  A heap that holds a group of equal keys meets one of its members in about one insert in ten.
 struct NoAny {
     GD_RH_FN bool operator()(bool) const { return false; }
 };
 template <int K, bool TIES, bool CHECK = false, class Heap, class Any = NoAny>
-GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int y, const unsigned int tm,
-                     const Any &any = Any()) {
+GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, unsigned int (&q)[4], const unsigned int y,
+                     const unsigned int tm, const Any &any = Any()) {
     static_assert(K == 200, "ancestor chain of slot K");
     static_assert(!(TIES && CHECK), "the check belongs to the plain form");
     unsigned int seen = 0u;  // CHECK: OR of the pairs read along the path
@@ -199,11 +204,12 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
     g[0] = 1;
     g[1] = 2 + (right0 ? 1 : 0);
     g[2] = 2 * g[1] + (right1 ? 1 : 0);
-    const unsigned int q12 = H.get(12), q25 = H.get(25), q50 = H.get(50), q100 = H.get(100);
+    const unsigned int q12 = q[0], q25 = q[1], q50 = q[2], q100 = q[3];
     // (two round trips: three levels below slot g[2] -- its children pair, both grandchildren pairs and all four
     // great-grandchildren pairs, seven dwords at constant offsets from one address -- then two levels below g[5].  Two, two and
     // one level were a round trip more per insert, and the inserts of the agent with the most candidates are the kernel's
     // duration: 452 -> 435 us)
+    bool at12, at25, at50, at100;  // the pop's path goes through slot 12 / 25 / 50 / 100
     {
         const int g2 = g[2];
         const unsigned int pc = H.pair(g2), pl = H.pair(2 * g2), pr2 = H.pair(2 * g2 + 1);
@@ -218,6 +224,9 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
         const unsigned int pgg = ra ? pb : pa;
         ck[4] = larger(pgg & 0xffffu, pgg >> 16, rc);
         g[5] = 2 * g[4] + (rc ? 1 : 0);
+        at12 = right0 && !right1 && !ra;
+        at25 = at12 && rb;
+        at50 = at25 && !rc;
         if (CHECK) seen |= pc | pg | pgg;
     }
     {
@@ -228,6 +237,7 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
         const unsigned int pg = ra ? pr2 : pl;
         ck[6] = larger(pg & 0xffffu, pg >> 16, rb);
         g[7] = 2 * g[6] + (rb ? 1 : 0);
+        at100 = at50 && !ra;
         if (CHECK) seen |= pc | pg;
     }
     // the old last element climbs back from the leaf hole past every moved child that is smaller: like make_heap's sifts, the
@@ -256,14 +266,18 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
     r[1] = v[0];
     r[2] = right0 ? r[2] : v[1];
     r[3] = right0 ? v[1] : r[3];
-    GD_RH_UNROLL
-    for (int j = 4; j < 8; j++) r[j] = g[2] == j ? v[2] : r[j];
+    {  // g[2] = 4 + 2 * right0 + right1: the pair (hl, hr) that level 1 chose from takes v[2] on the side of right1
+        const unsigned int nl = right1 ? hl : v[2], nr = right1 ? v[2] : hr;
+        r[4] = right0 ? r[4] : nl;
+        r[5] = right0 ? r[5] : nr;
+        r[6] = right0 ? nl : r[6];
+        r[7] = right0 ? nr : r[7];
+    }
     GD_RH_UNROLL
     for (int l = 3; l < 8; l++)
         if (l < 6 || g[l] < K) H.set(g[l], v[l]);  // levels 3..5 are always inside the heap
     // push_heap: the new element climbs from slot K along 100, 50, 25, 12, 6, 3, 1
-    const unsigned int qv[7] = {r[1], r[3], r[6], g[3] == 12 ? v[3] : q12, g[4] == 25 ? v[4] : q25,
-                                g[5] == 50 ? v[5] : q50, g[6] == 100 ? v[6] : q100};
+    const unsigned int qv[7] = {r[1], r[3], r[6], at12 ? v[3] : q12, at25 ? v[4] : q25, at50 ? v[5] : q50, at100 ? v[6] : q100};
     constexpr int chain[7] = {1, 3, 6, 12, 25, 50, 100};
     if (TIES) {
         bool pp[7];
@@ -273,8 +287,11 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
         r[3] = pp[1] ? (pp[0] ? qv[0] : y) : r[3];
         r[6] = pp[2] ? (pp[1] ? qv[1] : y) : r[6];
         GD_RH_UNROLL
-        for (int u = 3; u < 7; u++)
-            if (pp[u]) H.set(chain[u], pp[u - 1] ? qv[u - 1] : y);
+        for (int u = 3; u < 7; u++) {
+            const unsigned int nv = pp[u - 1] ? qv[u - 1] : y;
+            if (pp[u]) H.set(chain[u], nv);
+            q[u - 3] = pp[u] ? nv : qv[u];  // (qv carries the pop's patch)
+        }
         last = pp[6] ? qv[6] : y;
     } else {
         // chain position u receives its parent's value if that is below y, y if only its own is, and keeps its own
@@ -283,10 +300,28 @@ GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, co
         r[3] = med3(qv[0], qv[1], y);
         r[6] = med3(qv[1], qv[2], y);
         GD_RH_UNROLL
-        for (int u = 3; u < 7; u++) H.set(chain[u], med3(qv[u - 1], qv[u], y));
+        for (int u = 3; u < 7; u++) {
+            q[u - 3] = med3(qv[u - 1], qv[u], y);
+            H.set(chain[u], q[u - 3]);
+        }
         last = umin(qv[6], y);
     }
     return true;
+}
+// the mirrors of a column as it stands: for callers that do not keep them across rounds
+template <class Heap>
+GD_RH_FN void load_chain(const Heap &H, unsigned int (&q)[4]) {
+    q[0] = H.get(12);
+    q[1] = H.get(25);
+    q[2] = H.get(50);
+    q[3] = H.get(100);
+}
+template <int K, bool TIES, bool CHECK = false, class Heap, class Any = NoAny>
+GD_RH_FN bool insert(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int y, const unsigned int tm,
+                     const Any &any = Any()) {
+    unsigned int q[4];
+    load_chain(H, q);
+    return insert<K, TIES, CHECK>(H, r, last, q, y, tm, any);
 }
 
 // ---- where the equal-key form is needed ----
@@ -345,18 +380,25 @@ GD_RH_FN bool block_has_tie(const unsigned int (&wd)[4], const int left, const u
 // `round` is one of the eight; both return the number of inserts.
 enum Form { PLAIN, TIES, CHECKED };
 template <int K, Form F, class Heap, class Any = NoAny>
-GD_RH_FN int round(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int y, const bool mine,
-                   const unsigned int tm, TieTrack &t, const Any &any = Any()) {
+GD_RH_FN int round(const Heap &H, unsigned int (&r)[8], unsigned int &last, unsigned int (&q)[4], const unsigned int y,
+                   const bool mine, const unsigned int tm, TieTrack &t, const Any &any = Any()) {
     if (!(mine && (F == TIES ? key_lt(y, r[1], tm) : y < r[1]))) return 0;
     if (F == TIES) {
-        insert<K, true>(H, r, last, y, tm);
+        insert<K, true>(H, r, last, q, y, tm);
         t.tg = umin(t.tg, tied_or_none(y, tm));
     } else if (F == CHECKED) {
-        if (!insert<K, false, true>(H, r, last, y, tm, any)) insert<K, true>(H, r, last, y, tm);
+        if (!insert<K, false, true>(H, r, last, q, y, tm, any)) insert<K, true>(H, r, last, q, y, tm);
     } else {
-        insert<K, false>(H, r, last, y, tm);
+        insert<K, false>(H, r, last, q, y, tm);
     }
     return 1;
+}
+template <int K, Form F, class Heap, class Any = NoAny>
+GD_RH_FN int round(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int y, const bool mine,
+                   const unsigned int tm, TieTrack &t, const Any &any = Any()) {
+    unsigned int q[4];
+    load_chain(H, q);
+    return round<K, F>(H, r, last, q, y, mine, tm, t, any);
 }
 // the end of a block that ran with a track: the root below every tracked rank means none of them is left
 GD_RH_FN void block_end(const unsigned int root, const unsigned int tm, TieTrack &t) {
@@ -364,13 +406,20 @@ GD_RH_FN void block_end(const unsigned int root, const unsigned int tm, TieTrack
 }
 GD_RH_FN unsigned int block_rank(const unsigned int (&wd)[4], const int k) { return (k & 1) ? wd[k >> 1] >> 16 : wd[k >> 1] & 0xffffu; }
 template <int K, Form F, class Heap, class Any = NoAny>
-GD_RH_FN int block_rounds(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int (&wd)[4], const int left,
-                          const unsigned int tm, TieTrack &t, const Any &any = Any()) {
+GD_RH_FN int block_rounds(const Heap &H, unsigned int (&r)[8], unsigned int &last, unsigned int (&q)[4],
+                          const unsigned int (&wd)[4], const int left, const unsigned int tm, TieTrack &t, const Any &any = Any()) {
     int ins = 0;
     GD_RH_UNROLL
-    for (int k = 0; k < 8; k++) ins += round<K, F>(H, r, last, block_rank(wd, k), k < left, tm, t, any);
+    for (int k = 0; k < 8; k++) ins += round<K, F>(H, r, last, q, block_rank(wd, k), k < left, tm, t, any);
     if (F != PLAIN) block_end(r[1], tm, t);
     return ins;
+}
+template <int K, Form F, class Heap, class Any = NoAny>
+GD_RH_FN int block_rounds(const Heap &H, unsigned int (&r)[8], unsigned int &last, const unsigned int (&wd)[4], const int left,
+                          const unsigned int tm, TieTrack &t, const Any &any = Any()) {
+    unsigned int q[4];
+    load_chain(H, q);
+    return block_rounds<K, F>(H, r, last, q, wd, left, tm, t, any);
 }
 
 }  // namespace rank_heap
