@@ -27,4 +27,7 @@ def __getattr__(name):
     if name == "DeviceLinearProbe":
         from .lp_probe import DeviceLinearProbe
         return DeviceLinearProbe
+    if name == "ProbeReadout":
+        from .bc_readout import ProbeReadout
+        return ProbeReadout
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

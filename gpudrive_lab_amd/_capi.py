@@ -320,6 +320,30 @@ class GdLPRows(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("logits", "loss_row", "pred")]
 
 
+BC_READOUT_MAX = 8      # GD_BC_READOUT_MAX: the probes of one list of a gd_bc_readout
+BC_READOUT_NO_CLASS = 255  # the fill value of the class outputs of a closed-loop episode
+
+
+class GdBCReadoutProbe(C.Structure):
+    """gd_bc_readout_probe: a probe's packed and flat weights (device pointers)."""
+    _fields_ = [("packed", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class GdBCReadout(C.Structure):
+    """gd_bc_readout: the tap, the probes, the labels, the three outputs with their row strides and the bad-label counter of the
+    probe read-outs inside the BC forward (device pointers)."""
+    _fields_ = ([(n, C.c_int32) for n in ("tap", "layer", "n_other", "n_ego", "intervene", "reserved")] +
+                [("other", GdBCReadoutProbe * BC_READOUT_MAX), ("ego", GdBCReadoutProbe * BC_READOUT_MAX),
+                 ("labels", C.c_void_p), ("label", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("other_pred", "ego_pred", "ego_pred_prime")] +
+                [(n, C.c_int64) for n in ("other_stride", "ego_stride", "prime_stride")] + [("bad_labels", C.c_void_p)])
+
+
+class GdBCRolloutReads(C.Structure):
+    """gd_bc_rollout_reads: the per-step attention scores and the read-out of a closed-loop episode (device pointers)."""
+    _fields_ = [("ego_attn_score", C.c_void_p), ("readout", C.POINTER(GdBCReadout))]
+
+
 # every symbol include/gpudrive_amd.h declares
 SYMBOLS = [
     "gd_version", "gd_last_error", "gd_default_params", "gd_tensor_shape", "gd_create", "gd_destroy",
@@ -330,7 +354,7 @@ SYMBOLS = [
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
     "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_owned_rows", "gd_policy_forward_owned",
-    "gd_multi_policy_rollout", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
+    "gd_multi_policy_rollout", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_bc_hidden_layer", "gd_bc_forward_readout", "gd_bc_forward_rows_readout", "gd_bc_rollout_readout", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -440,6 +464,14 @@ def lib():
     L.gd_bc_rollout_compact.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers),
                                         C.POINTER(GdBCRolloutRows), C.c_int32]
     L.gd_bc_hidden.argtypes = [C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.gd_bc_hidden_layer.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 +
+                                     [C.c_void_p, C.c_void_p])
+    L.gd_bc_forward_readout.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
+                                        [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs), C.POINTER(GdBCReadout), C.c_void_p])
+    L.gd_bc_forward_rows_readout.argtypes = ([C.POINTER(GdBCPolicy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] +
+                                             [C.c_void_p] * 3 + [C.POINTER(GdBCOutputs), C.POINTER(GdBCReadout)] + [C.c_void_p] * 3)
+    L.gd_bc_rollout_readout.argtypes = [C.c_void_p, C.POINTER(GdBCPolicy), C.POINTER(GdBCRolloutBuffers),
+                                        C.POINTER(GdBCRolloutRows), C.POINTER(GdBCRolloutReads), C.c_int32]
     lp = [C.POINTER(GdBCPolicy), C.POINTER(GdLPProbe), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_lp_forward.argtypes = lp + [C.POINTER(GdLPRows), C.c_void_p]
     L.gd_lp_update.argtypes = lp + [C.c_void_p, C.c_void_p, C.POINTER(GdLPRows), C.c_void_p]

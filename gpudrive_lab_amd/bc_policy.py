@@ -19,6 +19,9 @@ with an L x L extent exists anywhere -- the scores of a (sample, head, 32-query 
     lr = live_rows(alive, out=lr)                                 # policy.live_rows: the rows of a [B] byte mask, on the device
     bc(obs, pm, rm, deterministic=True, out=actions, rows=lr)     # the listed rows only (gd_bc_forward_rows); the others keep
                                                                   # their bytes, every listed row gets the full forward's bits
+    h = bc.hidden(obs, pm, rm, tap="ro_attn", layer=0)            # [B, A, 64]: the tapped tokens after any self-attention layer
+    r = bc.read(obs, pm, rm, ProbeReadout(bc, "ro_attn", 0, other=[po], ego=[pe], labels=10))   # the forward plus the probes'
+                                                                  # classes read at that layer on the way (bc_readout)
 
 The state dict carries the reference module's own parameter names (`expected_shapes`), so a `torch.save`d reference model
 loads without renaming.  The draw is this project's: the reference samples the component with `dist.Categorical` and the
@@ -334,15 +337,16 @@ class DeviceBCPolicy:
                        ego_attn_score=lambda s, B: (B, HEADS, s.max_agents - 1), component=lambda s, B: (B,))
 
     def forward(self, obs, partner_mask, road_mask, want, *, deterministic=True, u=None, z=None, expert_actions=None, out=None,
-                rows=None):
+                rows=None, readout=None):
         """The one C call.  want: the names of the outputs to write, out of context, means, log_covariances, covariances,
         weights, actions, nll, ego_attn_score, component (`_OUT_SHAPES`); out: a dict with tensors for some of them, to be
         overwritten.  Returns a dict of the wanted tensors.  rows: None for all B rows, or a `policy.LiveRows` of this B
         (`policy.live_rows(mask, out=)`): the forward then runs on the listed rows only (`gd_bc_forward_rows`), reads index r of
         every input and writes index r of every output with the bits the full forward gives that row; rows that are not
         listed are not written, so every wanted output must be given in out= and keeps its bytes there.  The list's length
-        stays on the device: every chunk is launched, and the workgroups past the list return at once.  Every check happens
-        before the launch."""
+        stays on the device: every chunk is launched, and the workgroups past the list return at once.  readout: a
+        `bc_readout.ProbeReadout` of this policy (`read`): its outputs join the result, one more launch per chunk
+        (`gd_bc_forward_readout` / `gd_bc_forward_rows_readout`).  Every check happens before the launch."""
         from .policy import LiveRows
         if rows is not None and not isinstance(rows, LiveRows):
             raise ValueError(WHO + "rows must be a LiveRows (policy.live_rows(mask)), got %s" % type(rows).__name__)
@@ -356,6 +360,13 @@ class DeviceBCPolicy:
             if missing:
                 raise ValueError(WHO + "rows= needs out= for every wanted output (rows that are not listed keep the caller's "
                                  "bytes), missing: %s" % ", ".join(missing))
+        ro = None
+        if readout is not None:
+            from .bc_readout import ProbeReadout
+            if not isinstance(readout, ProbeReadout) or readout.policy is not self:
+                raise ValueError(WHO + "readout must be a ProbeReadout of this policy")
+            ro, ro_res = readout.bind((B,), out, need_out=rows is not None, who=WHO)
+            out = {k: v for k, v in (out or {}).items() if k not in ro_res}
         deterministic = bool(deterministic)
         if not deterministic:
             if u is None or z is None:
@@ -393,12 +404,31 @@ class DeviceBCPolicy:
             args = (C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, int(deterministic),
                     None if u is None else u.data_ptr(), None if z is None else z.data_ptr(),
                     None if expert_actions is None else expert_actions.data_ptr(), C.byref(o))
-            if rows is not None:
+            if ro is not None:
+                if rows is not None:
+                    _capi.check(self._L.gd_bc_forward_rows_readout(*args, C.byref(ro), rows.rows.data_ptr(), rows.count.data_ptr(),
+                                                                   stream), "gd_bc_forward_rows_readout")
+                else:
+                    _capi.check(self._L.gd_bc_forward_readout(*args, C.byref(ro), stream), "gd_bc_forward_readout")
+                res.update(ro_res)
+            elif rows is not None:
                 _capi.check(self._L.gd_bc_forward_rows(*args, rows.rows.data_ptr(), rows.count.data_ptr(), stream),
                             "gd_bc_forward_rows")
             else:
                 _capi.check(self._L.gd_bc_forward(*args, stream), "gd_bc_forward")
         return res
+
+    def read(self, obs, partner_mask, road_mask, readout, deterministic=True, u=None, z=None, rows=None, out=None):
+        """The forward with the probe read-outs of `readout` (a `bc_readout.ProbeReadout` of this policy) taken on the way: a
+        dict with actions [B, 1, 3] -- `__call__`'s bits -- and whichever of other_pred [B, Po, A - 1], ego_pred [B, Pe] and
+        ego_pred_prime [B, P] (uint8 classes 0 .. 63) the read-out defines.  One C call: the forward's launches plus one per
+        chunk right after the tapped layer, whatever the number of probes; no encoder layer runs twice.  out: a dict with
+        tensors of an earlier call.  rows: a `LiveRows` of B: only the listed rows are read and written, in every output
+        (out= must then hold them all).  No host synchronisation; with out= no allocation."""
+        if out is not None and not isinstance(out, dict):
+            raise ValueError(WHO + "read: out must be a dict of the outputs' tensors")
+        return self.forward(obs, partner_mask, road_mask, ("actions",), deterministic=deterministic, u=u, z=z, out=out, rows=rows,
+                            readout=readout)
 
     def c_struct(self):
         """A fresh gd_bc_policy over this object's blob and scratch."""
@@ -411,15 +441,20 @@ class DeviceBCPolicy:
 
     TAPS = {"fusion_attn": _capi.LP_TAP_FUSION, "ro_attn": _capi.LP_TAP_RO}
 
-    def hidden(self, obs, partner_mask, road_mask, tap="fusion_attn", out=None):
+    def hidden(self, obs, partner_mask, road_mask, tap="fusion_attn", layer=None, out=None):
         """The hidden states a linear probe reads (the reference's forward hooks on `fusion_attn` / `ro_attn`,
         baselines/il/linear_probing.py:68-95): [B, A, 64] float32, tokens 0 .. A - 1 (the ego, then the partners) of the tapped
         block's last_hidden_state.  One C call (`gd_bc_hidden`): per chunk the forward's own kernels run and stop at the tap -- for
-        'fusion_attn' no branch layer, no cross attention and no head is launched.  out: that tensor of an earlier call.  No host
-        synchronisation; with out= no allocation."""
+        'fusion_attn' no branch layer, no cross attention and no head is launched.  layer: None for the block's last layer, or
+        an int i in [0, layers of that block): the kernels stop after layer i of the block (`gd_bc_hidden_layer`), the output the
+        reference's hook on the block's child str(i) sees; ('ro_attn', 0) is the one baselines/il/test/intervention.py reads.
+        out: that tensor of an earlier call.  No host synchronisation; with out= no allocation."""
         B = self._inputs(obs, partner_mask, road_mask)
         if tap not in self.TAPS:
             raise ValueError(WHO + "tap must be 'fusion_attn' or 'ro_attn', got %r" % (tap,))
+        if layer is not None:
+            from .bc_readout import check_tap
+            layer = check_tap(self, tap, layer, WHO)
         shape = (B, self.max_agents, DIM)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -430,8 +465,12 @@ class DeviceBCPolicy:
         p = self.c_struct()
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(self._L.gd_bc_hidden(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
-                                             self.TAPS[tap], out.data_ptr(), stream), "gd_bc_hidden")
+            if layer is None:
+                _capi.check(self._L.gd_bc_hidden(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
+                                                 self.TAPS[tap], out.data_ptr(), stream), "gd_bc_hidden")
+            else:
+                _capi.check(self._L.gd_bc_hidden_layer(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
+                                                       self.TAPS[tap], layer, out.data_ptr(), stream), "gd_bc_hidden_layer")
         return out
 
     def __call__(self, obs, partner_mask, road_mask, deterministic=False, u=None, z=None, out=None, rows=None):

@@ -29,8 +29,27 @@ return at their first load.  Every result is `run()`'s bit for bit, except `row_
 step it was alive at (with `run()`, of the last step).  The row kernel still visits every row -- a dead row's window, masks and
 goal distance keep moving in the reference.
 
-Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos, `importance_weight.py` / `intervention.py`,
-fewer launches for the chunks past the list.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
+    ep = loop.run(attention=True, readout=ro)                      # ro: a bc_readout.ProbeReadout of the policy
+    ep.ego_attn_score                                              # [91, N, 4, A - 1] f32: get_context's ego_attn_score per step
+    ep.other_pred, ep.ego_pred, ep.ego_pred_prime                  # [91, N, Po, A - 1], [91, N, Pe], [91, N, P] uint8 classes
+    ep.world_importance(t)                                         # [W, 4, A] f32: importance_weight.py's scatter for step t
+
+`run(attention=True)` is the reference's baselines/il/test/importance_weight.py: at every step each live agent's ego -> partner
+cross-attention weights per head; `run(readout=ro)` is baselines/il/test/intervention.py: at every step the classes pairs of
+trained probes read at one layer (`bc_readout`).  Both are written by the episode's one C call (`gd_bc_rollout_readout`): the
+head kernel stores the scores from a per-step base pointer, and one launch per chunk right after the tapped layer reads every
+probe -- the loop stays one call and no encoder layer runs twice.  The arrays are step-major, like u and z: a step's slice is
+contiguous.  A row that is live before step t holds what `policy.context(..., ego_attn_score=)` / `policy.read(...)` give for
+that step's window and masks, bit for bit; a row that is dead before step t, and every step whose iteration does not exist,
+holds the fill: 0.0 in the scores, 255 in the classes.  With compact=True only live rows are computed, so the fill `run()` made
+stays; without it the forward runs on dead rows too: the read-out kernel drops a row whose `dead` byte is set, and one clean-up
+launch per step stores 0.0 over the scores the head kernel wrote for dead rows (the head kernel is the plain forward's and is
+left alone).  `attention=True` also keeps `dead_mask` (record's), which `world_importance` reads.  Every other field of the
+episode is bit-identical to the same `run()` without the two options.
+
+Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos / `plot_simulator_state`, `lp_weight.py` (not
+runnable in the reference as written), steering the action with the intervened token (the reference only reads
+`ego_pred_prime`), fewer launches for the chunks past the list.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
 caller's `sim.deleteAgents(...)` before `run()`; self-play is a mask with more rows."""
 import ctypes as C
 
@@ -74,6 +93,16 @@ def _check_policy(sim, policy):
         raise ValueError(WHO + "policy.max_agents is %d, the simulator's is %d" % (policy.max_agents, sim._A))
 
 
+def _check_readout(policy, readout):
+    if readout is None:
+        return
+    from .bc_readout import ProbeReadout
+    if not isinstance(readout, ProbeReadout):
+        raise ValueError(WHO + "readout must be a bc_readout.ProbeReadout, got %s" % type(readout).__name__)
+    if readout.policy is not policy:
+        raise ValueError(WHO + "readout reads another policy object")
+
+
 def _check_steps(n_steps):
     if isinstance(n_steps, bool) or not isinstance(n_steps, int) or not 1 <= n_steps <= EPISODE_LEN:
         raise ValueError(WHO + "n_steps must be an int in [1, 91], got %r" % (n_steps,))
@@ -85,10 +114,36 @@ class ClosedLoopEpisode:
     -1: never); init_goal_dist / goal_dist [N] f32; dead [N] bool; steps: the iterations the reference's loop runs before its
     `break` (a 0-d device tensor); window [N, R, D] f32, partner_mask [N, A - 1] bool (`partner_value == 2`), partner_value
     [N, A - 1] uint8 and road_mask [N, 200] bool as the policy last saw them; with record=True actions [N, 91, 3] (zeros once the
-    row is dead), dead_mask [N, 91] bool (default 1), ego_global_pos [N, 91, 2] and ego_global_rot [N, 91] (live rows only)."""
+    row is dead), dead_mask [N, 91] bool (default 1), ego_global_pos [N, 91, 2] and ego_global_rot [N, 91] (live rows only);
+    with attention=True ego_attn_score [91, N, 4, A - 1] f32 (0.0 where the row was dead before the step) and dead_mask; with
+    readout= other_pred [91, N, Po, A - 1], ego_pred [91, N, Pe], ego_pred_prime [91, N, P] uint8 (255 where it was dead)."""
 
     def __init__(self, **arrays):
         self.__dict__.update(arrays)
+
+    def world_importance(self, t):
+        """importance_weight.py:75-78 for step t, [W, 4, A] float32, in torch ops on the device with no host read: zeros, and
+        in every world with exactly ONE row live before step t, per head, the k-th agent slot (ascending) other than that row's
+        own slot receives partner column k of the row's score -- which is the slot that partner column observes (partner j of
+        ego slot a is slot j for j < a, j + 1 otherwise).  Needs run(attention=True)."""
+        if getattr(self, "ego_attn_score", None) is None:
+            raise ValueError(WHO + "world_importance needs run(attention=True)")
+        if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < EPISODE_LEN:
+            raise ValueError(WHO + "t must be an int in [0, 91), got %r" % (t,))
+        W, A = self.mask.shape
+        dev = self.mask.device
+        dead = torch.ones(W * A, dtype=torch.bool, device=dev)
+        dead[self.row_slot.long()] = self.dead_mask[:, t]
+        live = ~dead.view(W, A)
+        one = live.sum(dim=1) == 1                                     # [W]
+        a = live.to(torch.uint8).argmax(dim=1)                         # [W] the live slot where there is exactly one
+        n = self.row_of_slot.view(W, A).gather(1, a[:, None]).squeeze(1).clamp(min=0).long()
+        score = self.ego_attn_score[t].index_select(0, n)              # [W, 4, A - 1]
+        slot = torch.arange(A, device=dev)[None, :]
+        col = (slot - (slot > a[:, None]).long()).clamp(max=A - 2)     # the partner column that observes slot s
+        vals = score.gather(2, col[:, None, :].expand(W, 4, A))
+        keep = (one[:, None] & (slot != a[:, None]))[:, None, :].expand(W, 4, A)
+        return torch.where(keep, vals, torch.zeros((), dtype=torch.float32, device=dev))
 
     def summary(self):
         """off_road_rate, veh_coll_rate, goal_rate, collision_rate, goal_progress, goal_count, n_rows, iterations as a dict of
@@ -122,29 +177,38 @@ class ClosedLoopBC:
         self.row_of_slot[self.row_slot.long()] = torch.arange(n, dtype=torch.int32, device=sim._device)
 
     @staticmethod
-    def row_nbytes(max_agents, num_stack, record=False):
+    def row_nbytes(max_agents, num_stack, record=False, attention=False, readout=None):
         """Bytes one row takes in a run: the window, both masks, the partner value, the action, the running state and, with
-        record, 91 steps of every per-step array."""
+        record, 91 steps of every per-step array.  attention: 91 steps of [4, A - 1] float32 scores (and dead_mask, unless
+        record already counts it) -- 46 228 bytes a row at A = 128, so [91, N, 4, 127] is 154 MB at N = 832.  readout (a
+        `ProbeReadout`): 91 steps of one byte per class it reads (`readout.row_nbytes()`)."""
         A, R = max_agents, num_stack
         n = R * packed_width(A) * 4 + R * (A - 1) + R * ROAD_POINTS + (A - 1) + 3 * 4
         n += sum(_ITEMSIZE[dt] for _, dt, _ in _ROW_ARRAYS)
         if record:
             n += EPISODE_LEN * sum(c * _ITEMSIZE[dt] for _, c, dt, _ in _STEP_ARRAYS)
+        if attention:
+            n += EPISODE_LEN * (4 * (A - 1) * 4 + (0 if record else 1))
+        if readout is not None:
+            n += EPISODE_LEN * readout.row_nbytes()
         return n
 
     @staticmethod
-    def nbytes(sim, policy, record=False, mask=None, stochastic=False, compact=False):
+    def nbytes(sim, policy, record=False, mask=None, stochastic=False, compact=False, attention=False, readout=None):
         """What `run()` will allocate for `sim`, `policy` and `mask` (default: the controlled agents): N rows of `row_nbytes`,
         any_alive [92] int32 and the summary [8]; with stochastic the draws u [91, N] and z [91, N, 3]; with compact the row
         list, its count and scratch (`LiveRows.nbytes(N)`) and live_count [91] int32.  The policy's own blob and scratch are
-        the policy's (`policy.nbytes`).  (Synchronises, for N.)"""
+        the policy's (`policy.nbytes`).  attention / readout: the per-step read-outs, as in `row_nbytes` -- the scores alone are
+        [91, N, 4, A - 1] float32, 154 MB at N = 832 and A = 128.  (Synchronises, for N.)"""
         _check_sim(sim)
         _check_mask(sim, mask)
         _check_policy(sim, policy)
         if mask is None:
             mask = sim.controlled_state_tensor().to_torch().squeeze(-1) == 1
         n = int(mask.sum().item())
-        total = n * ClosedLoopBC.row_nbytes(sim._A, policy.num_stack, record) + (EPISODE_LEN + 1) * 4 + len(SUMMARY_NAMES) * 4
+        _check_readout(policy, readout)
+        total = n * ClosedLoopBC.row_nbytes(sim._A, policy.num_stack, record, attention, readout) + (EPISODE_LEN + 1) * 4 \
+            + len(SUMMARY_NAMES) * 4
         if stochastic:
             total += EPISODE_LEN * n * 4 * 4
         if compact:
@@ -172,15 +236,21 @@ class ClosedLoopBC:
         """Every array of a run is made here (fill None: need not be initialised)."""
         return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
 
-    def run(self, n_steps=EPISODE_LEN, deterministic=True, generator=None, record=False, compact=False):
+    def run(self, n_steps=EPISODE_LEN, deterministic=True, generator=None, record=False, compact=False, attention=False,
+            readout=None):
         """Reset every world, fill the running state and run `n_steps` steps with the policy in the loop in one C call; returns
         the `ClosedLoopEpisode`.  n_steps < 91 gives the prefix of the full episode.  deterministic=False: u [n_steps, N] and
         z [n_steps, N, 3] are drawn from `generator` (a device torch.Generator, required) before the call and consumed per
         step under csrc/bc_rule.hpp's draw; they are returned as `u` and `z`.  record: also keep the per-step arrays.  compact:
         run every step's forward on the list of the rows still alive (`gd_bc_rollout_compact`, see the module docstring); the
-        episode then has live_count [91] int32, the length of step t's list, 0 for t >= n_steps, and `live_rows`.  No host
-        synchronisation."""
+        episode then has live_count [91] int32, the length of step t's list, 0 for t >= n_steps, and `live_rows`.  attention:
+        also keep ego_attn_score [91, N, 4, A - 1] float32 (and dead_mask); readout: a `bc_readout.ProbeReadout` of the policy,
+        whose other_pred / ego_pred / ego_pred_prime are kept as [91, N, ...] uint8 (its labels, if a tensor, are [N] in row
+        order); see the module docstring for the fill of dead rows.  Both work with compact and deterministic=False, add one
+        launch per chunk and step (and, without compact, one clean-up launch per step for the scores), and change no other
+        field.  No host synchronisation."""
         _check_steps(n_steps)
+        _check_readout(getattr(self, "policy", None), readout)
         deterministic = bool(deterministic)
         if not deterministic and not isinstance(generator, torch.Generator):
             raise ValueError(WHO + "deterministic=False needs generator=, a torch.Generator on the simulator's device")
@@ -213,6 +283,21 @@ class ClosedLoopBC:
             for name, c, dt, fill in _STEP_ARRAYS:
                 out[name] = new(name, (n, T) if c == 1 else (n, T, c), dt, fill)
                 setattr(b, name, out[name].data_ptr())
+        reads = None
+        if attention or readout is not None:
+            reads = _capi.GdBCRolloutReads()
+            if attention:
+                out["ego_attn_score"] = new("ego_attn_score", (T, n, 4, A - 1), torch.float32, 0)
+                reads.ego_attn_score = out["ego_attn_score"].data_ptr()
+                if not record:
+                    out["dead_mask"] = new("dead_mask", (n, T), torch.bool, 1)
+                    b.dead_mask = out["dead_mask"].data_ptr()
+            if readout is not None:
+                from .bc_readout import NO_CLASS
+                filled = {name: new(name, (T, n) + readout.row_shape(name), torch.uint8, NO_CLASS) for name in readout.names}
+                ro, _ = readout.bind((T, n), filled, who=WHO)
+                out.update(filled)
+                reads.readout = C.pointer(ro)
         p = self._policy_struct()
         if compact:
             from .policy import LiveRows
@@ -223,12 +308,17 @@ class ClosedLoopBC:
             r.live_count = out["live_count"].data_ptr()
         sim.reset(list(range(sim._W)))
         sim._bind_stream()
-        if compact:
+        if reads is not None:
+            _capi.check(sim._L.gd_bc_rollout_readout(sim._h, C.byref(p), C.byref(b), C.byref(r) if compact else None,
+                                                     C.byref(reads), n_steps), "gd_bc_rollout_readout")
+        elif compact:
             _capi.check(sim._L.gd_bc_rollout_compact(sim._h, C.byref(p), C.byref(b), C.byref(r), n_steps), "gd_bc_rollout_compact")
         else:
             _capi.check(sim._L.gd_bc_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_bc_rollout")
         sim._after()
         out["dead"] = out["dead"].view(torch.bool)
+        if attention:
+            out.update(mask=self.mask, row_slot=self.row_slot, row_of_slot=self.row_of_slot)
         return ClosedLoopEpisode(steps=any_alive[:T].sum(), any_alive=any_alive, summary_tensor=summary, window=window,
                                  partner_mask=pm[:, R - 1].view(torch.bool), road_mask=rm[:, R - 1].view(torch.bool),
                                  partner_value=pv, row_actions=row_actions, **out)

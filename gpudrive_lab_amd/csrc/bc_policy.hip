@@ -35,26 +35,6 @@ namespace gd {
 
 namespace {
 
-// ---- the row list
-
-// A row list on the device and the chunk of it a launch covers: the workgroup of scratch slot s has list position q0 + s
-struct BCRows {
-    const int32_t *rows, *count;
-    int q0, n;
-};
-
-// The sample of scratch slot `slot`.  The four kernels below take the list as a parameter pack that is empty in the full
-// forward, whose sample is the slot itself (those instantiations are the kernels as they were before there was a list).  With a
-// list: row rows[q0 + slot], or -1 where the position is past the list (a length above n is read as n) or the entry is outside
-// [0, n).  Workgroup-uniform; the only loads a workgroup that returns makes.
-__device__ __forceinline__ int bc_sample(int slot) { return slot; }
-__device__ __forceinline__ int bc_sample(int slot, const BCRows &lr) {
-    const int q = lr.q0 + slot, c = *lr.count;
-    if (q >= (c < lr.n ? c : lr.n)) return -1;
-    const int r = lr.rows[q];
-    return r >= 0 && r < lr.n ? r : -1;
-}
-
 // ---- token embedding
 
 // grid (1 + ceil((A - 1) / 32) + 7, rows): tile 0 is the ego, then the partner tiles, then the road tiles.  List = (BCRows): obs
@@ -451,15 +431,20 @@ void launch_bc_head(const gd_bc_policy &p, hipStream_t st, const unsigned char *
 
 void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                        const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
-                       const float *expert_actions, const gd_bc_outputs &out) {
+                       const float *expert_actions, const gd_bc_outputs &out, const gd_bc_readout *readout,
+                       const unsigned char *dead) {
     const BCDims d = bc_dims(p);
     const size_t per = (size_t)p.chunk_rows * d.L * F;
     float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
+    const int read_at = readout ? bc_tap_layer(p, readout->tap, readout->layer) : -1;
     for (int r0 = 0; r0 < n; r0 += p.chunk_rows) {
         const int rows = std::min(p.chunk_rows, n - r0);
         const unsigned char *pm = partner_mask + (size_t)r0 * d.R * (d.A - 1), *rm = road_mask + (size_t)r0 * d.R * ROADS;
         launch_bc_embed(p, st, obs + (size_t)r0 * d.R * d.D, rows, X);
-        for (int i = 0; i < p.fusion_layers + p.branch_layers; i++) launch_bc_self_layer(p, st, pm, rm, rows, i, X, Kb, Vb, nullptr, nullptr);
+        for (int i = 0; i < p.fusion_layers + p.branch_layers; i++) {
+            launch_bc_self_layer(p, st, pm, rm, rows, i, X, Kb, Vb, nullptr, nullptr);
+            if (i == read_at) launch_bc_readout(p, st, *readout, dead, r0, rows, X, nullptr, nullptr, n);
+        }
         launch_bc_cross_kv(p, st, rows, X, Kb, Vb);
         launch_bc_head(p, st, partner_mask, road_mask, r0, rows, deterministic, u, z, expert_actions, out, X, Kb, Vb);
     }
@@ -469,7 +454,9 @@ void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, 
 // not know the list's length -- on the list instantiations; a chunk past the list is workgroups that return at their first load.
 void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                             const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
-                            const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows, const int32_t *count) {
+                            const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows, const int32_t *count,
+                            const gd_bc_readout *readout) {
+    const int read_at = readout ? bc_tap_layer(p, readout->tap, readout->layer) : -1;
     const BCDims d = bc_dims(p);
     const int A = p.max_agents, C = p.n_components;
     const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, C);
@@ -494,6 +481,7 @@ void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *
             hipLaunchKernelGGL(k_bc_kv<BCRows>, dim3(tiles, slots), dim3(64), 0, st, d, sg, p.blob, X, Kb, Vb, lr);
             hipLaunchKernelGGL(k_bc_attn<BCRows>, dim3(tiles, slots), dim3(64), 0, st, d, sg, p.blob, partner_mask, road_mask, X, Kb, Vb,
                                lr);
+            if (i == read_at) launch_bc_readout(p, st, *readout, nullptr, q0, (int)slots, X, rows, count, n);
         }
         hipLaunchKernelGGL(k_bc_kv<BCRows>, dim3((unsigned)(cross.s[0].tiles + cross.s[1].tiles), slots), dim3(64), 0, st, d, cross, p.blob,
                            X, Kb, Vb, lr);

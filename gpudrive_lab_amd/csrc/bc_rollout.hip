@@ -17,6 +17,8 @@
 //                   iteration exists, and whether it exists depends on every other row: inside one launch that would take
 //                   an atomic or a read of words other workgroups write.
 // and, before t = 0, k_bc_post(-1): the accumulators take the reset state's info (simulation.py:45-47) and any_alive[0] = 1.
+// gd_bc_rollout_readout (the read-outs in the loop) passes the step's slices to the forward and, without the list, launches
+// k_bc_score_fill after it: 0.0 over the attention scores of the rows that were dead before the step.
 // After the loop k_bc_summary: one workgroup, the fixed order of bc_rollout_rule.hpp.  No atomics anywhere.
 #include <hip/hip_runtime.h>
 
@@ -167,6 +169,13 @@ __global__ __launch_bounds__(256) void k_bc_post(DevSim d, gd_bc_rollout_buffers
     if (more && r.dead == 0) b.any_alive[t + 1] = 1;  // the same value from every live row: a plain store, no atomic
 }
 
+// grid (N, ceil(per_row / 256)): the scores [N][per_row] of one step, 0.0 over the rows that were dead before it
+__global__ __launch_bounds__(256) void k_bc_score_fill(gd_bc_rollout_buffers b, float *__restrict__ scores, int per_row) {
+    const int n = blockIdx.x, i = blockIdx.y * 256 + threadIdx.x;
+    if (i >= per_row || b.dead[n] == 0) return;
+    scores[(size_t)n * per_row + i] = 0.f;
+}
+
 __global__ __launch_bounds__(R::LANES) void k_bc_summary(gd_bc_rollout_buffers b) {
     __shared__ float s_part[R::LANES * 4];
     const int tid = threadIdx.x;
@@ -189,6 +198,10 @@ void launch_bc_rollout_actions(const DevSim &d, hipStream_t st, const gd_bc_roll
 
 void launch_bc_rollout_post(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t, bool more) {
     hipLaunchKernelGGL(k_bc_post, dim3((b.n_rows + 255) / 256), dim3(256), 0, st, d, b, t, d.W * d.A, more ? 1 : 0);
+}
+
+void launch_bc_rollout_score_fill(hipStream_t st, const gd_bc_rollout_buffers &b, float *scores, int per_row) {
+    hipLaunchKernelGGL(k_bc_score_fill, dim3(b.n_rows, (per_row + 255) / 256), dim3(256), 0, st, b, scores, per_row);
 }
 
 void launch_bc_rollout_summary(hipStream_t st, const gd_bc_rollout_buffers &b) {

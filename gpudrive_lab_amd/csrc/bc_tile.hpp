@@ -247,6 +247,26 @@ inline Segs bc_cross_segs(const gd_bc_policy &p) {
     return sg;
 }
 
+// ---- the row list
+
+// A row list on the device and the chunk of it a launch covers: the workgroup of scratch slot s has list position q0 + s
+struct BCRows {
+    const int32_t *rows, *count;
+    int q0, n;
+};
+
+// The sample of scratch slot `slot`.  The forward's four kernels (bc_policy.hip) and k_bc_readout (bc_readout.hip) take the list as a parameter pack that is empty in the full
+// forward, whose sample is the slot itself (those instantiations are the kernels as they were before there was a list).  With a
+// list: row rows[q0 + slot], or -1 where the position is past the list (a length above n is read as n) or the entry is outside
+// [0, n).  Workgroup-uniform; the only loads a workgroup that returns makes.
+__device__ __forceinline__ int bc_sample(int slot) { return slot; }
+__device__ __forceinline__ int bc_sample(int slot, const BCRows &lr) {
+    const int q = lr.q0 + slot, c = *lr.count;
+    if (q >= (c < lr.n ? c : lr.n)) return -1;
+    const int r = lr.rows[q];
+    return r >= 0 && r < lr.n ? r : -1;
+}
+
 }  // namespace
 
 }  // namespace gd

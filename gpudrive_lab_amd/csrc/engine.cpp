@@ -1925,6 +1925,50 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     });
 }
 
+// everything of a gd_bc_readout that gd_bc_forward_readout refuses (the policy has passed bc_forward_problem); nullptr when
+// everything is in order
+static const char *bc_readout_problem(const gd_bc_policy *p, const gd_bc_readout *r) {
+    if (!r) return "readout is required";
+    if (r->tap != GD_LP_TAP_FUSION && r->tap != GD_LP_TAP_RO) return "readout: tap must be GD_LP_TAP_FUSION or GD_LP_TAP_RO";
+    if (r->layer < 0 || r->layer >= (r->tap == GD_LP_TAP_RO ? p->branch_layers : p->fusion_layers))
+        return "readout: layer must be in [0, layers of the tapped block)";
+    if (r->n_other < 0 || r->n_other > GD_BC_READOUT_MAX || r->n_ego < 0 || r->n_ego > GD_BC_READOUT_MAX)
+        return "readout: n_other and n_ego must be in [0, 8]";
+    if (r->n_other + r->n_ego < 1) return "readout: at least one probe is required";
+    if (r->reserved != 0) return "readout: reserved must be 0";
+    if (r->intervene != 0 && r->intervene != 1) return "readout: intervene must be 0 or 1";
+    if (r->intervene && (r->n_other != r->n_ego)) return "readout: intervene needs n_other == n_ego";
+    for (int i = 0; i < r->n_other; i++) {
+        if (!r->other[i].packed || misaligned(r->other[i].packed, 16)) return "readout: a probe's packed is required, 16-byte aligned";
+        if (r->intervene && (!r->other[i].weight || misaligned(r->other[i].weight, 4)))
+            return "readout: an 'other' probe's weight is required with intervene, 4-byte aligned";
+    }
+    for (int i = 0; i < r->n_ego; i++)
+        if (!r->ego[i].packed || misaligned(r->ego[i].packed, 16)) return "readout: a probe's packed is required, 16-byte aligned";
+    if ((r->n_other && !r->other_pred) || (r->n_ego && !r->ego_pred) || (r->intervene && !r->ego_pred_prime))
+        return "readout: an output of a non-zero count is null";
+    if ((r->n_other && r->other_stride < (int64_t)r->n_other * (p->max_agents - 1)) || (r->n_ego && r->ego_stride < r->n_ego) ||
+        (r->intervene && r->prime_stride < r->n_ego))
+        return "readout: a stride is below its row";
+    if (misaligned(r->labels, 8)) return "readout: labels must be 8-byte aligned";
+    if (r->intervene && (!r->bad_labels || misaligned(r->bad_labels, 4)))
+        return "readout: bad_labels is required with intervene, 4-byte aligned";
+    return nullptr;
+}
+
+int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                          int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                          const gd_bc_readout *readout, void *stream) {
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
+    if (!why) why = bc_readout_problem(p, readout);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_readout: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_forward(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+                              expert_actions, *out, readout);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 // everything gd_bc_rollout refuses, for gd_bc_rollout_compact too; GD_OK when everything is in order
 static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
     const std::string w = std::string(who) + ": ";
@@ -1958,25 +2002,42 @@ static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p,
 // The loop of both drivers (bc_rollout.hip): r == nullptr is gd_bc_rollout's forward on all N rows, otherwise the list of the
 // rows with dead[n] == 0 in the loop.  When iteration t does not exist every row is dead: the list is empty and every
 // workgroup of the forward returns at its first load.
+// x (gd_bc_rollout_readout): step t's forward also writes the step's slices of the read-outs; without the list the read-out
+// kernel drops dead rows itself and one more launch zeroes the scores the head kernel stored for them.
 static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                          int32_t n_steps) {
+                          int32_t n_steps, const gd_bc_rollout_reads *x = nullptr) {
     return guarded([&]() {
         const size_t N = static_cast<size_t>(b->n_rows);
         gd_bc_outputs out{};
         out.actions = b->row_actions;
+        const int score_row = 4 * (p->max_agents - 1);
+        gd_bc_readout ro{};
+        if (x && x->readout) ro = *x->readout;
         gd::launch_bc_rollout_post(s->d, s->stream, *b, -1, true);
         HIP_CHECK(hipGetLastError());
         for (int t = 0; t < n_steps; t++) {
             const float *u = b->u ? b->u + t * N : nullptr, *z = b->z ? b->z + t * N * 3 : nullptr;
             gd::launch_bc_rollout_row(s->d, s->stream, *b, t, p->num_stack);
+            const gd_bc_readout *rd = nullptr;
+            if (x) {
+                out.ego_attn_score = x->ego_attn_score ? x->ego_attn_score + t * N * score_row : nullptr;
+                if (x->readout) {
+                    const gd_bc_readout &full = *x->readout;
+                    ro.other_pred = full.other_pred ? full.other_pred + t * N * full.other_stride : nullptr;
+                    ro.ego_pred = full.ego_pred ? full.ego_pred + t * N * full.ego_stride : nullptr;
+                    ro.ego_pred_prime = full.ego_pred_prime ? full.ego_pred_prime + t * N * full.prime_stride : nullptr;
+                    rd = &ro;
+                }
+            }
             if (r) {
                 gd::launch_live_rows(s->stream, b->dead, b->n_rows, r->rows, r->count, r->scratch,
                                      r->live_count ? r->live_count + t : nullptr, true);
                 gd::launch_bc_forward_rows(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u,
-                                           z, nullptr, out, r->rows, r->count);
+                                           z, nullptr, out, r->rows, r->count, rd);
             } else {
                 gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
-                                      nullptr, out);
+                                      nullptr, out, rd, b->dead);
+                if (out.ego_attn_score) gd::launch_bc_rollout_score_fill(s->stream, *b, out.ego_attn_score, score_row);
             }
             gd::launch_bc_rollout_actions(s->d, s->stream, *b, t);
             HIP_CHECK(hipGetLastError());
@@ -2245,6 +2306,42 @@ int gd_bc_rollout_compact(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_
     return bc_rollout_run(s, p, b, r, n_steps);
 }
 
+int gd_bc_forward_rows_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                               int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                               const gd_bc_outputs *out, const gd_bc_readout *readout, const int32_t *rows, const int32_t *count,
+                               void *stream) {
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
+    if (!why) why = bc_readout_problem(p, readout);
+    if (!why) why = row_list_problem(rows, count);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_readout: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_forward_rows(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+                                   expert_actions, *out, rows, count, readout);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// gd_bc_rollout (r == nullptr) or gd_bc_rollout_compact with the read-outs in the loop.  What needs no simulator is checked first.
+int gd_bc_rollout_readout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                          const gd_bc_rollout_reads *x, int32_t n_steps) {
+    const char *who = "gd_bc_rollout_readout";
+    if (!s || !p || !b || !x) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
+    const char *why = nullptr;
+    if (r) {
+        why = row_list_problem(r->rows, r->count);
+        if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
+        if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
+        if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
+    }
+    if (!why && !x->ego_attn_score && !x->readout) why = "reads needs ego_attn_score or readout";
+    if (!why && misaligned(x->ego_attn_score, 4)) why = "ego_attn_score must be 4-byte aligned";
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    if (const int rc = bc_rollout_problem(who, s, p, b, n_steps)) return rc;
+    if (x->readout)
+        if (const char *bad = bc_readout_problem(p, x->readout)) return fail(GD_ERR_INVALID, std::string(who) + ": " + bad);
+    return bc_rollout_run(s, p, b, r, n_steps, x);
+}
+
 // everything gd_bc_backward refuses; nullptr when everything is in order
 static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,
@@ -2396,6 +2493,21 @@ int gd_bc_hidden(const gd_bc_policy *p, const float *obs, const uint8_t *partner
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_hidden: ") + why);
     return guarded([&]() {
         gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_bc_hidden_layer(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                       int32_t tap, int32_t layer, float *out, void *stream) {
+    gd_bc_outputs none{};
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none);
+    if (!why && tap != GD_LP_TAP_FUSION && tap != GD_LP_TAP_RO) why = "tap must be GD_LP_TAP_FUSION or GD_LP_TAP_RO";
+    if (!why && (layer < 0 || layer >= (tap == GD_LP_TAP_RO ? p->branch_layers : p->fusion_layers)))
+        why = "layer must be in [0, layers of the tapped block)";
+    if (!why && (!out || misaligned(out, 16))) why = "out is required, 16-byte aligned";
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_hidden_layer: ") + why);
+    return guarded([&]() {
+        gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out, layer);
         HIP_CHECK(hipGetLastError());
     });
 }

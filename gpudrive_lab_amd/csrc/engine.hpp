@@ -270,6 +270,8 @@ void launch_bc_rollout_row(const DevSim &d, hipStream_t st, const gd_bc_rollout_
 void launch_bc_rollout_actions(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t);
 void launch_bc_rollout_post(const DevSim &d, hipStream_t st, const gd_bc_rollout_buffers &b, int t, bool more);
 void launch_bc_rollout_summary(hipStream_t st, const gd_bc_rollout_buffers &b);
+// the scores of step t ([N][4][A - 1]) of every row whose dead byte is set become 0.0 (gd_bc_rollout_readout without the list)
+void launch_bc_rollout_score_fill(hipStream_t st, const gd_bc_rollout_buffers &b, float *scores, int per_row);
 // policy_rollout.hip: the closed-loop PPO evaluator's launches (finish: the per-world kernel and the summary)
 void launch_policy_rollout_actions(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, int t);
 void launch_policy_rollout_book(const DevSim &d, hipStream_t st, const gd_policy_rollout_buffers &b, int t);
@@ -330,12 +332,18 @@ long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, in
 long long bc_scratch_floats(int max_agents, int chunk_rows);  // bc_policy.hip: the size of gd_bc_policy.scratch
 void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                        const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
-                       const float *expert_actions, const gd_bc_outputs &out);  // bc_policy.hip
+                       const float *expert_actions, const gd_bc_outputs &out, const gd_bc_readout *readout = nullptr,
+                       const unsigned char *dead = nullptr);  // bc_policy.hip
 // the forward on a device-resident row list: every chunk of list positions is launched, scratch by position, the rest by row
 void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                             const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                             const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows,
-                            const int32_t *count);  // bc_policy.hip
+                            const int32_t *count, const gd_bc_readout *readout = nullptr);  // bc_policy.hip
+// bc_readout.hip: the probe read-outs of one chunk, launched by the two forwards above right after self layer
+// bc_tap_layer(p, readout->tap, readout->layer) when `readout` is given (one launch).  dead: rows whose byte is set are dropped
+int bc_tap_layer(const gd_bc_policy &p, int tap, int layer);
+void launch_bc_readout(const gd_bc_policy &p, hipStream_t st, const gd_bc_readout &ro, const unsigned char *dead, int r0, int slots,
+                       const float *X, const int32_t *rows, const int32_t *count, int n);
 void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,
                                float *acc);  // bc_policy.hip (one launch)
 // bc_policy.hip: the forward's launches one by one, for the backward's recomputation (bc_grad.hip).  The masks of
@@ -361,7 +369,7 @@ void launch_bc_train_rows(const gd_bc_opt &o, hipStream_t st, int n, const float
 void launch_bc_adamw(const gd_bc_opt &o, hipStream_t st, const float *grad);  // (three launches)
 // lp_probe.hip
 void launch_bc_hidden(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
-                      const unsigned char *road_mask, int n, int tap, float *out);
+                      const unsigned char *road_mask, int n, int tap, float *out, int layer = -1);  // layer -1: the block's last
 // mode 0: logits and / or pred; 1: one gradient step; 2: one batch of the evaluation added to acc.  p: null for the baseline probe
 void launch_lp(const gd_bc_policy *p, const gd_lp_probe &lp, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                const unsigned char *road_mask, int n, const unsigned char *mask, const int64_t *labels, const gd_lp_rows *rows_out,

@@ -331,12 +331,12 @@ __global__ __launch_bounds__(NT) void k_lp_adamw(int K, P::AdamCoefs c, float we
     packed[e < F * K ? packed_at(e / K, e % K) : W64 + (e - F * K)] = p;
 }
 
-// the chunk's tokens up to the tapped block's output, in X
+// the chunk's tokens up to the output of layer `layer` of the tapped block (-1: its last), in X
 void launch_tap(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *pm, const unsigned char *rm, int r0,
-                int rows, int tap, float *X, float *Kb, float *Vb) {
+                int rows, int tap, float *X, float *Kb, float *Vb, int layer = -1) {
     const BCDims d = bc_dims(p);
     launch_bc_embed(p, st, obs + (size_t)r0 * d.R * d.D, rows, X);
-    const int layers = p.fusion_layers + (tap == GD_LP_TAP_RO ? p.branch_layers : 0);
+    const int layers = layer < 0 ? p.fusion_layers + (tap == GD_LP_TAP_RO ? p.branch_layers : 0) : bc_tap_layer(p, tap, layer) + 1;
     for (int i = 0; i < layers; i++)
         launch_bc_self_layer(p, st, pm + (size_t)r0 * d.R * (d.A - 1), rm + (size_t)r0 * d.R * ROADS, rows, i, X, Kb, Vb, nullptr, nullptr);
 }
@@ -344,13 +344,13 @@ void launch_tap(const gd_bc_policy &p, hipStream_t st, const float *obs, const u
 }  // namespace
 
 void launch_bc_hidden(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
-                      const unsigned char *road_mask, int n, int tap, float *out) {
+                      const unsigned char *road_mask, int n, int tap, float *out, int layer) {
     const BCDims d = bc_dims(p);
     const size_t per = (size_t)p.chunk_rows * d.L * F;
     float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
     for (int r0 = 0; r0 < n; r0 += p.chunk_rows) {
         const int rows = std::min(p.chunk_rows, n - r0);
-        launch_tap(p, st, obs, partner_mask, road_mask, r0, rows, tap, X, Kb, Vb);
+        launch_tap(p, st, obs, partner_mask, road_mask, r0, rows, tap, X, Kb, Vb, layer);
         hipLaunchKernelGGL(k_lp_copy, dim3((unsigned)((d.A * 16 + 255) / 256), (unsigned)rows), dim3(256), 0, st, d.A, d.L, r0, X, out);
     }
 }

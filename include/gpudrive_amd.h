@@ -1065,6 +1065,68 @@ int gd_lp_update(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs,
 int gd_lp_eval_accumulate(const gd_bc_policy *p, const gd_lp_probe *lp, const float *obs, const uint8_t *partner_mask,
                           const uint8_t *road_mask, int32_t n, const uint8_t *mask, const int64_t *labels, const gd_lp_rows *rows,
                           int32_t *acc, void *stream);
+/* gd_bc_hidden at any self-attention layer of the tapped block: layer in [0, fusion_layers) for GD_LP_TAP_FUSION, in
+ * [0, branch_layers) for GD_LP_TAP_RO; the forward's kernels stop after that layer of the block.  The block's last layer gives
+ * gd_bc_hidden's bits.  (GD_LP_TAP_RO, 0) is the layer the reference's baselines/il/test/intervention.py hooks (ro_attn's child
+ * '0').  GD_ERR_INVALID: a layer outside the block, whatever gd_bc_hidden refuses. */
+int gd_bc_hidden_layer(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                       int32_t tap, int32_t layer, float *out, void *stream);
+/* Probe read-outs inside the BC forward (csrc/bc_readout.hip, csrc/bc_readout_rule.hpp): what the reference's
+ * baselines/il/test/intervention.py reads per step from pairs of trained LinearProbPosition heads, taken from the chunk's
+ * scratch right after self layer (tap, layer) while it still holds that layer's output.  A probe is its two device buffers,
+ * read at call time (gd_lp_probe's `packed` and `weight`; K = 64): a probe that trains between two calls is followed in place. */
+enum { GD_BC_READOUT_MAX = 8 };
+typedef struct gd_bc_readout_probe {
+    const float *packed;         /* [4160] gd_lp_probe.packed; 16-byte aligned */
+    const float *weight;         /* [64 * 64 + 64] gd_lp_probe.weight; read for the 'other' probes of an intervention only */
+} gd_bc_readout_probe;
+typedef struct gd_bc_readout {
+    int32_t tap, layer;          /* as gd_bc_hidden_layer's */
+    int32_t n_other, n_ego;      /* 0 .. GD_BC_READOUT_MAX each, at least one in total */
+    int32_t intervene;           /* 0, or 1: ego_pred_prime is written; needs n_other == n_ego, pair p is (ego[p], other[p]) */
+    int32_t reserved;            /* 0 */
+    gd_bc_readout_probe other[GD_BC_READOUT_MAX], ego[GD_BC_READOUT_MAX];
+    const int64_t *labels;       /* [n] the label of every row (8-byte aligned), or NULL: `label` for every row */
+    int64_t label;
+    /* the outputs, one byte per class (0 .. 63); row r of each starts at r * its stride (bytes) */
+    uint8_t *other_pred;         /* row: [n_other][A - 1], the class of partner token 1 + j under other[q] (padded columns too) */
+    uint8_t *ego_pred;           /* row: [n_ego], the class of token 0 under ego[q] */
+    uint8_t *ego_pred_prime;     /* row: [n_ego], the class of fl32(token 0 + other[p].weight row label) under ego[p]; a label
+                                  * outside [0, 63] is no intervention (ego_pred's value) and the row counts in bad_labels */
+    int64_t other_stride, ego_stride, prime_stride;  /* >= n_other * (A - 1), n_ego, n_ego */
+    int32_t *bad_labels;         /* [1] += the rows read whose label is outside [0, 63] (once per row); required with intervene */
+} gd_bc_readout;
+/* gd_bc_forward / gd_bc_forward_rows plus ONE launch per chunk, whatever the number of probes, right after the tapped layer:
+ * every output of `out` given is gd_bc_forward's, bit for bit.  With the list only listed rows are read and written, keyed on
+ * the row.  Where the tap is a probe's own, other_pred / ego_pred are gd_lp_forward's pred of that probe.  No atomics, no host
+ * synchronisation, no allocation.  GD_ERR_INVALID, before any launch: whatever the forward refuses; a null readout, an unknown
+ * tap, a layer outside the block, counts outside their range or both 0, reserved != 0, intervene with unequal counts, a null or
+ * misaligned buffer of a probe that is read, a null output for a non-zero count, a stride below the row, labels that are not
+ * 8-byte aligned, a null or misaligned bad_labels with intervene. */
+int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                          int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                          const gd_bc_readout *readout, void *stream);
+int gd_bc_forward_rows_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                               int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                               const gd_bc_outputs *out, const gd_bc_readout *readout, const int32_t *rows, const int32_t *count,
+                               void *stream);
+/* The per-step read-outs of a closed-loop episode, step-major: the slice of step t is contiguous.  Device pointers owned by the
+ * caller, who fills them before the call: 0.0 in ego_attn_score, 255 in the classes. */
+typedef struct gd_bc_rollout_reads {
+    float *ego_attn_score;        /* [91][N][4][A - 1] gd_bc_outputs.ego_attn_score of every step, or NULL */
+    const gd_bc_readout *readout; /* or NULL.  Its outputs are [91][N] rows each: step t's rows start at t * N * stride; labels
+                                   * is [N], by row */
+} gd_bc_rollout_reads;
+/* gd_bc_rollout (rows == NULL) or gd_bc_rollout_compact with the read-outs in the loop: step t's forward is
+ * gd_bc_forward(_rows)_readout with the outputs' slices of step t.  A row that is live before step t gets that call's bits; a
+ * row that is dead before step t, and every row of a step whose iteration does not exist or is >= n_steps, keeps the caller's
+ * fill.  With the list only live rows are computed.  Without it the forward runs on dead rows too: k_bc_readout drops a row
+ * whose `dead` byte is set (it is neither stored nor counted in bad_labels), and one more launch per step stores 0.0 over the
+ * scores of dead rows.  Every other output is gd_bc_rollout's (gd_bc_rollout_compact's), bit for bit.
+ * GD_ERR_INVALID / GD_ERR_UNSUPPORTED: whatever gd_bc_rollout (gd_bc_rollout_compact) and gd_bc_forward_readout refuse; a null
+ * reads, a reads with neither member, an ego_attn_score that is not 4-byte aligned. */
+int gd_bc_rollout_readout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers,
+                          const gd_bc_rollout_rows *rows, const gd_bc_rollout_reads *reads, int32_t n_steps);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
