@@ -18,6 +18,27 @@ SHAPES = ((1, 64, 5), (3, 64, 1), (17, 64, 5), (2, 128, 5))
 ROADS = 200
 
 
+def _cfg(num_layer, head, C, clip):
+    return dict(num_layer=num_layer, head_num_layers=head, n_components=C, clip_value=clip)
+
+
+# (name, B, A, R, cfg): the configurations the host checks accept beyond CFG, each at the smallest shape that reaches what it
+# is named for.  top: 288 parameter tensors (bc_opt_rule::MAX_TENSORS), 112 head outputs, head depth 4, road kin 104, every
+# count at its limit.  sweep: the reference sweep's model, 252 tensors, the clip10 clamp.  c9 / c10: 63 and 70 head outputs,
+# either side of one wave.  deep_branch / deep_fusion: asymmetric layer counts in both directions, A = 128 and even kin, a
+# clamp floor above 0.  defaults: more rows than the default chunk_rows = partials = 128 (chunks of 128 + 2).
+EDGE_CASES = (
+    ("top", 3, 64, 8, _cfg((4, 4), 4, 16, -20.0)),
+    ("sweep", 3, 64, 5, _cfg((4, 3), 2, 6, -10.0)),
+    ("c9", 3, 64, 1, _cfg((1, 1), 0, 9, -20.0)),
+    ("c10", 3, 64, 1, _cfg((1, 1), 0, 10, -20.0)),
+    ("deep_branch", 2, 128, 2, _cfg((1, 4), 1, 2, -20.0)),
+    ("deep_fusion", 3, 64, 2, _cfg((4, 1), 3, 3, 2.0)),
+    ("defaults", 130, 64, 1, _cfg((1, 1), 0, 1, -20.0)),
+)
+EDGE = {name: (B, A, R, cfg) for name, B, A, R, cfg in EDGE_CASES}
+
+
 def state_dict(num_stack, cfg=CFG, seed=0):
     """A numpy default_rng fills each tensor in list order.  Scaled so that attention is not flat: the q / k weights are large
     enough that softmax rows have a clear maximum (scores of standard deviation about 4), LayerNorm gains and biases are not

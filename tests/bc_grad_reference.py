@@ -11,6 +11,11 @@ leave the forward's values what they are and change the backward alone):
     "soft_clamp"      the covariance clamp passes the gradient outside its bounds
     "tanh_gelu"       GELU's derivative is that of the tanh approximation
     "normed_residual" the attention residual adds the LayerNorm'ed input instead of the input
+and three that are the right rule at bc_cases.CFG and wrong only at configurations of bc_cases.EDGE_CASES (bc_reference.py
+states them for the forward):
+    "head_one_trip"   the head's outputs of index >= 64 stay at their bias: their rows of head.head get no gradient
+    "rg_at_ro"        rg_attn layer i runs on ro_attn layer i's weights for i >= min(fusion, branch)
+    "floor_m20"       the covariance clamp's floor is -20 whatever clip_value says
 
 Also here: the host program of csrc/bc_grad_rule.hpp and the float64 autograd of the mixture nll it is compared with."""
 import math
@@ -31,6 +36,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 COV_MAX = 3.58352
 ROADS = 200
 WRONG = ("additive_mask", "soft_clamp", "tanh_gelu", "normed_residual")
+WRONG_AT_EDGES = ("head_one_trip", "rg_at_ro", "floor_m20")
 MINIMAL = dict(num_layer=(1, 1), head_num_layers=0, n_components=1, clip_value=-20.0)
 MARGIN = 1e-3
 
@@ -45,7 +51,7 @@ class Net:
     parameter a leaf."""
 
     def __init__(self, sd, max_agents, cfg=BC.CFG, dtype=torch.float64, wrong=None, device="cpu"):
-        assert wrong is None or wrong in WRONG
+        assert wrong is None or wrong in WRONG + WRONG_AT_EDGES
         self.params = OrderedDict((k, v.detach().clone().to(device=device, dtype=dtype).requires_grad_(True)) for k, v in sd.items())
         self.A, self.cfg, self.dtype, self.wrong, self.device = max_agents, cfg, dtype, wrong, device
         self.margins = {}
@@ -116,7 +122,8 @@ class Net:
         for i in range(cfg["num_layer"][1]):
             objs = self._self(objs, obj_mask, "ro_attn.%d" % i)
         for i in range(cfg["num_layer"][1]):
-            roads = self._self(roads, rm, "rg_attn.%d" % i)
+            blk = "ro_attn" if self.wrong == "rg_at_ro" and i >= min(cfg["num_layer"]) else "rg_attn"
+            roads = self._self(roads, rm, "%s.%d" % (blk, i))
         ego_tok = objs[:, :1]
         ego_ro = self._cross(ego_tok, objs[:, 1:], pm, "ego_ro_attn")
         ego_rg = self._cross(ego_tok, roads, rm, "ego_rg_attn")
@@ -127,10 +134,13 @@ class Net:
             pre.append(self._lin(h, "head.residual_block.%d.0" % i))
             h = h + torch.relu(pre[-1])
         raw = self._lin(h, "head.head")
+        if self.wrong == "head_one_trip":
+            raw = torch.cat([raw[:, :64], self.params["head.head.bias"][64:].expand(B, -1)], dim=1)
         rc = raw[:, 3 * C:6 * C].detach()
         self.margins = dict(clamp=float(torch.minimum((rc - cfg["clip_value"]).abs(), (rc - COV_MAX).abs()).min()),
                             relu=float(torch.stack(pre).detach().abs().min()))
-        return mixture_nll(raw, torch.as_tensor(expert).to(device=self.device, dtype=self.dtype), C, cfg["clip_value"], soft_clamp=self.wrong == "soft_clamp")
+        return mixture_nll(raw, torch.as_tensor(expert).to(device=self.device, dtype=self.dtype), C,
+                           -20.0 if self.wrong == "floor_m20" else cfg["clip_value"], soft_clamp=self.wrong == "soft_clamp")
 
 
 def mixture_nll(raw, expert, C, clip_value, cov_max=COV_MAX, soft_clamp=False):
@@ -154,7 +164,8 @@ def gradients(sd, obs, pm, rm, expert, grad_nll, max_agents, cfg=BC.CFG, dtype=t
     net = Net(sd, max_agents, cfg, dtype, wrong)
     nll = net.nll(obs, pm, rm, expert)
     (nll * torch.as_tensor(grad_nll).to(dtype)).sum().backward()
-    return (OrderedDict((k, v.grad.double().numpy()) for k, v in net.params.items()), nll.detach().double().numpy(),
+    zero = lambda v: torch.zeros_like(v) if v.grad is None else v.grad  # noqa: E731  (a wrong rule may leave a tensor unused)
+    return (OrderedDict((k, zero(v).double().numpy()) for k, v in net.params.items()), nll.detach().double().numpy(),
             dict(net.margins))
 
 
@@ -171,20 +182,29 @@ def grad_weights(B, kind, seed=11):
 
 
 def case_key(B, A, R, cfg=BC.CFG):
-    return (B, A, R, cfg["num_layer"], cfg["head_num_layers"], cfg["n_components"])
+    return (B, A, R, cfg["num_layer"], cfg["head_num_layers"], cfg["n_components"], cfg["clip_value"])
 
 
 # The seed of bc_cases.inputs per case: the first (from 1) with which both margins of `Net.nll` exceed MARGIN in float64 on
 # bc_cases.state_dict(R, cfg), so that no clamp and no ReLU of the head can flip between float32 and float64
 # (tools/bc_grad_golden.py --seeds prints this table).  bc_cases.SHAPES at bc_cases.CFG, the chunked case, one minimal model.
+# The key carries clip_value: two of the edge cases differ from another key in the clamp alone.
 INPUT_SEEDS = {
-    (1, 64, 5, (3, 2), 2, 6): 1,  # margins clamp 0.404 relu 0.00157
-    (3, 64, 1, (3, 2), 2, 6): 1,  # margins clamp 0.0548 relu 0.00793
-    (17, 64, 5, (3, 2), 2, 6): 1,  # margins clamp 0.00452 relu 0.00188
-    (2, 128, 5, (3, 2), 2, 6): 2,  # margins clamp 0.145 relu 0.0206
-    (5, 64, 5, (3, 2), 2, 6): 1,  # margins clamp 0.0181 relu 0.0033
-    (8, 64, 5, (3, 2), 2, 6): 1,  # margins clamp 0.0801 relu 0.00103
-    (3, 64, 1, (1, 1), 0, 1): 1,  # margins clamp 1.87 relu 0.0153
+    (1, 64, 5, (3, 2), 2, 6, -20.0): 1,  # margins clamp 0.404 relu 0.00157
+    (3, 64, 1, (3, 2), 2, 6, -20.0): 1,  # margins clamp 0.0548 relu 0.00793
+    (17, 64, 5, (3, 2), 2, 6, -20.0): 1,  # margins clamp 0.00452 relu 0.00188
+    (2, 128, 5, (3, 2), 2, 6, -20.0): 2,  # margins clamp 0.145 relu 0.0206
+    (5, 64, 5, (3, 2), 2, 6, -20.0): 1,  # margins clamp 0.0181 relu 0.0033
+    (8, 64, 5, (3, 2), 2, 6, -20.0): 1,  # margins clamp 0.0801 relu 0.00103
+    (3, 64, 1, (1, 1), 0, 1, -20.0): 1,  # margins clamp 1.87 relu 0.0153
+    # bc_cases.EDGE_CASES: top, sweep, c9, c10, deep_branch, deep_fusion, defaults
+    (3, 64, 8, (4, 4), 4, 16, -20.0): 1,  # margins clamp 0.0729 relu 0.00105
+    (3, 64, 5, (4, 3), 2, 6, -10.0): 1,  # margins clamp 0.0303 relu 0.0158
+    (3, 64, 1, (1, 1), 0, 9, -20.0): 1,  # margins clamp 0.0173 relu 0.0153
+    (3, 64, 1, (1, 1), 0, 10, -20.0): 1,  # margins clamp 0.0147 relu 0.0153
+    (2, 128, 2, (1, 4), 1, 2, -20.0): 1,  # margins clamp 2.64 relu 0.00612
+    (3, 64, 2, (4, 1), 3, 3, 2.0): 1,  # margins clamp 0.304 relu 0.0159
+    (130, 64, 1, (1, 1), 0, 1, -20.0): 2,  # margins clamp 0.271 relu 0.00133
 }
 
 

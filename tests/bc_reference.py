@@ -7,7 +7,13 @@ module itself (tests/golden/bc_forward_*.npz).
                       scoring -FLT_MAX, under which a row with every key masked attends uniformly
     "normed_residual" the attention residual adds the LayerNorm'ed input instead of the input
     "entity_major"    a token's R rows are taken by reshaping [R, n, k] to [n, R k] without the permute
-    "tanh_gelu"       the tanh approximation of GELU instead of the erf form"""
+    "tanh_gelu"       the tanh approximation of GELU instead of the erf form
+and four that are the right rule at bc_cases.CFG and wrong only at the configurations of bc_cases.EDGE_CASES:
+    "head_one_trip"   the head's outputs of index >= 64 stay at their bias (one trip of a 64-lane loop over the 7 C outputs)
+    "rg_at_ro"        rg_attn layer i is read at ro_attn's offset (ro_attn layer i's weights) for i >= min(fusion, branch):
+                      it needs branch > fusion to show (a model with one branch layer has no such i)
+    "floor_m20"       the covariance clamp's floor is -20 whatever clip_value says
+    "eval_one_trip"   `evaluate` sums the rows below 64 of a batch only (one trip of a 64-lane loop over the rows)"""
 import math
 
 import numpy as np
@@ -126,25 +132,28 @@ def forward(sd, obs, partner_mask, road_mask, max_agents, num_layer, head_num_la
     for i in range(num_layer[1]):
         objs = self_layer(objs, obj_mask, sd, "ro_attn.%d" % i, wrong)
     for i in range(num_layer[1]):
-        roads = self_layer(roads, rm, sd, "rg_attn.%d" % i, wrong)
+        blk = "ro_attn" if wrong == "rg_at_ro" and i >= min(num_layer) else "rg_attn"
+        roads = self_layer(roads, rm, sd, "%s.%d" % (blk, i), wrong)
     ego_tok = objs[:, :1]
     ego_ro, score = cross_layer(ego_tok, objs[:, 1:], pm, sd, "ego_ro_attn", wrong)
     ego_rg, _ = cross_layer(ego_tok, roads, rm, sd, "ego_rg_attn", wrong)
     context = np.concatenate([ego_tok[:, 0], ego_ro[:, 0], ego_rg[:, 0]], axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
         score = score / score.sum(-1, keepdims=True)
-    out = head(sd, context, head_num_layers, C, clip_value)
+    out = head(sd, context, head_num_layers, C, clip_value, wrong)
     out.update(context=context, ego_attn_score=score)
     return out
 
 
-def head(sd, context, head_num_layers, C, clip_value):
+def head(sd, context, head_num_layers, C, clip_value, wrong=None):
     sd = _sd64(sd)
     x = np.maximum(linear(context, sd, "head.input_layer.0"), 0.0)
     for i in range(head_num_layers):
         x = x + np.maximum(linear(x, sd, "head.residual_block.%d.0" % i), 0.0)
     raw = linear(x, sd, "head.head")
-    return mixture(raw, C, clip_value)
+    if wrong == "head_one_trip":
+        raw[:, 64:] = sd["head.head.bias"][64:]
+    return mixture(raw, C, -20.0 if wrong == "floor_m20" else clip_value)
 
 
 def mixture(raw, C, clip_value):
@@ -187,19 +196,31 @@ def nll(means, log_covariances, weights, expert):
     return -(M[:, 0] + np.log(np.exp(wl - M).sum(-1)))
 
 
-def evaluate(batches):
+def evaluate_sums(batches, wrong=None):
+    """evaluate()'s running sums, float64 [11]: the sum over batches of the batch's mean nll [0] and mean |pred - expert| per
+    dimension [1..3]; the sums of |pred - expert| over the rows whose expert magnitude exceeds the dimension's threshold [4..6]
+    and their counts [7..9]; the number of batches [10]."""
+    thr = tuple(float(np.float32(v)) for v in (2.0, 0.035, 0.023))  # torch compares a float32 tensor with the scalar in float32
+    acc = np.zeros(11)
+    for row_nll, pred, expert in batches:
+        n = len(row_nll)
+        keep = slice(0, 64 if wrong == "eval_one_trip" else n)
+        expert = np.asarray(expert, np.float64)[keep]
+        err = np.abs(np.asarray(pred, np.float64)[keep] - expert)
+        acc[0] += float(np.sum(np.asarray(row_nll, np.float64)[keep])) / n
+        acc[1:4] += err.sum(0) / n
+        for k in range(3):
+            big = np.abs(expert[:, k]) > thr[k]
+            acc[4 + k] += err[big, k].sum()
+            acc[7 + k] += big.sum()
+        acc[10] += 1
+    return acc
+
+
+def evaluate(batches, wrong=None):
     """The reference's evaluate() (baselines/il/il.py:99-180) from per-batch (nll [B], predicted [B, 3], expert [B, 3]): its eight
     numbers.  Per-batch means averaged over batches; the std2 figures are global sums over global counts."""
-    thr = tuple(float(np.float32(v)) for v in (2.0, 0.035, 0.023))  # torch compares a float32 tensor with the scalar in float32
-    loss, d, s, n = 0.0, np.zeros(3), np.zeros(3), np.zeros(3)
-    for row_nll, pred, expert in batches:
-        err = np.abs(np.asarray(pred, np.float64) - np.asarray(expert, np.float64))
-        loss += float(np.mean(row_nll))
-        d += err.mean(0)
-        for k in range(3):
-            big = np.abs(np.asarray(expert, np.float64)[:, k]) > thr[k]
-            s[k] += err[big, k].sum()
-            n[k] += big.sum()
-    nb = len(batches)
+    a = evaluate_sums(batches, wrong)
+    nb = a[10]
     with np.errstate(invalid="ignore", divide="ignore"):
-        return [loss / nb, d[0] / nb, d[1] / nb, d[2] / nb, s[0] / n[0], s[1] / n[1], s[2] / n[2], 0.0]
+        return [a[0] / nb, a[1] / nb, a[2] / nb, a[3] / nb, a[4] / a[7], a[5] / a[8], a[6] / a[9], 0.0]

@@ -30,28 +30,47 @@ def layout(R=1, cfg=BC.CFG):
     return tuple(shapes), end, int(end[-1])
 
 
-def zero_tensor(end):
-    """The tensor the first gradient zeroes whole: a 64 x 64 weight a third of the way in."""
+def zero_tensor(end, start=None):
+    """The tensor the first gradient zeroes whole: a 64 x 64 weight a third of the way in (or the first from `start`)."""
     sizes = np.diff(np.concatenate([[0], end]))
-    t = len(end) // 3
+    t = len(end) // 3 if start is None else start
     while sizes[t] != 64 * 64:
         t += 1
     return t
 
 
-def gradients(end, seed=0):
+def gradients(end, seed=0, zero_from=None, largest=None):
     """Three gradients [G] float32, in the order of the steps: magnitudes 10^U(-8, 0), a norm far above 20, with one whole
-    tensor of exact zeros (`zero_tensor`); magnitudes 10^U(-8, -3), a norm below 20 (the clip coefficient is exactly 1);
-    magnitudes 10^U(-8, 0) again without zeros."""
+    tensor of exact zeros (`zero_tensor(end, zero_from)`); magnitudes 10^U(-8, -3), a norm below 20 (the clip coefficient is
+    exactly 1); magnitudes 10^U(-8, 0) again without zeros.  largest: a tensor index whose values are doubled (exact in
+    float32) in all three, so that a tensor that is already among the largest has the largest norm by a factor."""
     G = int(end[-1])
     rng = np.random.default_rng(seed)
     sign = lambda: rng.choice([-1.0, 1.0], G)  # noqa: E731
     big = (sign() * 10.0 ** rng.uniform(-8.0, 0.0, G)).astype(np.float32)
     small = (sign() * 10.0 ** rng.uniform(-8.0, -3.0, G)).astype(np.float32)
     holes = (sign() * 10.0 ** rng.uniform(-8.0, 0.0, G)).astype(np.float32)
-    t = zero_tensor(end)
+    t = zero_tensor(end, zero_from)
     holes[(end[t - 1] if t else 0):end[t]] = 0.0
+    if largest is not None:
+        assert largest != t
+        for g in (holes, small, big):
+            g[end[largest - 1]:end[largest]] *= np.float32(2.0)
     return [holes, small, big]
+
+
+SECOND_TRIP = 256  # k_bc_step's workgroup: tensors from this index on are loaded in its second trip
+
+
+def top_gradients(end):
+    """`gradients` for a layout of more than SECOND_TRIP tensors (bc_cases' `top`: 288): the tensor of zeros and the tensor of
+    the largest norm (head.input_layer.0.weight, the largest tensor of all, doubled) both have an index >= SECOND_TRIP.
+    Returns (gradients, zero tensor, largest tensor)."""
+    sizes = np.diff(np.concatenate([[0], end]))
+    largest = SECOND_TRIP + int(np.argmax(sizes[SECOND_TRIP:]))
+    zt = zero_tensor(end, SECOND_TRIP)
+    assert len(end) > SECOND_TRIP and zt >= SECOND_TRIP and sizes[largest] == sizes.max()
+    return gradients(end, zero_from=SECOND_TRIP, largest=largest), zt, largest
 
 
 def tensor_norms64(g, end):
@@ -71,20 +90,30 @@ def get_grad_norm(params):
     return best, arg
 
 
-def adamw_reference(params, grads, end, dtype, lr, betas, eps, weight_decay, max_norm):
+def adamw_reference(params, grads, end, dtype, lr, betas, eps, weight_decay, max_norm, wrong=None):
     """Per step a dict of params, exp_avg, exp_avg_sq (flat float64 numpy), total (the norm before clipping), max_grad_norm and
     max_grad_tensor (get_grad_norm after the clip): torch's clip_grad_norm_ and AdamW(foreach=False) over the T tensors of the
-    layout, on the CPU in `dtype`."""
+    layout, on the CPU in `dtype`.  wrong="first_256": the tensors from SECOND_TRIP on are left out of the clip norm and out of
+    the largest tensor norm (every gradient is still scaled by the coefficient and every parameter stepped) -- the right rule
+    for a layout of at most SECOND_TRIP tensors."""
+    assert wrong in (None, "first_256")
     cuts = [int(e) for e in end[:-1]]
     ps = [torch.nn.Parameter(torch.tensor(a).to(dtype)) for a in np.split(np.asarray(params), cuts)]
     opt = torch.optim.AdamW(ps, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, foreach=False)
     flat = lambda ts: np.concatenate([t.detach().double().numpy().reshape(-1) for t in ts])  # noqa: E731
+    seen = ps[:SECOND_TRIP] if wrong else ps
     out = []
     for g in grads:
         for p, a in zip(ps, np.split(np.asarray(g), cuts)):
             p.grad = torch.tensor(a).to(dtype)
-        total = torch.nn.utils.clip_grad_norm_(ps, max_norm, foreach=False)
-        best, arg = get_grad_norm(ps)
+        if wrong:
+            total = torch.linalg.vector_norm(torch.stack([p.grad.reshape(-1).norm(2) for p in seen]), 2)
+            coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
+            for p in ps:
+                p.grad.mul_(coef)
+        else:
+            total = torch.nn.utils.clip_grad_norm_(ps, max_norm, foreach=False)
+        best, arg = get_grad_norm(seen)
         opt.step()
         out.append(dict(params=flat(ps), exp_avg=flat([opt.state[p]["exp_avg"] for p in ps]),
                         exp_avg_sq=flat([opt.state[p]["exp_avg_sq"] for p in ps]), total=float(total.double()),

@@ -75,7 +75,8 @@ def selected(mask, exp):
 
 
 def standin_taps(sd, obs, pm, rm, A, dtype=torch.float32, cfg=BC.CFG):
-    """Both taps by bc_cases.StandIn's own layers in one dtype on the CPU: {tap: [B, A, 64] float64 numpy}."""
+    """Both taps by bc_cases.StandIn's own layers in one dtype on the CPU: {tap: [B, A, 64] float64 numpy}, and under (tap, i)
+    the same tokens after layer i of the block."""
     s = BC.StandIn(sd, A, cfg, dtype, "cpu")
     with torch.no_grad():
         o = torch.from_numpy(obs).to(dtype)
@@ -87,12 +88,15 @@ def standin_taps(sd, obs, pm, rm, A, dtype=torch.float32, cfg=BC.CFG):
         x = torch.cat([s._embed(ego, "ego_state_net").unsqueeze(1), s._embed(ro, "road_object_net"), s._embed(rg, "road_graph_net")], 1)
         ego_mask = torch.zeros(B, 1, dtype=torch.bool)
         all_mask, obj_mask = torch.cat([ego_mask, pmt, rmt], -1), torch.cat([ego_mask, pmt], -1)
+        out = {}
         for i in range(cfg["num_layer"][0]):
             x = s._self(x, all_mask, "fusion_attn.%d" % i)
-        out = {"fusion_attn": x[:, :A].double().numpy().copy()}
+            out[("fusion_attn", i)] = x[:, :A].double().numpy().copy()
+        out["fusion_attn"] = x[:, :A].double().numpy().copy()
         objs = x[:, :A]
         for i in range(cfg["num_layer"][1]):
             objs = s._self(objs, obj_mask, "ro_attn.%d" % i)
+            out[("ro_attn", i)] = objs.double().numpy().copy()
         out["ro_attn"] = objs.double().numpy().copy()
     return out
 

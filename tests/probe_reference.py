@@ -9,7 +9,8 @@ CLASSES = 64
 
 
 def taps(sd, obs, partner_mask, road_mask, max_agents, num_layer):
-    """{'fusion_attn', 'ro_attn'}: tokens 0 .. A - 1 of the block's last_hidden_state, [B, A, 64] float64."""
+    """{'fusion_attn', 'ro_attn'}: tokens 0 .. A - 1 of the block's last_hidden_state, [B, A, 64] float64; and under the key
+    (tap, i) the same tokens after layer i of that block (what `hidden(tap=, layer=i)` taps)."""
     sd = REF._sd64(sd)
     obs = np.asarray(obs, dtype=np.float64)
     A, B = max_agents, obs.shape[0]
@@ -20,12 +21,15 @@ def taps(sd, obs, partner_mask, road_mask, max_agents, num_layer):
                         REF.embed(rg, sd, "road_graph_net")], axis=1)
     ego_mask = np.zeros((B, 1), dtype=bool)
     all_mask, obj_mask = np.concatenate([ego_mask, pm, rm], 1), np.concatenate([ego_mask, pm], 1)
+    out = {}
     for i in range(num_layer[0]):
         x = REF.self_layer(x, all_mask, sd, "fusion_attn.%d" % i)
-    out = {"fusion_attn": x[:, :A].copy()}
+        out[("fusion_attn", i)] = x[:, :A].copy()
+    out["fusion_attn"] = x[:, :A].copy()
     objs = x[:, :A]
     for i in range(num_layer[1]):
         objs = REF.self_layer(objs, obj_mask, sd, "ro_attn.%d" % i)
+        out[("ro_attn", i)] = objs.copy()
     out["ro_attn"] = objs
     return out
 

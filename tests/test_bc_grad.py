@@ -67,8 +67,8 @@ def test_restatement_equals_the_reference_modules_backward():
 
 @pytest.mark.parametrize("key", list(GR.INPUT_SEEDS))
 def test_margins_keep_clamps_and_relus_from_flipping(key):
-    B, A, R, num_layer, hl, C_ = key
-    cfg = dict(num_layer=num_layer, head_num_layers=hl, n_components=C_, clip_value=-20.0)
+    B, A, R, num_layer, hl, C_, clip = key
+    cfg = dict(num_layer=num_layer, head_num_layers=hl, n_components=C_, clip_value=clip)
     sd, obs, pm, rm, expert, _ = GR.case_inputs(B, A, R, cfg)
     net = GR.Net(sd, A, cfg)
     with torch.no_grad():

@@ -15,6 +15,7 @@ from gpudrive_lab_amd import _capi
 from gpudrive_lab_amd import bc_policy as BP
 
 from . import bc_cases as BC
+from . import bc_grad_reference as GR
 from . import bc_reference as REF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,14 +23,19 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 _CACHE = {}
 
 
-def case(B, A, R):
-    """The seeded case and its float64 restatement, computed once and shared (nobody writes into it)."""
-    key = (B, A, R)
+def case(B, A, R, cfg=BC.CFG):
+    """The seeded case and its float64 restatement, computed once and shared (nobody writes into it).  At BC.CFG the weights
+    and inputs are bc_cases' own (seed 1); at any other configuration (bc_cases.EDGE_CASES) they are the backward tests'
+    (bc_grad_reference.state_dict and the input seed that keeps its margins), so that both suites share one case."""
+    key = GR.case_key(B, A, R, cfg)
     if key not in _CACHE:
-        sd = BC.state_dict(R)
-        obs, pm, rm, expert, u, z, kinds = BC.inputs(B, A, R)
-        ref = REF.forward(sd, obs, pm, rm, A, **BC.CFG)
-        _CACHE[key] = dict(sd=sd, obs=obs, pm=pm, rm=rm, expert=expert, u=u, z=z, kinds=kinds, ref=ref)
+        if cfg is BC.CFG:
+            sd, seed = BC.state_dict(R), 1
+        else:
+            sd, seed = GR.state_dict(R, cfg), GR.INPUT_SEEDS[key]
+        obs, pm, rm, expert, u, z, kinds = BC.inputs(B, A, R, seed=seed)
+        ref = REF.forward(sd, obs, pm, rm, A, **cfg)
+        _CACHE[key] = dict(sd=sd, obs=obs, pm=pm, rm=rm, expert=expert, u=u, z=z, kinds=kinds, ref=ref, cfg=cfg)
     return _CACHE[key]
 
 

@@ -22,10 +22,10 @@ GUARD = 64
 OUTPUTS = ("context", "means", "log_covariances", "covariances", "weights", "actions", "nll", "ego_attn_score", "component")
 
 
-def _policy(A, R, sd=None, chunk_rows=CHUNK):
+def _policy(A, R, sd=None, chunk_rows=CHUNK, cfg=BC.CFG):
     from gpudrive_lab_amd.bc_policy import DeviceBCPolicy
     return DeviceBCPolicy.from_state_dict(sd if sd is not None else _state_dict(R), max_agents=A, num_stack=R,
-                                          chunk_rows=chunk_rows, **BC.CFG)
+                                          chunk_rows=chunk_rows, **cfg)
 
 
 class _Guarded:
@@ -77,10 +77,10 @@ def _live_rows_of(rows, count=None):
     return lr, made
 
 
-def _forward_case(A, R):
+def _forward_case(A, R, cfg=BC.CFG):
     obs, pm, rm, expert, u, z, _ = BC.inputs(B_F, A, R)
     obs, pm, rm, expert, u, z = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (obs, pm, rm, expert, u, z))
-    pol = _policy(A, R, sd=BC.state_dict(R))
+    pol = _policy(A, R, sd=BC.state_dict(R, cfg), cfg=cfg)
     full = {det: pol.forward(obs, pm, rm, OUTPUTS, deterministic=det, u=u, z=z, expert_actions=expert) for det in (True, False)}
     assert not torch.equal(full[True]["actions"], full[False]["actions"]), "the draw changed nothing"
     outs = {}
@@ -130,6 +130,28 @@ def test_forward_on_a_row_list_equals_the_full_forward(A, R):
     _check_listed("A=%d R=%d the methods" % (A, R), [1, 5, 10], {k: outs[k] for k in written}, full[True])
     for k in ("log_covariances", "component"):
         assert bool((outs[k].buf == outs[k].canary).all()), k + " was not asked for"
+
+
+@pytest.mark.parametrize("name", ["top", "c10"])
+def test_forward_on_a_row_list_at_the_edge_configurations(name):
+    """bc_cases.EDGE_CASES' largest model and the first mixture whose head outputs take a second trip: the rows of a list have
+    the full forward's bits in every output, and nothing else is written."""
+    _, A, R, cfg = BC.EDGE[name]
+    pol, (obs, pm, rm, expert, u, z), full, outs = _forward_case(A, R, cfg)
+    out = {k: g.view for k, g in outs.items()}
+    assert full[True]["means"].shape == (B_F, 1, cfg["n_components"], 3)
+    lists = _lists()
+    for which in ("empty", "last", "first5", "eight_permuted", "all", "no_middle_chunk"):
+        rows = lists[which]
+        lr, made = _live_rows_of(rows)
+        for det in (True, False):
+            what = "%s list %s%s" % (name, which, " det" if det else " drawn")
+            for g in outs.values():
+                g.refill()
+            pol.forward(obs, pm, rm, OUTPUTS, deterministic=det, u=u, z=z, expert_actions=expert, out=out, rows=lr)
+            _check_listed(what, rows, outs, full[det])
+            for k, g in made.items():
+                g.check(what + " " + k)
 
 
 def test_a_count_above_b_and_entries_that_are_no_row():

@@ -14,6 +14,19 @@ The largest, 8.62, is the one-sample case, where the yardstick itself is one dra
 kernel's 3.6e-7, a few float32 ulps of a weight near 1; with 3 and 17 samples the ratios are about 1).  K is the next power
 of two at or above twice the largest: 32.  A ratio above 16 would be a bug, not a bound to raise.  (The recorded-episode
 batch, A = 128: 1.03, 1.23, 0.99, 1.05, 0.25.)
+The configurations of bc_cases.EDGE_CASES (test_forward_at_the_edge_configurations; weights and inputs are the backward
+tests', bc_grad_reference.case_inputs) under the same K, measured once:
+    name (B, A, R)            context  means  log_covariances  weights  nll
+    top (3, 64, 8)            0.89     1.61   1.90             1.56     2.52
+    sweep (3, 64, 5)          1.08     1.24   0.60             1.48     0.31
+    c9 (3, 64, 1)             1.56     1.47   1.75             2.85     1.84
+    c10 (3, 64, 1)            1.56     1.71   1.53             0.72     0.50
+    deep_branch (2, 128, 2)   1.08     0.75   0.74             1.28     0.49
+    deep_fusion (3, 64, 2)    0.64     0.83   0.71             2.73     0.73
+    defaults (130, 64, 1)     0.86     0.97   0.90             0 / 0    1.61
+(`defaults` has one component: its weight is exactly 1 on both sides.)  Depth does not move the ratio: `top` sums over twelve
+self-attention layers and stays where the three-row case of five layers is.  gd_bc_eval_accumulate called directly with 63,
+64, 65, 130 and 513 rows stays within 0.02 of its bound (n + 8) 2^-24 max(1, |value|).
 Actions, the component and ego_attn_score's normalisation are held to the rule in float64 on the kernel's OWN mixture
 parameters: the deterministic action exactly, the draw where u falls to within 1e-5 of the running sum."""
 import numpy as np
@@ -90,7 +103,7 @@ def _yardstick(c, A):
         ref = dict(c["ref"])
         ref["nll"] = REF.nll(ref["means"], ref["log_covariances"], ref["weights"], c["expert"][:, 0])
         c["ref_nll"] = ref["nll"]
-        c["E"] = BC.yardstick(BC.standin_float32(c["sd"], c["obs"], c["pm"], c["rm"], A, expert=c["expert"]), ref)
+        c["E"] = BC.yardstick(BC.standin_float32(c["sd"], c["obs"], c["pm"], c["rm"], A, c.get("cfg", BC.CFG), expert=c["expert"]), ref)
     return c["E"]
 
 
@@ -130,19 +143,21 @@ def _check_rule(what, got, u, z, det, A):
     assert (s >= 0).all() and (np.abs(s.sum(-1) - 1.0) <= (A + 8) * EPS).all(), what + ": ego_attn_score rows do not sum to 1"
 
 
-def _policy(A, R, sd=None, **kw):
+def _policy(A, R, sd=None, cfg=BC.CFG, **kw):
     from gpudrive_lab_amd.bc_policy import DeviceBCPolicy
-    return DeviceBCPolicy.from_state_dict(sd if sd is not None else BC.state_dict(R), max_agents=A, num_stack=R, **BC.CFG, **kw)
+    return DeviceBCPolicy.from_state_dict(sd if sd is not None else BC.state_dict(R), max_agents=A, num_stack=R, **cfg, **kw)
 
 
-@pytest.mark.parametrize("B,A,R", BC.SHAPES, ids=lambda v: str(v))
-def test_forward_against_the_float64_restatement(B, A, R):
-    c = case(B, A, R)
-    what = "B=%d A=%d R=%d" % (B, A, R)
-    bc = _policy(A, R, c["sd"])
+def _forward_checks(B, A, R, cfg, what):
+    """Everything the forward is held to at one case: K E on the compared outputs, nll and ego_attn_score; the float64 rule on the
+    kernel's own mixture parameters for the deterministic action and the draws; canaries, every byte written, equal bits
+    between calls.  Returns (case, the outputs on the host)."""
+    c = case(B, A, R, cfg)
+    C_, clip = cfg["n_components"], cfg["clip_value"]
+    bc = _policy(A, R, c["sd"], cfg)
     obs, pm, rm, expert, u, z = _dev(c["obs"], c["pm"], c["rm"], c["expert"], c["u"], c["z"])
     fresh = _host(bc.forward(obs, pm, rm, ALL, deterministic=True, expert_actions=expert))
-    assert fresh["actions"].shape == (B, 1, 3) and fresh["means"].shape == (B, 1, 6, 3) and fresh["weights"].shape == (B, 1, 6)
+    assert fresh["actions"].shape == (B, 1, 3) and fresh["means"].shape == (B, 1, C_, 3) and fresh["weights"].shape == (B, 1, C_)
     carver, out = _carved_outputs(bc, B)
     # the second call of the shape: no host synchronisation, out= buffers, canaries either side, every byte written
     _no_sync(lambda: bc.forward(obs, pm, rm, ALL, deterministic=True, expert_actions=expert, out=out))
@@ -175,11 +190,65 @@ def test_forward_against_the_float64_restatement(B, A, R):
         assert np.array_equal(bc(obs, pm, rm, u=d_u, z=z).cpu().numpy(), drawn["actions"])
     own = drawn["weights"][:, 0]
     assert np.array_equal(drawn["component"][0::2], np.argmax(own > 0, axis=-1)[0::2])  # u = 0: the first component with any mass
-    reached = np.cumsum(own.astype(np.float64), -1)[:, :-1].max(-1) > BC.edge_uniforms(2)[1] - 1e-5
-    assert (drawn["component"][1::2] == 5)[~reached[1::2]].all()  # u just below 1: the last, unless the sum is there before
-    # (f): raw covariances below clip_value and above 3.58352 are clamped exactly
+    reached = np.cumsum(own.astype(np.float64), -1)[:, :-1].max(-1, initial=0.0) > BC.edge_uniforms(2)[1] - 1e-5
+    assert (drawn["component"][1::2] == C_ - 1)[~reached[1::2]].all()  # u just below 1: the last, unless the sum is there before
+    # (f): raw covariances below clip_value and above 3.58352 are clamped exactly (pushed there where the mixture has room)
     lc = got["log_covariances"][:, 0].reshape(B, -1)
-    assert (lc[:, 1] == np.float32(-20.0)).all() and (lc[:, 5] == np.float32(3.58352)).all()
+    if cfg is BC.CFG:
+        assert (lc[:, 1] == np.float32(-20.0)).all() and (lc[:, 5] == np.float32(3.58352)).all()
+    # and wherever the float64 raw value lies outside a bound by more than the clamp margin, whatever pushed it there
+    raw = c["ref"]["raw"][:, 3 * C_:6 * C_]
+    below, above = raw < clip - 1e-3, raw > REF.COV_MAX + 1e-3
+    assert (lc[below] == np.float32(clip)).all() and (lc[above] == np.float32(3.58352)).all()
+    assert C_ < 2 or (below.any() and above.any()), what + ": the case has no covariance outside the clamp"
+    return c, got
+
+
+@pytest.mark.parametrize("B,A,R", BC.SHAPES, ids=lambda v: str(v))
+def test_forward_against_the_float64_restatement(B, A, R):
+    _forward_checks(B, A, R, BC.CFG, "B=%d A=%d R=%d" % (B, A, R))
+
+
+@pytest.mark.parametrize("name", [c[0] for c in BC.EDGE_CASES])
+def test_forward_at_the_edge_configurations(name):
+    """bc_cases.EDGE_CASES through the same checks.  Ratios measured once on an MI355X: the table in DESIGN section 2."""
+    B, A, R, cfg = BC.EDGE[name]
+    c, got = _forward_checks(B, A, R, cfg, "%s B=%d A=%d R=%d" % (name, B, A, R))
+    if name == "deep_fusion":  # a floor above 0: it cuts through the raw covariances, and the device's equal it exactly below
+        raw = c["ref"]["raw"][:, 3 * cfg["n_components"]:6 * cfg["n_components"]]
+        below, above = raw < cfg["clip_value"] - 1e-3, (raw > cfg["clip_value"] + 1e-3) & (raw < REF.COV_MAX - 1e-3)
+        assert below.any() and above.any()
+        lc = got["log_covariances"][:, 0].reshape(B, -1)
+        assert (lc[below] == np.float32(cfg["clip_value"])).all() and (lc[above] > np.float32(cfg["clip_value"])).all()
+
+
+@pytest.mark.parametrize("n", [63, 64, 65, 130, 513])
+def test_eval_accumulate_past_one_row_per_lane(n):
+    """gd_bc_eval_accumulate called directly, two batches of n rows into one accumulator between canaries, against
+    bc_reference.evaluate's sums in float64: (n + 8) 2^-24 max(1, |value|) per mean and per sum, the counts and the number of
+    batches exact, and the eight numbers of evaluate() from them."""
+    from gpudrive_lab_amd import _capi
+    from tests.test_bc_edge_cases import eval_batches, eval_bound
+    batches = eval_batches(n)
+    want = REF.evaluate_sums(batches)
+    carver = Carver()
+    acc = carver.carve("acc", (11,))
+    acc.zero_()
+    L = _capi.lib()
+    for nll, pred, ex in batches:
+        d_nll, d_pred, d_ex = _dev(nll, pred, ex)
+        _no_sync(lambda: _capi.check(L.gd_bc_eval_accumulate(n, d_nll.data_ptr(), d_pred.data_ptr(), d_ex.data_ptr(), acc.data_ptr(), None)))
+        torch.cuda.synchronize()
+    carver.assert_guards("gd_bc_eval_accumulate n = %d" % n)
+    got = acc.cpu().numpy().astype(np.float64)
+    bound = eval_bound(n, want)
+    print("BC EVAL n=%d err/bound %s" % (n, " ".join("%.2f" % v for v in (np.abs(got - want) / bound)[:7])))
+    assert (np.abs(got - want)[:7] <= bound[:7]).all(), (n, got, want)
+    assert np.array_equal(got[7:], want[7:]) and got[10] == 2, (n, got[7:], want[7:])
+    assert (want[7:10] > 0).all() and (want[7:10] < 2 * n).all(), "experts on both sides of every threshold"
+    eight = np.array(REF.evaluate(batches)[:7])
+    mine = np.concatenate([got[:4] / got[10], got[4:7] / got[7:10]])
+    assert (np.abs(mine - eight) <= eval_bound(n, eight)).all()
 
 
 def test_masked_features_do_not_reach_the_context_and_all_masked_rows_are_uniform():

@@ -80,6 +80,26 @@ def test_hidden_layer_none_and_last_are_todays_hidden(A, R):
             bc.hidden(obs, pm, rm, tap="ro_attn", layer=bad)
 
 
+@pytest.mark.parametrize("name", ["top", "deep_branch", "deep_fusion"])
+def test_hidden_layer_at_the_edge_layer_counts(name):
+    """(4, 4), (1, 4) and (4, 1) layers: layer=None and the block's last index are today's `hidden`, every inner index is another
+    tensor, and the index one past the block is refused.  (The values: test_gpu_lp_probe holds every index to float64.)"""
+    from tests import bc_grad_reference as GR
+    B, A, R, cfg = BC.EDGE[name]
+    bc = _policy(A, R, GR.state_dict(R, cfg), cfg, chunk_rows=2)
+    obs, pm, rm, _, _ = _inp(B, A, R)
+    for tap, n in zip(("fusion_attn", "ro_attn"), cfg["num_layer"]):
+        today = bc.hidden(obs, pm, rm, tap=tap)
+        _same(bc.hidden(obs, pm, rm, tap=tap, layer=None), today, "%s %s layer=None" % (name, tap))
+        seen = [bc.hidden(obs, pm, rm, tap=tap, layer=i) for i in range(n)]
+        _same(seen[-1], today, "%s %s layer=%d" % (name, tap, n - 1))
+        for i in range(n):
+            for j in range(i):
+                assert not torch.equal(seen[i], seen[j]), (name, tap, i, j)
+        with pytest.raises(ValueError, match="layer"):
+            bc.hidden(obs, pm, rm, tap=tap, layer=n)
+
+
 # ---- 2. where the tap is the probes' own, the read-out is their predict
 
 @pytest.mark.parametrize("tap,model", [("fusion_attn", "early_lp"), ("ro_attn", "late_lp")])

@@ -3,8 +3,9 @@
 The kernels are held to the host program of csrc/bc_opt_rule.hpp BIT FOR BIT (tests/test_bc_update.py holds that program to
 torch in float64), the fused call to its four parts bit for bit, its gradient to `TrainableBCPolicy`'s bit for bit, and one
 whole step to the float64 pipeline of the differentiable stand-in (tests/bc_update_reference.pipeline) within the bound
-tests/test_gpu_bc_grad.py derives for a step, with the same K.  Small models only: 64 agent slots, B in {1, 3, 8, 17},
-R in {1, 5}."""
+tests/test_gpu_bc_grad.py derives for a step, with the same K.  Small models: 64 agent slots, B in {1, 3, 8, 17},
+R in {1, 5}; and of bc_cases.EDGE_CASES `top` (288 tensors: the optimiser's kernels past their first 256, and the update's
+gradient in three chunks) and `defaults` (130 rows under the default chunk_rows and partials)."""
 import ctypes as C
 
 import numpy as np
@@ -91,12 +92,28 @@ def test_adamw_three_steps_are_the_host_programs_bit_for_bit():
     """gd_bc_adamw on the synthetic gradients of test_bc_update.py (above 20 with one whole tensor of zeros, below 20, above
     20), uploaded as they are: every word the three launches write against the host program, after every step."""
     R = 1
-    sd = BC.state_dict(R)
-    bc = _trainer(sd, 64, R, batch_size=4, **SMALL)
-    names, end, G = UR.layout(R)
+    _adamw_three_steps(R, BC.CFG, BC.state_dict(R), UR.gradients(UR.layout(R)[1]), UR.zero_tensor(UR.layout(R)[1]))
+
+
+def test_adamw_three_steps_at_288_tensors_are_the_host_programs_bit_for_bit():
+    """bc_cases' `top` layout: 288 tensors, bc_opt_rule::MAX_TENSORS.  The tensor of zeros and the tensor of the largest norm
+    both have an index >= 256, so max_grad_tensor, the clip norm and tensor_norms[256:] can only be the host program's if the
+    workgroup of 256 made its second trip over the tensors."""
+    _, _, R, cfg = BC.EDGE["top"]
+    _, end, _ = UR.layout(R, cfg)
+    grads, zt, largest = UR.top_gradients(end)
+    assert len(end) == 288 and zt >= 256 and largest >= 256
+    host = _adamw_three_steps(R, cfg, GR.state_dict(R, cfg), grads, zt)
+    for h in host:
+        assert h["max_grad_tensor"] == largest and (np.delete(h["tensor_norms"][256:], zt - 256) > 0).all()
+        assert h["tensor_norms"][:256].max() < h["tensor_norms"][largest]
+
+
+def _adamw_three_steps(R, cfg, sd, grads, zt):
+    bc = _trainer(sd, 64, R, cfg, batch_size=4, **SMALL)
+    names, end, G = UR.layout(R, cfg)
     assert names == bc._names and G == bc.G and np.array_equal(bc._tensor_end.cpu().numpy(), end)
     p0 = np.concatenate([sd[k].numpy().reshape(-1) for k in names])
-    grads = UR.gradients(end)
     z = np.zeros(G, np.float32)
     host = UR.run_adamw_host(p0, z, z, grads, end, **UR.ADAMW)
     _assert_blob_follows(bc, "before")
@@ -116,12 +133,13 @@ def test_adamw_three_steps_are_the_host_programs_bit_for_bit():
         sums = sums + np.array([h["total"], h["max_grad_norm"]], np.float32)
         assert np.array_equal(got["stats_sum"][4:], sums.view(np.int32)), what + ": stats_sum[4..6)"
         _assert_blob_follows(bc, what)
-    assert host[0]["total"] > 20 and host[1]["total"] < 20 and host[0]["tensor_norms"][UR.zero_tensor(end)] == 0
+    assert host[0]["total"] > 20 and host[1]["total"] < 20 and host[0]["tensor_norms"][zt] == 0
     # the scalars the last launch read
     scal = bc._scal.cpu().numpy()
     assert scal[0] == host[2]["total"] and scal[1] == np.float32(20.0) / (host[2]["total"] + np.float32(1e-6))
     sq = scal[4:].view(np.float64)
     assert sq.shape == (len(end),) and np.array_equal(np.sqrt(sq.astype(np.float32)), host[2]["tensor_norms"])
+    return host
 
 
 @pytest.mark.parametrize("n", UR.ROWS)
@@ -150,15 +168,29 @@ def test_train_rows_are_the_host_programs_bit_for_bit(n):
 
 def test_the_updates_gradient_is_the_trainable_policys_bit_for_bit():
     for B, A, R in ((17, 64, 5), (3, 64, 1)):
-        sd, (obs, expert, pm, rm) = _case_tensors(B, A, R)
-        bc = _trainer(sd, A, R, batch_size=32, **SMALL)
-        tbp = _train(sd, A, R, **SMALL)
-        bc.update(obs, expert, pm, rm)
-        tbp(obs, pm, rm, expert).mean().backward()
-        flat = torch.cat([p.grad.reshape(-1) for p in tbp.parameters()])
-        assert [k for k, _ in tbp.named_parameters()] == list(bc._names)
-        assert np.array_equal(_bits(bc.grad), _bits(flat)), (B, A, R)
-        assert np.abs(bc.grad.cpu().numpy()).max() > 0
+        _same_gradient_bits(B, A, R, BC.CFG, 32, SMALL)
+
+
+@pytest.mark.parametrize("name", ["top", "defaults"])
+def test_the_updates_gradient_at_the_edge_configurations(name):
+    """`top` with three chunks; `defaults` with the chunk_rows and partials every caller gets (128 each) and 130 rows."""
+    B, A, R, cfg = BC.EDGE[name]
+    bc, tbp = _same_gradient_bits(B, A, R, cfg, B, dict(chunk_rows=2, partials=3) if name == "top" else {})
+    if name == "defaults":
+        assert bc.policy.chunk_rows == tbp.chunk_rows == BP.DEFAULT_CHUNK == 128 and bc._g.num_partials == tbp.partials == 128 < B
+
+
+def _same_gradient_bits(B, A, R, cfg, batch_size, kw):
+    sd, (obs, expert, pm, rm) = _case_tensors(B, A, R, cfg)
+    bc = _trainer(sd, A, R, cfg, batch_size=batch_size, **kw)
+    tbp = _train(sd, A, R, cfg, **kw)
+    bc.update(obs, expert, pm, rm)
+    tbp(obs, pm, rm, expert).mean().backward()
+    flat = torch.cat([p.grad.reshape(-1) for p in tbp.parameters()])
+    assert [k for k, _ in tbp.named_parameters()] == list(bc._names)
+    assert np.array_equal(_bits(bc.grad), _bits(flat)), (B, A, R)
+    assert np.abs(bc.grad.cpu().numpy()).max() > 0
+    return bc, tbp
 
 
 def test_update_is_the_four_calls_bit_for_bit():

@@ -15,6 +15,11 @@ the kernel's error must be <= K E.  K was set from ratios measured ONCE on an MI
 The largest, 2.54, is the gradient of the 'ego' probe on 17 samples, of which 8 are selected: both the yardstick (1.1e-6) and the
 kernel's error (2.8e-6) are single draws of a few float32 roundings of a mean over 8 rows.  K = 8.
 K is the next power of two at or above twice the largest (5.08).  A ratio above 16 would be a bug, not a bound to raise.
+The taps of bc_cases.EDGE_CASES at every layer index (test_hidden_at_every_layer_of_the_edge_configurations), fusion layers
+then ro layers, the last of each the tap itself:
+    top (4, 4)          1.12 1.20 1.11 1.13   1.19 1.16 1.07 0.98
+    deep_branch (1, 4)  1.10                  1.17 1.04 1.06 1.14
+    deep_fusion (4, 1)  1.24 1.06 0.82 1.02   0.95
 pred, loss_row, the counters, the reduction of the partials and AdamW are held to the host program of csrc/lp_rule.hpp on the
 kernel's OWN logits, partials and gradient: exactly, except loss_row, where expf and logf stand between (4 float32 ulps of
 its terms, as the header states)."""
@@ -123,6 +128,33 @@ def test_hidden_of_both_taps_against_float64(B, A, R):
         _ratio(what, float(np.abs(got.astype(np.float64) - t64[tap]).max()), float(np.abs(t32[tap] - t64[tap]).max()))
     ctx = bc.context(obs, pm, rm).cpu().numpy()
     assert np.array_equal(got[:, 0].view(np.int32), ctx[:, :64].view(np.int32))  # ro_attn's token 0 IS the context's first third
+
+
+@pytest.mark.parametrize("name", ["top", "deep_branch", "deep_fusion"])
+def test_hidden_at_every_layer_of_the_edge_configurations(name):
+    """bc_cases.EDGE_CASES with the maximal and both asymmetric layer counts: `gd_bc_hidden` at both taps and
+    `gd_bc_hidden_layer` at every layer index the block has, each against its own float64 tap (a wrong layer offset gives
+    another layer's tokens).  The last index is the tap itself, bit for bit."""
+    B, A, R, cfg = BC.EDGE[name]
+    c = case(B, A, R, cfg)
+    t64 = PREF.taps(c["sd"], c["obs"], c["pm"], c["rm"], A, cfg["num_layer"])
+    t32 = PC.standin_taps(c["sd"], c["obs"], c["pm"], c["rm"], A, cfg=cfg)
+    bc = _policy(A, R, c["sd"], cfg, chunk_rows=2)  # a short last chunk
+    obs, pm, rm = _dev(c["obs"], c["pm"], c["rm"])
+    for tap, layers in zip(PC.TAPS, cfg["num_layer"]):
+        whole = bc.hidden(obs, pm, rm, tap=tap).cpu().numpy()
+        _ratio("hidden %s %s" % (tap, name), float(np.abs(whole.astype(np.float64) - t64[tap]).max()), float(np.abs(t32[tap] - t64[tap]).max()))
+        for i in range(layers):
+            what = "hidden %s layer %d %s" % (tap, i, name)
+            carver = Carver()
+            out = carver.carve("hidden", (B, A, 64))
+            bc.hidden(obs, pm, rm, tap=tap, layer=i, out=out)
+            carver.assert_guards(what)
+            got = out.cpu().numpy()
+            _ratio(what, float(np.abs(got.astype(np.float64) - t64[(tap, i)]).max()), float(np.abs(t32[(tap, i)] - t64[(tap, i)]).max()))
+        assert np.array_equal(got.view(np.int32), whole.view(np.int32)), what
+        if layers > 1:  # and a neighbouring layer's float64 tokens are far outside the bound: the index selects
+            assert np.abs(t64[(tap, layers - 2)] - t64[tap]).max() > 1000 * K * np.abs(t32[tap] - t64[tap]).max()
 
 
 def test_hidden_rows_above_the_chunk_equal_the_concatenation_of_the_chunks():

@@ -31,7 +31,7 @@ def positions(name_index, numel):
 
 def seeds():
     todo = [(B, A, R, BC.CFG) for B, A, R in BC.SHAPES] + [(5, 64, 5, BC.CFG), (8, 64, 5, BC.CFG)]
-    todo += [(3, 64, 1, GR.MINIMAL)]
+    todo += [(3, 64, 1, GR.MINIMAL)] + [(B, A, R, cfg) for _, B, A, R, cfg in BC.EDGE_CASES]
     for B, A, R, cfg in todo:
         sd = GR.state_dict(R, cfg)
         for seed in range(1, 400):
