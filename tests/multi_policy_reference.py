@@ -4,6 +4,12 @@ gd_multi_policy_rollout, gpudrive_lab_amd.multi_policy_rollout).  Test infrastru
 test_gpu_multi_policy.py; it never imports the evaluator.
 
   segment_starts(count), owned_list(mask, owner, P)   the owned row list in numpy
+  list_patterns / owner_patterns / many_block_patterns the masks and owners of the list and forward cases, shared by the CPU and
+                                                      the GPU tests
+  owned_list_blocks, blob_of_rows, world_counts_by_wave, summary(first_256=) the same results stated per block of 1024 rows,
+                                                      per position, per wave of 64 slots and per lane of 256 worlds, each with
+                                                      the WRONG rules the many-block, eight-policy, two-wave and 258-world cases
+                                                      are built to see (test_multi_policy.py shows that they do)
   compute_metrics(...), summary(...)                  lines 156-169 in numpy float32, and the per-policy totals
   metrics(control_mask, masks, done, info)            the bookkeeping half of the loop on scripted (done, info) sequences
   run_starts_host / run_metrics_host                  the drivers of the host program (tests/multi_policy_rule_host.cpp)
@@ -50,6 +56,134 @@ def owned_list(mask, owner, n_policies, sentinel):
     return rows, start, count
 
 
+BLOCK, BLOCK_LANES = 1024, 256  # GD_LIVE_ROWS_BLOCK rows to a block; the lanes that add up the blocks' counts
+
+
+def owned_list_blocks(mask, owner, n_policies, sentinel, wrong=None):
+    """owned_list stated by blocks of 1024 rows: per owner the blocks' counts, a block's first position = the counts of the
+    blocks before it, the segment's length = the counts of all blocks, a row's position = start + before + its rank among its
+    block's rows.  The right rule is owned_list's values.  wrong = 'one_trip': a lane adds the block of its own index only, so
+    blocks from 256 on reach neither sum; 'before_le': in a lane's trips after the first (i >= 256) `before` takes the
+    blocks i <= block.  Either is the right rule up to 256 blocks.  A position outside the array is dropped, a position
+    written twice holds the later row."""
+    mask, owner = np.asarray(mask) != 0, np.asarray(owner)
+    n = len(mask)
+    blocks = -(-n // BLOCK)
+    seen = min(blocks, BLOCK_LANES) if wrong == "one_trip" else blocks
+    rows = np.full(n + ALIGN * n_policies, sentinel, np.int32)
+    idx, cnt, before = [], np.zeros(n_policies, np.int32), []
+    for p in range(n_policies):
+        i = np.nonzero(mask & (owner == p))[0]
+        per_block = np.bincount(i // BLOCK, minlength=blocks)
+        per_block_seen = per_block.copy()
+        per_block_seen[seen:] = 0
+        incl = np.cumsum(per_block_seen)
+        idx.append(i)
+        cnt[p] = incl[-1]
+        excl = incl - per_block_seen
+        if wrong == "before_le":
+            excl[BLOCK_LANES:] = incl[BLOCK_LANES:]
+        before.append(excl)
+    start = segment_starts(cnt)
+    for p, i in enumerate(idx):
+        blk = i // BLOCK
+        first = np.searchsorted(blk, blk, side="left")  # the list index of the first row of the row's block
+        at = start[p] + before[p][blk] + (np.arange(len(i)) - first)
+        ok = at < len(rows)
+        rows[at[ok]] = i[ok]
+    for p in range(n_policies):  # the last block's padding, after every block's rows
+        rows[start[p] + cnt[p]:start[p + 1]] = -1
+    return rows, start, cnt
+
+
+def list_patterns(n, P, rng):
+    """The owned-list cases at any n: name -> (mask uint8 [n], owner uint8 [n])."""
+    ones = np.ones(n, np.uint8)
+    out = {"one-owner": (ones, np.full(n, P - 1, np.uint8)),
+           "alternating": (ones, (np.arange(n) % P).astype(np.uint8)),
+           "zero-mask": (np.zeros(n, np.uint8), (np.arange(n) % P).astype(np.uint8)),
+           "random-with-strangers": ((rng.random(n) < 0.7).astype(np.uint8) * rng.choice([1, 2, 255], n).astype(np.uint8),
+                                     rng.integers(0, P + 2, n).astype(np.uint8))}
+    out["random-with-strangers"][1][rng.random(n) < 0.05] = 255
+    if P >= 3:  # an owner with no rows between two with rows
+        gap = (np.arange(n) % 2 * (P - 1)).astype(np.uint8)
+        out["gap"] = (ones, gap)
+    return out
+
+
+def many_block_patterns(n, P, rng):
+    """The two cases of the lists of more than 256 blocks.  late: every set row of owner P - 1 lies in a block >= 256, every
+    set row of another owner in a block < 256 (at 256 blocks owner P - 1 has none).  straddle: owner 0 has set rows in blocks
+    255, 256 and the last block only (those of them that exist); with P > 1 the other owners share every row around them, so
+    that every start behind owner 0's depends on its count."""
+    blocks = -(-n // BLOCK)
+    blk = np.arange(n) // BLOCK
+    dense = (rng.random(n) < 0.5).astype(np.uint8)
+    late_owner = np.where(blk >= BLOCK_LANES, P - 1, rng.integers(0, max(P - 1, 1), n)).astype(np.uint8)
+    late_mask = dense.copy()
+    if blocks > BLOCK_LANES:  # the first and the last row behind block 255 are set: at 257 blocks that is one row
+        late_mask[BLOCK * BLOCK_LANES:][[0, -1]] = 1
+    if P == 1:
+        late_mask[blk < BLOCK_LANES] = 0
+    strad_owner = (rng.integers(1, P, n) if P > 1 else np.zeros(n)).astype(np.uint8)
+    strad_mask = dense.copy() if P > 1 else np.zeros(n, np.uint8)
+    for b in sorted({min(255, blocks - 1), min(256, blocks - 1), blocks - 1}):
+        sel = np.nonzero(blk == b)[0]
+        mine = sel[rng.random(len(sel)) < 0.4]
+        mine = np.union1d(mine, sel[[0, -1]])  # the block's first and last row among them
+        strad_owner[mine], strad_mask[mine] = 0, 1
+    return {"late": (late_mask, late_owner), "straddle": (strad_mask, strad_owner)}
+
+
+OWNER_SIZES = [33, 32, 1, 0, 33, 32, 1, 0]
+
+
+def owner_patterns(n, P, rng):
+    """The forward's cases: name -> (mask bool [n], owner uint8 [n]): segment counts that hit 0, 1, 32 and 33 where n allows."""
+    out = {}
+    sizes = OWNER_SIZES[:P] if P > 1 else [33]
+    for shift in range(P):  # the sizes dealt to the owners in every rotation, in consecutive blocks, the rest dead
+        owner, mask, at = np.full(n, 255, np.uint8), np.zeros(n, bool), 0
+        for p in range(P):
+            k = min(sizes[(p + shift) % P], n - at)
+            owner[at:at + k], mask[at:at + k] = p, True
+            at += k
+        out["blocks%d" % shift] = (mask, owner)
+    out["alternating"] = (np.ones(n, bool), (np.arange(n) % P).astype(np.uint8))
+    out["one-owner"] = (np.ones(n, bool), np.full(n, P - 1, np.uint8))
+    out["random-with-strangers"] = (rng.random(n) < 0.6, rng.integers(0, P + 1, n).astype(np.uint8))
+    out["empty"] = (np.zeros(n, bool), np.zeros(n, np.uint8))
+    return out
+
+
+def blob_of_rows(mask, owner, n_policies, wrong=None):
+    """[n]: the index of the weights the forward on the owned list gives row i (-1: the row is not listed), read off the list as
+    the kernels read it: position q is in segment segments(...)[q] and holds row rows[q].  wrong = 'blob_mod4': a segment's
+    weights come from blob[p % 4]."""
+    n = len(mask)
+    rows, start, count = owned_list(mask, owner, n_policies, -2)
+    seg = segments(start[:-1], count, n + ALIGN * n_policies)
+    blob = np.full(n, -1, np.int32)
+    listed = seg >= 0
+    blob[rows[listed]] = seg[listed] % 4 if wrong == "blob_mod4" else seg[listed]
+    return blob
+
+
+def world_counts_by_wave(owner, goal, collided, off_road, n_policies, wrong=None):
+    """[P, W, 4] int: per policy and world the rows with goal > 0, collided > 0, off_road > 0 and the rows, counted per wave of
+    64 slots and added over the waves.  owner [W, A] (-1: no row).  wrong = 'wave0': only the first wave's counts are added."""
+    owner = np.asarray(owner)
+    W, A = owner.shape
+    waves = 1 if wrong == "wave0" else -(-A // 64)
+    out = np.zeros((n_policies, W, 4), np.int64)
+    for p in range(n_policies):
+        mine = owner == p
+        for k, flag in enumerate((np.asarray(goal) > 0, np.asarray(collided) > 0, np.asarray(off_road) > 0, np.ones_like(mine))):
+            for v in range(waves):
+                out[p, :, k] += (mine & flag)[:, 64 * v:64 * v + 64].sum(1)
+    return out
+
+
 def segments(start, count, limit):
     """segment_of for every position below limit."""
     seg = np.full(limit, -1, np.int32)
@@ -76,10 +210,12 @@ def compute_metrics(accumulators, denominator):
     return out
 
 
-def summary(per_policy):
-    """[P, 4]: per policy the totals of goal_achieved_count, collided_count, off_road_count and n_rows in the fixed order."""
-    return np.array([[REF.ordered_sum(m["goal_achieved_count"]), REF.ordered_sum(m["collided_count"]),
-                      REF.ordered_sum(m["off_road_count"]), REF.ordered_sum(m["n_rows"])] for m in per_policy], f32)
+def summary(per_policy, wrong=None):
+    """[P, 4]: per policy the totals of goal_achieved_count, collided_count, off_road_count and n_rows in the fixed order.
+    wrong = 'first_256': a lane adds the world of its own index only."""
+    cut = 256 if wrong == "first_256" else None
+    return np.array([[REF.ordered_sum(m["goal_achieved_count"][:cut]), REF.ordered_sum(m["collided_count"][:cut]),
+                      REF.ordered_sum(m["off_road_count"][:cut]), REF.ordered_sum(m["n_rows"][:cut])] for m in per_policy], f32)
 
 
 def metrics(control_mask, masks, done, info):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from gpudrive_lab_amd import _capi
+from tests import bc_readout_reference as RR
 from tests.conftest import ROOT
 from tests.test_bc_live_rows import OK4, OK16, ODD, _buffers, _policy_struct, _refused
 from tests.test_bc_rollout import _stub_policy
@@ -145,6 +146,103 @@ def test_the_rule_host_program_under_the_sanitizers():
     labels = np.array([63, 64, -1, np.iinfo(np.int64).max, np.iinfo(np.int64).min, 0], np.int64)
     plain, san = _run_rule(logits, w, h, labels), _run_rule(logits, w, h, labels, sanitize=True)
     assert all(np.array_equal(a, b) for a, b in zip(plain[:3], san[:3])) and plain[3] == san[3] == 4
+
+
+# ---- the launch by chunk, tile and lane, and the wrong rules the larger cases are built to see
+
+WRONG = ("bad_first_64", "prime_tile0", "probe_cap3", "stride_A")
+
+
+def _tokens(B, A, seed=2):
+    return np.random.default_rng(seed).standard_normal((B, A, 64)).astype(np.float32)
+
+
+def _old_cases():
+    """The calls of test_gpu_bc_readout.py before the larger cases: at most 32 rows to a chunk, at most 3 probes to a list."""
+    lab35 = RR.labels_with(35, (0, 3, 31, 32, 34), seed=3)
+    lab_list = RR.labels_with(35, (2, 5), seed=9)
+    return {"2+1, no labels": dict(B=35, A=64, n=(2, 1), labels=None, chunk_rows=32),
+            "3+3, bad labels in both chunks": dict(B=35, A=64, n=(3, 3), labels=lab35, chunk_rows=32),
+            "2+2 at R = 5": dict(B=35, A=64, n=(2, 2), labels=RR.labels_with(35, ()), chunk_rows=32),
+            "1+1 on a list": dict(B=35, A=64, n=(1, 1), labels=lab_list, chunk_rows=8, rows=[0, 2, 3, 9, 17, 33, 34]),
+            "1+1, one label": dict(B=5, A=64, n=(1, 1), labels=7, chunk_rows=4)}
+
+
+def _new_cases():
+    mask, lab, _, _ = RR.list_case()
+    out = {"%d rows in chunks of %d" % k: dict(B=k[0], A=64, n=(2, 2), labels=RR.labels_with(k[0], bad), chunk_rows=k[1])
+           for k, bad in RR.TILE_CASES.items()}
+    out["a list of more than 64 rows"] = dict(B=130, A=64, n=(2, 2), labels=lab, chunk_rows=128, rows=np.nonzero(mask)[0])
+    for A in (64, 128):
+        out["8+8 at A = %d" % A] = dict(B=35, A=A, n=(8, 8), labels=RR.labels_with(35, ()), chunk_rows=32)
+    return out
+
+
+def _read(c, wrong=None):
+    h = _tokens(c["B"], c["A"])
+    return RR.read(h, RR.probe_heads(c["n"][0], 31), RR.probe_heads(c["n"][1], 41), labels=c["labels"], chunk_rows=c["chunk_rows"],
+                   rows=c.get("rows"), wrong=wrong)
+
+
+def _equal(a, b):
+    return a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_the_restated_launch_does_not_depend_on_the_chunk():
+    """What the GPU cases hold the device to: a row's classes are the same whichever tile or chunk it sits in, the count is the
+    number of rows read whose label is no class, and rows that are not listed keep the fill."""
+    for name, c in dict(_old_cases(), **_new_cases()).items():
+        r = _read(c)
+        one = _read(dict(c, chunk_rows=1))
+        assert _equal(r, one), name
+        rows = np.arange(c["B"]) if c.get("rows") is None else np.asarray(c["rows"])
+        lab = None if c["labels"] is None else np.broadcast_to(np.asarray(c["labels"]), (c["B"],))
+        assert r["bad"] == (0 if lab is None else int(((lab[rows] < 0) | (lab[rows] > 63)).sum())), name
+        unlisted = np.setdiff1d(np.arange(c["B"]), rows)
+        for k in ("other_pred", "ego_pred", "ego_pred_prime"):
+            if k in r:
+                assert (r[k][rows] < 64).all() and (r[k][unlisted] == RR.FILL).all(), (name, k)
+    for k, bad in RR.TILE_CASES.items():
+        assert _read(_new_cases()["%d rows in chunks of %d" % k])["bad"] == len(bad)
+    _, _, listed_bad, unlisted_bad = RR.list_case()
+    assert _read(_new_cases()["a list of more than 64 rows"])["bad"] == len(listed_bad) == 2 and len(unlisted_bad) == 1
+
+
+@pytest.mark.parametrize("wrong", WRONG)
+def test_a_rule_that_is_right_on_the_old_cases_is_caught_by_the_case_built_for_it(wrong):
+    """Each wrong rule changes no byte and no count on the calls the suite made before, and differs on the new case named for
+    it.  'stride_A' is the exception the old cases already saw: it is the right rule only with ONE 'other' probe (q = 0), and
+    is asserted to differ on the old calls with two and three; the new case takes the stride to q = 7 and to A = 128."""
+    old, new = _old_cases(), _new_cases()
+    for name, c in old.items():
+        same = _equal(_read(c, wrong), _read(c))
+        assert same == (wrong != "stride_A" or c["n"][0] == 1), (wrong, name)
+    caught = {"bad_first_64": ("130 rows in chunks of 128", "70 rows in chunks of 70", "a list of more than 64 rows"),
+              "prime_tile0": ("130 rows in chunks of 128", "70 rows in chunks of 70", "a list of more than 64 rows"),
+              "probe_cap3": ("8+8 at A = 64", "8+8 at A = 128"), "stride_A": ("8+8 at A = 64", "8+8 at A = 128")}[wrong]
+    for name in caught:
+        right, bad = _read(new[name]), _read(new[name], wrong)
+        assert not _equal(right, bad), (wrong, name)
+        if wrong == "bad_first_64":
+            assert bad["bad"] < right["bad"] and all(np.array_equal(right[k], bad[k]) for k in right if k != "bad")
+        if wrong == "prime_tile0":
+            rows = np.arange(new[name]["B"]) if new[name].get("rows") is None else new[name]["rows"]
+            late = rows[np.arange(len(rows)) % new[name]["chunk_rows"] >= 32]
+            assert (bad["ego_pred_prime"][late] == RR.FILL).all() and np.array_equal(bad["ego_pred"], right["ego_pred"])
+        if wrong == "probe_cap3":
+            for k in ("other_pred", "ego_pred", "ego_pred_prime"):
+                assert np.array_equal(bad[k][:, :4], right[k][:, :4]) and all((bad[k][:, q] != right[k][:, q]).any() for q in range(4, 8))
+        if wrong == "stride_A":
+            A = new[name]["A"]
+            assert np.array_equal(bad["other_pred"][:, 0], right["other_pred"][:, 0])
+            assert all((bad["other_pred"][:, q] != right["other_pred"][:, q]).any() for q in range(1, 8))
+            assert np.array_equal(bad["other_pred"][0, 7, 7:], right["other_pred"][0, 7, :A - 1 - 7]), "column j of probe 7 at 7 + j"
+    # each bad label of the tile cases decides the count under some rule: without the slots from 64 on the count drops by the
+    # labels that sit there, and those only
+    for k, rows in RR.TILE_CASES.items():
+        c = new["%d rows in chunks of %d" % k]
+        in_first_64 = sum(1 for r in rows if r % k[1] < 64)
+        assert _read(c, "bad_first_64")["bad"] == in_first_64 < len(rows)
 
 
 # ---- the refusals of ProbeReadout that need no device

@@ -16,9 +16,10 @@ import torch
 
 from gpudrive_lab_amd import _capi
 from tests import bc_cases as BC
+from tests import bc_readout_reference as RR
 from tests import bc_rollout_reference as REF
 from tests.test_gpu_bc_policy import _no_sync, _policy
-from tests.test_gpu_bc_rollout import IGNORE, REMOVED, _Env, _loop, _same, _sim
+from tests.test_gpu_bc_rollout import IGNORE, REMOVED, SCENES, _Env, _loop, _same, _sim
 from tests.test_gpu_bc_rollout import _policy as _loop_policy
 
 pytestmark = pytest.mark.gpu
@@ -126,6 +127,47 @@ def test_read_equals_the_probes_own_kernels(tap, model):
     _same(bc.read(obs, pm, rm, ro, deterministic=False, u=u, z=z)["actions"], bc(obs, pm, rm, u=u, z=z), "drawn actions")
     others[0].load_state_dict(_head(99))
     _same(bc.read(obs, pm, rm, ro)["other_pred"][:, 0], others[0].predict(obs, pm, rm).to(torch.uint8), "after load_state_dict")
+
+
+@pytest.mark.parametrize("A", [64, 128])
+@pytest.mark.parametrize("tap,model", [("fusion_attn", "early_lp"), ("ro_attn", "late_lp")])
+def test_read_of_eight_pairs_equals_the_probes_own_kernels(tap, model, A):
+    """bc_readout_rule::MAX_PROBES = 8 probes in either list, every head another: `ROArgs.opacked` / `oweight` / `epacked` at
+    3 .. 7 and other_pred's stride q * (A - 1) up to q = 7.  Column q of other_pred and ego_pred is probe q's own `predict`; the
+    prime of pair p is the prime of a read-out built from pair p alone (so `oweight[p]` is the p-th).  At A = 128 a slot has 4
+    partner tiles, the last with 31 rows: its last column, 126, is written (the outputs start as canaries) and equal."""
+    from gpudrive_lab_amd import ProbeReadout
+    B, R = 35, 1
+    bc = _policy(A, R, chunk_rows=32)
+    obs, pm, rm, _, _ = _inp(B, A, R)
+    others = [_probe(bc, model, "other", 110 + q) for q in range(8)]
+    egos = [_probe(bc, model, "ego", 120 + q) for q in range(8)]
+    labels = torch.from_numpy(RR.labels_with(B, ())).cuda()
+    ro = ProbeReadout(bc, tap=tap, layer=None, other=others, ego=egos, labels=labels)
+    out, wholes = {}, {}
+    for k in ro.names:
+        out[k], wholes[k] = _canaried((B,) + ro.row_shape(k))
+    r = bc.read(obs, pm, rm, ro, out=out)
+    assert tuple(r["other_pred"].shape) == (B, 8, A - 1) and tuple(r["ego_pred"].shape) == tuple(r["ego_pred_prime"].shape) == (B, 8)
+    for k in ro.names:
+        assert _guards_hold(wholes[k], out[k].numel()), k
+        assert bool((r[k] < 64).all()), "%s was not written whole" % k
+    seen = []
+    for q in range(8):
+        want = others[q].predict(obs, pm, rm).to(torch.uint8)
+        _same(r["other_pred"][:, q], want, "%s A=%d other[%d]" % (tap, A, q))
+        _same(r["other_pred"][:, q, A - 2], want[:, A - 2], "the last partner column")
+        _same(r["ego_pred"][:, q], egos[q].predict(obs, pm, rm).to(torch.uint8), "%s A=%d ego[%d]" % (tap, A, q))
+        one = bc.read(obs, pm, rm, ProbeReadout(bc, tap=tap, layer=None, other=[others[q]], ego=[egos[q]], labels=labels))
+        _same(r["ego_pred_prime"][:, q], one["ego_pred_prime"][:, 0], "%s A=%d the prime of pair %d alone" % (tap, A, q))
+        seen.append(torch.cat([r["other_pred"][:, q].flatten(), r["ego_pred"][:, q], r["ego_pred_prime"][:, q]]))
+    for q in range(8):
+        for j in range(q):  # distinct heads give distinct columns: a probe read in another's place shows
+            assert not torch.equal(seen[q], seen[j]), (q, j)
+        assert not torch.equal(r["ego_pred_prime"][:, q], r["ego_pred"][:, q]), "pair %d: the intervention changed no class" % q
+    assert A - 2 == {64: 62, 128: 126}[A] and (A - 1 + 31) // 32 == {64: 2, 128: 4}[A] and (A - 1) % 32 == 31
+    assert int(ro.bad_labels.item()) == 0
+    _same(r["actions"], bc(obs, pm, rm, deterministic=True), "actions")
 
 
 def test_read_makes_no_host_synchronisation_and_no_allocation_with_out():
@@ -273,13 +315,82 @@ def test_read_on_a_row_list_writes_listed_rows_only():
     assert int(full_ro.bad_labels.item()) == 2 and int(list_ro.bad_labels.item()) == 1  # only listed rows count
 
 
+# ---- 5b. more than one ego tile to a chunk
+
+def _pairs(bc, labels):
+    from gpudrive_lab_amd import ProbeReadout
+    return ProbeReadout(bc, "ro_attn", 0, other=[_probe(bc, "late_lp", "other", 91), _probe(bc, "early_lp", "other", 92)],
+                        ego=[_probe(bc, "late_lp", "ego", 93), _probe(bc, "early_lp", "ego", 94)], labels=labels)
+
+
+@pytest.mark.parametrize("B,chunk", sorted(RR.TILE_CASES))
+def test_a_rows_classes_do_not_depend_on_its_tile_or_chunk(B, chunk):
+    """chunk_rows = 128 is every caller's default and no stand-alone call ran above 32: B = 130 gives 4 ego tiles, two slots
+    per lane in the bad-label count and a second chunk of 2; B = chunk = 70 gives 3 ego tiles, the last with 6 live lanes, and
+    lanes 0 .. 5 a second slot.  Every output is held bit for bit to the same read through a policy of chunk_rows = 32 -- one
+    ego tile to a chunk, the tiling the float64 test and the probes' own kernels hold.  The labels outside 0 .. 63 sit where
+    RR.TILE_CASES says, all at once and one at a time, and `bad_labels` is the exact number each time."""
+    A, R = 64, 1
+    bc, small = _policy(A, R, chunk_rows=chunk), _policy(A, R, chunk_rows=32)
+    obs, pm, rm, _, _ = _inp(B, A, R)
+    bad_rows = RR.TILE_CASES[(B, chunk)]
+    assert -(-min(B, chunk) // 32) >= 3 and min(B, chunk) > 64 and all(0 <= r < B for r in bad_rows)
+    for rows in (bad_rows,) + tuple((r,) for r in bad_rows) + ((),):
+        lab = torch.from_numpy(RR.labels_with(B, rows)).cuda()
+        ro, ros = _pairs(bc, lab), _pairs(small, lab)
+        r, want = bc.read(obs, pm, rm, ro), small.read(obs, pm, rm, ros)
+        what = "B=%d chunk=%d bad labels at %s" % (B, chunk, list(rows))
+        for k in ("actions",) + ro.names:
+            _same(r[k], want[k], "%s %s" % (what, k))
+        assert int(ro.bad_labels.item()) == len(rows) == int(ros.bad_labels.item()), (what, int(ro.bad_labels.item()))
+        badt = torch.zeros(B, dtype=torch.bool, device="cuda")
+        badt[list(rows)] = True
+        _same(r["ego_pred_prime"][badt], r["ego_pred"][badt], what + ": a bad label is no intervention")
+        late = torch.arange(B, device="cuda") % chunk >= 32  # the rows of the ego tiles from the second on
+        assert bool((r["ego_pred_prime"][late & ~badt] != r["ego_pred"][late & ~badt]).any()), what + ": no class changed in a later tile"
+
+
+def test_a_row_list_of_more_than_64_rows():
+    """The list instantiation at a chunk of 128 positions with more than 64 listed rows: four ego tiles, listed rows in the
+    later ones, and a listed and an unlisted bad label at slots >= 64.  Listed rows equal the full read through chunk_rows = 32;
+    rows that are not listed keep the canary; only listed rows count."""
+    from gpudrive_lab_amd.policy import live_rows
+    B, A, R = 130, 64, 1
+    bc, small = _policy(A, R, chunk_rows=128), _policy(A, R, chunk_rows=32)
+    obs, pm, rm, _, _ = _inp(B, A, R)
+    mask_np, lab, listed_bad, unlisted_bad = RR.list_case(B)
+    mask = torch.from_numpy(mask_np).cuda()
+    assert int(mask.sum()) > 64 and all(mask_np[r] for r in listed_bad) and not any(mask_np[r] for r in unlisted_bad)
+    position = np.cumsum(mask_np) - 1
+    assert position[listed_bad[0]] == 0 and position[listed_bad[1]] >= 64 and unlisted_bad[0] >= 64
+    labels = torch.from_numpy(lab).cuda()
+    full_ro, list_ro = _pairs(small, labels), _pairs(bc, labels)
+    full = small.read(obs, pm, rm, full_ro)
+    out, wholes = {"actions": torch.full_like(full["actions"], 7.0)}, {}
+    for k in list_ro.names:
+        out[k], wholes[k] = _canaried(tuple(full[k].shape))
+    got = _no_sync(lambda: bc.read(obs, pm, rm, list_ro, rows=live_rows(mask), out=out))
+    for k in ("actions",) + list_ro.names:
+        _same(got[k][mask], full[k][mask], "listed rows of %s" % k)
+    assert bool((got["actions"][~mask] == 7.0).all())
+    for k in list_ro.names:
+        assert bool((got[k][~mask] == CANARY).all()), "%s: a row that is not listed was written" % k
+        assert _guards_hold(wholes[k], out[k].numel()), k
+    assert int(full_ro.bad_labels.item()) == 3 and int(list_ro.bad_labels.item()) == 2  # only listed rows count
+
+
 # ---- 6. in the loop
 
 LOOP = {  # name -> (A, R, dynamics, collision behaviour, labels, stochastic too)
     "128-5-removed": (128, 5, "delta_local", REMOVED, "rows", False),
     "128-5-ignore": (128, 5, "delta_local", IGNORE, 10, False),
     "64-1-removed": (64, 1, "delta_local", REMOVED, "rows", True),
+    "64-1-removed-67-rows": (64, 1, "delta_local", REMOVED, "rows", False),
 }
+# The scenes of a case (the others: SCENES, 26 rows).  The three scenes give 2, 3 and 8 rows at A = 64, so N > 64 needs nine
+# worlds, and nine are the fewest: eight times the largest scene and the second largest once, 67 rows -- three ego tiles to the
+# loop's one chunk, the last with 3 live lanes, and three lanes with a second slot in the bad-label count.
+LOOP_SCENES = {"64-1-removed-67-rows": [SCENES[2]] * 8 + [SCENES[1]]}
 NEW = ("ego_attn_score", "other_pred", "ego_pred", "ego_pred_prime")
 _CACHE = {}
 
@@ -322,7 +433,8 @@ def _loop_case(name):
         from gpudrive_lab_amd import ClosedLoopBC, ProbeReadout
         A, R, model, cb, labels, stochastic = LOOP[name]
         with _Env("linear"):
-            rsim, tsim = _sim(A, model, cb, "linear"), _sim(A, model, cb, "linear")
+            scenes = LOOP_SCENES.get(name, SCENES)
+            rsim, tsim = _sim(A, model, cb, "linear", scenes=scenes), _sim(A, model, cb, "linear", scenes=scenes)
             try:
                 pol = _loop_policy(A, R)
                 others = [_probe(pol, "late_lp", "other", 81), _probe(pol, "early_lp", "other", 82)]
@@ -334,7 +446,7 @@ def _loop_case(name):
                     lab = np.random.default_rng(N).integers(0, 64, N)
                     lab[0], lab[N - 1] = 64, -1
                     labels = torch.from_numpy(lab).cuda()
-                c = dict(N=N, A=A, loop_mask=loop.mask.clone(), row_slot=loop.row_slot.clone())
+                c = dict(N=N, A=A, loop_mask=loop.mask.clone(), row_slot=loop.row_slot.clone(), chunk_rows=pol.chunk_rows)
                 c["plain"] = loop.run(record=True)
                 c["plain_compact"] = loop.run(record=True, compact=True)
                 ro, roc = make(labels), make(labels)
@@ -380,6 +492,17 @@ def test_run_with_the_read_outs_equals_the_restated_loop(name):
     print("BC READOUT LOOP %s: rows %d iterations %d live row-steps %d dead row-steps %d bad %s"
           % (name, N, iters, int((~dead[:iters]).sum()), int(dead[:iters].sum()), c["bad"]))
     assert bool(dead[:iters].any()) and bool((~dead[:iters]).any()), "the case has no dead or no live row-step"
+    # how many rows a chunk of the loop's forward holds: run() reads all N rows in chunks of chunk_rows (dead rows dropped
+    # inside the launch), run(compact=True) the live rows of the step
+    live_most = int((~dead[:iters]).sum(1).max())
+    print("BC READOUT LOOP %s: N %d, most live rows in a step %d, chunk_rows %d" % (name, N, live_most, c["chunk_rows"]))
+    assert c["chunk_rows"] == 128 and live_most <= N <= c["chunk_rows"], "one chunk per step: the chunk holds N rows"
+    if name in LOOP_SCENES:
+        assert N == 67 and live_most > 64, "more than two ego tiles, and a second slot per lane in the bad-label count"
+        late = (~dead[:iters])[:, 32:].any(1)
+        assert bool(late.any()) and bool((ep.ego_pred_prime[:iters][late][:, 32:] != 255).any()), "no live row in a later ego tile"
+    else:
+        assert N == 26, "26 rows: one ego tile per chunk (the case of 67 rows has three)"
     for k in c["shapes"]:
         assert tuple(getattr(ep, k).shape) == (T, N) + c["shapes"][k]
         _same(getattr(ep, k), want[k], "%s %s" % (name, k))

@@ -14,33 +14,53 @@ from tests import policy_cases as PC
 from tests import ppo_rollout_reference as REF
 from tests.test_gpu_live_rows import CANARY, F_CANARY, _bits, _Carver
 from tests.test_gpu_policy import _no_sync
-from tests.test_gpu_ppo_rollout import (MATRIX, PER_ROW, PER_STEP, REMOVED, WORLD, T, _Carved, _Env, _same, _sim, _table)
+from tests.test_gpu_ppo_rollout import (BIG_W, MATRIX, PER_ROW, PER_STEP, REMOVED, SCENES, WORLD, T, _Carved, _Env, _same, _sim, _table)
+from tests.test_gpu_ppo_rollout import big_twins  # noqa: F401 (the module-scoped fixture: twin simulators of 258 worlds)
 
 pytestmark = pytest.mark.gpu
 
 SEEDS = (11, 12, 13)  # the weights of policies "a", "b", "c": tests/policy_cases.state_dict(seed, ego_width, n_actions)
 NAMES = ("a", "b", "c")
+SEEDS8 = SEEDS + (14, 15, 16, 17, 18)  # GD_POLICY_SET_MAX policies: the first three are a, b, c
+NAMES8 = NAMES + ("d", "e", "f", "g", "h")
 
 
 # ---- gd_owned_rows against the numpy restatement
-def _patterns(n, P, rng):
-    """name -> (mask uint8 [n], owner uint8 [n])."""
-    ones = np.ones(n, np.uint8)
-    out = {"one-owner": (ones, np.full(n, P - 1, np.uint8)),
-           "alternating": (ones, (np.arange(n) % P).astype(np.uint8)),
-           "zero-mask": (np.zeros(n, np.uint8), (np.arange(n) % P).astype(np.uint8)),
-           "random-with-strangers": ((rng.random(n) < 0.7).astype(np.uint8) * rng.choice([1, 2, 255], n).astype(np.uint8),
-                                     rng.integers(0, P + 2, n).astype(np.uint8))}
-    out["random-with-strangers"][1][rng.random(n) < 0.05] = 255
-    if P >= 3:  # an owner with no rows between two with rows
-        gap = (np.arange(n) % 2 * (P - 1)).astype(np.uint8)
-        out["gap"] = (ones, gap)
-    return out
+_patterns = MREF.list_patterns  # name -> (mask uint8 [n], owner uint8 [n])
+
+
+def _check_owned_rows(what, mask, owner, n, P, lr, carver, dev):
+    """One list against the restatement: counts, starts, every position, the padding, the canary past start[P], the guards,
+    two calls equal, and at P = 1 gd_live_rows' list."""
+    from gpudrive_lab_amd.policy import LiveRows, live_rows, owned_rows
+    rows, start, count = MREF.owned_list(mask, owner, P, CANARY)
+    carver.refill()
+    m, o = torch.from_numpy(mask).cuda(), torch.from_numpy(owner).cuda()
+    assert owned_rows(m, o, out=lr) is lr
+    carver.check(what)
+    assert lr.count.cpu().tolist() == count.tolist(), (what, lr.count.tolist(), count.tolist())
+    got_start = lr.start.cpu().numpy()
+    assert got_start.tolist() == start.tolist() and (got_start % 32 == 0).all(), (what, got_start, start)
+    got = lr.rows.cpu().numpy()
+    assert np.array_equal(got, rows), "%s: first difference at position %d" % (what, int(np.nonzero(got != rows)[0][0]))
+    for p in range(P):
+        seg = got[start[p]:start[p] + count[p]]
+        assert (np.diff(seg) > 0).all() and (got[start[p] + count[p]:start[p + 1]] == -1).all(), what
+    assert (got[start[P]:] == CANARY).all(), what + ": positions at or past start[P] were written"
+    first = [t.clone() for t in (lr.rows, lr.start, lr.count, lr.scratch)]
+    owned_rows(m, o, out=lr)
+    for a, b in zip(first, (lr.rows, lr.start, lr.count, lr.scratch)):
+        assert torch.equal(a, b), what + ": two calls differ"
+    if P == 1:
+        live = live_rows(m * (o == 0), out=LiveRows(n, dev))  # (a stranger's row is listed nowhere)
+        k = int(live.count)
+        assert k == int(count[0]) and torch.equal(live.rows[:k], lr.rows[:k]), what + ": not gd_live_rows' list"
+    return count
 
 
 @pytest.mark.parametrize("P", [1, 2, 3, 8])
 def test_owned_rows_equals_the_restatement(P):
-    from gpudrive_lab_amd.policy import LiveRows, OwnedRows, live_rows, owned_rows
+    from gpudrive_lab_amd.policy import OwnedRows, owned_rows
     rng = np.random.default_rng(100 + P)
     dev = torch.device("cuda", torch.cuda.current_device())
     for n in (1, 31, 32, 33, 1023, 1024, 1025, 2100):
@@ -49,29 +69,7 @@ def test_owned_rows_equals_the_restatement(P):
         assert lr.rows.numel() == n + 32 * P and lr.scratch.numel() == P * -(-n // 1024) and lr.start.numel() == P + 1
         assert OwnedRows.nbytes(n, P) == 4 * sum(t.numel() for t in (lr.rows, lr.start, lr.count, lr.scratch))
         for name, (mask, owner) in _patterns(n, P, rng).items():
-            what = "n=%d P=%d %s" % (n, P, name)
-            rows, start, count = MREF.owned_list(mask, owner, P, CANARY)
-            carver.refill()
-            m, o = torch.from_numpy(mask).cuda(), torch.from_numpy(owner).cuda()
-            assert owned_rows(m, o, out=lr) is lr
-            carver.check(what)
-            assert lr.count.cpu().tolist() == count.tolist(), (what, lr.count.tolist(), count.tolist())
-            got_start = lr.start.cpu().numpy()
-            assert got_start.tolist() == start.tolist() and (got_start % 32 == 0).all(), (what, got_start, start)
-            got = lr.rows.cpu().numpy()
-            assert np.array_equal(got, rows), "%s: first difference at position %d" % (what, int(np.nonzero(got != rows)[0][0]))
-            for p in range(P):
-                seg = got[start[p]:start[p] + count[p]]
-                assert (np.diff(seg) > 0).all() and (got[start[p] + count[p]:start[p + 1]] == -1).all(), what
-            assert (got[start[P]:] == CANARY).all(), what + ": positions at or past start[P] were written"
-            first = [t.clone() for t in (lr.rows, lr.start, lr.count, lr.scratch)]
-            owned_rows(m, o, out=lr)
-            for a, b in zip(first, (lr.rows, lr.start, lr.count, lr.scratch)):
-                assert torch.equal(a, b), what + ": two calls differ"
-            if P == 1:
-                live = live_rows(m * (o == 0), out=LiveRows(n, dev))  # (a stranger's row is listed nowhere)
-                k = int(live.count)
-                assert k == int(count[0]) and torch.equal(live.rows[:k], lr.rows[:k]), what + ": not gd_live_rows' list"
+            _check_owned_rows("n=%d P=%d %s" % (n, P, name), mask, owner, n, P, lr, carver, dev)
         if n == 1025:
             m, o = (torch.from_numpy(t).cuda() for t in _patterns(n, P, rng)["alternating"])
             fresh = owned_rows(m.view(torch.bool), o, P)  # without out=: a fresh list, the same values
@@ -83,23 +81,42 @@ def test_owned_rows_equals_the_restatement(P):
                 owned_rows(m, o, out=OwnedRows(n - 1, P, dev))
 
 
+MANY_BLOCKS = (262144, 262145, 1 << 20)  # 256 blocks: one term per lane; 257: lane 0 alone adds a second; 1024: four per lane
+
+
+@pytest.mark.parametrize("n", MANY_BLOCKS)
+@pytest.mark.parametrize("P", [1, 8])
+def test_owned_rows_at_more_blocks_than_lanes(P, n):
+    """k_owned_write adds up the blocks' counts with `for (i = tid; i < blocks; i += 256)`: above 256 blocks a lane takes a
+    second trip, with the split `i < block` inside it and the stride p * blocks at P = 8.  The patterns of the small sizes, and
+    `late` (owner P - 1 only in blocks >= 256: a total without the second trip gives it no rows and moves every later start)
+    and `straddle` (owner 0 in blocks 255, 256 and the last only: `before` at block 256 and at blocks - 1); that they are what
+    they are named for is asserted here on the inputs.  tests/test_multi_policy.py shows that a restatement with either fault
+    differs on them."""
+    from gpudrive_lab_amd.policy import OwnedRows
+    rng = np.random.default_rng(1000 * P + n % 1000)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    blocks = -(-n // 1024)
+    assert blocks == {262144: 256, 262145: 257, 1 << 20: 1024}[n]
+    carver = _Carver()
+    lr = OwnedRows(n, P, dev, new=carver.new)
+    assert lr.scratch.numel() == P * blocks
+    cases = dict(_patterns(n, P, rng), **MREF.many_block_patterns(n, P, rng))
+    blk = np.arange(n) // 1024
+    for name, (mask, owner) in cases.items():
+        count = _check_owned_rows("n=%d P=%d %s" % (n, P, name), mask, owner, n, P, lr, carver, dev)
+        if name == "late":
+            mine = (mask != 0) & (owner == P - 1)
+            assert (blk[mine] >= 256).all() and int(count[P - 1]) == int(mine.sum()) and (count[P - 1] > 0) == (blocks > 256)
+            assert P == 1 or ((blk[(mask != 0) & (owner < P - 1)] < 256).all() and (count[:P - 1] > 0).all())
+        if name == "straddle":
+            at = set(blk[(mask != 0) & (owner == 0)].tolist())
+            assert at == {b for b in (255, 256, blocks - 1) if b < blocks}, at
+            assert P == 1 or (count[1:] > 0).all()
+
+
 # ---- the forward on an owned list against every owner's full forward
-def _owner_patterns(n, P, rng):
-    """name -> (mask bool [n], owner uint8 [n]): segment counts that hit 0, 1, 32 and 33 where n allows."""
-    out = {}
-    sizes = [33, 32, 1, 0, 33, 32, 1, 0][:P] if P > 1 else [33]
-    for shift in range(P):  # the sizes dealt to the owners in every rotation, in consecutive blocks, the rest dead
-        owner, mask, at = np.full(n, 255, np.uint8), np.zeros(n, bool), 0
-        for p in range(P):
-            k = min(sizes[(p + shift) % P], n - at)
-            owner[at:at + k], mask[at:at + k] = p, True
-            at += k
-        out["blocks%d" % shift] = (mask, owner)
-    out["alternating"] = (np.ones(n, bool), (np.arange(n) % P).astype(np.uint8))
-    out["one-owner"] = (np.ones(n, bool), np.full(n, P - 1, np.uint8))
-    out["random-with-strangers"] = (rng.random(n) < 0.6, rng.integers(0, P + 1, n).astype(np.uint8))
-    out["empty"] = (np.zeros(n, bool), np.zeros(n, np.uint8))
-    return out
+_owner_patterns = MREF.owner_patterns  # name -> (mask bool [n], owner uint8 [n])
 
 
 def _canaries(n, na):
@@ -122,31 +139,47 @@ def _check_owned(what, mask, owner, P, got, got_logits, full):
         assert bool((g[~listed] == F_CANARY).all()), "%s: %s of a row that is not listed was written" % (what, name)
 
 
+N_EIGHT = 140  # the smallest n that holds the eight segment sizes 33, 32, 1, 0, 33, 32, 1, 0 (132 rows) and some dead rows
+
+
 @pytest.mark.parametrize("a,ew,na,n", [(64, 6, 91, 1), (64, 6, 91, 33), (64, 6, 91, 70), (64, 6, 91, 1100), (128, 9, 91, 70),
-                                       (128, 9, 91, 1100), (64, 6, 5, 70)])
+                                       (128, 9, 91, 1100), (64, 6, 5, 70), (64, 6, 91, N_EIGHT), (128, 9, 91, N_EIGHT)])
 def test_forward_on_an_owned_list_equals_each_owners_full_forward(a, ew, na, n):
+    """n = N_EIGHT runs P = 5 and P = 8 (the other sizes 1, 2 and 3): `OwnedList.blob[3 .. 7]` choose weights, an empty segment
+    lies between two full ones behind position 96, and segments of index >= 3 have a 32-row and a 1-row tail workgroup, in
+    every rotation of the sizes over the owners."""
     from gpudrive_lab_amd.policy import DevicePolicy, LiveRows, OwnedRows, PolicySet, live_rows, owned_rows
     rng = np.random.default_rng(7 * n + a)
     obs = torch.from_numpy(PC.observations(20 + n + a, n, a, ew)).cuda()
     u = torch.from_numpy(PC.uniforms(n + 3, n)).cuda()
-    pols = [DevicePolicy.from_state_dict(PC.state_dict(s, ew, na), max_agents=a, ego_width=ew) for s in SEEDS]
+    eight = n == N_EIGHT
+    assert not eight or n >= sum(MREF.OWNER_SIZES) > n - 32
+    pols = [DevicePolicy.from_state_dict(PC.state_dict(s, ew, na), max_agents=a, ego_width=ew) for s in (SEEDS8 if eight else SEEDS)]
     full = {}
     for det in (False, True):
         full[det] = []
         for pol in pols:
             logits = torch.empty((n, na), device="cuda")
             full[det].append((pol(obs, None if det else u, deterministic=det, logits_out=logits), logits))
-    assert not torch.equal(full[True][0][1], full[True][1][1]) and not torch.equal(full[True][1][1], full[True][2][1]), \
-        "the policies give the same logits: a mix-up of weights would not show"
+    for i in range(len(pols)):
+        for j in range(i):  # on every row, so that a row given another policy's weights shows whichever row it is
+            assert bool((_bits(full[True][i][1]) != _bits(full[True][j][1])).any(1).all()), \
+                "policies %d and %d give a row the same logits: a mix-up of weights would not show" % (j, i)
     out, logits_out = _canaries(n, na)
     dev = obs.device
-    for P in (1, 2, 3):
+    for P in ((5, 8) if eight else (1, 2, 3)):
         ps = PolicySet(pols[:P])
         lr = OwnedRows(n, P, dev)
         for name, (mask, owner) in _owner_patterns(n, P, rng).items():
             what = "A=%d ego=%d NA=%d N=%d P=%d %s" % (a, ew, na, n, P, name)
             m, o = torch.from_numpy(mask).cuda(), torch.from_numpy(owner).cuda()
             owned_rows(m, o, out=lr)
+            if eight and P == 8 and name.startswith("blocks"):  # what the case is for, on the device's own list
+                shift, count, start = int(name[6:]), lr.count.tolist(), lr.start.tolist()
+                assert count == [MREF.OWNER_SIZES[(p + shift) % 8] for p in range(8)], (what, count)
+                assert any(count[p] == 0 and start[p] > 96 and count[p - 1] > 0 and count[p + 1] > 0 for p in range(3, 7)), \
+                    (what, "no empty segment of index >= 3 between two full ones behind position 96")
+                assert any(count[p] == 32 for p in range(3, 8)) and any(count[p] == 33 for p in range(3, 8))
             for det in (False, True):
                 for t in out + (logits_out,):
                     _bits(t).fill_(F_CANARY)
@@ -193,9 +226,26 @@ ASSIGNMENTS = ("parity", "world", "single")
 # a collision and an excursion off the road, and row 6 of the REMOVED case collides and is removed, which empties c's segment
 # (test_the_cases_meet_the_conditions asserts both on the restated loop).
 SINGLE_ROW = {"64-ignore-linear": 23, "128-removed-linear": 6}
+# "mod8": eight policies, owner = slot % 8 among the controlled slots.  It runs on 128-removed-linear with EVERY object of the
+# scenes controlled (ALL_OBJECTS): as the other cases build that simulator, the controlled slots of the three scenes are
+# 0 .. 1, 0 .. 2 and eight of 0 .. 23 -- none in the second wave of k_mp_world's 128 lanes, and none with slot % 8 in (3, 5) --
+# so no seed and no assignment gives a policy rows in both halves.  With every object controlled the last scene has controlled
+# slots on either side of 64 (test_the_cases_meet_the_conditions asserts it on the restated loop's control_mask).
+ALL_OBJECTS = dict(isStaticAgentControlled=1, initOnlyValidAgentsAtFirstStep=0, IgnoreNonVehicles=0)
+MOD8 = ("128-removed-linear", "mod8")
 CASES = [("64-ignore-linear", "parity"), ("64-ignore-linear", "single"), ("128-removed-linear", "world"),
-         ("128-removed-linear", "single"), ("64-removed-linear-init11", "parity"), ("64-removed-linear-init11", "world")]
-DET = {("64-ignore-linear", "parity"), ("128-removed-linear", "world"), ("128-removed-linear", "single")}
+         ("128-removed-linear", "single"), ("64-removed-linear-init11", "parity"), ("64-removed-linear-init11", "world"), MOD8]
+DET = {("64-ignore-linear", "parity"), ("128-removed-linear", "world"), ("128-removed-linear", "single"), MOD8}
+N_POLICIES = {"parity": 2, "world": 2, "single": 3, "mod8": 8}
+
+
+def _sim_all_objects(A, cb, roads, scenes=SCENES):
+    """tests/test_gpu_ppo_rollout._sim with every object of the scenes controlled."""
+    from tests import parity
+    from tests.test_gpu_ppo_rollout import BASE, GOAL, ROADS
+    knn_order, algo, _ = ROADS[roads]
+    return parity.make_gpu_sim(scenes, max_agents=A, knn_order=knn_order, collisionBehaviour=cb, roadObservationAlgorithm=algo,
+                               distanceToGoalThreshold=GOAL, **dict(BASE, **ALL_OBJECTS))
 
 
 def _policies(A, seeds=SEEDS):
@@ -208,6 +258,8 @@ def _assign(case, assignment, ctrl, pols):
     W, A = ctrl.shape
     slot = torch.arange(A, device=ctrl.device).expand(W, A)
     world = torch.arange(W, device=ctrl.device).unsqueeze(1).expand(W, A)
+    if assignment == "mod8":
+        return {name: (pol, ctrl & (slot % 8 == p)) for p, (name, pol) in enumerate(zip(NAMES8, pols))}
     if assignment == "parity":
         masks = [ctrl & (slot % 2 == 0), ctrl & (slot % 2 == 1)]
     elif assignment == "world":
@@ -270,10 +322,11 @@ def _case(case, assignment):
         from gpudrive_lab_amd import ClosedLoopMultiPPO
         A, cb, roads, init = MATRIX[case]
         with _Env(roads):
-            rsim, tsim = _sim(A, cb, roads), _sim(A, cb, roads)
+            rsim, tsim = (_sim_all_objects(A, cb, roads), _sim_all_objects(A, cb, roads)) if key == MOD8 else \
+                (_sim(A, cb, roads), _sim(A, cb, roads))
             try:
                 ctrl = rsim.controlled_state_tensor().to_torch().squeeze(-1) == 1
-                pols = _assign(case, assignment, ctrl, _policies(A))
+                pols = _assign(case, assignment, ctrl, _policies(A, SEEDS8 if key == MOD8 else SEEDS))
                 ev = ClosedLoopMultiPPO(rsim, pols, init_steps=init)
                 ep = ev.run(generator=torch.Generator(device="cuda").manual_seed(5), record=True)
                 r = MREF.closed_loop(tsim, pols, _table(), u=ep.u, init_steps=init)
@@ -296,8 +349,8 @@ def _case(case, assignment):
 def test_run_equals_the_restated_loop(case, assignment):
     c = _case(case, assignment)
     ep, N = c["ep"], c["N"]
-    P = 3 if assignment == "single" else 2
-    assert ep.names == NAMES[:P] and tuple(ep.u.shape) == (T, N) and tuple(ep.policy_n_rows.shape) == (P, 6)
+    P = N_POLICIES[assignment]
+    assert ep.names == NAMES8[:P] and tuple(ep.u.shape) == (T, N) and tuple(ep.policy_n_rows.shape) == (P, 6)
     assert sorted(set(c["owner"].tolist())) == list(range(P))
     _compare(ep, c["r"], "%s %s" % (case, assignment))
     if "det" in c:
@@ -339,6 +392,30 @@ def test_the_cases_meet_the_conditions():
     world = rs[("128-removed-linear", "world")]
     for name in ("a", "b"):
         assert bool((world["policies"][name]["n_rows"] == 0).any()), "by world: every policy has worlds without rows"
+    # eight policies on 128 slots: every policy has a row; some policy has rows in both waves of k_mp_world in one world; a
+    # policy whose index only this case reaches has something to count
+    r = rs[MOD8]
+    ctrl = r["control_mask"].cpu().numpy()
+    slot = np.arange(ctrl.shape[1])
+    assert ctrl.shape[1] == 128 and all(float(r["policies"][name]["n_rows"].sum()) >= 1 for name in NAMES8)
+    both = [(w, p) for w in range(ctrl.shape[0]) for p in range(8)
+            if (ctrl[w] & (slot % 8 == p) & (slot < 64)).any() and (ctrl[w] & (slot % 8 == p) & (slot >= 64)).any()]
+    counted = {name: [int(r["policies"][name][k].sum()) for k in ("goal_achieved_count", "collided_count", "off_road_count")]
+               for name in NAMES8}
+    print("MULTI mod8: (world, policy) with rows in both halves of the slots %s; goal / collided / off-road counts %s" % (both, counted))
+    assert both, "no world in which a policy has rows on either side of slot 64"
+    assert any(sum(counted[name]) > 0 for name in NAMES8[3:]), "no policy of index >= 3 has a non-zero count"
+    # and the second wave's rows decide a count: some policy's count is another when only slots < 64 are counted
+    acc = {k: np.zeros(ctrl.shape, np.float32) for k in ("goal_achieved", "collided", "off_road")}
+    for k in acc:
+        acc[k][ctrl] = r[k].cpu().numpy()
+    owner = np.where(ctrl, slot % 8, -1)
+    right, wave0 = (MREF.world_counts_by_wave(owner, acc["goal_achieved"], acc["collided"], acc["off_road"], 8, wrong=wrong)
+                    for wrong in (None, "wave0"))
+    for p, name in enumerate(NAMES8):
+        for j, k in enumerate(("goal_achieved_count", "collided_count", "off_road_count", "n_rows")):
+            assert np.array_equal(right[p, :, j], r["policies"][name][k].cpu().numpy()), (name, k)
+    assert (right != wave0).any(), "the second wave counts nothing"
 
 
 def _seed(s):
@@ -416,7 +493,6 @@ def test_a_mask_slot_that_is_not_controlled_changes_the_denominator_only():
 def test_no_host_synchronisation_canaries_nbytes_and_evaluate():
     from gpudrive_lab_amd import ClosedLoopMultiPPO
     from gpudrive_lab_amd.ppo_rollout import EVALUATE_COLUMNS
-    from tests.test_gpu_ppo_rollout import SCENES
     A = 64
     batches = [[SCENES[0], SCENES[1], SCENES[2]], [SCENES[2], SCENES[0], SCENES[1]]]
     sim = _sim(A, REMOVED, scenes=batches[0])
@@ -458,3 +534,39 @@ def test_no_host_synchronisation_canaries_nbytes_and_evaluate():
                 assert same(res["policies"][name][k], torch.cat([getattr(e, "policy_" + k)[p] for e in eps]).cpu().numpy()), (name, k)
     finally:
         sim.close()
+
+
+# ---- past one world per lane of the per-policy summary
+def test_run_equals_the_restated_loop_on_258_worlds(big_twins):  # noqa: F811
+    """W = 258: lane l of k_mp_summary's 256 adds worlds l and l + 256 of every policy, so lanes 0 and 1 add a second term.
+    Three policies, owner = (world + slot) % 3, so that every policy has rows in worlds 256 and 257 and something to count
+    there (asserted on the restated loop's outputs): a summary that stops at 256 worlds differs for every policy.  Every
+    summed field is a count: integers whose total stays far below 2^24, so the float32 sums are exact in ANY order (asserted)
+    -- what this case holds the summary to is that every world is added exactly once per policy, not the order."""
+    from gpudrive_lab_amd import ClosedLoopMultiPPO
+    rsim, tsim = big_twins
+    A, W, P = 64, BIG_W, 3
+    assert W > 256 and W % 256 == 2
+    ctrl = rsim.controlled_state_tensor().to_torch().squeeze(-1) == 1
+    slot = torch.arange(A, device=ctrl.device).expand(W, A)
+    world = torch.arange(W, device=ctrl.device).unsqueeze(1).expand(W, A)
+    pols = {name: (pol, ctrl & ((world + slot) % P == p)) for p, (name, pol) in enumerate(zip(NAMES, _policies(A)))}
+    ev = ClosedLoopMultiPPO(rsim, pols)
+    ep = ev.run(generator=_seed(5), record=True)
+    r = MREF.closed_loop(tsim, pols, _table(), u=ep.u)
+    assert ev.num_agents == int(r["control_mask"].sum()) > 256 and tuple(ep.policy_n_rows.shape) == (P, W)
+    _compare(ep, r, "258 worlds")
+    flags = ("goal_achieved_count", "collided_count", "off_road_count")
+    per = [{k: r["policies"][name][k].cpu().numpy() for k in flags + ("n_rows",)} for name in NAMES]
+    print("MULTI 258 worlds: rows %d iterations %d policy_summary %s; worlds 256, 257: %s" % (
+        ev.num_agents, r["iterations"], r["policy_summary"].tolist(), [{k: v[256:].tolist() for k, v in m.items()} for m in per]))
+    for name, m in zip(NAMES, per):
+        assert (m["n_rows"][256:] > 0).all(), (name, "no rows in world 256 or 257")
+        assert sum(float(m[k][256:].sum()) for k in flags) > 0, (name, "nothing to count in worlds 256 and 257")
+        for k in flags + ("n_rows",):
+            v = m[k].astype(np.float64)
+            assert (v == np.round(v)).all() and 0 <= v.sum() < 2 ** 24, (name, k, "not exactly representable")
+            assert float(REF.ordered_sum(m[k])) == v.sum(), (name, k)
+    cut = MREF.summary(per, wrong="first_256")
+    assert (cut[:, :3] != r["policy_summary"][:, :3]).any(1).all() and (cut[:, 3] != r["policy_summary"][:, 3]).all(), \
+        "a summary of the first 256 worlds is the same for some policy"

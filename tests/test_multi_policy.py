@@ -442,3 +442,165 @@ def test_restated_metrics_break_and_prefix():
     p = MREF.metrics(control, _split(control), done[:7], info[:7])
     full = MREF.metrics(control, _split(control), done, info)
     assert p["iterations"] == 7 and np.array_equal(p["list_count"][:7], full["list_count"][:7])
+
+
+# ---- the restatements by block, position, wave and lane, and the wrong rules the new GPU cases are built to see
+SMALL = (1, 31, 32, 33, 1023, 1024, 1025, 2100)            # the sizes of test_owned_rows_equals_the_restatement
+MANY_BLOCKS = (262144, 262145, 1 << 20)                     # and of test_owned_rows_at_more_blocks_than_lanes
+BLOCK_RULES = (None, "one_trip", "before_le")
+
+
+def _lists_equal(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("P", [1, 2, 3, 8])
+def test_the_list_by_blocks_is_the_list_on_the_small_sizes_under_every_rule(P):
+    """The restatement by blocks of 1024 rows equals `owned_list` on every existing size and pattern; so do the rule whose sums
+    stop at 256 blocks and the rule whose split is `i <= block` from the second trip on (no existing size has more than 3
+    blocks)."""
+    rng = np.random.default_rng(100 + P)
+    for n in SMALL:
+        for name, (mask, owner) in MREF.list_patterns(n, P, rng).items():
+            want = MREF.owned_list(mask, owner, P, -7)
+            for wrong in BLOCK_RULES:
+                assert _lists_equal(MREF.owned_list_blocks(mask, owner, P, -7, wrong=wrong), want), (n, P, name, wrong)
+
+
+@pytest.mark.parametrize("P", [1, 8])
+@pytest.mark.parametrize("n", MANY_BLOCKS)
+def test_the_many_block_cases_see_the_rules_they_are_built_for(P, n):
+    """At more than 256 blocks `late` and `straddle` differ under 'one_trip' (at exactly 256 blocks that rule is the right one,
+    and is asserted equal), and so under 'before_le'; `late` under 'one_trip' loses owner P - 1's count and, at
+    P = 8, nothing else, which is what it is built to isolate.  The restatement stays fast at 2^20 rows (it is `owned_list`'s
+    cost, a few hundred milliseconds for all the patterns)."""
+    import time
+    rng = np.random.default_rng(1000 * P + n % 1000)
+    blocks = -(-n // 1024)
+    cases = dict(MREF.list_patterns(n, P, rng), **MREF.many_block_patterns(n, P, rng))
+    t0 = time.perf_counter()
+    want = {name: MREF.owned_list(mask, owner, P, -7) for name, (mask, owner) in cases.items()}
+    spent = time.perf_counter() - t0
+    print("MULTI owned_list n=%d P=%d: %d patterns in %.3f s" % (n, P, len(cases), spent))
+    for name, (mask, owner) in cases.items():
+        assert _lists_equal(MREF.owned_list_blocks(mask, owner, P, -7), want[name]), (n, P, name)
+    for name in ("late", "straddle"):
+        mask, owner = cases[name]
+        rows, start, count = want[name]
+        got = MREF.owned_list_blocks(mask, owner, P, -7, wrong="one_trip")
+        assert _lists_equal(got, want[name]) == (blocks <= 256), (n, P, name)
+        le = MREF.owned_list_blocks(mask, owner, P, -7, wrong="before_le")
+        assert _lists_equal(le, want[name]) == (blocks <= 256), (n, P, name)
+        assert _lists_equal(le[1:], want[name][1:]), "the counts and starts are the right ones: only positions move"
+        if blocks > 256 and name == "late":
+            assert got[2][P - 1] == 0 < count[P - 1] and got[2][:P - 1].tolist() == count[:P - 1].tolist()
+        if blocks > 256 and name == "straddle":
+            assert 0 < got[2][0] < count[0], "owner 0 keeps block 255's rows and loses the others"
+
+
+def test_the_restatement_of_the_list_is_vectorised():
+    """2^20 rows, 8 owners: well under a second, so the GPU case's time is the device's."""
+    import time
+    rng = np.random.default_rng(3)
+    n = 1 << 20
+    mask, owner = (rng.random(n) < 0.7).astype(np.uint8), rng.integers(0, 10, n).astype(np.uint8)
+    best = 1e9
+    for _ in range(2):
+        t0 = time.perf_counter()
+        MREF.owned_list(mask, owner, 8, -7)
+        best = min(best, time.perf_counter() - t0)
+    print("MULTI owned_list 2^20 rows, P = 8: %.3f s" % best)
+    assert best < 1.0
+
+
+N_EIGHT = 140
+
+
+def test_weights_from_blob_p_mod_4_show_at_eight_policies_only():
+    """Which weights the forward on an owned list gives a row, read off the list position by position: the owner's.  A rule
+    that takes blob[p % 4] is the same rule for P <= 4 -- every existing case -- and at P = 8 gives every listed row of owners
+    4 .. 7 other weights, in every pattern of the new case that lists such a row."""
+    for n, Ps in ((1, (1, 2, 3)), (33, (1, 2, 3)), (70, (1, 2, 3)), (1100, (1, 2, 3)), (N_EIGHT, (5, 8))):
+        rng = np.random.default_rng(7 * n + 64)
+        for P in Ps:
+            for name, (mask, owner) in MREF.owner_patterns(n, P, rng).items():
+                right = MREF.blob_of_rows(mask, owner, P)
+                listed = mask & (owner < P)
+                assert np.array_equal(right, np.where(listed, owner.astype(np.int32), -1)), (n, P, name)
+                bad = MREF.blob_of_rows(mask, owner, P, wrong="blob_mod4")
+                moved = listed & (owner >= 4)
+                assert np.array_equal(bad != right, moved), (n, P, name)
+                if P <= 3:
+                    assert not moved.any()
+                elif P == 8 and name != "empty":
+                    assert moved.any(), (name, "lists no row of an owner >= 4")
+    assert sum(MREF.OWNER_SIZES) == 132 <= N_EIGHT < 132 + 32
+
+
+def _mod8_world(A=128):
+    """Three worlds of 128 slots, owner = slot % 8 among the controlled slots: world 0 controlled below slot 64 only, world 1
+    from slot 64 on only, world 2 on both sides.  Accumulators > 0 on both sides."""
+    rng = np.random.default_rng(8)
+    ctrl = rng.random((3, A)) < 0.5
+    ctrl[0, 64:] = False
+    ctrl[1, :64] = False
+    owner = np.where(ctrl, np.arange(A) % 8, -1).astype(np.int32)
+    goal, coll, off = ((rng.random((3, A)) < 0.4).astype(f32) * rng.integers(1, 4, (3, A)) for _ in range(3))
+    den = ctrl.sum(1).astype(f32)
+    return owner, goal.astype(f32), coll.astype(f32), off.astype(f32), den
+
+
+def test_counts_of_the_first_wave_only_show_at_128_slots():
+    """The counts per wave of 64 slots, added over the waves, are compute_metrics' and the host program's on every existing
+    case (all of one wave: 8 slots), and so is the rule that adds the first wave only.  On 128 slots with eight policies on
+    either side of slot 64 that rule differs for every policy, in the world with rows on both sides and in the one with rows
+    in the second wave only."""
+    rng = np.random.default_rng(5)
+    W, A = 258, 8
+    big = (rng.integers(-1, 2, (W, A)).astype(np.int32),) + tuple(
+        ((rng.random((W, A)) < 0.3) * rng.integers(1, 4, (W, A))).astype(f32) for _ in range(3)) + (rng.integers(0, 12, W).astype(f32),)
+    for args, P in ((_constructed(), 3), (big, 2)):
+        want, _ = _want_metrics(*args, P)
+        for wrong in (None, "wave0"):
+            got = MREF.world_counts_by_wave(*args[:4], P, wrong=wrong)
+            for p in range(P):
+                for j, k in enumerate(("goal_achieved_count", "collided_count", "off_road_count", "n_rows")):
+                    assert np.array_equal(got[p, :, j].astype(f32), want[p][k]), (P, p, k, wrong)
+    args, P = _mod8_world(), 8
+    host, _ = MREF.run_metrics_host(*args, P)
+    want, _ = _want_metrics(*args, P)
+    right, bad = (MREF.world_counts_by_wave(*args[:4], P, wrong=wrong) for wrong in (None, "wave0"))
+    for p in range(P):
+        for j, k in enumerate(("goal_achieved_count", "collided_count", "off_road_count", "n_rows")):
+            assert np.array_equal(right[p, :, j].astype(f32), want[p][k]) and np.array_equal(host[p][k], want[p][k]), (p, k)
+        assert np.array_equal(bad[p, 0], right[p, 0]), "world 0 has no row from slot 64 on"
+        assert (bad[p, 1] == 0).all() and right[p, 1, 3] > 0 and 0 < bad[p, 2, 3] < right[p, 2, 3], p
+        assert (bad[p, :, :3] != right[p, :, :3]).any(), (p, "no flag of the second wave counts")
+
+
+def test_a_summary_of_the_first_256_worlds_shows_at_258():
+    """The rule that adds a lane's first world only is the right rule on every existing case of up to 256 worlds, and at 258
+    worlds with three policies, owner = (world + slot) % 3, it differs for every policy in every one of the four totals once
+    worlds 256 and 257 hold a row and a count of each (they do here by construction; the GPU case asserts it on its run)."""
+    per, _ = _want_metrics(*_constructed(), 3)
+    assert np.array_equal(MREF.summary(per, wrong="first_256"), MREF.summary(per))
+    control, done, info = _script()
+    two = MREF.metrics(control, _split(control), done, info)
+    assert np.array_equal(MREF.summary(two["policies"], wrong="first_256"), two["summary"])
+    rng = np.random.default_rng(11)
+    W, A, P = 258, 64, 3
+    ctrl = rng.random((W, A)) < 0.1
+    ctrl[256:, :6] = True
+    owner = np.where(ctrl, (np.arange(W)[:, None] + np.arange(A)[None, :]) % P, -1).astype(np.int32)
+    goal, coll, off = ((rng.random((W, A)) < 0.3).astype(f32) for _ in range(3))
+    goal[256:, :6] = coll[256:, :6] = off[256:, :6] = 1
+    den = ctrl.sum(1).astype(f32)
+    got, got_summary = MREF.run_metrics_host(owner, goal, coll, off, den, P)
+    want, want_summary = _want_metrics(owner, goal, coll, off, den, P)
+    _same_f32(got_summary, want_summary, "summary")
+    for p in range(P):
+        assert (want[p]["n_rows"][256:] > 0).all() and all(want[p][k][256:].sum() > 0 for k in MREF.WORLD_NAMES[0:5:2])
+        for k in MREF.WORLD_NAMES[0:5:2] + ("n_rows",):
+            v = want[p][k].astype(np.float64)
+            assert (v == np.round(v)).all() and float(REF.ordered_sum(want[p][k])) == v.sum() < 2 ** 24
+    assert (MREF.summary(want, wrong="first_256") != want_summary).all()
