@@ -40,7 +40,13 @@ Not here: the backward (`bc_train.TrainableBCPolicy`, gd_bc_backward); the gradi
 (`bc_rollout.ClosedLoopBC`, gd_bc_rollout, which calls this forward once per step, or with compact=True the forward on the list
 of the rows still alive);
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
-`ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64; bf16."""
+`ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64 or 128; training, probes and read-outs at 128; bf16.
+
+`network_dim=128` (with head_dim 64: the model of the reference's sweep, baselines/il/sweep.yaml) is the inference side at that
+width: `__call__`, `context` ([B, 384]), `gmm_params`, `nll`, `evaluate`, `rows=`, `load_state_dict` and the closed-loop driver
+with its attention scores, on the wide kernels (csrc/bc_policy_wide.hip, `gd_bc_forward_dim`): 4 heads of 32 channels, every
+encoder Linear 128 x 128, the GMM head behind `head.input_layer` still 64 wide.  `hidden`, `read`, `DeviceLinearProbe`,
+`ProbeReadout`, `TrainableBCPolicy` and `DeviceBC` refuse that width (ValueError, before the device is touched)."""
 import ctypes as C
 import math
 
@@ -74,35 +80,37 @@ def _linear(shapes, name, out, inp):
     shapes[name + ".weight"], shapes[name + ".bias"] = (out, inp), (out,)
 
 
-def _norm(shapes, name):
-    shapes[name + ".weight"], shapes[name + ".bias"] = (DIM,), (DIM,)
+def _norm(shapes, name, dim=DIM):
+    shapes[name + ".weight"], shapes[name + ".bias"] = (dim,), (dim,)
 
 
-def expected_shapes(num_stack, num_layer, head_num_layers, n_components):
-    """The state dict of the supported module, by the reference's own names, in the reference module's own order."""
-    s = {}
+def expected_shapes(num_stack, num_layer, head_num_layers, n_components, *, network_dim=DIM):
+    """The state dict of the supported module, by the reference's own names, in the reference module's own order.
+    network_dim (64 or 128) is the width of the embedders and of every attention layer; the GMM head behind
+    head.input_layer (3 network_dim -> 64) is head_dim = 64 wide at either."""
+    s, D = {}, network_dim
     for net, k in zip(NETS, NET_K):
         for i in range(4):  # Linear, Dropout, LayerNorm, Tanh
-            _linear(s, "%s.%d" % (net, 4 * i), DIM, k * num_stack if i == 0 else DIM)
-            _norm(s, "%s.%d" % (net, 4 * i + 2))
+            _linear(s, "%s.%d" % (net, 4 * i), D, k * num_stack if i == 0 else D)
+            _norm(s, "%s.%d" % (net, 4 * i + 2), D)
     for blk, n in zip(SELF_BLOCKS, (num_layer[0], num_layer[1], num_layer[1])):
         for i in range(n):
             p = "%s.%d" % (blk, i)
-            _norm(s, p + ".0.module.norm")
+            _norm(s, p + ".0.module.norm", D)
             for proj in "qkvo":
-                _linear(s, p + ".0.module.attention.%s_proj" % proj, DIM, DIM)
-            _norm(s, p + ".1.module.0")
-            _linear(s, p + ".1.module.1", DIM, DIM)
-            _linear(s, p + ".1.module.3", DIM, DIM)
+                _linear(s, p + ".0.module.attention.%s_proj" % proj, D, D)
+            _norm(s, p + ".1.module.0", D)
+            _linear(s, p + ".1.module.1", D, D)
+            _linear(s, p + ".1.module.3", D, D)
     for p in CROSS_LAYERS:
-        _norm(s, p + ".0.module.q_norm")
-        _norm(s, p + ".0.module.kv_norm")
+        _norm(s, p + ".0.module.q_norm", D)
+        _norm(s, p + ".0.module.kv_norm", D)
         for proj in "qkvo":
-            _linear(s, p + ".0.module.attention.%s_proj" % proj, DIM, DIM)
-        _norm(s, p + ".1.module.0")
-        _linear(s, p + ".1.module.1", DIM, DIM)
-        _linear(s, p + ".1.module.3", DIM, DIM)
-    _linear(s, "head.input_layer.0", DIM, CONTEXT)
+            _linear(s, p + ".0.module.attention.%s_proj" % proj, D, D)
+        _norm(s, p + ".1.module.0", D)
+        _linear(s, p + ".1.module.1", D, D)
+        _linear(s, p + ".1.module.3", D, D)
+    _linear(s, "head.input_layer.0", DIM, 3 * D)
     for i in range(head_num_layers):
         _linear(s, "head.residual_block.%d.0" % i, DIM, DIM)
     _linear(s, "head.head", n_components * (2 * ACTION_DIM + 1), DIM)
@@ -111,10 +119,16 @@ def expected_shapes(num_stack, num_layer, head_num_layers, n_components):
 
 def check_bc_args(state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num_head=4, head_num_layers=2, n_components=6,
                   clip_value=-20.0, *, network_dim=64, head_dim=64, network_num_layers=4, act_func="tanh", dropout=0.0,
-                  action_dim=3, time_dim=1, use_tom=None, chunk_rows=DEFAULT_CHUNK, who=WHO):
+                  action_dim=3, time_dim=1, use_tom=None, chunk_rows=DEFAULT_CHUNK, who=WHO, network_dims=(DIM,)):
     """Everything `DeviceBCPolicy` refuses, checked on the host before anything reaches the device (ValueError).  Returns
-    the expected shapes."""
-    for name, v, want in (("network_dim", network_dim, 64), ("head_dim", head_dim, 64), ("num_head", num_head, HEADS),
+    the expected shapes.  network_dims: the widths the caller has built -- (64,) unless it says otherwise, which is what the
+    backward and the optimiser say; `DeviceBCPolicy` alone passes (64, 128)."""
+    if not _is_int(network_dim) or network_dim not in network_dims:
+        if tuple(network_dims) == (DIM,):
+            raise ValueError(who + "network_dim must be 64 (nothing else is built), got %r" % (network_dim,))
+        raise ValueError(who + "network_dim must be %s (nothing else is built), got %r"
+                         % (" or ".join(str(v) for v in network_dims), network_dim))
+    for name, v, want in (("head_dim", head_dim, 64), ("num_head", num_head, HEADS),
                           ("network_num_layers", network_num_layers, 4), ("action_dim", action_dim, ACTION_DIM),
                           ("time_dim", time_dim, 1)):
         if not _is_int(v) or v != want:
@@ -141,7 +155,7 @@ def check_bc_args(state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num
         raise ValueError(who + "chunk_rows must be an int in [1, %d], got %r" % (MAX_CHUNK, chunk_rows))
     if not hasattr(state_dict, "keys") or not hasattr(state_dict, "__getitem__"):
         raise ValueError(who + "state_dict must be a mapping of names to tensors")
-    want = expected_shapes(num_stack, num_layer, head_num_layers, n_components)
+    want = expected_shapes(num_stack, num_layer, head_num_layers, n_components, network_dim=network_dim)
     keys = set(state_dict.keys())
     missing, extra = sorted(set(want) - keys), sorted(keys - set(want))
     if missing:
@@ -164,7 +178,7 @@ def _acc_row(r, h):
     return (r & 3) + 8 * (r >> 2) + 4 * h
 
 
-def pack_index(num_stack, num_layer, head_num_layers, n_components):
+def pack_index(num_stack, num_layer, head_num_layers, n_components, *, network_dim=DIM):
     """The layout of `gd_bc_policy.blob` as an index: blob = flat[pack_index], where flat is the state dict's tensors flattened
     and concatenated in `expected_shapes` order, followed by one zero (the index of every padding element: the odd last
     column of a first embedder layer).  Every parameter lands exactly once.  int64 numpy.
@@ -172,8 +186,14 @@ def pack_index(num_stack, num_layer, head_num_layers, n_components):
       first  [t 2][s ceil(K / 2)][lane] = W[32 t + c][2 s + h]          (the embedders' first Linear, K = 6 R or 13 R)
       mfma   [t2 2][t 2][r 16][lane]    = W[32 t2 + c][32 t + acc(r, h)]  (every 64 x 64 Linear applied to token tiles)
       trans  [in][out]                  = W[out][in]                      (the Linears of the one-token kernel)
-      nat    as stored                                                    (biases, LayerNorm gains and biases)"""
-    shapes = expected_shapes(num_stack, num_layer, head_num_layers, n_components)
+      nat    as stored                                                    (biases, LayerNorm gains and biases)
+    At network_dim = 128 (csrc/bc_tile_wide.hpp) the same forms in the same order with T = 4 tiles of 32 features where 64 has 2:
+      first  [t 4][s ceil(K / 2)][lane] = W[32 t + c][2 s + h]
+      mfma   [t2 4][t 4][r 16][lane]    = W[32 t2 + c][32 t + acc(r, h)]  (every 128 x 128 Linear applied to token tiles)
+      trans  [in][out]                  = W[out][in]                      (128 x 128 in the cross layers; head.input_layer is
+                                                                           [384][64], the GMM head behind it as at 64)"""
+    D, T = network_dim, network_dim // 32
+    shapes = expected_shapes(num_stack, num_layer, head_num_layers, n_components, network_dim=D)
     base, o = {}, 0
     for name, shape in shapes.items():
         base[name] = o
@@ -192,16 +212,16 @@ def pack_index(num_stack, num_layer, head_num_layers, n_components):
 
     def first(name, k):
         ks = (k + 1) // 2
-        t, s = np.arange(2)[:, None, None], np.arange(ks)[None, :, None]
+        t, s = np.arange(T)[:, None, None], np.arange(ks)[None, :, None]
         col = 2 * s + h[None, None, :] + 0 * t
         idx = base[name + ".weight"] + (32 * t + c[None, None, :]) * k + col
         parts.append(np.where(col < k, idx, zero).reshape(-1))
         nat(name + ".bias")
 
     def mfma(name):
-        t2, t, r = np.arange(2)[:, None, None, None], np.arange(2)[None, :, None, None], np.arange(16)[None, None, :, None]
+        t2, t, r = np.arange(T)[:, None, None, None], np.arange(T)[None, :, None, None], np.arange(16)[None, None, :, None]
         col = 32 * t + acc[r, h[None, None, None, :]]
-        parts.append((base[name + ".weight"] + (32 * t2 + c[None, None, None, :]) * DIM + col).reshape(-1))
+        parts.append((base[name + ".weight"] + (32 * t2 + c[None, None, None, :]) * D + col).reshape(-1))
         nat(name + ".bias")
 
     def trans(name):
@@ -241,17 +261,20 @@ def pack_index(num_stack, num_layer, head_num_layers, n_components):
     return np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in parts])
 
 
-def scratch_floats(max_agents, chunk_rows):
-    return chunk_rows * 3 * (max_agents + ROADS) * DIM
+def scratch_floats(max_agents, chunk_rows, network_dim=DIM):
+    return chunk_rows * 3 * (max_agents + ROADS) * network_dim
 
 
 class DeviceBCPolicy:
+    NETWORK_DIMS = (DIM, 128)  # the forward is built at both; everything that trains or probes is built at 64 only
+    network_dim, context_width = DIM, CONTEXT  # (an instance sets its own)
+
     def __init__(self, state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num_head=4, head_num_layers=2,
                  n_components=6, clip_value=-20.0, *, device="cuda", chunk_rows=DEFAULT_CHUNK, **fixed):
         """state_dict: the reference module's, float32.  max_agents: 64 or 128.  num_stack: 1..8.  num_layer: (fusion layers,
         ro_attn / rg_attn layers), 1..4 each.  head_num_layers: 0..4.  n_components: 1..16.  clip_value: a float.  chunk_rows:
         the rows the scratch holds (1..4096).  fixed: network_dim, head_dim, network_num_layers, act_func, dropout, action_dim,
-        time_dim, use_tom, accepted only at the values that are built (64, 64, 4, 'tanh', 0.0, 3, 1, None).  Anything else, a
+        time_dim, use_tom, accepted only at the values that are built (64 or 128, 64, 4, 'tanh', 0.0, 3, 1, None).  Anything else, a
         missing or extra key, a wrong shape or dtype is a ValueError raised before anything reaches the device."""
         unknown = sorted(set(fixed) - {"network_dim", "head_dim", "network_num_layers", "act_func", "dropout", "action_dim",
                                        "time_dim", "use_tom"})
@@ -261,7 +284,9 @@ class DeviceBCPolicy:
         self._cfg = dict(max_agents=max_agents, num_stack=num_stack, num_layer=num_layer, num_head=num_head,
                          head_num_layers=head_num_layers, n_components=n_components, clip_value=clip_value,
                          chunk_rows=chunk_rows, **fixed)
-        shapes = check_bc_args(state_dict, **self._cfg)
+        shapes = check_bc_args(state_dict, network_dims=self.NETWORK_DIMS, **self._cfg)
+        self.network_dim = D = fixed.get("network_dim", DIM)
+        self.context_width = 3 * D
         try:
             dev = torch.device(device)
         except (RuntimeError, TypeError) as e:
@@ -275,10 +300,10 @@ class DeviceBCPolicy:
         self._L = _capi.lib()
         self.device = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
         self._names = tuple(shapes)
-        self._index = torch.from_numpy(pack_index(num_stack, num_layer, head_num_layers, n_components)).to(self.device)
+        self._index = torch.from_numpy(pack_index(num_stack, num_layer, head_num_layers, n_components, network_dim=D)).to(self.device)
         self._zero = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.blob = torch.empty(self._index.numel(), dtype=torch.float32, device=self.device)
-        self._scratch = torch.empty(scratch_floats(max_agents, chunk_rows), dtype=torch.float32, device=self.device)
+        self._scratch = torch.empty(scratch_floats(max_agents, chunk_rows, D), dtype=torch.float32, device=self.device)
         self._pack(state_dict)
 
     @classmethod
@@ -293,16 +318,16 @@ class DeviceBCPolicy:
     def load_state_dict(self, state_dict):
         """Re-pack after an optimiser step: the same keys, shapes and dtypes (ValueError otherwise).  For tensors already on
         the device this is a concatenation and one gather on the device, on torch's current stream."""
-        check_bc_args(state_dict, **self._cfg)
+        check_bc_args(state_dict, network_dims=self.NETWORK_DIMS, **self._cfg)
         self._pack(state_dict)
 
     def nbytes(self, B):
         """What a call of B rows touches beyond its inputs, in bytes: the blob; the scratch, which is sized to the chunk and
-        not to B -- chunk_rows * 3 * (A + 200) * 64 float32 (32.2 MB at the default chunk of 128 rows and A = 128); and every
-        output of the row at once (context, means, covariances and their logs, weights, actions, nll, component,
-        ego_attn_score)."""
+        not to B -- chunk_rows * 3 * (A + 200) * network_dim float32 (32.2 MB at the default chunk of 128 rows, A = 128 and
+        network_dim 64; 64.5 MB at 128); and every output of the row at once (context, means, covariances and their logs,
+        weights, actions, nll, component, ego_attn_score)."""
         C_ = self.n_components
-        per_row = 4 * (CONTEXT + 3 * 3 * C_ + C_ + 3 + 1 + 1 + HEADS * (self.max_agents - 1))
+        per_row = 4 * (self.context_width + 3 * 3 * C_ + C_ + 3 + 1 + 1 + HEADS * (self.max_agents - 1))
         return 4 * (int(self.blob.numel()) + int(self._scratch.numel())) + B * per_row
 
     # ---- argument checks
@@ -331,7 +356,7 @@ class DeviceBCPolicy:
             expert = expert.view(B, ACTION_DIM)
         return self._tensor("expert_actions ([B, 1, 3] or [B, 3])", expert, (torch.float32,), (B, ACTION_DIM))
 
-    _OUT_SHAPES = dict(context=lambda s, B: (B, CONTEXT), means=lambda s, B: (B, 1, s.n_components, 3),
+    _OUT_SHAPES = dict(context=lambda s, B: (B, s.context_width), means=lambda s, B: (B, 1, s.n_components, 3),
                        log_covariances=lambda s, B: (B, 1, s.n_components, 3), covariances=lambda s, B: (B, 1, s.n_components, 3),
                        weights=lambda s, B: (B, 1, s.n_components), actions=lambda s, B: (B, 1, 3), nll=lambda s, B: (B,),
                        ego_attn_score=lambda s, B: (B, HEADS, s.max_agents - 1), component=lambda s, B: (B,))
@@ -350,6 +375,8 @@ class DeviceBCPolicy:
         from .policy import LiveRows
         if rows is not None and not isinstance(rows, LiveRows):
             raise ValueError(WHO + "rows must be a LiveRows (policy.live_rows(mask)), got %s" % type(rows).__name__)
+        if readout is not None:
+            self._only_64("read-outs")
         B = self._inputs(obs, partner_mask, road_mask)
         if rows is not None:
             if rows.n != B:
@@ -394,17 +421,20 @@ class DeviceBCPolicy:
                 res[name] = torch.empty(shape, dtype=dt, device=self.device)
         for name, t in res.items():
             setattr(o, name, t.data_ptr())
-        p = _capi.GdBCPolicy()
-        p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = self.max_agents, self.num_stack, *self.num_layer
-        p.head_layers, p.n_components, p.clip_value, p.chunk_rows = self.head_num_layers, self.n_components, self.clip_value, self.chunk_rows
-        p.blob, p.blob_floats = self.blob.data_ptr(), self.blob.numel()
-        p.scratch, p.scratch_floats = self._scratch.data_ptr(), self._scratch.numel()
+        wide = self.network_dim != DIM
+        p = self.c_struct_dim() if wide else self.c_struct()
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             args = (C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, int(deterministic),
                     None if u is None else u.data_ptr(), None if z is None else z.data_ptr(),
                     None if expert_actions is None else expert_actions.data_ptr(), C.byref(o))
-            if ro is not None:
+            if wide:  # the 64-wide policy keeps the entry points it had; gd_bc_*_dim at 64 are those, bit for bit
+                if rows is not None:
+                    _capi.check(self._L.gd_bc_forward_rows_dim(*args, rows.rows.data_ptr(), rows.count.data_ptr(), stream),
+                                "gd_bc_forward_rows_dim")
+                else:
+                    _capi.check(self._L.gd_bc_forward_dim(*args, stream), "gd_bc_forward_dim")
+            elif ro is not None:
                 if rows is not None:
                     _capi.check(self._L.gd_bc_forward_rows_readout(*args, C.byref(ro), rows.rows.data_ptr(), rows.count.data_ptr(),
                                                                    stream), "gd_bc_forward_rows_readout")
@@ -425,6 +455,7 @@ class DeviceBCPolicy:
         chunk right after the tapped layer, whatever the number of probes; no encoder layer runs twice.  out: a dict with
         tensors of an earlier call.  rows: a `LiveRows` of B: only the listed rows are read and written, in every output
         (out= must then hold them all).  No host synchronisation; with out= no allocation."""
+        self._only_64("read")
         if out is not None and not isinstance(out, dict):
             raise ValueError(WHO + "read: out must be a dict of the outputs' tensors")
         return self.forward(obs, partner_mask, road_mask, ("actions",), deterministic=deterministic, u=u, z=z, out=out, rows=rows,
@@ -439,6 +470,17 @@ class DeviceBCPolicy:
         p.scratch, p.scratch_floats = self._scratch.data_ptr(), self._scratch.numel()
         return p
 
+    def c_struct_dim(self):
+        """A fresh gd_bc_policy_dim: `c_struct` with this policy's network_dim beside it (the gd_bc_*_dim entry points)."""
+        p = _capi.GdBCPolicyDim()
+        p.base, p.network_dim, p.reserved = self.c_struct(), self.network_dim, 0
+        return p
+
+    def _only_64(self, what):
+        """What reads 64-wide tokens (hidden states, probes, read-outs) refuses a wider policy before the device is touched."""
+        if self.network_dim != DIM:
+            raise ValueError(WHO + "%s is built at network_dim 64 only, this policy has network_dim %d" % (what, self.network_dim))
+
     TAPS = {"fusion_attn": _capi.LP_TAP_FUSION, "ro_attn": _capi.LP_TAP_RO}
 
     def hidden(self, obs, partner_mask, road_mask, tap="fusion_attn", layer=None, out=None):
@@ -449,6 +491,7 @@ class DeviceBCPolicy:
         an int i in [0, layers of that block): the kernels stop after layer i of the block (`gd_bc_hidden_layer`), the output the
         reference's hook on the block's child str(i) sees; ('ro_attn', 0) is the one baselines/il/test/intervention.py reads.
         out: that tensor of an earlier call.  No host synchronisation; with out= no allocation."""
+        self._only_64("hidden")
         B = self._inputs(obs, partner_mask, road_mask)
         if tap not in self.TAPS:
             raise ValueError(WHO + "tap must be 'fusion_attn' or 'ro_attn', got %r" % (tap,))
@@ -483,7 +526,7 @@ class DeviceBCPolicy:
                             out=None if out is None else {"actions": out}, rows=rows)["actions"]
 
     def context(self, obs, partner_mask, road_mask, out=None, ego_attn_score=None, rows=None):
-        """get_context's first value, [B, 192] = [ego | ego_ro | ego_rg]; ego_attn_score: a [B, 4, A - 1] float32 tensor to
+        """get_context's first value, [B, 3 * network_dim] = [ego | ego_ro | ego_rg]; ego_attn_score: a [B, 4, A - 1] float32 tensor to
         receive its second value.  rows: as in `forward` (out= is then required)."""
         want, o = ["context"], {"context": out}
         if ego_attn_score is not None:

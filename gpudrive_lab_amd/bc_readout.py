@@ -62,6 +62,8 @@ class ProbeReadout:
         from .lp_probe import DeviceLinearProbe
         if not isinstance(policy, BP.DeviceBCPolicy):
             raise ValueError(WHO + "policy must be a DeviceBCPolicy, got %s" % type(policy).__name__)
+        if policy.network_dim != 64:
+            raise ValueError(WHO + "the read-outs read 64-wide tokens: the policy's network_dim must be 64, got %d" % policy.network_dim)
         self.layer = check_tap(policy, tap, layer)
         lists = []
         for name, probes in (("other", other), ("ego", ego)):

@@ -47,6 +47,10 @@ launch per step stores 0.0 over the scores the head kernel wrote for dead rows (
 left alone).  `attention=True` also keeps `dead_mask` (record's), which `world_importance` reads.  Every other field of the
 episode is bit-identical to the same `run()` without the two options.
 
+A policy of `network_dim=128` (`DeviceBCPolicy(..., network_dim=128)`, the reference sweep's model) drives the same loop through
+`gd_bc_rollout_dim` with the wide forward in it: `run()`, `compact`, `record`, the seeded draw and `attention=True` as above;
+`readout=` is a ValueError there (the probes read 64-wide tokens).
+
 Not here: the per-label (TURN / NORMAL / ...) grouping and the CSV, videos / `plot_simulator_state`, `lp_weight.py` (not
 runnable in the reference as written), steering the action with the intervened token (the reference only reads
 `ego_pred_prime`), fewer launches for the chunks past the list.  The late-fusion PPO policy in such a loop is `ppo_rollout.ClosedLoopPPO`.  `remove_agents_by_id` / `partner_portion_test` are the
@@ -250,6 +254,9 @@ class ClosedLoopBC:
         launch per chunk and step (and, without compact, one clean-up launch per step for the scores), and change no other
         field.  No host synchronisation."""
         _check_steps(n_steps)
+        if readout is not None and getattr(getattr(self, "policy", None), "network_dim", 64) != 64:
+            raise ValueError(WHO + "readout= is built at network_dim 64 only, the policy has network_dim %d"
+                             % self.policy.network_dim)
         _check_readout(getattr(self, "policy", None), readout)
         deterministic = bool(deterministic)
         if not deterministic and not isinstance(generator, torch.Generator):
@@ -308,7 +315,11 @@ class ClosedLoopBC:
             r.live_count = out["live_count"].data_ptr()
         sim.reset(list(range(sim._W)))
         sim._bind_stream()
-        if reads is not None:
+        if pol.network_dim != 64:  # the wide forward in the same loop (a 64-wide policy keeps the entry points it had)
+            pd = pol.c_struct_dim()
+            _capi.check(sim._L.gd_bc_rollout_dim(sim._h, C.byref(pd), C.byref(b), C.byref(r) if compact else None,
+                                                 None if reads is None else C.byref(reads), n_steps), "gd_bc_rollout_dim")
+        elif reads is not None:
             _capi.check(sim._L.gd_bc_rollout_readout(sim._h, C.byref(p), C.byref(b), C.byref(r) if compact else None,
                                                      C.byref(reads), n_steps), "gd_bc_rollout_readout")
         elif compact:

@@ -1886,7 +1886,7 @@ int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_
 // everything gd_bc_forward refuses; nullptr when everything is in order
 static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
                                       int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
-                                      const gd_bc_outputs *out) {
+                                      const gd_bc_outputs *out, int dim = 64) {
     if (!p || !obs || !partner_mask || !road_mask || !out) return "null argument";
     if (!deterministic && (!u || !z)) return "u and z are required unless deterministic";
     if (out->nll && !expert_actions) return "expert_actions is required with out->nll";
@@ -1900,10 +1900,17 @@ static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, c
     if (p->chunk_rows < 1 || p->chunk_rows > 4096) return "chunk_rows must be in [1, 4096]";
     if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
     if (!p->blob || !p->scratch) return "blob and scratch are required";
-    if (p->blob_floats != gd::bc_blob_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
-        return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
-    if (p->scratch_floats < gd::bc_scratch_floats(p->max_agents, p->chunk_rows))
-        return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 64";
+    if (dim == 128) {  // gd_bc_policy_dim: the wide layout (bc_policy_wide.hip)
+        if (p->blob_floats != gd::bc_blob_floats_wide(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+            return "blob_floats is not the layout's size at network_dim 128 for these layer counts, num_stack and n_components";
+        if (p->scratch_floats < gd::bc_scratch_floats_wide(p->max_agents, p->chunk_rows))
+            return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 128";
+    } else {
+        if (p->blob_floats != gd::bc_blob_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+            return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
+        if (p->scratch_floats < gd::bc_scratch_floats(p->max_agents, p->chunk_rows))
+            return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 64";
+    }
     if (misaligned(p->blob, 16) || misaligned(p->scratch, 256)) return "blob must be 16-byte aligned, scratch 256-byte aligned";
     if (misaligned(obs, 4) || (u && misaligned(u, 4)) || (z && misaligned(z, 4)) || (expert_actions && misaligned(expert_actions, 4)) ||
         misaligned(out->context, 4) || misaligned(out->means, 4) || misaligned(out->log_covariances, 4) ||
@@ -1970,7 +1977,8 @@ int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t
 }
 
 // everything gd_bc_rollout refuses, for gd_bc_rollout_compact too; GD_OK when everything is in order
-static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
+static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps,
+                              int dim = 64) {
     const std::string w = std::string(who) + ": ";
     if (!s || !p || !b) return fail(GD_ERR_INVALID, w + "null argument");
     if (!b->row_slot || !b->row_of_slot || !b->window || !b->partner_mask || !b->road_mask || !b->partner_value || !b->row_actions ||
@@ -1986,7 +1994,7 @@ static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p,
     gd_bc_outputs out{};
     out.actions = b->row_actions;
     if (const char *why = bc_forward_problem(p, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic, b->u, b->z,
-                                             nullptr, &out))
+                                             nullptr, &out, dim))
         return fail(GD_ERR_INVALID, w + why);
     if (misaligned(b->window, 16) || misaligned(b->goal_achieved, 4) || misaligned(b->off_road, 4) || misaligned(b->veh_collision, 4) ||
         misaligned(b->goal_step, 4) || misaligned(b->off_road_step, 4) || misaligned(b->init_goal_dist, 4) ||
@@ -2004,8 +2012,9 @@ static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p,
 // workgroup of the forward returns at its first load.
 // x (gd_bc_rollout_readout): step t's forward also writes the step's slices of the read-outs; without the list the read-out
 // kernel drops dead rows itself and one more launch zeroes the scores the head kernel stored for them.
+// dim == 128 (gd_bc_rollout_dim): the wide forward in the same loop; there is no read-out at that width.
 static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                          int32_t n_steps, const gd_bc_rollout_reads *x = nullptr) {
+                          int32_t n_steps, const gd_bc_rollout_reads *x = nullptr, int dim = 64) {
     return guarded([&]() {
         const size_t N = static_cast<size_t>(b->n_rows);
         gd_bc_outputs out{};
@@ -2032,11 +2041,19 @@ static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_
             if (r) {
                 gd::launch_live_rows(s->stream, b->dead, b->n_rows, r->rows, r->count, r->scratch,
                                      r->live_count ? r->live_count + t : nullptr, true);
-                gd::launch_bc_forward_rows(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u,
-                                           z, nullptr, out, r->rows, r->count, rd);
+                if (dim == 128)
+                    gd::launch_bc_forward_rows_wide(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows,
+                                                    b->deterministic != 0, u, z, nullptr, out, r->rows, r->count);
+                else
+                    gd::launch_bc_forward_rows(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
+                                               u, z, nullptr, out, r->rows, r->count, rd);
             } else {
-                gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
-                                      nullptr, out, rd, b->dead);
+                if (dim == 128)
+                    gd::launch_bc_forward_wide(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
+                                               u, z, nullptr, out);
+                else
+                    gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
+                                          nullptr, out, rd, b->dead);
                 if (out.ego_attn_score) gd::launch_bc_rollout_score_fill(s->stream, *b, out.ego_attn_score, score_row);
             }
             gd::launch_bc_rollout_actions(s->d, s->stream, *b, t);
@@ -2340,6 +2357,73 @@ int gd_bc_rollout_readout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_
     if (x->readout)
         if (const char *bad = bc_readout_problem(p, x->readout)) return fail(GD_ERR_INVALID, std::string(who) + ": " + bad);
     return bc_rollout_run(s, p, b, r, n_steps, x);
+}
+
+// what the *_dim entry points refuse of the struct itself, before its base is looked at; nullptr when it is in order
+static const char *bc_dim_problem(const gd_bc_policy_dim *p) {
+    if (!p) return "null argument";
+    if (p->network_dim != 64 && p->network_dim != 128) return "network_dim must be 64 or 128";
+    if (p->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                      int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                      void *stream) {
+    const char *why = bc_dim_problem(p);
+    if (!why) why = bc_forward_problem(&p->base, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, p->network_dim);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_dim: ") + why);
+    return guarded([&]() {
+        if (p->network_dim == 128)
+            gd::launch_bc_forward_wide(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u,
+                                       z, expert_actions, *out);
+        else
+            gd::launch_bc_forward(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+                                  expert_actions, *out);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                           int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                           const gd_bc_outputs *out, const int32_t *rows, const int32_t *count, void *stream) {
+    const char *why = bc_dim_problem(p);
+    if (!why) why = bc_forward_problem(&p->base, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, p->network_dim);
+    if (!why) why = row_list_problem(rows, count);
+    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_dim: ") + why);
+    return guarded([&]() {
+        if (p->network_dim == 128)
+            gd::launch_bc_forward_rows_wide(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n,
+                                            deterministic != 0, u, z, expert_actions, *out, rows, count);
+        else
+            gd::launch_bc_forward_rows(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u,
+                                       z, expert_actions, *out, rows, count);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
+// gd_bc_rollout, gd_bc_rollout_compact (r) or gd_bc_rollout_readout (x) at the policy's width.  What needs no simulator first.
+int gd_bc_rollout_dim(gd_sim *s, const gd_bc_policy_dim *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                      const gd_bc_rollout_reads *x, int32_t n_steps) {
+    const char *who = "gd_bc_rollout_dim";
+    if (!s || !p || !b) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
+    const char *why = bc_dim_problem(p);
+    if (!why && r) {
+        why = row_list_problem(r->rows, r->count);
+        if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
+        if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
+        if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
+    }
+    if (!why && x) {
+        if (!x->ego_attn_score && !x->readout) why = "reads needs ego_attn_score or readout";
+        else if (misaligned(x->ego_attn_score, 4)) why = "ego_attn_score must be 4-byte aligned";
+        else if (x->readout && p->network_dim != 64) why = "reads->readout must be NULL unless network_dim is 64 (the probes read 64-wide tokens)";
+    }
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    if (const int rc = bc_rollout_problem(who, s, &p->base, b, n_steps, p->network_dim)) return rc;
+    if (x && x->readout)
+        if (const char *bad = bc_readout_problem(&p->base, x->readout)) return fail(GD_ERR_INVALID, std::string(who) + ": " + bad);
+    return bc_rollout_run(s, &p->base, b, r, n_steps, x, p->network_dim);
 }
 
 // everything gd_bc_backward refuses; nullptr when everything is in order

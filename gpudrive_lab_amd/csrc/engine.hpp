@@ -339,6 +339,15 @@ void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *
                             const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                             const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows,
                             const int32_t *count, const gd_bc_readout *readout = nullptr);  // bc_policy.hip
+// bc_policy_wide.hip: the same forward at network_dim = 128 (gd_bc_policy_dim); no read-outs there
+long long bc_blob_floats_wide(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);
+long long bc_scratch_floats_wide(int max_agents, int chunk_rows);
+void launch_bc_forward_wide(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                            const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                            const float *expert_actions, const gd_bc_outputs &out);
+void launch_bc_forward_rows_wide(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+                                 const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
+                                 const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows, const int32_t *count);
 // bc_readout.hip: the probe read-outs of one chunk, launched by the two forwards above right after self layer
 // bc_tap_layer(p, readout->tap, readout->layer) when `readout` is given (one launch).  dead: rows whose byte is set are dropped
 int bc_tap_layer(const gd_bc_policy &p, int tap, int layer);

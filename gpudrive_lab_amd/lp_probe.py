@@ -98,6 +98,8 @@ def check_probe_args(policy, state_dict, model, exp, lr, eps, betas, weight_deca
     else:
         if not isinstance(policy, BP.DeviceBCPolicy):
             raise ValueError(WHO + "policy must be a DeviceBCPolicy for model %r" % (model,))
+        if policy.network_dim != 64:
+            raise ValueError(WHO + "the probes read 64-wide tokens: the policy's network_dim must be 64, got %d" % policy.network_dim)
         if max_agents not in (None, policy.max_agents) or num_stack not in (None, policy.num_stack):
             raise ValueError(WHO + "max_agents and num_stack are the policy's (%d, %d)" % (policy.max_agents, policy.num_stack))
         A, R = policy.max_agents, policy.num_stack

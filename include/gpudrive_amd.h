@@ -633,7 +633,7 @@ typedef struct gd_bc_policy {
 } gd_bc_policy;
 /* The outputs of one forward (device pointers); NULL: not written.  Every byte of every one given is stored by every call. */
 typedef struct gd_bc_outputs {
-    float *context;          /* [n][192] */
+    float *context;          /* [n][192] ([n][384] at network_dim 128, gd_bc_forward_dim) */
     float *means;            /* [n][C][3] */
     float *log_covariances;  /* [n][C][3] the clamped raw values */
     float *covariances;      /* [n][C][3] their exp */
@@ -1127,6 +1127,35 @@ typedef struct gd_bc_rollout_reads {
  * reads, a reads with neither member, an ego_attn_score that is not 4-byte aligned. */
 int gd_bc_rollout_readout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_rollout_buffers *buffers,
                           const gd_bc_rollout_rows *rows, const gd_bc_rollout_reads *reads, int32_t n_steps);
+/* The BC policy at another network_dim: gd_bc_policy, whose size is fixed, with the encoder's width beside it.  128 is the model
+ * of the reference's sweep (baselines/il/sweep.yaml: network_dim 128, head_dim 64, num_layer [4, 3]): every embedder Linear,
+ * LayerNorm, q / k / v / o projection and MLP Linear is 128 wide, the 4 heads have 32 channels (q is multiplied once, after the
+ * bias, by the float32 nearest to 32^-1/2), the context is [n][384], head.input_layer is 384 -> 64 and the GMM head behind it
+ * stays 64 wide.  At 128: base.blob_floats is the layout's at that width (`pack_index(..., network_dim=128)`) and
+ * base.scratch_floats >= chunk_rows * 3 * (A + 200) * 128.  The inference side only: the backward, the update, gd_bc_hidden, the
+ * linear probes and the read-outs take a gd_bc_policy and stay 64 wide. */
+typedef struct gd_bc_policy_dim {
+    gd_bc_policy base;
+    int32_t network_dim;  /* 64 or 128 */
+    int32_t reserved;     /* 0 */
+} gd_bc_policy_dim;
+/* gd_bc_forward and gd_bc_forward_rows at p->network_dim: the same arguments, checks and guarantees; out->context is
+ * [n][3 * network_dim].  At 64 they run gd_bc_forward's (gd_bc_forward_rows') own kernels and give its bits.  At 128: the wide
+ * kernels (csrc/bc_policy_wide.hip), 2 fusion_layers + 2 branch_layers + 3 launches per chunk as at 64, no host synchronisation, no
+ * allocation, no atomics.  GD_ERR_INVALID, before any launch: whatever those refuse, a network_dim other than 64 or 128,
+ * reserved != 0, blob_floats or scratch_floats not that width's. */
+int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                      int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                      void *stream);
+int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                           int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                           const gd_bc_outputs *out, const int32_t *rows, const int32_t *count, void *stream);
+/* The closed-loop episode at p->network_dim: gd_bc_rollout (rows == NULL, reads == NULL), gd_bc_rollout_compact (rows) or
+ * gd_bc_rollout_readout (reads) with that forward in the loop, every output as those define it.  reads->ego_attn_score is
+ * allowed at either width; reads->readout must be NULL unless network_dim is 64 (GD_ERR_INVALID: the probes read 64-wide
+ * tokens).  Otherwise GD_ERR_INVALID / GD_ERR_UNSUPPORTED: whatever those three and gd_bc_forward_dim refuse. */
+int gd_bc_rollout_dim(gd_sim *sim, const gd_bc_policy_dim *policy, const gd_bc_rollout_buffers *buffers,
+                      const gd_bc_rollout_rows *rows, const gd_bc_rollout_reads *reads, int32_t n_steps);
 /* Episode bookkeeping on the device: PufferGPUDrive.step()'s tracking of live agents,
  * episode returns / lengths / collision and off-road counts, finished worlds and their asynchronous reset
  * (gpudrive/env/env_puffer.py:250-403; rewards gpudrive/env/env_torch.py:469-505) without a host round trip.
