@@ -44,7 +44,7 @@ of the rows still alive);
 
 `network_dim=128` (with head_dim 64: the model of the reference's sweep, baselines/il/sweep.yaml) is the inference side at that
 width: `__call__`, `context` ([B, 384]), `gmm_params`, `nll`, `evaluate`, `rows=`, `load_state_dict` and the closed-loop driver
-with its attention scores, on the wide kernels (csrc/bc_policy_wide.hip, `gd_bc_forward_dim`): 4 heads of 32 channels, every
+with its attention scores, on the kernels' T = 4 instantiations (csrc/bc_policy.hip, `gd_bc_forward_dim`): 4 heads of 32 channels, every
 encoder Linear 128 x 128, the GMM head behind `head.input_layer` still 64 wide.  `hidden`, `read`, `DeviceLinearProbe`,
 `ProbeReadout`, `TrainableBCPolicy` and `DeviceBC` refuse that width (ValueError, before the device is touched)."""
 import ctypes as C
@@ -187,7 +187,7 @@ def pack_index(num_stack, num_layer, head_num_layers, n_components, *, network_d
       mfma   [t2 2][t 2][r 16][lane]    = W[32 t2 + c][32 t + acc(r, h)]  (every 64 x 64 Linear applied to token tiles)
       trans  [in][out]                  = W[out][in]                      (the Linears of the one-token kernel)
       nat    as stored                                                    (biases, LayerNorm gains and biases)
-    At network_dim = 128 (csrc/bc_tile_wide.hpp) the same forms in the same order with T = 4 tiles of 32 features where 64 has 2:
+    At network_dim = 128 (csrc/bc_tile.hpp, BCEnc<4>) the same forms in the same order with T = 4 tiles of 32 features where 64 has 2:
       first  [t 4][s ceil(K / 2)][lane] = W[32 t + c][2 s + h]
       mfma   [t2 4][t 4][r 16][lane]    = W[32 t2 + c][32 t + acc(r, h)]  (every 128 x 128 Linear applied to token tiles)
       trans  [in][out]                  = W[out][in]                      (128 x 128 in the cross layers; head.input_layer is

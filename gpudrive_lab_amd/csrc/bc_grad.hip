@@ -21,7 +21,7 @@
 //                 the lane, P and dS from the saved m, l and D of each query row, dV^T += dO^T P, dK^T += Q^T dS; then
 //                 k_proj, v_proj and q_proj back to the normed input, the LayerNorm, plus the residual's share.  Owns dX[token].
 //   k_bcg_embed   a wave per 32 tokens of one kind: the four embedder layers, last to first, each recomputed from obs.
-// Every product over a token tile is v_mfma_f32_32x32x2_f32 on the transposed tile of bc_tile.hpp: dX^T = W^T dY^T is linear64
+// Every product over a token tile is v_mfma_f32_32x32x2_f32 on the transposed tile of bc_tile.hpp: dX^T = W^T dY^T is linear
 // with the transposed weights (k_bcg_transpose writes them once per call), dW = dY^T X contracts the tile's 32 tokens after one
 // trip of both tiles through LDS.  Weight gradients: a launch has `num_partials` workgroups of one wave; workgroup w takes the
 // (row, tile) pairs w, w + num_partials, .. in ascending order and adds each pair's share to ITS slice of `partials` (natural
@@ -35,6 +35,8 @@ namespace gd {
 
 namespace {
 
+using E = BCEnc<2>;  // the backward exists at network_dim 64 only, where the encoder's width is F and a square weight W64
+
 constexpr int LDW = F + 1;                       // a [32 tokens][64] tile in LDS, padded against bank conflicts
 constexpr int LXW = 129;                         // the first embedder layer's input tile: up to 8 * 13 = 104 columns, padded to 128
 constexpr int MAX_T = 104;
@@ -43,7 +45,7 @@ constexpr float INV_SQRT_2PI = 0.3989422804014327f;
 // the gradient's layout: the state dict's order, natural row-major tensors.  It is the blob's layout without the first
 // embedder layers' padding, so every field after the embedders sits at its blob offset plus one constant.
 BCLayout bc_nat_layout(int R, int n_self, int head_layers, int C) {
-    BCLayout L = bc_layout(R, n_self, head_layers, C);
+    BCLayout L = bc_layout<2>(R, n_self, head_layers, C);
     const int kin[3] = {EGO_K * R, PARTNER_K * R, ROAD_K * R};
     int o = 0;
     for (int e = 0; e < 3; e++) {
@@ -285,38 +287,38 @@ __global__ __launch_bounds__(64) void k_bcg_post(BCDims d, Segs sg, int rows, Gr
             f16v x[2], o[2];
             load_tok(gb.O + at, o, h);
             load_tok(xs + at, x, h);
-            linear64(o, w + S_OW, w + S_OB, z, lane, h);
+            linear(o, w + E::S_OW, w + E::S_OB, z, lane, h);
 #pragma unroll
             for (int t = 0; t < 2; t++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) z[t][r] = z[t][r] + x[t][r];
         }
-        layer_norm_keep(z, zh, rstd, w + S_MG, w + S_MB, h);
-        linear64(z, w + S_W1, w + S_B1, z1, lane, h);
+        layer_norm_keep(z, zh, rstd, w + E::S_MG, w + E::S_MB, h);
+        linear(z, w + E::S_W1, w + E::S_B1, z1, lane, h);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) g1[t][r] = gelu_erf(z1[t][r]);
         load_tok(gb.dX + at, dout, h);
         if (!live) zero_tile(dout);
-        linear_grads(nw + S_W2, nw + S_B2, dout, g1, ldA, ldB, lane, live);
-        linear64_nb(dout, wt + S_W2, dt, lane);
+        linear_grads(nw + E::S_W2, nw + E::S_B2, dout, g1, ldA, ldB, lane, live);
+        linear64_nb(dout, wt + E::S_W2, dt, lane);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) dt[t][r] = dt[t][r] * gelu_erf_grad(z1[t][r]);
-        linear_grads(nw + S_W1, nw + S_B1, dt, z, ldA, ldB, lane, live);
-        linear64_nb(dt, wt + S_W1, g1, lane);  // g1: now the gradient at the MLP's LayerNorm output
-        norm_grads(nw + S_MG, nw + S_MB, g1, zh, ldA, ldB, lane, live);
-        layer_norm_back(g1, zh, rstd, w + S_MG, h);
+        linear_grads(nw + E::S_W1, nw + E::S_B1, dt, z, ldA, ldB, lane, live);
+        linear64_nb(dt, wt + E::S_W1, g1, lane);  // g1: now the gradient at the MLP's LayerNorm output
+        norm_grads(nw + E::S_MG, nw + E::S_MB, g1, zh, ldA, ldB, lane, live);
+        layer_norm_back(g1, zh, rstd, w + E::S_MG, h);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) dout[t][r] = dout[t][r] + g1[t][r];  // dy: the gradient at the attention residual's sum
         f16v o[2];
         load_tok(gb.O + at, o, h);  // (again: kept from the start it would cost 32 registers through the whole MLP)
-        linear_grads(nw + S_OW, nw + S_OB, dout, o, ldA, ldB, lane, live);
-        linear64_nb(dout, wt + S_OW, dt, lane);  // dO
+        linear_grads(nw + E::S_OW, nw + E::S_OB, dout, o, ldA, ldB, lane, live);
+        linear64_nb(dout, wt + E::S_OW, dt, lane);  // dO
         if (live) {
             store_tok(gb.dX + at, dout, h);
             store_tok(gb.dO + at, dt, h);
@@ -348,8 +350,8 @@ __global__ __launch_bounds__(64) void k_bcg_dq(BCDims d, Segs sg, int rows, Grad
         float *__restrict__ nw = slice + s.w + gb.nat_delta;
         f16v hn[2], q[2], dao[2], dq[2];
         load_tok(xs + at, hn, h);
-        layer_norm(hn, w + S_NG, w + S_NB, h);
-        linear64(hn, w + S_QW, w + S_QB, q, lane, h);
+        layer_norm(hn, w + E::S_NG, w + E::S_NB, h);
+        linear(hn, w + E::S_QW, w + E::S_QB, q, lane, h);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(64) void k_bcg_dq(BCDims d, Segs sg, int rows, Grad
             for (int r = 0; r < 8; r++) dq[t][rb + r] = live ? acc[r] * 0.25f : 0.f;
         }
         if (live) store_tok(gb.dQ + at, dq, h);
-        linear_grads(nw + S_QW, nw + S_QB, dq, hn, ldA, ldB, lane, live);
+        linear_grads(nw + E::S_QW, nw + E::S_QB, dq, hn, ldA, ldB, lane, live);
     }
 }
 
@@ -504,24 +506,24 @@ __global__ __launch_bounds__(64) void k_bcg_dkv(BCDims d, Segs sg, int rows, Gra
         f16v hn[2], xh[2], dh[2], tmp[2];
         float rstd;
         load_tok(xs + at, hn, h);
-        layer_norm_keep(hn, xh, rstd, w + S_NG, w + S_NB, h);
-        linear_grads(nw + S_KW, nw + S_KB, dk, hn, ldA, ldB, lane, live);
-        linear_grads(nw + S_VW, nw + S_VB, dv, hn, ldA, ldB, lane, live);
-        linear64_nb(dk, wt + S_KW, dh, lane);
-        linear64_nb(dv, wt + S_VW, tmp, lane);
+        layer_norm_keep(hn, xh, rstd, w + E::S_NG, w + E::S_NB, h);
+        linear_grads(nw + E::S_KW, nw + E::S_KB, dk, hn, ldA, ldB, lane, live);
+        linear_grads(nw + E::S_VW, nw + E::S_VB, dv, hn, ldA, ldB, lane, live);
+        linear64_nb(dk, wt + E::S_KW, dh, lane);
+        linear64_nb(dv, wt + E::S_VW, tmp, lane);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) dh[t][r] = dh[t][r] + tmp[t][r];
         load_tok(gb.dQ + at, dk, h);  // dk: now this token's dQ
         if (!live) zero_tile(dk);
-        linear64_nb(dk, wt + S_QW, tmp, lane);
+        linear64_nb(dk, wt + E::S_QW, tmp, lane);
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++) dh[t][r] = dh[t][r] + tmp[t][r];
-        norm_grads(nw + S_NG, nw + S_NB, dh, xh, ldA, ldB, lane, live);
-        layer_norm_back(dh, xh, rstd, w + S_NG, h);
+        norm_grads(nw + E::S_NG, nw + E::S_NB, dh, xh, ldA, ldB, lane, live);
+        layer_norm_back(dh, xh, rstd, w + E::S_NG, h);
         load_tok(gb.dX + at, tmp, h);  // the residual's share, k_bcg_post's
 #pragma unroll
         for (int t = 0; t < 2; t++)
@@ -596,7 +598,7 @@ __device__ __forceinline__ void embed_forward(const BCDims &d, int kind, int ec,
         for (int r = 0; r < 16; r++) a[t][r] = tanhf(a[t][r]);
     for (int i = 0; i + 1 < upto; i++) {
         const float *__restrict__ w = rest + 3 * F + i * (W64 + 3 * F);
-        linear64(a, w, w + W64, o, lane, h);
+        linear(a, w, w + W64, o, lane, h);
         layer_norm(o, w + W64 + F, w + W64 + 2 * F, h);
 #pragma unroll
         for (int t = 0; t < 2; t++)
@@ -630,7 +632,7 @@ __global__ __launch_bounds__(64) void k_bcg_embed(BCDims d, BCLayout L, BCLayout
             embed_forward(d, kind, ec, x, w0, rest, i, a, lane, h);  // the input of layer i
             const float *__restrict__ w = rest + 3 * F + (i - 1) * (W64 + 3 * F);
             float *__restrict__ nwl = nrest + 3 * F + (i - 1) * (W64 + 3 * F);
-            linear64(a, w, w + W64, z, lane, h);
+            linear(a, w, w + W64, z, lane, h);
             layer_norm_keep(z, xh, rstd, w + W64 + F, w + W64 + 2 * F, h);
 #pragma unroll
             for (int t = 0; t < 2; t++)
@@ -722,7 +724,7 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
     __shared__ float prob[2][4][ROADS];
     __shared__ float ds[4][ROADS];
     __shared__ float qs[2][F];
-    __shared__ float ctx[CTX], dctx[CTX];
+    __shared__ float ctx[E::CTX], dctx[E::CTX];
     __shared__ float vec[F];
     __shared__ float raw[MAX_HEAD_OUT], draw[MAX_HEAD_OUT];
     __shared__ float hin[5][F], pre[5][F];
@@ -740,9 +742,9 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
             CrossKeep &k = keep[ci];
             const int tok0 = ci ? d.A : 1, nk = ci ? ROADS : d.A - 1;
             const float *__restrict__ w = blob + L.cross[ci];
-            const float *__restrict__ wb = w + C_BODY;
-            k.qn = wave_ln_keep(xq, k.xhq, k.rstdq, w + C_QG, w + C_QB, lane);
-            qs[ci][lane] = matvec64(wb + S_QW, wb + S_QB, k.qn, lane) * 0.25f;
+            const float *__restrict__ wb = w + E::C_BODY;
+            k.qn = wave_ln_keep(xq, k.xhq, k.rstdq, w + E::C_QG, w + E::C_QB, lane);
+            qs[ci][lane] = matvec64(wb + E::S_QW, wb + E::S_QB, k.qn, lane) * 0.25f;
             __syncthreads();
             for (int j = lane; j < nk; j += 64) {
                 const float *__restrict__ kp = Kb + base + (size_t)(tok0 + j) * F;
@@ -771,16 +773,16 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
             float o = 0.f;
             for (int j = 0; j < nk; j++) o = o + prob[ci][hd][j] * Vb[base + (size_t)(tok0 + j) * F + lane];
             k.o = o;
-            k.y = matvec64(wb + S_OW, wb + S_OB, o, lane) + xq;
-            k.zn = wave_ln_keep(k.y, k.zh, k.rstdm, wb + S_MG, wb + S_MB, lane);
-            k.z1 = matvec64(wb + S_W1, wb + S_B1, k.zn, lane);
+            k.y = matvec64(wb + E::S_OW, wb + E::S_OB, o, lane) + xq;
+            k.zn = wave_ln_keep(k.y, k.zh, k.rstdm, wb + E::S_MG, wb + E::S_MB, lane);
+            k.z1 = matvec64(wb + E::S_W1, wb + E::S_B1, k.zn, lane);
             k.g1 = gelu_erf(k.z1);
-            ctx[F * (1 + ci) + lane] = k.y + matvec64(wb + S_W2, wb + S_B2, k.g1, lane);
+            ctx[F * (1 + ci) + lane] = k.y + matvec64(wb + E::S_W2, wb + E::S_B2, k.g1, lane);
             __syncthreads();
         }
         // the GMM head, forward
         float hcur = blob[L.head_in_b + lane];
-        for (int k = 0; k < CTX; k++) hcur = hcur + blob[L.head_in_w + k * F + lane] * ctx[k];
+        for (int k = 0; k < E::CTX; k++) hcur = hcur + blob[L.head_in_w + k * F + lane] * ctx[k];
         pre[0][lane] = hcur;
         hcur = fmaxf(hcur, 0.f);
         for (int i = 0; i < a.head_layers; i++) {
@@ -830,7 +832,7 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
                 const float dpo = __shfl(dp, o);
 #pragma unroll
                 for (int j = 0; j < 3; j++) {
-                    const int at = L.head_in_w + o * CTX + F * j + lane;
+                    const int at = L.head_in_w + o * E::CTX + F * j + lane;
                     slice[at] = slice[at] + dpo * ctx[F * j + lane];
                     dc[j] = dc[j] + gb.WT[at] * dpo;
                 }
@@ -845,19 +847,19 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
         for (int ci = 0; ci < 2; ci++) {
             const CrossKeep &k = keep[ci];
             const int tok0 = ci ? d.A : 1, nk = ci ? ROADS : d.A - 1;
-            const int cw = L.cross[ci], cb = cw + C_BODY;
+            const int cw = L.cross[ci], cb = cw + E::C_BODY;
             const float *__restrict__ wtb = gb.WT + cb;
             float *__restrict__ nb = slice + cb, *__restrict__ nw = slice + cw;
             const float dout = dctx[F * (1 + ci) + lane];
-            outer64(nb + S_W2, nb + S_B2, dout, k.g1, lane);
-            const float dz1 = matvec64_t(wtb + S_W2, dout, lane) * gelu_erf_grad(k.z1);
-            outer64(nb + S_W1, nb + S_B1, dz1, k.zn, lane);
-            const float dzn = matvec64_t(wtb + S_W1, dz1, lane);
-            nb[S_MG + lane] = nb[S_MG + lane] + dzn * k.zh;
-            nb[S_MB + lane] = nb[S_MB + lane] + dzn;
-            const float dy = dout + wave_ln_back(dzn, k.zh, k.rstdm, blob[cb + S_MG + lane]);
-            outer64(nb + S_OW, nb + S_OB, dy, k.o, lane);
-            const float dao = matvec64_t(wtb + S_OW, dy, lane);
+            outer64(nb + E::S_W2, nb + E::S_B2, dout, k.g1, lane);
+            const float dz1 = matvec64_t(wtb + E::S_W2, dout, lane) * gelu_erf_grad(k.z1);
+            outer64(nb + E::S_W1, nb + E::S_B1, dz1, k.zn, lane);
+            const float dzn = matvec64_t(wtb + E::S_W1, dz1, lane);
+            nb[E::S_MG + lane] = nb[E::S_MG + lane] + dzn * k.zh;
+            nb[E::S_MB + lane] = nb[E::S_MB + lane] + dzn;
+            const float dy = dout + wave_ln_back(dzn, k.zh, k.rstdm, blob[cb + E::S_MG + lane]);
+            outer64(nb + E::S_OW, nb + E::S_OB, dy, k.o, lane);
+            const float dao = matvec64_t(wtb + E::S_OW, dy, lane);
             dxq = dxq + dy;
             // the one-query attention
             __syncthreads();
@@ -892,11 +894,11 @@ __global__ __launch_bounds__(64) void k_bcg_head(BCDims d, BCLayout L, HeadGradA
                 dq = dq + dsj * Kb[at];
             }
             dq = dq * 0.25f;
-            outer64(nb + S_QW, nb + S_QB, dq, k.qn, lane);
-            const float dqn = matvec64_t(wtb + S_QW, dq, lane);
-            nw[C_QG + lane] = nw[C_QG + lane] + dqn * k.xhq;
-            nw[C_QB + lane] = nw[C_QB + lane] + dqn;
-            dxq = dxq + wave_ln_back(dqn, k.xhq, k.rstdq, blob[cw + C_QG + lane]);
+            outer64(nb + E::S_QW, nb + E::S_QB, dq, k.qn, lane);
+            const float dqn = matvec64_t(wtb + E::S_QW, dq, lane);
+            nw[E::C_QG + lane] = nw[E::C_QG + lane] + dqn * k.xhq;
+            nw[E::C_QB + lane] = nw[E::C_QB + lane] + dqn;
+            dxq = dxq + wave_ln_back(dqn, k.xhq, k.rstdq, blob[cw + E::C_QG + lane]);
         }
         gb.dX[base + lane] = dxq;
     }
@@ -908,13 +910,13 @@ TList transposes(const gd_bc_policy &p, const BCLayout &L) {
     for (int e = 0; e < 3; e++)
         for (int i = 0; i < 3; i++) add(L.net_rest[e] + 3 * F + i * (W64 + 3 * F), 0, 0);
     for (int i = 0; i < p.fusion_layers + 2 * p.branch_layers; i++)
-        for (int f : {S_QW, S_KW, S_VW, S_OW, S_W1, S_W2}) add(L.self0 + i * S_SIZE + f, 0, 0);
+        for (int f : {E::S_QW, E::S_KW, E::S_VW, E::S_OW, E::S_W1, E::S_W2}) add(L.self0 + i * E::S_SIZE + f, 0, 0);
     for (int ci = 0; ci < 2; ci++) {
-        const int cb = L.cross[ci] + C_BODY;
-        add(cb + S_KW, 0, 0), add(cb + S_VW, 0, 0);
-        for (int f : {S_QW, S_OW, S_W1, S_W2}) add(cb + f, F, F);
+        const int cb = L.cross[ci] + E::C_BODY;
+        add(cb + E::S_KW, 0, 0), add(cb + E::S_VW, 0, 0);
+        for (int f : {E::S_QW, E::S_OW, E::S_W1, E::S_W2}) add(cb + f, F, F);
     }
-    add(L.head_in_w, CTX, F);
+    add(L.head_in_w, E::CTX, F);
     for (int i = 0; i < p.head_layers; i++) add(L.head_res + i * (W64 + F), F, F);
     add(L.head_w, F, 7 * p.n_components);
     return tl;
@@ -937,7 +939,7 @@ void launch_bc_backward(const gd_bc_policy &p, const gd_bc_grad &g, hipStream_t 
                         float *grad) {
     const int A = p.max_agents, R = p.num_stack, NL = p.fusion_layers + p.branch_layers, P = g.num_partials;
     const BCDims d = bc_dims(p);
-    const BCLayout L = bc_layout(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
+    const BCLayout L = bc_layout<2>(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
     const BCLayout N = bc_nat_layout(R, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
     const size_t per = (size_t)p.chunk_rows * d.L * F;
     float *X = p.scratch, *Kb = p.scratch + per, *Vb = p.scratch + 2 * per;
@@ -956,7 +958,7 @@ void launch_bc_backward(const gd_bc_policy &p, const gd_bc_grad &g, hipStream_t 
     };
     gd_bc_outputs out{};
     out.nll = nll;
-    const Segs cross = bc_cross_segs(p);
+    const Segs cross = bc_cross_segs<2>(p);
     for (int r0 = 0; r0 < n; r0 += p.chunk_rows) {
         const int rows = std::min(p.chunk_rows, n - r0);
         const size_t used = (size_t)rows * d.L * F;
@@ -974,7 +976,7 @@ void launch_bc_backward(const gd_bc_policy &p, const gd_bc_grad &g, hipStream_t 
         hipLaunchKernelGGL(k_bcg_kvx, dim3((unsigned)P), dim3(64), 0, st, d, cross, rows, gb, X);
         for (int i = NL - 1; i >= 0; i--) {
             const float *xs = XS + (size_t)i * per;
-            const Segs sg = bc_layer_segs(p, i);
+            const Segs sg = bc_layer_segs<2>(p, i);
             copy(xs, X, used);
             launch_bc_self_layer(p, st, pm, rm, rows, i, X, Kb, Vb, gb.O, gb.ML);
             hipLaunchKernelGGL(k_bcg_post, dim3((unsigned)P), dim3(64), 0, st, d, sg, rows, gb, xs);

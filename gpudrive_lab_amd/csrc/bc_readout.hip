@@ -5,10 +5,10 @@
 //   k_bc_readout   ONE launch per chunk for every probe and all three read-outs; a wave per tile of 32 rows, as in k_lp_rows.
 //                  Partner tiles (only with 'other' probes): tile i of slot s is the partner columns 32 i .. 32 i + 31, the tokens
 //                  1 + column (the last tile holds 31 rows: A - 1 is 63 or 127).  Ego tiles: token 0 of 32 consecutive slots.
-//                  Per probe bc_tile.hpp's linear64 on the probe's packed weights -- k_lp_rows' logits, bit for bit -- the tile of
+//                  Per probe bc_tile.hpp's linear on the probe's packed weights -- k_lp_rows' logits, bit for bit -- the tile of
 //                  logits through LDS so that a lane owns a row, lp_rule.hpp's first maximum, one byte stored per row.  The
 //                  intervention adds row `label` of the paired 'other' probe's natural-layout head.weight to the ego token, one
-//                  float32 add per feature, before the 'ego' probe's linear64.  The first ego tile also counts the chunk's rows
+//                  float32 add per feature, before the 'ego' probe's linear.  The first ego tile also counts the chunk's rows
 //                  whose label is outside [0, 63] and adds them to bad_labels: the chunks of a stream run one after the other, so
 //                  the counter has one writer at a time and needs no atomic.
 // The list instantiation (List = BCRows) is keyed as the forward's: X by slot, labels and every output by the row.  `dead`
@@ -43,7 +43,7 @@ __device__ __forceinline__ int ro_sample(const ROArgs &, int slot, const BCRows 
 __device__ __forceinline__ unsigned char tile_class(const f16v (&x)[2], const float *__restrict__ packed, float *ldZ, int lane, int h,
                                                     int col) {
     f16v z[2];
-    linear64(x, packed, packed + W64, z, lane, h);
+    linear(x, packed, packed + W64, z, lane, h);
     __syncthreads();  // the tile before this one has been read
 #pragma unroll
     for (int t = 0; t < 2; t++)

@@ -1,7 +1,11 @@
 // What the device BC policy forward (bc_policy.hip) and backward (bc_grad.hip) share: the layout of gd_bc_policy.blob, the
-// transposed 32-token tile (lane (c = lane & 31, h = lane >> 5) belongs to token c; its two 16-register accumulators hold the
-// features 32 t + acc_row(r, h)), the 64 x 64 Linear and the LayerNorm on it, the one-token helpers of the head kernels, and
-// the segments a self-attention launch covers.  Everything has internal linkage: each translation unit compiles its own.
+// transposed 32-token tile (lane (c = lane & 31, h = lane >> 5) belongs to token c; its T 16-register accumulators hold the
+// features 32 t + acc_row(r, h)), the Linear and the LayerNorm on it, the one-token helpers of the head kernels, and the
+// segments a self-attention launch covers.  Everything has internal linkage: each translation unit compiles its own.
+// The encoder's width is a parameter, T = network_dim / 32 tiles per token: 2 (network_dim 64, every kernel) or 4 (128, the
+// forward only).  The tile helpers deduce T from the accumulator array; the widths and the offsets of a layer's fields are
+// BCEnc<T>; the layout and the segments are templates on T.  A file that exists at 64 only names BCEnc<2> once.  At T = 2
+// everything here compiles to the code it was before there was a T (tools/isa_same.py is how that is checked).
 #pragma once
 
 #include <float.h>
@@ -19,16 +23,26 @@ namespace {
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-constexpr int F = 64, ROADS = 200, ROAD_K = 13, PARTNER_K = 6, EGO_K = 6, CTX = 192, W64 = F * F;
+// F is the width of the GMM head behind head.input_layer: 64 at either network_dim
+constexpr int F = 64, ROADS = 200, ROAD_K = 13, PARTNER_K = 6, EGO_K = 6, W64 = F * F;
 constexpr float LN_EPS = 1e-5f;
 constexpr int MAX_HEAD_OUT = 7 * bc_rule::MAX_COMPONENTS;
 
-// offsets inside one self-attention layer, in floats (gpudrive_lab_amd/bc_policy.py `pack_index` states the same order)
-constexpr int S_NG = 0, S_NB = 64, S_QW = 128, S_QB = S_QW + W64, S_KW = S_QB + F, S_KB = S_KW + W64, S_VW = S_KB + F,
-              S_VB = S_VW + W64, S_OW = S_VB + F, S_OB = S_OW + W64, S_MG = S_OB + F, S_MB = S_MG + F, S_W1 = S_MB + F,
-              S_B1 = S_W1 + W64, S_W2 = S_B1 + F, S_B2 = S_W2 + W64, S_SIZE = S_B2 + F;
-// a cross-attention layer: q_norm, kv_norm, then the same fields (q, o and the MLP transposed [in][out], k and v packed)
-constexpr int C_QG = 0, C_QB = 64, C_KVG = 128, C_KVB = 192, C_BODY = 128, C_SIZE = S_SIZE + C_BODY;
+// the encoder at network_dim = 32 T (gpudrive_lab_amd/bc_policy.py `pack_index` states the same order with the same T)
+template <int T>
+struct BCEnc {
+    // features of a token, floats of a square weight, the context's width, channels of one of the four heads
+    static constexpr int FE = 32 * T, W = FE * FE, CTX = 3 * FE, HC = FE / 4;
+    // HC^-1/2, by which q is multiplied once, after the bias: 1/4, and 32^-1/2 as the float32 nearest to it (0x3e3504f3)
+    static constexpr float QSCALE = T == 2 ? 0.25f : 0.17677669529663687f;
+    // offsets inside one self-attention layer, in floats
+    static constexpr int S_NG = 0, S_NB = FE, S_QW = 2 * FE, S_QB = S_QW + W, S_KW = S_QB + FE, S_KB = S_KW + W, S_VW = S_KB + FE,
+                         S_VB = S_VW + W, S_OW = S_VB + FE, S_OB = S_OW + W, S_MG = S_OB + FE, S_MB = S_MG + FE, S_W1 = S_MB + FE,
+                         S_B1 = S_W1 + W, S_W2 = S_B1 + FE, S_B2 = S_W2 + W, S_SIZE = S_B2 + FE;
+    // a cross-attention layer: q_norm, kv_norm, then the same fields (q, o and the MLP transposed [in][out], k and v packed)
+    static constexpr int C_QG = 0, C_QB = FE, C_KVG = 2 * FE, C_KVB = 3 * FE, C_BODY = 2 * FE, C_SIZE = S_SIZE + C_BODY;
+    static_assert(T == 2 || T == 4, "network_dim is 64 or 128");
+};
 
 struct BCLayout {
     int net_w0[3], net_rest[3];  // 0: ego, 1: partner, 2: road.  rest: b0, g0, be0, then 3 x (W packed, b, g, be)
@@ -37,18 +51,20 @@ struct BCLayout {
 
 __host__ __device__ inline int first_steps(int k) { return (k + 1) / 2; }
 
+template <int T>
 BCLayout bc_layout(int R, int n_self, int head_layers, int C) {
+    using E = BCEnc<T>;
     BCLayout L;
     int o = 0;
     auto take = [&](int n) { const int at = o; o += n; return at; };
     const int kin[3] = {EGO_K * R, PARTNER_K * R, ROAD_K * R};
     for (int e = 0; e < 3; e++) {
-        L.net_w0[e] = take(2 * first_steps(kin[e]) * 64);
-        L.net_rest[e] = take(3 * F + 3 * (W64 + 3 * F));
+        L.net_w0[e] = take(T * first_steps(kin[e]) * 64);
+        L.net_rest[e] = take(3 * E::FE + 3 * (E::W + 3 * E::FE));
     }
-    L.self0 = take(n_self * S_SIZE);
-    L.cross[0] = take(C_SIZE), L.cross[1] = take(C_SIZE);
-    L.head_in_w = take(CTX * F), L.head_in_b = take(F);
+    L.self0 = take(n_self * E::S_SIZE);
+    L.cross[0] = take(E::C_SIZE), L.cross[1] = take(E::C_SIZE);
+    L.head_in_w = take(E::CTX * F), L.head_in_b = take(F);
     L.head_res = take(head_layers * (W64 + F));
     L.head_w = take(F * 7 * C), L.head_b = take(7 * C);
     L.total = o;
@@ -58,42 +74,44 @@ BCLayout bc_layout(int R, int n_self, int head_layers, int C) {
 // accumulator register r of lane half h holds this row of a 32 x 32 tile
 __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// o = W a + b on the transposed tile; w is packed [t2 2][t 2][r 16][lane] = W[32 t2 + c][32 t + acc(r, h)]
-__device__ __forceinline__ void linear64(const f16v (&a)[2], const float *__restrict__ w, const float *__restrict__ b, f16v (&o)[2],
-                                         int lane, int h) {
+// o = W a + b on the transposed tile; w is packed [t2 T][t T][r 16][lane] = W[32 t2 + c][32 t + acc(r, h)]
+template <int T>
+__device__ __forceinline__ void linear(const f16v (&a)[T], const float *__restrict__ w, const float *__restrict__ b, f16v (&o)[T],
+                                       int lane, int h) {
 #pragma unroll
-    for (int t2 = 0; t2 < 2; t2++) {
+    for (int t2 = 0; t2 < T; t2++) {
 #pragma unroll
         for (int r = 0; r < 16; r++) o[t2][r] = b[32 * t2 + acc_row(r, h)];
 #pragma unroll
-        for (int t = 0; t < 2; t++)
+        for (int t = 0; t < T; t++)
 #pragma unroll
             for (int r = 0; r < 16; r++)
-                o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[((t2 * 2 + t) * 16 + r) * 64 + lane], a[t][r], o[t2], 0, 0, 0);
+                o[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(w[((t2 * T + t) * 16 + r) * 64 + lane], a[t][r], o[t2], 0, 0, 0);
     }
 }
 
-// LayerNorm over the 64 features of this lane's token (32 here, 32 in the other lane half), biased variance, affine; in place
-__device__ __forceinline__ void layer_norm(f16v (&a)[2], const float *__restrict__ g, const float *__restrict__ be, int h) {
+// LayerNorm over the 32 T features of this lane's token (half here, half in the other lane half), biased variance, affine; in place
+template <int T>
+__device__ __forceinline__ void layer_norm(f16v (&a)[T], const float *__restrict__ g, const float *__restrict__ be, int h) {
     float sum = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int r = 0; r < 16; r++) sum = sum + a[t][r];
     sum = sum + __shfl_xor(sum, 32);
-    const float mean = sum * (1.f / 64.f);
+    const float mean = sum * (1.f / (32 * T));
     float sq = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             a[t][r] = a[t][r] - mean;
             sq = sq + a[t][r] * a[t][r];
         }
     sq = sq + __shfl_xor(sq, 32);
-    const float rstd = 1.f / sqrtf(sq * (1.f / 64.f) + LN_EPS);
+    const float rstd = 1.f / sqrtf(sq * (1.f / (32 * T)) + LN_EPS);
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int f = 32 * t + acc_row(r, h);
@@ -101,10 +119,11 @@ __device__ __forceinline__ void layer_norm(f16v (&a)[2], const float *__restrict
         }
 }
 
-// a token row of 64 floats (256-byte aligned) <-> the transposed tile: registers 4 q .. 4 q + 3 are 16 contiguous bytes
-__device__ __forceinline__ void load_tok(const float *__restrict__ row, f16v (&a)[2], int h) {
+// a token row of 32 T floats (128 T-byte aligned) <-> the transposed tile: registers 4 q .. 4 q + 3 are 16 contiguous bytes
+template <int T>
+__device__ __forceinline__ void load_tok(const float *__restrict__ row, f16v (&a)[T], int h) {
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const f4 v = *reinterpret_cast<const f4 *>(row + 32 * t + 8 * q + 4 * h);
@@ -113,9 +132,10 @@ __device__ __forceinline__ void load_tok(const float *__restrict__ row, f16v (&a
         }
 }
 
-__device__ __forceinline__ void store_tok(float *__restrict__ row, const f16v (&a)[2], int h) {
+template <int T>
+__device__ __forceinline__ void store_tok(float *__restrict__ row, const f16v (&a)[T], int h) {
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             f4 v;
@@ -178,6 +198,34 @@ __device__ __forceinline__ float matvec64(const float *__restrict__ wt, const fl
     return o;
 }
 
+// the same two for a workgroup of 128 threads, a thread per feature of a 128-wide token; buf is 128 floats of LDS.  Every thread
+// sums the 128 entries itself in ascending order, so every thread holds the same bits and no sum has two owners.
+__device__ __forceinline__ float block_ln128(float a, const float *__restrict__ g, const float *__restrict__ be, int tid, float *buf) {
+    buf[tid] = a;
+    __syncthreads();
+    float sum = 0.f;
+    for (int k = 0; k < 128; k++) sum = sum + buf[k];
+    const float dlt = a - sum * (1.f / 128.f);
+    __syncthreads();
+    buf[tid] = dlt * dlt;
+    __syncthreads();
+    float sq = 0.f;
+    for (int k = 0; k < 128; k++) sq = sq + buf[k];
+    __syncthreads();
+    const float rstd = 1.f / sqrtf(sq * (1.f / 128.f) + LN_EPS);
+    return (dlt * rstd) * g[tid] + be[tid];
+}
+
+// out[tid] = b[tid] + sum_k wt[k][tid] v[k], ascending k; wt is the weight transposed [in 128][out 128]
+__device__ __forceinline__ float block_matvec128(const float *__restrict__ wt, const float *__restrict__ b, float v, int tid, float *buf) {
+    buf[tid] = v;
+    __syncthreads();
+    float o = b[tid];
+    for (int k = 0; k < 128; k++) o = o + wt[k * 128 + tid] * buf[k];
+    __syncthreads();
+    return o;
+}
+
 struct BCHeadArgs {
     int head_layers, C, deterministic;
     float clip;
@@ -186,28 +234,36 @@ struct BCHeadArgs {
     int32_t *component;
 };
 
+template <int T>
 Seg self_seg(int tok0, int ntok, int w) {
+    using E = BCEnc<T>;
     Seg s{};
     s.tok0 = tok0, s.ntok = ntok, s.tiles = (ntok + 31) / 32, s.w = w;
-    s.ng = w + S_NG, s.nb = w + S_NB, s.kw = w + S_KW, s.kb = w + S_KB, s.vw = w + S_VW, s.vb = w + S_VB;
+    s.ng = w + E::S_NG, s.nb = w + E::S_NB, s.kw = w + E::S_KW, s.kb = w + E::S_KB, s.vw = w + E::S_VW, s.vb = w + E::S_VB;
     return s;
 }
 
-// the first embedder layer of a tile: gathers the token's R rows from obs (time is the slow index inside a token)
-template <int KT>
+// the first embedder layer of a tile: gathers the token's R rows from obs (time is the slow index inside a token); w0 is packed
+// [t T][s ceil(K / 2)][lane] = W[32 t + c][2 s + h]
+template <int KT, int T>
 __device__ __forceinline__ void embed_first(const float *__restrict__ x, int D, int R, int base, int e, const float *__restrict__ w0,
-                                            const float *__restrict__ b0, f16v (&a)[2], int lane, int h) {
+                                            const float *__restrict__ b0, f16v (&a)[T], int lane, int h) {
     const int kin = KT * R, ks = first_steps(kin);
 #pragma unroll
-    for (int t = 0; t < 2; t++)
+    for (int t = 0; t < T; t++)
 #pragma unroll
         for (int r = 0; r < 16; r++) a[t][r] = b0[32 * t + acc_row(r, h)];
     for (int s = 0; s < ks; s++) {
         const int k = 2 * s + h;
         const float xv = k < kin ? x[(size_t)(k / KT) * D + base + e * KT + (k % KT)] : 0.f;
 #pragma unroll
-        for (int t = 0; t < 2; t++) a[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[(t * ks + s) * 64 + lane], xv, a[t], 0, 0, 0);
+        for (int t = 0; t < T; t++) a[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[(t * ks + s) * 64 + lane], xv, a[t], 0, 0, 0);
     }
+}
+
+template <int T>
+inline BCLayout bc_layout(const gd_bc_policy &p) {
+    return bc_layout<T>(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
 }
 
 inline BCDims bc_dims(const gd_bc_policy &p) {
@@ -217,32 +273,36 @@ inline BCDims bc_dims(const gd_bc_policy &p) {
 
 // self-attention layer `layer` of the fusion_layers + branch_layers launches: a fusion layer over all L tokens, or ro_attn and
 // rg_attn layer (layer - fusion_layers) as the two segments of one launch
+template <int T>
 inline Segs bc_layer_segs(const gd_bc_policy &p, int layer) {
+    constexpr int S_SIZE = BCEnc<T>::S_SIZE;
     const int A = p.max_agents;
-    const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
+    const BCLayout L = bc_layout<T>(p);
     Segs sg{};
     if (layer < p.fusion_layers) {
-        sg.n = 1, sg.s[0] = self_seg(0, A + ROADS, L.self0 + layer * S_SIZE);
+        sg.n = 1, sg.s[0] = self_seg<T>(0, A + ROADS, L.self0 + layer * S_SIZE);
     } else {
         const int i = layer - p.fusion_layers;
         sg.n = 2;
-        sg.s[0] = self_seg(0, A, L.self0 + (p.fusion_layers + i) * S_SIZE);
-        sg.s[1] = self_seg(A, ROADS, L.self0 + (p.fusion_layers + p.branch_layers + i) * S_SIZE);
+        sg.s[0] = self_seg<T>(0, A, L.self0 + (p.fusion_layers + i) * S_SIZE);
+        sg.s[1] = self_seg<T>(A, ROADS, L.self0 + (p.fusion_layers + p.branch_layers + i) * S_SIZE);
     }
     return sg;
 }
 
 // the two cross attentions' keys and values: the kv_norm'ed partner tokens and road tokens
+template <int T>
 inline Segs bc_cross_segs(const gd_bc_policy &p) {
+    using E = BCEnc<T>;
     const int A = p.max_agents;
-    const BCLayout L = bc_layout(p.num_stack, p.fusion_layers + 2 * p.branch_layers, p.head_layers, p.n_components);
+    const BCLayout L = bc_layout<T>(p);
     Segs sg{};
     sg.n = 2;
     for (int ci = 0; ci < 2; ci++) {
         Seg &s = sg.s[ci];
-        const int w = L.cross[ci], wb = w + C_BODY;
+        const int w = L.cross[ci], wb = w + E::C_BODY;
         s.tok0 = ci ? A : 1, s.ntok = ci ? ROADS : A - 1, s.tiles = (s.ntok + 31) / 32, s.w = w;
-        s.ng = w + C_KVG, s.nb = w + C_KVB, s.kw = wb + S_KW, s.kb = wb + S_KB, s.vw = wb + S_VW, s.vb = wb + S_VB;
+        s.ng = w + E::C_KVG, s.nb = w + E::C_KVB, s.kw = wb + E::S_KW, s.kb = wb + E::S_KB, s.vw = wb + E::S_VW, s.vb = wb + E::S_VB;
     }
     return sg;
 }

@@ -1900,17 +1900,12 @@ static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, c
     if (p->chunk_rows < 1 || p->chunk_rows > 4096) return "chunk_rows must be in [1, 4096]";
     if (n < 1 || n > (1 << 20)) return "n must be in [1, 2^20]";
     if (!p->blob || !p->scratch) return "blob and scratch are required";
-    if (dim == 128) {  // gd_bc_policy_dim: the wide layout (bc_policy_wide.hip)
-        if (p->blob_floats != gd::bc_blob_floats_wide(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
-            return "blob_floats is not the layout's size at network_dim 128 for these layer counts, num_stack and n_components";
-        if (p->scratch_floats < gd::bc_scratch_floats_wide(p->max_agents, p->chunk_rows))
-            return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 128";
-    } else {
-        if (p->blob_floats != gd::bc_blob_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
-            return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
-        if (p->scratch_floats < gd::bc_scratch_floats(p->max_agents, p->chunk_rows))
-            return "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 64";
-    }
+    if (p->blob_floats != gd::bc_blob_floats(dim, p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+        return dim == 128 ? "blob_floats is not the layout's size at network_dim 128 for these layer counts, num_stack and n_components"
+                          : "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
+    if (p->scratch_floats < gd::bc_scratch_floats(dim, p->max_agents, p->chunk_rows))
+        return dim == 128 ? "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 128"
+                          : "scratch_floats is below chunk_rows * 3 * (max_agents + 200) * 64";
     if (misaligned(p->blob, 16) || misaligned(p->scratch, 256)) return "blob must be 16-byte aligned, scratch 256-byte aligned";
     if (misaligned(obs, 4) || (u && misaligned(u, 4)) || (z && misaligned(z, 4)) || (expert_actions && misaligned(expert_actions, 4)) ||
         misaligned(out->context, 4) || misaligned(out->means, 4) || misaligned(out->log_covariances, 4) ||
@@ -1926,7 +1921,7 @@ int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partne
     if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out))
         return fail(GD_ERR_INVALID, std::string("gd_bc_forward: ") + why);
     return guarded([&]() {
-        gd::launch_bc_forward(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+        gd::launch_bc_forward(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
                               expert_actions, *out);
         HIP_CHECK(hipGetLastError());
     });
@@ -1970,7 +1965,7 @@ int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t
     if (!why) why = bc_readout_problem(p, readout);
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_readout: ") + why);
     return guarded([&]() {
-        gd::launch_bc_forward(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+        gd::launch_bc_forward(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
                               expert_actions, *out, readout);
         HIP_CHECK(hipGetLastError());
     });
@@ -2041,19 +2036,11 @@ static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_
             if (r) {
                 gd::launch_live_rows(s->stream, b->dead, b->n_rows, r->rows, r->count, r->scratch,
                                      r->live_count ? r->live_count + t : nullptr, true);
-                if (dim == 128)
-                    gd::launch_bc_forward_rows_wide(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows,
-                                                    b->deterministic != 0, u, z, nullptr, out, r->rows, r->count);
-                else
-                    gd::launch_bc_forward_rows(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
-                                               u, z, nullptr, out, r->rows, r->count, rd);
+                gd::launch_bc_forward_rows(*p, dim, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
+                                           u, z, nullptr, out, r->rows, r->count, rd);
             } else {
-                if (dim == 128)
-                    gd::launch_bc_forward_wide(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0,
-                                               u, z, nullptr, out);
-                else
-                    gd::launch_bc_forward(*p, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
-                                          nullptr, out, rd, b->dead);
+                gd::launch_bc_forward(*p, dim, s->stream, b->window, b->partner_mask, b->road_mask, b->n_rows, b->deterministic != 0, u, z,
+                                      nullptr, out, rd, b->dead);
                 if (out.ego_attn_score) gd::launch_bc_rollout_score_fill(s->stream, *b, out.ego_attn_score, score_row);
             }
             gd::launch_bc_rollout_actions(s->d, s->stream, *b, t);
@@ -2303,7 +2290,7 @@ int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *p
     if (!why) why = row_list_problem(rows, count);
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows: ") + why);
     return guarded([&]() {
-        gd::launch_bc_forward_rows(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+        gd::launch_bc_forward_rows(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
                                    expert_actions, *out, rows, count);
         HIP_CHECK(hipGetLastError());
     });
@@ -2332,7 +2319,7 @@ int gd_bc_forward_rows_readout(const gd_bc_policy *p, const float *obs, const ui
     if (!why) why = row_list_problem(rows, count);
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_readout: ") + why);
     return guarded([&]() {
-        gd::launch_bc_forward_rows(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
+        gd::launch_bc_forward_rows(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
                                    expert_actions, *out, rows, count, readout);
         HIP_CHECK(hipGetLastError());
     });
@@ -2374,12 +2361,8 @@ int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t
     if (!why) why = bc_forward_problem(&p->base, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, p->network_dim);
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_dim: ") + why);
     return guarded([&]() {
-        if (p->network_dim == 128)
-            gd::launch_bc_forward_wide(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u,
-                                       z, expert_actions, *out);
-        else
-            gd::launch_bc_forward(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
-                                  expert_actions, *out);
+        gd::launch_bc_forward(p->base, p->network_dim, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0,
+                              u, z, expert_actions, *out);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -2392,12 +2375,8 @@ int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const ui
     if (!why) why = row_list_problem(rows, count);
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_dim: ") + why);
     return guarded([&]() {
-        if (p->network_dim == 128)
-            gd::launch_bc_forward_rows_wide(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n,
-                                            deterministic != 0, u, z, expert_actions, *out, rows, count);
-        else
-            gd::launch_bc_forward_rows(p->base, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u,
-                                       z, expert_actions, *out, rows, count);
+        gd::launch_bc_forward_rows(p->base, p->network_dim, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n,
+                                   deterministic != 0, u, z, expert_actions, *out, rows, count);
         HIP_CHECK(hipGetLastError());
     });
 }
@@ -2499,7 +2478,7 @@ static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
     if (o->reserved != 0) return "reserved must be 0";
     if (o->grad_floats != gd::bc_grad_floats(o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
         return "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
-    if (o->blob_floats != gd::bc_blob_floats(o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+    if (o->blob_floats != gd::bc_blob_floats(64, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
         return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
     if (o->num_tensors != gd::bc_num_tensors(o->fusion_layers, o->branch_layers, o->head_layers))
         return "num_tensors is not the state dict's tensor count for these layer counts";
@@ -2549,7 +2528,7 @@ int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *op
     if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_update: ") + why);
     return guarded([&]() {
         hipStream_t st = static_cast<hipStream_t>(stream);
-        gd::launch_bc_forward(*p, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
+        gd::launch_bc_forward(*p, 64, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
         gd::launch_bc_train_rows(o, st, n, o.nll, o.actions, expert_actions, o.grad_nll);
         gd::launch_bc_backward(*p, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
         gd::launch_bc_adamw(o, st, o.grad);

@@ -328,26 +328,18 @@ void launch_ppo_loss(const gd_ppo &o, hipStream_t st, const float *newlogprob, c
                      const float *old_logprob, const float *old_value, const float *adv, const float *ret, float *d_logprob,
                      float *d_entropy, float *d_value);  // ppo.hip (one launch)
 void launch_ppo_adam(const gd_ppo &o, hipStream_t st, const float *grad);  // ppo.hip (two launches)
-long long bc_blob_floats(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);  // bc_policy.hip
-long long bc_scratch_floats(int max_agents, int chunk_rows);  // bc_policy.hip: the size of gd_bc_policy.scratch
-void launch_bc_forward(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+// bc_policy.hip.  dim: network_dim, 64 or 128 (gd_bc_policy_dim); the read-outs exist at 64 only
+long long bc_blob_floats(int dim, int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);
+long long bc_scratch_floats(int dim, int max_agents, int chunk_rows);  // the size of gd_bc_policy.scratch
+void launch_bc_forward(const gd_bc_policy &p, int dim, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                        const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                        const float *expert_actions, const gd_bc_outputs &out, const gd_bc_readout *readout = nullptr,
-                       const unsigned char *dead = nullptr);  // bc_policy.hip
+                       const unsigned char *dead = nullptr);
 // the forward on a device-resident row list: every chunk of list positions is launched, scratch by position, the rest by row
-void launch_bc_forward_rows(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
+void launch_bc_forward_rows(const gd_bc_policy &p, int dim, hipStream_t st, const float *obs, const unsigned char *partner_mask,
                             const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
                             const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows,
-                            const int32_t *count, const gd_bc_readout *readout = nullptr);  // bc_policy.hip
-// bc_policy_wide.hip: the same forward at network_dim = 128 (gd_bc_policy_dim); no read-outs there
-long long bc_blob_floats_wide(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);
-long long bc_scratch_floats_wide(int max_agents, int chunk_rows);
-void launch_bc_forward_wide(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
-                            const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
-                            const float *expert_actions, const gd_bc_outputs &out);
-void launch_bc_forward_rows_wide(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *partner_mask,
-                                 const unsigned char *road_mask, int n, bool deterministic, const float *u, const float *z,
-                                 const float *expert_actions, const gd_bc_outputs &out, const int32_t *rows, const int32_t *count);
+                            const int32_t *count, const gd_bc_readout *readout = nullptr);
 // bc_readout.hip: the probe read-outs of one chunk, launched by the two forwards above right after self layer
 // bc_tap_layer(p, readout->tap, readout->layer) when `readout` is given (one launch).  dead: rows whose byte is set are dropped
 int bc_tap_layer(const gd_bc_policy &p, int tap, int layer);

@@ -8,7 +8,7 @@
 //   k_lp_rows     grid (num_partials), one wave each.  Workgroup w takes the tiles w, w + num_partials, .. of the chunk in
 //                 ascending order.  A tile is 32 rows: for 'other' the partner columns 32 i .. 32 i + 31 of one sample, which are
 //                 the tokens 1 + column (one off the 32-token tiles the attention kernel wrote, and the last tile holds 31 rows:
-//                 A - 1 is 63 or 127), for 'ego' token 0 of 32 consecutive samples.  Logits by bc_tile.hpp's linear64 from the
+//                 A - 1 is 63 or 127), for 'ego' token 0 of 32 consecutive samples.  Logits by bc_tile.hpp's linear from the
 //                 probe's packed weights; the tile of logits goes through LDS so that a lane owns a whole row for the row rule;
 //                 g and x (zeros for a row that is not selected) go through LDS again as the operands of the gradient's MFMA
 //                 chain over the rows, whose accumulators start from the workgroup's partial and return to it after its last
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(64) void k_lp_rows(LPArgs a) {
         } else {
             load_tok(a.X + ((size_t)b * a.L + (other ? 1 + j : 0)) * F, x, h);
         }
-        linear64(x, a.packed, a.packed + W64, z, lane, h);
+        linear(x, a.packed, a.packed + W64, z, lane, h);
         if (a.logits && live) store_tok(a.logits + gr * F, z, h);
 
         __syncthreads();  // the tile before this one has been read

@@ -1140,8 +1140,8 @@ typedef struct gd_bc_policy_dim {
     int32_t reserved;     /* 0 */
 } gd_bc_policy_dim;
 /* gd_bc_forward and gd_bc_forward_rows at p->network_dim: the same arguments, checks and guarantees; out->context is
- * [n][3 * network_dim].  At 64 they run gd_bc_forward's (gd_bc_forward_rows') own kernels and give its bits.  At 128: the wide
- * kernels (csrc/bc_policy_wide.hip), 2 fusion_layers + 2 branch_layers + 3 launches per chunk as at 64, no host synchronisation, no
+ * [n][3 * network_dim].  At 64 they run gd_bc_forward's (gd_bc_forward_rows') own kernels and give its bits.  At 128: the same
+ * kernels at T = 4 (csrc/bc_policy.hip), 2 fusion_layers + 2 branch_layers + 3 launches per chunk as at 64, no host synchronisation, no
  * allocation, no atomics.  GD_ERR_INVALID, before any launch: whatever those refuse, a network_dim other than 64 or 128,
  * reserved != 0, blob_floats or scratch_floats not that width's. */
 int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,

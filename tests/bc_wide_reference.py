@@ -1,5 +1,5 @@
 """The BC policy restated in float64 numpy with the encoder's width as a parameter: what the 128-wide forward
-(gd_bc_forward_dim, csrc/bc_policy_wide.hip) is held to.  tests/bc_reference.py fixes DIM = 64; this is the same restatement,
+(gd_bc_forward_dim, csrc/bc_policy.hip at T = 4) is held to.  tests/bc_reference.py fixes DIM = 64; this is the same restatement,
 in this repository's own words, for `network_dim` D and head_dim 64: every embedder, LayerNorm and attention Linear is D wide,
 the 4 heads have D / 4 channels and q is scaled by (D / 4)^-1/2, the context is 3 D wide, and the GMM head behind
 head.input_layer (3 D -> 64) is as at 64.  tests/test_bc_wide.py pins it to the reference module itself at D = 128

@@ -74,7 +74,7 @@ def test_the_comparison_catches_each_wide_mistake(wrong, name, output):
         assert np.array_equal(bad["context"], c["ref"]["context"])
 
 
-# ---- the blob at 128: an emulation of what the wide kernels read (csrc/bc_tile_wide.hpp), written out again here
+# ---- the blob at 128: an emulation of what the kernels read at T = 4 (csrc/bc_tile.hpp), written out again here
 
 FW, T, F = 128, 4, 64
 LANE = np.arange(64)
@@ -108,7 +108,7 @@ class Blob:
         return W[:, :kin]
 
     def mfma(self):
-        """linear128: the A operand of k-step (t, r) for output tile t2 is w[((t2 4 + t) 16 + r) 64 + lane]."""
+        """linear at T = 4: the A operand of k-step (t, r) for output tile t2 is w[((t2 4 + t) 16 + r) 64 + lane]."""
         w = self.nat(FW * FW)
         W = np.full((FW, FW), np.nan)
         for t2 in range(T):

@@ -1,5 +1,5 @@
 """GPU suite: the BC policy forward and the closed-loop driver at network_dim = 128 (gd_bc_forward_dim, gd_bc_forward_rows_dim,
-gd_bc_rollout_dim; csrc/bc_policy_wide.hip) against the float64 restatement with the width as a parameter
+gd_bc_rollout_dim; csrc/bc_policy.hip at T = 4) against the float64 restatement with the width as a parameter
 (tests/bc_wide_reference.py, pinned to the reference module by tests/test_bc_wide.py) on the cases of tests/bc_wide_cases.py.
 
 context, means, clamped raw covariances, weights, NLL and ego_attn_score: the yardstick E of a case and an output is the maximum

@@ -2,7 +2,7 @@
 """developer tool: the BC forward at network_dim = 128 against eager torch and against the 64-wide forward.
 
 B = 512, A = 128, R = 5, num_layer (4, 3), head 2, C = 6 (the reference sweep's model), synthetic observations, 40 % padding.
-    (a) the wide `DeviceBCPolicy` forward with out= (gd_bc_forward_dim, csrc/bc_policy_wide.hip)
+    (a) the wide `DeviceBCPolicy` forward with out= (gd_bc_forward_dim, csrc/bc_policy.hip at T = 4)
     (b) the eager float32 stand-in at 128 on the same GPU, same weights and inputs (tests/bc_wide_cases.WideStandIn)
     (c) the 64-wide `DeviceBCPolicy` forward at the same layer counts, for scale
 Device events around 10 calls after a warm-up of 3, three runs of each in alternation; peak allocated memory of (a) and (b) from
