@@ -88,8 +88,7 @@ class DeviceBC:
         amsgrad, `clip_grad_norm_(max_grad_norm)`.  partials, chunk_rows: `TrainableBCPolicy`'s (None: 128 partial
         gradients).  Everything is allocated here, once (`nbytes`).  Anything not built is a ValueError raised before anything
         reaches the device."""
-        unknown = sorted(set(fixed) - {"network_dim", "head_dim", "network_num_layers", "act_func", "dropout", "action_dim",
-                                       "time_dim", "use_tom"})
+        unknown = sorted(set(fixed) - BP.FIXED)
         if unknown:
             raise ValueError(WHO + "unknown argument(s) %s" % ", ".join(unknown))
         num_layer = tuple(num_layer) if isinstance(num_layer, list) else num_layer

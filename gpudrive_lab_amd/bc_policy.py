@@ -66,6 +66,8 @@ DEFAULT_CHUNK = 128
 MAX_CHUNK = 4096
 EVAL_NAMES = ("test_loss", "dx_loss", "dy_loss", "dyaw_loss", "dx_std2_loss", "dy_std2_loss", "dyaw_std2_loss", "tom_loss")
 WHO = "DeviceBCPolicy: "
+# the reference module's keyword arguments that are accepted only at the values that are built (`check_bc_args`)
+FIXED = frozenset(("network_dim", "head_dim", "network_num_layers", "act_func", "dropout", "action_dim", "time_dim", "use_tom"))
 
 
 def _is_int(v):
@@ -276,8 +278,7 @@ class DeviceBCPolicy:
         the rows the scratch holds (1..4096).  fixed: network_dim, head_dim, network_num_layers, act_func, dropout, action_dim,
         time_dim, use_tom, accepted only at the values that are built (64 or 128, 64, 4, 'tanh', 0.0, 3, 1, None).  Anything else, a
         missing or extra key, a wrong shape or dtype is a ValueError raised before anything reaches the device."""
-        unknown = sorted(set(fixed) - {"network_dim", "head_dim", "network_num_layers", "act_func", "dropout", "action_dim",
-                                       "time_dim", "use_tom"})
+        unknown = sorted(set(fixed) - FIXED)
         if unknown:
             raise ValueError(WHO + "unknown argument(s) %s" % ", ".join(unknown))
         num_layer = tuple(num_layer) if isinstance(num_layer, list) else num_layer
@@ -421,31 +422,21 @@ class DeviceBCPolicy:
                 res[name] = torch.empty(shape, dtype=dt, device=self.device)
         for name, t in res.items():
             setattr(o, name, t.data_ptr())
+        # The entry, chosen once: gd_bc_forward[_rows][_readout], or gd_bc_forward[_rows]_dim for the wide policy (the 64-wide
+        # policy keeps the entry points it had; gd_bc_*_dim at 64 are those, bit for bit).  The tail follows the name.
         wide = self.network_dim != DIM
+        entry = "gd_bc_forward" + ("_rows" if rows is not None else "") + ("_dim" if wide else "_readout" if ro is not None else "")
         p = self.c_struct_dim() if wide else self.c_struct()
+        tail = ([] if ro is None else [C.byref(ro)]) + ([] if rows is None else [rows.rows.data_ptr(), rows.count.data_ptr()])
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            args = (C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, int(deterministic),
-                    None if u is None else u.data_ptr(), None if z is None else z.data_ptr(),
-                    None if expert_actions is None else expert_actions.data_ptr(), C.byref(o))
-            if wide:  # the 64-wide policy keeps the entry points it had; gd_bc_*_dim at 64 are those, bit for bit
-                if rows is not None:
-                    _capi.check(self._L.gd_bc_forward_rows_dim(*args, rows.rows.data_ptr(), rows.count.data_ptr(), stream),
-                                "gd_bc_forward_rows_dim")
-                else:
-                    _capi.check(self._L.gd_bc_forward_dim(*args, stream), "gd_bc_forward_dim")
-            elif ro is not None:
-                if rows is not None:
-                    _capi.check(self._L.gd_bc_forward_rows_readout(*args, C.byref(ro), rows.rows.data_ptr(), rows.count.data_ptr(),
-                                                                   stream), "gd_bc_forward_rows_readout")
-                else:
-                    _capi.check(self._L.gd_bc_forward_readout(*args, C.byref(ro), stream), "gd_bc_forward_readout")
-                res.update(ro_res)
-            elif rows is not None:
-                _capi.check(self._L.gd_bc_forward_rows(*args, rows.rows.data_ptr(), rows.count.data_ptr(), stream),
-                            "gd_bc_forward_rows")
-            else:
-                _capi.check(self._L.gd_bc_forward(*args, stream), "gd_bc_forward")
+            _capi.check(getattr(self._L, entry)(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
+                                                int(deterministic), None if u is None else u.data_ptr(),
+                                                None if z is None else z.data_ptr(),
+                                                None if expert_actions is None else expert_actions.data_ptr(), C.byref(o), *tail,
+                                                stream), entry)
+        if ro is not None:
+            res.update(ro_res)
         return res
 
     def read(self, obs, partner_mask, road_mask, readout, deterministic=True, u=None, z=None, rows=None, out=None):

@@ -226,15 +226,6 @@ class ClosedLoopBC:
         self.sim.set_maps(scenes)
         self._set_rows(self.mask if self._explicit else None)
 
-    def _policy_struct(self):
-        pol = self.policy
-        p = _capi.GdBCPolicy()
-        p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = pol.max_agents, pol.num_stack, *pol.num_layer
-        p.head_layers, p.n_components, p.clip_value, p.chunk_rows = pol.head_num_layers, pol.n_components, pol.clip_value, pol.chunk_rows
-        p.blob, p.blob_floats = pol.blob.data_ptr(), pol.blob.numel()
-        p.scratch, p.scratch_floats = pol._scratch.data_ptr(), pol._scratch.numel()
-        return p
-
     @staticmethod
     def _new(name, shape, dtype, fill, device):
         """Every array of a run is made here (fill None: need not be initialised)."""
@@ -305,7 +296,7 @@ class ClosedLoopBC:
                 ro, _ = readout.bind((T, n), filled, who=WHO)
                 out.update(filled)
                 reads.readout = C.pointer(ro)
-        p = self._policy_struct()
+        r = None
         if compact:
             from .policy import LiveRows
             out["live_rows"] = lr = LiveRows(n, dev, new=self._new)  # (kept with the episode: the call is still running)
@@ -315,17 +306,13 @@ class ClosedLoopBC:
             r.live_count = out["live_count"].data_ptr()
         sim.reset(list(range(sim._W)))
         sim._bind_stream()
-        if pol.network_dim != 64:  # the wide forward in the same loop (a 64-wide policy keeps the entry points it had)
-            pd = pol.c_struct_dim()
-            _capi.check(sim._L.gd_bc_rollout_dim(sim._h, C.byref(pd), C.byref(b), C.byref(r) if compact else None,
-                                                 None if reads is None else C.byref(reads), n_steps), "gd_bc_rollout_dim")
-        elif reads is not None:
-            _capi.check(sim._L.gd_bc_rollout_readout(sim._h, C.byref(p), C.byref(b), C.byref(r) if compact else None,
-                                                     C.byref(reads), n_steps), "gd_bc_rollout_readout")
-        elif compact:
-            _capi.check(sim._L.gd_bc_rollout_compact(sim._h, C.byref(p), C.byref(b), C.byref(r), n_steps), "gd_bc_rollout_compact")
-        else:
-            _capi.check(sim._L.gd_bc_rollout(sim._h, C.byref(p), C.byref(b), n_steps), "gd_bc_rollout")
+        # The entry and how much of (list, reads) it takes, chosen once.  A 64-wide policy keeps the entry points it had.
+        wide = pol.network_dim != 64
+        entry, takes = (("gd_bc_rollout_dim", 2) if wide else ("gd_bc_rollout_readout", 2) if reads is not None
+                        else ("gd_bc_rollout_compact", 1) if compact else ("gd_bc_rollout", 0))
+        p = pol.c_struct_dim() if wide else pol.c_struct()
+        tail = (None if r is None else C.byref(r), None if reads is None else C.byref(reads))[:takes]
+        _capi.check(getattr(sim._L, entry)(sim._h, C.byref(p), C.byref(b), *tail, n_steps), entry)
         sim._after()
         out["dead"] = out["dead"].view(torch.bool)
         if attention:

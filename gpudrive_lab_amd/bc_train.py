@@ -105,8 +105,7 @@ class TrainableBCPolicy(nn.Module):
         128 times the parameters, about 150 MB, allocated at the first forward and kept).  The sums are deterministic for a
         given P and chunk_rows."""
         super().__init__()
-        unknown = sorted(set(fixed) - {"network_dim", "head_dim", "network_num_layers", "act_func", "dropout", "action_dim",
-                                       "time_dim", "use_tom"})
+        unknown = sorted(set(fixed) - BP.FIXED)
         if unknown:
             raise ValueError(WHO + "unknown argument(s) %s" % ", ".join(unknown))
         num_layer = tuple(num_layer) if isinstance(num_layer, list) else num_layer

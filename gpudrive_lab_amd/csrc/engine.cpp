@@ -1883,10 +1883,27 @@ int gd_ppo_update_dropout(const gd_policy *p, const gd_policy_grad *g, const gd_
     });
 }
 
-// everything gd_bc_forward refuses; nullptr when everything is in order
+// everything the calls that take a row list refuse of it; nullptr when everything is in order
+static const char *row_list_problem(const int32_t *rows, const int32_t *count) {
+    if (!rows || !count) return "rows and count are required";
+    if (misaligned(rows, 4) || misaligned(count, 4)) return "rows and count must be 4-byte aligned";
+    return nullptr;
+}
+
+// everything the closed loops refuse of their list of live rows (gd_bc_rollout_rows, gd_policy_rollout_rows: the same fields)
+static const char *rollout_rows_problem(const int32_t *rows, const int32_t *count, const int32_t *scratch, const int32_t *live_count,
+                                        int32_t reserved) {
+    if (const char *why = row_list_problem(rows, count)) return why;
+    if (!scratch || misaligned(scratch, 4)) return "scratch is required and must be 4-byte aligned";
+    if (misaligned(live_count, 4)) return "live_count must be 4-byte aligned";
+    if (reserved != 0) return "the row list's reserved must be 0";
+    return nullptr;
+}
+
+// everything the BC forward refuses at network_dim dim (64 or 128), whoever calls it; nullptr when everything is in order
 static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
                                       int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
-                                      const gd_bc_outputs *out, int dim = 64) {
+                                      const gd_bc_outputs *out, int dim) {
     if (!p || !obs || !partner_mask || !road_mask || !out) return "null argument";
     if (!deterministic && (!u || !z)) return "u and z are required unless deterministic";
     if (out->nll && !expert_actions) return "expert_actions is required with out->nll";
@@ -1915,19 +1932,7 @@ static const char *bc_forward_problem(const gd_bc_policy *p, const float *obs, c
     return nullptr;
 }
 
-int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
-                  int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
-                  void *stream) {
-    if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out))
-        return fail(GD_ERR_INVALID, std::string("gd_bc_forward: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_forward(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
-                              expert_actions, *out);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// everything of a gd_bc_readout that gd_bc_forward_readout refuses (the policy has passed bc_forward_problem); nullptr when
+// everything of a gd_bc_readout that the entries with one refuse (the policy has passed bc_forward_problem); nullptr when
 // everything is in order
 static const char *bc_readout_problem(const gd_bc_policy *p, const gd_bc_readout *r) {
     if (!r) return "readout is required";
@@ -1958,24 +1963,98 @@ static const char *bc_readout_problem(const gd_bc_policy *p, const gd_bc_readout
     return nullptr;
 }
 
-int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
-                          int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
-                          const gd_bc_readout *readout, void *stream) {
-    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
-    if (!why) why = bc_readout_problem(p, readout);
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_readout: ") + why);
+// what the *_dim entry points refuse of the struct itself, before its base is looked at; nullptr when it is in order
+static const char *bc_dim_problem(const gd_bc_policy_dim *p) {
+    if (!p) return "null argument";
+    if (p->network_dim != 64 && p->network_dim != 128) return "network_dim must be 64 or 128";
+    if (p->reserved != 0) return "reserved must be 0";
+    return nullptr;
+}
+
+// The policy and the width an entry runs at: a gd_bc_policy is 64 wide, a gd_bc_policy_dim says its own.  why: bc_dim_problem's
+// answer, with which dim is not to be used; p is NULL only where the entry's own argument is.
+struct BCAt {
+    const gd_bc_policy *p;
+    int dim;
+    const char *why;
+};
+static BCAt bc_at(const gd_bc_policy *p) { return {p, 64, nullptr}; }
+static BCAt bc_at(const gd_bc_policy_dim *p) { return {p ? &p->base : nullptr, p ? p->network_dim : 0, bc_dim_problem(p)}; }
+
+// what an entry takes beside the arguments every entry of its family has
+enum { BC_READOUT = 1, BC_ROWS = 2 };
+
+// The one checked forward behind the six gd_bc_forward* entries.  takes: the read-out and / or the row list, which the entry
+// then requires (their own checks refuse a NULL); an entry that takes none passes none.  The order of refusal is every entry's:
+// the _dim struct, the policy and the buffers at its width, the read-out, the row list.
+static int bc_forward(const char *who, int takes, BCAt at, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                      int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                      const gd_bc_outputs *out, const gd_bc_readout *readout, const int32_t *rows, const int32_t *count, void *stream) {
+    const char *why = at.why;
+    if (!why) why = bc_forward_problem(at.p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, at.dim);
+    if (!why && (takes & BC_READOUT)) why = bc_readout_problem(at.p, readout);
+    if (!why && (takes & BC_ROWS)) why = row_list_problem(rows, count);
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     return guarded([&]() {
-        gd::launch_bc_forward(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
-                              expert_actions, *out, readout);
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (takes & BC_ROWS)
+            gd::launch_bc_forward_rows(*at.p, at.dim, st, obs, partner_mask, road_mask, n, deterministic != 0, u, z, expert_actions, *out,
+                                       rows, count, readout);
+        else
+            gd::launch_bc_forward(*at.p, at.dim, st, obs, partner_mask, road_mask, n, deterministic != 0, u, z, expert_actions, *out,
+                                  readout);
         HIP_CHECK(hipGetLastError());
     });
 }
 
-// everything gd_bc_rollout refuses, for gd_bc_rollout_compact too; GD_OK when everything is in order
+int gd_bc_forward(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                  int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                  void *stream) {
+    return bc_forward("gd_bc_forward", 0, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, nullptr,
+                      nullptr, nullptr, stream);
+}
+
+int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                       int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                       const int32_t *rows, const int32_t *count, void *stream) {
+    return bc_forward("gd_bc_forward_rows", BC_ROWS, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out,
+                      nullptr, rows, count, stream);
+}
+
+int gd_bc_forward_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                          int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                          const gd_bc_readout *readout, void *stream) {
+    return bc_forward("gd_bc_forward_readout", BC_READOUT, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z,
+                      expert_actions, out, readout, nullptr, nullptr, stream);
+}
+
+int gd_bc_forward_rows_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                               int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                               const gd_bc_outputs *out, const gd_bc_readout *readout, const int32_t *rows, const int32_t *count,
+                               void *stream) {
+    return bc_forward("gd_bc_forward_rows_readout", BC_READOUT | BC_ROWS, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z,
+                      expert_actions, out, readout, rows, count, stream);
+}
+
+int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
+                      int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
+                      void *stream) {
+    return bc_forward("gd_bc_forward_dim", 0, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out,
+                      nullptr, nullptr, nullptr, stream);
+}
+
+int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                           int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
+                           const gd_bc_outputs *out, const int32_t *rows, const int32_t *count, void *stream) {
+    return bc_forward("gd_bc_forward_rows_dim", BC_ROWS, bc_at(p), obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions,
+                      out, nullptr, rows, count, stream);
+}
+
+// everything the closed loop refuses of the simulator, the buffers and the policy at network_dim dim (none of them NULL); GD_OK
+// when everything is in order
 static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps,
-                              int dim = 64) {
+                              int dim) {
     const std::string w = std::string(who) + ": ";
-    if (!s || !p || !b) return fail(GD_ERR_INVALID, w + "null argument");
     if (!b->row_slot || !b->row_of_slot || !b->window || !b->partner_mask || !b->road_mask || !b->partner_value || !b->row_actions ||
         !b->dead || !b->goal_achieved || !b->off_road || !b->veh_collision || !b->goal_step || !b->off_road_step ||
         !b->init_goal_dist || !b->goal_dist || !b->any_alive || !b->summary)
@@ -2002,14 +2081,14 @@ static int bc_rollout_problem(const char *who, gd_sim *s, const gd_bc_policy *p,
     return GD_OK;
 }
 
-// The loop of both drivers (bc_rollout.hip): r == nullptr is gd_bc_rollout's forward on all N rows, otherwise the list of the
-// rows with dead[n] == 0 in the loop.  When iteration t does not exist every row is dead: the list is empty and every
-// workgroup of the forward returns at its first load.
-// x (gd_bc_rollout_readout): step t's forward also writes the step's slices of the read-outs; without the list the read-out
-// kernel drops dead rows itself and one more launch zeroes the scores the head kernel stored for them.
-// dim == 128 (gd_bc_rollout_dim): the wide forward in the same loop; there is no read-out at that width.
+// The loop of every driver (bc_rollout.hip): r == nullptr is the forward on all N rows, otherwise the list of the rows with
+// dead[n] == 0 in the loop.  When iteration t does not exist every row is dead: the list is empty and every workgroup of the
+// forward returns at its first load.
+// x: step t's forward also writes the step's slices of the read-outs; without the list the read-out kernel drops dead rows
+// itself and one more launch zeroes the scores the head kernel stored for them.
+// dim == 128: the wide forward in the same loop; there is no read-out at that width.
 static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                          int32_t n_steps, const gd_bc_rollout_reads *x = nullptr, int dim = 64) {
+                          int32_t n_steps, const gd_bc_rollout_reads *x, int dim) {
     return guarded([&]() {
         const size_t N = static_cast<size_t>(b->n_rows);
         gd_bc_outputs out{};
@@ -2054,10 +2133,47 @@ static int bc_rollout_run(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_
     });
 }
 
+// The one checked loop behind the four gd_bc_rollout* entries.  takes: the list (r) and / or the reads (x) the entry refuses to
+// go without; both are optional otherwise.  What needs no simulator is checked first: the _dim struct, the list, the reads.
+static int bc_rollout(const char *who, int takes, gd_sim *s, BCAt at, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                      const gd_bc_rollout_reads *x, int32_t n_steps) {
+    const std::string w = std::string(who) + ": ";
+    if (!s || !at.p || !b || ((takes & BC_ROWS) && !r) || ((takes & BC_READOUT) && !x))
+        return fail(GD_ERR_INVALID, w + "null argument");
+    const char *why = at.why;
+    if (!why && r) why = rollout_rows_problem(r->rows, r->count, r->scratch, r->live_count, r->reserved);
+    if (!why && x && !x->ego_attn_score && !x->readout) why = "reads needs ego_attn_score or readout";
+    if (!why && x && misaligned(x->ego_attn_score, 4)) why = "ego_attn_score must be 4-byte aligned";
+    if (!why && x && x->readout && at.dim != 64)
+        why = "reads->readout must be NULL unless network_dim is 64 (the probes read 64-wide tokens)";
+    if (why) return fail(GD_ERR_INVALID, w + why);
+    if (const int rc = bc_rollout_problem(who, s, at.p, b, n_steps, at.dim)) return rc;
+    if (x && x->readout)
+        if (const char *bad = bc_readout_problem(at.p, x->readout)) return fail(GD_ERR_INVALID, w + bad);
+    return bc_rollout_run(s, at.p, b, r, n_steps, x, at.dim);
+}
+
 // The closed-loop episode: gd_record_expert's loop with the policy where the logged action was.
 int gd_bc_rollout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, int32_t n_steps) {
-    if (const int rc = bc_rollout_problem("gd_bc_rollout", s, p, b, n_steps)) return rc;
-    return bc_rollout_run(s, p, b, nullptr, n_steps);
+    return bc_rollout("gd_bc_rollout", 0, s, bc_at(p), b, nullptr, nullptr, n_steps);
+}
+
+// gd_bc_rollout with the list of live rows and gd_bc_forward_rows in the loop.
+int gd_bc_rollout_compact(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                          int32_t n_steps) {
+    return bc_rollout("gd_bc_rollout_compact", BC_ROWS, s, bc_at(p), b, r, nullptr, n_steps);
+}
+
+// gd_bc_rollout (r == nullptr) or gd_bc_rollout_compact with the read-outs in the loop.
+int gd_bc_rollout_readout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                          const gd_bc_rollout_reads *x, int32_t n_steps) {
+    return bc_rollout("gd_bc_rollout_readout", BC_READOUT, s, bc_at(p), b, r, x, n_steps);
+}
+
+// gd_bc_rollout, gd_bc_rollout_compact (r) or gd_bc_rollout_readout (x) at the policy's width.
+int gd_bc_rollout_dim(gd_sim *s, const gd_bc_policy_dim *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
+                      const gd_bc_rollout_reads *x, int32_t n_steps) {
+    return bc_rollout("gd_bc_rollout_dim", 0, s, bc_at(p), b, r, x, n_steps);
 }
 
 // everything gd_policy_rollout refuses, for gd_policy_rollout_compact too; GD_OK when everything is in order
@@ -2130,13 +2246,6 @@ int gd_policy_rollout(gd_sim *s, const gd_policy *p, const gd_policy_rollout_buf
     return policy_rollout_run(s, p, b, nullptr, n_steps);
 }
 
-// everything the calls that take a row list refuse of it; nullptr when everything is in order
-static const char *row_list_problem(const int32_t *rows, const int32_t *count) {
-    if (!rows || !count) return "rows and count are required";
-    if (misaligned(rows, 4) || misaligned(count, 4)) return "rows and count must be 4-byte aligned";
-    return nullptr;
-}
-
 int gd_live_rows(const uint8_t *mask, int32_t n, int32_t *rows, int32_t *count, int32_t *scratch, void *stream) {
     if (!mask || !scratch) return fail(GD_ERR_INVALID, "gd_live_rows: null argument");
     if (const char *why = row_list_problem(rows, count)) return fail(GD_ERR_INVALID, std::string("gd_live_rows: ") + why);
@@ -2167,11 +2276,7 @@ int gd_policy_rollout_compact(gd_sim *s, const gd_policy *p, const gd_policy_rol
                               int32_t n_steps) {
     const char *who = "gd_policy_rollout_compact";
     if (!s || !p || !b || !r) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
-    const char *why = row_list_problem(r->rows, r->count);
-    if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
-    if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
-    if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
-    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    if (const char *why = rollout_rows_problem(r->rows, r->count, r->scratch, r->live_count, r->reserved)) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     if (const int rc = policy_rollout_problem(who, s, p, b, n_steps)) return rc;
     return policy_rollout_run(s, p, b, r, n_steps);
 }
@@ -2283,128 +2388,6 @@ int gd_multi_policy_rollout(gd_sim *s, const gd_policy_set *set, const gd_policy
     });
 }
 
-int gd_bc_forward_rows(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
-                       int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
-                       const int32_t *rows, const int32_t *count, void *stream) {
-    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
-    if (!why) why = row_list_problem(rows, count);
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_forward_rows(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
-                                   expert_actions, *out, rows, count);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// gd_bc_rollout with the list of live rows and gd_bc_forward_rows in the loop.  The list is checked first: it needs no simulator.
-int gd_bc_rollout_compact(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                          int32_t n_steps) {
-    const char *who = "gd_bc_rollout_compact";
-    if (!s || !p || !b || !r) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
-    const char *why = row_list_problem(r->rows, r->count);
-    if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
-    if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
-    if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
-    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
-    if (const int rc = bc_rollout_problem(who, s, p, b, n_steps)) return rc;
-    return bc_rollout_run(s, p, b, r, n_steps);
-}
-
-int gd_bc_forward_rows_readout(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
-                               int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
-                               const gd_bc_outputs *out, const gd_bc_readout *readout, const int32_t *rows, const int32_t *count,
-                               void *stream) {
-    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out);
-    if (!why) why = bc_readout_problem(p, readout);
-    if (!why) why = row_list_problem(rows, count);
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_readout: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_forward_rows(*p, 64, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0, u, z,
-                                   expert_actions, *out, rows, count, readout);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// gd_bc_rollout (r == nullptr) or gd_bc_rollout_compact with the read-outs in the loop.  What needs no simulator is checked first.
-int gd_bc_rollout_readout(gd_sim *s, const gd_bc_policy *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                          const gd_bc_rollout_reads *x, int32_t n_steps) {
-    const char *who = "gd_bc_rollout_readout";
-    if (!s || !p || !b || !x) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
-    const char *why = nullptr;
-    if (r) {
-        why = row_list_problem(r->rows, r->count);
-        if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
-        if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
-        if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
-    }
-    if (!why && !x->ego_attn_score && !x->readout) why = "reads needs ego_attn_score or readout";
-    if (!why && misaligned(x->ego_attn_score, 4)) why = "ego_attn_score must be 4-byte aligned";
-    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
-    if (const int rc = bc_rollout_problem(who, s, p, b, n_steps)) return rc;
-    if (x->readout)
-        if (const char *bad = bc_readout_problem(p, x->readout)) return fail(GD_ERR_INVALID, std::string(who) + ": " + bad);
-    return bc_rollout_run(s, p, b, r, n_steps, x);
-}
-
-// what the *_dim entry points refuse of the struct itself, before its base is looked at; nullptr when it is in order
-static const char *bc_dim_problem(const gd_bc_policy_dim *p) {
-    if (!p) return "null argument";
-    if (p->network_dim != 64 && p->network_dim != 128) return "network_dim must be 64 or 128";
-    if (p->reserved != 0) return "reserved must be 0";
-    return nullptr;
-}
-
-int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
-                      int32_t deterministic, const float *u, const float *z, const float *expert_actions, const gd_bc_outputs *out,
-                      void *stream) {
-    const char *why = bc_dim_problem(p);
-    if (!why) why = bc_forward_problem(&p->base, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, p->network_dim);
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_dim: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_forward(p->base, p->network_dim, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, deterministic != 0,
-                              u, z, expert_actions, *out);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
-                           int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
-                           const gd_bc_outputs *out, const int32_t *rows, const int32_t *count, void *stream) {
-    const char *why = bc_dim_problem(p);
-    if (!why) why = bc_forward_problem(&p->base, obs, partner_mask, road_mask, n, deterministic, u, z, expert_actions, out, p->network_dim);
-    if (!why) why = row_list_problem(rows, count);
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_forward_rows_dim: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_forward_rows(p->base, p->network_dim, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n,
-                                   deterministic != 0, u, z, expert_actions, *out, rows, count);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// gd_bc_rollout, gd_bc_rollout_compact (r) or gd_bc_rollout_readout (x) at the policy's width.  What needs no simulator first.
-int gd_bc_rollout_dim(gd_sim *s, const gd_bc_policy_dim *p, const gd_bc_rollout_buffers *b, const gd_bc_rollout_rows *r,
-                      const gd_bc_rollout_reads *x, int32_t n_steps) {
-    const char *who = "gd_bc_rollout_dim";
-    if (!s || !p || !b) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
-    const char *why = bc_dim_problem(p);
-    if (!why && r) {
-        why = row_list_problem(r->rows, r->count);
-        if (!why && (!r->scratch || misaligned(r->scratch, 4))) why = "scratch is required and must be 4-byte aligned";
-        if (!why && misaligned(r->live_count, 4)) why = "live_count must be 4-byte aligned";
-        if (!why && r->reserved != 0) why = "the row list's reserved must be 0";
-    }
-    if (!why && x) {
-        if (!x->ego_attn_score && !x->readout) why = "reads needs ego_attn_score or readout";
-        else if (misaligned(x->ego_attn_score, 4)) why = "ego_attn_score must be 4-byte aligned";
-        else if (x->readout && p->network_dim != 64) why = "reads->readout must be NULL unless network_dim is 64 (the probes read 64-wide tokens)";
-    }
-    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
-    if (const int rc = bc_rollout_problem(who, s, &p->base, b, n_steps, p->network_dim)) return rc;
-    if (x && x->readout)
-        if (const char *bad = bc_readout_problem(&p->base, x->readout)) return fail(GD_ERR_INVALID, std::string(who) + ": " + bad);
-    return bc_rollout_run(s, &p->base, b, r, n_steps, x, p->network_dim);
-}
-
 // everything gd_bc_backward refuses; nullptr when everything is in order
 static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,
@@ -2413,7 +2396,7 @@ static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *
     gd_bc_outputs none{};
     if (!g || !expert_actions || !grad_nll || !grad)
         why = "null argument";
-    else if ((why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &none)))
+    else if ((why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &none, 64)))
         ;
     else if (g->num_partials < 1 || g->num_partials > 4096)
         why = "num_partials must be in [1, 4096]";
@@ -2514,7 +2497,7 @@ int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *op
     const char *why = nullptr;
     if (!expert_actions || !o.actions || !o.nll || !o.grad_nll || !o.grad)
         why = "null argument (expert_actions, or opt's actions, nll, grad_nll or grad)";
-    if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out);
+    if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out, 64);
     if (!why) why = bc_train_rows_problem(opt, n, o.nll, o.actions, expert_actions, o.grad_nll);
     if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
     if (!why) why = bc_adamw_problem(opt, o.grad);
@@ -2547,32 +2530,30 @@ int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, con
     });
 }
 
-int gd_bc_hidden(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, int32_t tap,
-                 float *out, void *stream) {
+// The body of gd_bc_hidden (layer == nullptr: the tapped block's last layer) and gd_bc_hidden_layer.  The tokens are 64 wide.
+static int bc_hidden(const char *who, const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
+                     int32_t n, int32_t tap, const int32_t *layer, float *out, void *stream) {
     gd_bc_outputs none{};
-    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none);
+    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none, 64);
     if (!why && tap != GD_LP_TAP_FUSION && tap != GD_LP_TAP_RO) why = "tap must be GD_LP_TAP_FUSION or GD_LP_TAP_RO";
+    if (!why && layer && (*layer < 0 || *layer >= (tap == GD_LP_TAP_RO ? p->branch_layers : p->fusion_layers)))
+        why = "layer must be in [0, layers of the tapped block)";
     if (!why && (!out || misaligned(out, 16))) why = "out is required, 16-byte aligned";
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_hidden: ") + why);
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     return guarded([&]() {
-        gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out);
+        gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out, layer ? *layer : -1);
         HIP_CHECK(hipGetLastError());
     });
 }
 
+int gd_bc_hidden(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, int32_t tap,
+                 float *out, void *stream) {
+    return bc_hidden("gd_bc_hidden", p, obs, partner_mask, road_mask, n, tap, nullptr, out, stream);
+}
+
 int gd_bc_hidden_layer(const gd_bc_policy *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n,
                        int32_t tap, int32_t layer, float *out, void *stream) {
-    gd_bc_outputs none{};
-    const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none);
-    if (!why && tap != GD_LP_TAP_FUSION && tap != GD_LP_TAP_RO) why = "tap must be GD_LP_TAP_FUSION or GD_LP_TAP_RO";
-    if (!why && (layer < 0 || layer >= (tap == GD_LP_TAP_RO ? p->branch_layers : p->fusion_layers)))
-        why = "layer must be in [0, layers of the tapped block)";
-    if (!why && (!out || misaligned(out, 16))) why = "out is required, 16-byte aligned";
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_hidden_layer: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_hidden(*p, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, tap, out, layer);
-        HIP_CHECK(hipGetLastError());
-    });
+    return bc_hidden("gd_bc_hidden_layer", p, obs, partner_mask, road_mask, n, tap, &layer, out, stream);
 }
 
 // everything the three gd_lp_* entries refuse; nullptr when everything is in order.  mode: launch_lp's
@@ -2594,7 +2575,7 @@ static const char *lp_problem(const gd_bc_policy *p, const gd_lp_probe *lp, cons
         if (lp->in_features != k) return "in_features must be 6 num_stack ('ego') or 12 num_stack ('other') for the baseline probe";
     } else {
         gd_bc_outputs none{};
-        if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none)) return why;
+        if (const char *why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, nullptr, &none, 64)) return why;
         if (lp->max_agents != p->max_agents || lp->num_stack != p->num_stack) return "max_agents and num_stack must be the policy's";
         if (lp->in_features != 64) return "in_features must be 64 with a policy";
     }

@@ -39,14 +39,14 @@ EDGE_CASES = (
 EDGE = {name: (B, A, R, cfg) for name, B, A, R, cfg in EDGE_CASES}
 
 
-def state_dict(num_stack, cfg=CFG, seed=0):
+def state_dict(num_stack, cfg=CFG, seed=0, network_dim=64):
     """A numpy default_rng fills each tensor in list order.  Scaled so that attention is not flat: the q / k weights are large
     enough that softmax rows have a clear maximum (scores of standard deviation about 4), LayerNorm gains and biases are not
     1 / 0, biases are not 0.  Two raw covariances are pushed below clip_value and above 3.58352 through the head's bias."""
     rng = np.random.default_rng(seed)
     C = cfg["n_components"]
     sd = {}
-    for name, shape in BP.expected_shapes(num_stack, cfg["num_layer"], cfg["head_num_layers"], C).items():
+    for name, shape in BP.expected_shapes(num_stack, cfg["num_layer"], cfg["head_num_layers"], C, network_dim=network_dim).items():
         n = rng.standard_normal(shape)
         if len(shape) == 2:
             v = n * ((2.0 if (".q_proj." in name or ".k_proj." in name) else 1.0) / np.sqrt(shape[1]))
@@ -57,7 +57,7 @@ def state_dict(num_stack, cfg=CFG, seed=0):
         sd[name] = v
     b = sd["head.head.bias"]
     b[3 * C + 1] = cfg["clip_value"] - 10.0  # case (f): below the clamp
-    b[3 * C + 5] = 10.0                      # case (f): above 3.58352
+    b[3 * C + (5 if C > 1 else 2)] = 10.0    # case (f): above 3.58352
     return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in sd.items()}
 
 
@@ -130,17 +130,19 @@ def overwrite_masked(obs, pm, rm, A, seed=7):
 
 class StandIn:
     """The module as eager torch in one dtype on one device: the project's own stand-in for EarlyFusionAttnBCNet in eval mode
-    (same state dict names; F.layer_norm, F.gelu, masked_fill with -finfo.max, softmax, einsum, as the reference writes it)."""
+    (same state dict names; F.layer_norm, F.gelu, masked_fill with -finfo.max, softmax, einsum, as the reference writes it).
+    The width is the state dict's: LayerNorm over D features, 4 heads of D / 4 channels."""
 
     def __init__(self, sd, max_agents, cfg=CFG, dtype=torch.float32, device="cpu"):
         self.sd = {k: v.detach().to(device=device, dtype=dtype) for k, v in sd.items()}
         self.A, self.cfg, self.dtype, self.device = max_agents, cfg, dtype, device
+        self.D = int(sd["ego_state_net.2.weight"].shape[0])
 
     def _lin(self, x, name):
         return F.linear(x, self.sd[name + ".weight"], self.sd[name + ".bias"])
 
     def _ln(self, x, name):
-        return F.layer_norm(x, (64,), self.sd[name + ".weight"], self.sd[name + ".bias"], 1e-5)
+        return F.layer_norm(x, (self.D,), self.sd[name + ".weight"], self.sd[name + ".bias"], 1e-5)
 
     def _embed(self, x, net):
         for i in range(4):
@@ -148,14 +150,14 @@ class StandIn:
         return x
 
     def _attention(self, xq, xkv, mask, name):
-        B, N, J = xq.shape[0], xq.shape[1], xkv.shape[1]
-        split = lambda t, n: t.reshape(B, n, 4, 16).permute(0, 2, 1, 3)  # noqa: E731
-        q = split(self._lin(xq, name + ".q_proj"), N) * 16 ** -0.5
+        B, N, J, ch = xq.shape[0], xq.shape[1], xkv.shape[1], self.D // 4
+        split = lambda t, n: t.reshape(B, n, 4, ch).permute(0, 2, 1, 3)  # noqa: E731
+        q = split(self._lin(xq, name + ".q_proj"), N) * ch ** -0.5
         k, v = split(self._lin(xkv, name + ".k_proj"), J), split(self._lin(xkv, name + ".v_proj"), J)
         attn = torch.einsum("bhic,bhjc->bhij", q, k)
         attn.masked_fill_(mask[:, None, None, :], -torch.finfo(attn.dtype).max)
         attn = attn.softmax(dim=-1)
-        o = torch.einsum("bhij,bhjc->bhic", attn, v).permute(0, 2, 1, 3).reshape(B, N, 64)
+        o = torch.einsum("bhij,bhjc->bhic", attn, v).permute(0, 2, 1, 3).reshape(B, N, self.D)
         return self._lin(o, name + ".o_proj"), attn
 
     def _mlp(self, x, name):

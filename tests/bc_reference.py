@@ -1,6 +1,9 @@
 """The BC policy (the reference's EarlyFusionAttnBCNet in eval mode) restated in float64 numpy from a state dict, in this
-repository's own words: what gd_bc_forward is held to.  tests/test_bc_policy.py pins this restatement to the reference
-module itself (tests/golden/bc_forward_*.npz).
+repository's own words: what gd_bc_forward and gd_bc_forward_dim are held to.  The width is the state dict's: for `network_dim`
+D and head_dim 64 every embedder, LayerNorm and attention Linear is D wide, the 4 heads have D / 4 channels and q is scaled by
+(D / 4)^-1/2, the context is 3 D wide, and the GMM head behind head.input_layer (3 D -> 64) is 64 wide at either width.
+tests/test_bc_policy.py pins this restatement to the reference module itself at 64 (tests/golden/bc_forward_*.npz),
+tests/test_bc_wide.py at 128 (tests/golden/bc_wide_forward_*.npz).
 
 `wrong=` switches ONE rule to a plausible mistake, so that the tests can show the comparison catches it:
     "inf_fill"        masked keys are excluded (probability 0; a row with no key left gives a zero attention output) instead of
@@ -13,14 +16,19 @@ and four that are the right rule at bc_cases.CFG and wrong only at the configura
     "rg_at_ro"        rg_attn layer i is read at ro_attn's offset (ro_attn layer i's weights) for i >= min(fusion, branch):
                       it needs branch > fusion to show (a model with one branch layer has no such i)
     "floor_m20"       the covariance clamp's floor is -20 whatever clip_value says
-    "eval_one_trip"   `evaluate` sums the rows below 64 of a batch only (one trip of a 64-lane loop over the rows)"""
+    "eval_one_trip"   `evaluate` sums the rows below 64 of a batch only (one trip of a 64-lane loop over the rows)
+and four that the 128 case invites (the right rule at 64):
+    "scale16"         q * 0.25, the 64-wide kernel's constant, instead of q * 32^-1/2
+    "heads_of_16"     eight heads of 16 channels (the 64-wide head size kept) instead of four of 32
+    "ctx192"          the head reads the first 192 context inputs only (the 64-wide CTX kept)
+    "ln64"            LayerNorm statistics over the first 64 features only (one lane per feature, one wave)"""
 import math
 
 import numpy as np
 
 FLT_MAX = float(np.finfo(np.float32).max)
 COV_MAX = 3.58352
-ROADS, EGO_K, PARTNER_K, ROAD_K, DIM, HEADS = 200, 6, 6, 13, 64, 4
+ROADS, EGO_K, PARTNER_K, ROAD_K, DIM, HEADS = 200, 6, 6, 13, 64, 4  # DIM: the narrow width, and the GMM head's at either
 _erf = np.vectorize(math.erf, otypes=[np.float64])
 
 
@@ -28,9 +36,10 @@ def _sd64(sd):
     return {k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64) for k, v in sd.items()}
 
 
-def layer_norm(x, sd, name):
-    mean = x.mean(-1, keepdims=True)
-    var = ((x - mean) ** 2).mean(-1, keepdims=True)  # biased
+def layer_norm(x, sd, name, wrong=None):
+    stat = x[..., :64] if wrong == "ln64" else x
+    mean = stat.mean(-1, keepdims=True)
+    var = ((stat - mean) ** 2).mean(-1, keepdims=True)  # biased
     return (x - mean) / np.sqrt(var + 1e-5) * sd[name + ".weight"] + sd[name + ".bias"]
 
 
@@ -57,19 +66,21 @@ def unpack(obs, A, wrong=None):
     return out
 
 
-def embed(x, sd, net):
+def embed(x, sd, net, wrong=None):
     for i in range(4):  # Linear -> [dropout: identity] -> LayerNorm -> tanh
-        x = np.tanh(layer_norm(linear(x, sd, "%s.%d" % (net, 4 * i)), sd, "%s.%d" % (net, 4 * i + 2)))
+        x = np.tanh(layer_norm(linear(x, sd, "%s.%d" % (net, 4 * i)), sd, "%s.%d" % (net, 4 * i + 2), wrong))
     return x
 
 
 def attention(xq, xkv, mask, sd, name, wrong=None):
-    """xq [B, N, 64], xkv [B, J, 64] (both already normed), mask [B, J] bool (True: padding).  Returns (o_proj output
-    [B, N, 64], the attention probabilities [B, 4, N, J])."""
-    B, N, _ = xq.shape
+    """xq [B, N, D], xkv [B, J, D] (both already normed), mask [B, J] bool (True: padding).  Returns (o_proj output
+    [B, N, D], the attention probabilities [B, 4, N, J])."""
+    B, N, D = xq.shape
     J = xkv.shape[1]
-    split = lambda t, n: t.reshape(B, n, HEADS, DIM // HEADS).transpose(0, 2, 1, 3)  # noqa: E731
-    q = split(linear(xq, sd, name + ".q_proj"), N) * (DIM // HEADS) ** -0.5
+    heads = D // 16 if wrong == "heads_of_16" else HEADS
+    ch = D // heads
+    split = lambda t, n: t.reshape(B, n, heads, ch).transpose(0, 2, 1, 3)  # noqa: E731
+    q = split(linear(xq, sd, name + ".q_proj"), N) * (0.25 if wrong == "scale16" else ch ** -0.5)
     k = split(linear(xkv, sd, name + ".k_proj"), J)
     v = split(linear(xkv, sd, name + ".v_proj"), J)
     s = np.einsum("bhic,bhjc->bhij", q, k)
@@ -84,25 +95,25 @@ def attention(xq, xkv, mask, sd, name, wrong=None):
         s = np.where(m, -FLT_MAX, s)
         e = np.exp(s - s.max(-1, keepdims=True))
         p = e / e.sum(-1, keepdims=True)
-    o = np.einsum("bhij,bhjc->bhic", p, v).transpose(0, 2, 1, 3).reshape(B, N, DIM)
+    o = np.einsum("bhij,bhjc->bhic", p, v).transpose(0, 2, 1, 3).reshape(B, N, D)
     return linear(o, sd, name + ".o_proj"), p
 
 
 def mlp(x, sd, name, wrong=None):
-    z = linear(layer_norm(x, sd, name + ".0"), sd, name + ".1")
+    z = linear(layer_norm(x, sd, name + ".0", wrong), sd, name + ".1")
     return x + linear(gelu(z, wrong), sd, name + ".3")
 
 
 def self_layer(x, mask, sd, name, wrong=None):
-    h = layer_norm(x, sd, name + ".0.module.norm")
+    h = layer_norm(x, sd, name + ".0.module.norm", wrong)
     o, _ = attention(h, h, mask, sd, name + ".0.module.attention", wrong)
     x = o + (h if wrong == "normed_residual" else x)
     return mlp(x, sd, name + ".1.module", wrong)
 
 
 def cross_layer(xq, xkv, mask, sd, name, wrong=None):
-    q = layer_norm(xq, sd, name + ".0.module.q_norm")
-    kv = layer_norm(xkv, sd, name + ".0.module.kv_norm")
+    q = layer_norm(xq, sd, name + ".0.module.q_norm", wrong)
+    kv = layer_norm(xkv, sd, name + ".0.module.kv_norm", wrong)
     o, p = attention(q, kv, mask, sd, name + ".0.module.attention", wrong)
     x = o + (q if wrong == "normed_residual" else xq)
     return mlp(x, sd, name + ".1.module", wrong), p[:, :, 0, :]
@@ -113,8 +124,8 @@ def clamp_logcov(raw, clip_value):
 
 
 def forward(sd, obs, partner_mask, road_mask, max_agents, num_layer, head_num_layers, n_components, clip_value, wrong=None):
-    """Everything the module computes for a batch, float64: context [B, 192], ego_attn_score [B, 4, A - 1], raw [B, 7 C], means
-    and log_covariances and covariances [B, C, 3], weights [B, C]."""
+    """Everything the module computes for a batch, float64; the width is the state dict's: context [B, 3 D], ego_attn_score
+    [B, 4, A - 1], raw [B, 7 C], means and log_covariances and covariances [B, C, 3], weights [B, C]."""
     sd = _sd64(sd)
     obs = np.asarray(obs, dtype=np.float64)
     A, C = max_agents, n_components
@@ -122,8 +133,8 @@ def forward(sd, obs, partner_mask, road_mask, max_agents, num_layer, head_num_la
     pm = np.asarray(partner_mask).astype(bool)[:, -1]
     rm = np.asarray(road_mask).astype(bool)[:, -1]
     ego, ro, rg = unpack(obs, A, wrong)
-    x = np.concatenate([embed(ego, sd, "ego_state_net")[:, None], embed(ro, sd, "road_object_net"),
-                        embed(rg, sd, "road_graph_net")], axis=1)
+    x = np.concatenate([embed(ego, sd, "ego_state_net", wrong)[:, None], embed(ro, sd, "road_object_net", wrong),
+                        embed(rg, sd, "road_graph_net", wrong)], axis=1)
     ego_mask = np.zeros((B, 1), dtype=bool)
     all_mask, obj_mask = np.concatenate([ego_mask, pm, rm], 1), np.concatenate([ego_mask, pm], 1)
     for i in range(num_layer[0]):
@@ -147,7 +158,8 @@ def forward(sd, obs, partner_mask, road_mask, max_agents, num_layer, head_num_la
 
 def head(sd, context, head_num_layers, C, clip_value, wrong=None):
     sd = _sd64(sd)
-    x = np.maximum(linear(context, sd, "head.input_layer.0"), 0.0)
+    w, b = sd["head.input_layer.0.weight"], sd["head.input_layer.0.bias"]
+    x = np.maximum((context[:, :192] @ w[:, :192].T if wrong == "ctx192" else context @ w.T) + b, 0.0)
     for i in range(head_num_layers):
         x = x + np.maximum(linear(x, sd, "head.residual_block.%d.0" % i), 0.0)
     raw = linear(x, sd, "head.head")

@@ -1,4 +1,4 @@
-"""The BC policy at network_dim = 128 without a GPU: the wide restatement against the reference module, the wide layout of
+"""The BC policy at network_dim = 128 without a GPU: the restatement at that width against the reference module, the wide layout of
 the blob against an emulation of the wide kernels' lane maps, the unchanged 64-wide results, every refusal, the new struct
 and the C entry points' checks."""
 import ctypes as C
@@ -16,7 +16,6 @@ from gpudrive_lab_amd import bc_policy as BP
 from tests import bc_cases as BC
 from tests import bc_reference as REF
 from tests import bc_wide_cases as WC
-from tests import bc_wide_reference as WREF
 from tests.conftest import ROOT
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -51,22 +50,13 @@ def test_restatement_equals_the_reference_module(name):
         assert np.abs(g[k] - v).max() <= 1e-12 * np.abs(g[k]).max(), k
 
 
-def test_the_restatement_at_64_is_the_64_wide_one():
-    B, A, R = 3, 64, 1
-    sd = BC.state_dict(R)
-    obs, pm, rm = BC.inputs(B, A, R)[:3]
-    a, b = REF.forward(sd, obs, pm, rm, A, **BC.CFG), WREF.forward(sd, obs, pm, rm, A, **BC.CFG)
-    for k in ("context", "ego_attn_score", "raw"):
-        assert np.array_equal(a[k], b[k]), k
-
-
 # (wrong, case, output): the encoder's mistakes move the context; "ctx192" is a mistake of the head, which reads the context and
 # cannot move it, so it is held to the same bound on the means
 @pytest.mark.parametrize("wrong,name,output", [("scale16", "wide_min", "context"), ("heads_of_16", "wide_a128", "context"),
                                                ("ctx192", "wide_sweep", "means"), ("ln64", "wide_sweep", "context")])
 def test_the_comparison_catches_each_wide_mistake(wrong, name, output):
     c = WC.case(name)
-    bad = WREF.forward(c["sd"], c["obs"], c["pm"], c["rm"], c["A"], wrong=wrong, **c["cfg"])
+    bad = REF.forward(c["sd"], c["obs"], c["pm"], c["rm"], c["A"], wrong=wrong, **c["cfg"])
     moved = np.abs(bad[output] - c["ref"][output]).max()
     print("%s on %s: %s moves by %.3g = %.3g E" % (wrong, name, output, moved, moved / c["E"][output]))
     assert moved >= 4 * K * c["E"][output]
@@ -182,7 +172,7 @@ def test_pack_index_at_128_is_what_the_wide_kernels_read():
     for k in names:  # exact: a gather moves bits
         assert np.array_equal(seen[k], c["sd"][k].numpy().astype(np.float64)), k
     # and the forward on what the kernels see is the reference's: embedders, the self layers, the cross layers and the head
-    got = WREF.forward(seen, c["obs"], c["pm"], c["rm"], c["A"], **cfg)
+    got = REF.forward(seen, c["obs"], c["pm"], c["rm"], c["A"], **cfg)
     for k in ("context", "raw", "ego_attn_score"):  # (the same float64 values through other strides: BLAS may round otherwise)
         assert np.abs(got[k] - c["ref"][k]).max() <= 1e-12 * np.abs(c["ref"][k]).max(), k
 
@@ -219,7 +209,7 @@ def test_the_64_wide_layout_is_unchanged(R, num_layer, hl, C_):
 
 def test_every_refusal_at_128():
     B, A, R, cfg = WC.CASES["wide_min"]
-    wide, narrow = WC.state_dict(R, cfg), WC.state_dict(R, cfg, network_dim=64)
+    wide, narrow = BC.state_dict(R, cfg, network_dim=WC.DIM), BC.state_dict(R, cfg, network_dim=64)
     ok = dict(max_agents=A, num_stack=R, num_head=4, **cfg)
     both = dict(network_dims=(64, 128))
     assert list(BP.check_bc_args(wide, network_dim=128, **both, **ok)) == list(wide)
@@ -248,7 +238,7 @@ def test_training_refuses_128():
     from gpudrive_lab_amd.bc_opt import DeviceBC
     from gpudrive_lab_amd.bc_train import TrainableBCPolicy
     B, A, R, cfg = WC.CASES["wide_min"]
-    wide = WC.state_dict(R, cfg)
+    wide = BC.state_dict(R, cfg, network_dim=WC.DIM)
     ok = dict(max_agents=A, num_stack=R, num_head=4, **cfg)
     with pytest.raises(ValueError, match="TrainableBCPolicy: network_dim must be 64"):
         TrainableBCPolicy(wide, network_dim=128, **ok)

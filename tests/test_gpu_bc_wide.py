@@ -1,9 +1,9 @@
 """GPU suite: the BC policy forward and the closed-loop driver at network_dim = 128 (gd_bc_forward_dim, gd_bc_forward_rows_dim,
-gd_bc_rollout_dim; csrc/bc_policy.hip at T = 4) against the float64 restatement with the width as a parameter
-(tests/bc_wide_reference.py, pinned to the reference module by tests/test_bc_wide.py) on the cases of tests/bc_wide_cases.py.
+gd_bc_rollout_dim; csrc/bc_policy.hip at T = 4) against the float64 restatement, which takes the width from the state dict
+(tests/bc_reference.py, pinned to the reference module at 128 by tests/test_bc_wide.py) on the cases of tests/bc_wide_cases.py.
 
 context, means, clamped raw covariances, weights, NLL and ego_attn_score: the yardstick E of a case and an output is the maximum
-absolute error of torch's float32 CPU forward of the wide stand-in (bc_wide_cases.WideStandIn) against float64 on that case --
+absolute error of torch's float32 CPU forward of the stand-in at that width (bc_cases.StandIn) against float64 on that case --
 the reference side's own error, not the kernel's; the kernel's error must be <= K E with the project's K = 32, and a ratio above
 16 would be a bug to find.  Ratios measured on an MI355X (printed per case by this test with -s):
     name (B, A, R)          context  means  log_covariances  weights  nll    ego_attn_score
@@ -129,14 +129,14 @@ def test_chunks_rows_and_reloaded_weights_give_the_same_bits():
             rest = got[k][[1, 2]]
             assert (rest == (-7 if k == "component" else np.float32(F_CANARY))).all(), (k, "rows that are not listed were written")
     # load_state_dict with other weights equals a fresh policy of those weights
-    sd2 = WC.state_dict(c["R"], c["cfg"], seed=11)
+    sd2 = BC.state_dict(c["R"], c["cfg"], seed=11, network_dim=WC.DIM)
     small.load_state_dict({k: v.cuda() for k, v in sd2.items()})
     fresh = _policy(c, sd=sd2, chunk_rows=8)
     a = _host(small.forward(obs, pm, rm, ALL, **kw))
     _same_bits(a, _host(fresh.forward(obs, pm, rm, ALL, **kw)), "load_state_dict against a fresh policy")
     assert np.abs(a["context"] - full["context"]).max() > 0.1
     with pytest.raises(ValueError, match="shape"):
-        small.load_state_dict(WC.state_dict(c["R"], c["cfg"], network_dim=64))
+        small.load_state_dict(BC.state_dict(c["R"], c["cfg"], network_dim=64))
 
 
 def test_the_dim_entry_points_at_64_are_the_64_wide_forward():
@@ -223,7 +223,7 @@ def _loop_case(name):
         with _Env(roads):
             rsim, tsim = _sim(A, model, cb, roads), _sim(A, model, cb, roads)
             try:
-                pol = DeviceBCPolicy.from_state_dict(WC.state_dict(R, LOOP_CFG), max_agents=A, num_stack=R, network_dim=128, **LOOP_CFG)
+                pol = DeviceBCPolicy.from_state_dict(BC.state_dict(R, LOOP_CFG, network_dim=WC.DIM), max_agents=A, num_stack=R, network_dim=128, **LOOP_CFG)
                 loop = ClosedLoopBC(rsim, pol)
                 c = _LOOP
                 c["N"], c["A"], c["R"], c["pol"] = loop.num_agents, A, R, pol

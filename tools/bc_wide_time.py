@@ -3,7 +3,7 @@
 
 B = 512, A = 128, R = 5, num_layer (4, 3), head 2, C = 6 (the reference sweep's model), synthetic observations, 40 % padding.
     (a) the wide `DeviceBCPolicy` forward with out= (gd_bc_forward_dim, csrc/bc_policy.hip at T = 4)
-    (b) the eager float32 stand-in at 128 on the same GPU, same weights and inputs (tests/bc_wide_cases.WideStandIn)
+    (b) the eager float32 stand-in at 128 on the same GPU, same weights and inputs (tests/bc_cases.StandIn)
     (c) the 64-wide `DeviceBCPolicy` forward at the same layer counts, for scale
 Device events around 10 calls after a warm-up of 3, three runs of each in alternation; peak allocated memory of (a) and (b) from
 torch's allocator statistics (a fresh peak per side; the inputs and weights are allocated before).  Writes
@@ -19,7 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gpudrive_lab_amd.bc_policy import DeviceBCPolicy, obs_width  # noqa: E402
 from tests import bc_cases as BC  # noqa: E402
-from tests import bc_wide_cases as WC  # noqa: E402
 
 B, A, R = 512, 128, 5
 CFG = BC._cfg((4, 3), 2, 6, -20.0)
@@ -55,10 +54,10 @@ def main():
     obs = torch.from_numpy(rng.uniform(-1, 1, (B, R, obs_width(A))).astype(np.float32)).cuda()
     pm = torch.from_numpy(rng.random((B, R, A - 1)) < 0.4).cuda()
     rm = torch.from_numpy(rng.random((B, R, 200)) < 0.4).cuda()
-    sd_w, sd_n = WC.state_dict(R, CFG), WC.state_dict(R, CFG, network_dim=64)
+    sd_w, sd_n = BC.state_dict(R, CFG, network_dim=128), BC.state_dict(R, CFG, network_dim=64)
     wide = DeviceBCPolicy.from_state_dict(sd_w, max_agents=A, num_stack=R, network_dim=128, **CFG)
     narrow = DeviceBCPolicy.from_state_dict(sd_n, max_agents=A, num_stack=R, **CFG)
-    eager = WC.WideStandIn(sd_w, A, CFG, torch.float32, "cuda")
+    eager = BC.StandIn(sd_w, A, CFG, torch.float32, "cuda")
     out_w, out_n = torch.empty((B, 1, 3), device="cuda"), torch.empty((B, 1, 3), device="cuda")
     sides = {
         "wide_hip": lambda: wide(obs, pm, rm, deterministic=True, out=out_w),

@@ -4,14 +4,9 @@ for the device only (the Makefile's flags plus --cuda-device-only -S), cuts the 
 every kernel of OLD with the kernel of NEW it is mapped to: the body and the .amdhsa_kernel descriptor, with the kernel's
 own mangled name and the .LBB<n>_ / .Lfunc_end<n> numbers normalised.  It looks at nothing inside a body.
 tools/isa_same.py OLD NEW bc_policy.hip bc_grad.hip ... [--map REGEX=REPL ...]   (a file missing from one tree is skipped there)
-A kernel's demangled name takes the first rule that matches it, --map before MAP.  Exit status 1 if a kernel of OLD is
-missing from NEW or differs."""
+A kernel's demangled name takes the first --map rule that matches it (a refactor that renames kernels says how).  Exit
+status 1 if a kernel of OLD is missing from NEW or differs."""
 import os, re, subprocess, sys, tempfile
-
-# the 128-wide copies became instantiations of the width-templated kernels: T = network_dim / 32 is the first argument
-MAP = [(r"k_bcw_head<", "k_bc_head_block<"), (r"k_bcw_(\w+)<(?=>)", r"k_bc_\1<4"), (r"k_bcw_(\w+)<", r"k_bc_\1<4, "),
-       (r"k_bc_(embed|kv|attn)<(?=>)", r"k_bc_\1<2"), (r"k_bc_(embed|kv|attn)<", r"k_bc_\1<2, ")]
-
 
 def kernels(tree, files):
     d = os.path.join(tree, "gpudrive_lab_amd", "csrc")
@@ -37,7 +32,7 @@ for a in sys.argv[1:]:
     if a == "--map": continue
     (rules if "=" in a else args).append(a)
 if len(args) < 3: sys.exit(__doc__)
-rules = [tuple(r.split("=", 1)) for r in rules] + MAP
+rules = [tuple(r.split("=", 1)) for r in rules]
 old, new = kernels(args[0], args[2:]), kernels(args[1], args[2:])
 by_name = {k.split(" ", 1)[1]: v for k, v in new.items()}  # a kernel may have moved to another file
 bad = 0
