@@ -9,9 +9,9 @@ from ._capi import build, lib_path  # noqa: F401
 
 def __getattr__(name):
     # torch is imported only when the module that needs it is asked for
-    if name == "TrainableBCPolicy":
-        from .bc_train import TrainableBCPolicy
-        return TrainableBCPolicy
+    if name in ("TrainableBCPolicy", "TrainableBCPolicyDim"):
+        from . import bc_train
+        return getattr(bc_train, name)
     if name == "DeviceBC":
         from .bc_opt import DeviceBC
         return DeviceBC

@@ -23,9 +23,14 @@ masked score receives none (a row whose keys are all masked gives its uniform sh
 and keys), the covariance clamp passes the gradient on [clip_value, 3.58352], bounds included, and an exact 0 outside, the
 head's ReLU passes nothing at a pre-activation <= 0.  `obs` gets no gradient.
 
+`TrainableBCPolicyDim` is the same module at the widths the backward is built at, 64 and 128: `network_dim=128` (with head_dim 64,
+num_layer (4, 3): the model of the reference's sweep, baselines/il/sweep.yaml) trains on the kernels' T = 4 instantiations through
+`gd_bc_forward_dim` / `gd_bc_backward_dim`, and a `DeviceBCPolicy(..., network_dim=128)` follows with `load_state_dict`.
+`TrainableBCPolicy` itself keeps refusing any width but 64, as `gd_bc_backward` keeps taking a `gd_bc_policy`.
+
 Not here: gradient clipping and AdamW (any torch optimiser works on this module; `bc_opt.DeviceBC` is the whole step on the
 device, gd_bc_update, without it); non-zero dropout; `aux_head` / `use_tom`; `l1_loss` / `focal_loss`; bf16; a gradient with respect to the
-observations; any tuning beyond one wave per workgroup."""
+observations; any tuning beyond one wave per workgroup; `DeviceBC` (the whole step on the device) at 128."""
 import ctypes as C
 
 import numpy as np
@@ -42,14 +47,15 @@ MAX_PARTIALS = 4096
 _ALLOCATIONS = 16  # tensors a step allocates, for the allocator's rounding in nbytes
 
 
-def grad_floats(num_stack, num_layer, head_num_layers, n_components):
-    return sum(int(np.prod(s)) for s in BP.expected_shapes(num_stack, num_layer, head_num_layers, n_components).values())
+def grad_floats(num_stack, num_layer, head_num_layers, n_components, *, network_dim=BP.DIM):
+    return sum(int(np.prod(s)) for s in BP.expected_shapes(num_stack, num_layer, head_num_layers, n_components,
+                                                           network_dim=network_dim).values())
 
 
-def grad_scratch_floats(max_agents, chunk_rows, num_layer, blob_floats):
+def grad_scratch_floats(max_agents, chunk_rows, num_layer, blob_floats, *, network_dim=BP.DIM):
     """gd_bc_grad.scratch: the transposed weights, the self-attention layers' inputs, and five token buffers with the
-    softmax row statistics of one chunk."""
-    return (blob_floats + 63) // 64 * 64 + chunk_rows * (max_agents + BP.ROADS) * (BP.DIM * (num_layer[0] + num_layer[1] + 5) + 16)
+    softmax row statistics of one chunk (csrc/bc_grad.hip `bc_grad_scratch_floats` is the C side's one statement of it)."""
+    return (blob_floats + 63) // 64 * 64 + chunk_rows * (max_agents + BP.ROADS) * (network_dim * (num_layer[0] + num_layer[1] + 5) + 16)
 
 
 class _BCStep(torch.autograd.Function):
@@ -63,10 +69,11 @@ class _BCStep(torch.autograd.Function):
         o = _capi.GdBCOutputs()
         o.nll = nll.data_ptr()
         p = mod._policy_struct(blob)
+        forward, who = (_capi.lib().gd_bc_forward_dim, "gd_bc_forward_dim") if mod._wide else (_capi.lib().gd_bc_forward, "gd_bc_forward")
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(_capi.lib().gd_bc_forward(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, 1,
-                                                  None, None, expert.data_ptr(), C.byref(o), stream), "gd_bc_forward")
+            _capi.check(forward(C.byref(p), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B, 1,
+                                None, None, expert.data_ptr(), C.byref(o), stream), who)
         ctx.save_for_backward(obs, partner_mask, road_mask, expert, *params)  # (torch's version check catches a step in between)
         ctx.mod, ctx.blob = mod, blob
         return nll
@@ -82,11 +89,11 @@ class _BCStep(torch.autograd.Function):
         p, g = mod._policy_struct(blob), _capi.GdBCGrad()
         g.scratch, g.scratch_floats = mod._grad_scratch.data_ptr(), mod._grad_scratch.numel()
         g.partials, g.grad_floats, g.num_partials = mod._partials.data_ptr(), mod._G, mod.partials
+        backward, who = (_capi.lib().gd_bc_backward_dim, "gd_bc_backward_dim") if mod._wide else (_capi.lib().gd_bc_backward, "gd_bc_backward")
         with torch.cuda.device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _capi.check(_capi.lib().gd_bc_backward(C.byref(p), C.byref(g), obs.data_ptr(), partner_mask.data_ptr(),
-                                                   road_mask.data_ptr(), B, expert.data_ptr(), d_nll.data_ptr(), None,
-                                                   grad.data_ptr(), stream), "gd_bc_backward")
+            _capi.check(backward(C.byref(p), C.byref(g), obs.data_ptr(), partner_mask.data_ptr(), road_mask.data_ptr(), B,
+                                 expert.data_ptr(), d_nll.data_ptr(), None, grad.data_ptr(), stream), who)
         views, o = [], 0
         for shape in mod._shapes:
             k = int(np.prod(shape))
@@ -96,6 +103,8 @@ class _BCStep(torch.autograd.Function):
 
 
 class TrainableBCPolicy(nn.Module):
+    NETWORK_DIMS = (BP.DIM,)  # the widths this name accepts; `TrainableBCPolicyDim` is the class at every width that is built
+
     def __init__(self, state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num_head=4, head_num_layers=2,
                  n_components=6, clip_value=-20.0, *, device=None, chunk_rows=BP.DEFAULT_CHUNK, partials=None, **fixed):
         """`DeviceBCPolicy`'s arguments, refused alike on the host (ValueError) before anything reaches the device.  device:
@@ -103,7 +112,7 @@ class TrainableBCPolicy(nn.Module):
         a state dict to be exchanged -- `forward` is what needs the GPU and says so.  partials: P in [1, 4096], the number
         of one-wave workgroups of each backward launch and of partial gradients the last launch adds in order (default 128:
         128 times the parameters, about 150 MB, allocated at the first forward and kept).  The sums are deterministic for a
-        given P and chunk_rows."""
+        given P and chunk_rows.  fixed: `DeviceBCPolicy`'s; network_dim must be one of the class's NETWORK_DIMS."""
         super().__init__()
         unknown = sorted(set(fixed) - BP.FIXED)
         if unknown:
@@ -111,7 +120,9 @@ class TrainableBCPolicy(nn.Module):
         num_layer = tuple(num_layer) if isinstance(num_layer, list) else num_layer
         shapes = BP.check_bc_args(state_dict, max_agents=max_agents, num_stack=num_stack, num_layer=num_layer, num_head=num_head,
                                   head_num_layers=head_num_layers, n_components=n_components, clip_value=clip_value,
-                                  chunk_rows=chunk_rows, who=WHO, **fixed)
+                                  chunk_rows=chunk_rows, who=WHO, network_dims=self.NETWORK_DIMS, **fixed)
+        self.network_dim = D = fixed.get("network_dim", BP.DIM)
+        self._wide = D != BP.DIM  # a 64-wide instance of either class calls gd_bc_forward / gd_bc_backward
         if partials is None:
             partials = DEFAULT_PARTIALS
         if not BP._is_int(partials) or not 1 <= partials <= MAX_PARTIALS:
@@ -127,7 +138,7 @@ class TrainableBCPolicy(nn.Module):
         self.chunk_rows, self.partials = chunk_rows, partials
         self.obs_width = BP.obs_width(max_agents)
         self._names, self._shapes = tuple(shapes), tuple(shapes.values())
-        self._G = grad_floats(num_stack, num_layer, head_num_layers, n_components)
+        self._G = grad_floats(num_stack, num_layer, head_num_layers, n_components, network_dim=D)
         for name in self._names:  # e.g. fusion_attn.0.0.module.norm.weight: plain containers under the reference's names
             *path, leaf = name.split(".")
             at = self
@@ -136,11 +147,11 @@ class TrainableBCPolicy(nn.Module):
                     at.add_module(part, nn.Module())
                 at = at._modules[part]
             at.register_parameter(leaf, nn.Parameter(state_dict[name].detach().to(device=dev, copy=True)))
-        index = BP.pack_index(num_stack, num_layer, head_num_layers, n_components)
+        index = BP.pack_index(num_stack, num_layer, head_num_layers, n_components, network_dim=D)
         self.register_buffer("_index", torch.from_numpy(index).to(dev), persistent=False)
         self.register_buffer("_zero", torch.zeros(1, dtype=torch.float32, device=dev), persistent=False)
-        self._sizes = (BP.scratch_floats(max_agents, chunk_rows),
-                       grad_scratch_floats(max_agents, chunk_rows, num_layer, int(index.size)), partials * self._G)
+        self._sizes = (BP.scratch_floats(max_agents, chunk_rows, D),
+                       grad_scratch_floats(max_agents, chunk_rows, num_layer, int(index.size), network_dim=D), partials * self._G)
         self._scratch = self._grad_scratch = self._partials = None
 
     def _workspace(self, dev):
@@ -153,20 +164,28 @@ class TrainableBCPolicy(nn.Module):
         return cls(state_dict, max_agents, num_stack, **kw)
 
     def _policy_struct(self, blob):
-        p = _capi.GdBCPolicy()
+        """A fresh gd_bc_policy, or at 128 the gd_bc_policy_dim that holds it (what the entries of `_BCStep` take)."""
+        if self._wide:
+            pd = _capi.GdBCPolicyDim()
+            pd.network_dim, pd.reserved = self.network_dim, 0
+            p = pd.base
+        else:
+            pd = p = _capi.GdBCPolicy()
         p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = self.max_agents, self.num_stack, *self.num_layer
         p.head_layers, p.n_components, p.clip_value, p.chunk_rows = self.head_num_layers, self.n_components, self.clip_value, self.chunk_rows
         p.blob, p.blob_floats = blob.data_ptr(), blob.numel()
         p.scratch, p.scratch_floats = self._scratch.data_ptr(), self._scratch.numel()
-        return p
+        return pd
 
     def nbytes(self, B):
         """An upper bound on everything a step (forward plus backward) of B rows touches beyond its inputs, in bytes.  The
         part that does not depend on B: the flat weights and the blob of the step, the flat gradient and the `.grad`
         tensors of a first backward, the allocator's rounding; and what the module allocates at its first forward: the forward's scratch
-        (chunk_rows * 3 * (A + 200) * 64 floats), the backward's (the transposed weights and chunk_rows * (A + 200) * (64 *
-        (layers + 5) + 16) floats) and `partials` times the parameters.  Per row: the nll, its upstream gradient and that
-        gradient's contiguous float32 copy."""
+        (chunk_rows * 3 * (A + 200) * network_dim floats), the backward's (the transposed weights and chunk_rows * (A + 200) *
+        (network_dim * (layers + 5) + 16) floats) and `partials` times the parameters.  Per row: the nll, its upstream gradient
+        and that gradient's contiguous float32 copy.  At the reference sweep's model (network_dim 128, num_layer (4, 3), num_stack 5,
+        6 components) the parameters are 1,399,274 floats and the default 128 partials 716 MB: pass a smaller `partials` where
+        that is too much."""
         G = self._G
         fixed = 4 * ((G + 1) + int(self._index.numel()) + 2 * G) + 512 * _ALLOCATIONS
         once = 4 * sum(self._sizes) + 512 * 3
@@ -205,3 +224,9 @@ class TrainableBCPolicy(nn.Module):
             params.append(p)
         self._workspace(dev)
         return _BCStep.apply(self, obs, partner_mask, road_mask, expert_actions, *params)
+
+
+class TrainableBCPolicyDim(TrainableBCPolicy):
+    """`TrainableBCPolicy` at every width the backward is built at: `network_dim=64` (the default; the same C calls and bits
+    as `TrainableBCPolicy`) or `network_dim=128`, the reference sweep's model."""
+    NETWORK_DIMS = (BP.DIM, 128)

@@ -30,7 +30,7 @@
 // 2 F + 2 S + 3 launches per chunk for F fusion and S branch layers.  Every sum has one owner and a fixed order; no atomics; no
 // host synchronisation; every byte of every output given is stored on every call.  Masks are read with byte loads (their rows
 // have odd pitch).  An MFMA is a chain of fmaf in k order with one rounding per product; everything else rounds every operation.
-// The backward (bc_grad.hip, 64 only) reruns these kernels per chunk through launch_bc_embed, launch_bc_self_layer,
+// The backward (bc_grad.hip, at either width) reruns these kernels per chunk through launch_bc_embed, launch_bc_self_layer,
 // launch_bc_cross_kv and launch_bc_head; its SAVE instantiation of the attention kernel also stores the attention output
 // before o_proj and the softmax's row statistics.
 // The forward on a row list (gd_bc_forward_rows, launch_bc_forward_rows) is the same launches on the kernels' list
@@ -123,8 +123,8 @@ __global__ __launch_bounds__(64) void k_bc_kv(BCDims d, Segs sg, const float *__
 __device__ __forceinline__ float *bc_save_o(float *osave, float *) { return osave; }
 __device__ __forceinline__ float *bc_save_ml(float *, float *ml) { return ml; }
 
-// grid (sum of tiles, rows).  Save = (float *osave, float *ml), at 64 only: also store the attention output before o_proj (osave
-// [b][token][64]) and per (token, head) the softmax's final running max and its sum (ml [b][token][8]: m of the four heads,
+// grid (sum of tiles, rows).  Save = (float *osave, float *ml): also store the attention output before o_proj (osave
+// [b][token][32 T]) and per (token, head) the softmax's final running max and its sum (ml [b][token][8]: m of the four heads,
 // then the four sums), for the backward.  Save = (BCRows): the forward on a row list, the masks are the whole call's, X / K / V
 // are indexed by slot
 template <int T, class... Save>
@@ -136,7 +136,6 @@ __global__ __launch_bounds__(64) void k_bc_attn(BCDims d, Segs sg, const float *
     constexpr int FE = E::FE, HC = E::HC;
     constexpr bool SAVE = sizeof...(Save) == 2, LIST = sizeof...(Save) == 1;
     constexpr bool KEEP_X = T == 2;  // a register-pressure decision: at 128 the layer's input is read again for the residual
-    static_assert(!SAVE || T == 2, "the backward exists at network_dim 64 only");
     __shared__ unsigned char msk[MAX_TOKENS];
     const int lane = threadIdx.x, h = lane >> 5, col = lane & 31;
     const int slot = blockIdx.y;
@@ -663,33 +662,62 @@ void launch_bc_forward_rows(const gd_bc_policy &p, int dim, hipStream_t st, cons
         forward_rows<2>(p, st, obs, partner_mask, road_mask, n, a, rows, count, readout);
 }
 
-// ---- the forward's launches one by one at 64, for the backward's recomputation
+// ---- the forward's launches one by one at network_dim dim, for the backward's recomputation (and the probe's, at 64)
 
-void launch_bc_embed(const gd_bc_policy &p, hipStream_t st, const float *obs, int rows, float *X) {
-    embed<2>(p, st, obs, (unsigned)rows, X);
-}
+namespace {
 
-void launch_bc_self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows,
-                          int layer, float *X, float *Kb, float *Vb, float *osave, float *ml) {
-    const Segs sg = bc_layer_segs<2>(p, layer);
-    kv<2>(p, st, sg, (unsigned)rows, X, Kb, Vb);
+template <int T>
+void self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows, int layer, float *X,
+                float *Kb, float *Vb, float *osave, float *ml) {
+    const Segs sg = bc_layer_segs<T>(p, layer);
+    kv<T>(p, st, sg, (unsigned)rows, X, Kb, Vb);
     if (osave)
-        attn<2>(p, st, sg, pm, rm, (unsigned)rows, X, Kb, Vb, osave, ml);
+        attn<T>(p, st, sg, pm, rm, (unsigned)rows, X, Kb, Vb, osave, ml);
     else
-        attn<2>(p, st, sg, pm, rm, (unsigned)rows, X, Kb, Vb);
+        attn<T>(p, st, sg, pm, rm, (unsigned)rows, X, Kb, Vb);
 }
 
-void launch_bc_cross_kv(const gd_bc_policy &p, hipStream_t st, int rows, const float *X, float *Kb, float *Vb) {
-    kv<2>(p, st, bc_cross_segs<2>(p), (unsigned)rows, X, Kb, Vb);
+template <int T>
+void head_of_chunk(const gd_bc_policy &p, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask, int r0,
+                   int rows, const BCHeadArgs &a, const float *X, const float *Kb, const float *Vb) {
+    const int A = p.max_agents, R = p.num_stack;
+    head<T>(p, st, partner_mask + (size_t)r0 * R * (A - 1), road_mask + (size_t)r0 * R * ROADS, (unsigned)rows,
+            offset(a, r0, A, BCEnc<T>::CTX), X, Kb, Vb);
+}
+
+}  // namespace
+
+void launch_bc_embed(const gd_bc_policy &p, int dim, hipStream_t st, const float *obs, int rows, float *X) {
+    if (dim == 128)
+        embed<4>(p, st, obs, (unsigned)rows, X);
+    else
+        embed<2>(p, st, obs, (unsigned)rows, X);
+}
+
+void launch_bc_self_layer(const gd_bc_policy &p, int dim, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows,
+                          int layer, float *X, float *Kb, float *Vb, float *osave, float *ml) {
+    if (dim == 128)
+        self_layer<4>(p, st, pm, rm, rows, layer, X, Kb, Vb, osave, ml);
+    else
+        self_layer<2>(p, st, pm, rm, rows, layer, X, Kb, Vb, osave, ml);
+}
+
+void launch_bc_cross_kv(const gd_bc_policy &p, int dim, hipStream_t st, int rows, const float *X, float *Kb, float *Vb) {
+    if (dim == 128)
+        kv<4>(p, st, bc_cross_segs<4>(p), (unsigned)rows, X, Kb, Vb);
+    else
+        kv<2>(p, st, bc_cross_segs<2>(p), (unsigned)rows, X, Kb, Vb);
 }
 
 // the masks, u, z, expert_actions and every output are the WHOLE call's; the chunk is its rows r0 .. r0 + rows
-void launch_bc_head(const gd_bc_policy &p, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask, int r0,
-                    int rows, bool deterministic, const float *u, const float *z, const float *expert_actions,
+void launch_bc_head(const gd_bc_policy &p, int dim, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask,
+                    int r0, int rows, bool deterministic, const float *u, const float *z, const float *expert_actions,
                     const gd_bc_outputs &out, const float *X, const float *Kb, const float *Vb) {
-    const int A = p.max_agents, R = p.num_stack;
-    head<2>(p, st, partner_mask + (size_t)r0 * R * (A - 1), road_mask + (size_t)r0 * R * ROADS, (unsigned)rows,
-            offset(head_args(p, deterministic, u, z, expert_actions, out), r0, A, BCEnc<2>::CTX), X, Kb, Vb);
+    const BCHeadArgs a = head_args(p, deterministic, u, z, expert_actions, out);
+    if (dim == 128)
+        head_of_chunk<4>(p, st, partner_mask, road_mask, r0, rows, a, X, Kb, Vb);
+    else
+        head_of_chunk<2>(p, st, partner_mask, road_mask, r0, rows, a, X, Kb, Vb);
 }
 
 void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,

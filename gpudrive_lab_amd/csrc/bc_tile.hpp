@@ -3,7 +3,7 @@
 // features 32 t + acc_row(r, h)), the Linear and the LayerNorm on it, the one-token helpers of the head kernels, and the
 // segments a self-attention launch covers.  Everything has internal linkage: each translation unit compiles its own.
 // The encoder's width is a parameter, T = network_dim / 32 tiles per token: 2 (network_dim 64, every kernel) or 4 (128, the
-// forward only).  The tile helpers deduce T from the accumulator array; the widths and the offsets of a layer's fields are
+// forward and the backward).  The tile helpers deduce T from the accumulator array; the widths and the offsets of a layer's fields are
 // BCEnc<T>; the layout and the segments are templates on T.  A file that exists at 64 only names BCEnc<2> once.  At T = 2
 // everything here compiles to the code it was before there was a T (tools/isa_same.py is how that is checked).
 #pragma once

@@ -2388,15 +2388,15 @@ int gd_multi_policy_rollout(gd_sim *s, const gd_policy_set *set, const gd_policy
     });
 }
 
-// everything gd_bc_backward refuses; nullptr when everything is in order
+// everything the BC backward refuses at network_dim dim (64 or 128), whoever calls it; nullptr when everything is in order
 static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll,
-                                       const float *nll, const float *grad) {
+                                       const float *nll, const float *grad, int dim) {
     const char *why = nullptr;
     gd_bc_outputs none{};
     if (!g || !expert_actions || !grad_nll || !grad)
         why = "null argument";
-    else if ((why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &none, 64)))
+    else if ((why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &none, dim)))
         ;
     else if (g->num_partials < 1 || g->num_partials > 4096)
         why = "num_partials must be in [1, 4096]";
@@ -2404,11 +2404,15 @@ static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *
         why = "reserved must be 0";
     else if (!g->scratch || !g->partials)
         why = "scratch and partials are required";
-    else if (g->grad_floats != gd::bc_grad_floats(p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
-        why = "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
-    else if (g->scratch_floats < gd::bc_grad_scratch_floats(p->max_agents, p->chunk_rows, p->fusion_layers, p->branch_layers, p->blob_floats))
-        why = "grad scratch_floats is below blob_floats rounded up to 64 + chunk_rows * (max_agents + 200) * (64 * (fusion_layers + "
-              "branch_layers + 5) + 16)";
+    else if (g->grad_floats != gd::bc_grad_floats(dim, p->num_stack, p->fusion_layers, p->branch_layers, p->head_layers, p->n_components))
+        why = dim == 128 ? "grad_floats is not the parameters' count at network_dim 128 for these layer counts, num_stack and n_components"
+                         : "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
+    else if (g->scratch_floats <
+             gd::bc_grad_scratch_floats(dim, p->max_agents, p->chunk_rows, p->fusion_layers, p->branch_layers, p->blob_floats))
+        why = dim == 128 ? "grad scratch_floats is below blob_floats rounded up to 64 + chunk_rows * (max_agents + 200) * (128 * "
+                           "(fusion_layers + branch_layers + 5) + 16)"
+                         : "grad scratch_floats is below blob_floats rounded up to 64 + chunk_rows * (max_agents + 200) * (64 * "
+                           "(fusion_layers + branch_layers + 5) + 16)";
     else if (misaligned(g->scratch, 256) || misaligned(g->partials, 16) || misaligned(grad, 16))
         why = "grad scratch must be 256-byte aligned, partials and grad 16-byte aligned";
     else if (misaligned(grad_nll, 4) || misaligned(nll, 4))
@@ -2416,16 +2420,31 @@ static const char *bc_backward_problem(const gd_bc_policy *p, const gd_bc_grad *
     return why;
 }
 
+// The one checked backward behind gd_bc_backward and gd_bc_backward_dim.  The order of refusal: the _dim struct, then the
+// policy, the buffers and the gradient's sizes at its width.
+static int bc_backward(const char *who, BCAt at, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                       const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
+                       void *stream) {
+    const char *why = at.why;
+    if (!why) why = bc_backward_problem(at.p, g, obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll, grad, at.dim);
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
+    return guarded([&]() {
+        gd::launch_bc_backward(*at.p, at.dim, *g, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, expert_actions,
+                               grad_nll, nll, grad);
+        HIP_CHECK(hipGetLastError());
+    });
+}
+
 int gd_bc_backward(const gd_bc_policy *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                    const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll, float *grad,
                    void *stream) {
-    if (const char *why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll, grad))
-        return fail(GD_ERR_INVALID, std::string("gd_bc_backward: ") + why);
-    return guarded([&]() {
-        gd::launch_bc_backward(*p, *g, static_cast<hipStream_t>(stream), obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll,
-                               grad);
-        HIP_CHECK(hipGetLastError());
-    });
+    return bc_backward("gd_bc_backward", bc_at(p), g, obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll, grad, stream);
+}
+
+int gd_bc_backward_dim(const gd_bc_policy_dim *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                       const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll,
+                       float *grad, void *stream) {
+    return bc_backward("gd_bc_backward_dim", bc_at(p), g, obs, partner_mask, road_mask, n, expert_actions, grad_nll, nll, grad, stream);
 }
 
 // everything gd_bc_train_rows refuses; nullptr when everything is in order
@@ -2459,7 +2478,7 @@ static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
     if (o->head_layers < 0 || o->head_layers > 4) return "head_layers must be in [0, 4]";
     if (o->n_components < 1 || o->n_components > 16) return "n_components must be in [1, 16]";
     if (o->reserved != 0) return "reserved must be 0";
-    if (o->grad_floats != gd::bc_grad_floats(o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+    if (o->grad_floats != gd::bc_grad_floats(64, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
         return "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
     if (o->blob_floats != gd::bc_blob_floats(64, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
         return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
@@ -2499,7 +2518,7 @@ int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *op
         why = "null argument (expert_actions, or opt's actions, nll, grad_nll or grad)";
     if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out, 64);
     if (!why) why = bc_train_rows_problem(opt, n, o.nll, o.actions, expert_actions, o.grad_nll);
-    if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
+    if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad, 64);
     if (!why) why = bc_adamw_problem(opt, o.grad);
     if (!why && (o.max_rows < 1 || o.max_rows > (1 << 20))) why = "max_rows must be in [1, 2^20]";
     if (!why && n > o.max_rows) why = "n is above max_rows (the row scratch holds max_rows rows)";
@@ -2513,7 +2532,7 @@ int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *op
         hipStream_t st = static_cast<hipStream_t>(stream);
         gd::launch_bc_forward(*p, 64, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
         gd::launch_bc_train_rows(o, st, n, o.nll, o.actions, expert_actions, o.grad_nll);
-        gd::launch_bc_backward(*p, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
+        gd::launch_bc_backward(*p, 64, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
         gd::launch_bc_adamw(o, st, o.grad);
         HIP_CHECK(hipGetLastError());
     });

@@ -347,22 +347,23 @@ void launch_bc_readout(const gd_bc_policy &p, hipStream_t st, const gd_bc_readou
                        const float *X, const int32_t *rows, const int32_t *count, int n);
 void launch_bc_eval_accumulate(hipStream_t st, int n, const float *nll, const float *actions, const float *expert_actions,
                                float *acc);  // bc_policy.hip (one launch)
-// bc_policy.hip: the forward's launches one by one, for the backward's recomputation (bc_grad.hip).  The masks of
+// bc_policy.hip: the forward's launches one by one at network_dim dim (64 or 128), for the backward's recomputation
+// (bc_grad.hip) and the probe's hidden states (lp_probe.hip, 64).  The masks of
 // launch_bc_self_layer and obs of launch_bc_embed are the CHUNK's; launch_bc_head takes the whole call's and the chunk's first row.
 // osave / ml non-null: the attention kernel's SAVE instantiation (the output before o_proj, the softmax's row statistics)
-void launch_bc_embed(const gd_bc_policy &p, hipStream_t st, const float *obs, int rows, float *X);
-void launch_bc_self_layer(const gd_bc_policy &p, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows,
+void launch_bc_embed(const gd_bc_policy &p, int dim, hipStream_t st, const float *obs, int rows, float *X);
+void launch_bc_self_layer(const gd_bc_policy &p, int dim, hipStream_t st, const unsigned char *pm, const unsigned char *rm, int rows,
                           int layer, float *X, float *Kb, float *Vb, float *osave, float *ml);
-void launch_bc_cross_kv(const gd_bc_policy &p, hipStream_t st, int rows, const float *X, float *Kb, float *Vb);
-void launch_bc_head(const gd_bc_policy &p, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask, int r0,
-                    int rows, bool deterministic, const float *u, const float *z, const float *expert_actions,
+void launch_bc_cross_kv(const gd_bc_policy &p, int dim, hipStream_t st, int rows, const float *X, float *Kb, float *Vb);
+void launch_bc_head(const gd_bc_policy &p, int dim, hipStream_t st, const unsigned char *partner_mask, const unsigned char *road_mask,
+                    int r0, int rows, bool deterministic, const float *u, const float *z, const float *expert_actions,
                     const gd_bc_outputs &out, const float *X, const float *Kb, const float *Vb);
-// bc_grad.hip
-long long bc_grad_floats(int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);
-long long bc_grad_scratch_floats(int max_agents, int chunk_rows, int fusion_layers, int branch_layers, long long blob_floats);
-void launch_bc_backward(const gd_bc_policy &p, const gd_bc_grad &g, hipStream_t st, const float *obs, const unsigned char *partner_mask,
-                        const unsigned char *road_mask, int n, const float *expert_actions, const float *grad_nll, float *nll,
-                        float *grad);
+// bc_grad.hip: the parameters' count, the backward's scratch and the backward itself at network_dim dim (64 or 128)
+long long bc_grad_floats(int dim, int num_stack, int fusion_layers, int branch_layers, int head_layers, int n_components);
+long long bc_grad_scratch_floats(int dim, int max_agents, int chunk_rows, int fusion_layers, int branch_layers, long long blob_floats);
+void launch_bc_backward(const gd_bc_policy &p, int dim, const gd_bc_grad &g, hipStream_t st, const float *obs,
+                        const unsigned char *partner_mask, const unsigned char *road_mask, int n, const float *expert_actions,
+                        const float *grad_nll, float *nll, float *grad);
 // bc_opt.hip
 int bc_num_tensors(int fusion_layers, int branch_layers, int head_layers);  // the tensors of the state dict
 void launch_bc_train_rows(const gd_bc_opt &o, hipStream_t st, int n, const float *nll, const float *actions,

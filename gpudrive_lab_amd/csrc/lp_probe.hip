@@ -335,10 +335,10 @@ __global__ __launch_bounds__(NT) void k_lp_adamw(int K, P::AdamCoefs c, float we
 void launch_tap(const gd_bc_policy &p, hipStream_t st, const float *obs, const unsigned char *pm, const unsigned char *rm, int r0,
                 int rows, int tap, float *X, float *Kb, float *Vb, int layer = -1) {
     const BCDims d = bc_dims(p);
-    launch_bc_embed(p, st, obs + (size_t)r0 * d.R * d.D, rows, X);
+    launch_bc_embed(p, 64, st, obs + (size_t)r0 * d.R * d.D, rows, X);
     const int layers = layer < 0 ? p.fusion_layers + (tap == GD_LP_TAP_RO ? p.branch_layers : 0) : bc_tap_layer(p, tap, layer) + 1;
     for (int i = 0; i < layers; i++)
-        launch_bc_self_layer(p, st, pm + (size_t)r0 * d.R * (d.A - 1), rm + (size_t)r0 * d.R * ROADS, rows, i, X, Kb, Vb, nullptr, nullptr);
+        launch_bc_self_layer(p, 64, st, pm + (size_t)r0 * d.R * (d.A - 1), rm + (size_t)r0 * d.R * ROADS, rows, i, X, Kb, Vb, nullptr, nullptr);
 }
 
 }  // namespace

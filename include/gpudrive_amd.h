@@ -1132,8 +1132,8 @@ int gd_bc_rollout_readout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_r
  * LayerNorm, q / k / v / o projection and MLP Linear is 128 wide, the 4 heads have 32 channels (q is multiplied once, after the
  * bias, by the float32 nearest to 32^-1/2), the context is [n][384], head.input_layer is 384 -> 64 and the GMM head behind it
  * stays 64 wide.  At 128: base.blob_floats is the layout's at that width (`pack_index(..., network_dim=128)`) and
- * base.scratch_floats >= chunk_rows * 3 * (A + 200) * 128.  The inference side only: the backward, the update, gd_bc_hidden, the
- * linear probes and the read-outs take a gd_bc_policy and stay 64 wide. */
+ * base.scratch_floats >= chunk_rows * 3 * (A + 200) * 128.  The forward, the closed loop and the backward (gd_bc_backward_dim)
+ * take it; the update, gd_bc_hidden, the linear probes and the read-outs take a gd_bc_policy and stay 64 wide. */
 typedef struct gd_bc_policy_dim {
     gd_bc_policy base;
     int32_t network_dim;  /* 64 or 128 */
@@ -1150,6 +1150,16 @@ int gd_bc_forward_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t
 int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const uint8_t *partner_mask, const uint8_t *road_mask,
                            int32_t n, int32_t deterministic, const float *u, const float *z, const float *expert_actions,
                            const gd_bc_outputs *out, const int32_t *rows, const int32_t *count, void *stream);
+/* gd_bc_backward at p->network_dim: the same arguments, checks, guarantees and stages.  At 64 it runs gd_bc_backward's own
+ * launches and gives its bits.  At 128 (csrc/bc_grad.hip at T = 4): g->grad_floats is the parameters' count at that width,
+ * g->scratch_floats >= blob_floats rounded up to 64 + chunk_rows * (A + 200) * (128 * (fusion_layers + branch_layers + 5) + 16);
+ * nll is gd_bc_forward_dim's bit for bit; the head's stage is a workgroup of 128 threads per row whose sums across its two
+ * waves go through LDS in ascending order.  No atomics; equal inputs, chunk_rows and num_partials give equal bits.
+ * GD_ERR_INVALID, before any launch: whatever gd_bc_backward refuses, a network_dim other than 64 or 128, reserved != 0, a
+ * blob, scratch, grad_floats or grad scratch_floats not that width's. */
+int gd_bc_backward_dim(const gd_bc_policy_dim *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
+                       const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll,
+                       float *grad, void *stream);
 /* The closed-loop episode at p->network_dim: gd_bc_rollout (rows == NULL, reads == NULL), gd_bc_rollout_compact (rows) or
  * gd_bc_rollout_readout (reads) with that forward in the loop, every output as those define it.  reads->ego_attn_score is
  * allowed at either width; reads->readout must be NULL unless network_dim is 64 (GD_ERR_INVALID: the probes read 64-wide

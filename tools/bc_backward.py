@@ -7,6 +7,10 @@
   (b) the differentiable stand-in of tests/bc_grad_reference.py (Net: the reference's operators under eager torch float32
       autograd) on the same device, the same weights and the same inputs.
 
+With --dim 128 the model is the reference sweep's (network_dim 128, num_layer (4, 3)): (a) is TrainableBCPolicyDim
+(gd_bc_forward_dim, gd_bc_backward_dim), (b) the stand-in of tests/bc_wide_grad_reference.py; the result also carries the
+launches per chunk.  profiles/bc_wide_backward.json is `--dim 128 --out` of it.
+
 Inputs are tools/bc_forward.py's: synthetic observations uniform in [-1, 1], masks 40 % padding.  (a) and (b) alternate in one
 process, --runs each: device events around --calls steps after a warm-up.  Reported: the median and the range of the
 microseconds per step, the peak device memory either side allocates during a step, (a)'s forward alone (the share of the
@@ -15,7 +19,7 @@ relative difference between (a)'s and (b)'s gradients per tensor.
 The per-kernel split takes two more steps, the second without a device:
   1. rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bc_backward.py --runs 1 --calls 5 --only a
   2. tools/bc_backward.py --merge FILE --kernel-stats DIR/.../*_kernel_stats.csv
-tools/bc_backward.py [--rows 512] [--agents 128] [--stack 5] [--runs 3] [--calls 10] [--only a] [--out FILE]"""
+tools/bc_backward.py [--dim 64] [--rows 512] [--agents 128] [--stack 5] [--runs 3] [--calls 10] [--only a] [--out FILE]"""
 import argparse
 import csv
 import json
@@ -31,10 +35,11 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from bc_forward import peak_bytes, summary, timed  # noqa: E402
-from gpudrive_lab_amd import TrainableBCPolicy  # noqa: E402
+from gpudrive_lab_amd import TrainableBCPolicyDim  # noqa: E402  (at 64 it is TrainableBCPolicy: the same C calls)
 from gpudrive_lab_amd.bc_policy import obs_width  # noqa: E402
 from tests import bc_cases as BC  # noqa: E402
 from tests import bc_grad_reference as GR  # noqa: E402
+from tests import bc_wide_grad_reference as WGR  # noqa: E402
 
 
 def merge(path, stats):
@@ -55,6 +60,7 @@ def merge(path, stats):
 
 def arguments():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dim", type=int, choices=(64, 128), default=64)
     ap.add_argument("--rows", type=int, default=512)
     ap.add_argument("--agents", type=int, default=128)
     ap.add_argument("--stack", type=int, default=5)
@@ -70,11 +76,17 @@ def arguments():
 
 
 def main(args):
-    B, A, R, cfg = args.rows, args.agents, args.stack, BC.CFG
-    sd = BC.state_dict(R, cfg)
+    B, A, R = args.rows, args.agents, args.stack
+    cfg = BC.CFG if args.dim == 64 else BC._cfg((4, 3), 2, 6, -20.0)
+    sd = BC.state_dict(R, cfg, network_dim=args.dim)
     kw = {} if args.chunk_rows is None else dict(chunk_rows=args.chunk_rows)
-    tbp = TrainableBCPolicy.from_state_dict(sd, max_agents=A, num_stack=R, device="cuda", partials=args.partials, **cfg, **kw)
-    res = dict(tool="tools/bc_backward.py", rows=B, slots=A, num_stack=R, obs_width=obs_width(A), config=cfg, runs=args.runs,
+    tbp = TrainableBCPolicyDim.from_state_dict(sd, max_agents=A, num_stack=R, device="cuda", partials=args.partials,
+                                               network_dim=args.dim, **cfg, **kw)
+    layers = sum(cfg["num_layer"])
+    # per chunk: the forward (embed, kv + attn per layer, cross kv, no head without nll), XS copies, head, kvx, then per layer a
+    # copy, kv, attn<SAVE>, post, dq, dkv, and the embedders
+    res = dict(tool="tools/bc_backward.py", network_dim=args.dim, backward_launches_per_chunk=1 + 3 * layers + 1 + 2 + 6 * layers + 1,
+               parameters=tbp._G, rows=B, slots=A, num_stack=R, obs_width=obs_width(A), config=cfg, runs=args.runs,
                calls=args.calls, observations="synthetic", source_stamp=bench.source_stamp(), chunk_rows=tbp.chunk_rows,
                partials=tbp.partials, a_nbytes=tbp.nbytes(B))
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -97,7 +109,7 @@ def main(args):
     if args.only == "a":
         a_us = [timed(step_a, args.calls) for _ in range(args.runs)]
     else:
-        net = GR.Net(sd, A, cfg, torch.float32, device="cuda")
+        net = (GR.Net if args.dim == 64 else WGR.Net)(sd, A, cfg, torch.float32, device="cuda")
 
         def step_b():
             for p in net.params.values():

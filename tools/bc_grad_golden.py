@@ -3,8 +3,10 @@
 tests/bc_grad_reference.py, call `gmm_loss(net, context, expert)[0].backward()`, and write tests/golden/bc_grad_<B>_<A>_<R>.npz:
 per parameter tensor of the module, in its own order, the gradient's sum, its L2 norm and its values at 32 seeded positions
 (not whole gradients), and the loss.  Results and names only: the weights and the inputs come from the seeds.
+With --dim 128 the same at network_dim 128 (head_dim 64) on bc_wide_cases' `wide_min` with the inputs of
+tests/bc_wide_grad_reference.py: tests/golden/bc_wide_grad_wide_min.npz.
 
-    tools/bc_grad_golden.py /path/to/reference/checkout
+    tools/bc_grad_golden.py /path/to/reference/checkout [--dim 128]
     tools/bc_grad_golden.py --seeds        # no reference needed: search the input seeds that keep the margins, print the table
 
 Runs where the reference checkout is; never part of a test run."""
@@ -20,8 +22,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from tests import bc_cases as BC  # noqa: E402
 from tests import bc_grad_reference as GR  # noqa: E402
+from tests import bc_wide_cases as WC  # noqa: E402
+from tests import bc_wide_grad_reference as WGR  # noqa: E402
 
 GOLDEN_CASE = (3, 64, 1)  # samples a, b and c; the smallest of bc_cases.SHAPES
+WIDE_GOLDEN_CASE = "wide_min"  # the same three samples at network_dim 128
 POSITIONS = 32
 
 
@@ -52,14 +57,21 @@ def main():
         return seeds()
     from bc_reference_golden import load_reference
     mods = load_reference(sys.argv[1])
-    cfg = BC.CFG
-    B, A, R = GOLDEN_CASE
+    dim = int(sys.argv[sys.argv.index("--dim") + 1]) if "--dim" in sys.argv else 64
+    if dim == 128:
+        sd, obs, pm, rm, expert, _, A, cfg = WGR.case_inputs(WIDE_GOLDEN_CASE)
+        B, R = len(obs), WC.CASES[WIDE_GOLDEN_CASE][2]
+        path = os.path.join(ROOT, "tests", "golden", "bc_wide_grad_%s.npz" % WIDE_GOLDEN_CASE)
+    else:
+        cfg = BC.CFG
+        B, A, R = GOLDEN_CASE
+        sd, obs, pm, rm, expert, _ = GR.case_inputs(B, A, R)
+        path = os.path.join(ROOT, "tests", "golden", "bc_grad_%d_%d_%d.npz" % GOLDEN_CASE)
     env = types.SimpleNamespace(ego_state=True, partner_obs=True, road_map_obs=True, max_num_agents_in_scene=A, roadgraph_top_k=200)
-    exp = types.SimpleNamespace(network_dim=64, network_num_layers=4, act_func="tanh", dropout=0.0, num_layer=cfg["num_layer"],
+    exp = types.SimpleNamespace(network_dim=dim, network_num_layers=4, act_func="tanh", dropout=0.0, num_layer=cfg["num_layer"],
                                 num_head=4, head_dim=64, head_num_layers=cfg["head_num_layers"], n_components=cfg["n_components"],
                                 action_dim=3, clip_value=cfg["clip_value"])
     net = mods["model"].EarlyFusionAttnBCNet(env, exp, num_stack=R).double().train()  # dropout 0.0: train mode is eval mode
-    sd, obs, pm, rm, expert, _ = GR.case_inputs(B, A, R)
     net.load_state_dict({k: v.double() for k, v in sd.items()})
     context, _, _ = net.get_context(torch.from_numpy(obs).double(), [torch.from_numpy(pm), torch.from_numpy(rm)])
     loss, _ = mods["loss"].gmm_loss(net, context, torch.from_numpy(expert).double())
@@ -69,7 +81,6 @@ def main():
         g = p.grad.numpy().reshape(-1)
         pos = positions(i, g.size)
         names.append(name), sums.append(g.sum()), norms.append(np.sqrt((g * g).sum())), at.append(pos), vals.append(g[pos])
-    path = os.path.join(ROOT, "tests", "golden", "bc_grad_%d_%d_%d.npz" % GOLDEN_CASE)
     np.savez_compressed(path, names=np.array(names), sums=np.array(sums), norms=np.array(norms), positions=np.array(at),
                         values=np.array(vals), loss=np.array(float(loss.detach())))
     print(path, os.path.getsize(path), "bytes")
