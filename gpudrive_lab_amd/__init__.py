@@ -12,9 +12,9 @@ def __getattr__(name):
     if name in ("TrainableBCPolicy", "TrainableBCPolicyDim"):
         from . import bc_train
         return getattr(bc_train, name)
-    if name == "DeviceBC":
-        from .bc_opt import DeviceBC
-        return DeviceBC
+    if name in ("DeviceBC", "DeviceBCDim"):
+        from . import bc_opt
+        return getattr(bc_opt, name)
     if name in ("ClosedLoopBC", "ClosedLoopEpisode"):
         from . import bc_rollout
         return getattr(bc_rollout, name)

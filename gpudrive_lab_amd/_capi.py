@@ -359,7 +359,7 @@ SYMBOLS = [
     "gd_policy_forward_dropout", "gd_policy_evaluate_dropout", "gd_policy_backward_dropout", "gd_ppo_update_dropout",
     "gd_bc_forward", "gd_bc_backward", "gd_bc_eval_accumulate", "gd_bc_train_rows", "gd_bc_adamw", "gd_bc_update",
     "gd_bc_rollout", "gd_policy_rollout", "gd_live_rows", "gd_policy_forward_rows", "gd_policy_rollout_compact", "gd_owned_rows", "gd_policy_forward_owned",
-    "gd_multi_policy_rollout", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_bc_hidden_layer", "gd_bc_forward_readout", "gd_bc_forward_rows_readout", "gd_bc_rollout_readout", "gd_bc_forward_dim", "gd_bc_forward_rows_dim", "gd_bc_rollout_dim", "gd_bc_backward_dim", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
+    "gd_multi_policy_rollout", "gd_bc_forward_rows", "gd_bc_rollout_compact", "gd_bc_hidden", "gd_bc_hidden_layer", "gd_bc_forward_readout", "gd_bc_forward_rows_readout", "gd_bc_rollout_readout", "gd_bc_forward_dim", "gd_bc_forward_rows_dim", "gd_bc_rollout_dim", "gd_bc_backward_dim", "gd_bc_adamw_dim", "gd_bc_update_dim", "gd_lp_forward", "gd_lp_update", "gd_lp_eval_accumulate", "gd_episode_step",
     "gd_sync",
     "gd_pack_observations_conditioned", "gd_episode_draw_weights", "gd_episode_set_warmup",
     "gd_set_learner_rows", "gd_attach_packed_rows", "gd_attach_packed_rows_conditioned", "gd_set_discrete_actions",
@@ -485,6 +485,9 @@ def lib():
                                     C.POINTER(GdBCRolloutRows), C.POINTER(GdBCRolloutReads), C.c_int32]
     L.gd_bc_backward_dim.argtypes = ([C.POINTER(GdBCPolicyDim), C.POINTER(GdBCGrad), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32] +
                                      [C.c_void_p] * 5)
+    L.gd_bc_adamw_dim.argtypes = [C.POINTER(GdBCOpt), C.c_int32, C.c_void_p, C.c_void_p]
+    L.gd_bc_update_dim.argtypes = ([C.POINTER(GdBCPolicyDim), C.POINTER(GdBCGrad), C.POINTER(GdBCOpt)] + [C.c_void_p] * 3 +
+                                   [C.c_int32, C.c_void_p, C.c_void_p])
     lp = [C.POINTER(GdBCPolicy), C.POINTER(GdLPProbe), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.gd_lp_forward.argtypes = lp + [C.POINTER(GdLPRows), C.c_void_p]
     L.gd_lp_update.argtypes = lp + [C.c_void_p, C.c_void_p, C.POINTER(GdLPRows), C.c_void_p]

@@ -19,6 +19,14 @@ stores each updated weight to the flat layout and to the blob, and `bc.policy` f
 forward of the step runs twice, once for the statistics and once inside the backward's recomputation (about 4 % of a step each),
 as it does with `TrainableBCPolicy`, whose autograd forward and backward are the same two calls.
 
+`DeviceBCDim` is the same object at the widths the step is built at, 64 and 128: `network_dim=128` (with head_dim 64 and
+num_layer (4, 3): the model of the reference's sweep, baselines/il/sweep.yaml) is `gd_bc_update_dim`, the same four stages
+through `gd_bc_forward_dim`, `gd_bc_backward_dim` and `gd_bc_adamw_dim`; the optimiser's kernels have no width in them.
+
+    bc = DeviceBCDim(net.state_dict(), max_agents=128, num_stack=5, num_layer=(4, 3), network_dim=128, partials=32)
+
+`DeviceBC` itself keeps refusing any width but 64, as `gd_bc_update` keeps taking a `gd_bc_policy`.
+
 Not here: the aux head / `use_tom`; `l1_loss` / `focal_loss`; non-zero dropout; bf16; amsgrad; best-checkpoint saving and
 wandb logging (the caller's: `evaluate`, `state_dict` and `losses` are what they need); a faster `gd_bc_backward`."""
 import ctypes as C
@@ -35,11 +43,13 @@ STATS = _capi.BC_STATS
 WHO = "DeviceBC: "
 
 
-def blob_of(num_stack, num_layer, head_num_layers, n_components):
-    """The inverse of `bc_policy.pack_index`: blob_of[e] is the one place of flat parameter e in `gd_bc_policy.blob`.  int32
-    numpy [G].  ValueError if some parameter had no place or more than one (the layout gives every parameter exactly one)."""
-    index = BP.pack_index(num_stack, num_layer, head_num_layers, n_components)
-    G = grad_floats(num_stack, num_layer, head_num_layers, n_components)
+def blob_of(num_stack, num_layer, head_num_layers, n_components, *, network_dim=BP.DIM):
+    """The inverse of `bc_policy.pack_index` at network_dim: blob_of[e] is the one place of flat parameter e in
+    `gd_bc_policy.blob`.  int32 numpy [G].  ValueError if some parameter had no place or more than one (the layout gives every
+    parameter exactly one, at either width)."""
+    width = {} if network_dim == BP.DIM else dict(network_dim=network_dim)  # (64 is both functions' default)
+    index = BP.pack_index(num_stack, num_layer, head_num_layers, n_components, **width)
+    G = grad_floats(num_stack, num_layer, head_num_layers, n_components, **width)
     if index.min() < 0 or index.max() > G or (np.bincount(index, minlength=G + 1)[:G] != 1).any():
         raise ValueError("blob_of: a parameter without exactly one place in the blob")
     inv = np.empty(G + 1, dtype=np.int64)
@@ -79,15 +89,19 @@ def check_opt_args(batch_size, learning_rate, betas, eps, weight_decay, max_grad
 
 
 class DeviceBC:
+    NETWORK_DIMS = (BP.DIM,)  # the widths this name accepts; `DeviceBCDim` is the class at every width that is built
+
     def __init__(self, state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num_head=4, head_num_layers=2,
                  n_components=6, clip_value=-20.0, *, batch_size=512, learning_rate=5e-4, betas=(0.9, 0.999), eps=1e-4,
                  weight_decay=0.01, max_grad_norm=20.0, partials=None, chunk_rows=BP.DEFAULT_CHUNK, device="cuda", **fixed):
         """state_dict and the model arguments: `DeviceBCPolicy`'s (fixed: network_dim, head_dim, network_num_layers, act_func,
-        dropout, action_dim, time_dim, use_tom at the values that are built).  batch_size: the most rows an `update` takes.
-        The hyper-parameters are il.yaml's and il.py:210, 286's: `torch.optim.AdamW(lr, betas, eps, weight_decay)` without
-        amsgrad, `clip_grad_norm_(max_grad_norm)`.  partials, chunk_rows: `TrainableBCPolicy`'s (None: 128 partial
-        gradients).  Everything is allocated here, once (`nbytes`).  Anything not built is a ValueError raised before anything
-        reaches the device."""
+        dropout, action_dim, time_dim, use_tom at the values that are built; network_dim must be one of the class's
+        NETWORK_DIMS).  batch_size: the most rows an `update` takes.  The hyper-parameters are il.yaml's and il.py:210, 286's:
+        `torch.optim.AdamW(lr, betas, eps, weight_decay)` without amsgrad, `clip_grad_norm_(max_grad_norm)`.  partials,
+        chunk_rows: `TrainableBCPolicy`'s (None: 128 partial gradients).  Everything is allocated here, once (`nbytes`):
+        `partials` times the parameters is the largest part -- 150 MB at the defaults, and 716 MB beside 266 MB of backward
+        scratch at the sweep's model (network_dim 128, num_layer (4, 3), 1,399,274 parameters) -- and `partials` is the knob
+        where that is too much.  Anything not built is a ValueError raised before anything reaches the device."""
         unknown = sorted(set(fixed) - BP.FIXED)
         if unknown:
             raise ValueError(WHO + "unknown argument(s) %s" % ", ".join(unknown))
@@ -95,9 +109,11 @@ class DeviceBC:
         model = dict(max_agents=max_agents, num_stack=num_stack, num_layer=num_layer, num_head=num_head,
                      head_num_layers=head_num_layers, n_components=n_components, clip_value=clip_value, chunk_rows=chunk_rows,
                      **fixed)
-        self._shapes = BP.check_bc_args(state_dict, who=WHO, **model)
+        self._shapes = BP.check_bc_args(state_dict, who=WHO, network_dims=self.NETWORK_DIMS, **model)
+        self.network_dim = D = fixed.get("network_dim", BP.DIM)
+        self._wide = D != BP.DIM  # a 64-wide instance of either class calls gd_bc_update
         self.partials = check_opt_args(batch_size, learning_rate, betas, eps, weight_decay, max_grad_norm, partials)
-        self.policy = BP.DeviceBCPolicy(state_dict, device=device, **model)
+        self.policy = BP.DeviceBCPolicy(state_dict, device=device, **model)  # (network_dim travels in `fixed`)
         self.max_agents, self.num_stack, self.num_layer = max_agents, num_stack, num_layer
         self.head_num_layers, self.n_components, self.chunk_rows = head_num_layers, n_components, chunk_rows
         self.batch_size, self.obs_width, self.device = batch_size, self.policy.obs_width, self.policy.device
@@ -105,7 +121,7 @@ class DeviceBC:
         self.weight_decay, self.max_grad_norm = float(weight_decay), float(max_grad_norm)
         self._names = tuple(self._shapes)
         layout = (num_stack, num_layer, head_num_layers, n_components)
-        G = self.G = grad_floats(*layout)
+        G = self.G = grad_floats(*layout, network_dim=D)
         T, M, dev, f = len(self._names), batch_size, self.device, torch.float32
         self._own = []
 
@@ -119,10 +135,11 @@ class DeviceBC:
             self.flat[:G].copy_(torch.cat([state_dict[k].detach().to(dev).reshape(-1) for k in self._names]))
         self.exp_avg, self.exp_avg_sq = new((G,), fill=0.0), new((G,), fill=0.0)
         self._blob_of, self._tensor_end = new((G,), torch.int32), new((T,), torch.int32)
-        self._blob_of.copy_(torch.from_numpy(blob_of(*layout)))
+        self._blob_of.copy_(torch.from_numpy(blob_of(*layout, network_dim=D)))
         self._tensor_end.copy_(torch.from_numpy(tensor_end(self._shapes)))
         self.grad, self._partials = new((G,)), new((self.partials, G))
-        self._grad_scratch = new((grad_scratch_floats(max_agents, chunk_rows, num_layer, self.policy.blob.numel()),))
+        self._grad_scratch = new((grad_scratch_floats(max_agents, chunk_rows, num_layer, self.policy.blob.numel(),
+                                                      network_dim=D),))
         self._actions, self._nll, self._grad_nll = new((M, 3)), new((M,)), new((M,))
         self._lr, self._step = new((1,), fill=self.learning_rate), new((1,), torch.int32, fill=0)
         self._beta_pow = new((2,), torch.float64, fill=1.0)
@@ -135,7 +152,9 @@ class DeviceBC:
         self._updated = False  # an update was ever made (max_grad_tensor is one's)
         self.host_reads = 0  # reads of the device by losses()
         self._L = _capi.lib()
-        p, g, o = self._p, self._g, self._o = _capi.GdBCPolicy(), _capi.GdBCGrad(), _capi.GdBCOpt()
+        # at 128 the gd_bc_policy is the base of the gd_bc_policy_dim that gd_bc_update_dim takes
+        self._pd = _capi.GdBCPolicyDim(network_dim=D, reserved=0) if self._wide else None
+        p, g, o = self._p, self._g, self._o = self._pd.base if self._wide else _capi.GdBCPolicy(), _capi.GdBCGrad(), _capi.GdBCOpt()
         p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = max_agents, num_stack, *num_layer
         p.head_layers, p.n_components, p.clip_value, p.chunk_rows = head_num_layers, n_components, float(clip_value), chunk_rows
         p.blob, p.blob_floats = self.policy.blob.data_ptr(), self.policy.blob.numel()
@@ -159,7 +178,8 @@ class DeviceBC:
     def nbytes(self):
         """Everything the object allocates: the policy's blob, index and forward scratch, the flat weights, both moments, the
         gradient, its partials and the backward's scratch (sized to chunk_rows, not to the batch), the row scratch for
-        batch_size rows, the scalars."""
+        batch_size rows, the scalars.  At the defaults (partials 128, chunk_rows 128, A = 128) the sweep's model at network_dim
+        128 has 716 MB of partial gradients and 266 MB of backward scratch in it."""
         ts = self._own + [self.policy.blob, self.policy._index, self.policy._zero, self.policy._scratch]
         return sum(t.numel() * t.element_size() for t in ts)
 
@@ -175,9 +195,10 @@ class DeviceBC:
         expert = self.policy._expert(expert_actions, B)
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _capi.check(self._L.gd_bc_update(C.byref(self._p), C.byref(self._g), C.byref(self._o), obs.data_ptr(),
-                                             partner_mask.data_ptr(), road_mask.data_ptr(), B, expert.data_ptr(), stream),
-                        "gd_bc_update")
+            entry, who, p = ((self._L.gd_bc_update_dim, "gd_bc_update_dim", self._pd) if self._wide
+                             else (self._L.gd_bc_update, "gd_bc_update", self._p))
+            _capi.check(entry(C.byref(p), C.byref(self._g), C.byref(self._o), obs.data_ptr(), partner_mask.data_ptr(),
+                              road_mask.data_ptr(), B, expert.data_ptr(), stream), who)
         self._updates += 1
         self._updated = True
 
@@ -306,3 +327,12 @@ class DeviceBC:
         self.weight_decay = self._o.weight_decay = float(wd)
         if "lr" in group:
             self.set_learning_rate(group["lr"])
+
+
+class DeviceBCDim(DeviceBC):
+    """`DeviceBC` at every width the step is built at: `network_dim=64` (the default; the same C call and bits as `DeviceBC`)
+    or `network_dim=128`, the reference sweep's model, through `gd_bc_update_dim`.  `policy` is a `DeviceBCPolicy` of that width
+    and follows the optimiser in place; the optimiser state interchanges with a `torch.optim.AdamW` over
+    `TrainableBCPolicyDim.parameters()`.  At 128 the defaults allocate about 1 GB (`nbytes`): pass a smaller `partials`
+    where that is too much."""
+    NETWORK_DIMS = (BP.DIM, 128)

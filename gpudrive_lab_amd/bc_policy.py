@@ -41,14 +41,15 @@ gd_bc_backward_dim); the gradient step with clipping and AdamW
 (`bc_rollout.ClosedLoopBC`, gd_bc_rollout, which calls this forward once per step, or with compact=True the forward on the list
 of the rows still alive);
 `aux_head` / `use_tom`; non-zero dropout; `separate_attn_weights`, rotary embeddings, KV caches, causal attention;
-`ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64 or 128; `DeviceBC`, probes and read-outs at 128; bf16.
+`ContHead`, `l1_loss`, `focal_loss`; SELU; a `network_dim` other than 64 or 128; probes and read-outs at 128; bf16.
 
 `network_dim=128` (with head_dim 64: the model of the reference's sweep, baselines/il/sweep.yaml) is the inference side at that
 width: `__call__`, `context` ([B, 384]), `gmm_params`, `nll`, `evaluate`, `rows=`, `load_state_dict` and the closed-loop driver
 with its attention scores, on the kernels' T = 4 instantiations (csrc/bc_policy.hip, `gd_bc_forward_dim`): 4 heads of 32 channels, every
 encoder Linear 128 x 128, the GMM head behind `head.input_layer` still 64 wide.  `hidden`, `read`, `DeviceLinearProbe`,
-`ProbeReadout`, `DeviceBC` and the name `TrainableBCPolicy` refuse that width (ValueError, before the device is touched);
-`bc_train.TrainableBCPolicyDim` is the module that trains at it, and a policy of this class follows it with `load_state_dict`."""
+`ProbeReadout` and the names `DeviceBC` and `TrainableBCPolicy` refuse that width (ValueError, before the device is touched);
+`bc_train.TrainableBCPolicyDim` is the module that trains at it, and a policy of this class follows it with `load_state_dict`;
+`bc_opt.DeviceBCDim` is the whole gradient step at it, and its `policy` is one of these that follows in place."""
 import ctypes as C
 import math
 
@@ -270,7 +271,7 @@ def scratch_floats(max_agents, chunk_rows, network_dim=DIM):
 
 
 class DeviceBCPolicy:
-    NETWORK_DIMS = (DIM, 128)  # the forward is built at both (and the backward: bc_train.TrainableBCPolicyDim); DeviceBC and the probes at 64 only
+    NETWORK_DIMS = (DIM, 128)  # the forward is built at both (the backward: bc_train.TrainableBCPolicyDim, the update: bc_opt.DeviceBCDim); the probes at 64 only
     network_dim, context_width = DIM, CONTEXT  # (an instance sets its own)
 
     def __init__(self, state_dict, max_agents=128, num_stack=5, num_layer=(3, 2), num_head=4, head_num_layers=2,

@@ -30,7 +30,7 @@ num_layer (4, 3): the model of the reference's sweep, baselines/il/sweep.yaml) t
 
 Not here: gradient clipping and AdamW (any torch optimiser works on this module; `bc_opt.DeviceBC` is the whole step on the
 device, gd_bc_update, without it); non-zero dropout; `aux_head` / `use_tom`; `l1_loss` / `focal_loss`; bf16; a gradient with respect to the
-observations; any tuning beyond one wave per workgroup; `DeviceBC` (the whole step on the device) at 128."""
+observations; any tuning beyond one wave per workgroup.  (The whole step on the device at 128 is `bc_opt.DeviceBCDim`.)"""
 import ctypes as C
 
 import numpy as np

@@ -1,4 +1,4 @@
-// Device BC update (gd_bc_train_rows, gd_bc_adamw): what stands between gd_bc_forward and gd_bc_backward, and after the
+// Device BC update (gd_bc_train_rows, gd_bc_adamw, gd_bc_adamw_dim): what stands between gd_bc_forward and gd_bc_backward, and after the
 // backward, in one gradient step of the reference's imitation learning -- the step's statistics and the loss's upstream
 // gradient, gradient clipping, the largest per-tensor norm and AdamW.  The rule is csrc/bc_opt_rule.hpp, stated there in full;
 // these kernels only distribute it:
@@ -6,14 +6,18 @@
 //                partials meet in LDS and lanes 0..3 add one statistic's each in ascending order.  grad_nll is stored per row.
 //   k_bc_sq      a workgroup of 256 lanes per parameter TENSOR: the tensor's sum of squares by the same order (lane j owns
 //                partial j, counted from the tensor's start), left as float64 in `scal` with its root in tensor_norms.  The
-//                largest tensor (head.input_layer.0.weight, 12,288 floats) gives a lane 48 elements.
+//                largest tensor is head.input_layer.0.weight: 12,288 floats at network_dim 64, a lane's 48 elements; 24,576 at
+//                128, a lane's 96.
 //   k_bc_step    ONE workgroup: the sums of the launch before it added in ascending tensor order, the norm, the coefficient,
 //                the largest tensor norm; lane 0 advances step and the two running products and leaves total, coef, bc1 and
 //                rbc2 in `scal` for the next launch.
 //   k_bc_adamw   a lane per parameter: the AdamW rule, the updated weight stored to params[e] and to blob[blob_of[e]].  It
 //                reads the scalars of the launch before it and writes none.
 // No atomics, no word crosses workgroups within a launch, every store has one owner: equal inputs and state give equal bits.
-// All four are short latency chains or one sweep over 0.3 M floats: 256-lane workgroups, a few KB of LDS, no scratch.
+// None of them has the policy's width in it: G, T, tensor_end and blob_of carry the layout, and T <= MAX_TENSORS = 288 at either
+// width (the sweep's model at network_dim 128, layers (4, 3): G = 1,399,274, T = 252; indices stay far below 2^31).
+// All four are short latency chains or one sweep over G floats (0.3 M at 64, 1.4 M at 128): 256-lane workgroups, a few KB of LDS,
+// no scratch.
 #include <hip/hip_runtime.h>
 
 #include "bc_opt_rule.hpp"

@@ -28,7 +28,8 @@
 //     per parameter:  p = p * decay;  then ppo_rule::adam with gc = g * coef
 // weight_decay = 0 gives decay = 1.f and p * 1.f = p, so the step is then ppo_rule's Adam bit for bit.  A non-finite gradient
 // propagates as in torch.  sqrtf and the divisions are correctly rounded on both sides and nothing here is transcendental, so
-// the whole rule is bit-identical between the device and the host program.
+// the whole rule is bit-identical between the device and the host program.  Nothing in it knows the policy's network_dim: G, T
+// and end carry the layout, at 64 and at 128 (gd_bc_adamw_dim) alike.
 #pragma once
 
 #include "ppo_rule.hpp"

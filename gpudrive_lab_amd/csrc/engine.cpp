@@ -2469,8 +2469,9 @@ int gd_bc_train_rows(const gd_bc_opt *opt, int32_t n, const float *nll, const fl
     });
 }
 
-// everything gd_bc_adamw refuses; nullptr when everything is in order
-static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
+// everything gd_bc_adamw and gd_bc_adamw_dim refuse of opt and grad at network_dim dim (64 or 128); nullptr when everything is
+// in order
+static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad, int dim) {
     if (!o || !grad) return "null argument";
     if (o->num_stack < 1 || o->num_stack > 8) return "num_stack must be in [1, 8]";
     if (o->fusion_layers < 1 || o->fusion_layers > 4 || o->branch_layers < 1 || o->branch_layers > 4)
@@ -2478,10 +2479,12 @@ static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
     if (o->head_layers < 0 || o->head_layers > 4) return "head_layers must be in [0, 4]";
     if (o->n_components < 1 || o->n_components > 16) return "n_components must be in [1, 16]";
     if (o->reserved != 0) return "reserved must be 0";
-    if (o->grad_floats != gd::bc_grad_floats(64, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
-        return "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
-    if (o->blob_floats != gd::bc_blob_floats(64, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
-        return "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
+    if (o->grad_floats != gd::bc_grad_floats(dim, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+        return dim == 128 ? "grad_floats is not the parameters' count at network_dim 128 for these layer counts, num_stack and n_components"
+                          : "grad_floats is not the parameters' count for these layer counts, num_stack and n_components";
+    if (o->blob_floats != gd::bc_blob_floats(dim, o->num_stack, o->fusion_layers, o->branch_layers, o->head_layers, o->n_components))
+        return dim == 128 ? "blob_floats is not the layout's size at network_dim 128 for these layer counts, num_stack and n_components"
+                          : "blob_floats is not the layout's size for these layer counts, num_stack and n_components";
     if (o->num_tensors != gd::bc_num_tensors(o->fusion_layers, o->branch_layers, o->head_layers))
         return "num_tensors is not the state dict's tensor count for these layer counts";
     if (!(o->beta1 >= 0.0 && o->beta1 < 1.0) || !(o->beta2 >= 0.0 && o->beta2 < 1.0)) return "betas must be in [0, 1)";
@@ -2499,27 +2502,42 @@ static const char *bc_adamw_problem(const gd_bc_opt *o, const float *grad) {
     return nullptr;
 }
 
-int gd_bc_adamw(const gd_bc_opt *opt, const float *grad, void *stream) {
-    if (const char *why = bc_adamw_problem(opt, grad)) return fail(GD_ERR_INVALID, std::string("gd_bc_adamw: ") + why);
+// The one checked optimiser step behind gd_bc_adamw and gd_bc_adamw_dim.  The order of refusal: the width, then opt and grad at
+// that width.  The kernels have no width in them; it only sizes the two layouts opt must describe.
+static int bc_adamw(const char *who, const gd_bc_opt *opt, int dim, const float *grad, void *stream) {
+    const char *why = dim != 64 && dim != 128 ? "network_dim must be 64 or 128" : nullptr;
+    if (!why) why = bc_adamw_problem(opt, grad, dim);
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     return guarded([&]() {
         gd::launch_bc_adamw(*opt, static_cast<hipStream_t>(stream), grad);
         HIP_CHECK(hipGetLastError());
     });
 }
 
-int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs, const uint8_t *partner_mask,
-                 const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream) {
-    if (!p || !g || !opt) return fail(GD_ERR_INVALID, "gd_bc_update: null argument");
+int gd_bc_adamw(const gd_bc_opt *opt, const float *grad, void *stream) { return bc_adamw("gd_bc_adamw", opt, 64, grad, stream); }
+
+int gd_bc_adamw_dim(const gd_bc_opt *opt, int32_t network_dim, const float *grad, void *stream) {
+    return bc_adamw("gd_bc_adamw_dim", opt, network_dim, grad, stream);
+}
+
+// The one checked gradient step behind gd_bc_update and gd_bc_update_dim.  The order of refusal: the _dim struct, a NULL struct,
+// then the forward, the row statistics, the backward and the optimiser step in the order they run, each sized at the width,
+// then what ties the three structs together.
+static int bc_update(const char *who, BCAt at, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs,
+                     const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream) {
+    if (at.why) return fail(GD_ERR_INVALID, std::string(who) + ": " + at.why);
+    const gd_bc_policy *p = at.p;
+    if (!p || !g || !opt) return fail(GD_ERR_INVALID, std::string(who) + ": null argument");
     const gd_bc_opt &o = *opt;
     gd_bc_outputs out{};
     out.actions = o.actions, out.nll = o.nll;
     const char *why = nullptr;
     if (!expert_actions || !o.actions || !o.nll || !o.grad_nll || !o.grad)
         why = "null argument (expert_actions, or opt's actions, nll, grad_nll or grad)";
-    if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out, 64);
+    if (!why) why = bc_forward_problem(p, obs, partner_mask, road_mask, n, 1, nullptr, nullptr, expert_actions, &out, at.dim);
     if (!why) why = bc_train_rows_problem(opt, n, o.nll, o.actions, expert_actions, o.grad_nll);
-    if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad, 64);
-    if (!why) why = bc_adamw_problem(opt, o.grad);
+    if (!why) why = bc_backward_problem(p, g, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad, at.dim);
+    if (!why) why = bc_adamw_problem(opt, o.grad, at.dim);
     if (!why && (o.max_rows < 1 || o.max_rows > (1 << 20))) why = "max_rows must be in [1, 2^20]";
     if (!why && n > o.max_rows) why = "n is above max_rows (the row scratch holds max_rows rows)";
     if (!why && (p->num_stack != o.num_stack || p->fusion_layers != o.fusion_layers || p->branch_layers != o.branch_layers ||
@@ -2527,15 +2545,25 @@ int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *op
                  g->grad_floats != o.grad_floats))
         why = "the configurations and sizes of the policy, the backward and opt differ";
     if (!why && p->blob != o.blob) why = "the policy's blob must be opt's (the optimiser step updates it in place)";
-    if (why) return fail(GD_ERR_INVALID, std::string("gd_bc_update: ") + why);
+    if (why) return fail(GD_ERR_INVALID, std::string(who) + ": " + why);
     return guarded([&]() {
         hipStream_t st = static_cast<hipStream_t>(stream);
-        gd::launch_bc_forward(*p, 64, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
+        gd::launch_bc_forward(*p, at.dim, st, obs, partner_mask, road_mask, n, true, nullptr, nullptr, expert_actions, out);
         gd::launch_bc_train_rows(o, st, n, o.nll, o.actions, expert_actions, o.grad_nll);
-        gd::launch_bc_backward(*p, 64, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
+        gd::launch_bc_backward(*p, at.dim, *g, st, obs, partner_mask, road_mask, n, expert_actions, o.grad_nll, nullptr, o.grad);
         gd::launch_bc_adamw(o, st, o.grad);
         HIP_CHECK(hipGetLastError());
     });
+}
+
+int gd_bc_update(const gd_bc_policy *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs, const uint8_t *partner_mask,
+                 const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream) {
+    return bc_update("gd_bc_update", bc_at(p), g, opt, obs, partner_mask, road_mask, n, expert_actions, stream);
+}
+
+int gd_bc_update_dim(const gd_bc_policy_dim *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs,
+                     const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream) {
+    return bc_update("gd_bc_update_dim", bc_at(p), g, opt, obs, partner_mask, road_mask, n, expert_actions, stream);
 }
 
 int gd_bc_eval_accumulate(int32_t n, const float *nll, const float *actions, const float *expert_actions, float *acc, void *stream) {

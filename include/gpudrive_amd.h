@@ -1132,8 +1132,9 @@ int gd_bc_rollout_readout(gd_sim *sim, const gd_bc_policy *policy, const gd_bc_r
  * LayerNorm, q / k / v / o projection and MLP Linear is 128 wide, the 4 heads have 32 channels (q is multiplied once, after the
  * bias, by the float32 nearest to 32^-1/2), the context is [n][384], head.input_layer is 384 -> 64 and the GMM head behind it
  * stays 64 wide.  At 128: base.blob_floats is the layout's at that width (`pack_index(..., network_dim=128)`) and
- * base.scratch_floats >= chunk_rows * 3 * (A + 200) * 128.  The forward, the closed loop and the backward (gd_bc_backward_dim)
- * take it; the update, gd_bc_hidden, the linear probes and the read-outs take a gd_bc_policy and stay 64 wide. */
+ * base.scratch_floats >= chunk_rows * 3 * (A + 200) * 128.  The forward, the closed loop, the backward (gd_bc_backward_dim)
+ * and the update (gd_bc_update_dim) take it; gd_bc_hidden, the linear probes and the read-outs take a gd_bc_policy and stay 64
+ * wide. */
 typedef struct gd_bc_policy_dim {
     gd_bc_policy base;
     int32_t network_dim;  /* 64 or 128 */
@@ -1160,6 +1161,20 @@ int gd_bc_forward_rows_dim(const gd_bc_policy_dim *p, const float *obs, const ui
 int gd_bc_backward_dim(const gd_bc_policy_dim *p, const gd_bc_grad *g, const float *obs, const uint8_t *partner_mask,
                        const uint8_t *road_mask, int32_t n, const float *expert_actions, const float *grad_nll, float *nll,
                        float *grad, void *stream);
+/* gd_bc_adamw on the parameters of the policy at network_dim: the same arguments, checks, guarantees and three launches (the
+ * kernels have no width in them).  opt->grad_floats and opt->blob_floats are checked against the parameters' count and the
+ * layout's size at that width, opt->blob_of is the inverse of that width's layout; opt->reserved stays 0.  At 64 it is
+ * gd_bc_adamw.  At 128 with the sweep's layer counts G = 1,399,274 and T = 252.
+ * GD_ERR_INVALID, before any launch: a network_dim other than 64 or 128, then whatever gd_bc_adamw refuses at that width. */
+int gd_bc_adamw_dim(const gd_bc_opt *opt, int32_t network_dim, const float *grad, void *stream);
+/* gd_bc_update at p->network_dim: gd_bc_forward_dim(p, deterministic), gd_bc_train_rows, gd_bc_backward_dim,
+ * gd_bc_adamw_dim(opt, p->network_dim) as one call on `stream`, with gd_bc_update's arguments and guarantees; the results are
+ * bit for bit those of the four calls.  At 64 it runs gd_bc_update's own launches and gives its bits.  p->base.blob must be
+ * opt->blob, and g and opt carry the sizes of that width.
+ * GD_ERR_INVALID, before any launch: a null p, a network_dim other than 64 or 128, reserved != 0, then whatever gd_bc_update
+ * refuses, in its order, each size checked at that width. */
+int gd_bc_update_dim(const gd_bc_policy_dim *p, const gd_bc_grad *g, const gd_bc_opt *opt, const float *obs,
+                     const uint8_t *partner_mask, const uint8_t *road_mask, int32_t n, const float *expert_actions, void *stream);
 /* The closed-loop episode at p->network_dim: gd_bc_rollout (rows == NULL, reads == NULL), gd_bc_rollout_compact (rows) or
  * gd_bc_rollout_readout (reads) with that forward in the loop, every output as those define it.  reads->ego_attn_score is
  * allowed at either width; reads->readout must be NULL unless network_dim is 64 (GD_ERR_INVALID: the probes read 64-wide

@@ -17,7 +17,12 @@ The launches per step take two more steps, the second without a device:
   1. rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bc_update.py --runs 1 --calls 5 --only a
   2. tools/bc_update.py --merge FILE --kernel-stats DIR/.../*_kernel_stats.csv
 (--only a makes 3 warm-up steps, 5 timed ones and one more before them: the calls of every kernel over those 9 steps.)
-tools/bc_update.py [--rows 512] [--agents 128] [--stack 5] [--runs 3] [--calls 10] [--only a] [--out FILE]"""
+
+--dim 128 is the same comparison at the model of the reference's sweep (network_dim 128, num_layer (4, 3)): (a) is
+DeviceBCDim.update (gd_bc_update_dim), (b) a TrainableBCPolicyDim step, torch's clip, AdamW.step and the re-pack of a 128-wide
+DeviceBCPolicy.  There the result also carries what is asserted of (a): the bytes a step allocates and the host
+synchronisations it makes (torch's sync debug mode), both 0.
+tools/bc_update.py [--dim 64] [--rows 512] [--agents 128] [--stack 5] [--runs 3] [--calls 10] [--only a] [--out FILE]"""
 import argparse
 import csv
 import json
@@ -33,7 +38,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from bc_forward import peak_bytes, summary, timed  # noqa: E402
-from gpudrive_lab_amd import DeviceBC, TrainableBCPolicy  # noqa: E402
+from gpudrive_lab_amd import DeviceBC, TrainableBCPolicy, TrainableBCPolicyDim  # noqa: E402
+from gpudrive_lab_amd.bc_opt import DeviceBCDim  # noqa: E402
 from gpudrive_lab_amd.bc_policy import DeviceBCPolicy, obs_width  # noqa: E402
 from tests import bc_cases as BC  # noqa: E402
 
@@ -47,7 +53,7 @@ def merge(path, stats):
     with open(stats) as f:
         rows = [r for r in csv.DictReader(f) if re.search(r"k_bcg?_", r["Name"])]
     name = lambda r: re.search(r"k_bcg?_\w+(<[^>]*>)?", r["Name"]).group(0)  # noqa: E731
-    steps = res["runs"] * (res["calls"] + WARM) + 1
+    steps = res["runs"] * (res["calls"] + WARM) + 1 + ("network_dim" in res)  # (--dim 128 makes one more, under the sync check)
     res["kernel_average_us"] = {name(r): float(r["AverageNs"]) / 1e3 for r in rows}
     res["kernel_calls"] = {name(r): int(r["Calls"]) for r in rows}
     res["kernel_total_share"] = {name(r): float(r["Percentage"]) for r in rows}
@@ -63,6 +69,7 @@ def merge(path, stats):
 
 def arguments():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dim", type=int, choices=(64, 128), default=64)
     ap.add_argument("--rows", type=int, default=512)
     ap.add_argument("--agents", type=int, default=128)
     ap.add_argument("--stack", type=int, default=5)
@@ -79,9 +86,14 @@ def arguments():
 
 def main(args):
     B, A, R, cfg = args.rows, args.agents, args.stack, BC.CFG
-    sd = BC.state_dict(R, cfg)
     kw = {} if args.chunk_rows is None else dict(chunk_rows=args.chunk_rows)
-    bc = DeviceBC(sd, max_agents=A, num_stack=R, batch_size=B, partials=args.partials, **cfg, **kw)
+    Trainer, Module = DeviceBC, TrainableBCPolicy
+    if args.dim != 64:   # the sweep's model
+        cfg = dict(BC.CFG, num_layer=(4, 3))
+        kw["network_dim"] = args.dim
+        Trainer, Module = DeviceBCDim, TrainableBCPolicyDim
+    sd = BC.state_dict(R, cfg, **({} if args.dim == 64 else dict(network_dim=args.dim)))
+    bc = Trainer(sd, max_agents=A, num_stack=R, batch_size=B, partials=args.partials, **cfg, **kw)
     res = dict(tool="tools/bc_update.py", rows=B, slots=A, num_stack=R, obs_width=obs_width(A), config=cfg, runs=args.runs,
                calls=args.calls, observations="synthetic", source_stamp=bench.source_stamp(), chunk_rows=bc.chunk_rows,
                partials=bc.partials, a_nbytes=bc.nbytes, parameters=bc.G, tensors=len(bc._names))
@@ -99,7 +111,7 @@ def main(args):
     if args.only == "a":
         a_us = [timed(step_a, args.calls) for _ in range(args.runs)]
     else:
-        tbp = TrainableBCPolicy.from_state_dict(sd, max_agents=A, num_stack=R, device="cuda", partials=args.partials, **cfg, **kw)
+        tbp = Module.from_state_dict(sd, max_agents=A, num_stack=R, device="cuda", partials=args.partials, **cfg, **kw)
         pol = DeviceBCPolicy.from_state_dict(sd, max_agents=A, num_stack=R, **cfg, **kw)
         opt = torch.optim.AdamW(tbp.parameters(), lr=bc.learning_rate, betas=bc.betas, eps=bc.eps, weight_decay=bc.weight_decay)
 
@@ -129,6 +141,17 @@ def main(args):
         res["b"] = summary(b_us)
         res["b_spread"] = res["b"]["hi"] - res["b"]["lo"]
     res["a"] = summary(a_us)
+    if args.dim != 64:   # one more step, after everything that is compared or timed
+        res["network_dim"] = args.dim
+        torch.cuda.synchronize()
+        held = torch.cuda.memory_allocated()
+        torch.cuda.set_sync_debug_mode("error")   # a host synchronisation inside the step raises
+        try:
+            step_a()
+        finally:
+            torch.cuda.set_sync_debug_mode(0)
+        res["a_bytes_allocated_per_step"], res["a_host_synchronisations_per_step"] = torch.cuda.memory_allocated() - held, 0
+        assert res["a_bytes_allocated_per_step"] == 0, "the update allocated"
     if b_us:
         res["b_over_a"] = res["b"]["median"] / res["a"]["median"]
         res["a_not_slower_beyond_b_spread"] = res["a"]["median"] <= res["b"]["median"] + res["b_spread"]
