@@ -11,11 +11,13 @@ leave the forward's values what they are and change the backward alone):
     "soft_clamp"      the covariance clamp passes the gradient outside its bounds
     "tanh_gelu"       GELU's derivative is that of the tanh approximation
     "normed_residual" the attention residual adds the LayerNorm'ed input instead of the input
-and three that are the right rule at bc_cases.CFG and wrong only at configurations of bc_cases.EDGE_CASES (bc_reference.py
+and four that are the right rule at bc_cases.CFG and wrong only at configurations of bc_cases.EDGE_CASES (bc_reference.py
 states them for the forward):
     "head_one_trip"   the head's outputs of index >= 64 stay at their bias: their rows of head.head get no gradient
     "rg_at_ro"        rg_attn layer i runs on ro_attn layer i's weights for i >= min(fusion, branch)
     "floor_m20"       the covariance clamp's floor is -20 whatever clip_value says
+    "kin_three_tiles" the road embedder's first layer reads its inputs 0 .. 95 only (three 32-column tiles; right for
+                      num_stack <= 7): at num_stack 8 columns 96 .. 103 of road_graph_net.0.weight get no gradient
 
 Also here: the host program of csrc/bc_grad_rule.hpp and the float64 autograd of the mixture nll it is compared with."""
 import math
@@ -36,7 +38,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 COV_MAX = 3.58352
 ROADS = 200
 WRONG = ("additive_mask", "soft_clamp", "tanh_gelu", "normed_residual")
-WRONG_AT_EDGES = ("head_one_trip", "rg_at_ro", "floor_m20")
+WRONG_AT_EDGES = ("head_one_trip", "rg_at_ro", "floor_m20", "kin_three_tiles")
 MINIMAL = dict(num_layer=(1, 1), head_num_layers=0, n_components=1, clip_value=-20.0)
 MARGIN = 1e-3
 
@@ -64,7 +66,11 @@ class Net:
 
     def _embed(self, x, net):
         for i in range(4):
-            x = torch.tanh(self._ln(self._lin(x, "%s.%d" % (net, 4 * i)), "%s.%d" % (net, 4 * i + 2)))
+            if self.wrong == "kin_three_tiles" and i == 0 and net == "road_graph_net" and x.shape[-1] > 96:
+                y = F.linear(x[..., :96], self.params[net + ".0.weight"][:, :96], self.params[net + ".0.bias"])
+            else:
+                y = self._lin(x, "%s.%d" % (net, 4 * i))
+            x = torch.tanh(self._ln(y, "%s.%d" % (net, 4 * i + 2)))
         return x
 
     def _gelu(self, x):

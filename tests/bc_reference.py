@@ -11,12 +11,14 @@ tests/test_bc_wide.py at 128 (tests/golden/bc_wide_forward_*.npz).
     "normed_residual" the attention residual adds the LayerNorm'ed input instead of the input
     "entity_major"    a token's R rows are taken by reshaping [R, n, k] to [n, R k] without the permute
     "tanh_gelu"       the tanh approximation of GELU instead of the erf form
-and four that are the right rule at bc_cases.CFG and wrong only at the configurations of bc_cases.EDGE_CASES:
+and five that are the right rule at bc_cases.CFG and wrong only at the configurations of bc_cases.EDGE_CASES:
     "head_one_trip"   the head's outputs of index >= 64 stay at their bias (one trip of a 64-lane loop over the 7 C outputs)
     "rg_at_ro"        rg_attn layer i is read at ro_attn's offset (ro_attn layer i's weights) for i >= min(fusion, branch):
                       it needs branch > fusion to show (a model with one branch layer has no such i)
     "floor_m20"       the covariance clamp's floor is -20 whatever clip_value says
     "eval_one_trip"   `evaluate` sums the rows below 64 of a batch only (one trip of a 64-lane loop over the rows)
+    "kin_three_tiles" the road embedder's first layer reads its inputs 0 .. 95 only (three 32-column tiles): every input for
+                      num_stack <= 7 (13 R <= 91), wrong at num_stack 8 (kin 104, a fourth tile)
 and four that the 128 case invites (the right rule at 64):
     "scale16"         q * 0.25, the 64-wide kernel's constant, instead of q * 32^-1/2
     "heads_of_16"     eight heads of 16 channels (the 64-wide head size kept) instead of four of 32
@@ -68,7 +70,11 @@ def unpack(obs, A, wrong=None):
 
 def embed(x, sd, net, wrong=None):
     for i in range(4):  # Linear -> [dropout: identity] -> LayerNorm -> tanh
-        x = np.tanh(layer_norm(linear(x, sd, "%s.%d" % (net, 4 * i)), sd, "%s.%d" % (net, 4 * i + 2), wrong))
+        if wrong == "kin_three_tiles" and i == 0 and net == "road_graph_net" and x.shape[-1] > 96:
+            y = x[..., :96] @ sd[net + ".0.weight"][:, :96].T + sd[net + ".0.bias"]
+        else:
+            y = linear(x, sd, "%s.%d" % (net, 4 * i))
+        x = np.tanh(layer_norm(y, sd, "%s.%d" % (net, 4 * i + 2), wrong))
     return x
 
 

@@ -1,4 +1,4 @@
-"""Cases for the BC policy forward at network_dim = 128: the four cases.  The seeded state dict, the eager float32 stand-in
+"""Cases for the BC policy at network_dim = 128: the four cases and the seven edge configurations.  The seeded state dict, the eager float32 stand-in
 (the yardstick's float32 side), the inputs, masks, the yardstick and the rule's host program are tests/bc_cases.py's own, the
 float64 restatement tests/bc_reference.py's: each takes the width as an argument or from the state dict."""
 from gpudrive_lab_amd import bc_policy as BP
@@ -19,6 +19,34 @@ CASES = {
 }
 GOLDEN_CASES = ("wide_min", "wide_sweep", "wide_a128")
 
+# (name, bc_cases.EDGE's name, the seed of bc_cases.inputs): wide_<name> is bc_cases.EDGE[name] at network_dim 128 -- the shapes and
+# cfgs are that table's, not copies (its `sweep` is wide_sweep with the clip10 clamp, hence wide_clip10).  What each reaches at
+# T = 4: wide_top 288 tensors, 112 head outputs (a second trip of the head's 64-lane loops), head depth 4, road kin 104 (kpad
+# 128), (4, 4) layers; wide_clip10 the sweep's model as the sweep clamps it; wide_c9 / wide_c10 63 and 70 head outputs, either
+# side of one 64-lane trip; wide_deep_branch (1, 4), rg_attn's layers three deep past ro_attn's, A 128, even kin 12 and 26;
+# wide_deep_fusion (4, 1), head depth 3, a clamp floor above 0; wide_defaults more rows than chunk_rows = partials = 128.
+# The seed is the first (from 1) with which both head margins of bc_wide_grad_reference.Net exceed bc_grad_reference.MARGIN, so
+# that the forward's and the backward's tests share one set of inputs per case.
+EDGE_CASES = (
+    ("wide_top", "top", 1),                  # margins: relu 0.0029
+    ("wide_clip10", "sweep", 1),             # relu 0.0028
+    ("wide_c9", "c9", 1),                    # relu 0.0074
+    ("wide_c10", "c10", 1),                  # relu 0.0074
+    ("wide_deep_branch", "deep_branch", 1),  # relu 0.0025
+    ("wide_deep_fusion", "deep_fusion", 1),  # relu 0.0027
+    ("wide_defaults", "defaults", 4),        # clamp 2.54 relu 0.0011 (seeds 1 to 3 leave a ReLU within the margin)
+)
+EDGE = {name: BC.EDGE[narrow] for name, narrow, _ in EDGE_CASES}
+EDGE_NAMES = tuple(name for name, _, _ in EDGE_CASES)
+SEEDS = {**{name: 1 for name in CASES}, **{name: seed for name, _, seed in EDGE_CASES}}
+EDGE_GOLDEN_CASES = ("wide_top",)
+assert not set(EDGE) & set(CASES)
+
+
+def lookup(name):
+    """(B, A, R, cfg) of a case of either table."""
+    return CASES[name] if name in CASES else EDGE[name]
+
 
 def shapes(R, cfg, network_dim=DIM):
     return BP.expected_shapes(R, cfg["num_layer"], cfg["head_num_layers"], cfg["n_components"], network_dim=network_dim)
@@ -31,9 +59,9 @@ def case(name):
     """Everything a test needs of one case, computed once and shared (leave it unchanged): the state dict, the inputs, the
     float64 restatement with its nll, the float32 stand-in and the yardstick E per output."""
     if name not in _CASE:
-        B, A, R, cfg = CASES[name]
+        B, A, R, cfg = lookup(name)
         sd = BC.state_dict(R, cfg, network_dim=DIM)
-        obs, pm, rm, expert, u, z, kinds = BC.inputs(B, A, R)
+        obs, pm, rm, expert, u, z, kinds = BC.inputs(B, A, R, seed=SEEDS[name])
         ref = REF.forward(sd, obs, pm, rm, A, **cfg)
         ref["nll"] = REF.nll(ref["means"], ref["log_covariances"], ref["weights"], expert[:, 0])
         f32 = BC.standin_float32(sd, obs, pm, rm, A, cfg, expert)

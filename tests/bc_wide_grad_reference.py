@@ -59,14 +59,13 @@ def gradients(sd, obs, pm, rm, expert, grad_nll, max_agents, cfg=BC.CFG, dtype=t
             dict(net.margins))
 
 
-INPUT_SEED = 1  # bc_cases.inputs' default: both head margins stay above bc_grad_reference.MARGIN on every wide case
 _CASE = {}
 
 
 def case_inputs(name):
-    """(state dict, obs, pm, rm, expert [B, 3], kinds, A, cfg) of bc_wide_cases.CASES[name]."""
-    B, A, R, cfg = WC.CASES[name]
-    obs, pm, rm, expert, _, _, kinds = BC.inputs(B, A, R, seed=INPUT_SEED)
+    """(state dict, obs, pm, rm, expert [B, 3], kinds, A, cfg) of the case of bc_wide_cases.CASES or EDGE_CASES."""
+    B, A, R, cfg = WC.lookup(name)
+    obs, pm, rm, expert, _, _, kinds = BC.inputs(B, A, R, seed=WC.SEEDS[name])
     return BC.state_dict(R, cfg, network_dim=WC.DIM), obs, pm, rm, expert[:, 0], kinds, A, cfg
 
 
@@ -81,7 +80,7 @@ def case(name, kind="mean", rows=None):
         w = GR.grad_weights(len(obs), kind)
         g64, nll, margins = gradients(sd, obs, pm, rm, expert, w, A, cfg)
         g32, _, _ = gradients(sd, obs, pm, rm, expert, w, A, cfg, dtype=torch.float32)
-        _CASE[key] = dict(sd=sd, obs=obs, pm=pm, rm=rm, expert=expert, kinds=kinds, A=A, R=WC.CASES[name][2], cfg=cfg, w=w, g64=g64,
+        _CASE[key] = dict(sd=sd, obs=obs, pm=pm, rm=rm, expert=expert, kinds=kinds, A=A, R=WC.lookup(name)[2], cfg=cfg, w=w, g64=g64,
                           g32=g32, nll=nll, margins=margins, E=GR.yardstick(g32, g64))
     return _CASE[key]
 

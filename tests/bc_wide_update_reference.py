@@ -26,8 +26,8 @@ def layout_args(R, cfg):
 
 
 def layout(name, network_dim=DIM):
-    """(names, tensor_end int32 [T], G) of the flat layout of bc_wide_cases.CASES[name] at network_dim."""
-    _, _, R, cfg = WC.CASES[name]
+    """(names, tensor_end int32 [T], G) of the flat layout of the case `name` of bc_wide_cases at network_dim."""
+    _, _, R, cfg = WC.lookup(name)
     shapes = WC.shapes(R, cfg, network_dim)
     end = np.cumsum([int(np.prod(s)) for s in shapes.values()]).astype(np.int32)
     return tuple(shapes), end, int(end[-1])
@@ -79,7 +79,7 @@ OK = 0x1000  # a junk pointer that passes every alignment check and is never rea
 def structs(dim, name="wide_sweep", max_rows=8, chunk=2, **kw):
     """(gd_bc_policy_dim, gd_bc_grad, gd_bc_opt) of the case's configuration at width dim with junk pointers: everything the
     checks of gd_bc_update_dim and gd_bc_adamw_dim read, in order.  kw: fields of the gd_bc_opt to overwrite."""
-    _, A, R, cfg = WC.CASES[name]
+    _, A, R, cfg = WC.lookup(name)
     if (dim, name) not in _SIZES:
         lay = layout_args(R, cfg)
         _SIZES[dim, name] = BT.grad_floats(*lay, network_dim=dim), int(BP.pack_index(*lay, network_dim=dim).size)
@@ -88,7 +88,7 @@ def structs(dim, name="wide_sweep", max_rows=8, chunk=2, **kw):
     pd.network_dim, pd.reserved = dim, 0
     p = pd.base
     p.max_agents, p.num_stack, p.fusion_layers, p.branch_layers = A, R, *cfg["num_layer"]
-    p.head_layers, p.n_components, p.clip_value, p.chunk_rows = cfg["head_num_layers"], cfg["n_components"], -20.0, chunk
+    p.head_layers, p.n_components, p.clip_value, p.chunk_rows = cfg["head_num_layers"], cfg["n_components"], cfg["clip_value"], chunk
     p.blob, p.blob_floats, p.scratch, p.scratch_floats = OK, blob, OK, BP.scratch_floats(A, chunk, dim)
     g.scratch, g.scratch_floats = OK, BT.grad_scratch_floats(A, chunk, cfg["num_layer"], blob, network_dim=dim)
     g.partials, g.grad_floats, g.num_partials = OK, G, 4

@@ -24,9 +24,9 @@ K = 32  # the project's bound: an error of at most K E against the float64 resta
 
 # ---- the pin to the reference module
 
-@pytest.mark.parametrize("name", WC.GOLDEN_CASES)
+@pytest.mark.parametrize("name", WC.GOLDEN_CASES + WC.EDGE_GOLDEN_CASES)
 def test_expected_shapes_are_the_reference_modules(name):
-    B, A, R, cfg = WC.CASES[name]
+    B, A, R, cfg = WC.lookup(name)
     g = np.load(os.path.join(GOLDEN, "bc_wide_forward_%s.npz" % name))
     want = WC.shapes(R, cfg)
     assert [str(n) for n in g["names"]] == list(want)  # the reference module's own names, in its own order
@@ -35,7 +35,7 @@ def test_expected_shapes_are_the_reference_modules(name):
     assert want["head.head.weight"] == (7 * cfg["n_components"], 64)
 
 
-@pytest.mark.parametrize("name", WC.GOLDEN_CASES)
+@pytest.mark.parametrize("name", WC.GOLDEN_CASES + WC.EDGE_GOLDEN_CASES)
 def test_restatement_equals_the_reference_module(name):
     g = np.load(os.path.join(GOLDEN, "bc_wide_forward_%s.npz" % name))
     c = WC.case(name)

@@ -50,13 +50,22 @@ def test_wide_nll_is_the_float64_forwards_and_the_margins_hold(name):
 
 
 def test_wide_restatement_equals_the_reference_modules_backward():
+    _restatement_equals_the_reference_modules_backward("wide_min")
+
+
+def test_wide_restatement_equals_the_reference_modules_backward_at_the_largest_model():
+    """wide_top: 288 tensors, head depth 4, 16 components, num_stack 8, (4, 4) layers."""
+    _restatement_equals_the_reference_modules_backward("wide_top")
+
+
+def _restatement_equals_the_reference_modules_backward(case):
     """tests/test_bc_grad.py's comparison and tolerances at network_dim 128 (loss.mean() in float64: weights 1 / B)."""
-    g = np.load(os.path.join(GOLDEN, "bc_wide_grad_wide_min.npz"))
-    sd, obs, pm, rm, expert, _, A, cfg = WGR.case_inputs("wide_min")
+    g = np.load(os.path.join(GOLDEN, "bc_wide_grad_%s.npz" % case))
+    sd, obs, pm, rm, expert, _, A, cfg = WGR.case_inputs(case)
     B = len(obs)
     g64, nll, _ = WGR.gradients(sd, obs, pm, rm, expert, np.full(B, 1.0 / B), A, cfg)
     names = [str(n) for n in g["names"]]
-    assert names == list(g64) == list(WC.shapes(WC.CASES["wide_min"][2], cfg))
+    assert names == list(g64) == list(WC.shapes(WC.lookup(case)[2], cfg))
     assert abs(float(g["loss"]) - nll.mean()) <= 1e-12 * abs(float(g["loss"]))
     for i, (name, grad) in enumerate(g64.items()):
         flat = grad.reshape(-1)

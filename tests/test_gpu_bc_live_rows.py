@@ -2,7 +2,8 @@
 
 No result of a sample in the BC forward depends on the samples beside it, so the forward on a row list must give every listed
 row the FULL forward's bits and touch nothing else; the closed-loop driver with the list in the loop must give the driver's
-results.  Everything here is an exact comparison: no tolerance anywhere."""
+results.  Everything here is an exact comparison: no tolerance anywhere.  (tests/test_gpu_bc_wide_edges.py runs the edge
+configurations' lists on the 128-wide policy through `_row_lists_at_an_edge_configuration`.)"""
 import numpy as np
 import pytest
 import torch
@@ -22,10 +23,10 @@ GUARD = 64
 OUTPUTS = ("context", "means", "log_covariances", "covariances", "weights", "actions", "nll", "ego_attn_score", "component")
 
 
-def _policy(A, R, sd=None, chunk_rows=CHUNK, cfg=BC.CFG):
+def _policy(A, R, sd=None, chunk_rows=CHUNK, cfg=BC.CFG, **width):
     from gpudrive_lab_amd.bc_policy import DeviceBCPolicy
     return DeviceBCPolicy.from_state_dict(sd if sd is not None else _state_dict(R), max_agents=A, num_stack=R,
-                                          chunk_rows=chunk_rows, **cfg)
+                                          chunk_rows=chunk_rows, **cfg, **width)
 
 
 class _Guarded:
@@ -77,10 +78,11 @@ def _live_rows_of(rows, count=None):
     return lr, made
 
 
-def _forward_case(A, R, cfg=BC.CFG):
+def _forward_case(A, R, cfg=BC.CFG, **width):
+    """width: network_dim=128 for the wide policy (tests/test_gpu_bc_wide_edges.py); nothing for the 64-wide one."""
     obs, pm, rm, expert, u, z, _ = BC.inputs(B_F, A, R)
     obs, pm, rm, expert, u, z = (torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (obs, pm, rm, expert, u, z))
-    pol = _policy(A, R, sd=BC.state_dict(R, cfg), cfg=cfg)
+    pol = _policy(A, R, sd=BC.state_dict(R, cfg, **width), cfg=cfg, **width)
     full = {det: pol.forward(obs, pm, rm, OUTPUTS, deterministic=det, u=u, z=z, expert_actions=expert) for det in (True, False)}
     assert not torch.equal(full[True]["actions"], full[False]["actions"]), "the draw changed nothing"
     outs = {}
@@ -136,8 +138,11 @@ def test_forward_on_a_row_list_equals_the_full_forward(A, R):
 def test_forward_on_a_row_list_at_the_edge_configurations(name):
     """bc_cases.EDGE_CASES' largest model and the first mixture whose head outputs take a second trip: the rows of a list have
     the full forward's bits in every output, and nothing else is written."""
-    _, A, R, cfg = BC.EDGE[name]
-    pol, (obs, pm, rm, expert, u, z), full, outs = _forward_case(A, R, cfg)
+    _row_lists_at_an_edge_configuration(name, *BC.EDGE[name][1:])
+
+
+def _row_lists_at_an_edge_configuration(name, A, R, cfg, **width):
+    pol, (obs, pm, rm, expert, u, z), full, outs = _forward_case(A, R, cfg, **width)
     out = {k: g.view for k, g in outs.items()}
     assert full[True]["means"].shape == (B_F, 1, cfg["n_components"], 3)
     lists = _lists()

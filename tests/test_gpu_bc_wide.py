@@ -10,6 +10,8 @@ the reference side's own error, not the kernel's; the kernel's error must be <= 
     wide_min (3, 64, 1)     1.17     1.21   1.92             0 / 0    2.28   3.11
     wide_sweep (3, 64, 5)   1.30     1.55   0.98             4.29     0.49   1.59
     wide_a128 (2, 128, 2)   1.18     1.98   2.58             0.54     0.51   1.02
+The edge configurations of bc_wide_cases.EDGE_CASES run through this file's `_forward_checks` from tests/test_gpu_bc_wide_edges.py,
+whose docstring has their ratios (the largest 4.55, wide_top's weights).
 (`wide_min` has one component: its weight is exactly 1 on both sides; its nll is of magnitude 1e9, a covariance clamped at
 exp(-20) under a squared error, and E is 820 there.)  The largest, 4.29, is three rows' weights at E = 4.3e-7, a few float32
 ulps of a weight near 1, as the one-sample case is at 64.
@@ -46,6 +48,12 @@ def _inputs(c):
 
 @pytest.mark.parametrize("name", WC.GOLDEN_CASES)
 def test_forward_against_the_float64_restatement(name):
+    _forward_checks(name)
+
+
+def _forward_checks(name):
+    """Everything the wide forward is held to at one case of bc_wide_cases (tests/test_gpu_bc_wide_edges.py runs the edge
+    configurations through it).  Returns (case, the outputs on the host, the ratios)."""
     c = WC.case(name)
     B, A, C_ = c["B"], c["A"], c["cfg"]["n_components"]
     bc = _policy(c)
@@ -100,6 +108,7 @@ def test_forward_against_the_float64_restatement(name):
     # uint8 masks are bool masks
     _same_bits(got, _host(bc.forward(obs, pm.to(torch.uint8), rm.to(torch.uint8), ALL, deterministic=True, expert_actions=expert)),
                name + " uint8 masks")
+    return c, got, ratios
 
 
 def test_chunks_rows_and_reloaded_weights_give_the_same_bits():

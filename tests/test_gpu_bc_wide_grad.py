@@ -8,7 +8,8 @@ K = 32 E_p (this test prints the ratios per case and tensor with -s).  The worst
 MI355X: wide_min 2.76 (mean) and 2.92 (seeded), wide_a128 5.11, wide_sweep 2.77; wide_chunks with chunk_rows 2 and partials
 1 / 3 / 128: 11.33 / 4.22 / 2.84 (the 11.33 is ego_rg_attn's v_proj bias, 1,000 keys summed in one chain); wide_sweep's row c
 with the masked entities' features overwritten 4.55; the C call on carved buffers 4.22; one training step at wide_sweep 0.089
-of its bound.  DESIGN section 6 has the table."""
+of its bound.  DESIGN section 6 has the table.  The edge configurations of bc_wide_cases.EDGE_CASES (tests/test_gpu_bc_wide_edges.py):
+wide_top 3.08, wide_clip10 2.85, wide_c9 5.66, wide_c10 6.07, wide_deep_branch 5.75, wide_deep_fusion 2.68, wide_defaults 2.30."""
 import ctypes as C
 
 import numpy as np

@@ -6,7 +6,9 @@ on the sweep's layout (1.4 M parameters, 252 tensors; tests/test_bc_wide_update.
 there), the fused call to its four parts bit for bit, its gradient to `TrainableBCPolicyDim`'s bit for bit, and one whole step
 to the float64 pipeline of the differentiable restatement at that width (tests/bc_wide_update_reference.pipeline) within the
 bound tests/test_gpu_bc_grad.py derives for a step, with the wide backward's yardstick (K = 32, E_p of
-tests/bc_wide_grad_reference.py)."""
+tests/bc_wide_grad_reference.py).  tests/test_gpu_bc_wide_edges.py runs `_one_update_against_the_float64_pipeline` and
+`_update_against_its_parts` at wide_top (288 tensors: the optimiser's kernels past their first 256; at most 0.11 of the step's
+bound) and `DeviceBCDim` with every default on wide_defaults' 130 rows."""
 import ctypes as C
 
 import numpy as np
@@ -203,11 +205,14 @@ def test_update_is_its_four_parts_bit_for_bit_in_several_chunks():
 def test_one_update_against_the_float64_pipeline():
     """tests/test_gpu_bc_update.py's test and bound (tests/test_gpu_bc_grad.py derives it) on wide_min with the wide backward's
     yardstick, d = K E_p; the step's statistics within the wide forward tests' K E of float64."""
-    name = "wide_min"
+    _one_update_against_the_float64_pipeline("wide_min", **SMALL)
+
+
+def _one_update_against_the_float64_pipeline(name, **kw):
     c = WGR.case(name, "mean")
     B = len(c["obs"])
     want, losses = WUR.pipeline(c)
-    bc = _trainer(c, batch_size=B, **SMALL)
+    bc = _trainer(c, batch_size=B, **kw)
     bc.update(*_inputs(c))
     got = {k: v.cpu().numpy().astype(np.float64) for k, v in bc.state_dict().items()}
     lr, eps = UR.ADAMW["lr"], UR.ADAMW["eps"]

@@ -3,13 +3,15 @@
 tests/bc_grad_reference.py, call `gmm_loss(net, context, expert)[0].backward()`, and write tests/golden/bc_grad_<B>_<A>_<R>.npz:
 per parameter tensor of the module, in its own order, the gradient's sum, its L2 norm and its values at 32 seeded positions
 (not whole gradients), and the loss.  Results and names only: the weights and the inputs come from the seeds.
-With --dim 128 the same at network_dim 128 (head_dim 64) on bc_wide_cases' `wide_min` with the inputs of
-tests/bc_wide_grad_reference.py: tests/golden/bc_wide_grad_wide_min.npz.
+With --dim 128 the same at network_dim 128 (head_dim 64) on bc_wide_cases' `wide_min` and `wide_top` with the inputs of
+tests/bc_wide_grad_reference.py: tests/golden/bc_wide_grad_wide_min.npz and bc_wide_grad_wide_top.npz.
 
     tools/bc_grad_golden.py /path/to/reference/checkout [--dim 128]
     tools/bc_grad_golden.py --seeds        # no reference needed: search the input seeds that keep the margins, print the table
 
-Runs where the reference checkout is; never part of a test run."""
+Runs where the reference checkout is; never part of a test run.  The file is float64 autograd's output, whose summation order
+depends on the host's CPU and BLAS: bc_wide_grad_wide_min.npz regenerates to 1e-15 relative of the committed file, not to its
+bytes, on a host other than the one that wrote it (the tests compare at 1e-12); keep the committed file unless the case changes."""
 import os
 import sys
 import types
@@ -26,7 +28,7 @@ from tests import bc_wide_cases as WC  # noqa: E402
 from tests import bc_wide_grad_reference as WGR  # noqa: E402
 
 GOLDEN_CASE = (3, 64, 1)  # samples a, b and c; the smallest of bc_cases.SHAPES
-WIDE_GOLDEN_CASE = "wide_min"  # the same three samples at network_dim 128
+WIDE_GOLDEN_CASES = ("wide_min", "wide_top")  # the same three samples at network_dim 128: the smallest model and the largest
 POSITIONS = 32
 
 
@@ -59,14 +61,16 @@ def main():
     mods = load_reference(sys.argv[1])
     dim = int(sys.argv[sys.argv.index("--dim") + 1]) if "--dim" in sys.argv else 64
     if dim == 128:
-        sd, obs, pm, rm, expert, _, A, cfg = WGR.case_inputs(WIDE_GOLDEN_CASE)
-        B, R = len(obs), WC.CASES[WIDE_GOLDEN_CASE][2]
-        path = os.path.join(ROOT, "tests", "golden", "bc_wide_grad_%s.npz" % WIDE_GOLDEN_CASE)
+        for name in WIDE_GOLDEN_CASES:
+            sd, obs, pm, rm, expert, _, A, cfg = WGR.case_inputs(name)
+            write(mods, dim, sd, obs, pm, rm, expert, A, WC.lookup(name)[2], cfg, os.path.join(ROOT, "tests", "golden", "bc_wide_grad_%s.npz" % name))
     else:
-        cfg = BC.CFG
         B, A, R = GOLDEN_CASE
         sd, obs, pm, rm, expert, _ = GR.case_inputs(B, A, R)
-        path = os.path.join(ROOT, "tests", "golden", "bc_grad_%d_%d_%d.npz" % GOLDEN_CASE)
+        write(mods, dim, sd, obs, pm, rm, expert, A, R, BC.CFG, os.path.join(ROOT, "tests", "golden", "bc_grad_%d_%d_%d.npz" % GOLDEN_CASE))
+
+
+def write(mods, dim, sd, obs, pm, rm, expert, A, R, cfg, path):
     env = types.SimpleNamespace(ego_state=True, partner_obs=True, road_map_obs=True, max_num_agents_in_scene=A, roadgraph_top_k=200)
     exp = types.SimpleNamespace(network_dim=dim, network_num_layers=4, act_func="tanh", dropout=0.0, num_layer=cfg["num_layer"],
                                 num_head=4, head_dim=64, head_num_layers=cfg["head_num_layers"], n_components=cfg["n_components"],

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """developer tool: run the reference's EarlyFusionAttnBCNet on the CPU in float64 with the seeded weights and inputs of
-tests/bc_cases.py (network_dim 64) and of the cases of tests/bc_wide_cases.py that are not about chunks (network_dim 128,
-head_dim 64) and write tests/golden/bc_forward_<B>_<A>_<R>.npz and bc_wide_forward_<name>.npz: the module's parameter names and
+tests/bc_cases.py (network_dim 64) and of the cases of tests/bc_wide_cases.py that are not about chunks, with `wide_top` of its
+edge configurations (network_dim 128, head_dim 64) and write tests/golden/bc_forward_<B>_<A>_<R>.npz and bc_wide_forward_<name>.npz: the module's parameter names and
 shapes, and its context, means, covariances, weights, deterministic action, ego_attn_score and gmm_loss's per-row value.
 Outputs and names only: the weights and the inputs come from the seeds.
 
@@ -47,9 +47,9 @@ def load_reference(ref):
 def main():
     mods = load_reference(sys.argv[1])
     out_dir = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden")
-    cases = [("bc_forward_%d_%d_%d.npz" % (B, A, R), B, A, R, BC.CFG, 64) for B, A, R in BC.SHAPES]
-    cases += [("bc_wide_forward_%s.npz" % name, *WC.CASES[name], WC.DIM) for name in WC.GOLDEN_CASES]
-    for fname, B, A, R, cfg, dim in cases:
+    cases = [("bc_forward_%d_%d_%d.npz" % (B, A, R), B, A, R, BC.CFG, 64, 1) for B, A, R in BC.SHAPES]
+    cases += [("bc_wide_forward_%s.npz" % name, *WC.lookup(name), WC.DIM, WC.SEEDS[name]) for name in WC.GOLDEN_CASES + WC.EDGE_GOLDEN_CASES]
+    for fname, B, A, R, cfg, dim, seed in cases:
         env = types.SimpleNamespace(ego_state=True, partner_obs=True, road_map_obs=True, max_num_agents_in_scene=A,
                                     roadgraph_top_k=200)
         exp = types.SimpleNamespace(network_dim=dim, network_num_layers=4, act_func="tanh", dropout=0.0, num_layer=cfg["num_layer"],
@@ -59,7 +59,7 @@ def main():
         names = list(net.state_dict().keys())
         shapes = [tuple(v.shape) for v in net.state_dict().values()]
         net.load_state_dict({k: v.double() for k, v in BC.state_dict(R, cfg, network_dim=dim).items()})
-        obs, pm, rm, expert, _, _, _ = BC.inputs(B, A, R)
+        obs, pm, rm, expert, _, _, _ = BC.inputs(B, A, R, seed=seed)
         with torch.no_grad():
             t_obs, t_exp = torch.from_numpy(obs).double(), torch.from_numpy(expert).double()
             context, score, _ = net.get_context(t_obs, [torch.from_numpy(pm), torch.from_numpy(rm)])
